@@ -6,10 +6,14 @@ starts (tcmi_bamfile_to_device; "inputs already resident in HBM when the timed r
 "step" is one BAM of BASELINE configs[1] (1M synthetic 150-bp reads over a 29 903-bp reference) through HIP BGZF inflate + CRC +
 record chain + pack -> HIP tally + call -> host consensus walk -> FASTA text, with the stages of consecutive BAMs overlapped
 (trueconsense_amd.engine.FileRunner.run_resident).  The synthetic BAM files are written, read and copied to the device before the clock
-starts.  `--steps K --warmup W`: W untimed BAMs, then the K files as one queue, cycled `repeats` times so that the timed region lasts
->= `--min-seconds` (K x repeats timed BAMs; `--min-seconds 0`: exactly K).
+starts.  `--steps K --warmup W`: two untimed BAMs per GPU context (setup: a context allocates its arena on its first BAM), W untimed
+BAMs, then exactly K timed BAMs as one queue (`--min-seconds S > 0`: the K files cycled `repeats` times so that the timed region
+lasts >= S, K x repeats timed BAMs).
 
-Secondary blocks of the same JSON line:
+A plain run does only what the headline needs: inputs, warm-up, the timed steps, `--dump-outputs DIR` (the FASTA text of the last
+timed step as DIR/fasta_last_step.npy, its ASCII codes in float32), the JSON line.  Everything below runs only with `--full`.
+
+Secondary blocks of the same JSON line (`--full`):
   file_to_fasta    the PCIe-inclusive rate, measured the same way in the same run: the same files from the page cache (read into pinned
                    memory, H2D of the compressed bytes, then the headline's stages) — round 2's headline
   e2e_single_bam   one BAM file at a time, nothing overlapped: per-stage latency (configs[1] as written)
@@ -22,7 +26,7 @@ Secondary blocks of the same JSON line:
                    1 thread and N threads, plus the host walk
   fasta_bit_exact, fasta_all_timed       file 0 / every consensus of the timed path compared with the oracle chain (outside the clock)
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--files F] [--indels] [--split-bam [--from-file]]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--reads R] [--files F] [--indels] [--split-bam [--from-file]]
 
 N > 1: one rank per GPU — launched by the driver with torch.distributed.run, or, when no launcher's WORLD_SIZE is in the environment,
 by this script itself (spawn_ranks: N fresh child processes before anything touches a GPU); every rank processes its own BAM files
@@ -450,8 +454,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32, help="timed BAM files (each one BAM file -> FASTA)")
     ap.add_argument("--warmup", type=int, default=4)
-    ap.add_argument("--min-seconds", type=float, default=1.0,
-                    help="the K files are cycled `repeats` times in one queue so that the timed region lasts at least this long (0: exactly K)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="> 0: the K files are cycled `repeats` times in one queue so that the timed region lasts at least this long (0: exactly K)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs, per-kernel times, rooflines, the CPU baseline and the checks against the oracle chain")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the FASTA text of the last timed step to DIR/fasta_last_step.npy (ASCII codes, float32)")
     ap.add_argument("--reads", type=int, default=1_000_000)
     ap.add_argument("--files", type=int, default=8, help="distinct synthetic BAM files per rank, cycled through")
     ap.add_argument("--level", type=int, default=6, help="zlib level the synthetic BAMs are written with (samtools' default is 6)")
@@ -482,6 +490,8 @@ def main():
                     help="BASELINE configs[4]: ONE BAM of gpus x --reads reads, each rank tallies its contiguous read range, "
                          "one reduce (RCCL) of the count matrix per step, base calling on rank 0")
     a = ap.parse_args()
+    if a.dump_outputs and (a.split_bam or a.only_resident):
+        ap.error("--dump-outputs writes the headline path's outputs: not with --split-bam or --only-resident")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:               # no launcher around us: be it (nothing has touched a GPU yet)
         sys.exit(spawn_ranks(a.gpus))
@@ -572,37 +582,46 @@ def run_bench(a, rank, local_rank, world, rehearse, dist, torch, np, _ffi, sy, C
         k, v = kv.split("=")
         for c in runner.contexts:
             c.set_option(k, int(v))
+    primed = []
+
     def timed_leg(run):
-        """run(indices, names) -> FASTA texts.  Warm-up, one untimed pass over the K files to size the job (the K timed steps take
-        ~ 25 ms on one GPU, too short for a stable figure), then ONE queue of K x `repeats` files (>= --min-seconds of work, one
-        pipeline fill and drain) as the timed region, bracketed by sync + barrier; the slowest rank's time counts."""
+        """run(indices, names) -> FASTA texts.  Warm-up, then ONE queue of K files (one pipeline fill and drain) as the timed region,
+        bracketed by sync + barrier; the slowest rank's time counts.  --min-seconds > 0: one untimed pass over the K files sizes the
+        job, and the queue holds K x `repeats` files (>= --min-seconds of work).  --full: HIP events around every kernel."""
+        if not primed:
+            # setup, before the warm-up: a context allocates its workspace and device arena on its first BAM, and the contexts take
+            # BAMs from one queue — two per context reach them all, so that no allocation lands in the timed region
+            run(list(range(2 * runner.n_ctx)), None)
+            primed.append(True)
         if a.warmup > 0:
             run(list(range(a.warmup)), None)
-        for c in runner.contexts:
-            c.profile(True)                                      # HIP events around every kernel of the cold path
-        fence()
-        t0 = time.perf_counter()
-        run(list(range(a.steps)), None)
-        fence()
-        repeats = max(1, int(np.ceil(a.min_seconds / max(1e-6, time.perf_counter() - t0)))) if a.min_seconds > 0 else 1
-        if dist is not None:
-            t = torch.tensor([repeats], dtype=torch.int64, device="cpu" if rehearse else "cuda")
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            repeats = int(t.item())
+        repeats = 1
+        if a.min_seconds > 0:
+            fence()
+            t0 = time.perf_counter()
+            run(list(range(a.steps)), None)
+            fence()
+            repeats = max(1, int(np.ceil(a.min_seconds / max(1e-6, time.perf_counter() - t0))))
+            if dist is not None:
+                t = torch.tensor([repeats], dtype=torch.int64, device="cpu" if rehearse else "cuda")
+                dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                repeats = int(t.item())
         n_timed = a.steps * repeats
         runner.seconds = {k: 0.0 for k in runner.seconds}
         runner.decoded_on = {k: 0 for k in runner.decoded_on}
-        for c in runner.contexts:
-            c.profile(False)
-            c.profile(True)
+        if a.full:
+            for c in runner.contexts:
+                c.profile(True)                                  # HIP events around every kernel of the cold path
         fence()
         t0 = time.perf_counter()
         fastas = run(list(range(n_timed)), ["S%d" % (i % len(paths)) for i in range(n_timed)])
         fence()
         dt = time.perf_counter() - t0
-        cold = kernel_times(runner.contexts, _ffi, n_timed)
-        for c in runner.contexts:
-            c.profile(False)
+        cold = None
+        if a.full:
+            cold = kernel_times(runner.contexts, _ffi, n_timed)
+            for c in runner.contexts:
+                c.profile(False)
         dt_ranks = [dt]
         if dist is not None:
             dt_ranks = [None] * world
@@ -614,7 +633,10 @@ def run_bench(a, rank, local_rank, world, rehearse, dist, torch, np, _ffi, sy, C
                 "busy": {k: v / n_timed for k, v in runner.seconds.items()}, "decoded_on": dict(runner.decoded_on)}
 
     # ---- the PCIe-inclusive leg: BAM FILES (page cache) -> FASTA text: read into pinned memory, H2D of the compressed bytes, GPU, walk ----
-    leg_file = timed_leg(lambda idx, names: runner.run([file_of(i) for i in idx], names=names, ref_len=L))
+    # (--full; with --host-decode it is the headline)
+    leg_file = None
+    if a.full or a.host_decode:
+        leg_file = timed_leg(lambda idx, names: runner.run([file_of(i) for i in idx], names=names, ref_len=L))
     # ---- headline: the same files' compressed bytes RESIDENT IN HBM when the clock starts (read and copied before it) -> FASTA text ----
     leg = leg_file
     dbams = []
@@ -624,15 +646,19 @@ def run_bench(a, rank, local_rank, world, rehearse, dist, torch, np, _ffi, sy, C
         leg = timed_leg(lambda idx, names: runner.run_resident([dbams[i % len(dbams)] for i in idx], names=names, ref_len=L))
     fastas, dt, dt_ranks, repeats, n_timed, cold = leg["fastas"], leg["dt"], leg["dt_ranks"], leg["repeats"], leg["n_timed"], leg["cold"]
     if rank != 0:
-        if not a.no_resident:
+        if a.full and not a.no_resident:
             resident_leg(a, ctx, Pipeline, local_rank, np, _ffi, sy, ref, orfs, L, rank, fence)
         return None
+    if a.dump_outputs:
+        # what the caller of the timed path receives for its last step: that BAM's FASTA text (header line + consensus)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "fasta_last_step.npy"), np.frombuffer(fastas[-1].encode("ascii"), np.uint8).astype(np.float32))
 
     out = {
         "metric": "reference positions/sec (BAM file -> consensus FASTA, 1M reads x 29 903 bp per BAM)",
         "value_definition": ("compressed BAM file bytes resident in HBM when the clock starts -> FASTA text on the host (BGZF inflate, record chain, "
                              "pack, tally, call on the GPU; consensus walk on the host); the PCIe-inclusive rate from files in the page "
-                             "cache is file_to_fasta" if dbams else "BAM files in the page cache -> FASTA text, host decode (--host-decode)"),
+                             "cache is file_to_fasta (--full)" if dbams else "BAM files in the page cache -> FASTA text, host decode (--host-decode)"),
         "value": L * n_timed * world / dt, "unit": "positions/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": 1e3 * dt / n_timed, "ms_per_step_per_rank": {"min": 1e3 * min(dt_ranks) / n_timed, "max": 1e3 * max(dt_ranks) / n_timed},
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -652,8 +678,11 @@ def run_bench(a, rank, local_rank, world, rehearse, dist, torch, np, _ffi, sy, C
                    "bam_file_bytes": os.path.getsize(paths[0]), "bam_inflated_bytes": inflated_size(paths[0]),
                    "input_generation_seconds_outside_clock": t_gen},
         "e2e_stage_busy_seconds_per_bam": leg["busy"],
-        "cold_kernels_pipelined": cold,
     }
+    if not a.full:
+        out["value_resident"] = out["value"]
+        return out
+    out["cold_kernels_pipelined"] = cold
     if dbams:
         fb = os.path.getsize(paths[0])
         out["file_to_fasta"] = {

@@ -249,7 +249,7 @@ def _bench_ranks(extra, env_extra=None, nproc=2, launcher=True):
 
 @pytest.mark.gpu
 def test_bench_many_bam_shard_two_ranks_rehearsal():
-    d = _bench_ranks(["--steps", "3", "--warmup", "1", "--reads", "40000", "--files", "2", "--no-cpu-baseline", "--no-resident"])
+    d = _bench_ranks(["--full", "--steps", "3", "--warmup", "1", "--reads", "40000", "--files", "2", "--no-cpu-baseline", "--no-resident"])
     assert d["n_gpus"] == 2 and d["steps"] == 3 and d["scaling"] == "weak" and d["fasta_bit_exact"] is True
     assert d["value"] > 0 and d["unit"] == "positions/s" and "roofline" in d
 
@@ -258,7 +258,7 @@ def test_bench_many_bam_shard_two_ranks_rehearsal():
 def test_bench_gpus_2_without_a_launcher_starts_its_own_ranks():
     """`python bench.py --gpus 2` (plain python, as the driver's N = 1 command is shaped): the flag alone must shard — two child ranks,
     started before the parent touches a GPU, one JSON line with n_gpus 2."""
-    d = _bench_ranks(["--steps", "4", "--warmup", "1", "--reads", "40000", "--files", "2", "--no-cpu-baseline", "--no-resident", "--no-hard-bam",
+    d = _bench_ranks(["--full", "--steps", "4", "--warmup", "1", "--reads", "40000", "--files", "2", "--no-cpu-baseline", "--no-resident", "--no-hard-bam",
                       "--no-cli-batch", "--no-configs2", "--no-configs0", "--min-seconds", "0"], launcher=False)
     assert d["n_gpus"] == 2 and d["steps"] == 4 and d["scaling"] == "weak" and d["fasta_bit_exact"] is True
     assert d["ms_per_step_per_rank"]["max"] >= d["ms_per_step_per_rank"]["min"] > 0
@@ -305,7 +305,7 @@ def test_bench_many_bam_shard_four_ranks_rehearsal():
     """The driver's N = 8 launch shape at tiny sizes, to shake out collisions of temporary files, ports and thread counts between
     the ranks of one host — with FOUR ranks: the GPU boxes allow at most six processes on a card at once, and the test runner
     itself holds one (six ranks were killed by the box's process guard)."""
-    d = _bench_ranks(["--steps", "2", "--warmup", "1", "--reads", "20000", "--files", "2", "--no-cpu-baseline", "--no-resident", "--no-hard-bam",
+    d = _bench_ranks(["--full", "--steps", "2", "--warmup", "1", "--reads", "20000", "--files", "2", "--no-cpu-baseline", "--no-resident", "--no-hard-bam",
                       "--no-cli-batch", "--no-configs2", "--min-seconds", "0"], nproc=4)
     assert d["n_gpus"] == 4 and d["steps"] == 2 and d["scaling"] == "weak" and d["fasta_bit_exact"] is True
     assert d["fasta_all_timed"]["all_equal_the_oracle_chain"] is True

@@ -16,7 +16,7 @@ mode=$1; shift
 lib_of() { [ "$1" = default ] && echo $PWD/trueconsense_amd/lib/libtcmi.so || echo $PWD/trueconsense_amd/lib/var/lib$1.so; }
 headline() {  # tag, env assignments..., -- bench args
   tag=$1; shift; envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-cli-batch --no-configs2 --no-configs0 --no-hard-bam --no-resident $BENCH_ARGS "$@" \
+  env "${envs[@]}" timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-cli-batch --no-configs2 --no-configs0 --no-hard-bam --no-resident $BENCH_ARGS "$@" \
       > gpurun_out/ab/$tag.json 2> gpurun_out/ab/$tag.err || { echo "$tag: fail"; tail -3 gpurun_out/ab/$tag.err; exit 1; }
   echo "$tag: $(python3 tools/bench_summary.py gpurun_out/ab/$tag.json 2>/dev/null | sed -n '1,3p' | tr '\n' ' ')"
 }

@@ -2,7 +2,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 d=gpurun_out/pmc3; mkdir -p $d
 for set in "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY" "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
 n=$(echo $set | cut -c1-16 | tr ' ' '_')
-rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d/$n -- python3 bench.py --no-resident --no-cpu-baseline --steps 8 --warmup 2 --min-seconds 0 --gpu-streams 1 > $d/$n.json 2> $d/$n.err || { tail -5 $d/$n.err; exit 1; }
+rocprofv3 --kernel-trace --pmc $set --output-format csv -d $d/$n -- python3 bench.py --full --no-resident --no-cpu-baseline --steps 8 --warmup 2 --min-seconds 0 --gpu-streams 1 > $d/$n.json 2> $d/$n.err || { tail -5 $d/$n.err; exit 1; }
 done
 python3 - $d/* <<'PY'
 import csv, sys, glob, collections

@@ -6,7 +6,7 @@
 out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p $out
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --no-resident --no-cpu-baseline --no-cli-batch --no-hard-bam --no-configs2 --no-configs0 --gpu-streams 3 --steps 16 --warmup 2 "$@" > $out/bench_under_rocprof.json 2> $out/rocprof.err || { tail -5 $out/rocprof.err; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 bench.py --full --no-resident --no-cpu-baseline --no-cli-batch --no-hard-bam --no-configs2 --no-configs0 --gpu-streams 3 --steps 16 --warmup 2 "$@" > $out/bench_under_rocprof.json 2> $out/rocprof.err || { tail -5 $out/rocprof.err; exit 1; }
 f=$(ls $out/stats/*/*kernel_stats.csv | head -1)
 cp $f $out/kernel_stats.csv
 cat $out/kernel_stats.csv
