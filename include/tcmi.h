@@ -145,6 +145,23 @@ void *tcmi_ctx_stream(tcmi_ctx *ctx);              /* the hipStream_t all launch
  *   "profile_every"  with profiling enabled, every n-th tcmi_step_begin has its kernels bracketed by events,
  *                    the others go out unmeasured (default 1) */
 int  tcmi_ctx_set_option(tcmi_ctx *ctx, const char *key, int value);
+/* ---- several contigs on one coordinate axis (a BAM aligned to a multi-record reference) ----------------------------------
+ * tcmi_ctx_set_layout: from now on every upload of the context (tcmi_readset_upload, tcmi_readset_from_bamfile[_blocks],
+ * tcmi_bamfile_step) piles reference t's reads up at pos + shift[t] instead of refusing them: reference t owns the positions
+ * [shift[t], shift[t] + slot_len[t]) of the count matrix, and the tally, the call and the step see one axis.  shift[t] < 0: the
+ * reads of reference t are dropped, like unmapped reads.  The slots of the kept references must ascend in reference order and not
+ * overlap (a file sorted by (tid, pos) then stays sorted on the axis) and end below 2^29.  A kept read that ends past its slot is
+ * refused (TCMI_E_UNSUPPORTED), never tallied into the next slot.  n_ref = 0: no layout (reference 0 only, the default).
+ * Under a layout, tcmi_bamfile_step takes its two-call path, tcmi_readset_modal_tokens / tcmi_readset_ins_entries return
+ * TCMI_E_UNSUPPORTED (use tcmi_modal_tokens_layout), and tcmi_readset_upload_batch / tcmi_split_step return TCMI_E_UNSUPPORTED.
+ * The context keeps one device table, rewritten by every call with n_ref > 0: a read set with reads longer than 512 positions
+ * must be stepped before another layout is set (else TCMI_E_UNSUPPORTED), as before the context's next upload.          */
+int  tcmi_ctx_set_layout(tcmi_ctx *ctx, int32_t n_ref, const int64_t *shift, const int64_t *slot_len);
+/* per reference, the kept reads' max end (exclusive, in the reference's own coordinates; 0: no read) of a read set uploaded
+ * under a layout of n_ref references (tcmi_reads_extent of that reference's reads alone) */
+int  tcmi_readset_ref_extents(const tcmi_readset *rs, int32_t n_ref, int64_t *max_end);
+/* mapped reads of a read set uploaded under a layout whose reference has no slot (shift < 0): dropped, not tallied */
+int  tcmi_readset_dropped(const tcmi_readset *rs, int64_t *n_dropped);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
  * "decode_batched" — files (or ranges) whose blocks the device decoder took in batches ("decode_token_mb");
@@ -282,6 +299,12 @@ int tcmi_modal_tokens(const tcmi_reads *reads, int32_t n_pos, const int64_t *pos
                       int32_t min_base_quality, uint32_t flag_filter, int ignore_orphans,
                       int64_t max_depth, int ignore_overlaps, char *tokens, int64_t tokens_cap, int64_t *token_off,
                       int64_t *n_tokens, int32_t *status_flags);
+/* The same under a contig layout (tcmi_ctx_set_layout's arguments): positions are on the layout's axis, reference t's reads sit
+ * at pos + shift[t]; mates on different references never count as overlapping. */
+int tcmi_modal_tokens_layout(const tcmi_reads *reads, int32_t n_ref, const int64_t *shift, const int64_t *slot_len, int32_t n_pos,
+                             const int64_t *positions, int32_t min_base_quality, uint32_t flag_filter, int ignore_orphans,
+                             int64_t max_depth, int ignore_overlaps, char *tokens, int64_t tokens_cap, int64_t *token_off,
+                             int64_t *n_tokens, int32_t *status_flags);
 
 /* ---- many BAMs: native batch runner (BASELINE.json configs[3]: independent BAMs, no collective).
  * The calling thread queues step i+1 behind step i on one stream over `n_slots` workspaces while
@@ -321,6 +344,8 @@ int  tcmi_bam_header(const tcmi_bam *bam, int32_t *n_ref, const char **ref0_name
 int  tcmi_bam_info(const tcmi_bam *bam, int64_t *n_reads, int32_t *sorted, int64_t *file_bytes,
                    int64_t *inflated_bytes, int64_t *n_blocks, int64_t *n_cigar, int64_t *n_qual);
 const char *tcmi_bam_text(const tcmi_bam *bam);    /* SAM header text, owned by bam                */
+/* name and length of reference i (0 <= i < n_ref) of the header; the name is owned by bam */
+int  tcmi_bam_ref(const tcmi_bam *bam, int32_t i, const char **name, int64_t *len);
 
 /* ---- BAM decoded ON THE DEVICE (the default file path; the host reader above stays for files it does not take) ----
  * tcmi_bamfile_read: HOST — file bytes into pinned memory, BGZF block table, BAM header (only the leading blocks the
@@ -335,6 +360,7 @@ int  tcmi_bamfile_free(tcmi_bamfile *f);
 int  tcmi_bamfile_info(const tcmi_bamfile *f, int64_t *file_bytes, int64_t *inflated_bytes, int64_t *n_blocks, int32_t *n_ref,
                        const char **ref0_name, int64_t *ref0_len);
 const char *tcmi_bamfile_text(const tcmi_bamfile *f);
+int  tcmi_bamfile_ref(const tcmi_bamfile *f, int32_t i, const char **name, int64_t *len);   /* as tcmi_bam_ref */
 const char *tcmi_bamfile_path(const tcmi_bamfile *f);
 /* The file's compressed bytes into HBM, to stay until tcmi_bamfile_free: tcmi_readset_from_bamfile[_blocks] on that device then
  * start from device memory, no PCIe copy per call (a file a peer GPU, a NIC or a storage engine delivered into HBM looks like

@@ -91,6 +91,9 @@ def GetArgs(givenargs):
                                        help="GPUs of this node to use: with --batch the manifest's samples are dealt to N processes,\n"
                                             "one per GPU (independent files, no exchange); with -i ONE BAM file is shared — every GPU\n"
                                             "takes a range of its BGZF blocks, one reduce of the count matrix")))
+    additive.append((("--per-contig",), dict(action="store_true",
+                                             help="one consensus per record of -ref (a multi-record reference, e.g. a segmented virus):\n"
+                                                  "records named {name}_{record}, all in -o; -vcf / -ogff / -doc cover every record")))
     # (is this the --batch form?  asked of a small parser of its own: "--batch=FILE" and argparse's abbreviations count too)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--batch", default=None)
@@ -243,6 +246,21 @@ def run_batch(a):
         runner.close()
 
 
+def run_per_contig(a):
+    """--per-contig: trueconsense_amd.contigs; a refused input or a read past its contig's slot exits 1 with nothing written."""
+    from . import _ffi
+    from .contigs import ContigError, run
+    t0 = time.perf_counter()
+    try:
+        info = run(a)
+    except (ContigError, _ffi.TcmiError) as e:
+        print(f"{e}. Exiting...", file=sys.stderr)
+        sys.exit(1)
+    if a.stats:
+        with open(a.stats, "w") as fh:
+            json.dump(dict({"seconds": {"per_contig": time.perf_counter() - t0}}, **info), fh)
+
+
 def main(args=None):
     """TrueConsense.py:212-264."""
     if not args:
@@ -252,6 +270,18 @@ def main(args=None):
               "Use 'TrueConsense -h' to see the help document")
         sys.exit(1)
     a = GetArgs(args)
+    if a.per_contig:                                # (its refusals come before any GPU work, and before --gpus deals anything out)
+        for flag, bad in (("--batch", a.batch), ("--gpus N>1", a.gpus and a.gpus > 1), ("--index-override", a.index_override)):
+            if bad:
+                print(f"--per-contig does not go with {flag}. Exiting...")
+                sys.exit(1)
+        from .contigs import ContigError, bam_header_refs, layout_for
+        from .io import fasta
+        try:
+            layout_for(fasta.read_records(a.reference), *bam_header_refs(a.input))
+        except ContigError as e:
+            print(f"{e}. Exiting...")
+            sys.exit(1)
     if a.gpus and a.gpus > 1:
         rc = run_gpus(a)
         if rc:
@@ -261,6 +291,8 @@ def main(args=None):
         os.environ["TCMI_DEVICE"] = str(a.device)
     if a.batch:
         return run_batch(a)
+    if a.per_contig:
+        return run_per_contig(a)
     t = {"start": time.perf_counter()}
 
     from .engine import LazyBam

@@ -52,6 +52,9 @@ _SIGS = {
     "tcmi_ctx_sync": (_int, [_vp]),
     "tcmi_ctx_stream": (_vp, [_vp]),
     "tcmi_ctx_set_option": (_int, [_vp, C.c_char_p, _int]),
+    "tcmi_ctx_set_layout": (_int, [_vp, _i32, _vp, _vp]),
+    "tcmi_readset_ref_extents": (_int, [_vp, _i32, _vp]),
+    "tcmi_readset_dropped": (_int, [_vp, _P(_i64)]),
     "tcmi_ctx_stat": (_int, [_vp, C.c_char_p, _P(_i64)]),
     "tcmi_profile_enable": (_int, [_vp, _int]),
     "tcmi_profile_reset": (_int, [_vp]),
@@ -75,6 +78,7 @@ _SIGS = {
     "tcmi_consensus_walk": (_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp, C.c_char_p, _vp,
                                    _int, _vp, _i64, _P(_i64), _vp, _vp, _P(_i64)]),
     "tcmi_modal_tokens": (_int, [_P(Reads), _i32, _vp, _i32, _u32, _int, _i64, _int, _vp, _i64, _vp, _vp, _P(_i32)]),
+    "tcmi_modal_tokens_layout": (_int, [_P(Reads), _i32, _vp, _vp, _i32, _vp, _i32, _u32, _int, _i64, _int, _vp, _i64, _vp, _vp, _P(_i32)]),
     "tcmi_pipeline_create": (_int, [_int, _int, _int, _P(_vp)]),
     "tcmi_pipeline_destroy": (_int, [_vp]),
     "tcmi_pipeline_set_orfs": (_int, [_vp, _i32, _vp, _vp, _vp]),
@@ -85,11 +89,13 @@ _SIGS = {
     "tcmi_bam_free": (_int, [_vp]),
     "tcmi_bam_reads": (_int, [_vp, _P(Reads)]),
     "tcmi_bam_header": (_int, [_vp, _P(_i32), _P(C.c_char_p), _P(_i64)]),
+    "tcmi_bam_ref": (_int, [_vp, _i32, _P(C.c_char_p), _P(_i64)]),
     "tcmi_bam_info": (_int, [_vp, _P(_i64), _P(_i32), _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_i64)]),
     "tcmi_bam_text": (C.c_char_p, [_vp]),
     "tcmi_bamfile_read": (_int, [C.c_char_p, _P(_vp)]),
     "tcmi_bamfile_free": (_int, [_vp]),
     "tcmi_bamfile_info": (_int, [_vp, _P(_i64), _P(_i64), _P(_i64), _P(_i32), _P(C.c_char_p), _P(_i64)]),
+    "tcmi_bamfile_ref": (_int, [_vp, _i32, _P(C.c_char_p), _P(_i64)]),
     "tcmi_bamfile_text": (C.c_char_p, [_vp]),
     "tcmi_bamfile_path": (C.c_char_p, [_vp]),
     "tcmi_bamfile_to_device": (_int, [_vp, _vp]),

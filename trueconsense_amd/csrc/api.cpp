@@ -174,6 +174,8 @@ int tcmi_ctx_destroy(tcmi_ctx *c)
     c->upload_scratch = nullptr;
     tcmi_dev_arena_free(c->dev_arena);
     c->dev_arena = nullptr;
+    if (c->d_lay) (void)hipFree(c->d_lay);
+    c->d_lay = nullptr;
     for (auto &b : c->blob_pool) (void)hipFree(b.p);
     c->blob_pool.clear();
     if (c->tok_dev) (void)hipFree(c->tok_dev);
@@ -229,6 +231,56 @@ int tcmi_ctx_set_option(tcmi_ctx *c, const char *key, int value)
     else if (!std::strcmp(key, "split_sub")) c->split_sub = value < 0 ? 0 : value > 8 ? 8 : value;
 
     else return tcmi_fail(c, TCMI_E_ARG, "unknown option %s", key);
+    return TCMI_OK;
+}
+
+} // extern "C"
+
+int tcmi_layout_build(int32_t n_ref, const int64_t *shift, const int64_t *slot_len, tcmi_layout *out, char *msg, size_t msg_cap)
+{
+    out->shift.clear(); out->end.clear();
+    if (n_ref < 0 || (n_ref > 0 && (!shift || !slot_len))) { std::snprintf(msg, msg_cap, "bad layout arguments"); return TCMI_E_ARG; }
+    int64_t prev_end = 0;
+    for (int32_t t = 0; t < n_ref; ++t) {
+        if (shift[t] < 0) continue;                                 // (a reference whose reads are dropped)
+        if (slot_len[t] < 1 || shift[t] < prev_end || shift[t] + slot_len[t] > (int64_t)TCMI_F_EVPOS) {
+            std::snprintf(msg, msg_cap, "layout: slot %d [%lld, +%lld) overlaps the slot in front, is empty or ends beyond 2^29", t,
+                          (long long)shift[t], (long long)slot_len[t]);
+            return TCMI_E_ARG;
+        }
+        prev_end = shift[t] + slot_len[t];
+    }
+    out->shift.assign(shift, shift + n_ref);
+    out->end.resize((size_t)n_ref);
+    for (int32_t t = 0; t < n_ref; ++t) out->end[(size_t)t] = shift[t] < 0 ? -1 : shift[t] + slot_len[t];
+    return TCMI_OK;
+}
+
+extern "C" {
+
+int tcmi_ctx_set_layout(tcmi_ctx *c, int32_t n_ref, const int64_t *shift, const int64_t *slot_len)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    char msg[200];
+    tcmi_layout L;
+    const int rc = tcmi_layout_build(n_ref, shift, slot_len, &L, msg, sizeof msg);
+    if (rc) return tcmi_fail(c, rc, "%s", msg);
+    if (n_ref > 0) {
+        std::vector<int32_t> h((size_t)n_ref * 2);
+        for (int32_t t = 0; t < n_ref; ++t) { h[(size_t)t] = (int32_t)L.shift_of(t); h[(size_t)(n_ref + t)] = (int32_t)L.end[(size_t)t]; }
+        TCMI_HIP(c, hipSetDevice(c->device));
+        TCMI_HIP(c, hipStreamSynchronize(c->stream));      // (nothing queued may still read the table that is rewritten)
+        const size_t need = (size_t)n_ref * 3 * 4;
+        if (need > c->d_lay_cap) {
+            if (c->d_lay) (void)hipFree(c->d_lay);
+            c->d_lay = nullptr; c->d_lay_cap = 0;
+            TCMI_HIP(c, hipMalloc((void **)&c->d_lay, need));
+            c->d_lay_cap = need;
+        }
+        TCMI_HIP(c, hipMemcpy(c->d_lay, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+        ++c->lay_gen;                                        // (clearing the layout leaves the table as it is)
+    }
+    c->layout = std::move(L);
     return TCMI_OK;
 }
 
@@ -759,6 +811,7 @@ int tcmi_split_step(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first_block, i
                     const uint8_t **plain, const uint8_t **alt, const uint8_t **flags)
 {
     if (!ctx || !f || !d_counts || !reduce || !rs_out) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
+    if (ctx->layout.n()) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not take a contig layout (tcmi_ctx_set_layout)");
     if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld");
     if (world < 1 || rank < 0 || rank >= world) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 <= rank < world");
     *rs_out = nullptr;

@@ -348,6 +348,14 @@ int tcmi_bamfile_read_threads(const char *path, int read_threads, tcmi_bamfile *
     return TCMI_OK;
 }
 
+int tcmi_bamfile_ref(const tcmi_bamfile *f, int32_t i, const char **name, int64_t *len)
+{
+    if (!f || i < 0 || (size_t)i >= f->ref_name.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "no reference %d in the header", i);
+    if (name) *name = f->ref_name[(size_t)i].c_str();
+    if (len) *len = f->ref_len[(size_t)i];
+    return TCMI_OK;
+}
+
 int tcmi_bamfile_info(const tcmi_bamfile *f, int64_t *file_bytes, int64_t *inflated_bytes, int64_t *n_blocks, int32_t *n_ref,
                       const char **ref0_name, int64_t *ref0_len)
 {
@@ -738,7 +746,8 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
     TCMI_HIP(ctx, hipSetDevice(ctx->device));
     static const bool timing = std::getenv("TCMI_UPLOAD_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    for (int attempt = 0; ctx->one_sync && try_fused && attempt < 2; ++attempt) {
+    // (the one-sync path knows no contig layout: under one the several-kernel path packs)
+    for (int attempt = 0; ctx->one_sync && try_fused && ctx->layout.n() == 0 && attempt < 2; ++attempt) {
         SplitScope back(ctx);
         Decoded D;
         tcmi_fused_job J;
@@ -801,7 +810,7 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
         return TCMI_OK;
     }
     tcmi_readset_free(ctx, rs);
-    if (rc == TCMI_E_UNSUPPORTED)
+    if (rc == TCMI_E_UNSUPPORTED && !(why & (1u << 13)))        // (PKF_SLOT_OVF: the packer's own words name the read and the reference)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the device packer declined (flags 0x%x: long reads, far positions, a second reference or malformed reads): host reader",
                          f->path.c_str(), why);
     return rc;
@@ -834,7 +843,8 @@ int tcmi_bamfile_step(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t ref_len, int
     if (!ctx || !f || !rs_out || !L_out) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     *rs_out = nullptr;
     TCMI_HIP(ctx, hipSetDevice(ctx->device));
-    for (int attempt = 0; ctx->one_sync && ctx->step_L == 0 && !ctx->call_pending && attempt < 2; ++attempt) {
+    // (the one-sync path knows no contig layout: under one it declines to the two-call path, which honours it)
+    for (int attempt = 0; ctx->one_sync && ctx->layout.n() == 0 && ctx->step_L == 0 && !ctx->call_pending && attempt < 2; ++attempt) {
         static const bool timing = std::getenv("TCMI_STEP_TIMING") != nullptr;       // diagnostic: where the host's time goes, per 256 calls
         static thread_local double t_acc[5] = {0, 0, 0, 0, 0};
         static thread_local int t_n = 0;

@@ -353,6 +353,14 @@ int tcmi_bam_reads(const tcmi_bam *bam, tcmi_reads *reads)
     return TCMI_OK;
 }
 
+int tcmi_bam_ref(const tcmi_bam *bam, int32_t i, const char **name, int64_t *len)
+{
+    if (!bam || i < 0 || (size_t)i >= bam->ref_name.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "no reference %d in the header", i);
+    if (name) *name = bam->ref_name[(size_t)i].c_str();
+    if (len) *len = bam->ref_len[(size_t)i];
+    return TCMI_OK;
+}
+
 int tcmi_bam_header(const tcmi_bam *bam, int32_t *n_ref, const char **ref0_name, int64_t *ref0_len)
 {
     if (!bam) return tcmi_fail(nullptr, TCMI_E_ARG, "bam is NULL");

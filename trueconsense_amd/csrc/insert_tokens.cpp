@@ -344,10 +344,11 @@ int tcmi_modal_from_dev_entries(int32_t n_pos, const tcmi_dev_entry *ents, const
     return rc;
 }
 
-extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64_t *positions /* 1-based, ascending */,
-                                 int32_t min_base_quality, uint32_t flag_filter, int ignore_orphans, int64_t max_depth,
-                                 int ignore_overlaps, char *tokens, int64_t tokens_cap, int64_t *token_off /* [n_pos+1] */,
-                                 int64_t *n_tokens /* [n_pos] */, int32_t *status_flags)
+// the sweep; `lay`: reference t's reads sit at pos + shift on the one axis the positions are given in (no layout: reference 0 only)
+static int modal_tokens_impl(const tcmi_reads *r, const tcmi_layout &lay, int32_t n_pos, const int64_t *positions /* 1-based, ascending */,
+                             int32_t min_base_quality, uint32_t flag_filter, int ignore_orphans, int64_t max_depth,
+                             int ignore_overlaps, char *tokens, int64_t tokens_cap, int64_t *token_off /* [n_pos+1] */,
+                             int64_t *n_tokens /* [n_pos] */, int32_t *status_flags)
 {
     if (!r || n_pos < 0 || (n_pos > 0 && (!positions || !tokens || !token_off || !n_tokens)))
         return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
@@ -369,7 +370,16 @@ extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64
             }
             n_placed = lo;
         }
-        const int32_t *pb = r->pos, *pe = r->pos + n_placed;
+        std::vector<int32_t> axis;                              // under a layout: positions on the axis (ascending for reads sorted by (tid, pos))
+        if (lay.n()) {
+            axis.resize((size_t)n_placed);
+            for (int64_t i = 0; i < n_placed; ++i) {
+                const int64_t sh = lay.shift_of(r->tid ? r->tid[i] : 0);
+                const int64_t g = sh >= 0 ? r->pos[i] + sh : (i ? axis[(size_t)i - 1] : 0);     // (a dropped reference's reads: where the axis is)
+                axis[(size_t)i] = (int32_t)std::max<int64_t>(g, i ? axis[(size_t)i - 1] : 0);
+            }
+        }
+        const int32_t *pb = lay.n() ? axis.data() : r->pos, *pe = pb + n_placed;
         for (int32_t k = 0; k < n_pos; ++k) {
             const int64_t col = positions[k] - 1;
             const int64_t a = std::lower_bound(pb, pe, (int32_t)std::max<int64_t>(col - r->sorted_max_span + 1, INT32_MIN / 2),
@@ -392,7 +402,9 @@ extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64
         const int64_t my_qoff = qoff;
         qoff += lq;
         const unsigned fl = r->flag[i];
-        if ((fl & 0x4) || (r->tid && r->tid[i] != 0) || r->pos[i] < 0) continue;   // Events.py:64: references[0] only
+        const int32_t my_tid = r->tid ? r->tid[i] : 0;
+        const int64_t shift = lay.shift_of(my_tid);
+        if ((fl & 0x4) || shift < 0 || r->pos[i] < 0) continue;   // Events.py:64: references[0] only (or the layout's references)
         if (fl & flag_filter) continue;
         if (ignore_orphans && (fl & 0x1) && !(fl & 0x2)) continue;
         const uint32_t *cg = r->cigar + r->cigar_off[i];
@@ -401,7 +413,7 @@ extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64
         for (int64_t k = 0; k < nc; ++k)
             if (consumes_ref(cg[k] & 0xF)) span += cg[k] >> 4;
         if (span == 0) continue;
-        const int64_t beg = r->pos[i], end = beg + span;      // 0-based half-open
+        const int64_t beg = r->pos[i] + shift, end = beg + span;      // 0-based half-open
         // candidate columns c = position-1 in [beg, end)
         const int64_t *lo = std::lower_bound(positions, positions + n_pos, beg + 1);
         for (const int64_t *pp = lo; pp < positions + n_pos && *pp - 1 < end; ++pp) {
@@ -441,10 +453,11 @@ extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64
                                 if (consumes_ref(o2)) xr += cg[k2] >> 4;
                             }
                         }
-                        e.pos = r->pos[i]; e.end = end; e.flag = (uint16_t)fl; e.l_qseq = (int32_t)lq;
+                        e.pos = (int32_t)beg; e.end = end; e.flag = (uint16_t)fl; e.l_qseq = (int32_t)lq;
                         e.tid = r->tid ? r->tid[i] : 0;
                         e.mtid = r->next_tid ? r->next_tid[i] : -1;
                         e.mpos = r->next_pos ? r->next_pos[i] : -1;
+                        if (r->next_tid && r->next_tid[i] == my_tid && e.mpos >= 0) e.mpos += (int32_t)shift;    // (a mate on the same reference: on the axis too)
                         e.isize = r->tlen ? r->tlen[i] : 0;
                         e.name_hash = (r->names && r->name_off) ? fnv1a(r->names + r->name_off[i], (size_t)(r->name_off[i + 1] - r->name_off[i])) : 0;
                         const char first = is_match(op) ? base(qpos) : (op == 3 ? (rev ? '<' : '>') : '*');
@@ -494,7 +507,7 @@ extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64
             if (i < 0 || i >= r->n_reads) continue;
             const uint32_t *cg = r->cigar + r->cigar_off[i];
             const int64_t nc = (int64_t)(r->cigar_off[i + 1] - r->cigar_off[i]), lq = r->l_qseq[i];
-            int64_t x = r->pos[i], y = 0;
+            int64_t x = r->pos[i] + std::max<int64_t>(lay.shift_of(r->tid ? r->tid[i] : 0), 0), y = 0;     // (on the axis, as the request)
             for (int64_t k = 0; k < nc; ++k) {
                 const unsigned op = cg[k] & 0xF;
                 const int64_t len = cg[k] >> 4;
@@ -522,4 +535,26 @@ extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64
     if (rc) return rc;
     if (status_flags) *status_flags = status;
     return TCMI_OK;
+}
+
+extern "C" int tcmi_modal_tokens(const tcmi_reads *r, int32_t n_pos, const int64_t *positions, int32_t min_base_quality, uint32_t flag_filter,
+                                 int ignore_orphans, int64_t max_depth, int ignore_overlaps, char *tokens, int64_t tokens_cap, int64_t *token_off,
+                                 int64_t *n_tokens, int32_t *status_flags)
+{
+    const tcmi_layout none;
+    return modal_tokens_impl(r, none, n_pos, positions, min_base_quality, flag_filter, ignore_orphans, max_depth, ignore_overlaps, tokens,
+                             tokens_cap, token_off, n_tokens, status_flags);
+}
+
+extern "C" int tcmi_modal_tokens_layout(const tcmi_reads *r, int32_t n_ref, const int64_t *shift, const int64_t *slot_len, int32_t n_pos,
+                                        const int64_t *positions, int32_t min_base_quality, uint32_t flag_filter, int ignore_orphans,
+                                        int64_t max_depth, int ignore_overlaps, char *tokens, int64_t tokens_cap, int64_t *token_off,
+                                        int64_t *n_tokens, int32_t *status_flags)
+{
+    char msg[200];
+    tcmi_layout lay;
+    const int rc = tcmi_layout_build(n_ref, shift, slot_len, &lay, msg, sizeof msg);
+    if (rc) return tcmi_fail(nullptr, rc, "%s", msg);
+    return modal_tokens_impl(r, lay, n_pos, positions, min_base_quality, flag_filter, ignore_orphans, max_depth, ignore_overlaps, tokens,
+                             tokens_cap, token_off, n_tokens, status_flags);
 }

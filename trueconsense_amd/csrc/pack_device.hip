@@ -143,7 +143,7 @@ __device__ inline bool is_match(uint32_t op) { return op == 0 || op == 7 || op =
 constexpr uint32_t INFO_PROJ = 1u << 10, INFO_KEPT = 1u << 11;
 // flags raised for the host
 enum { PKF_LONG = 1, PKF_FARPOS = 2, PKF_BADREAD = 4, PKF_EVENT_OVF = 8, PKF_CHUNK_OVF = 16, PKF_HEADER_OVF = 32, PKF_WORD_OVF = 64,
-       PKF_MULTIREF = 128 };
+       PKF_MULTIREF = 128, PKF_SLOT_OVF = 1u << 13 /* a kept read ends past its contig's slot (tcmi_ctx_set_layout) */ };
 
 struct PackTotals {                 // device scalars, copied back to the host
     unsigned long long alg_bytes;
@@ -158,6 +158,8 @@ struct PackTotals {                 // device scalars, copied back to the host
     // pk_place, a block range: where its first record starts / where the first record behind it starts, as offsets into the range's
     // stream + 1 (0: no record starts in the range / the chain was never fixed) — tcmi_readset_range_anchors
     unsigned long long range_first, range_next;
+    unsigned long long slot_ovf;    // a contig layout: (read index + 1) << 24 | reference of the last kept read that ends past its slot (0: none)
+    unsigned long long n_dropped;   // a contig layout: mapped reads on references without a slot
 };
 
 // words a read takes in the plane stream: its pairs, the zero pair behind them, and — for an even number of pairs — one more zero pair,
@@ -187,14 +189,46 @@ __device__ inline uint2 block_scan2(uint2 v, uint2 *wave_tot /* LDS [PB / 64] */
 // ---- 1: classify ----------------------------------------------------------------------------------------------
 // what one read is to the packer: its per-read word (0: not kept), the words it takes in the plane stream, its SURVEY §8-d bytes,
 // its end; `longread`: left to tally_stream_kernel (a device-decoded stream only; from flat arrays PKF_LONG is raised instead)
-struct Classified { uint32_t word, nwords, len; unsigned long long alg; int32_t end; bool longread; };
+struct Classified { uint32_t word, nwords, len; unsigned long long alg; int32_t end; bool longread, slot_ovf; };
 
-__device__ inline Classified classify_view(const ReadView &v, int32_t mode, int32_t pos_shift, const uint8_t *rec, bool stream_long_ok, PackTotals *tot)
+// where reference `tid` starts on the one coordinate axis: without a contig layout reference 0 at the uniform shift (batched uploads),
+// with one its table entry (a handful of words, read through the scalar cache); < 0: the read does not pile up
+__device__ inline int32_t shift_of(const PackSrc &s, int32_t tid)
 {
-    Classified c = {0u, 0u, 0u, 0ull, 0, false};
-    bool kept = !(v.flag & 0x4u) && v.tid == 0 && v.pos >= 0 && !v.bad;
-    if (v.broken || (v.bad && !(v.flag & 0x4u) && v.tid == 0 && v.pos >= 0)) atomicOr(&tot->flags, (uint32_t)PKF_BADREAD);
-    if (!(v.flag & 0x4u) && v.tid > 0) atomicOr(&tot->flags, (uint32_t)PKF_MULTIREF);   // (the host packer words the error)
+    if (s.n_lay == 0) return tid == 0 ? s.pos_shift : -1;
+    return tid >= 0 && tid < s.n_lay ? s.lay[tid] : -1;
+}
+__device__ inline int32_t slot_end_of(const PackSrc &s, int32_t tid) { return s.n_lay == 0 ? 0x7FFFFFFF : s.lay[s.n_lay + tid]; }
+
+// the kept reads' max end per reference (a contig layout): called by every lane of the wavefront; one atomic per reference the
+// wavefront holds reads of (one or two in a sorted file)
+__device__ inline void ref_extent_max(int32_t *ext, int32_t t, int32_t e)
+{
+    bool todo = t >= 0 && e > 0;
+    for (;;) {
+        const unsigned long long m = __ballot(todo);
+        if (!m) break;
+        const int lead = (int)__builtin_ctzll(m);
+        const int32_t lt = __shfl(t, lead, 64);
+        const bool same = todo && t == lt;
+        int32_t v = same ? e : 0;
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+        if ((int)(threadIdx.x & 63) == lead) atomicMax(ext + lt, v);
+        if (same) todo = false;
+    }
+}
+
+// `shift`: where the read's reference starts on the axis (< 0: not piled up), `slot_end`: where its slot ends, `layout`: a contig
+// layout is set (reads on other references are not an error then)
+__device__ inline Classified classify_view(const ReadView &v, int32_t mode, int32_t shift, int32_t slot_end, bool layout, const uint8_t *rec,
+                                           bool stream_long_ok, PackTotals *tot)
+{
+    Classified c = {0u, 0u, 0u, 0ull, 0, false, false};
+    const int32_t pos_shift = shift;
+    bool kept = !(v.flag & 0x4u) && shift >= 0 && v.pos >= 0 && !v.bad;
+    if (v.broken || (v.bad && !(v.flag & 0x4u) && shift >= 0 && v.pos >= 0)) atomicOr(&tot->flags, (uint32_t)PKF_BADREAD);
+    if (!layout && !(v.flag & 0x4u) && v.tid > 0) atomicOr(&tot->flags, (uint32_t)PKF_MULTIREF);   // (the host packer words the error)
     if (!kept) return c;
     // one walk over the CIGAR: reference span, and is it [H]*[S]* (M|=|X)+ [S]*[H]* ?
     int64_t span = 0, m = 0, y0 = 0;
@@ -220,6 +254,7 @@ __device__ inline Classified classify_view(const ReadView &v, int32_t mode, int3
     const int64_t end = (int64_t)v.pos + pos_shift + span;
     const int64_t len = simple ? m : span;
     if (end >= (int64_t)TCMI_F_EVPOS) { atomicOr(&tot->flags, (uint32_t)PKF_FARPOS); return c; }
+    if (end > (int64_t)slot_end) { atomicOr(&tot->flags, (uint32_t)PKF_SLOT_OVF); c.slot_ovf = true; return c; }      // (never tallied into the next slot)
     c.alg = (unsigned long long)(12 + 4 * (int64_t)v.n_cigar + ((int64_t)v.l_seq + 1) / 2);
     c.end = (int32_t)end;
     if (len > TCMI_D_MAXLEN) {
@@ -247,9 +282,16 @@ __global__ __launch_bounds__(PB) void pk_classify(PackSrc s, uint32_t *info, uin
     unsigned long long my_alg = 0;
     int32_t my_end = 0;
     uint32_t my_len = 0;
+    int32_t my_tid = -1, my_lend = 0;
+    bool dropped = false;
     if (i < s.n) {
         const ReadView v = view(s, i);
-        const Classified c = classify_view(v, s.mode, s.pos_shift, s.mode == 1 ? s.stream + s.rec_off[i] : nullptr, gen_idx != nullptr, tot);
+        const int32_t shift = shift_of(s, v.tid);
+        const Classified c = classify_view(v, s.mode, shift, shift >= 0 ? slot_end_of(s, v.tid) : 0, s.n_lay != 0,
+                                           s.mode == 1 ? s.stream + s.rec_off[i] : nullptr, gen_idx != nullptr, tot);
+        if (c.end > 0) { my_tid = v.tid; my_lend = c.end - shift; }
+        if (c.slot_ovf) atomicMax(&tot->slot_ovf, ((unsigned long long)(i + 1) << 24) | (unsigned long long)min(v.tid, 0xFFFFFF));   // (the read the host names)
+        dropped = s.n_lay && shift < 0 && !(v.flag & 0x4u) && v.tid >= 0 && v.pos >= 0;
         if (c.longread) gen_idx[atomicAdd(&tot->n_gen, 1u)] = (uint32_t)i;
         word = c.word; nwords = c.nwords; my_alg = c.alg; my_end = c.end; my_len = c.len;
         info[i] = word;
@@ -257,7 +299,12 @@ __global__ __launch_bounds__(PB) void pk_classify(PackSrc s, uint32_t *info, uin
         // pk_pack goes straight there instead of chasing record offset -> header -> CIGAR -> SEQ through four dependent loads
         const unsigned long long so = (unsigned long long)(v.seq - (s.mode == 0 ? s.seq : s.stream));
         rd_seq[i] = make_uint2((uint32_t)so, ((uint32_t)(so >> 32) & 0xFFu) | ((uint32_t)min(v.l_seq, 0xFFFFFF) << 8));
-        rd_pos[i] = v.pos;                      // (pk_scatter's copy: it need not go back to the record)
+        rd_pos[i] = c.word ? v.pos + shift : v.pos;     // (pk_scatter's copy, on the axis: it need not go back to the record)
+    }
+    if (s.n_lay) {
+        ref_extent_max(s.lay_ext, my_tid, my_lend);
+        const unsigned long long m = __ballot(dropped);            // (one atomic per wavefront that holds dropped reads)
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(&tot->n_dropped, (unsigned long long)__popcll(m));
     }
     const uint2 incl = block_scan2(make_uint2(word ? 1u : 0u, nwords), s_w);
     if (threadIdx.x == PB - 1) blk_sum[blockIdx.x] = incl;
@@ -331,7 +378,7 @@ __global__ __launch_bounds__(PB) void pk_scatter(PackSrc s, const uint32_t *info
         const uint2 base = blk_base[blockIdx.x];
         const uint32_t j = base.x + incl.x - 1u;
         c_idx[j] = (uint32_t)i;
-        c_pos[j] = rd_pos[i] + s.pos_shift;
+        c_pos[j] = rd_pos[i];
         c_info[j] = w;
         c_woff[j] = base.y + incl.y - mine.y;
         c_seq[j] = rd_seq[i];
@@ -851,7 +898,7 @@ __global__ __launch_bounds__(PB) void pk_index(FusedArgs a)
             ReadView v = view_rec(rec);
             // (a record that claims to end behind the stream: nothing of it is followed — the chain check will refuse the file)
             if (roff + 4ull + ld_u32(rec) > a.stream_len) { v.bad = true; v.broken = true; v.n_cigar = 0; }
-            const Classified c = classify_view(v, 1, 0, rec, true, a.tot);
+            const Classified c = classify_view(v, 1, v.tid == 0 ? 0 : -1, 0x7FFFFFFF, false, rec, true, a.tot);
             word = c.word; nwords = c.nwords;
             my_alg += c.alg; my_end = max(my_end, c.end); my_len = max(my_len, c.len);
             if (room) {
@@ -1310,6 +1357,12 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     std::memset(h_tot, 0, sizeof *h_tot);
     PackTotals &tot = *h_tot;
     TCMI_HIP(ctx, hipMemsetAsync(d_tot, 0, sizeof(PackTotals), ctx->stream));
+    const int32_t n_lay = ctx->layout.n();
+    std::vector<int32_t> h_ext((size_t)n_lay);
+    if (n_lay) {                            // the context's contig layout (tcmi_ctx_set_layout): its table, the extents zeroed
+        src.lay = ctx->d_lay; src.lay_ext = ctx->d_lay + 2 * n_lay; src.n_lay = n_lay;
+        TCMI_HIP(ctx, hipMemsetAsync(src.lay_ext, 0, (size_t)n_lay * 4, ctx->stream));
+    }
     if (n > 0) {
         (void)hipGetLastError();
         tcmi_prof_begin(ctx, TCMI_K_PACK_CLASSIFY);
@@ -1319,9 +1372,17 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
         TCMI_HIP(ctx, hipGetLastError());
     }
     TCMI_HIP(ctx, hipMemcpyAsync(h_tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_lay) TCMI_HIP(ctx, hipMemcpyAsync(h_ext.data(), src.lay_ext, (size_t)n_lay * 4, hipMemcpyDeviceToHost, ctx->stream));
     TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (tot.flags & PKF_SLOT_OVF) {         // (the host packer / host reader word it with the contig's name: the caller falls back to them)
+        *why = tot.flags;
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "read %lld on reference %d ends past the end of its contig's slot", (long long)(tot.slot_ovf >> 24) - 1,
+                         (int)(tot.slot_ovf & 0xFFFFFF));
+    }
     if (tot.flags) { *why = tot.flags; return TCMI_E_UNSUPPORTED; }
     const int64_t nf = (int64_t)tot.n_kept;
+    rs->n_lay = n_lay; rs->d_lay = src.lay; rs->lay_gen = ctx->lay_gen; rs->n_dropped = (int64_t)tot.n_dropped;
+    rs->ref_ext.assign(h_ext.begin(), h_ext.end());
     rs->n_piled = nf + (int64_t)tot.n_gen; rs->f_reads = nf; rs->alg_bytes = (int64_t)tot.alg_bytes; rs->max_end = tot.max_end; rs->max_len = (int32_t)tot.max_len;
     rs->packed_on_device = 1;
     if (tot.n_gen) {                        // long reads: tallied from the stream, which stays in the arena until this context's next upload
@@ -1622,7 +1683,7 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
     if (w >= n_gen) return;
     const ReadView v = view(s, (int64_t)gen_idx[w]);
     auto add = [&](int col, int32_t p) { if ((uint32_t)p < (uint32_t)L) atomicAdd(&counts[(int64_t)col * ld + p], 1); };
-    int32_t x = v.pos + s.pos_shift, y = 0;
+    int32_t x = v.pos + shift_of(s, v.tid), y = 0;
     const int32_t x0 = x;
     for (uint32_t k = 0; k < v.n_cigar; ++k) {
         const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k), op = c & 0xFu;
@@ -1656,6 +1717,9 @@ int tcmi_launch_tally_stream(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, i
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set's long reads lie in a decoded stream that is gone (another upload on this context): upload it again");
     PackSrc s = {};
     s.stream = rs->d_stream; s.rec_off = rs->d_rec_off; s.mode = 1; s.n = rs->n_reads; s.pos_shift = 0;
+    if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's contig layout changed since the read set was uploaded: upload it again");
+    s.lay = rs->d_lay; s.n_lay = rs->n_lay;
     (void)hipGetLastError();
     tcmi_prof_begin(ctx, TCMI_K_TALLY_GENERAL);
     hipLaunchKernelGGL(tally_stream_kernel, dim3((unsigned)((rs->s_reads + 3) / 4)), dim3(256), 0, ctx->stream, s, rs->d_gen_idx, (uint32_t)rs->s_reads,
@@ -1706,6 +1770,8 @@ static int collect_ins_entries(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n_
 
     if (rs->s_reads > 0)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "long reads lie outside the packed set: their tokens are not looked at here (host sweep)");
+    if (rs->n_lay > 0)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set was uploaded under a contig layout: host sweep (tcmi_modal_tokens_layout)");
     if (!rs->d_stream || rs->arena_epoch != ctx->arena_epoch || rs->device != ctx->device)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set's decoded stream is no longer (or never was) resident on this context: host sweep");
     for (int32_t k = 1; k < n_pos; ++k)

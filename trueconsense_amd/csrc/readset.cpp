@@ -27,10 +27,10 @@ int64_t ref_span(const uint32_t *cg, int64_t n)
 // collide with the first reference's columns and its BuildIndex fails (indexing.py:137-151).  They never
 // pile up here, and an upload that meets a mapped one fails with TCMI_E_UNSUPPORTED instead of tallying it onto
 // reference 0's coordinates.
-inline bool piles_up(const tcmi_reads *r, int64_t i, int64_t *span)
+inline bool piles_up(const tcmi_reads *r, int64_t i, int64_t *span, const tcmi_layout &lay)
 {
     if (r->flag[i] & 0x4) return false;
-    if (r->tid && r->tid[i] != 0) return false;
+    if (lay.shift_of(r->tid ? r->tid[i] : 0) < 0) return false;
     if (r->pos[i] < 0) return false;
     *span = ref_span(r->cigar + r->cigar_off[i], (int64_t)(r->cigar_off[i + 1] - r->cigar_off[i]));
     return *span > 0;
@@ -118,6 +118,8 @@ struct Sel { const tcmi_reads *r; int64_t i, off, y0, len, seg; bool projected; 
 struct GSel { const tcmi_reads *r; int64_t i, off; };
 struct Part {                       // what one classification thread found in its slice of a BAM
     std::vector<Sel> fsel; std::vector<GSel> gsel;
+    std::vector<int64_t> ref_ext;   // under a contig layout: the kept reads' max end per reference, in its own coordinates
+    int64_t n_dropped = 0;          // ... and the mapped reads on references without a slot
     int64_t g_cig = 0, g_seqw = 0, alg = 0, max_end = 0; bool any_cut = false;
     int err = TCMI_OK; char msg[160] = {0};
 };
@@ -153,9 +155,10 @@ int tcmi_reads_extent(const tcmi_reads *r, int64_t ref_len, int64_t *out_L)
     if (rc) return rc;
     if (!out_L) return tcmi_fail(nullptr, TCMI_E_ARG, "out_L is NULL");
     int64_t L = ref_len > 0 ? ref_len : 0;
+    const tcmi_layout none;
     for (int64_t i = 0; i < r->n_reads; ++i) {
         int64_t span;
-        if (!piles_up(r, i, &span)) continue;
+        if (!piles_up(r, i, &span, none)) continue;
         if (r->pos[i] + span > L) L = r->pos[i] + span;
     }
     *out_L = L;
@@ -242,16 +245,19 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
     fsel.clear();
     gsel.clear();
     int64_t g_cig = 0, g_seqw = 0, alg = 0, max_end = 0;
+    std::vector<int64_t> ref_ext;
+    int64_t n_dropped = 0;
     bool any_cut = false;
     // every BAM's reads in `host_threads` contiguous slices, each into its own lists, joined in order afterwards
     const int n_cls = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)ctx->host_threads, 64, n_reads_in / 65536 + 1}));
     std::vector<Part> &parts = SC.parts;
     parts.resize((size_t)n_batch * (size_t)n_cls);
-    for (Part &P : parts) { P.fsel.clear(); P.gsel.clear(); P.g_cig = P.g_seqw = P.alg = P.max_end = 0; P.any_cut = false; P.err = TCMI_OK; }
+    const tcmi_layout &lay = ctx->layout;
+    for (Part &P : parts) { P.fsel.clear(); P.gsel.clear(); P.g_cig = P.g_seqw = P.alg = P.max_end = 0; P.any_cut = false; P.err = TCMI_OK; P.ref_ext.assign((size_t)lay.n(), 0); P.n_dropped = 0; }
     auto classify = [&](int32_t bi, int t) {
         Part &P = parts[(size_t)bi * (size_t)n_cls + (size_t)t];
         const tcmi_reads *r = batch[bi];
-        const int64_t off = (int64_t)bi * stride;
+        const int64_t off0 = (int64_t)bi * stride;
         const int64_t i0 = r->n_reads * t / n_cls, i1 = r->n_reads * (t + 1) / n_cls;
         auto fail = [&](int code, const char *fmt, long long x, long long y, long long z) {
             P.err = code;
@@ -259,10 +265,16 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
         };
         for (int64_t i = i0; i < i1; ++i) {
             int64_t span;
-            if (r->tid && r->tid[i] > 0 && !(r->flag[i] & 0x4))
+            if (!lay.n() && r->tid && r->tid[i] > 0 && !(r->flag[i] & 0x4))
                 return fail(TCMI_E_UNSUPPORTED, "read %lld is mapped to reference %lld: only single-reference alignments are supported "
                                                 "(the reference implementation keys columns by position only and fails on these)%.0lld", i, r->tid[i], 0);
-            if (!piles_up(r, i, &span)) continue;
+            const int32_t tid = r->tid ? r->tid[i] : 0;
+            if (lay.n() && lay.shift_of(tid) < 0 && tid >= 0 && !(r->flag[i] & 0x4) && r->pos[i] >= 0) ++P.n_dropped;
+            if (!piles_up(r, i, &span, lay)) continue;
+            const int64_t off = off0 + (lay.n() ? lay.shift_of(tid) : 0);
+            if (lay.n() && off + r->pos[i] + span > lay.end_of(tid))
+                return fail(TCMI_E_UNSUPPORTED, "read %lld on reference %lld ends past the end of its contig's slot (at %lld)", i, tid, r->pos[i] + span);
+            if (lay.n() && r->pos[i] + span > P.ref_ext[(size_t)tid]) P.ref_ext[(size_t)tid] = r->pos[i] + span;
             const uint32_t *cg = r->cigar + r->cigar_off[i];
             const int64_t nc = (int64_t)(r->cigar_off[i + 1] - r->cigar_off[i]);
             if (nc > 65535) return fail(TCMI_E_UNSUPPORTED, "read %lld has %lld CIGAR ops (> 65535)%.0lld", i, nc, 0);
@@ -308,6 +320,10 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
             gsel.insert(gsel.end(), P.gsel.begin(), P.gsel.end());
             g_cig += P.g_cig; g_seqw += P.g_seqw; alg += P.alg; max_end = std::max(max_end, P.max_end); any_cut |= P.any_cut;
         }
+        ref_ext.assign((size_t)lay.n(), 0);
+        for (const Part &P : parts) n_dropped += P.n_dropped;
+        for (const Part &P : parts)
+            for (size_t t = 0; t < P.ref_ext.size(); ++t) ref_ext[t] = std::max(ref_ext[t], P.ref_ext[t]);
     }
 
     if (any_cut)                                // pieces of long reads start further right than the reads that follow them
@@ -584,6 +600,7 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
     tcmi_readset *rs = new tcmi_readset();
     rs->uid = next_uid.fetch_add(1);
     rs->n_reads = n_reads_in; rs->n_piled = nf + ng; rs->alg_bytes = alg; rs->max_end = max_end; rs->device = ctx->device;
+    rs->n_lay = lay.n(); rs->ref_ext = std::move(ref_ext); rs->n_dropped = n_dropped; rs->lay_gen = ctx->lay_gen;
     rs->f_reads = nf; rs->f_chunks = (int64_t)chunks.size(); rs->f_words = (int64_t)f_seq_n;
     rs->f_events = (int64_t)f_event.size();
     rs->g_reads = ng; rs->n_rounds = n_rounds; rs->n_cigar = g_cig; rs->n_seqw = g_seqw;
@@ -621,7 +638,25 @@ int tcmi_readset_upload(tcmi_ctx *ctx, const tcmi_reads *r, tcmi_readset **out)
 int tcmi_readset_upload_batch(tcmi_ctx *ctx, const tcmi_reads *const *reads, int32_t n, int64_t stride, tcmi_readset **out)
 {
     if (n < 1 || n > 4096 || stride <= 0 || stride % 256) return tcmi_fail(ctx, TCMI_E_ARG, "need 1 <= n <= 4096 and a positive stride that is a multiple of 256");
+    if (ctx && ctx->layout.n()) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "batched uploads do not take a contig layout (tcmi_ctx_set_layout)");
     return upload_impl(ctx, reads, n, stride, out);
+}
+
+int tcmi_readset_ref_extents(const tcmi_readset *rs, int32_t n_ref, int64_t *max_end)
+{
+    if (!rs || n_ref < 0 || (n_ref > 0 && !max_end)) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    if (rs->parts.size() || (size_t)n_ref != rs->ref_ext.size())
+        return tcmi_fail(nullptr, TCMI_E_ARG, "the read set holds %zu per-reference extents (uploaded under a layout of that size), not %d",
+                         rs->parts.size() ? (size_t)0 : rs->ref_ext.size(), n_ref);
+    for (int32_t t = 0; t < n_ref; ++t) max_end[t] = rs->ref_ext[(size_t)t];
+    return TCMI_OK;
+}
+
+int tcmi_readset_dropped(const tcmi_readset *rs, int64_t *n_dropped)
+{
+    if (!rs || !n_dropped) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    *n_dropped = rs->n_dropped;
+    return TCMI_OK;
 }
 
 int tcmi_readset_info(const tcmi_readset *rs, int64_t *n_reads, int64_t *n_piled, int64_t *alg, int64_t *dev,

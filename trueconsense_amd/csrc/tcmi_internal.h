@@ -11,6 +11,24 @@
 
 #include "../../include/tcmi.h"
 
+// ---- several contigs on one coordinate axis (tcmi_ctx_set_layout) --------------------------------------------------
+// Reference t's reads pile up at pos + shift[t]; shift[t] < 0: they do not pile up (a reference the caller has no record of);
+// a kept read must end at or before end[t] = shift[t] + slot_len[t].  No layout (n() == 0): reference 0 at 0, nothing else.
+// The one rule of the host packer (readset.cpp) and the host insert sweep (insert_tokens.cpp); pack_device.hip holds the same
+// table on the device.
+struct tcmi_layout {
+    std::vector<int64_t> shift, end;
+    int32_t n() const { return (int32_t)shift.size(); }
+    int64_t shift_of(int32_t tid) const
+    {
+        if (shift.empty()) return tid == 0 ? 0 : -1;
+        return tid >= 0 && tid < n() ? shift[(size_t)tid] : -1;
+    }
+    int64_t end_of(int32_t tid) const { return shift.empty() ? INT64_MAX : end[(size_t)tid]; }
+};
+// checks n_ref / shift / slot_len (slots in ascending order, disjoint, below TCMI_F_EVPOS) and fills *out; TCMI_OK or TCMI_E_ARG
+int tcmi_layout_build(int32_t n_ref, const int64_t *shift, const int64_t *slot_len, tcmi_layout *out, char *msg, size_t msg_cap);
+
 // ---- device read layout -------------------------------------------------------------
 // Only reads that pile up (mapped, tid == 0, pos >= 0, reference span > 0)
 // are kept, in two sets:
@@ -97,6 +115,13 @@ struct tcmi_readset {
     const uint64_t *d_rec_off = nullptr;
     const uint32_t *d_cidx = nullptr;
     const int32_t *d_cpos = nullptr;
+    // uploaded under a contig layout: its size, the device table (tally_stream_kernel shifts the long reads with it) and the kept
+    // reads' max end per reference, in the reference's own coordinates (tcmi_readset_ref_extents)
+    int32_t n_lay = 0;
+    const int32_t *d_lay = nullptr;
+    uint64_t lay_gen = 0;           // the context's layout generation at the upload (the device table is rewritten by the next layout)
+    std::vector<int64_t> ref_ext;
+    int64_t n_dropped = 0;          // mapped reads on references without a slot (tcmi_readset_dropped)
     const uint32_t *d_gen_idx = nullptr;   // records of reads too long for the packed set (s_reads of them): tally_stream_kernel walks them in the stream
     int64_t s_reads = 0;
     // a read set of a block RANGE of a file (tcmi_readset_from_bamfile_blocks): where its first record starts when the range began
@@ -151,6 +176,12 @@ struct tcmi_ctx {
     // (hipMalloc + hipFree cost more than the pack kernels, and hipFree waits for the device)
     struct Blob { char *p; size_t bytes; };
     std::vector<Blob> blob_pool;
+    // the contig layout of tcmi_ctx_set_layout (host form) and its device table {shift[n], end[n], ext[n]} (int32): one grow-only
+    // buffer, rewritten by every layout; lay_gen counts the rewrites (a read set's long reads need the table it was uploaded under)
+    tcmi_layout layout;
+    int32_t *d_lay = nullptr;
+    size_t d_lay_cap = 0;
+    uint64_t lay_gen = 0;
     // scratch of tcmi_readset_modal_tokens (columns, ranges, entries): device + pinned host, grow-only
     char *tok_dev = nullptr, *tok_host = nullptr;
     size_t tok_dev_cap = 0, tok_host_cap = 0;
@@ -256,6 +287,9 @@ struct tcmi_pack_src {
     const uint8_t *stream; const uint64_t *rec_off;
     int64_t n;
     int32_t mode, pos_shift;
+    // a contig layout (tcmi_ctx_set_layout; n_lay = 0: none, reference 0 at pos_shift): lay[t] = shift of reference t (< 0: dropped),
+    // lay[n_lay + t] = the end of its slot; lay_ext[t]: the kept reads' max end on reference t, in its own coordinates (atomicMax)
+    const int32_t *lay; int32_t *lay_ext; int32_t n_lay;
 };
 // one read on one insert-candidate column, as the device kernel hands it to the host (pack_device.hip -> insert_tokens.cpp)
 struct tcmi_dev_entry {

@@ -32,6 +32,18 @@ class ReadSet:
         # and where the first record behind it starts, offsets into the file's inflated stream (-1: none) — distributed.check_range_anchors
         self.range_anchors = (a.value, b.value)
 
+    def ref_extents(self, n_ref):
+        """Uploaded under a contig layout of n_ref references: per reference the kept reads' max end in its own coordinates."""
+        out = np.zeros(int(n_ref), np.int64)
+        check(lib().tcmi_readset_ref_extents(self.handle, int(n_ref), ptr(out)))
+        return out
+
+    def dropped(self):
+        """Uploaded under a contig layout: mapped reads whose reference has no slot (not tallied)."""
+        n = C.c_int64(0)
+        check(lib().tcmi_readset_dropped(self.handle, C.byref(n)))
+        return n.value
+
     def free(self):
         if self.handle:
             lib().tcmi_readset_free(self.ctx.handle, self.handle)
@@ -99,6 +111,16 @@ class Context:
         ms, n = C.c_double(0), C.c_int64(0)
         check(lib().tcmi_profile_get(self.handle, kernel, C.byref(ms), C.byref(n)), self.handle)
         return ms.value, n.value
+
+    def set_layout(self, shift=None, slot_len=None):
+        """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
+        slot_len[t] positions.  No arguments: back to reference 0 only."""
+        shift = np.ascontiguousarray([] if shift is None else shift, np.int64)
+        slot_len = np.ascontiguousarray([] if slot_len is None else slot_len, np.int64)
+        if len(shift) != len(slot_len):
+            raise ValueError("shift and slot_len differ in length")
+        check(lib().tcmi_ctx_set_layout(self.handle, len(shift), ptr(shift) if len(shift) else None,
+                                        ptr(slot_len) if len(slot_len) else None), self.handle)
 
     # ---- stage A
     def upload(self, reads):
@@ -388,10 +410,11 @@ DEFAULT_MAX_DEPTH = 8000
 
 
 def modal_tokens(reads, positions, min_base_quality=DEFAULT_MIN_BASE_QUALITY, flag_filter=DEFAULT_FLAG_FILTER,
-                 ignore_orphans=True, max_depth=DEFAULT_MAX_DEPTH, ignore_overlaps=True):
+                 ignore_orphans=True, max_depth=DEFAULT_MAX_DEPTH, ignore_overlaps=True, layout=None):
     """For each 1-based position: (modal upper-cased token or None, n_tokens) under pysam's default pileup arguments
     (Events.py:66).  Raises TcmiError(E_UNSUPPORTED) where overlapping mates meet a deletion on the column (the one case of
-    pysam's overlap handling that is not modelled)."""
+    pysam's overlap handling that is not modelled).  layout = (shift, slot_len): positions on a contig layout's axis
+    (tcmi_modal_tokens_layout)."""
     positions = np.ascontiguousarray(sorted(int(p) for p in positions), np.int64)
     n = len(positions)
     if n == 0:
@@ -403,9 +426,13 @@ def modal_tokens(reads, positions, min_base_quality=DEFAULT_MIN_BASE_QUALITY, fl
         off = np.zeros(n + 1, np.int64)
         cnt = np.zeros(n, np.int64)
         deep = C.c_int32(0)
-        rc = lib().tcmi_modal_tokens(C.byref(r), n, ptr(positions), int(min_base_quality), int(flag_filter),
-                                     int(bool(ignore_orphans)), int(max_depth), int(bool(ignore_overlaps)), C.cast(buf, C.c_void_p), cap,
-                                     ptr(off), ptr(cnt), C.byref(deep))
+        tail = (int(min_base_quality), int(flag_filter), int(bool(ignore_orphans)), int(max_depth), int(bool(ignore_overlaps)),
+                C.cast(buf, C.c_void_p), cap, ptr(off), ptr(cnt), C.byref(deep))
+        if layout is None:
+            rc = lib().tcmi_modal_tokens(C.byref(r), n, ptr(positions), *tail)
+        else:
+            sh, sl = (np.ascontiguousarray(x, np.int64) for x in layout)
+            rc = lib().tcmi_modal_tokens_layout(C.byref(r), len(sh), ptr(sh), ptr(sl), n, ptr(positions), *tail)
         if rc == _ffi.E_ARG and b"token buffer too small" in (lib().tcmi_last_error(None) or b"") and cap < (1 << 30):
             cap *= 16
             continue
@@ -422,6 +449,17 @@ def modal_tokens(reads, positions, min_base_quality=DEFAULT_MIN_BASE_QUALITY, fl
     return out
 
 
+def _header_refs(fn, h, n_ref):
+    """(names, lengths) of every reference of a BAM header (`references` / `lengths` keep pysam's first-reference view)."""
+    names, lens = [], []
+    for i in range(n_ref):
+        name, ln = C.c_char_p(), C.c_int64(0)
+        check(fn(h, i, C.byref(name), C.byref(ln)))
+        names.append((name.value or b"").decode())
+        lens.append(ln.value)
+    return tuple(names), tuple(lens)
+
+
 class BamFile:
     """A BAM decoded by libtcmi (tcmi_bam_load): pysam.AlignmentFile's role for this path."""
 
@@ -435,6 +473,7 @@ class BamFile:
         self.nreferences = n_ref.value
         self.references = ((name.value or b"").decode(),) if n_ref.value else ()
         self.lengths = (ln.value,) if n_ref.value else ()
+        self.all_references, self.all_lengths = _header_refs(lib().tcmi_bam_ref, h, n_ref.value)
         v = [C.c_int64(0), C.c_int32(0)] + [C.c_int64(0) for _ in range(5)]
         check(lib().tcmi_bam_info(h, *[C.byref(x) for x in v]))
         (self.n_reads, self.sorted, self.file_bytes, self.inflated_bytes, self.n_blocks, self.n_cigar,
@@ -512,6 +551,7 @@ class DeviceBam:
         self.nreferences = n_ref.value
         self.references = ((name.value or b"").decode(),) if n_ref.value else ()
         self.lengths = (ln.value,) if n_ref.value else ()
+        self.all_references, self.all_lengths = _header_refs(lib().tcmi_bamfile_ref, h, n_ref.value)
         self.text = (lib().tcmi_bamfile_text(h) or b"").decode("utf-8", "replace")
 
     def to_device(self, ctx):

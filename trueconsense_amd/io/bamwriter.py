@@ -101,11 +101,13 @@ def write_bam(path, reads, ref_name="ref", ref_len=0, level=1, sam_text=None, bl
         fh.write(_EOF)
 
 
-def write_bam_fast(path, pos, flag, seq_packed, read_len, ref_name="ref", ref_len=0, level=1, qual=30, part=(True, True), first_id=0, names=None):
+def write_bam_fast(path, pos, flag, seq_packed, read_len, ref_name="ref", ref_len=0, level=1, qual=30, part=(True, True), first_id=0, names=None,
+                   tid=None, refs=None):
     """Vectorised writer for the bench workload: n reads, all `read_len`M, flags from `flag`,
     seq_packed uint8 [n, ceil(read_len/2)] in BAM nibble order, constant quality.  part = (first, last): a large file is written
     in several calls, slice by slice (the header goes with the first, the end-of-file block with the last); first_id numbers the names.
-    qual: one value, or uint8 [n, read_len]; names: uint8 [n, k] (k characters each, no NUL) instead of the seven-digit numbers."""
+    qual: one value, or uint8 [n, read_len]; names: uint8 [n, k] (k characters each, no NUL) instead of the seven-digit numbers.
+    tid: int32 [n] reference of every read (default 0); refs: [(name, length), ...] for more than one @SQ."""
     n = len(pos)
     nb = (read_len + 1) // 2
     name_len = 8 if names is None else names.shape[1] + 1     # fixed-width names: 7 digits (or the caller's characters) + NUL
@@ -115,7 +117,7 @@ def write_bam_fast(path, pos, flag, seq_packed, read_len, ref_name="ref", ref_le
         a = np.ascontiguousarray(arr, dt).view(np.uint8).reshape(n, -1)
         rec[:, col:col + a.shape[1]] = a
     put(0, np.full(n, rec_len), "<i4")
-    put(4, np.zeros(n), "<i4")                      # refID
+    put(4, np.zeros(n) if tid is None else tid, "<i4")     # refID
     put(8, pos, "<i4")
     rec[:, 12] = name_len
     rec[:, 13] = 60
@@ -146,10 +148,13 @@ def write_bam_fast(path, pos, flag, seq_packed, read_len, ref_name="ref", ref_le
     s0 = 36 + name_len + 4
     rec[:, s0:s0 + nb] = seq_packed
     rec[:, s0 + nb:s0 + nb + read_len] = qual
-    text = "@HD\tVN:1.6\tSO:coordinate\n@SQ\tSN:%s\tLN:%d\n" % (ref_name, ref_len)
-    tb, nmb = text.encode(), ref_name.encode() + b"\0"
-    head = (b"BAM\1" + struct.pack("<i", len(tb)) + tb + struct.pack("<i", 1) + struct.pack("<i", len(nmb)) + nmb +
-            struct.pack("<i", ref_len))
+    refs = refs or [(ref_name, ref_len)]
+    text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join("@SQ\tSN:%s\tLN:%d\n" % r for r in refs)
+    tb = text.encode()
+    head = b"BAM\1" + struct.pack("<i", len(tb)) + tb + struct.pack("<i", len(refs))
+    for name, ln in refs:
+        nmb = name.encode() + b"\0"
+        head += struct.pack("<i", len(nmb)) + nmb + struct.pack("<i", ln)
     block = 0xFF00
     per = max(1, block // (4 + rec_len))            # whole records per block, as htslib cuts them
     with open(path, "wb" if part[0] else "ab") as fh:

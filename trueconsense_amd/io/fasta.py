@@ -23,3 +23,22 @@ def read_first_record(path):
 
 def first_length(path):
     return len(read_first_record(path)[1])
+
+
+def read_records(path):
+    """-> [(id, sequence), ...] of every record, in file order (ids as read_first_record gives them)."""
+    out, rid, chunks = [], None, []
+    with open(path) as fh:
+        for line in fh:
+            if line.startswith(">"):
+                if rid is not None:
+                    out.append((rid, "".join(chunks)))
+                parts = line[1:].split(None, 1)
+                rid, chunks = (parts[0] if parts else ""), []
+            elif rid is not None:
+                chunks.append(line.strip())
+    if rid is not None:
+        out.append((rid, "".join(chunks)))
+    if not out:
+        raise ValueError("%s holds no FASTA record" % path)
+    return out
