@@ -51,7 +51,7 @@ def entries_for(reads, positions, flag_filter=0x4 | 0x100 | 0x200 | 0x400, ignor
                         e = np.zeros(1, ENT)[0]
                         e["qual"] = (int(qual[qo[i] + qpos]) if qual is not None else 255) if qpos < lq else 0
                         nb = nib(qpos)
-                        bits = nb | (0x10 if op in MATCH else 0)
+                        bits = nb | (0x10 if op in MATCH and qpos < lq else 0)
                         first = NT[nb] if op in MATCH else (("<" if rev else ">") if op == 3 else "*")
                         if first == "=":
                             first = "," if rev else "."

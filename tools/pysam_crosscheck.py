@@ -68,6 +68,28 @@ def cases():
                       "tlen": -(mate + 30 - start)})
     pairs.sort(key=lambda r: r["pos"])
     out.append(("overlapping mates (ignore_overlaps)", ss.reads_from_spec({"reads": pairs}), 600, [214, 215, 216]))
+    # mates whose matched bases on the column lie beyond their SEQ ('*', or shorter than the CIGAR): modelled as no base for the
+    # overlap tweak; htslib reads past SEQ there, so this is the case that pins (or refutes) the rule
+    rng = np.random.default_rng(9)
+    short = []
+    for k in range(300):
+        start = 100 + int(rng.integers(0, 6))
+        mate = start + int(rng.integers(0, 8))
+        seq1 = "".join("ACGT"[int(x)] for x in rng.integers(0, 4, 20))
+        seq2 = seq1[mate - start:] + "".join("ACGT"[int(x)] for x in rng.integers(0, 4, mate - start))
+        cut = int(rng.integers(0, 12))                     # 0: SEQ '*'; else the first `cut` bases only
+        if rng.random() < 0.5:
+            seq2 = seq2[:cut] if cut else "*"
+        else:
+            seq1 = seq1[:cut] if cut else "*"
+        name = "short%d" % k
+        q1, q2 = int(rng.integers(10, 41)), int(rng.integers(10, 41))
+        short.append({"pos": start, "flag": 99, "cigar": "20M", "seq": seq1, "qual": [q1] * (0 if seq1 == "*" else len(seq1)), "name": name,
+                      "mtid": 0, "mpos": mate, "tlen": mate + 20 - start})
+        short.append({"pos": mate, "flag": 147, "cigar": "20M", "seq": seq2, "qual": [q2] * (0 if seq2 == "*" else len(seq2)), "name": name,
+                      "mtid": 0, "mpos": start, "tlen": -(mate + 20 - start)})
+    short.sort(key=lambda r: r["pos"])
+    out.append(("overlapping mates without SEQ / with a short SEQ", ss.reads_from_spec({"reads": short}), 400, [108, 110, 112, 115]))
     return out
 
 

@@ -20,6 +20,9 @@
 //                        itself when both mates have a base there; and — a mate whose token is a deletion / ref-skip is
 //                        tested on the quality of its NEXT query base (htslib's qpos) — on that base's reference position
 //                        when it is a matched base, for which the other mate is probed there (tcmi_probe).
+//                        A matched base that lies beyond the read's SEQ (SEQ '*', or shorter than the CIGAR says) is no base
+//                        for the tweak: a modelled choice (the oracle, the probe and the device entries' bit 0x10 make it too);
+//                        htslib reads past SEQ at such a position, so parity there is unpinned.
 #include <algorithm>
 #include <cstring>
 #include <functional>
@@ -73,7 +76,7 @@ struct Entry {
     uint16_t flag;
     uint8_t qual;               // base quality pysam tests: at the column's query position, or — deletion / ref-skip tokens — of the next base
     uint8_t base;               // 4-bit code of that base
-    bool on_base;               // the token's first character is a base of this read sitting on the column
+    bool on_base;               // the token's first character is a base of this read sitting on the column (a matched op, within SEQ)
     int64_t idx = -1;           // the read (for probes): index in the caller's arrays / compacted index on the device
     int32_t qref = -1;          // !on_base: reference position of the matched base whose quality is tested, or -1: that base is
                                 // not a matched one (inserted, clipped, beyond SEQ) and no overlap tweak can reach it
@@ -440,7 +443,7 @@ static int modal_tokens_impl(const tcmi_reads *r, const tcmi_layout &lay, int32_
                         Entry e;
                         e.key = 0;
                         e.qual = (uint8_t)q;
-                        e.on_base = is_match(op);
+                        e.on_base = is_match(op) && qpos < lq;  // (a matched base beyond SEQ is no base for the overlap tweak)
                         e.base = (uint8_t)(qpos < lq ? ((qpos & 1) ? (s[qpos >> 1] & 0xF) : (s[qpos >> 1] >> 4)) : 15);
                         e.idx = i;
                         e.qref = -1;

@@ -1145,7 +1145,7 @@ __global__ __launch_bounds__(PB) void ins_entries_kernel(InsArgs a)
                 tcmi_dev_entry e;
                 e.qual = (uint8_t)(qpos < lq ? byte_at(qual + qpos) : 0u);
                 const uint32_t nib = qpos < lq ? nib_at(v.seq, (int32_t)qpos) : 15u;
-                e.bits = (uint8_t)(nib | (is_match(op) ? 0x10u : 0u));
+                e.bits = (uint8_t)(nib | (is_match(op) && qpos < lq ? 0x10u : 0u));   // 0x10: a base on the column (within SEQ)
                 // first character: "=ACMGRSVTWYHKDBN", '=' prints as '.' / ',' by strand; '*' for a deleted base, '>' '<' for a skip
                 const char *NT = "=ACMGRSVTWYHKDBN";
                 char first = is_match(op) ? NT[nib] : (op == 3 ? (rev ? '<' : '>') : '*');
@@ -2011,7 +2011,8 @@ extern "C" int tcmi_ins_entries_rebase(void *entries, int64_t n_entries, int64_t
     if (n_entries < 0 || (n_entries > 0 && !entries) || long_base < 0) return tcmi_fail(nullptr, TCMI_E_ARG, "bad argument");
     tcmi_dev_entry *e = static_cast<tcmi_dev_entry *>(entries);
     for (int64_t i = 0; i < n_entries; ++i)
-        if ((e[i].bits & 0x40) && !(e[i].bits & 0x80)) {        // the key says where the insertion's bases lie: bits 8-39
+        if (e[i].key && (e[i].bits & 0x40) && !(e[i].bits & 0x80)) {   // the key says where the insertion's bases lie: bits 8-39
+                                                                        // (key 0: no token; the kernel wrote nothing else there)
             const uint64_t at = ((e[i].key >> 8) & 0xFFFFFFFFull) + (uint64_t)long_base;
             if (at > 0xFFFFFFFFull) return tcmi_fail(nullptr, TCMI_E_UNSUPPORTED, "more than 4 GiB of long insertions on the candidate columns");
             e[i].key = (e[i].key & ~(0xFFFFFFFFull << 8)) | (at << 8);

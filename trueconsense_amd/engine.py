@@ -412,9 +412,9 @@ DEFAULT_MAX_DEPTH = 8000
 def modal_tokens(reads, positions, min_base_quality=DEFAULT_MIN_BASE_QUALITY, flag_filter=DEFAULT_FLAG_FILTER,
                  ignore_orphans=True, max_depth=DEFAULT_MAX_DEPTH, ignore_overlaps=True, layout=None):
     """For each 1-based position: (modal upper-cased token or None, n_tokens) under pysam's default pileup arguments
-    (Events.py:66).  Raises TcmiError(E_UNSUPPORTED) where overlapping mates meet a deletion on the column (the one case of
-    pysam's overlap handling that is not modelled).  layout = (shift, slot_len): positions on a contig layout's axis
-    (tcmi_modal_tokens_layout)."""
+    (Events.py:66).  Overlapping mates with a deletion / ref-skip on the column are resolved too: the sweep probes the other mate
+    on the next query base's reference position itself, so status bit 1 never comes back from it (the check below is a guard).
+    layout = (shift, slot_len): positions on a contig layout's axis (tcmi_modal_tokens_layout)."""
     positions = np.ascontiguousarray(sorted(int(p) for p in positions), np.int64)
     n = len(positions)
     if n == 0:
