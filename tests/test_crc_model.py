@@ -1,4 +1,4 @@
-"""The algebra of the CRC-32 that bgzf_copy takes while it flushes a block's bytes (csrc/bgzf_decode.hip), restated in
+"""The algebra of the CRC-32 that bgzf_copy takes while it flushes a block's bytes (csrc/bgzf_copy.hip), restated in
 Python and compared with zlib.crc32: the CRC in its linear form (register starts at 0, the standard's all-ones start = the block's
 first four bytes inverted, zero bytes in front of a message change nothing), per-lane COLUMNS of the 2 KiB segments
 (acc = later_2K(acc) ^ crc(column's 32 bytes), slicing by 4), the pairwise join of the 64 columns, the move past the tail, and the

@@ -3,10 +3,10 @@
 #   gpu_ab.sh tests [files...]               the decoder's and the packer's GPU tests, default build (first thing in a call)
 #   gpu_ab.sh inflate KINDS LIB...           decoder kernel times (tools/inflate_time.py) per file kind ("headline,hard,real") and build, twice
 #   gpu_ab.sh bench REPS LIB...              the bench's headline legs per build
-#   gpu_ab.sh env VAR REPS VALUE...          ... per value of an environment variable (GPU_MAX_HW_QUEUES, TCMI_TEAM_BYTES, ...)
+#   gpu_ab.sh env VAR REPS VALUE...          ... per value of an environment variable (GPU_MAX_HW_QUEUES, TCMI_READ_THREADS, ...)
 #   gpu_ab.sh ctxopt KEY REPS VALUE...       ... per value of a context option (tcmi_ctx_set_option: mid_wait, prefix_kernels, ...)
 #   gpu_ab.sh args REPS "ARGS"...            ... per set of bench flags ("--gpu-streams 3" "--gpu-streams 8": contexts; "--decoders 4 --gpu-streams 6")
-#   gpu_ab.sh inflate-env VAR KINDS VALUE... decoder kernel times per value of an environment variable (TCMI_SYM_WINDOW, TCMI_SYM_BLOCKS, ...)
+#   gpu_ab.sh inflate-env VAR KINDS VALUE... decoder kernel times per value of an environment variable (TCMI_SYM_WINDOW, ...)
 #   gpu_ab.sh stamps KINDS LIB...            phase clocks of bgzf_symbols / bgzf_copy (tools/inflate_stamps.py; builds with -DTCMI_COPY_PHASES for bgzf_copy's)
 # LIB: "default" = trueconsense_amd/lib/libtcmi.so, else trueconsense_amd/lib/var/lib<LIB>.so (tools/build_variant.sh NAME "flags";
 # libbase.so: a copy of the build before the change under test).  Extra bench flags: BENCH_ARGS="--gpu-streams 6".

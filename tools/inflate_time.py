@@ -1,4 +1,4 @@
-# kernel times of the device BGZF decoder (bgzf_symbols + bgzf_copy, or bgzf_inflate under TCMI_INFLATE_LEGACY=1), from HIP
+# kernel times of the device BGZF decoder (bgzf_symbols + bgzf_copy), from HIP
 # events, single stream: python3 tools/inflate_time.py [headline|hard|real] [n_reads]
 # (real: distinct names and qualities drawn like an Illumina run's — 3.3 : 1, what samtools writes for real data)
 import os, sys, time, tempfile, numpy as np

@@ -5,7 +5,7 @@
 // The host only reads the file, walks the gzip member headers (18 bytes per block) and inflates the first block(s) far
 // enough to parse the BAM header; the compressed bytes (a few MB .. tens of MB) cross PCIe once.
 //
-//   (bgzf_decode.hip)  bgzf_symbols + bgzf_copy: the compressed blocks -> the inflated stream and every block's record starts
+//   (bgzf_symbols.hip, bgzf_copy.hip)  bgzf_symbols + bgzf_copy: the compressed blocks -> the inflated stream and every block's record starts
 //                  (bgzf_copy also takes every block's CRC-32 against its trailer while it flushes the bytes: no pass of its own)
 //   rec_compact    per-block record lists -> one dense array of record offsets (block scan + copy)
 //

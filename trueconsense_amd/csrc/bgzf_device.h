@@ -1,6 +1,30 @@
 // bgzf_device.h — what the device BGZF decoder's translation units share (bam_device.hip: host side, CRC-32, record index;
-// bgzf_decode.hip: the decode kernels): block descriptors, status words, Huffman table entries and the table builder.
+// bgzf_symbols.hip, bgzf_copy.hip: the decode kernels): block descriptors, status words, Huffman table entries and the table
+// builder — and the contract between the two kernels: the token format, the stamp buffer, their launch functions.
 // Wire format: SAM spec §4.1 (BGZF), RFC 1951 (DEFLATE); pysam / htslib's role for indexing.py:19,96-100.
+//
+// DEVICE: the BGZF blocks of a BAM file -> the inflated BAM byte stream + the record starts of every block, in two kernels:
+//
+//   bgzf_symbols   Huffman symbols -> tokens.  A block's symbols are decoded by 32 lanes (two blocks per workgroup; 64 when a
+//                  payload exceeds 4 KB: one block per workgroup, staged a window at a time beyond 16 KB), speculatively in parallel.
+//   bgzf_copy      tokens -> bytes: the LZ77 copies through an LDS ring of the recent output, the chain of BAM records, the flush —
+//                  and the block's CRC-32 against its trailer, taken from the ring while a segment is flushed.
+//
+// Why two kernels.  A deflate stream is serial twice over: the position of symbol k + 1 is known only when symbol k is decoded,
+// and a match may copy what the previous match produced.  Round 2's one-kernel decoder walked both chains in one wavefront, one
+// symbol at a time: ~60 wave-instructions per symbol, all of them issued for a single useful lane, and the kernel was bound by
+// instruction issue.  bgzf_symbols cuts the first chain into pieces that 32 or 64 lanes decode at once (its file says how),
+// bgzf_copy takes the second 64 tokens at a time (its file).  What passes between them is the token array:
+//
+// Tokens (32 bits): literal 1<<31 | byte — or two literals in one token, 1<<31 | 1<<24 | byte | next byte << 8: a lane whose symbol is a
+// literal of at most nine bits takes the next code in the same round if that is such a literal too and starts in the same stretch
+// of bits (meeting points stay round starts; literal-heavy chunks are the ones whose lanes take longest) —; match len (9 bits) | (dist - 1) << 9; raw 1<<30 | len << 17 | offset of the bytes from
+// the block's payload start (a stored deflate block, in pieces of <= 8 191 bytes).  Block b's tokens lie in order at
+// BlockDesc::tok, n_tok[b] of them; two-literal tokens are written by bgzf_symbols<1, *> only and read by bgzf_copy<true, *> only.
+// A launch takes a range of the file's blocks and the token array's base: a file whose tokens do not fit the context's scratch is
+// decoded a batch of blocks at a time (bam_device.hip: decode_enqueue).
+//
+// Bit / byte work, bound by instruction issue and the LDS pipe, not by HBM and not a contraction: no MFMA.
 #pragma once
 #include "tcmi_internal.h"
 
@@ -177,10 +201,19 @@ __device__ __forceinline__ bool build_table(const uint8_t *lens, int n, uint16_t
     return uni(ok ? 1u : 0u) != 0;
 }
 
+// ---- between bgzf_symbols and bgzf_copy: the tokens (see the head of this file) ----------------------------------------------------
+constexpr uint32_t TOK_LIT = 1u << 31, TOK_RAW = 1u << 30;
+constexpr uint32_t TOK_LIT2 = 1u << 24;              // a literal token that carries TWO bytes (the second in bits 8 - 15): bits 24 - 25 = literals - 1
+constexpr uint32_t RAW_PIECE = 8191;
+
+// ---- the stamp buffer (diagnostic, TCMI_INFLATE_STAMPS; tools/inflate_stamps.py reads it): 16 words per block and kernel, bgzf_symbols'
+// for all the launch's blocks first, then bgzf_copy's; s_memtime at the phase boundaries and a few counters.  Null: no stamps.
+#define TCMI_STAMP(buf_, blk_, k_) do { if (buf_) { if ((threadIdx.x & 63) == 0) (buf_)[(size_t)(blk_) * 16 + (k_)] = __builtin_amdgcn_s_memtime(); } } while (0)
+#define TCMI_STAMP_ADD(buf_, blk_, k_, v_) do { if (buf_) { if ((threadIdx.x & 63) == 0) (buf_)[(size_t)(blk_) * 16 + (k_)] += (v_); } } while (0)
 
 } // namespace
 
-// bgzf_decode.hip: compressed file + block table in HBM -> inflated stream, record starts per block, a status word per block
+// bgzf_symbols.hip / bgzf_copy.hip: compressed file + block table in HBM -> inflated stream, record starts per block, a status word per block
 // (everything on ctx->stream; the arrays are the caller's, sized as bam_device.hip's decode_on_device sizes them)
 struct tcmi_bgzf_decode_args {
     const uint8_t *d_file;          // compressed file, 16-byte aligned, >= 4 KiB of slack behind it
@@ -202,4 +235,10 @@ struct tcmi_bgzf_decode_args {
     int scratch_div = 1;            // (tests) a lane of bgzf_symbols may park 1 / scratch_div of its share of the token scratch: overflowing lanes send their block through pass B
     int short_tokens;               // the file compresses less than ~12 : 1 (many short matches): bgzf_copy's variant with teams; 2: less than ~4 : 1: ... and short far matches finished in the set-up
 };
-int tcmi_bgzf_decode_launch(tcmi_ctx *ctx, const tcmi_bgzf_decode_args &a);
+int tcmi_bgzf_decode_launch(tcmi_ctx *ctx, const tcmi_bgzf_decode_args &a);          // (bgzf_copy.hip) both kernels, in order
+// Its two halves, on ctx->stream, for the launch's nb blocks from b_first on.  `stamps`: that kernel's part of the stamp buffer, or
+// null; `report`: a line on stderr about the variant chosen and how many workgroups of it a compute unit holds (diagnostic).
+// bgzf_symbols.hip: *two_literals = the variant chosen may have written tokens of two literals
+int tcmi_bgzf_symbols_launch(tcmi_ctx *ctx, const tcmi_bgzf_decode_args &a, size_t b_first, size_t nb, uint64_t *stamps, bool report, bool *two_literals);
+// bgzf_copy.hip: two_literals as bgzf_symbols_launch said
+int tcmi_bgzf_copy_launch(tcmi_ctx *ctx, const tcmi_bgzf_decode_args &a, size_t b_first, size_t nb, uint64_t *stamps, bool report, bool two_literals);

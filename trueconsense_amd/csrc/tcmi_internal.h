@@ -216,7 +216,7 @@ struct tcmi_ctx {
     int split_sub = 0;
     std::vector<tcmi_ctx *> helpers;
     // ... started one behind the other: a sub-range's first inflate kernel waits for the bgzf_symbols of the sub-range in front (an event), so
-    // that the sub-ranges run skewed — symbols of k + 1 under copy of k under pack of k - 1 — instead of in step (bgzf_decode.hip:
+    // that the sub-ranges run skewed — symbols of k + 1 under copy of k under pack of k - 1 — instead of in step (bgzf_copy.hip:
     // tcmi_bgzf_decode_launch records `ev_after_sym` and calls `after_sym` once per decode)
     int sym_scratch_div = 1;         // option "sym_scratch_div" (tests): bgzf_symbols' lanes park 1 / n of their share before they overflow (pass B)
     int h2d_pieces = 0;              // option "h2d_pieces": 0 / -1 = one copy (default), n = n pieces
