@@ -1,5 +1,5 @@
 """Test infrastructure: the 48-byte insert-candidate entries of include/tcmi.h (TCMI_INS_ENTRY_BYTES; csrc/tcmi_internal.h
-tcmi_dev_entry, written on the device by pack_device.hip's ins_entries_kernel), restated in plain Python from flat read arrays — so
+tcmi_dev_entry, written on the device by ins_entries.hip's ins_entries_kernel), restated in plain Python from flat read arrays — so
 that the exchange of configs[4] (distributed.consensus_split_bamfile: pieces per rank, concatenated per column in rank order, voted on
 by tcmi_modal_from_entries) can be tested on a box without a GPU, against the oracle's own vote (oracle/tc_oracle.py region_tokens,
 which follows pysam's default region pile-up behind Events.py:47-82)."""

@@ -23,6 +23,27 @@ void *tcmi_ctx_pinned(tcmi_ctx *ctx, size_t bytes)
     return ctx->h_pin;
 }
 
+int tcmi_arena_reserve(tcmi_ctx *ctx, size_t bytes)
+{
+    tcmi_dev_arena &A = ctx->dev_arena;
+    A.used = 0;
+    ++ctx->arena_epoch;                         // whatever lived in the arena is gone
+    if (A.cap >= bytes) return TCMI_OK;
+    if (A.base) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(A.base); A.base = nullptr; A.cap = 0; }
+    const size_t want = bytes + bytes / 8 + (1 << 20);
+    if (hipMalloc((void **)&A.base, want) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "hipMalloc(%zu) for the pack scratch failed", want);
+    A.cap = want;
+    return TCMI_OK;
+}
+
+void *tcmi_arena_take(tcmi_ctx *ctx, size_t bytes)
+{
+    tcmi_dev_arena &A = ctx->dev_arena;
+    const size_t at = tcmi_align256(A.used);
+    A.used = at + bytes;
+    return A.base + at;
+}
+
 int tcmi_fail(tcmi_ctx *ctx, int code, const char *fmt, ...)
 {
     char buf[1024];
@@ -172,8 +193,7 @@ int tcmi_ctx_destroy(tcmi_ctx *c)
     free_ws(c);
     tcmi_upload_scratch_free(c->upload_scratch);
     c->upload_scratch = nullptr;
-    tcmi_dev_arena_free(c->dev_arena);
-    c->dev_arena = nullptr;
+    if (c->dev_arena.base) (void)hipFree(c->dev_arena.base);
     if (c->d_lay) (void)hipFree(c->d_lay);
     c->d_lay = nullptr;
     for (auto &b : c->blob_pool) (void)hipFree(b.p);

@@ -431,7 +431,6 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
     const size_t nb = f->blocks.size(), nb_own = ranged ? (size_t)own : nb;
     D.nb = nb; D.nb_own = nb_own;
     if (nb == 0) return TCMI_OK;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     // bounds on the records for the arena: a record takes at least 36 bytes of the stream; reserve for records of >= 64 bytes
     // (block_size + 32 fixed bytes + name + CIGAR + SEQ + QUAL of a 15-base read) — the arena cannot grow under live data
     D.max_rec = f->inflated / 36 + 16;
@@ -454,22 +453,23 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
         tok_words = std::max(tok_words, f->tok_total - at);
         batch_at.push_back(nb);
     }
-    const size_t b_file = resident ? 256 : al(f->cap), b_desc = al(nb * sizeof(BlockDesc)), b_out = al(f->inflated + 128),
-                 b_slot = al(nb * (size_t)MAX_REC_PER_BLOCK * 4), b_small = al(nb * 4) * 5 + al(nb * 8) + al(nb * 512) + 256,
-                 b_tok = al(tok_words * 4 + 256);
+    const size_t b_nb4 = tcmi_align256(nb * 4), b_nb8 = tcmi_align256(nb * 8);         // one 4-byte / 8-byte word per block
+    const size_t b_file = resident ? 256 : tcmi_align256(f->cap), b_desc = tcmi_align256(nb * sizeof(BlockDesc)),
+                 b_out = tcmi_align256(f->inflated + 128), b_slot = tcmi_align256(nb * (size_t)MAX_REC_PER_BLOCK * 4),
+                 b_small = b_nb4 * 5 + b_nb8 + tcmi_align256(nb * 512) + 256, b_tok = tcmi_align256(tok_words * 4 + 256);
     D.b_rest = rest_bytes(D.guess_rec, nb);
-    if (!tcmi_arena_reserve_take(ctx, b_file + b_desc + b_out + b_slot + b_small + b_tok + D.b_rest + 16 * 256, 0)) return TCMI_E_NOMEM;
+    if (tcmi_arena_reserve(ctx, b_file + b_desc + b_out + b_slot + b_small + b_tok + D.b_rest + 16 * 256)) return TCMI_E_NOMEM;
     uint8_t *d_file = (uint8_t *)tcmi_arena_take(ctx, b_file);
     D.d_desc = (BlockDesc *)tcmi_arena_take(ctx, b_desc);
     D.d_out = (uint8_t *)tcmi_arena_take(ctx, b_out);
     D.d_slot = (uint32_t *)tcmi_arena_take(ctx, b_slot);
-    D.d_nrec = (uint32_t *)tcmi_arena_take(ctx, al(nb * 4));
-    D.d_over = (int32_t *)tcmi_arena_take(ctx, al(nb * 4));
-    D.d_stat = (uint32_t *)tcmi_arena_take(ctx, al(nb * 4));
-    D.d_first = (uint32_t *)tcmi_arena_take(ctx, al(nb * 4));
-    D.d_base = (uint64_t *)tcmi_arena_take(ctx, al(nb * 8));
+    D.d_nrec = (uint32_t *)tcmi_arena_take(ctx, b_nb4);
+    D.d_over = (int32_t *)tcmi_arena_take(ctx, b_nb4);
+    D.d_stat = (uint32_t *)tcmi_arena_take(ctx, b_nb4);
+    D.d_first = (uint32_t *)tcmi_arena_take(ctx, b_nb4);
+    D.d_base = (uint64_t *)tcmi_arena_take(ctx, b_nb8);
     D.d_total = (unsigned long long *)tcmi_arena_take(ctx, 256);
-    uint32_t *d_ntok = (uint32_t *)tcmi_arena_take(ctx, al(nb * 4));
+    uint32_t *d_ntok = (uint32_t *)tcmi_arena_take(ctx, b_nb4);
     uint32_t *d_tok = (uint32_t *)tcmi_arena_take(ctx, b_tok);
 
     // Option "h2d_pieces" (off by default): many compressed bytes from the host (a rank's range of a large file: 48 MB for 6.25 M reads, a
@@ -570,7 +570,6 @@ int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, 
     const size_t nb = D.nb, nb_own = D.nb_own;
     const bool ranged = D.ranged;
     if (nb == 0) { Dout->d_out = nullptr; Dout->d_rec = nullptr; Dout->d_desc = nullptr; Dout->n = 0; return TCMI_OK; }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     uint8_t *d_out = D.d_out;
     BlockDesc *d_desc = D.d_desc;
     uint32_t *d_slot = D.d_slot, *d_nrec = D.d_nrec, *d_stat = D.d_stat, *d_first = D.d_first;
@@ -637,7 +636,7 @@ int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, 
     const size_t need_rest = rest_bytes(n, nb);
     if (need_rest > b_rest)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: %zu very short records need more device scratch than was reserved: host reader", f->path.c_str(), n);
-    uint64_t *d_rec = (uint64_t *)tcmi_arena_take(ctx, al(n * 8 + 8));
+    uint64_t *d_rec = (uint64_t *)tcmi_arena_take(ctx, tcmi_align256(n * 8 + 8));
     tcmi_prof_begin(ctx, TCMI_K_RECORDS);
     if (n) hipLaunchKernelGGL(rec_compact, dim3((unsigned)nb_own), dim3(256), 0, ctx->stream, d_desc, d_slot, d_nrec, d_base, d_rec);
     tcmi_prof_end(ctx, TCMI_K_RECORDS);

@@ -297,7 +297,7 @@ int emit_modal(std::vector<std::vector<Entry>> &entries, const std::vector<std::
 
 } // namespace
 
-// Entries produced on the device (pack_device.hip, ins_entries_kernel) -> the same finalisation as the host sweep.
+// Entries produced on the device (ins_entries.hip, ins_entries_kernel) -> the same finalisation as the host sweep.
 int tcmi_modal_from_dev_entries(int32_t n_pos, const tcmi_dev_entry *ents, const int64_t *ent_off, const int32_t *ent_cnt,
                                 int32_t min_base_quality, int64_t max_depth, int ignore_overlaps, const tcmi_prober *prober, char *tokens,
                                 int64_t tokens_cap, int64_t *token_off, int64_t *n_tokens, int32_t *status_flags, const uint8_t *long_text,
@@ -345,6 +345,34 @@ int tcmi_modal_from_dev_entries(int32_t n_pos, const tcmi_dev_entry *ents, const
     const int rc = emit_modal(entries, long_tokens, min_base_quality, max_depth, ignore_overlaps, prober, tokens, tokens_cap, token_off, n_tokens, &status);
     if (status_flags) *status_flags = status;
     return rc;
+}
+
+// The vote over entries gathered from several read sets (tcmi_readset_ins_entries of every rank): per column the concatenation, in file
+// order, of the pieces the ranks sent; tcmi_ins_entries_rebase moved the text offsets of piece k's long insertions behind the texts of
+// the pieces in front of it (their texts concatenated in `long_text`).
+extern "C" int tcmi_modal_from_entries(int32_t n_pos, void *entries, const int64_t *ent_off, int32_t min_base_quality, int64_t max_depth,
+                                       int ignore_overlaps, const uint8_t *long_text, int64_t long_bytes, char *tokens, int64_t tokens_cap,
+                                       int64_t *token_off, int64_t *n_tokens, int32_t *status_flags)
+{
+    if (n_pos < 0 || !ent_off || (n_pos > 0 && (!tokens || !token_off || !n_tokens))) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    std::vector<int32_t> cnt((size_t)std::max(n_pos, 0));
+    for (int32_t k = 0; k < n_pos; ++k) cnt[(size_t)k] = (int32_t)(ent_off[k + 1] - ent_off[k]);
+    return tcmi_modal_from_dev_entries(n_pos, static_cast<const tcmi_dev_entry *>(entries), ent_off, cnt.data(), min_base_quality, max_depth, ignore_overlaps,
+                                       nullptr, tokens, tokens_cap, token_off, n_tokens, status_flags, long_text, (size_t)std::max<int64_t>(long_bytes, 0));
+}
+
+extern "C" int tcmi_ins_entries_rebase(void *entries, int64_t n_entries, int64_t long_base)
+{
+    if (n_entries < 0 || (n_entries > 0 && !entries) || long_base < 0) return tcmi_fail(nullptr, TCMI_E_ARG, "bad argument");
+    tcmi_dev_entry *e = static_cast<tcmi_dev_entry *>(entries);
+    for (int64_t i = 0; i < n_entries; ++i)
+        if (e[i].key && (e[i].bits & 0x40) && !(e[i].bits & 0x80)) {   // the key says where the insertion's bases lie: bits 8-39
+                                                                        // (key 0: no token; the kernel wrote nothing else there)
+            const uint64_t at = ((e[i].key >> 8) & 0xFFFFFFFFull) + (uint64_t)long_base;
+            if (at > 0xFFFFFFFFull) return tcmi_fail(nullptr, TCMI_E_UNSUPPORTED, "more than 4 GiB of long insertions on the candidate columns");
+            e[i].key = (e[i].key & ~(0xFFFFFFFFull << 8)) | (at << 8);
+        }
+    return TCMI_OK;
 }
 
 // the sweep; `lay`: reference t's reads sit at pos + shift on the one axis the positions are given in (no layout: reference 0 only)

@@ -1,22 +1,29 @@
 // pack_device.hip — DEVICE: BAM-native reads -> the bit-plane layout tally_planes.hip consumes.
 //
-// What the reference does per pileup token in Python (indexing.py:100-139: pileup membership, the token of every
-// covered position, parse_query_sequences' classification) is decided here per READ by HIP kernels, straight from
-// the arrays a BAM holds (SAM spec §4.2: pos, flag, l_seq, CIGAR words, 4-bit SEQ) — either as the flat arrays of
-// struct tcmi_reads copied to the device as they are, or from the inflated BAM byte stream itself (bam_device.hip):
+// What the reference does per pileup token in Python (indexing.py:100-139: pileup membership, the token of every covered position,
+// parse_query_sequences' classification) is decided here per READ by HIP kernels, straight from what a BAM holds (SAM spec §4.2: pos,
+// flag, l_seq, CIGAR words, 4-bit SEQ; pack_device.h: one read as the kernels see it).  Two chains of kernels fill the same read set.
 //
-//   pk_classify   one lane per read: does it pile up, reference span, CIGAR shape ([H][S]M[S][H] reads
-//                 are taken as they are, anything else is projected onto the reference), words it will occupy;
-//                 per-workgroup sums for the scan
+// The several-kernel packer (tcmi_pack_on_device): the flat arrays of struct tcmi_reads copied to the device as they are, or an inflated
+// BAM stream with its record index (bam_device.hip: files the one-sync packer declines); the host reads the totals back twice.
+//   pk_classify   one lane per read: does it pile up, reference span, CIGAR shape ([H][S]M[S][H] reads are taken as they
+//                 are, anything else is projected onto the reference), words it will occupy; per-workgroup sums for the scan
 //   pk_scan       exclusive scan of the per-workgroup sums (one workgroup)
 //   pk_scatter    compacted index of every kept read + its word offset (block scan + the scanned sums)
-//   pk_pack       one workgroup per run of consecutive kept reads: cuts it into chunks (window <= 768 positions,
-//                 <= 255 reads per lane, <= 8 stages that fill the tally kernel's LDS stage buffer), writes the chunk
-//                 records, ONE packed header word per read, the coverage runs (reads of equal position and length),
-//                 and per read the bases as {lo, hi} bit planes: 4-bit codes are classified eight at a time with
-//                 SWAR bit tricks (one-hot test, C|T and G|T planes, 3-step bit squeeze), CIGAR ops are walked by the
-//                 read's lane (M/=/X copy bit fields, D -> X events, insertions -> I events on the base before,
-//                 every covered position without an A/C/G/T base -> OTHER event)
+//   pk_pack       one workgroup per run of consecutive kept reads: cuts it into chunks (window <= 768 positions, <= 255 reads per lane,
+//                 <= 8 stages that fill the tally kernel's LDS stage buffer), writes the chunk records, ONE packed header word per read
+//                 and the coverage runs (reads of equal position and length)
+//   pk_planes     one lane per 32 bases: the bases as {lo, hi} bit planes — 4-bit codes classified eight at a time with SWAR bit tricks
+//                 (one-hot test, C|T and G|T planes, bit squeeze); a projected read has its CIGAR walked by its own lane (M/=/X copy
+//                 bit fields, D -> X events, insertions -> I events on the base before, every covered position without an A/C/G/T
+//                 base -> OTHER event)
+// The one-sync packer (tcmi_pack_fused_enqueue, _report, _finish): an inflated BAM stream as bgzf_copy left it, one workgroup per BGZF
+// block, queued from CAPACITIES so that the host waits once per file (the comment above pk_index says why it has this shape).
+//   pk_prefix     (files of very many blocks) prefix sums of the blocks' counts
+//   pk_index      the block's records: their place in the record index, classification as in pk_classify, the record chain across it
+//   pk_place      the chain check, the kept reads' entries and bit planes (pk_scatter's and pk_planes' work) at their final places
+//   pk_pack       as above, from the counts pk_place left on the device
+//   pk_report     totals and per-block verdicts into pinned host memory, behind whatever the caller queued behind the packer
 //
 // HBM-streaming byte / bit work: no MFMA.  Input 91 B + 20 B of offsets per 150-bp read, output 52 B.
 #include <algorithm>
@@ -27,93 +34,14 @@
 
 #include "tally_common.h"
 #include "bgzf_device.h"
+#include "pack_device.h"
 
 namespace {
 
 constexpr int PB = 256;                          // lanes per workgroup of every kernel here
 constexpr int PK_CMAX = 1024;                    // most reads one pk_pack workgroup takes
+constexpr int64_t PK_LONGEST = (int64_t)TCMI_F_MAXSTAGE * 400;     // reads in the longest chunk the balancing rule aims for: TCMI_F_MAXSTAGE stages of 400 reads
 constexpr uint32_t NIB = 0x11111111u;
-
-using PackSrc = tcmi_pack_src;
-
-struct ReadView {
-    int32_t tid, pos, l_seq;
-    uint32_t flag, n_cigar;
-    const uint8_t *cigar;       // n_cigar little-endian words, not necessarily aligned
-    const uint8_t *seq;         // ceil(l_seq / 2) bytes
-    bool bad;                   // inconsistent offsets / lengths
-    bool broken;                // ... of a BAM record (any record, mapped or not: the file is not a BAM file then)
-};
-
-__device__ inline uint32_t ld_u32(const uint8_t *p)
-{
-    uint32_t w;                                 // (the record fields of a BAM stream sit at any byte offset: one unaligned dword load)
-    __builtin_memcpy(&w, p, 4);
-    return w;
-}
-
-// a record of the inflated BAM stream, `rec` at its block_size field (any byte address)
-__device__ inline ReadView view_rec(const uint8_t *rec)
-{
-    ReadView v;
-    v.bad = false;
-    v.broken = false;
-    const uint8_t *r = rec + 4;                             // behind block_size
-    // the fixed fields in two loads at the record's own (any) byte address — unaligned access mode; twelve aligned dword loads
-    // and funnel shifts kept the kernel waiting on the address unit: every lane's record lies in a cache line of its own
-    uint32_t h[6];                                         // block_size, refID, pos, l_read_name|mapq|bin, n_cigar_op|flag, l_seq
-    __builtin_memcpy(h, r - 4, 16);
-    __builtin_memcpy(h + 4, r + 12, 8);
-    v.tid = (int32_t)h[1];
-    v.pos = (int32_t)h[2];
-    const uint32_t w2 = h[3], w3 = h[4];
-    const uint32_t l_name = w2 & 0xFFu;
-    v.n_cigar = w3 & 0xFFFFu;
-    v.flag = w3 >> 16;
-    v.l_seq = (int32_t)h[5];
-    // The record walk only checked block_size itself: the variable-length fields must fit into it (what bam_reader.cpp's
-    // "alignment record fields overrun block_size" refuses) — a forged l_seq or n_cigar_op would otherwise send the kernels
-    // that follow the CIGAR and the bases far behind the record, or behind the stream.
-    const uint32_t block_size = h[0];
-    const uint64_t need = 32ull + l_name + 4ull * v.n_cigar + ((uint64_t)(uint32_t)v.l_seq + 1) / 2 + (uint64_t)(uint32_t)v.l_seq;
-    v.bad = v.l_seq < 0 || l_name == 0 || need > block_size;
-    v.broken = v.bad;
-    if (v.bad) v.n_cigar = 0;
-    v.cigar = r + 32 + l_name;
-    v.seq = v.cigar + 4 * (size_t)v.n_cigar;
-    return v;
-}
-
-__device__ inline ReadView view(const PackSrc &s, int64_t i)
-{
-    ReadView v;
-    v.bad = false;
-    v.broken = false;
-    if (s.mode == 0) {
-        v.tid = s.tid ? s.tid[i] : 0;
-        v.pos = s.pos[i];
-        v.l_seq = s.l_qseq[i];
-        v.flag = s.flag[i];
-        const uint64_t c0 = s.cigar_off[i], c1 = s.cigar_off[i + 1], q0 = s.seq_off[i], q1 = s.seq_off[i + 1];
-        v.bad = c1 < c0 || c1 - c0 > 65535u || q1 < q0 || v.l_seq < 0 || (int64_t)(q1 - q0) < ((int64_t)v.l_seq + 1) / 2;
-        v.n_cigar = v.bad ? 0u : (uint32_t)(c1 - c0);
-        v.cigar = reinterpret_cast<const uint8_t *>(s.cigar + c0);
-        v.seq = s.seq + q0;
-    } else v = view_rec(s.stream + s.rec_off[i]);
-    return v;
-}
-
-__device__ inline uint32_t nib_at(const uint8_t *seq, int32_t q)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(seq + (q >> 1));
-    const uint32_t w = *reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3) >> ((a & 3) * 8);
-    return (q & 1) ? (w & 15u) : ((w >> 4) & 15u);
-}
-__device__ inline uint32_t byte_at(const uint8_t *p)
-{
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    return (*reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3) >> ((a & 3) * 8)) & 0xFFu;
-}
 
 // does the record carry a CG:B aux field (the real CIGAR of a read with more than 65 535 operations, SAM spec §4.2.2)?
 __device__ inline bool has_cg_tag(const uint8_t *aux, const uint8_t *end)
@@ -135,9 +63,6 @@ __device__ inline bool has_cg_tag(const uint8_t *aux, const uint8_t *end)
     }
     return false;
 }
-
-__device__ inline bool consumes_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-__device__ inline bool is_match(uint32_t op) { return op == 0 || op == 7 || op == 8; }
 
 // per-read word of pk_classify: len (10 bits, <= TCMI_D_MAXLEN) | projected << 10 | kept << 11 | y0 << 12
 constexpr uint32_t INFO_PROJ = 1u << 10, INFO_KEPT = 1u << 11;
@@ -191,13 +116,6 @@ __device__ inline uint2 block_scan2(uint2 v, uint2 *wave_tot /* LDS [PB / 64] */
 // its end; `longread`: left to tally_stream_kernel (a device-decoded stream only; from flat arrays PKF_LONG is raised instead)
 struct Classified { uint32_t word, nwords, len; unsigned long long alg; int32_t end; bool longread, slot_ovf; };
 
-// where reference `tid` starts on the one coordinate axis: without a contig layout reference 0 at the uniform shift (batched uploads),
-// with one its table entry (a handful of words, read through the scalar cache); < 0: the read does not pile up
-__device__ inline int32_t shift_of(const PackSrc &s, int32_t tid)
-{
-    if (s.n_lay == 0) return tid == 0 ? s.pos_shift : -1;
-    return tid >= 0 && tid < s.n_lay ? s.lay[tid] : -1;
-}
 __device__ inline int32_t slot_end_of(const PackSrc &s, int32_t tid) { return s.n_lay == 0 ? 0x7FFFFFFF : s.lay[s.n_lay + tid]; }
 
 // the kept reads' max end per reference (a contig layout): called by every lane of the wavefront; one atomic per reference the
@@ -309,7 +227,7 @@ __global__ __launch_bounds__(PB) void pk_classify(PackSrc s, uint32_t *info, uin
     const uint2 incl = block_scan2(make_uint2(word ? 1u : 0u, nwords), s_w);
     if (threadIdx.x == PB - 1) blk_sum[blockIdx.x] = incl;
     // algorithmic bytes and extent: per-workgroup partials that pk_scan folds (same-address atomics serialise in L2:
-    // 31 000 of them cost 0.39 ms)
+    // 31 000 of them cost 0.39 ms); the twin of the fold that ends pk_index
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         my_alg += (unsigned long long)__shfl_xor((long long)my_alg, d, 64);
@@ -461,29 +379,6 @@ __device__ inline void fetch32(const uint8_t *seq, int32_t l_seq, int32_t yy, in
     lo &= mask; hi &= mask; ok &= mask;
 }
 
-// htslib resolve_cigar2's peek at the last reference base of op k: is an insertion reported there?
-__device__ inline bool ins_after(const uint8_t *cg, uint32_t n, uint32_t k)
-{
-    if (k + 1 >= n) return false;
-    const uint32_t c2 = ld_u32(cg + 4 * (size_t)(k + 1)), op2 = c2 & 0xFu;
-    uint32_t tot = 0;
-    if (op2 == 1) {
-        tot = c2 >> 4;
-        for (uint32_t j = k + 2; j < n; ++j) {
-            const uint32_t c = ld_u32(cg + 4 * (size_t)j), o = c & 0xFu;
-            if (o == 1) tot += c >> 4;
-            else if (o != 6) break;
-        }
-    } else if (op2 == 6 && k + 2 < n) {
-        for (uint32_t j = k + 2; j < n; ++j) {
-            const uint32_t c = ld_u32(cg + 4 * (size_t)j), o = c & 0xFu;
-            if (o == 1) tot += c >> 4;
-            else if (consumes_ref(o)) break;
-        }
-    }
-    return tot > 0;
-}
-
 // 32 consecutive bases of a read that lies on the reference as it is ([H][S]M[S][H]): one unaligned 16-byte load (+ the byte behind
 // it for a read whose first aligned base sits in a low nibble) -> the pair {C|T, G|T} and the "is A/C/G/T" plane.
 // p: the byte that holds base y (= y0 + 32 q), odd: y is odd, have: bases of the pair the read really has (< 32: masked)
@@ -564,7 +459,7 @@ __device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals
                 if (ins) push_event(o, tot, (uint32_t)(gpos + x + oplen - 1) | TCMI_F_EV_I);
                 x += oplen;
             }
-            if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) y += oplen;
+            if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) y += oplen;     // (consumes_query, written out: the call changes pk_place's code)
         }
         flush_to(npair);
     }
@@ -581,10 +476,10 @@ __global__ __launch_bounds__(PB) void pk_pack(PackOut o, const int32_t *c_pos, c
     if (dev_slots > 0) {
         n_kept = (uint32_t)min(tot->n_kept, (unsigned long long)0xFFFFFFF0u);
         n_words = (uint32_t)min(tot->n_words, (unsigned long long)o.word_cap - 18ull);
-        int64_t C = 2048;
+        int64_t C = 2048;                                       // (the twin of tcmi_pack_on_device's rule: one shared function changes this kernel's code)
         if (dev_slots < (1ll << 30)) {
-            const int64_t longest = (int64_t)TCMI_F_MAXSTAGE * 400, nf = n_kept;
-            const int64_t k = max((int64_t)1, (nf + dev_slots * longest - 1) / (dev_slots * longest));
+            const int64_t nf = n_kept;
+            const int64_t k = max((int64_t)1, (nf + dev_slots * PK_LONGEST - 1) / (dev_slots * PK_LONGEST));
             C = max((int64_t)64, (nf + k * dev_slots - 1) / (k * dev_slots));
         }
         reads_per_wg = (int)min(C, (int64_t)PK_CMAX);
@@ -744,7 +639,7 @@ __global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const ui
     __syncthreads();
     const uint8_t *bytes = src.mode == 0 ? src.seq : src.stream;
     const uint32_t n_slots = (w_end - w_first) >> 1;
-    for (uint32_t k = tid; k < n_slots; k += PB) {
+    for (uint32_t k = tid; k < n_slots; k += PB) {                  // (the twin of pk_place's loop over its tile's places)
         const uint32_t ow = s_owner[k];
         if (ow == 0xFFFFu) continue;
         const int t = (int)(ow & 255u), q = (int)(ow >> 8);
@@ -916,6 +811,7 @@ __global__ __launch_bounds__(PB) void pk_index(FusedArgs a)
         tot_k += s_w[0].x; tot_w += s_w[0].y;
         __syncthreads();
     }
+    // (the twin of the fold that ends pk_classify: one shared function changes this kernel's code)
 #pragma unroll
     for (int dd = 32; dd >= 1; dd >>= 1) {
         my_alg += (unsigned long long)__shfl_xor((long long)my_alg, dd, 64);
@@ -1064,7 +960,7 @@ __global__ __launch_bounds__(PB) void pk_place(FusedArgs a)
         }
         __syncthreads();
         uint2 *dst = reinterpret_cast<uint2 *>(a.o.seq + 2u + w_first);                      // (word offsets are multiples of 4: 8-byte aligned)
-        for (uint32_t k = tid; k < (tile_w >> 1); k += PB) {
+        for (uint32_t k = tid; k < (tile_w >> 1); k += PB) {           // (the twin of pk_planes' loop: one shared function reorders this kernel's code)
             const uint32_t ow = s_owner[k];
             if (ow == 0xFFFFu) continue;
             const int tt = (int)(ow & 255u), q = (int)(ow >> 8);
@@ -1089,250 +985,56 @@ __global__ __launch_bounds__(PB) void pk_place(FusedArgs a)
     }
 }
 
-// ---- insert-candidate columns: every read of a column as an entry for the host's token vote (Events.py:47-82) -----------------
-// One lane per (candidate column, read that starts within TCMI_D_MAXLEN positions before it).  The lane applies the samtools
-// stepper's filters, finds the CIGAR op that covers the column and builds what pysam's get_query_sequences(add_indels=True)
-// would print for it as a packed 64-bit key (insert_tokens.cpp), with the quality pysam tests, the base, the mate fields and a
-// hash of the read name; the few thousand entries per column go to the host, which applies the rules that depend on the other
-// reads of the column (max_depth admission, overlapping mates, the vote).  The decoded reads themselves never leave the device.
-struct InsArgs {
-    PackSrc src;
-    const uint32_t *c_idx;
-    const int32_t *cols;            // [n_cand] 0-based columns
-    const int64_t *lo;              // [n_cand] first compacted read index to look at
-    const int64_t *off;             // [n_cand + 1] pair offsets: candidate k owns pairs [off[k], off[k+1])
-    tcmi_dev_entry *out;            // [off[n_cand]]: pair p's entry at out[p] — in file order; key 0: the read gives none on that column
-    int32_t n_cand;
-    uint32_t flag_filter;
-    int32_t ignore_orphans;
-    // insertions of more than 12 bases do not fit the entry's key: their bases (one 4-bit code per byte) go here, the key says where
-    uint8_t *long_text;
-    uint32_t *long_cursor;          // bytes taken
-    uint32_t long_cap;
-};
-
-
-__global__ __launch_bounds__(PB) void ins_entries_kernel(InsArgs a)
-{
-    const int64_t p = (int64_t)blockIdx.x * PB + threadIdx.x;
-    if (p >= a.off[a.n_cand]) return;
-    a.out[p].key = 0;                                           // (overwritten below if the read has a token on the column)
-    int k = 0;
-    while (k + 1 < a.n_cand && p >= a.off[k + 1]) ++k;          // (a handful of candidates)
-    const int64_t j = a.lo[k] + (p - a.off[k]);
-    const int32_t col = a.cols[k];
-    const uint32_t i = a.c_idx[j];
-    const ReadView v = view(a.src, i);
-    if (v.flag & a.flag_filter) return;
-    if (a.ignore_orphans && (v.flag & 0x1u) && !(v.flag & 0x2u)) return;
-    // the op that covers the column
-    int64_t x = v.pos, y = 0;
-    int64_t span = 0;
-    for (uint32_t c = 0; c < v.n_cigar; ++c) {
-        const uint32_t w = ld_u32(v.cigar + 4 * (size_t)c);
-        if (consumes_ref(w & 0xFu)) span += w >> 4;
-    }
-    if (col < v.pos || col >= v.pos + span) return;
-    for (uint32_t c = 0; c < v.n_cigar; ++c) {
-        const uint32_t w = ld_u32(v.cigar + 4 * (size_t)c), op = w & 0xFu;
-        const int64_t len = w >> 4;
-        if (consumes_ref(op)) {
-            if (col < x + len) {
-                const bool rev = v.flag & 0x10u;
-                const int32_t lq = v.l_seq;
-                const int64_t qpos = is_match(op) ? y + (col - x) : y;
-                const uint8_t *qual = v.seq + ((size_t)lq + 1) / 2;
-                tcmi_dev_entry e;
-                e.qual = (uint8_t)(qpos < lq ? byte_at(qual + qpos) : 0u);
-                const uint32_t nib = qpos < lq ? nib_at(v.seq, (int32_t)qpos) : 15u;
-                e.bits = (uint8_t)(nib | (is_match(op) && qpos < lq ? 0x10u : 0u));   // 0x10: a base on the column (within SEQ)
-                // first character: "=ACMGRSVTWYHKDBN", '=' prints as '.' / ',' by strand; '*' for a deleted base, '>' '<' for a skip
-                const char *NT = "=ACMGRSVTWYHKDBN";
-                char first = is_match(op) ? NT[nib] : (op == 3 ? (rev ? '<' : '>') : '*');
-                if (first == '=') first = rev ? ',' : '.';
-                // p->indel of htslib's resolve_cigar2 on the last reference base of the op
-                int64_t indel = 0;
-                if (col == x + len - 1 && c + 1 < v.n_cigar) {
-                    const uint32_t w2 = ld_u32(v.cigar + 4 * (size_t)(c + 1)), op2 = w2 & 0xFu;
-                    if (op2 == 2 && op != 2) {
-                        indel = -(int64_t)(w2 >> 4);
-                        for (uint32_t t = c + 2; t < v.n_cigar; ++t) { const uint32_t wt = ld_u32(v.cigar + 4 * (size_t)t); if ((wt & 0xFu) != 2) break; indel -= wt >> 4; }
-                    } else if (op2 == 1) {
-                        indel = w2 >> 4;
-                        for (uint32_t t = c + 2; t < v.n_cigar; ++t) {
-                            const uint32_t wt = ld_u32(v.cigar + 4 * (size_t)t), o = wt & 0xFu;
-                            if (o == 1) indel += wt >> 4; else if (o != 6) break;
-                        }
-                    } else if (op2 == 6 && c + 2 < v.n_cigar) {
-                        for (uint32_t t = c + 2; t < v.n_cigar; ++t) {
-                            const uint32_t wt = ld_u32(v.cigar + 4 * (size_t)t), o = wt & 0xFu;
-                            if (o == 1) indel += wt >> 4; else if (consumes_ref(o)) break;
-                        }
-                    }
-                }
-                uint64_t key = (1ull << 63) | (uint8_t)first;
-                if (indel > 12) {
-                    // does not fit the key: bits 8-39 where its bases start in the text buffer, bits 40-62 how many (bits |= 0x40;
-                    // 0x80: the buffer is full or the insertion absurdly long — the host sweep takes the BAM)
-                    e.bits |= 0x40;
-                    const uint32_t slot = indel < (1 << 23) ? atomicAdd(a.long_cursor, (uint32_t)indel) : a.long_cap;
-                    if (indel < (1 << 23) && (uint64_t)slot + (uint64_t)indel <= a.long_cap) {
-                        for (int64_t t = 1; t <= indel; ++t) {
-                            const int64_t q2 = qpos + t;
-                            a.long_text[slot + (uint32_t)(t - 1)] = (uint8_t)(q2 >= lq ? 15u : nib_at(v.seq, (int32_t)q2));
-                        }
-                        key |= ((uint64_t)slot << 8) | ((uint64_t)indel << 40);
-                    } else e.bits |= 0x80;
-                } else if (indel > 0) {
-                    key |= (1ull << 8) | ((uint64_t)indel << 10);
-                    bool any_eq = false;
-                    for (int64_t t = 1; t <= indel; ++t) {
-                        const int64_t q2 = qpos + t;
-                        const uint32_t nb = q2 >= lq ? 15u : nib_at(v.seq, (int32_t)q2);
-                        any_eq |= nb == 0;
-                        key |= (uint64_t)nb << (15 + 4 * (t - 1));
-                    }
-                    if (any_eq && rev) key |= 1ull << 14;
-                } else if (indel < 0) {
-                    key |= (2ull << 8) | ((uint64_t)(-indel) << 10);
-                }
-                e.key = key;
-                // mate fields and the name (behind block_size: refID 0, pos 4, l_read_name 8, ..., next_refID 20, next_pos 24, tlen 28, name 32)
-                const uint8_t *r = a.src.stream + a.src.rec_off[i] + 4;
-                const int32_t mtid = (int32_t)ld_u32(r + 20);
-                e.mpos = (int32_t)ld_u32(r + 24);
-                e.isize = (int32_t)ld_u32(r + 28);
-                if (mtid >= 0 && mtid != v.tid) e.bits |= 0x20;
-                const uint32_t l_name = ld_u32(r + 8) & 0xFFu;
-                uint64_t h = 1469598103934665603ull;
-                for (uint32_t t = 0; t + 1 < l_name; ++t) { h ^= byte_at(r + 32 + t); h *= 1099511628211ull; }
-                e.name_hash = h ? h : 1;
-                e.j = (uint32_t)j; e.pos = v.pos; e.end = (int32_t)(v.pos + span); e.l_qseq = lq; e.flag = (uint16_t)v.flag;
-                // a deletion / ref-skip token is tested on the quality of the next query base: a matched one? on which reference position
-                // (where the overlap tweak of a pair of mates can reach it: insert_tokens.cpp)
-                e.qref = -1;
-                if (!is_match(op) && qpos < lq) {
-                    int64_t xr = x + len;
-                    for (uint32_t t = c + 1; t < v.n_cigar; ++t) {
-                        const uint32_t wt = ld_u32(v.cigar + 4 * (size_t)t), o = wt & 0xFu;
-                        if (is_match(o)) { if ((wt >> 4) > 0 && xr <= INT32_MAX) e.qref = (int32_t)xr; break; }
-                        if ((o == 1 || o == 4) && (wt >> 4) > 0) break;
-                        if (consumes_ref(o)) xr += wt >> 4;
-                    }
-                }
-                a.out[p] = e;
-                return;
-            }
-            x += len;
-        }
-        if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) y += len;
-    }
-}
-
-// do the kept reads ascend by position?  (the packer also takes input with a few reads out of place; the range search below does not)
-__global__ __launch_bounds__(256) void ins_sorted_kernel(const int32_t *c_pos, int64_t nf, uint32_t *unsorted)
-{
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x + 1;
-    if (i < nf && c_pos[i] < c_pos[i - 1]) atomicOr(unsorted, 1u);
-}
-
-// which of the kept reads (ascending positions) can cover column cols[k]: those that start in (col - max_len, col]
-__global__ __launch_bounds__(64) void ins_ranges_kernel(const int32_t *c_pos, int64_t nf, const int32_t *cols, int32_t n_cand, int32_t max_len,
-                                                        int64_t *lo, int64_t *hi)
-{
-    const int k = blockIdx.x * 64 + threadIdx.x;
-    if (k >= n_cand) return;
-    const int64_t first = (int64_t)cols[k] - max_len + 1, last = cols[k];
-    int64_t a = 0, b = nf;
-    while (a < b) { const int64_t m = (a + b) >> 1; if ((int64_t)c_pos[m] < first) a = m + 1; else b = m; }
-    lo[k] = a;
-    b = nf;
-    while (a < b) { const int64_t m = (a + b) >> 1; if ((int64_t)c_pos[m] <= last) a = m + 1; else b = m; }
-    hi[k] = a;
-}
-
-// does read j (compacted index) have a matched base on reference position `ref`?  -> matched | base << 8 | quality << 16
-struct ProbeArgs {
-    PackSrc src;
-    const uint32_t *c_idx;
-    const int64_t *idx;
-    const int32_t *ref;
-    uint32_t *out;
-    int32_t n;
-};
-
-__global__ __launch_bounds__(64) void ins_probe_kernel(ProbeArgs a)
-{
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= a.n) return;
-    uint32_t res = 15u << 8;
-    const ReadView v = view(a.src, a.c_idx[a.idx[t]]);
-    const int64_t ref = a.ref[t];
-    int64_t x = v.pos, y = 0;
-    for (uint32_t c = 0; c < v.n_cigar; ++c) {
-        const uint32_t w = ld_u32(v.cigar + 4 * (size_t)c), op = w & 0xFu;
-        const int64_t len = w >> 4;
-        if (consumes_ref(op)) {
-            if (ref < x + len) {
-                if (is_match(op) && ref >= x) {
-                    const int64_t q = y + (ref - x);
-                    if (q < v.l_seq) {
-                        const uint8_t *qual = v.seq + ((size_t)v.l_seq + 1) / 2;
-                        res = 1u | (nib_at(v.seq, (int32_t)q) << 8) | (byte_at(qual + q) << 16);
-                    }
-                }
-                break;
-            }
-            x += len;
-        }
-        if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) y += len;
-    }
-    a.out[t] = res;
-}
-
 } // namespace
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-struct tcmi_dev_arena {             // grow-only device scratch of a context (freed with it): the packers' temporaries
-    char *base = nullptr;
-    size_t cap = 0, used = 0;
-};
-
-static int arena_reserve(tcmi_ctx *ctx, size_t bytes)
+// a read set's allocation: from the context's pool of freed read sets when one of about this size lies there
+static char *take_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t want)
 {
-    if (!ctx->dev_arena) ctx->dev_arena = new tcmi_dev_arena();
-    tcmi_dev_arena &A = *ctx->dev_arena;
-    A.used = 0;
-    ++ctx->arena_epoch;                         // whatever lived in the arena is gone
-    if (A.cap >= bytes) return TCMI_OK;
-    if (A.base) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(A.base); A.base = nullptr; A.cap = 0; }
-    const size_t want = bytes + bytes / 8 + (1 << 20);
-    if (hipMalloc((void **)&A.base, want) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "hipMalloc(%zu) for the pack scratch failed", want);
-    A.cap = want;
+    for (size_t k = 0; k < ctx->blob_pool.size(); ++k)
+        if (ctx->blob_pool[k].bytes >= want && ctx->blob_pool[k].bytes <= want + want / 2 + (1 << 20)) {
+            char *blob = ctx->blob_pool[k].p;
+            rs->blob_bytes = ctx->blob_pool[k].bytes;
+            ctx->blob_pool.erase(ctx->blob_pool.begin() + (long)k);
+            return blob;
+        }
+    char *blob = nullptr;
+    if (hipMalloc((void **)&blob, want + want / 16) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    rs->blob_bytes = want + want / 16;
+    return blob;
+}
+
+// one allocation for everything the tally kernel reads: headers | planes | chunk records | runs | events, and 256 bytes of slack
+// behind the last array (pk_pack zeroes them)
+static int carve_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t n_reads, uint32_t word_cap, uint32_t chunk_cap, uint32_t event_cap, PackOut *o)
+{
+    const size_t b_len = tcmi_align256(n_reads * 4), b_seq = tcmi_align256((size_t)word_cap * 4), b_run = b_len,
+                 b_chk = tcmi_align256((size_t)chunk_cap * sizeof(tcmi_fast_chunk)), b_ev = tcmi_align256((size_t)event_cap * 4);
+    const size_t want = b_len + b_seq + b_chk + b_run + b_ev + 256;
+    char *blob = take_blob(ctx, rs, want);
+    if (!blob) return tcmi_fail(ctx, TCMI_E_NOMEM, "hipMalloc(%zu) for the packed read set failed", want + want / 16);
+    rs->d_blob = blob;
+    o->lenoff = (uint32_t *)blob;
+    o->seq = (uint32_t *)(blob + b_len);
+    o->chunks = (tcmi_fast_chunk *)(blob + b_len + b_seq);
+    o->covrun = (uint32_t *)(blob + b_len + b_seq + b_chk);
+    o->events = (uint32_t *)(blob + b_len + b_seq + b_chk + b_run);
+    o->word_cap = word_cap; o->chunk_cap = chunk_cap; o->event_cap = event_cap;
+    o->slack = reinterpret_cast<uint32_t *>(blob + b_len + b_seq + b_chk + b_run + b_ev);
     return TCMI_OK;
 }
 
-static void *arena_take(tcmi_ctx *ctx, size_t bytes)
+static void point_at_blob(tcmi_readset *rs, const PackOut &o)       // (the several-kernel packer: only once it has succeeded)
 {
-    tcmi_dev_arena &A = *ctx->dev_arena;
-    const size_t at = (A.used + 255) & ~(size_t)255;
-    A.used = at + bytes;
-    return A.base + at;
+    rs->d_flenoff = o.lenoff; rs->d_fseq = o.seq; rs->d_fchunk = o.chunks; rs->d_fcovrun = o.covrun; rs->d_fevent = o.events;
 }
 
-void tcmi_dev_arena_free(tcmi_dev_arena *a)
+// what the packed set takes of its allocation
+static int64_t packed_bytes(const PackTotals &tot)
 {
-    if (!a) return;
-    if (a->base) (void)hipFree(a->base);
-    delete a;
+    return (int64_t)tot.n_kept * 4 + ((int64_t)tot.n_words + 4) * 4 + (int64_t)tot.n_chunks * (int64_t)sizeof(tcmi_fast_chunk) + (int64_t)tot.n_runs * 4 +
+           (int64_t)tot.n_events * 4;
 }
-
-void *tcmi_arena_reserve_take(tcmi_ctx *ctx, size_t total, size_t first)   // (bam_device.hip shares the arena)
-{
-    if (arena_reserve(ctx, total)) return nullptr;
-    return arena_take(ctx, first);
-}
-void *tcmi_arena_take(tcmi_ctx *ctx, size_t bytes) { return arena_take(ctx, bytes); }
 
 // Pack `n` reads described by `src` (device pointers) into a read set.  Returns TCMI_E_UNSUPPORTED (with `*why` set) when
 // the input needs the host packer: entries longer than TCMI_D_MAXLEN, positions beyond 2^29, malformed reads (the host
@@ -1344,14 +1046,14 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     const int64_t n = src.n;
     if (n > 0xFFFFFFF0ll) { *why = PKF_LONG; return TCMI_E_UNSUPPORTED; }
     const int64_t n_blk = (n + PB - 1) / PB;
-    uint32_t *info = (uint32_t *)arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4);
-    uint2 *rd_seq = (uint2 *)arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 8);
-    int32_t *rd_pos = (int32_t *)arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4);
-    uint2 *blk_sum = (uint2 *)arena_take(ctx, (size_t)std::max<int64_t>(n_blk, 1) * 8);
-    unsigned long long *blk_alg = (unsigned long long *)arena_take(ctx, (size_t)std::max<int64_t>(n_blk, 1) * 8);
-    int32_t *blk_end = (int32_t *)arena_take(ctx, (size_t)std::max<int64_t>(n_blk, 1) * 4);
-    PackTotals *d_tot = (PackTotals *)arena_take(ctx, sizeof(PackTotals));
-    uint32_t *gen_idx = src.mode == 1 ? (uint32_t *)arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4) : nullptr;
+    uint32_t *info = (uint32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4);
+    uint2 *rd_seq = (uint2 *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 8);
+    int32_t *rd_pos = (int32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4);
+    uint2 *blk_sum = (uint2 *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n_blk, 1) * 8);
+    unsigned long long *blk_alg = (unsigned long long *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n_blk, 1) * 8);
+    int32_t *blk_end = (int32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n_blk, 1) * 4);
+    PackTotals *d_tot = (PackTotals *)tcmi_arena_take(ctx, sizeof(PackTotals));
+    uint32_t *gen_idx = src.mode == 1 ? (uint32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4) : nullptr;
     PackTotals *h_tot = (PackTotals *)tcmi_ctx_pinned(ctx, sizeof(PackTotals));     // (pinned: the two read-backs below)
     if (!h_tot) return tcmi_fail(ctx, TCMI_E_NOMEM, "pinned scratch for the packer's totals");
     std::memset(h_tot, 0, sizeof *h_tot);
@@ -1392,12 +1094,12 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     if (nf == 0) return TCMI_OK;
     if (tot.n_words > 0xF0000000ull) { *why = PKF_WORD_OVF; return TCMI_E_UNSUPPORTED; }
 
-    // chunk size: as readset.cpp — long chunks, but a multiple of the resident workgroups of them
-    int64_t C = 2048;
     const int n_stages = ctx->chunk_stages > 0 ? std::min(ctx->chunk_stages, TCMI_F_MAXSTAGE) : TCMI_F_MAXSTAGE;
+    // reads per pk_pack workgroup: as readset.cpp — long chunks, but a multiple of the resident workgroups of them (its twin: pk_pack, dev_slots > 0)
+    int64_t C = 2048;
     if (ctx->chunk_stages == 0 && ctx->balance_chunks) {
-        const int64_t slots = (int64_t)ctx->n_cu * ctx->wg_per_cu, longest = (int64_t)TCMI_F_MAXSTAGE * 400;
-        const int64_t k = (nf + slots * longest - 1) / (slots * longest);
+        const int64_t slots = (int64_t)ctx->n_cu * ctx->wg_per_cu;
+        const int64_t k = (nf + slots * PK_LONGEST - 1) / (slots * PK_LONGEST);
         C = std::max<int64_t>(64, (nf + k * slots - 1) / (k * slots));
     }
     C = std::min<int64_t>(C, PK_CMAX);
@@ -1406,42 +1108,17 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     const uint32_t chunk_cap = (uint32_t)std::min<int64_t>(nf, 4 * n_wg + (int64_t)tot.max_end / 128 + 64);
     const uint32_t word_cap = (uint32_t)(tot.n_words + 2 + 16);        // the zero pair in front, the reads, slack for the last 16-byte load
 
-    uint32_t *c_idx = (uint32_t *)arena_take(ctx, (size_t)nf * 4);
-    int32_t *c_pos = (int32_t *)arena_take(ctx, (size_t)nf * 4);
-    uint32_t *c_info = (uint32_t *)arena_take(ctx, (size_t)nf * 4);
-    uint32_t *c_woff = (uint32_t *)arena_take(ctx, (size_t)nf * 4);
-    uint2 *c_seq = (uint2 *)arena_take(ctx, (size_t)nf * 8);
-    if (ctx->dev_arena->used > ctx->dev_arena->cap) { return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: pack scratch under-reserved"); }
+    uint32_t *c_idx = (uint32_t *)tcmi_arena_take(ctx, (size_t)nf * 4);
+    int32_t *c_pos = (int32_t *)tcmi_arena_take(ctx, (size_t)nf * 4);
+    uint32_t *c_info = (uint32_t *)tcmi_arena_take(ctx, (size_t)nf * 4);
+    uint32_t *c_woff = (uint32_t *)tcmi_arena_take(ctx, (size_t)nf * 4);
+    uint2 *c_seq = (uint2 *)tcmi_arena_take(ctx, (size_t)nf * 8);
+    if (ctx->dev_arena.used > ctx->dev_arena.cap) { return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: pack scratch under-reserved"); }
 
     uint32_t event_cap = (uint32_t)std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(1 << 20, nf / 2));
     for (int attempt = 0;; ++attempt) {
         PackOut o = {};
-        // one allocation for everything the tally kernel reads: headers | planes | chunk records | runs | events
-        const size_t b_len = ((size_t)nf * 4 + 255) & ~(size_t)255, b_seq = ((size_t)word_cap * 4 + 255) & ~(size_t)255,
-                     b_chk = ((size_t)chunk_cap * sizeof(tcmi_fast_chunk) + 255) & ~(size_t)255, b_run = b_len,
-                     b_ev = ((size_t)event_cap * 4 + 255) & ~(size_t)255;
-        char *blob = nullptr;
-        const size_t want = b_len + b_seq + b_chk + b_run + b_ev + 256;
-        for (size_t k = 0; k < ctx->blob_pool.size(); ++k)       // a freed read set of about this size?
-            if (ctx->blob_pool[k].bytes >= want && ctx->blob_pool[k].bytes <= want + want / 2 + (1 << 20)) {
-                blob = ctx->blob_pool[k].p;
-                rs->blob_bytes = ctx->blob_pool[k].bytes;
-                ctx->blob_pool.erase(ctx->blob_pool.begin() + (long)k);
-                break;
-            }
-        if (!blob) {
-            rs->blob_bytes = want + want / 16;
-            if (hipMalloc((void **)&blob, rs->blob_bytes) != hipSuccess)
-                return tcmi_fail(ctx, TCMI_E_NOMEM, "hipMalloc(%zu) for the packed read set failed", rs->blob_bytes);
-        }
-        rs->d_blob = blob;
-        o.lenoff = (uint32_t *)blob;
-        o.seq = (uint32_t *)(blob + b_len);
-        o.chunks = (tcmi_fast_chunk *)(blob + b_len + b_seq);
-        o.covrun = (uint32_t *)(blob + b_len + b_seq + b_chk);
-        o.events = (uint32_t *)(blob + b_len + b_seq + b_chk + b_run);
-        o.word_cap = word_cap; o.chunk_cap = chunk_cap; o.event_cap = event_cap;
-        o.slack = reinterpret_cast<uint32_t *>(blob + b_len + b_seq + b_chk + b_run + b_ev);                // 256 bytes behind the last array: pk_pack zeroes them
+        if (const int rc = carve_blob(ctx, rs, (size_t)nf, word_cap, chunk_cap, event_cap, &o)) return rc;
         if (attempt > 0) TCMI_HIP(ctx, hipMemsetAsync(&d_tot->n_chunks, 0, 4 * sizeof(uint32_t), ctx->stream));    // n_chunks, n_events, n_runs, word_cursor (the first time: pk_scan)
         (void)hipGetLastError();
         tcmi_prof_begin(ctx, TCMI_K_PACK);
@@ -1456,7 +1133,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
         TCMI_HIP(ctx, hipMemcpyAsync(h_tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
         TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (tot.n_events > event_cap && attempt == 0) {          // rare: a read set full of N / indel tokens — once more with room for all
-            (void)hipFree(blob);
+            (void)hipFree(rs->d_blob);
             rs->d_blob = nullptr;
             rs->blob_bytes = 0;
             event_cap = tot.n_events + 1024;
@@ -1466,14 +1143,13 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
             *why = tot.flags ? tot.flags : (uint32_t)PKF_EVENT_OVF;
             return TCMI_E_UNSUPPORTED;
         }
-        rs->d_flenoff = o.lenoff; rs->d_fseq = o.seq; rs->d_fchunk = o.chunks; rs->d_fcovrun = o.covrun; rs->d_fevent = o.events;
+        point_at_blob(rs, o);
         if (src.mode == 1) {                    // the stream and the index stay in the arena until this context's next upload
             rs->d_stream = src.stream; rs->d_rec_off = src.rec_off; rs->d_cidx = c_idx; rs->d_cpos = c_pos;
             rs->arena_epoch = ctx->arena_epoch;
         }
         rs->f_chunks = tot.n_chunks; rs->f_words = (int64_t)tot.n_words + 4; rs->f_events = tot.n_events;
-        rs->dev_bytes = nf * 4 + ((int64_t)tot.n_words + 4) * 4 + (int64_t)tot.n_chunks * (int64_t)sizeof(tcmi_fast_chunk) +
-                        (int64_t)tot.n_runs * 4 + (int64_t)tot.n_events * 4;
+        rs->dev_bytes = packed_bytes(tot);
         return TCMI_OK;
     }
 }
@@ -1489,54 +1165,45 @@ __global__ __launch_bounds__(256) void pk_report(const PackTotals *tot, const un
 }
 
 // ---- the one-sync path: pk_index + pk_place + pk_pack queued from capacities, checked after the caller's one wait ------------------------------
-static char *take_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t want)
-{
-    for (size_t k = 0; k < ctx->blob_pool.size(); ++k)           // a freed read set of about this size?
-        if (ctx->blob_pool[k].bytes >= want && ctx->blob_pool[k].bytes <= want + want / 2 + (1 << 20)) {
-            char *blob = ctx->blob_pool[k].p;
-            rs->blob_bytes = ctx->blob_pool[k].bytes;
-            ctx->blob_pool.erase(ctx->blob_pool.begin() + (long)k);
-            return blob;
-        }
-    char *blob = nullptr;
-    rs->blob_bytes = want + want / 16;
-    if (hipMalloc((void **)&blob, rs->blob_bytes) != hipSuccess) { (void)hipGetLastError(); rs->blob_bytes = 0; return nullptr; }
-    return blob;
-}
+// the pinned buffer pk_report fills, as byte offsets: PackTotals | blk_alg [n_blocks] | blk_end [n_blocks] | stat [n_blocks]
+struct ReportPin {
+    size_t alg, end, stat, bytes;
+    explicit ReportPin(int64_t nb) : alg(tcmi_align256(sizeof(PackTotals))), end(alg + tcmi_align256((size_t)nb * 8)),
+                                     stat(end + tcmi_align256((size_t)nb * 4)), bytes(stat + tcmi_align256((size_t)nb * 4)) {}
+};
 
 int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs)
 {
     const int64_t nb = job->n_blocks, cap = std::max<int64_t>(job->rec_cap, 1);
     if (cap > 0x7FFFFFF0ll) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "too many records for the one-pass packer");
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    uint2 *agg = (uint2 *)arena_take(ctx, al((size_t)nb * 8));
-    unsigned long long *fn = (unsigned long long *)arena_take(ctx, al((size_t)nb * 8));
-    uint32_t *rec_base = (uint32_t *)arena_take(ctx, al((size_t)nb * 4));
-    uint4 *rrec = (uint4 *)arena_take(ctx, (size_t)cap * 16);
-    unsigned long long *blk_alg = (unsigned long long *)arena_take(ctx, al((size_t)nb * 8));
-    int32_t *blk_end = (int32_t *)arena_take(ctx, al((size_t)nb * 4));
-    PackTotals *d_tot = (PackTotals *)arena_take(ctx, sizeof(PackTotals));
+    uint2 *agg = (uint2 *)tcmi_arena_take(ctx, tcmi_align256((size_t)nb * 8));
+    unsigned long long *fn = (unsigned long long *)tcmi_arena_take(ctx, tcmi_align256((size_t)nb * 8));
+    uint32_t *rec_base = (uint32_t *)tcmi_arena_take(ctx, tcmi_align256((size_t)nb * 4));
+    uint4 *rrec = (uint4 *)tcmi_arena_take(ctx, (size_t)cap * 16);
+    unsigned long long *blk_alg = (unsigned long long *)tcmi_arena_take(ctx, tcmi_align256((size_t)nb * 8));
+    int32_t *blk_end = (int32_t *)tcmi_arena_take(ctx, tcmi_align256((size_t)nb * 4));
+    PackTotals *d_tot = (PackTotals *)tcmi_arena_take(ctx, sizeof(PackTotals));
     // (every workgroup adds up what lies in front of its block: a few thousand words for a 1M-read file, but quadratic in the blocks —
     //  at 67 000 blocks, a 4 GiB stream, it was 40 % of these kernels' time: from 16 384 blocks on three small scan launches do it)
     const bool prefix = ctx->prefix_kernels > 0 || (ctx->prefix_kernels == 0 && nb >= 16384);
-    unsigned long long *pre = prefix ? (unsigned long long *)arena_take(ctx, al(((size_t)nb + 1) * 8) * 3) : nullptr;
-    job->d_rec = (uint64_t *)arena_take(ctx, (size_t)cap * 8 + 8);
-    job->c_idx = (uint32_t *)arena_take(ctx, (size_t)cap * 4);
-    job->c_pos = (int32_t *)arena_take(ctx, (size_t)cap * 4);
-    uint32_t *c_info = (uint32_t *)arena_take(ctx, (size_t)cap * 4);
-    uint32_t *c_woff = (uint32_t *)arena_take(ctx, (size_t)cap * 4);
-    uint2 *c_seq = (uint2 *)arena_take(ctx, (size_t)cap * 8);
-    job->gen_idx = (uint32_t *)arena_take(ctx, (size_t)cap * 4);
-    if (ctx->dev_arena->used > ctx->dev_arena->cap) return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: one-pass packer scratch under-reserved");
+    unsigned long long *pre = prefix ? (unsigned long long *)tcmi_arena_take(ctx, tcmi_align256(((size_t)nb + 1) * 8) * 3) : nullptr;
+    job->d_rec = (uint64_t *)tcmi_arena_take(ctx, (size_t)cap * 8 + 8);
+    job->c_idx = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
+    job->c_pos = (int32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
+    uint32_t *c_info = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
+    uint32_t *c_woff = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
+    uint2 *c_seq = (uint2 *)tcmi_arena_take(ctx, (size_t)cap * 8);
+    job->gen_idx = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
+    if (ctx->dev_arena.used > ctx->dev_arena.cap) return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: one-pass packer scratch under-reserved");
     job->d_tot = d_tot;
-    const size_t pin_bytes = al(sizeof(PackTotals)) + al((size_t)nb * 8) + al((size_t)nb * 4) + al((size_t)nb * 4);
-    job->h_pin = (char *)tcmi_ctx_pinned(ctx, pin_bytes);
+    job->h_pin = (char *)tcmi_ctx_pinned(ctx, ReportPin(nb).bytes);
     if (!job->h_pin) return tcmi_fail(ctx, TCMI_E_NOMEM, "pinned scratch for the packer's totals");
     // capacities: what the arrays of the packed read set are sized for (a file beyond them takes the several-kernel path)
     const int n_stages = ctx->chunk_stages > 0 ? std::min(ctx->chunk_stages, TCMI_F_MAXSTAGE) : TCMI_F_MAXSTAGE;
     const bool balance = ctx->chunk_stages == 0 && ctx->balance_chunks;
-    const int64_t slots = (int64_t)ctx->n_cu * ctx->wg_per_cu, longest = (int64_t)TCMI_F_MAXSTAGE * 400;
-    const int64_t k_cap = std::max<int64_t>(1, (cap + slots * longest - 1) / (slots * longest));
+    // (the grid: at least the workgroups the reads-per-workgroup rule leaves for any number of kept reads up to `cap`; pk_pack works the rule out itself)
+    const int64_t slots = (int64_t)ctx->n_cu * ctx->wg_per_cu;
+    const int64_t k_cap = std::max<int64_t>(1, (cap + slots * PK_LONGEST - 1) / (slots * PK_LONGEST));
     const int64_t n_wg = balance ? std::max<int64_t>(k_cap * slots, (cap + PK_CMAX - 1) / PK_CMAX) : (cap + PK_CMAX - 1) / PK_CMAX + (cap + 2047) / 2048;
     // words: a read of len positions takes <= len / 16 + 7 words, and a read without long deletions / skips has len <= l_seq,
     // each base of which takes 1.5 bytes of the stream (others overflow the capacity: PKF_WORD_OVF, the other path)
@@ -1546,18 +1213,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     job->chunk_cap = (uint32_t)std::min<int64_t>(cap, 4 * n_wg + job->len_bound / 128 + 64);
     job->event_cap = (uint32_t)std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(1 << 20, cap / 2));
     PackOut o = {};
-    const size_t b_len = al((size_t)cap * 4), b_seq = al((size_t)job->word_cap * 4), b_chk = al((size_t)job->chunk_cap * sizeof(tcmi_fast_chunk)),
-                 b_run = b_len, b_ev = al((size_t)job->event_cap * 4);
-    char *blob = take_blob(ctx, rs, b_len + b_seq + b_chk + b_run + b_ev + 256);
-    if (!blob) return tcmi_fail(ctx, TCMI_E_NOMEM, "hipMalloc for the packed read set failed");
-    rs->d_blob = blob;
-    o.lenoff = (uint32_t *)blob;
-    o.seq = (uint32_t *)(blob + b_len);
-    o.chunks = (tcmi_fast_chunk *)(blob + b_len + b_seq);
-    o.covrun = (uint32_t *)(blob + b_len + b_seq + b_chk);
-    o.events = (uint32_t *)(blob + b_len + b_seq + b_chk + b_run);
-    o.word_cap = job->word_cap; o.chunk_cap = job->chunk_cap; o.event_cap = job->event_cap;
-    o.slack = reinterpret_cast<uint32_t *>(blob + b_len + b_seq + b_chk + b_run + b_ev);
+    if (const int rc = carve_blob(ctx, rs, (size_t)cap, job->word_cap, job->chunk_cap, job->event_cap, &o)) return rc;
     TCMI_HIP(ctx, hipMemsetAsync(d_tot, 0, sizeof(PackTotals), ctx->stream));
     FusedArgs a = {};
     a.stream = job->d_stream; a.stream_len = job->stream_len; a.blocks = static_cast<const BlockDesc *>(job->d_desc);
@@ -1566,7 +1222,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     a.agg = agg; a.fn = fn; a.rec_base = rec_base; a.rrec = rrec; a.rec_off = job->d_rec; a.rec_cap = (uint32_t)cap;
     a.c_idx = job->c_idx; a.c_pos = job->c_pos; a.c_info = c_info; a.c_woff = c_woff; a.c_seq = c_seq; a.gen_idx = job->gen_idx;
     a.o = o; a.blk_alg = blk_alg; a.blk_end = blk_end; a.tot = d_tot;
-    const size_t pre_n = al(((size_t)nb + 1) * 8) / 8;
+    const size_t pre_n = tcmi_align256(((size_t)nb + 1) * 8) / 8;
     if (prefix) { a.pre_rec = pre; a.pre_k = pre + pre_n; a.pre_w = pre + 2 * pre_n; }
     (void)hipGetLastError();
     tcmi_prof_begin(ctx, TCMI_K_PACK_CLASSIFY);
@@ -1588,7 +1244,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     job->d_blk_alg = blk_alg; job->d_blk_end = blk_end;
     // the read set as the tally launch needs it before anyone has read the totals: capacities + where the real counts lie
     rs->packed_on_device = 1;
-    rs->d_flenoff = o.lenoff; rs->d_fseq = o.seq; rs->d_fchunk = o.chunks; rs->d_fcovrun = o.covrun; rs->d_fevent = o.events;
+    point_at_blob(rs, o);
     rs->f_chunks = job->chunk_cap; rs->f_events = job->event_cap;
     rs->d_dev_counts = &d_tot->n_chunks;
     static_assert(offsetof(PackTotals, n_events) == offsetof(PackTotals, n_chunks) + 4, "the tally kernel reads {n_chunks, n_events}");
@@ -1602,15 +1258,14 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
 // the last launch of the one-sync path's chain: totals and per-block verdicts into the job's pinned buffer
 int tcmi_pack_fused_report(tcmi_ctx *ctx, tcmi_fused_job *job)
 {
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int64_t nb = job->n_blocks;
+    const ReportPin pin(nb);
     char *h = job->h_pin;
     (void)hipGetLastError();
     hipLaunchKernelGGL(pk_report, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, static_cast<const PackTotals *>(job->d_tot),
                        static_cast<const unsigned long long *>(job->d_blk_alg), static_cast<const int32_t *>(job->d_blk_end), job->d_stat, (int32_t)nb,
-                       reinterpret_cast<PackTotals *>(h), reinterpret_cast<unsigned long long *>(h + al(sizeof(PackTotals))),
-                       reinterpret_cast<int32_t *>(h + al(sizeof(PackTotals)) + al((size_t)nb * 8)),
-                       reinterpret_cast<uint32_t *>(h + al(sizeof(PackTotals)) + al((size_t)nb * 8) + al((size_t)nb * 4)));
+                       reinterpret_cast<PackTotals *>(h), reinterpret_cast<unsigned long long *>(h + pin.alg), reinterpret_cast<int32_t *>(h + pin.end),
+                       reinterpret_cast<uint32_t *>(h + pin.stat));
     TCMI_HIP(ctx, hipGetLastError());
     return TCMI_OK;
 }
@@ -1618,12 +1273,12 @@ int tcmi_pack_fused_report(tcmi_ctx *ctx, tcmi_fused_job *job)
 int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs, uint32_t *why)
 {
     (void)ctx;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int64_t nb = job->n_blocks;
+    const ReportPin pin(nb);
     const PackTotals &tot = *reinterpret_cast<const PackTotals *>(job->h_pin);
-    const unsigned long long *blk_alg = reinterpret_cast<const unsigned long long *>(job->h_pin + al(sizeof(PackTotals)));
-    const int32_t *blk_end = reinterpret_cast<const int32_t *>(job->h_pin + al(sizeof(PackTotals)) + al((size_t)nb * 8));
-    const uint32_t *stat = reinterpret_cast<const uint32_t *>(job->h_pin + al(sizeof(PackTotals)) + al((size_t)nb * 8) + al((size_t)nb * 4));
+    const unsigned long long *blk_alg = reinterpret_cast<const unsigned long long *>(job->h_pin + pin.alg);
+    const int32_t *blk_end = reinterpret_cast<const int32_t *>(job->h_pin + pin.end);
+    const uint32_t *stat = reinterpret_cast<const uint32_t *>(job->h_pin + pin.stat);
     uint32_t flags = tot.flags;
     for (int64_t b = 0; b < nb; ++b) if (stat[b] != ST_OK) flags |= PKF_STAT;
     if (tot.n_rec > (unsigned long long)job->rec_cap) flags |= PKF_REC_OVF;
@@ -1643,89 +1298,7 @@ int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs,
     rs->range_first = tot.range_first ? (int64_t)(tot.range_first - 1ull) : -1;
     rs->range_next = tot.range_next ? (int64_t)(tot.range_next - 1ull) : -1;
     rs->f_chunks = nf ? tot.n_chunks : 0; rs->f_words = nf ? (int64_t)tot.n_words + 4 : 0; rs->f_events = tot.n_events;
-    rs->dev_bytes = nf * 4 + ((int64_t)tot.n_words + 4) * 4 + (int64_t)tot.n_chunks * (int64_t)sizeof(tcmi_fast_chunk) + (int64_t)tot.n_runs * 4 +
-                    (int64_t)tot.n_events * 4;
-    return TCMI_OK;
-}
-
-// ---- tally_stream_kernel: the reads the packer left out (spans above TCMI_D_MAXLEN), straight from the inflated BAM stream -------
-// One wavefront per read.  The CIGAR is walked op by op (wave-uniform), the lanes take the positions of an op 64 at a time and add
-// each token to the count matrix with a global atomic — the token rules of tally.hip's tally_read_general: a
-// matched base counts by its letter, a deleted position counts X unless an insertion follows the deletion's last base ("*+.."),
-// the last reference base in front of an insertion counts I, every position from pos to the end counts coverage (M, =, X, D, N).
-namespace {
-__device__ inline bool st_ins_after(const uint8_t *cg, int n, int k)        // htslib resolve_cigar2's peek at the last base of op k
-{
-    if (k + 1 >= n) return false;
-    const uint32_t op2 = ld_u32(cg + 4 * (size_t)(k + 1)) & 0xFu;
-    int64_t tot = 0;
-    if (op2 == 1) {
-        tot = ld_u32(cg + 4 * (size_t)(k + 1)) >> 4;
-        for (int j = k + 2; j < n; ++j) {
-            const uint32_t c = ld_u32(cg + 4 * (size_t)j), o = c & 0xFu;
-            if (o == 1) tot += c >> 4;
-            else if (o != 6) break;
-        }
-    } else if (op2 == 6 && k + 2 < n) {
-        for (int j = k + 2; j < n; ++j) {
-            const uint32_t c = ld_u32(cg + 4 * (size_t)j), o = c & 0xFu;
-            if (o == 1) tot += c >> 4;
-            else if (consumes_ref(o)) break;
-        }
-    }
-    return tot > 0;
-}
-
-__global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint32_t *gen_idx, uint32_t n_gen, int32_t *counts, int64_t ld, int32_t L)
-{
-    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (w >= n_gen) return;
-    const ReadView v = view(s, (int64_t)gen_idx[w]);
-    auto add = [&](int col, int32_t p) { if ((uint32_t)p < (uint32_t)L) atomicAdd(&counts[(int64_t)col * ld + p], 1); };
-    int32_t x = v.pos + shift_of(s, v.tid), y = 0;
-    const int32_t x0 = x;
-    for (uint32_t k = 0; k < v.n_cigar; ++k) {
-        const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k), op = c & 0xFu;
-        const int32_t len = (int32_t)(c >> 4);
-        if (consumes_ref(op)) {
-            const bool ins = len > 0 && st_ins_after(v.cigar, (int)v.n_cigar, (int)k);
-            if (is_match(op)) {
-                for (int32_t j = lane; j < len; j += 64) {
-                    const int32_t q = y + j;
-                    const uint32_t nib = q < v.l_seq ? nib_at(v.seq, q) : 15u;          // past SEQ -> 'N'
-                    if (__popc(nib) == 1) { const int b = __ffs(nib) - 1; add(b == 0 ? TCMI_A : b == 1 ? TCMI_C : b == 2 ? TCMI_G : TCMI_T, x + j); }
-                }
-            } else if (op == 2) {
-                const int32_t nx = ins ? len - 1 : len;                              // "*+.." does not count X
-                for (int32_t j = lane; j < nx; j += 64) add(TCMI_X, x + j);
-            }
-            if (ins && lane == 0) add(TCMI_I, x + len - 1);
-            x += len;
-        }
-        if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) y += len;
-    }
-    for (int32_t p = x0 + lane; p < x; p += 64) add(TCMI_COV, p);
-}
-} // namespace
-
-// the long reads of a device-decoded read set into the count matrix (tcmi_launch_tally calls it behind the packed set's kernel)
-int tcmi_launch_tally_stream(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts)
-{
-    if (rs->s_reads <= 0) return TCMI_OK;
-    if (!rs->d_stream || rs->arena_epoch != ctx->arena_epoch || rs->device != ctx->device)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set's long reads lie in a decoded stream that is gone (another upload on this context): upload it again");
-    PackSrc s = {};
-    s.stream = rs->d_stream; s.rec_off = rs->d_rec_off; s.mode = 1; s.n = rs->n_reads; s.pos_shift = 0;
-    if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's contig layout changed since the read set was uploaded: upload it again");
-    s.lay = rs->d_lay; s.n_lay = rs->n_lay;
-    (void)hipGetLastError();
-    tcmi_prof_begin(ctx, TCMI_K_TALLY_GENERAL);
-    hipLaunchKernelGGL(tally_stream_kernel, dim3((unsigned)((rs->s_reads + 3) / 4)), dim3(256), 0, ctx->stream, s, rs->d_gen_idx, (uint32_t)rs->s_reads,
-                       d_counts, ld, (int32_t)L);
-    tcmi_prof_end(ctx, TCMI_K_TALLY_GENERAL);
-    TCMI_HIP(ctx, hipGetLastError());
+    rs->dev_bytes = packed_bytes(tot);
     return TCMI_OK;
 }
 
@@ -1735,13 +1308,12 @@ int tcmi_upload_and_pack_on_device(tcmi_ctx *ctx, const tcmi_reads *r, tcmi_read
     *why = 0;
     const int64_t n = r->n_reads;
     const size_t n_cig = n ? (size_t)r->cigar_off[n] : 0, n_seq = n ? (size_t)r->seq_off[n] : 0;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t sz[8] = {al((size_t)n * 4), al((size_t)n * 2), al((size_t)n * 4), r->tid ? al((size_t)n * 4) : 0, al((size_t)(n + 1) * 8),
-                          al(n_cig * 4 + 64), al((size_t)(n + 1) * 8), al(n_seq + 128)};
+    const size_t b_n4 = tcmi_align256((size_t)n * 4), b_off = tcmi_align256((size_t)(n + 1) * 8);
+    const size_t sz[8] = {b_n4, tcmi_align256((size_t)n * 2), b_n4, r->tid ? b_n4 : 0, b_off, tcmi_align256(n_cig * 4 + 64), b_off, tcmi_align256(n_seq + 128)};
     size_t src_bytes = 0;
     for (size_t b : sz) src_bytes += b + 256;
-    const size_t tmp_bytes = al((size_t)n * 4) * 11 + al((size_t)((n + PB - 1) / PB + 1) * 8) * 3 + 4096 + 16 * 256;
-    int rc = arena_reserve(ctx, src_bytes + tmp_bytes);
+    const size_t tmp_bytes = b_n4 * 11 + tcmi_align256((size_t)((n + PB - 1) / PB + 1) * 8) * 3 + 4096 + 16 * 256;
+    int rc = tcmi_arena_reserve(ctx, src_bytes + tmp_bytes);
     if (rc) return rc;
     PackSrc s = {};
     s.mode = 0; s.n = n; s.pos_shift = 0;
@@ -1752,270 +1324,11 @@ int tcmi_upload_and_pack_on_device(tcmi_ctx *ctx, const tcmi_reads *r, tcmi_read
                            {r->seq_off, (size_t)(n + 1) * 8, sz[6], (const void **)&s.seq_off}, {r->seq, n_seq, sz[7], (const void **)&s.seq}};
     for (const Item &it : items) {
         if (!it.h || it.room == 0) { *it.d = nullptr; continue; }
-        char *d = (char *)arena_take(ctx, it.room);
+        char *d = (char *)tcmi_arena_take(ctx, it.room);
         *it.d = d;
         if (it.bytes) TCMI_HIP(ctx, hipMemcpyAsync(d, it.h, it.bytes, hipMemcpyHostToDevice, ctx->stream));
         TCMI_HIP(ctx, hipMemsetAsync(d + it.bytes, 0, it.room - it.bytes, ctx->stream));   // the 24-byte window loads of fetch32 may run past the last read
     }
     if (n == 0) { rs->packed_on_device = 1; return TCMI_OK; }
     return tcmi_pack_on_device(ctx, &s, rs, why);
-}
-
-// the device half of Events.ExtractInserts for a device-decoded read set: every read that can reach a candidate column as a 48-byte
-// entry (ins_entries_kernel), in file order per column, in the context's pinned scratch (valid until the context's next call)
-static int collect_ins_entries(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n_pos, const int64_t *positions, uint32_t flag_filter, int ignore_orphans,
-                               std::vector<int64_t> &off, std::vector<int32_t> &cnt, const tcmi_dev_entry **ents_out, std::vector<uint8_t> &long_text)
-{
-    if (!ctx || !rs || n_pos < 0 || (n_pos > 0 && !positions)) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
-
-    if (rs->s_reads > 0)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "long reads lie outside the packed set: their tokens are not looked at here (host sweep)");
-    if (rs->n_lay > 0)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set was uploaded under a contig layout: host sweep (tcmi_modal_tokens_layout)");
-    if (!rs->d_stream || rs->arena_epoch != ctx->arena_epoch || rs->device != ctx->device)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set's decoded stream is no longer (or never was) resident on this context: host sweep");
-    for (int32_t k = 1; k < n_pos; ++k)
-        if (positions[k] <= positions[k - 1]) return tcmi_fail(ctx, TCMI_E_ARG, "positions must ascend");
-    off.assign((size_t)n_pos + 1, 0); cnt.assign((size_t)n_pos, 0); *ents_out = nullptr; long_text.clear();
-    if (n_pos == 0) return TCMI_OK;
-    TCMI_HIP(ctx, hipSetDevice(ctx->device));
-    const int64_t nf = rs->f_reads;
-    // The kept reads ascend by position (the device packer takes nothing else): which of them can reach each column is a
-    // binary search on the device; what comes back is two numbers per column.  Scratch (device + pinned host) belongs to the
-    // context and only grows: hipMalloc / hipFree per file cost more than the kernels (hipFree waits for the whole device).
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    auto scratch = [&](size_t dev_bytes, size_t host_bytes) -> int {
-        if (ctx->tok_dev_cap < dev_bytes) {
-            if (ctx->tok_dev) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->tok_dev); ctx->tok_dev = nullptr; ctx->tok_dev_cap = 0; }
-            const size_t want = dev_bytes + dev_bytes / 4 + (1 << 20);
-            if (hipMalloc((void **)&ctx->tok_dev, want) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "insert-token scratch (%zu bytes)", want);
-            ctx->tok_dev_cap = want;
-        }
-        if (ctx->tok_host_cap < host_bytes) {
-            if (ctx->tok_host) { (void)hipStreamSynchronize(ctx->stream); (void)hipHostFree(ctx->tok_host); ctx->tok_host = nullptr; ctx->tok_host_cap = 0; }
-            const size_t want = host_bytes + host_bytes / 4 + (1 << 20);
-            if (hipHostMalloc((void **)&ctx->tok_host, want, hipHostMallocDefault) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "insert-token host scratch (%zu bytes)", want);
-            ctx->tok_host_cap = want;
-        }
-        return TCMI_OK;
-    };
-    std::vector<int32_t> cols((size_t)n_pos);
-    for (int32_t k = 0; k < n_pos; ++k) cols[(size_t)k] = (int32_t)(positions[k] - 1);
-    const size_t b_cols = al((size_t)n_pos * 4), b_lo = al((size_t)n_pos * 8), b_off = al(((size_t)n_pos + 1) * 8);
-    {
-        const int rc = scratch(b_cols + 2 * b_lo + b_off, 2 * b_lo);
-        if (rc) return rc;
-    }
-    int32_t *d_cols = (int32_t *)ctx->tok_dev;
-    int64_t *d_lo = (int64_t *)(ctx->tok_dev + b_cols), *d_hi = (int64_t *)(ctx->tok_dev + b_cols + b_lo), *d_off = (int64_t *)(ctx->tok_dev + b_cols + 2 * b_lo);
-    int64_t *h_lo = (int64_t *)ctx->tok_host, *h_hi = (int64_t *)(ctx->tok_host + b_lo);
-    const int32_t max_len = (int32_t)std::min<int64_t>(std::max<int64_t>(rs->max_len, 1), TCMI_D_MAXLEN);
-    TCMI_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), (size_t)n_pos * 4, hipMemcpyHostToDevice, ctx->stream));
-    (void)hipGetLastError();
-    uint32_t *d_unsorted = (uint32_t *)d_off;                   // (the offsets go there later)
-    TCMI_HIP(ctx, hipMemsetAsync(d_unsorted, 0, 4, ctx->stream));
-    if (nf > 1) hipLaunchKernelGGL(ins_sorted_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, ctx->stream, rs->d_cpos, nf, d_unsorted);
-    hipLaunchKernelGGL(ins_ranges_kernel, dim3((unsigned)((n_pos + 63) / 64)), dim3(64), 0, ctx->stream, rs->d_cpos, nf, d_cols, n_pos, max_len, d_lo, d_hi);
-    TCMI_HIP(ctx, hipGetLastError());
-    TCMI_HIP(ctx, hipMemcpyAsync(h_lo, d_lo, (size_t)n_pos * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TCMI_HIP(ctx, hipMemcpyAsync(h_hi, d_hi, (size_t)n_pos * 8, hipMemcpyDeviceToHost, ctx->stream));
-    uint32_t unsorted = 0;
-    TCMI_HIP(ctx, hipMemcpyAsync(&unsorted, d_unsorted, 4, hipMemcpyDeviceToHost, ctx->stream));
-    TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (unsorted) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "reads are not sorted by position: host sweep");
-    const std::vector<int64_t> lo_v(h_lo, h_lo + n_pos), hi_v(h_hi, h_hi + n_pos);   // (the scratch below may move)
-    for (int32_t k = 0; k < n_pos; ++k) off[(size_t)k + 1] = off[(size_t)k] + std::max<int64_t>(0, hi_v[(size_t)k] - lo_v[(size_t)k]);
-    const int64_t total = off[(size_t)n_pos];
-    for (int32_t k = 0; k < n_pos; ++k) cnt[(size_t)k] = (int32_t)(off[(size_t)k + 1] - off[(size_t)k]);
-    const tcmi_dev_entry *ents = nullptr;
-    constexpr size_t LONG_TEXT_CAP = 4u << 20;                  // bases of insertions longer than 12 on the candidate columns of one call
-    if (total > 0) {
-        const size_t b_head = b_cols + 2 * b_lo + b_off, b_ent = al((size_t)total * sizeof(tcmi_dev_entry));
-        const int rc = scratch(b_head + b_ent + 256 + LONG_TEXT_CAP, std::max(2 * b_lo, b_ent));
-        if (rc) return rc;
-        // (a regrown device buffer lost the columns and ranges: they are sent again — all tiny)
-        d_cols = (int32_t *)ctx->tok_dev;
-        d_lo = (int64_t *)(ctx->tok_dev + b_cols); d_off = (int64_t *)(ctx->tok_dev + b_cols + 2 * b_lo);
-        InsArgs a;
-        a.src = {};
-        a.src.stream = rs->d_stream; a.src.rec_off = rs->d_rec_off; a.src.mode = 1; a.src.n = rs->n_reads;
-        a.c_idx = rs->d_cidx;
-        a.out = (tcmi_dev_entry *)(ctx->tok_dev + b_head);
-        a.cols = d_cols; a.lo = d_lo; a.off = d_off;
-        a.n_cand = n_pos; a.flag_filter = flag_filter; a.ignore_orphans = ignore_orphans;
-        a.long_cursor = (uint32_t *)(ctx->tok_dev + b_head + b_ent); a.long_text = (uint8_t *)(ctx->tok_dev + b_head + b_ent + 256); a.long_cap = (uint32_t)LONG_TEXT_CAP;
-        TCMI_HIP(ctx, hipMemsetAsync(a.long_cursor, 0, 4, ctx->stream));
-        TCMI_HIP(ctx, hipMemcpyAsync(d_cols, cols.data(), (size_t)n_pos * 4, hipMemcpyHostToDevice, ctx->stream));
-        TCMI_HIP(ctx, hipMemcpyAsync(d_lo, lo_v.data(), (size_t)n_pos * 8, hipMemcpyHostToDevice, ctx->stream));
-        TCMI_HIP(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)n_pos + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(ins_entries_kernel, dim3((unsigned)((total + PB - 1) / PB)), dim3(PB), 0, ctx->stream, a);
-        TCMI_HIP(ctx, hipGetLastError());
-        TCMI_HIP(ctx, hipMemcpyAsync(ctx->tok_host, a.out, (size_t)total * sizeof(tcmi_dev_entry), hipMemcpyDeviceToHost, ctx->stream));
-        uint32_t long_used = 0;
-        TCMI_HIP(ctx, hipMemcpyAsync(&long_used, a.long_cursor, 4, hipMemcpyDeviceToHost, ctx->stream));
-        TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));       // (lo_v / off / cols were pageable: their copies are done)
-        ents = (const tcmi_dev_entry *)ctx->tok_host;
-        if (long_used) {                                        // (rare: a long insertion on a candidate column) its bases
-            long_text.resize(std::min<size_t>(long_used, LONG_TEXT_CAP));
-            TCMI_HIP(ctx, hipMemcpy(long_text.data(), a.long_text, long_text.size(), hipMemcpyDeviceToHost));
-        }
-    }
-    *ents_out = ents;
-    return TCMI_OK;
-}
-
-extern "C" int tcmi_readset_modal_tokens(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n_pos, const int64_t *positions,
-                                         int32_t min_base_quality, uint32_t flag_filter, int ignore_orphans, int64_t max_depth,
-                                         int ignore_overlaps, char *tokens, int64_t tokens_cap, int64_t *token_off, int64_t *n_tokens,
-                                         int32_t *status_flags)
-{
-    if (!ctx || !rs || n_pos < 0 || (n_pos > 0 && (!positions || !tokens || !token_off || !n_tokens)))
-        return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
-    if (!rs->parts.empty())
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "a read set of sub-ranges (tcmi_split_step): collect its entries (tcmi_readset_ins_entries) and vote on them (tcmi_modal_from_entries)");
-    if (n_pos == 0) { if (status_flags) *status_flags = 0; return TCMI_OK; }
-    std::vector<int64_t> off;
-    std::vector<int32_t> cnt;
-    std::vector<uint8_t> long_text;
-    const tcmi_dev_entry *ents = nullptr;
-    {
-        const int rc = collect_ins_entries(ctx, rs, n_pos, positions, flag_filter, ignore_orphans, off, cnt, &ents, long_text);
-        if (rc) return rc;
-    }
-    const int64_t nf = rs->f_reads;
-    // the other mate of an overlapping pair, looked at on one reference position (rare: a pair with a deletion on a candidate column)
-    const tcmi_prober prober = [&](const std::vector<tcmi_probe_req> &req, std::vector<tcmi_probe_res> &res) -> int {
-        const size_t n = req.size();
-        std::vector<int64_t> idx(n);
-        std::vector<int32_t> ref(n);
-        std::vector<uint32_t> out(n);
-        for (size_t t = 0; t < n; ++t) {
-            if (req[t].idx < 0 || req[t].idx >= nf) return tcmi_fail(ctx, TCMI_E_ARG, "internal: probe of read %lld", (long long)req[t].idx);
-            idx[t] = req[t].idx; ref[t] = req[t].ref;
-        }
-        char *buf = nullptr;
-        hipError_t e = hipMalloc((void **)&buf, n * 16);
-        if (e != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "probe buffers: %s", hipGetErrorString(e));
-        ProbeArgs a;
-        a.src = {};
-        a.src.stream = rs->d_stream; a.src.rec_off = rs->d_rec_off; a.src.mode = 1; a.src.n = rs->n_reads;
-        a.c_idx = rs->d_cidx;
-        a.idx = (const int64_t *)buf; a.ref = (const int32_t *)(buf + n * 8); a.out = (uint32_t *)(buf + n * 12); a.n = (int32_t)n;
-        e = hipMemcpyAsync((void *)a.idx, idx.data(), n * 8, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((void *)a.ref, ref.data(), n * 4, hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) {
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(ins_probe_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, a);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(out.data(), a.out, n * 4, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        (void)hipFree(buf);
-        if (e != hipSuccess) return tcmi_fail(ctx, TCMI_E_HIP, "probe kernel failed: %s", hipGetErrorString(e));
-        for (size_t t = 0; t < n; ++t) res[t] = tcmi_probe_res{(uint8_t)(out[t] & 1u), (uint8_t)((out[t] >> 8) & 15u), (uint8_t)(out[t] >> 16)};
-        return TCMI_OK;
-    };
-    return tcmi_modal_from_dev_entries(n_pos, ents, off.data(), cnt.data(), min_base_quality, max_depth, ignore_overlaps, &prober, tokens,
-                                       tokens_cap, token_off, n_tokens, status_flags, long_text.data(), long_text.size());
-}
-
-// The entries themselves (48 bytes each, opaque to the caller) instead of the vote: ranks that share ONE file (BASELINE configs[4])
-// each collect the entries of the candidate columns from the records of their own block range and send them to the rank that
-// calls; concatenated in rank order (= file order) they are what tcmi_readset_modal_tokens votes on (tcmi_modal_from_entries).
-extern "C" int tcmi_readset_ins_entries(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n_pos, const int64_t *positions, uint32_t flag_filter,
-                                        int ignore_orphans, void *entries, int64_t entries_cap, int64_t *ent_off, uint8_t *long_text,
-                                        int64_t long_cap, int64_t *long_used)
-{
-    if (!ctx || !rs || n_pos < 0 || !ent_off || (n_pos > 0 && !positions)) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
-    static_assert(sizeof(tcmi_dev_entry) == TCMI_INS_ENTRY_BYTES, "include/tcmi.h promises 48-byte entries");
-    std::vector<int64_t> off;
-    std::vector<int32_t> cnt;
-    std::vector<uint8_t> text;
-    const tcmi_dev_entry *ents = nullptr;
-    if (!rs->parts.empty()) {
-        // a read set of sub-ranges: the parts' entries per column one behind the other — file order —, the text offsets of a part's
-        // long insertions moved behind the texts of the parts in front of it (what rank 0 does with the ranks' pieces)
-        const size_t P = rs->parts.size();
-        std::vector<std::vector<int64_t>> p_off(P);
-        std::vector<std::vector<tcmi_dev_entry>> p_ent(P);
-        std::vector<int64_t> p_base(P, 0);
-        for (size_t p = 0; p < P; ++p) {
-            const tcmi_readset::Part &pt = rs->parts[p];
-            p_off[p].assign((size_t)n_pos + 1, 0);
-            p_base[p] = (int64_t)text.size();
-            if (pt.rs->n_piled == 0 || pt.rs->f_reads == 0) continue;
-            std::vector<uint8_t> t1;
-            const tcmi_dev_entry *e1 = nullptr;
-            const int rc = collect_ins_entries(pt.cx, pt.rs, n_pos, positions, flag_filter, ignore_orphans, p_off[p], cnt, &e1, t1);
-            if (rc) return tcmi_fail(ctx, rc, "%s", pt.cx->err.c_str());
-            const int64_t n1 = p_off[p][(size_t)n_pos];
-            if (n1) p_ent[p].assign(e1, e1 + n1);                // (the part's pinned scratch is its context's: copied out before the next call there)
-            if (n1 && p_base[p]) {
-                const int rc2 = tcmi_ins_entries_rebase(p_ent[p].data(), n1, p_base[p]);
-                if (rc2) return rc2;
-            }
-            text.insert(text.end(), t1.begin(), t1.end());
-        }
-        ent_off[0] = 0;
-        for (int32_t k = 0; k < n_pos; ++k) {
-            int64_t n = 0;
-            for (size_t p = 0; p < P; ++p) n += p_off[p][(size_t)k + 1] - p_off[p][(size_t)k];
-            ent_off[k + 1] = ent_off[k] + n;
-        }
-        if (long_used) *long_used = (int64_t)text.size();
-        if (ent_off[n_pos] > entries_cap || (int64_t)text.size() > long_cap)
-            return tcmi_fail(ctx, TCMI_E_ARG, "entry buffer too small: %lld entries, %zu bytes of long insertions (ent_off / long_used say what is needed)",
-                             (long long)ent_off[n_pos], text.size());
-        tcmi_dev_entry *dst = static_cast<tcmi_dev_entry *>(entries);
-        for (int32_t k = 0; k < n_pos; ++k)
-            for (size_t p = 0; p < P; ++p) {
-                const int64_t a = p_off[p][(size_t)k], b = p_off[p][(size_t)k + 1];
-                if (b > a) { std::memcpy(dst, p_ent[p].data() + a, (size_t)(b - a) * sizeof(tcmi_dev_entry)); dst += b - a; }
-            }
-        if (!text.empty()) std::memcpy(long_text, text.data(), text.size());
-        return TCMI_OK;
-    }
-    if (rs->n_piled == 0 || rs->f_reads == 0) {                 // (no kept reads in this range: no entries)
-        for (int32_t k = 0; k <= n_pos; ++k) ent_off[k] = 0;
-        if (long_used) *long_used = 0;
-        return TCMI_OK;
-    }
-    const int rc = collect_ins_entries(ctx, rs, n_pos, positions, flag_filter, ignore_orphans, off, cnt, &ents, text);
-    if (rc) return rc;
-    for (int32_t k = 0; k <= n_pos; ++k) ent_off[k] = off[(size_t)k];
-    if (long_used) *long_used = (int64_t)text.size();
-    if (off[(size_t)n_pos] > entries_cap || (int64_t)text.size() > long_cap)
-        return tcmi_fail(ctx, TCMI_E_ARG, "entry buffer too small: %lld entries, %zu bytes of long insertions (ent_off / long_used say what is needed)",
-                         (long long)off[(size_t)n_pos], text.size());
-    if (off[(size_t)n_pos]) std::memcpy(entries, ents, (size_t)off[(size_t)n_pos] * sizeof(tcmi_dev_entry));
-    if (!text.empty()) std::memcpy(long_text, text.data(), text.size());
-    return TCMI_OK;
-}
-
-// ... and the vote over entries gathered from several read sets (HOST): per column the concatenation, in file order, of the pieces the
-// ranks sent; `long_base[k]` rebases the text offsets of piece k's long insertions (their texts concatenated in `long_text`).
-extern "C" int tcmi_modal_from_entries(int32_t n_pos, void *entries, const int64_t *ent_off, int32_t min_base_quality, int64_t max_depth,
-                                       int ignore_overlaps, const uint8_t *long_text, int64_t long_bytes, char *tokens, int64_t tokens_cap,
-                                       int64_t *token_off, int64_t *n_tokens, int32_t *status_flags)
-{
-    if (n_pos < 0 || !ent_off || (n_pos > 0 && (!tokens || !token_off || !n_tokens))) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
-    std::vector<int32_t> cnt((size_t)std::max(n_pos, 0));
-    for (int32_t k = 0; k < n_pos; ++k) cnt[(size_t)k] = (int32_t)(ent_off[k + 1] - ent_off[k]);
-    return tcmi_modal_from_dev_entries(n_pos, static_cast<const tcmi_dev_entry *>(entries), ent_off, cnt.data(), min_base_quality, max_depth, ignore_overlaps,
-                                       nullptr, tokens, tokens_cap, token_off, n_tokens, status_flags, long_text, (size_t)std::max<int64_t>(long_bytes, 0));
-}
-
-extern "C" int tcmi_ins_entries_rebase(void *entries, int64_t n_entries, int64_t long_base)
-{
-    if (n_entries < 0 || (n_entries > 0 && !entries) || long_base < 0) return tcmi_fail(nullptr, TCMI_E_ARG, "bad argument");
-    tcmi_dev_entry *e = static_cast<tcmi_dev_entry *>(entries);
-    for (int64_t i = 0; i < n_entries; ++i)
-        if (e[i].key && (e[i].bits & 0x40) && !(e[i].bits & 0x80)) {   // the key says where the insertion's bases lie: bits 8-39
-                                                                        // (key 0: no token; the kernel wrote nothing else there)
-            const uint64_t at = ((e[i].key >> 8) & 0xFFFFFFFFull) + (uint64_t)long_base;
-            if (at > 0xFFFFFFFFull) return tcmi_fail(nullptr, TCMI_E_UNSUPPORTED, "more than 4 GiB of long insertions on the candidate columns");
-            e[i].key = (e[i].key & ~(0xFFFFFFFFull << 8)) | (at << 8);
-        }
-    return TCMI_OK;
 }

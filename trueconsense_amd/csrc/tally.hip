@@ -3,10 +3,11 @@
 // Replaces indexing.BuildIndex (TrueConsense/indexing.py:75-154): htslib's pileup plus the
 // per-token Python loop parse_query_sequences (indexing.py:102-132).  Semantics: SURVEY §8-P.
 //
-// Two kernels, one per device read set (tcmi_internal.h):
+// One kernel per device read set (tcmi_internal.h), and one for what the device packer leaves in the stream:
 //   tally_fast_kernel    ALIGNED reads (one match op): bit-sliced register accumulation,
 //                        no atomics in the inner loop — see the comment above it.
 //   tally_atomic_kernel  GENERAL reads (any CIGAR): token-by-token walk, LDS atomics.
+//   tally_stream_kernel  reads of a device-decoded stream that span more than a chunk's window: one wavefront per read.
 //
 // tally_atomic_kernel decomposition (read-major; the count matrix is a commutative integer sum):
 //   workgroup  = `rounds_per_wg` consecutive ROUNDS of 256 coordinate-sorted reads
@@ -18,7 +19,7 @@
 // to global atomics: always correct, only slower.
 //
 // Integer work, HBM-streaming: no MFMA anywhere (BASELINE.json north_star).
-#include "tcmi_internal.h"
+#include "pack_device.h"
 
 namespace {
 
@@ -48,12 +49,8 @@ struct TallyArgs {
     int32_t rounds_per_wg;
 };
 
-__device__ inline bool op_consumes_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-__device__ inline bool op_is_match(uint32_t op) { return op == 0 || op == 7 || op == 8; }
-__device__ inline bool op_consumes_query(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
-
-// htslib resolve_cigar2's peek at the last reference base of op k
-__device__ inline bool ins_after(const uint32_t *cg, int n, int k)
+// htslib resolve_cigar2's peek at the last reference base of op k, over aligned CIGAR words (its twin: pack_device.h's ins_after)
+__device__ inline bool ins_after_words(const uint32_t *cg, int n, int k)
 {
     if (k + 1 >= n) return false;
     const uint32_t op2 = cg[k + 1] & 0xF;
@@ -69,7 +66,7 @@ __device__ inline bool ins_after(const uint32_t *cg, int n, int k)
         for (int j = k + 2; j < n; ++j) {
             const uint32_t o = cg[j] & 0xF;
             if (o == 1) tot += cg[j] >> 4;
-            else if (op_consumes_ref(o)) break;
+            else if (consumes_ref(o)) break;
         }
     }
     return tot > 0;
@@ -126,9 +123,9 @@ __device__ inline void tally_read_general(uint32_t *win, int32_t *covd, const Ta
     for (int k = 0; k < nc; ++k) {
         const uint32_t c = cg[k], op = c & 0xF;
         const int32_t len = (int32_t)(c >> 4);
-        if (op_consumes_ref(op)) {
-            const bool ins = len > 0 && ins_after(cg, nc, k);
-            if (op_is_match(op)) {
+        if (consumes_ref(op)) {
+            const bool ins = len > 0 && ins_after_words(cg, nc, k);
+            if (is_match(op)) {
                 uint32_t word = 0;
                 for (int32_t j = 0; j < len; ++j) {
                     const int32_t q = y + j;
@@ -146,7 +143,7 @@ __device__ inline void tally_read_general(uint32_t *win, int32_t *covd, const Ta
             if (ins) add_token(win, a, PL_I, x + len - 1, P0);        // '+' in the token
             x += len;
         }
-        if (op_consumes_query(op)) y += len;
+        if (consumes_query(op)) y += len;
     }
     add_coverage(covd, a, pos, x, P0);                                // M/=/X, D and N all add coverage
 }
@@ -208,7 +205,63 @@ __global__ __launch_bounds__(BLOCK) void tally_atomic_kernel(TallyArgs a)
     }
 }
 
+// ---- tally_stream_kernel: the reads the packer left out (spans above TCMI_D_MAXLEN), straight from the inflated BAM stream -------
+// One wavefront per read.  The CIGAR is walked op by op (wave-uniform), the lanes take the positions of an op 64 at a time and add
+// each token to the count matrix with a global atomic — the token rules of tally_read_general above: a
+// matched base counts by its letter, a deleted position counts X unless an insertion follows the deletion's last base ("*+.."),
+// the last reference base in front of an insertion counts I, every position from pos to the end counts coverage (M, =, X, D, N).
+__global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint32_t *gen_idx, uint32_t n_gen, int32_t *counts, int64_t ld, int32_t L)
+{
+    const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (w >= n_gen) return;
+    const ReadView v = view(s, (int64_t)gen_idx[w]);
+    auto add = [&](int col, int32_t p) { if ((uint32_t)p < (uint32_t)L) atomicAdd(&counts[(int64_t)col * ld + p], 1); };
+    int32_t x = v.pos + shift_of(s, v.tid), y = 0;
+    const int32_t x0 = x;
+    for (uint32_t k = 0; k < v.n_cigar; ++k) {
+        const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k), op = c & 0xFu;
+        const int32_t len = (int32_t)(c >> 4);
+        if (consumes_ref(op)) {
+            const bool ins = len > 0 && ins_after(v.cigar, v.n_cigar, k);
+            if (is_match(op)) {
+                for (int32_t j = lane; j < len; j += 64) {
+                    const int32_t q = y + j;
+                    const uint32_t nib = q < v.l_seq ? nib_at(v.seq, q) : 15u;          // past SEQ -> 'N'
+                    if (__popc(nib) == 1) { const int b = __ffs(nib) - 1; add(b == 0 ? TCMI_A : b == 1 ? TCMI_C : b == 2 ? TCMI_G : TCMI_T, x + j); }
+                }
+            } else if (op == 2) {
+                const int32_t nx = ins ? len - 1 : len;                              // "*+.." does not count X
+                for (int32_t j = lane; j < nx; j += 64) add(TCMI_X, x + j);
+            }
+            if (ins && lane == 0) add(TCMI_I, x + len - 1);
+            x += len;
+        }
+        if (consumes_query(op)) y += len;
+    }
+    for (int32_t p = x0 + lane; p < x; p += 64) add(TCMI_COV, p);
+}
+
 } // namespace
+
+// the long reads of a device-decoded read set into the count matrix (behind the packed set's kernel)
+static int launch_tally_stream(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts)
+{
+    if (rs->s_reads <= 0) return TCMI_OK;
+    if (!rs->d_stream || rs->arena_epoch != ctx->arena_epoch || rs->device != ctx->device)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set's long reads lie in a decoded stream that is gone (another upload on this context): upload it again");
+    PackSrc s = stream_src(rs);
+    if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's contig layout changed since the read set was uploaded: upload it again");
+    s.lay = rs->d_lay; s.n_lay = rs->n_lay;
+    (void)hipGetLastError();
+    tcmi_prof_begin(ctx, TCMI_K_TALLY_GENERAL);
+    hipLaunchKernelGGL(tally_stream_kernel, dim3((unsigned)((rs->s_reads + 3) / 4)), dim3(256), 0, ctx->stream, s, rs->d_gen_idx, (uint32_t)rs->s_reads,
+                       d_counts, ld, (int32_t)L);
+    tcmi_prof_end(ctx, TCMI_K_TALLY_GENERAL);
+    TCMI_HIP(ctx, hipGetLastError());
+    return TCMI_OK;
+}
 
 int tcmi_launch_tally(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts)
 {
@@ -216,8 +269,8 @@ int tcmi_launch_tally(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t 
         const int rc = tcmi_launch_tally_fast(ctx, rs, L, ld, d_counts);
         if (rc) return rc;
     }
-    if (rs->s_reads > 0) {                                    // long reads of a device-decoded stream (pack_device.hip)
-        const int rc = tcmi_launch_tally_stream(ctx, rs, L, ld, d_counts);
+    if (rs->s_reads > 0) {                                    // long reads of a device-decoded stream
+        const int rc = launch_tally_stream(ctx, rs, L, ld, d_counts);
         if (rc) return rc;
     }
     if (rs->g_reads == 0) return TCMI_OK;

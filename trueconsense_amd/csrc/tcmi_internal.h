@@ -14,8 +14,8 @@
 // ---- several contigs on one coordinate axis (tcmi_ctx_set_layout) --------------------------------------------------
 // Reference t's reads pile up at pos + shift[t]; shift[t] < 0: they do not pile up (a reference the caller has no record of);
 // a kept read must end at or before end[t] = shift[t] + slot_len[t].  No layout (n() == 0): reference 0 at 0, nothing else.
-// The one rule of the host packer (readset.cpp) and the host insert sweep (insert_tokens.cpp); pack_device.hip holds the same
-// table on the device.
+// The one rule of the host packer (readset.cpp) and the host insert sweep (insert_tokens.cpp); the kernels read the same
+// table on the device (pack_device.h: shift_of).
 struct tcmi_layout {
     std::vector<int64_t> shift, end;
     int32_t n() const { return (int32_t)shift.size(); }
@@ -164,13 +164,15 @@ struct tcmi_ride {                  // a finished matrix waiting for its call (s
 
 struct tcmi_upload_scratch;              // host buffers of tcmi_readset_upload, kept between calls (readset.cpp)
 void tcmi_upload_scratch_free(tcmi_upload_scratch *s);
-struct tcmi_dev_arena;                   // grow-only device scratch of the device packer / BAM decoder (pack_device.hip)
-void tcmi_dev_arena_free(tcmi_dev_arena *a);
+struct tcmi_dev_arena {                  // grow-only device scratch of a context (freed with it): the BAM decoder's and the packers' temporaries (api.cpp)
+    char *base = nullptr;
+    size_t cap = 0, used = 0;
+};
 
 struct tcmi_ctx {
     int device = -1;
     tcmi_upload_scratch *upload_scratch = nullptr;
-    tcmi_dev_arena *dev_arena = nullptr;
+    tcmi_dev_arena dev_arena;
     uint64_t arena_epoch = 0;        // bumped whenever the arena is handed out anew
     // device-packed read sets hand their allocation back when they are freed; the next upload of a similar size takes it
     // (hipMalloc + hipFree cost more than the pack kernels, and hipFree waits for the device)
@@ -291,7 +293,7 @@ struct tcmi_pack_src {
     // lay[n_lay + t] = the end of its slot; lay_ext[t]: the kept reads' max end on reference t, in its own coordinates (atomicMax)
     const int32_t *lay; int32_t *lay_ext; int32_t n_lay;
 };
-// one read on one insert-candidate column, as the device kernel hands it to the host (pack_device.hip -> insert_tokens.cpp)
+// one read on one insert-candidate column, as the device kernel hands it to the host (ins_entries.hip -> insert_tokens.cpp)
 struct tcmi_dev_entry {
     uint64_t key;               // packed token (insert_tokens.cpp)
     uint64_t name_hash;         // FNV-1a of the read name
@@ -345,12 +347,13 @@ struct tcmi_fused_job {
 int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs);
 int tcmi_pack_fused_report(tcmi_ctx *ctx, tcmi_fused_job *job);     // queue it LAST (behind the tally and the call, if any): then wait, then _finish
 int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs, uint32_t *why);
-void *tcmi_arena_reserve_take(tcmi_ctx *ctx, size_t total, size_t first);
+// the context's device arena (api.cpp): _reserve hands it out anew, `bytes` large (whatever lived in it is gone: arena_epoch tells);
+// _take carves the next piece, 256-byte aligned — the takers check `used > cap` once they have taken all
+int tcmi_arena_reserve(tcmi_ctx *ctx, size_t bytes);
 void *tcmi_arena_take(tcmi_ctx *ctx, size_t bytes);
 // kernels (tally.hip / call.hip)
 int tcmi_launch_tally(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts);
 int tcmi_launch_tally_fast(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts);
-int tcmi_launch_tally_stream(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts);
 // pipeline-internal: a step whose call kernel rides in the NEXT step's tally launch (api.cpp)
 int tcmi_step_begin_deferred(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int32_t mincov, int include_ambig, tcmi_ctx *prev);
 int tcmi_step_flush(tcmi_ctx *ctx);
@@ -359,3 +362,4 @@ int tcmi_launch_call(tcmi_ctx *ctx, int32_t *d_counts, int64_t L, int64_t ld, in
                      int32_t *d_events, int32_t *d_event_counts);
 
 static inline int64_t tcmi_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+static inline size_t tcmi_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }     // the pieces of device buffers start on 256 bytes
