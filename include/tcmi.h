@@ -162,6 +162,24 @@ int  tcmi_ctx_set_layout(tcmi_ctx *ctx, int32_t n_ref, const int64_t *shift, con
 int  tcmi_readset_ref_extents(const tcmi_readset *rs, int32_t n_ref, int64_t *max_end);
 /* mapped reads of a read set uploaded under a layout whose reference has no slot (shift < 0): dropped, not tallied */
 int  tcmi_readset_dropped(const tcmi_readset *rs, int64_t *n_dropped);
+/* ---- read filter (additive: the reference tallies every mapped record, indexing.py:100 stepper="nofilter") ---------------
+ * A record PASSES iff mapq >= min_mapq, (flag & require_flags) == require_flags and (flag & exclude_flags) == 0 — samtools view
+ * -q / -f / -F; MAPQ is a plain number (255 is not special).  A record that fails is ignored wherever an unmapped record (FLAG
+ * 0x4) is ignored: it is not kept, raises no refusal of its own (second reference, far position, slot overrun, long read from
+ * flat arrays, CG:B tag), is not counted as dropped under a layout, takes no part in the order asked of kept reads and gives no
+ * insert-candidate entry — every result equals the unfiltered result for the file without the failing records.  It is still a
+ * link of the record chain, and a structurally broken record still condemns the file.  min_mapq outside 0..255 or a flag word
+ * above 0xFFFF: TCMI_E_ARG.  The default 0, 0, 0 passes everything.
+ *   tcmi_ctx_set_read_filter  from now on governs every read set the context builds from a record stream decoded on the device
+ *                     (tcmi_readset_from_bamfile[_blocks], tcmi_bamfile_step, tcmi_split_step and its sub-range helper contexts,
+ *                     the file runner's contexts: tcmi_filerunner_ctx — the runner's host-reader fallbacks apply the filter of
+ *                     its contexts too).  The read set remembers the filter it was built under: tcmi_readset_modal_tokens and
+ *                     tcmi_readset_ins_entries apply it beside their flag_filter whatever the context is set to later.  Flat
+ *                     arrays (tcmi_readset_upload[_batch], tcmi_tally, tcmi_modal_tokens[_layout]) carry no MAPQ and are taken
+ *                     as given: whoever built them filters them (tcmi_bam_filter).
+ *   tcmi_readset_filtered     records of the file / block range that failed the filter the read set was built under */
+int  tcmi_ctx_set_read_filter(tcmi_ctx *ctx, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags);
+int  tcmi_readset_filtered(const tcmi_readset *rs, int64_t *n_filtered);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
  * "decode_batched" — files (or ranges) whose blocks the device decoder took in batches ("decode_token_mb");
@@ -346,6 +364,13 @@ int  tcmi_bam_info(const tcmi_bam *bam, int64_t *n_reads, int32_t *sorted, int64
 const char *tcmi_bam_text(const tcmi_bam *bam);    /* SAM header text, owned by bam                */
 /* name and length of reference i (0 <= i < n_ref) of the header; the name is owned by bam */
 int  tcmi_bam_ref(const tcmi_bam *bam, int32_t i, const char **name, int64_t *len);
+/* MAPQ of every record ([n_reads], owned by bam): struct tcmi_reads carries none */
+int  tcmi_bam_mapq(const tcmi_bam *bam, const uint8_t **mapq);
+/* The read filter of tcmi_ctx_set_read_filter for the host reader's output: removes the failing records from a loaded file in
+ * place — every per-read array, the offsets, names, mate fields and qualities are compacted, `sorted` and the span behind
+ * sorted_max_span are taken again over what is left — so that tcmi_bam_reads, tcmi_bam_info and everything behind them see the
+ * passing records only.  *n_removed (may be NULL): records removed by this call. */
+int  tcmi_bam_filter(tcmi_bam *bam, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, int64_t *n_removed);
 
 /* ---- BAM decoded ON THE DEVICE (the default file path; the host reader above stays for files it does not take) ----
  * tcmi_bamfile_read: HOST — file bytes into pinned memory, BGZF block table, BAM header (only the leading blocks the

@@ -1,0 +1,603 @@
+"""The read filter (--min-mapq / --require-flags / --exclude-flags; tcmi_ctx_set_read_filter, tcmi_bam_filter): a record passes iff
+mapq >= min_mapq, (flag & require) == require and (flag & exclude) == 0, and a record that fails is ignored wherever an unmapped
+one is.  The property checked on every path: file A (mixed records) UNDER the filter equals file B (the same records without the
+failing ones, in the same order) WITHOUT it — counts (also against the oracle's tally of the kept subset), extents, insert tokens,
+refusals, the four output files.  Every fixture asserts that 20 - 60 % of A's records fail: a condition on the input."""
+import ctypes as C
+import functools
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import c_oracle
+from tests import fuzz_reads as fz
+from tests import synth_small as ss
+from trueconsense_amd import TrueConsense as cli
+from trueconsense_amd import _ffi, distributed, engine
+from trueconsense_amd import synthetic as sy
+from trueconsense_amd.io import bamwriter
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+L = 2000
+MAPQS = (0, 1, 19, 20, 21, 60, 255)
+BITS = ((0x100, 0.1), (0x200, 0.1), (0x400, 0.25), (0x800, 0.1), (0x2, 0.75))      # FLAG bit, how often it is ORed in
+FILTERS = {"mapq": (20, 0, 0), "require": (0, 0x2, 0), "exclude": (0, 0, 0x500), "all": (1, 0x2, 0x400)}
+
+
+def passes(r, f):
+    return r["mapq"] >= f[0] and (r["flag"] & f[1]) == f[1] and (r["flag"] & f[2]) == 0
+
+
+def randomise(rng, specs):
+    """MAPQ from MAPQS and random filterable FLAG bits onto every record"""
+    for r in specs:
+        r["mapq"] = int(rng.choice(MAPQS))
+        for bit, p in BITS:
+            if rng.random() < p:
+                r["flag"] |= bit
+    return specs
+
+
+def arrays(specs):
+    d = ss.reads_from_spec({"reads": specs})
+    d["mapq"] = np.array([r["mapq"] for r in specs], np.uint8)
+    return d
+
+
+def kept(specs, f):
+    """B's records and the number that failed; the fixture's condition: 20 - 60 % fail, both classes there"""
+    b = [r for r in specs if passes(r, f)]
+    n_fail = len(specs) - len(b)
+    assert b and n_fail and 0.2 <= n_fail / len(specs) <= 0.6, (n_fail, len(specs))
+    return b, n_fail
+
+
+def _background(rng, ref, n, tid=0, tag=""):
+    """reads of 30 - 150 bases: plain, with an insertion, a deletion or soft clips; a few unmapped (FLAG 0x4) ones among them"""
+    out = []
+    for k in range(n):
+        ln = int(rng.integers(30, 151))
+        pos = int(rng.integers(0, len(ref) - ln - 8))
+        a = int(rng.integers(5, ln - 10))
+        shape = rng.random()
+        if shape < 0.7:
+            cig = [(ln, "M")]
+        elif shape < 0.8:
+            cig = [(a, "M"), (int(rng.integers(1, 4)), "I"), (ln - a, "M")]
+        elif shape < 0.9:
+            cig = [(a, "M"), (int(rng.integers(1, 6)), "D"), (ln - a, "M")]
+        else:
+            cig = [(3, "S"), (ln, "M"), (2, "S")]
+        flag = (16 if rng.random() < 0.5 else 0) | (4 if rng.random() < 0.02 else 0)
+        out.append(fz._read(rng, ref, pos, cig, flag, "%sr%d" % (tag, k), tid))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def mixed():
+    """-> (reference, GFF rows, A's records): ~3 000 background reads on L = 2 000 and three planted insertions (insert candidates)"""
+    rng = np.random.default_rng(20240)
+    ref, orfs = sy.make_reference(seed=3, L=L, cds=[(100, 900), (1100, 1900)])
+    specs = _background(rng, ref, 2400)
+    for c, n_ins in ((400, 2), (1000, 13), (1500, 5)):
+        specs += fz._site(rng, ref, L, c, "", 0, 200, "MI", n_ins, False)
+    specs.sort(key=lambda r: r["pos"])
+    return ref, orfs, randomise(rng, specs)
+
+
+def write_pair(tmp_path, specs, f, tag="", **kw):
+    """A and B as files -> (path A, path B, B's arrays, failing records)"""
+    b, n_fail = kept(specs, f)
+    pa, pb = str(tmp_path / (tag + "A.bam")), str(tmp_path / (tag + "B.bam"))
+    kw.setdefault("block", 4096)
+    kw.setdefault("ref_len", L)
+    bamwriter.write_bam(pa, arrays(specs), **kw)
+    rb = arrays(b)
+    bamwriter.write_bam(pb, rb, **kw)
+    return pa, pb, rb, n_fail
+
+
+# ------------------------------------------------------------------------------------------------------------------------ CPU
+def _files(tmp_path):
+    p = {}
+    for name in ("x.bam", "r.fa", "f.gff"):
+        (tmp_path / name).write_text("x")
+        p[name] = str(tmp_path / name)
+    return ["-i", p["x.bam"], "-ref", p["r.fa"], "-gff", p["f.gff"], "-cov", "30", "-name", "S", "-o", "o.fa"]
+
+
+def test_cli_parses_the_three_flags(tmp_path):
+    base = _files(tmp_path)
+    a = cli.GetArgs(base)
+    assert (a.min_mapq, a.require_flags, a.exclude_flags) == (0, 0, 0) and cli.read_filter_of(a) is None
+    a = cli.GetArgs(base + ["--min-mapq", "20", "--require-flags", "0x2", "--exclude-flags", "3840"])
+    assert cli.read_filter_of(a) == (20, 2, 0xF00)
+    a = cli.GetArgs(base + ["--exclude-flags", "0xFFFF", "--min-mapq", "255"])
+    assert cli.read_filter_of(a) == (255, 0, 0xFFFF)
+    for bad in (["--min-mapq", "256"], ["--min-mapq", "-1"], ["--min-mapq", "q"], ["--require-flags", "0x10000"], ["--exclude-flags", "65536"],
+                ["--exclude-flags", "-4"], ["--require-flags", "dup"]):
+        with pytest.raises(SystemExit) as e:
+            cli.GetArgs(base + bad)
+        assert e.value.code == 2, bad
+
+
+def test_gpus_children_get_the_filter_only_when_it_is_set(tmp_path):
+    base = _files(tmp_path)
+    for single in (True, False):
+        argv = cli._child_argv(cli.GetArgs(base), single)
+        assert not any(x.startswith(("--min-mapq", "--require", "--exclude")) for x in argv)
+        argv = cli._child_argv(cli.GetArgs(base + ["--min-mapq", "20", "--require-flags", "2", "--exclude-flags", "0x900"]), single)
+        child = cli.GetArgs(argv if single else argv + ["-i", base[1], "-name", "S", "-o", "o.fa"])
+        assert cli.read_filter_of(child) == (20, 2, 0x900)
+    argv = cli._child_argv(cli.GetArgs(base + ["--exclude-flags", "0x400"]), True)
+    assert "--min-mapq" not in argv and "--require-flags" not in argv and cli.read_filter_of(cli.GetArgs(argv)) == (0, 0, 0x400)
+
+
+def test_write_bam_writes_mapq_and_the_host_reader_gives_it_back(tmp_path):
+    _, _, specs = mixed()
+    rd = arrays(specs)
+    path = str(tmp_path / "A.bam")
+    bamwriter.write_bam(path, rd, ref_len=L, block=4096)
+    bam = engine.BamFile(path)
+    assert np.array_equal(bam.arrays()["mapq"], rd["mapq"]) and set(MAPQS) == set(rd["mapq"].tolist())
+    assert np.array_equal(c_oracle.read_bam(path)["mapq"], rd["mapq"])
+    assert bam.n_records == bam.n_reads == len(specs) and bam.n_removed == 0
+    bam.close()
+    del rd["mapq"]                                              # no mapq key: 60, as before
+    bamwriter.write_bam(path, rd, ref_len=L)
+    assert set(engine.BamFile(path).mapq().tolist()) == {60}
+    n = 50                                                      # the vectorised writer: one value, or one per read
+    pos, flag, seq = np.arange(n, dtype=np.int32) * 3, np.zeros(n, np.uint16), np.full((n, 10), 0x12, np.uint8)
+    bamwriter.write_bam_fast(path, pos, flag, seq, 20, ref_len=L)
+    assert set(engine.BamFile(path).mapq().tolist()) == {60}
+    mq = (np.arange(n) * 5).astype(np.uint8)
+    bamwriter.write_bam_fast(path, pos, flag, seq, 20, ref_len=L, mapq=mq)
+    assert np.array_equal(engine.BamFile(path).mapq(), mq)
+
+
+@pytest.mark.parametrize("name", sorted(FILTERS))
+@pytest.mark.parametrize("split_records", (False, True))
+def test_host_reader_filter_equals_the_file_without_the_failing_records(tmp_path, name, split_records):
+    """tcmi_bam_filter compacts every array: BamFile(A, read_filter=f).arrays() == BamFile(B).arrays(), array by array."""
+    f = FILTERS[name]
+    _, _, specs = mixed()
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f, split_records=split_records)
+    a, b = engine.BamFile(pa, read_filter=f), engine.BamFile(pb)
+    assert a.n_records == len(specs) and a.n_removed == n_fail and a.n_removed + a.n_reads == a.n_records
+    assert (a.n_reads, a.sorted, a.n_cigar, a.n_qual) == (b.n_reads, b.sorted, b.n_cigar, b.n_qual)
+    xa, xb = a.arrays(), b.arrays()
+    for k in xb:
+        if k not in ("_owner", "n_reads"):
+            assert np.array_equal(xa[k], xb[k]), k
+    assert np.array_equal(xa["mapq"], rb["mapq"]) and np.array_equal(xa["flag"], rb["flag"])
+    assert a.as_struct()[0].sorted_max_span == b.as_struct()[0].sorted_max_span > 0
+    cols = list(range(1, L + 1, 9)) + [401, 1001, 1501]
+    assert engine.modal_tokens(a, cols) == engine.modal_tokens(b, cols)
+    assert np.array_equal(c_oracle.tally(xa, L), c_oracle.tally(rb, L))
+    a.close()
+    b.close()
+
+
+def test_host_reader_filter_takes_sortedness_and_the_span_again(tmp_path):
+    """An out-of-place record and the longest read, both failing: the file is unsorted and wide before the filter, sorted and narrow
+    after it — as B is.  A filter that fails everything leaves an empty, sorted file; the zero filter changes nothing."""
+    rng = np.random.default_rng(5)
+    ref, _ = sy.make_reference(seed=3, L=L, cds=[])
+    specs = sorted(_background(rng, ref, 300), key=lambda r: r["pos"])
+    for r in specs:
+        r["mapq"] = 60 if rng.random() < 0.7 else 0
+    stray = fz._read(rng, ref, 5, [(40, "M")], 0, "stray")
+    wide = fz._read(rng, ref, 900, [(30, "M"), (900, "N"), (30, "M")], 0, "wide")
+    stray["mapq"] = wide["mapq"] = 0
+    specs.insert(200, stray)
+    specs.insert(next(i for i, r in enumerate(specs) if r["pos"] > 900), wide)
+    f = (20, 0, 0)
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f)
+    raw, a, b = engine.BamFile(pa), engine.BamFile(pa, read_filter=f), engine.BamFile(pb)
+    assert raw.sorted == 0 and raw.as_struct()[0].sorted_max_span == 0
+    assert a.sorted == b.sorted == 1 and 0 < a.as_struct()[0].sorted_max_span == b.as_struct()[0].sorted_max_span < 200
+    none = engine.BamFile(pa, read_filter=(0, 0x1000, 0))
+    assert none.n_reads == 0 and none.n_removed == none.n_records == len(specs) and none.sorted == 1 and none.arrays()["n_reads"] == 0
+    same = engine.BamFile(pa, read_filter=(0, 0, 0))
+    assert same.n_removed == 0 and np.array_equal(same.arrays()["pos"], raw.arrays()["pos"])
+
+
+@functools.lru_cache(maxsize=None)
+def token_case():
+    """-> (reference, A's records): fuzz_reads.token_specs (mate pairs, planted insertions) with one column more than 8 000 reads deep;
+    in 60 % of the proper pairs exactly one mate fails on MAPQ; in front of the deep column's 8 600 passing reads (file order) stand
+    3 000 failing ones: were they counted towards max_depth, the column would lose passing reads."""
+    rng = np.random.default_rng(1000)
+    ref, _ = sy.make_reference(seed=1, L=400, cds=[])
+    specs = fz.token_specs(rng, ref, deep=True)                 # (its own flags: every filtered kind, supplementary, orphans)
+    by_name = {}
+    for r in specs:
+        r["mapq"] = int(rng.choice(MAPQS))
+        by_name.setdefault(r["name"], []).append(r)
+    for name, rs in by_name.items():
+        if name.startswith("p") and len(rs) == 2 and rng.random() < 0.6:
+            k = int(rng.integers(0, 2))
+            rs[k]["mapq"], rs[1 - k]["mapq"] = int(rng.choice((0, 1, 19))), int(rng.choice((20, 21, 60, 255)))
+    first = next(i for i, r in enumerate(specs) if r["name"].startswith("d"))
+    c = 200
+    front = [fz._read(rng, ref, c - 4, [(5, "M"), (3, "I"), (4, "M")], 16 if k % 2 else 0, "x%d" % k) for k in range(3000)]
+    for r in front:
+        r["mapq"] = (0, 1, 19)[len(r["seq"]) % 3]
+    for r in specs:
+        if r["name"].startswith("d"):
+            r["mapq"] = 60
+    return ref, specs[:first] + front + specs[first:]
+
+
+TOKEN_F = (20, 0, 0)
+
+
+def test_host_sweep_of_filtered_a_equals_b(tmp_path):
+    _, specs = token_case()
+    assert sum(1 for r in specs if r["name"].startswith("p") and not passes(r, TOKEN_F)) >= 5
+    pa, pb, rb, _ = write_pair(tmp_path, specs, TOKEN_F, ref_len=400, block=0xFF00)
+    cols = list(range(1, 413))
+    a, b = engine.BamFile(pa, read_filter=TOKEN_F), engine.BamFile(pb)
+    got = engine.modal_tokens(a, cols)
+    assert got == engine.modal_tokens(b, cols) == engine.modal_tokens(rb, cols)
+    assert got[201][1] < engine.modal_tokens(b, [201], max_depth=0)[201][1]        # (max_depth cuts the deep column in B)
+    assert got != engine.modal_tokens(engine.BamFile(pa), cols)
+
+
+def test_argument_errors():
+    lib = _ffi.lib()
+    assert lib.tcmi_ctx_set_read_filter(None, 0, 0, 0) == _ffi.E_ARG
+    assert lib.tcmi_bam_filter(None, 0, 0, 0, None) == _ffi.E_ARG
+    assert lib.tcmi_readset_filtered(None, None) == _ffi.E_ARG
+    assert lib.tcmi_bam_mapq(None, None) == _ffi.E_ARG
+
+
+def test_bam_filter_argument_ranges(tmp_path):
+    _, _, specs = mixed()
+    path = str(tmp_path / "A.bam")
+    bamwriter.write_bam(path, arrays(specs[:50]), ref_len=L)
+    bam = engine.BamFile(path)
+    n = C.c_int64(7)
+    for bad in ((-1, 0, 0), (256, 0, 0), (0, 0x10000, 0), (0, 0, 0x10000)):
+        assert _ffi.lib().tcmi_bam_filter(bam.handle, *bad, C.byref(n)) == _ffi.E_ARG, bad
+        assert b"read filter" in _ffi.lib().tcmi_last_error(None)
+    assert _ffi.lib().tcmi_bam_filter(bam.handle, 255, 0xFFFF, 0, C.byref(n)) == 0 and n.value == 50
+    with pytest.raises(_ffi.TcmiError):
+        engine.BamFile(path, read_filter=(300, 0, 0))
+
+
+# ------------------------------------------------------------------------------------------------------------------------ GPU
+@pytest.fixture(scope="module")
+def ctx():
+    with engine.Context(0) as c:
+        yield c
+
+
+PATHS = ("one_sync", "several_kernels", "tally_variant_1", "host_reader", "host_reader_cigar_walk")
+
+
+def through(ctx, how, path, f, n_pos):
+    """the file under filter f on one path -> (counts, n_piled, max_end, filtered, records of the file).  tally_variant = 1 with the
+    device decoder (its packer builds the aligned set whatever the option says), and with the host reader, whose packer then sends
+    every read through the CIGAR-walk kernel."""
+    try:
+        ctx.set_option("tally_variant", int(how in ("tally_variant_1", "host_reader_cigar_walk")))
+        if how.startswith("host_reader"):
+            bam = engine.BamFile(path, read_filter=f)
+            rs = ctx.upload(bam)
+            counts = ctx.tally(bam, L=n_pos) if how == "host_reader" else ctx.step(rs, n_pos, 0, True)[3]
+            out = (counts, rs.n_piled, rs.max_end, bam.n_removed, bam.n_records)
+            rs.free()
+            bam.close()
+            return out
+        ctx.set_option("one_sync", int(how != "several_kernels"))
+        ctx.set_read_filter(*f)
+        d = engine.DeviceBam(path)
+        try:
+            t0 = ctx.stat("one_sync_taken")
+            rs = ctx.upload_bamfile(d)
+            assert ctx.stat("one_sync_taken") - t0 == int(how != "several_kernels"), (how, ctx.stat("one_sync_last_decline_flags"))
+            out = (ctx.step(rs, n_pos, 0, True)[3], rs.n_piled, rs.max_end, rs.filtered, rs.n_reads)
+            rs.free()
+            return out
+        finally:
+            d.close()
+    finally:
+        ctx.set_option("one_sync", 1)
+        ctx.set_option("tally_variant", 0)
+        ctx.set_read_filter()
+
+
+def check_pair(ctx, pa, pb, rb, f, n_fail, n_a, hows=PATHS):
+    n_pos = c_oracle.extent(rb, L)
+    want = c_oracle.tally(rb, n_pos)
+    for how in hows:
+        ca, piled_a, end_a, filt_a, rec_a = through(ctx, how, pa, f, n_pos)
+        cb, piled_b, end_b, filt_b, rec_b = through(ctx, how, pb, (0, 0, 0), n_pos)
+        assert np.array_equal(ca, cb) and np.array_equal(ca, want), how
+        assert (piled_a, end_a) == (piled_b, end_b) and (filt_a, filt_b) == (n_fail, 0), (how, piled_a, piled_b, filt_a, n_fail)
+        assert (rec_a, rec_b) == (n_a, n_a - n_fail), how
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", sorted(FILTERS))
+@pytest.mark.parametrize("split_records", (False, True))
+def test_counts_of_filtered_a_equal_b_and_the_oracle(ctx, tmp_path, name, split_records):
+    """Each criterion alone and all three together, whole records per block and records that straddle blocks, over the one-sync
+    packer, the several-kernel packer, the host reader and its CIGAR-walk tally."""
+    f = FILTERS[name]
+    _, _, specs = mixed()
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f, split_records=split_records)
+    d = engine.DeviceBam(pa)
+    assert d.n_blocks >= 24
+    d.close()
+    check_pair(ctx, pa, pb, rb, f, n_fail, len(specs))
+
+
+def _record_bytes(rd, i):
+    return 36 + int(rd["name_off"][i + 1] - rd["name_off"][i]) + 1 + 4 * int(rd["cigar_off"][i + 1] - rd["cigar_off"][i]) + \
+        (int(rd["l_qseq"][i]) + 1) // 2 + int(rd["l_qseq"][i])
+
+
+@pytest.mark.gpu
+def test_failing_records_at_block_edges(ctx, tmp_path):
+    """By hand: a failing record that is the first of its BGZF block, one that is the last of its block, a block of nothing but
+    failing records, and the file's last record failing (bamwriter cuts a block when the next record does not fit: replayed here)."""
+    rng = np.random.default_rng(9)
+    ref, _ = sy.make_reference(seed=3, L=L, cds=[])
+    specs = sorted(_background(rng, ref, 1500), key=lambda r: r["pos"])
+    for r in specs:
+        r["flag"] &= ~4
+        r["mapq"] = int(rng.choice((0, 19, 20, 21, 60, 255)))
+    rd = arrays(specs)
+    block, fill, blocks = 4096, 0, [[]]
+    for i in range(len(specs)):
+        n = _record_bytes(rd, i)
+        if fill and fill + n > block:
+            blocks.append([])
+            fill = 0
+        blocks[-1].append(i)
+        fill += n
+    assert len(blocks) >= 20
+    for i in [blocks[3][0], blocks[5][-1], len(specs) - 1] + blocks[7]:
+        specs[i]["mapq"] = 19
+    for i in blocks[6] + blocks[8] + blocks[3][1:] + blocks[5][:-1]:
+        specs[i]["mapq"] = 60                                   # (their neighbours pass)
+    f = (20, 0, 0)
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f)
+    d = engine.DeviceBam(pa)
+    assert d.n_blocks == len(blocks) + 2                        # (+ the header's block and the end-of-file block: the replay holds)
+    d.close()
+    check_pair(ctx, pa, pb, rb, f, n_fail, len(specs))
+
+
+@pytest.mark.gpu
+def test_long_reads_one_passing_one_failing(ctx, tmp_path):
+    """Two reads of about 700 positions (tally_stream_kernel walks them where they lie in the stream): only the passing one is listed."""
+    rng = np.random.default_rng(4)
+    ref, _ = sy.make_reference(seed=3, L=L, cds=[])
+    specs = [fz._read(rng, ref, 100, [(300, "M"), (5, "D"), (400, "M")], 0, "keep"), fz._read(rng, ref, 150, [(700, "M")], 16, "fail")]
+    specs[0]["mapq"], specs[1]["mapq"] = 20, 19
+    f = (20, 0, 0)
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f)
+    check_pair(ctx, pa, pb, rb, f, n_fail, 2)
+    ctx.set_read_filter(*f)
+    d = engine.DeviceBam(pa)
+    rs = ctx.upload_bamfile(d)
+    assert (rs.n_piled, rs.filtered) == (1, 1)
+    rs.free()
+    d.close()
+    ctx.set_read_filter()
+
+
+@pytest.mark.gpu
+def test_supplementary_records_on_a_second_reference(ctx, tmp_path):
+    """Two @SQ, reference 1 holds supplementary alignments only: refused today (a mapped read on a second reference), taken with
+    exclude_flags = 0x800 — on both packers and by the host reader — and equal to B."""
+    rng = np.random.default_rng(6)
+    ref, _ = sy.make_reference(seed=3, L=L, cds=[])
+    specs = sorted(_background(rng, ref, 600), key=lambda r: r["pos"])
+    for r in specs:
+        r["mapq"] = int(rng.choice(MAPQS))
+        r["flag"] = (r["flag"] & ~4) | (0x800 if rng.random() < 0.3 else 0)
+    other = [fz._read(rng, ref, 10 + 50 * k, [(60, "M")], 0x800, "sup%d" % k, 1) for k in range(5)]
+    for r in other:
+        r["mapq"] = 60
+    specs += other
+    f = (0, 0, 0x800)
+    refs = [("ref", L), ("other", L)]
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f, refs=refs)
+    for one_sync in (1, 0):
+        ctx.set_option("one_sync", one_sync)
+        d = engine.DeviceBam(pa)
+        with pytest.raises(_ffi.TcmiError) as e:
+            ctx.upload_bamfile(d)
+        d.close()
+        assert e.value.code == _ffi.E_UNSUPPORTED
+    ctx.set_option("one_sync", 1)
+    with pytest.raises(_ffi.TcmiError):
+        ctx.upload(engine.BamFile(pa))
+    check_pair(ctx, pa, pb, rb, f, n_fail, len(specs))
+
+
+@pytest.mark.gpu
+def test_a_filter_that_fails_everything_and_the_zero_filter(ctx, tmp_path):
+    _, _, specs = mixed()
+    pa = str(tmp_path / "A.bam")
+    bamwriter.write_bam(pa, arrays(specs), ref_len=L, block=4096)
+    for how in PATHS:
+        counts, piled, end, filtered, n_rec = through(ctx, how, pa, (0, 0x1000, 0), L)
+        assert not counts.any() and (piled, end, filtered, n_rec) == (0, 0, len(specs), len(specs)), how
+    d = engine.DeviceBam(pa)
+    rs = ctx.upload_bamfile(d)                                  # never set
+    never = (ctx.step(rs, L + 200, 0, True)[3], rs.n_piled, rs.max_end, rs.filtered)
+    rs.free()
+    d.close()
+    got = through(ctx, "one_sync", pa, (0, 0, 0), L + 200)
+    assert np.array_equal(got[0], never[0]) and got[1:4] == never[1:] and never[3] == 0
+    for bad in ((256, 0, 0), (-1, 0, 0), (0, 0x10000, 0), (0, 0, 1 << 20)):
+        with pytest.raises(_ffi.TcmiError) as e:
+            ctx.set_read_filter(*bad)
+        assert e.value.code == _ffi.E_ARG
+
+
+@pytest.mark.gpu
+def test_device_tokens_of_filtered_a_equal_b_and_the_read_set_remembers(ctx, tmp_path):
+    """ctx.readset_modal_tokens under both packers: mate pairs with one failing mate, and the deep column, where 3 000 failing reads
+    stand in front of 8 600 passing ones (max_depth = 8 000 admits passing reads only).  The read set keeps the filter it was built
+    under: with the context back at 0, 0, 0 its tokens are still B's."""
+    _, specs = token_case()
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, TOKEN_F, ref_len=400, block=0xFF00)
+    cols = list(range(1, 413))
+    want = engine.modal_tokens(rb, cols)
+    assert want[201][1] < engine.modal_tokens(rb, [201], max_depth=0)[201][1]      # (max_depth cuts the deep column in B)
+    for one_sync in (1, 0):
+        ctx.set_option("one_sync", one_sync)
+        db = engine.DeviceBam(pb)
+        rs = ctx.upload_bamfile(db)
+        assert ctx.readset_modal_tokens(rs, cols) == want
+        rs.free()
+        db.close()
+        da = engine.DeviceBam(pa)
+        ctx.set_read_filter(*TOKEN_F)
+        rs = ctx.upload_bamfile(da)
+        assert rs.filtered == n_fail
+        assert ctx.readset_modal_tokens(rs, cols) == want, one_sync
+        ctx.set_read_filter()                                   # the context forgets, the read set does not
+        assert ctx.readset_modal_tokens(rs, cols) == want, one_sync
+        ents = distributed._entries_of_readset(ctx, rs, cols)
+        rs.free()
+        rs = ctx.upload_bamfile(da)                             # ... and a read set built now sees every record
+        assert rs.filtered == 0 and ctx.readset_modal_tokens(rs, cols) != want
+        assert distributed._entries_of_readset(ctx, rs, cols)[1] != ents[1]
+        rs.free()
+        da.close()
+    ctx.set_option("one_sync", 1)
+
+
+def _gff(orfs, seqid="S"):
+    return [{"start": o["start"], "end": o["end"], "strand": o["strand"]} for o in orfs]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("split_sub", (1, 2))
+def test_one_file_over_three_ranks(tmp_path, split_sub):
+    """split_ranks_in_turn(A, world = 3, read_filter = f): counts, tokens and FASTA of the single-context run on B — the ranges in one
+    piece, and as two sub-ranges each (helper contexts take the filter along)."""
+    f = FILTERS["all"]
+    ref, orfs, specs = mixed()
+    big = specs if split_sub == 1 else None
+    if big is None:                                             # (sub-ranges want at least 64 blocks a piece: the same records four times over)
+        big = sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in specs], key=lambda r: r["pos"])
+    pa, pb, rb, n_fail = write_pair(tmp_path, big, f, block=1024 if split_sub == 2 else 4096)
+    n_pos = c_oracle.extent(rb, L)
+    tm = {}
+    ta = distributed.split_ranks_in_turn(pa, n_pos, _gff(orfs), 10, 3, return_parts=True, read_filter=f, split_sub=split_sub, timings=tm)
+    tb = distributed.split_ranks_in_turn(pb, n_pos, _gff(orfs), 10, 1, return_parts=True, split_sub=1)
+    assert ta[0] == tb[0] and np.array_equal(ta[1], tb[1]) and ta[2] == tb[2]
+    assert np.array_equal(ta[1], c_oracle.tally(rb, n_pos)) and len(ta[2]) >= 1
+    assert (tm["split_sub_taken"] > 0) == (split_sub == 2)
+
+
+def _outputs(tag):
+    vcf = [ln for ln in open(tag + ".vcf") if not ln.startswith("##")]
+    return open(tag + ".fa").read(), open(tag + ".gff").read(), open(tag + ".tsv").read(), vcf
+
+
+def _run_cli(monkeypatch, args):
+    monkeypatch.setattr(sys, "argv", ["TrueConsense", "ARGS"])
+    cli.main(args)
+
+
+FLAGS = ["--min-mapq", "1", "--require-flags", "0x2", "--exclude-flags", "1024"]       # FILTERS["all"]
+
+
+@pytest.mark.gpu
+def test_cli_single_sample_and_batch(tmp_path, monkeypatch):
+    """-i A with the three flags == -i B without, file by file (the VCF outside its ## header lines); --stats counts the failing
+    records and keeps `reads` the file's record count; the same through --batch (the native runner), the straddling layout included."""
+    monkeypatch.chdir(tmp_path)
+    f = FILTERS["all"]
+    ref, orfs, specs = mixed()
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f)
+    pa2, pb2, _, _ = write_pair(tmp_path, specs, f, tag="s", split_records=True)
+    open("r.fa", "w").write(">ref x\n" + ref + "\n")
+    head, body = sy.gff_text(orfs, seqid="ref")
+    open("g.gff", "w").write(head + body)
+    common = ["-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S"]
+    for tag, bam, extra in (("a", pa, FLAGS), ("b", pb, [])):
+        _run_cli(monkeypatch, ["-i", bam] + common + ["-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv",
+                                                      "--stats", tag + ".json"] + extra)
+    assert _outputs("a") == _outputs("b") and len(open("a.fa").read().split("\n")[1]) > L       # (a planted insertion was taken)
+    sa, sb = json.load(open("a.json")), json.load(open("b.json"))
+    assert (sa["reads"], sa["reads_filtered"]) == (len(specs), n_fail) and (sb["reads"], sb["reads_filtered"]) == (len(specs) - n_fail, 0)
+    assert open("a.tsv").read() != _unfiltered(monkeypatch, pa, common)
+    for tag, bams, extra in (("ma", (pa, pa2), FLAGS), ("mb", (pb, pb2), [])):
+        with open(tag + ".tsv.in", "w") as fh:
+            for k, bam in enumerate(bams):
+                fh.write("\t".join([bam, "S"] + ["%s%d.%s" % (tag, k, e) for e in ("fa", "vcf", "gff", "tsv")]) + "\n")
+        _run_cli(monkeypatch, ["--batch", tag + ".tsv.in", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10"] + extra)
+    for k in (0, 1):
+        assert _outputs("ma%d" % k) == _outputs("mb%d" % k) == _outputs("b"), k
+
+
+def _unfiltered(monkeypatch, bam, common):
+    """(the process's one context is back at no filter for a run without the flags)"""
+    _run_cli(monkeypatch, ["-i", bam] + common + ["-o", "raw.fa", "-doc", "raw.tsv"])
+    return open("raw.tsv").read()
+
+
+@pytest.mark.gpu
+def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
+    """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange): the children get the flags, every rank sets the filter."""
+    monkeypatch.chdir(tmp_path)
+    f = FILTERS["all"]
+    ref, orfs, specs = mixed()
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f, split_records=True)
+    open("r.fa", "w").write(">ref x\n" + ref + "\n")
+    head, body = sy.gff_text(orfs, seqid="ref")
+    open("g.gff", "w").write(head + body)
+    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=ROOT)
+    for tag, bam, extra in (("a", pa, FLAGS + ["--gpus", "2"]), ("b", pb, [])):
+        argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", bam, "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S",
+                "-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv"] + extra
+        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-1500:]
+    assert _outputs("a") == _outputs("b")
+
+
+@pytest.mark.gpu
+def test_cli_per_contig(tmp_path, monkeypatch):
+    """--per-contig on two contigs: extents, the dropped count and the host sweep of the insert candidates see passing records only."""
+    monkeypatch.chdir(tmp_path)
+    f = FILTERS["all"]
+    rng = np.random.default_rng(8)
+    recs, rows, specs = [], [], []
+    for t, (name, ln) in enumerate((("c0", 1500), ("c1", 1200))):
+        ref, orfs = sy.make_reference(seed=30 + t, L=ln, cds=[(100, 700)])
+        recs.append((name, ref))
+        rows.append((name, orfs))
+        part = _background(rng, ref, 900, tid=t, tag=name)
+        part += fz._site(rng, ref, ln, 800, name, t, 200, "MI", 3, False)
+        specs += sorted(part, key=lambda r: r["pos"])
+    extra = [fz._read(rng, recs[0][1], 20 * k, [(50, "M")], 0, "x%d" % k, 2) for k in range(30)]       # a reference the FASTA does not name
+    specs = randomise(rng, specs + extra)
+    pa, pb, rb, n_fail = write_pair(tmp_path, specs, f, refs=[("c0", 1500), ("c1", 1200), ("X", 900)])
+    with open("r.fa", "w") as fh:
+        for name, ref in recs:
+            fh.write(">%s\n%s\n" % (name, ref))
+    with open("g.gff", "w") as fh:
+        fh.write("##gff-version 3\n")
+        for name, orfs in rows:
+            fh.write(sy.gff_text(orfs, seqid=name)[1])
+    for tag, bam, more in (("a", pa, FLAGS), ("b", pb, [])):
+        _run_cli(monkeypatch, ["-i", bam, "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "-o", tag + ".fa", "-vcf", tag + ".vcf",
+                               "-ogff", tag + ".gff", "-doc", tag + ".tsv", "--per-contig", "--stats", tag + ".json"] + more)
+    assert _outputs("a") == _outputs("b") and open("a.fa").read().count(">") == 2
+    sa, sb = json.load(open("a.json")), json.load(open("b.json"))
+    assert sa["dropped_reads"] == sb["dropped_reads"] == sum(1 for r in extra if passes(r, f) and not r["flag"] & 4) > 0
+    assert (sa["reads"], sa["reads_filtered"], sb["reads_filtered"]) == (len(specs), n_fail, 0)

@@ -3,7 +3,9 @@
     python -m trueconsense_amd.TrueConsense -i x.bam -ref r.fa -gff r.gff -cov 30 -name S -o out.fa
         [-vcf out.vcf] [-doc cov.tsv] [-ogff out.gff] [-t N] [-noambig] [--index-override f.csv.gz]
 
-Additive flags (not in the reference): --device N (GPU ordinal), --stats FILE (JSON timings), and
+Additive flags (not in the reference): --device N (GPU ordinal), --stats FILE (JSON timings), the read filter
+--min-mapq N / --require-flags F / --exclude-flags F (samtools view -q / -f / -F: a record that fails is ignored as an unmapped
+one is; the reference tallies every mapped record), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -44,6 +46,28 @@ def _file_arg(parser, suffixes, what, missing_exit, multi_suffix=False):
             parser.error(f"{what[0]} {color.YELLOW}({fname}){color.END} doesn't seem to be {what[1]}.")
         return fname
     return check
+
+
+def _range_arg(parser, flag, hi):
+    """argparse `type=` callable: an integer in 0..hi, decimal or 0x... (else parser.error, exit code 2)."""
+    def check(text):
+        try:
+            v = int(text, 0)
+        except ValueError:
+            try:
+                v = int(text, 10)
+            except ValueError:
+                v = -1
+        if not 0 <= v <= hi:
+            parser.error(f"{flag} takes an integer from 0 to {hi} (decimal or 0x...), not {color.YELLOW}{text}{color.END}.")
+        return v
+    return check
+
+
+def read_filter_of(a):
+    """The parsed namespace's read filter -> (min_mapq, require_flags, exclude_flags), or None when none was asked for."""
+    f = (a.min_mapq, a.require_flags, a.exclude_flags)
+    return f if any(f) else None
 
 
 def GetArgs(givenargs):
@@ -94,6 +118,13 @@ def GetArgs(givenargs):
     additive.append((("--per-contig",), dict(action="store_true",
                                              help="one consensus per record of -ref (a multi-record reference, e.g. a segmented virus):\n"
                                                   "records named {name}_{record}, all in -o; -vcf / -ogff / -doc cover every record")))
+    additive.append((("--min-mapq",), dict(type=_range_arg(parser, "--min-mapq", 255), default=0, metavar="N",
+                                           help="ignore alignment records with MAPQ below N (samtools view -q)")))
+    additive.append((("--require-flags",), dict(type=_range_arg(parser, "--require-flags", 0xFFFF), default=0, metavar="F",
+                                                help="ignore records that lack any of these FLAG bits (samtools view -f; decimal or 0x...)")))
+    additive.append((("--exclude-flags",), dict(type=_range_arg(parser, "--exclude-flags", 0xFFFF), default=0, metavar="F",
+                                                help="ignore records with any of these FLAG bits, e.g. 0x400 duplicates, 0x900 secondary\n"
+                                                     "and supplementary (samtools view -F; decimal or 0x...)")))
     # (is this the --batch form?  asked of a small parser of its own: "--batch=FILE" and argparse's abbreviations count too)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--batch", default=None)
@@ -145,6 +176,11 @@ def _child_argv(a, single):
     out = ["-ref", a.reference, "-gff", a.features, "-cov", str(a.coverage_level), "-t", str(a.threads)]
     if a.noambiguity:
         out.append("-noambig")
+    if a.min_mapq:                                  # (the read filter, only where one was asked for)
+        out += ["--min-mapq", str(a.min_mapq)]
+    for flag, v in (("--require-flags", a.require_flags), ("--exclude-flags", a.exclude_flags)):
+        if v:
+            out += [flag, "0x%x" % v]
     if single:
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]
         for flag, v in (("-vcf", a.variants), ("-doc", a.depth_of_coverage), ("-ogff", a.output_gff)):
@@ -225,7 +261,7 @@ def run_batch(a):
     cores = max(1, min(int(a.threads), os.cpu_count() or 1))
     runner = FileRunner(int(os.environ.get("TCMI_DEVICE", "0")), gffrows, a.coverage_level, a.noambiguity is False,
                         decoders=min(4, max(1, cores // 4)), decode_threads=max(1, cores // 2), walkers=min(4, max(1, cores // 4)),
-                        gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1)
+                        gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a))
     runner.set_outputs(refID, refseq, vcf_header(date.today().strftime("%Y%m%d"), sys.argv[1:], a.reference, refID), IndexGff.header.raw_text,
                        [gff_row_columns(r) for r in gffrows])
     try:
@@ -295,8 +331,10 @@ def main(args=None):
         return run_per_contig(a)
     t = {"start": time.perf_counter()}
 
-    from .engine import LazyBam
-    bam = LazyBam(a.input, threads=a.threads)       # reads reach the host only if an insert candidate needs its tokens
+    from .engine import LazyBam, read_filter_args
+    flt = read_filter_of(a)
+    _state.default_context().set_read_filter(*read_filter_args(flt))       # (always: the process's one context may have served another call)
+    bam = LazyBam(a.input, threads=a.threads, read_filter=flt)      # reads reach the host only if an insert candidate needs its tokens
     t["bam_open"] = time.perf_counter()
     counts = build_counts(bam, a.reference)         # decoded, packed and tallied on the device
     IndexGff = Gffindex(a.features)
@@ -324,7 +362,7 @@ def main(args=None):
         with open(a.stats, "w") as fh:
             secs = {k: t[k] - t[keys[i - 1]] for i, k in enumerate(keys) if i}
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
-            json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads,
+            json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "bam_bytes": os.path.getsize(a.input)}, fh)
 
 

@@ -56,6 +56,8 @@ _SIGS = {
     "tcmi_readset_ref_extents": (_int, [_vp, _i32, _vp]),
     "tcmi_readset_dropped": (_int, [_vp, _P(_i64)]),
     "tcmi_ctx_stat": (_int, [_vp, C.c_char_p, _P(_i64)]),
+    "tcmi_ctx_set_read_filter": (_int, [_vp, _i32, _u32, _u32]),
+    "tcmi_readset_filtered": (_int, [_vp, _P(_i64)]),
     "tcmi_profile_enable": (_int, [_vp, _int]),
     "tcmi_profile_reset": (_int, [_vp]),
     "tcmi_profile_get": (_int, [_vp, _int, _P(C.c_double), _P(_i64)]),
@@ -92,6 +94,8 @@ _SIGS = {
     "tcmi_bam_ref": (_int, [_vp, _i32, _P(C.c_char_p), _P(_i64)]),
     "tcmi_bam_info": (_int, [_vp, _P(_i64), _P(_i32), _P(_i64), _P(_i64), _P(_i64), _P(_i64), _P(_i64)]),
     "tcmi_bam_text": (C.c_char_p, [_vp]),
+    "tcmi_bam_mapq": (_int, [_vp, _P(_P(C.c_uint8))]),
+    "tcmi_bam_filter": (_int, [_vp, _i32, _u32, _u32, _P(_i64)]),
     "tcmi_bamfile_read": (_int, [C.c_char_p, _P(_vp)]),
     "tcmi_bamfile_free": (_int, [_vp]),
     "tcmi_bamfile_info": (_int, [_vp, _P(_i64), _P(_i64), _P(_i64), _P(_i32), _P(C.c_char_p), _P(_i64)]),

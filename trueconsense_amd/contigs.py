@@ -22,7 +22,7 @@ from datetime import date
 import numpy as np
 
 from . import _ffi, _state
-from .engine import BamFile, DeviceBam, modal_tokens
+from .engine import BamFile, DeviceBam, modal_tokens, read_filter_args
 from .Events import _parse_token, candidates_from_flags
 from .io import fasta
 from .indexing import Gffindex
@@ -110,12 +110,16 @@ def _name_slot_overrun(err, host, header_names):
     return ContigError('read "%s" on contig "%s" ends past the end of the contig\'s slot (its length + %d positions)' % (read, contig, GUARD))
 
 
-def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True):
+def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
+                 info=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
-    first; a file it declines goes through the host reader (same layout)."""
+    first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
+    exclude_flags): extents, `dropped` and the host BamFile see the passing records only; info (a dict) receives "reads" (the
+    file's records) and "reads_filtered"."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
+    ctx.set_read_filter(*read_filter_args(read_filter))
     host = None
     try:
         rs = None
@@ -128,24 +132,29 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         finally:
             d.close()
         if rs is None:
-            host = BamFile(path, threads=threads)
+            host = BamFile(path, threads=threads, read_filter=read_filter)
             try:
                 rs = ctx.upload(host)
             except _ffi.TcmiError as e:
                 raise _name_slot_overrun(e, host, header_names) from e
         try:
             ext, dropped = rs.ref_extents(n_ref), rs.dropped()
+            if info is not None:
+                info.update(reads=host.n_records if host is not None else rs.n_reads, reads_filtered=host.n_removed if host is not None else rs.filtered)
             plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
         finally:
             rs.free()
     finally:
         ctx.set_layout()
+        ctx.set_read_filter()
     return plain, alt, flags, counts, ext, dropped, host
 
 
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
-    -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name}."""
+    -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
+    from .TrueConsense import read_filter_of
+    flt, seen = read_filter_of(a), {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
     hdr_names, hdr_lens = bam_header_refs(a.input)
@@ -155,7 +164,7 @@ def run(a):
     ctx = _state.default_context()
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
-                                                                 threads=a.threads, want_counts=want_counts)
+                                                                 threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen)
 
     # every contig's slice of the call records (the call is position-local: a slice's records are the split run's)
     per = []
@@ -171,7 +180,7 @@ def run(a):
     toks = {}
     if cand:
         if host is None:
-            host = BamFile(a.input, threads=a.threads)
+            host = BamFile(a.input, threads=a.threads, read_filter=flt)
         toks = {p: t for p, (t, _) in modal_tokens(host, [g for _, g in cand], layout=(shift, slot)).items()}
 
     today = date.today().strftime("%Y%m%d")
@@ -214,4 +223,4 @@ def run(a):
             out.write("".join(doc))
     with open(a.output, "w") as out:
         out.write("".join(fa))
-    return {"contigs": len(records), "dropped_reads": int(dropped)}
+    return dict({"contigs": len(records), "dropped_reads": int(dropped)}, **seen)

@@ -256,6 +256,15 @@ int tcmi_ctx_set_option(tcmi_ctx *c, const char *key, int value)
 
 } // extern "C"
 
+int tcmi_read_filter_build(tcmi_ctx *ctx, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, tcmi_read_filter *out)
+{
+    if (min_mapq < 0 || min_mapq > 255) return tcmi_fail(ctx, TCMI_E_ARG, "read filter: min_mapq %d is outside 0..255", (int)min_mapq);
+    if (require_flags > 0xFFFFu || exclude_flags > 0xFFFFu)
+        return tcmi_fail(ctx, TCMI_E_ARG, "read filter: flag words 0x%x / 0x%x do not fit the 16 bits of a BAM FLAG", require_flags, exclude_flags);
+    out->min_mapq = (uint32_t)min_mapq; out->require = require_flags; out->exclude = exclude_flags;
+    return TCMI_OK;
+}
+
 int tcmi_layout_build(int32_t n_ref, const int64_t *shift, const int64_t *slot_len, tcmi_layout *out, char *msg, size_t msg_cap)
 {
     out->shift.clear(); out->end.clear();
@@ -301,6 +310,16 @@ int tcmi_ctx_set_layout(tcmi_ctx *c, int32_t n_ref, const int64_t *shift, const 
         ++c->lay_gen;                                        // (clearing the layout leaves the table as it is)
     }
     c->layout = std::move(L);
+    return TCMI_OK;
+}
+
+int tcmi_ctx_set_read_filter(tcmi_ctx *c, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    tcmi_read_filter f = {0, 0, 0};
+    const int rc = tcmi_read_filter_build(c, min_mapq, require_flags, exclude_flags, &f);
+    if (rc) return rc;
+    c->flt = f;                                                 // (a kernel argument of the next upload: nothing queued reads it)
     return TCMI_OK;
 }
 
@@ -736,6 +755,7 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     for (tcmi_ctx *h : ctx->helpers) {                          // (the caller's decoder options)
         h->verify_crc = ctx->verify_crc; h->decode_token_mb = ctx->decode_token_mb; h->one_sync = ctx->one_sync; h->mid_wait = ctx->mid_wait;
         h->prefix_kernels = ctx->prefix_kernels; h->h2d_pieces = ctx->h2d_pieces; h->sym_scratch_div = ctx->sym_scratch_div; h->prof = false;
+        h->flt = ctx->flt;
     }
     TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));            // (the matrix is zero before anybody adds to it)
     std::vector<tcmi_readset *> rs((size_t)K, nullptr);
@@ -810,11 +830,12 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     tcmi_readset *sum = new tcmi_readset();
     sum->device = ctx->device; sum->packed_on_device = 2;
     sum->range_first = rs[0]->range_first; sum->range_next = rs[(size_t)K - 1]->range_next;
+    sum->flt = ctx->flt;
     for (int k = 0; k < K; ++k) {
         const tcmi_readset *r = rs[(size_t)k];
         sum->n_reads += r->n_reads; sum->n_piled += r->n_piled; sum->alg_bytes += r->alg_bytes; sum->dev_bytes += r->dev_bytes;
         sum->max_end = std::max(sum->max_end, r->max_end); sum->max_len = std::max(sum->max_len, r->max_len); sum->s_reads += r->s_reads;
-        sum->f_reads += r->f_reads;
+        sum->f_reads += r->f_reads; sum->n_filtered += r->n_filtered;
         sum->parts.push_back({k == 0 ? ctx : ctx->helpers[(size_t)k - 1], rs[(size_t)k]});
     }
     *out = sum;

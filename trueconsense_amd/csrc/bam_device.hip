@@ -787,9 +787,11 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
     if (n_reads_out) *n_reads_out = (int64_t)D.n;
     tcmi_pack_src s = {};
     s.stream = D.d_out; s.rec_off = D.d_rec; s.n = (int64_t)D.n; s.mode = 1; s.pos_shift = 0;
+    s.flt = tcmi_filter_pack(ctx->flt);
     tcmi_readset *rs = new tcmi_readset();
     rs->uid = g_next_uid.fetch_add(1);
     rs->n_reads = (int64_t)D.n;
+    rs->flt = ctx->flt;
     rs->device = ctx->device;
     uint32_t why = 0;
     rc = D.n ? tcmi_pack_on_device(ctx, &s, rs, &why) : TCMI_OK;

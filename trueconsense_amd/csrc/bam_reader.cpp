@@ -353,6 +353,79 @@ int tcmi_bam_reads(const tcmi_bam *bam, tcmi_reads *reads)
     return TCMI_OK;
 }
 
+int tcmi_bam_mapq(const tcmi_bam *bam, const uint8_t **mapq)
+{
+    if (!bam || !mapq) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    *mapq = bam->mapq.data();
+    return TCMI_OK;
+}
+
+// The read filter for the host reader's output: the passing records moved to the front of every array, in order (record w of the
+// result is the w-th passing record; w <= i throughout, so nothing is overwritten before it has been read), then `sorted` and the
+// longest span taken again over what is left, as tcmi_bam_load takes them.
+int tcmi_bam_filter(tcmi_bam *bam, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, int64_t *n_removed)
+{
+    if (!bam) return tcmi_fail(nullptr, TCMI_E_ARG, "bam is NULL");
+    tcmi_read_filter f = {0, 0, 0};
+    const int rc = tcmi_read_filter_build(nullptr, min_mapq, require_flags, exclude_flags, &f);
+    if (rc) return rc;
+    if (n_removed) *n_removed = 0;
+    if (!tcmi_filter_on(f)) return TCMI_OK;
+    const int64_t n = bam->n;
+    int64_t w = 0;
+    uint64_t co = 0, so = 0, qo = 0, no = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const size_t si = (size_t)i;
+        if (!tcmi_filter_pass(f, bam->flag[si], bam->mapq[si])) continue;
+        const uint64_t c0 = bam->cigar_off[si], nc = bam->cigar_off[si + 1] - c0, s0 = bam->seq_off[si], ns = bam->seq_off[si + 1] - s0,
+                       q0 = bam->qual_off[si], nq = bam->qual_off[si + 1] - q0, m0 = bam->name_off[si], nn = bam->name_off[si + 1] - m0;
+        const size_t sw = (size_t)w;
+        if (w != i) {
+            std::memmove(bam->cigar.data() + co, bam->cigar.data() + c0, (size_t)nc * 4);
+            std::memmove(bam->seq.data() + so, bam->seq.data() + s0, (size_t)ns);
+            std::memmove(bam->qual.data() + qo, bam->qual.data() + q0, (size_t)nq);
+            std::memmove(bam->names.data() + no, bam->names.data() + m0, (size_t)nn);
+            bam->pos[sw] = bam->pos[si]; bam->l_qseq[sw] = bam->l_qseq[si]; bam->tid[sw] = bam->tid[si];
+            bam->next_tid[sw] = bam->next_tid[si]; bam->next_pos[sw] = bam->next_pos[si]; bam->tlen[sw] = bam->tlen[si];
+            bam->flag[sw] = bam->flag[si]; bam->mapq[sw] = bam->mapq[si];
+        }
+        bam->cigar_off[sw] = co; bam->seq_off[sw] = so; bam->qual_off[sw] = qo; bam->name_off[sw] = no;
+        co += nc; so += ns; qo += nq; no += nn;
+        ++w;
+    }
+    const size_t k = (size_t)w;
+    bam->cigar_off[k] = co; bam->seq_off[k] = so; bam->qual_off[k] = qo; bam->name_off[k] = no;
+    bam->cigar_off.resize(k + 1); bam->seq_off.resize(k + 1); bam->qual_off.resize(k + 1); bam->name_off.resize(k + 1);
+    bam->pos.resize(k); bam->l_qseq.resize(k); bam->tid.resize(k); bam->next_tid.resize(k); bam->next_pos.resize(k); bam->tlen.resize(k);
+    bam->flag.resize(k); bam->mapq.resize(k);
+    // (the buffers keep their allocation; what they hold ends with a zero element, as tcmi_bam_load leaves them)
+    bam->cigar.data()[co] = 0; bam->seq.data()[so] = 0; bam->qual.data()[qo] = 0;
+    bam->cigar.n = (size_t)co + 1; bam->seq.n = (size_t)so + 1; bam->qual.n = (size_t)qo + 1; bam->names.n = (size_t)no + 1;
+    if (n_removed) *n_removed = n - w;
+    bam->n = w;
+    // sorted and the longest span, over what is left (the rule of tcmi_bam_load's fill)
+    bam->sorted = 1;
+    bam->max_span = 0;
+    int32_t last_tid = 0, last_pos = -1;
+    bool seen_unplaced = false;
+    for (size_t i = 0; i < k; ++i) {
+        int64_t span = 0;
+        for (uint64_t c = bam->cigar_off[i]; c < bam->cigar_off[i + 1]; ++c) {
+            const unsigned op = bam->cigar.data()[c] & 0xF;
+            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += bam->cigar.data()[c] >> 4;
+        }
+        bam->max_span = std::max(bam->max_span, span);
+        const int32_t tid = bam->tid[i], pos = bam->pos[i];
+        if (tid < 0) seen_unplaced = true;
+        else {
+            if (seen_unplaced || tid < last_tid || (tid == last_tid && pos < last_pos)) bam->sorted = 0;
+            last_tid = tid;
+            last_pos = pos;
+        }
+    }
+    return TCMI_OK;
+}
+
 int tcmi_bam_ref(const tcmi_bam *bam, int32_t i, const char **name, int64_t *len)
 {
     if (!bam || i < 0 || (size_t)i >= bam->ref_name.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "no reference %d in the header", i);

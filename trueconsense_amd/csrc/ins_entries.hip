@@ -47,7 +47,7 @@ __global__ __launch_bounds__(PB) void ins_entries_kernel(InsArgs a)
     const int32_t col = a.cols[k];
     const uint32_t i = a.c_idx[j];
     const ReadView v = view(a.src, i);
-    if (v.flag & a.flag_filter) return;
+    if ((v.flag & a.flag_filter) || !passes(a.src.flt, v)) return;   // (the read set's own filter: no failing record is among the kept reads; tested all the same)
     if (a.ignore_orphans && (v.flag & 0x1u) && !(v.flag & 0x2u)) return;
     // the op that covers the column
     int64_t x = v.pos, y = 0;

@@ -13,12 +13,14 @@ inline PackSrc stream_src(const tcmi_readset *rs)
 {
     PackSrc s = {};
     s.stream = rs->d_stream; s.rec_off = rs->d_rec_off; s.mode = 1; s.n = rs->n_reads;
+    s.flt = tcmi_filter_pack(rs->flt);          // (the filter the read set was built under)
     return s;
 }
 
 struct ReadView {
     int32_t tid, pos, l_seq;
     uint32_t flag, n_cigar;
+    uint32_t mapq;              // (flat arrays carry none: 255)
     const uint8_t *cigar;       // n_cigar little-endian words, not necessarily aligned
     const uint8_t *seq;         // ceil(l_seq / 2) bytes
     bool bad;                   // inconsistent offsets / lengths
@@ -48,6 +50,7 @@ __device__ inline ReadView view_rec(const uint8_t *rec)
     v.pos = (int32_t)h[2];
     const uint32_t w2 = h[3], w3 = h[4];
     const uint32_t l_name = w2 & 0xFFu;
+    v.mapq = (w2 >> 8) & 0xFFu;
     v.n_cigar = w3 & 0xFFFFu;
     v.flag = w3 >> 16;
     v.l_seq = (int32_t)h[5];
@@ -74,6 +77,7 @@ __device__ inline ReadView view(const PackSrc &s, int64_t i)
         v.pos = s.pos[i];
         v.l_seq = s.l_qseq[i];
         v.flag = s.flag[i];
+        v.mapq = 255u;
         const uint64_t c0 = s.cigar_off[i], c1 = s.cigar_off[i + 1], q0 = s.seq_off[i], q1 = s.seq_off[i + 1];
         v.bad = c1 < c0 || c1 - c0 > 65535u || q1 < q0 || v.l_seq < 0 || (int64_t)(q1 - q0) < ((int64_t)v.l_seq + 1) / 2;
         v.n_cigar = v.bad ? 0u : (uint32_t)(c1 - c0);
@@ -81,6 +85,13 @@ __device__ inline ReadView view(const PackSrc &s, int64_t i)
         v.seq = s.seq + q0;
     } else v = view_rec(s.stream + s.rec_off[i]);
     return v;
+}
+
+// the read filter (tcmi_ctx_set_read_filter): a record that fails is ignored wherever an unmapped one is
+__device__ inline bool filter_on(const tcmi_filter_words &f) { return (f.flags | f.min_mapq) != 0u; }
+__device__ inline bool passes(const tcmi_filter_words &f, const ReadView &v)
+{
+    return (v.flag & f.flags & 0xFFFFu) == (f.flags >> 16) && v.mapq >= f.min_mapq;
 }
 
 __device__ inline uint32_t nib_at(const uint8_t *seq, int32_t q)

@@ -85,6 +85,7 @@ struct PackTotals {                 // device scalars, copied back to the host
     unsigned long long range_first, range_next;
     unsigned long long slot_ovf;    // a contig layout: (read index + 1) << 24 | reference of the last kept read that ends past its slot (0: none)
     unsigned long long n_dropped;   // a contig layout: mapped reads on references without a slot
+    uint32_t n_filtered;            // a read filter: records that failed it (records are fewer than 2^31: PKF_REC_OVF)
 };
 
 // words a read takes in the plane stream: its pairs, the zero pair behind them, and — for an even number of pairs — one more zero pair,
@@ -116,6 +117,21 @@ __device__ inline uint2 block_scan2(uint2 v, uint2 *wave_tot /* LDS [PB / 64] */
 // its end; `longread`: left to tally_stream_kernel (a device-decoded stream only; from flat arrays PKF_LONG is raised instead)
 struct Classified { uint32_t word, nwords, len; unsigned long long alg; int32_t end; bool longread, slot_ovf; };
 
+// The read filter, where a record enters the packer: a record that fails is marked unmapped — from here on it is ignored wherever a
+// record with FLAG 0x4 is — and counted: one ballot over the lanes that are here and one atomic per wavefront that holds any (the lanes
+// of a wavefront's tail are not here: the lowest failing lane adds).  Without a filter (both words 0) every record passes: no atomic.
+// pk_classify asks filter_on first (uniform) and skips the compares too; pk_index, which sits at the scalar-register ceiling, does
+// not — the branch around these few instructions cost it two more vector registers than the instructions themselves.
+__device__ inline void filter_view(ReadView &v, const tcmi_filter_words &flt, PackTotals *tot)
+{
+    const bool failed = !passes(flt, v);
+    const unsigned long long m = __ballot(failed);
+    if (failed) {
+        v.flag |= 0x4u;
+        if ((int)(threadIdx.x & 63) == (int)__builtin_ctzll(m)) atomicAdd(&tot->n_filtered, (uint32_t)__popcll(m));
+    }
+}
+
 __device__ inline int32_t slot_end_of(const PackSrc &s, int32_t tid) { return s.n_lay == 0 ? 0x7FFFFFFF : s.lay[s.n_lay + tid]; }
 
 // the kept reads' max end per reference (a contig layout): called by every lane of the wavefront; one atomic per reference the
@@ -138,7 +154,8 @@ __device__ inline void ref_extent_max(int32_t *ext, int32_t t, int32_t e)
 }
 
 // `shift`: where the read's reference starts on the axis (< 0: not piled up), `slot_end`: where its slot ends, `layout`: a contig
-// layout is set (reads on other references are not an error then)
+// layout is set (reads on other references are not an error then).  The read filter: the callers hand a failing record in with FLAG
+// 0x4 set (filter_view) — it is ignored in the three places below, and in pk_classify's `dropped`, exactly as an unmapped record is
 __device__ inline Classified classify_view(const ReadView &v, int32_t mode, int32_t shift, int32_t slot_end, bool layout, const uint8_t *rec,
                                            bool stream_long_ok, PackTotals *tot)
 {
@@ -203,7 +220,8 @@ __global__ __launch_bounds__(PB) void pk_classify(PackSrc s, uint32_t *info, uin
     int32_t my_tid = -1, my_lend = 0;
     bool dropped = false;
     if (i < s.n) {
-        const ReadView v = view(s, i);
+        ReadView v = view(s, i);
+        if (filter_on(s.flt)) filter_view(v, s.flt, tot);
         const int32_t shift = shift_of(s, v.tid);
         const Classified c = classify_view(v, s.mode, shift, shift >= 0 ? slot_end_of(s, v.tid) : 0, s.n_lay != 0,
                                            s.mode == 1 ? s.stream + s.rec_off[i] : nullptr, gen_idx != nullptr, tot);
@@ -710,6 +728,7 @@ struct FusedArgs {
     uint32_t *c_idx; int32_t *c_pos; uint32_t *c_info; uint32_t *c_woff; uint2 *c_seq;     // out [rec_cap]: the kept reads, compacted
     uint32_t *gen_idx;              // out [rec_cap]: reads left to tally_stream_kernel
     PackOut o;                      // plane stream + events (caps inside)
+    tcmi_filter_words flt;          // the context's read filter: two uniform words
     unsigned long long *blk_alg;    // out [n_blocks]: algorithmic bytes | longest span << 48
     int32_t *blk_end;               // out [n_blocks]: max end
     PackTotals *tot;
@@ -793,6 +812,7 @@ __global__ __launch_bounds__(PB) void pk_index(FusedArgs a)
             ReadView v = view_rec(rec);
             // (a record that claims to end behind the stream: nothing of it is followed — the chain check will refuse the file)
             if (roff + 4ull + ld_u32(rec) > a.stream_len) { v.bad = true; v.broken = true; v.n_cigar = 0; }
+            filter_view(v, a.flt, a.tot);
             const Classified c = classify_view(v, 1, v.tid == 0 ? 0 : -1, 0x7FFFFFFF, false, rec, true, a.tot);
             word = c.word; nwords = c.nwords;
             my_alg += c.alg; my_end = max(my_end, c.end); my_len = max(my_len, c.len);
@@ -1084,6 +1104,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     if (tot.flags) { *why = tot.flags; return TCMI_E_UNSUPPORTED; }
     const int64_t nf = (int64_t)tot.n_kept;
     rs->n_lay = n_lay; rs->d_lay = src.lay; rs->lay_gen = ctx->lay_gen; rs->n_dropped = (int64_t)tot.n_dropped;
+    rs->n_filtered = (int64_t)tot.n_filtered;
     rs->ref_ext.assign(h_ext.begin(), h_ext.end());
     rs->n_piled = nf + (int64_t)tot.n_gen; rs->f_reads = nf; rs->alg_bytes = (int64_t)tot.alg_bytes; rs->max_end = tot.max_end; rs->max_len = (int32_t)tot.max_len;
     rs->packed_on_device = 1;
@@ -1222,6 +1243,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     a.agg = agg; a.fn = fn; a.rec_base = rec_base; a.rrec = rrec; a.rec_off = job->d_rec; a.rec_cap = (uint32_t)cap;
     a.c_idx = job->c_idx; a.c_pos = job->c_pos; a.c_info = c_info; a.c_woff = c_woff; a.c_seq = c_seq; a.gen_idx = job->gen_idx;
     a.o = o; a.blk_alg = blk_alg; a.blk_end = blk_end; a.tot = d_tot;
+    a.flt = tcmi_filter_pack(ctx->flt); rs->flt = ctx->flt;
     const size_t pre_n = tcmi_align256(((size_t)nb + 1) * 8) / 8;
     if (prefix) { a.pre_rec = pre; a.pre_k = pre + pre_n; a.pre_w = pre + 2 * pre_n; }
     (void)hipGetLastError();
@@ -1295,6 +1317,7 @@ int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs,
     rs->n_reads = (int64_t)tot.n_rec;
     rs->n_piled = nf + (int64_t)tot.n_gen; rs->f_reads = nf; rs->alg_bytes = (int64_t)alg; rs->max_end = mend; rs->max_len = (int32_t)mlen;
     rs->s_reads = (int64_t)tot.n_gen;
+    rs->n_filtered = (int64_t)tot.n_filtered;
     rs->range_first = tot.range_first ? (int64_t)(tot.range_first - 1ull) : -1;
     rs->range_next = tot.range_next ? (int64_t)(tot.range_next - 1ull) : -1;
     rs->f_chunks = nf ? tot.n_chunks : 0; rs->f_words = nf ? (int64_t)tot.n_words + 4 : 0; rs->f_events = tot.n_events;

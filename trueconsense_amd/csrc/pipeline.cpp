@@ -585,6 +585,7 @@ int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, con
                 std::string host_err;
                 if (rc == TCMI_E_UNSUPPORTED) {                  // the host reader takes it
                     rc = tcmi_bam_load(paths[i], r->host_threads, &hb);
+                    if (!rc) rc = tcmi_bam_filter(hb, (int32_t)ctx->flt.min_mapq, ctx->flt.require, ctx->flt.exclude, nullptr);   // (the context's read filter)
                     if (rc) host_err = tcmi_last_error(nullptr); // (its words: it failed without a context)
                     if (!rc) {
                         tcmi_reads reads;
@@ -674,6 +675,9 @@ int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, con
                 int rc = TCMI_OK;
                 if (cand) {                                      // insert tokens need the reads on the host
                     rc = tcmi_bam_load(paths[i], r->host_threads, &hb);
+                    // (the contexts' read filter — the caller sets the same one on all of them: the sweep sees passing records only)
+                    const tcmi_read_filter wf = r->ctxs[0]->flt;
+                    if (!rc) rc = tcmi_bam_filter(hb, (int32_t)wf.min_mapq, wf.require, wf.exclude, nullptr);
                     if (!rc) tcmi_bam_reads(hb, &reads);
                 }
                 const char *nm = names && names[i] ? names[i] : "sample";

@@ -659,6 +659,13 @@ int tcmi_readset_dropped(const tcmi_readset *rs, int64_t *n_dropped)
     return TCMI_OK;
 }
 
+int tcmi_readset_filtered(const tcmi_readset *rs, int64_t *n_filtered)
+{
+    if (!rs || !n_filtered) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    *n_filtered = rs->n_filtered;
+    return TCMI_OK;
+}
+
 int tcmi_readset_info(const tcmi_readset *rs, int64_t *n_reads, int64_t *n_piled, int64_t *alg, int64_t *dev,
                       int64_t *max_end)
 {

@@ -29,6 +29,34 @@ struct tcmi_layout {
 // checks n_ref / shift / slot_len (slots in ascending order, disjoint, below TCMI_F_EVPOS) and fills *out; TCMI_OK or TCMI_E_ARG
 int tcmi_layout_build(int32_t n_ref, const int64_t *shift, const int64_t *slot_len, tcmi_layout *out, char *msg, size_t msg_cap);
 
+// ---- read filter (tcmi_ctx_set_read_filter, tcmi_bam_filter) ------------------------------------------------------------
+// A record passes iff mapq >= min_mapq, (flag & require) == require, (flag & exclude) == 0; a failing record is ignored wherever an
+// unmapped one is.  The one rule of the kernels (pack_device.h: passes) and of the host reader's compaction (bam_reader.cpp).
+struct tcmi_read_filter {
+    uint32_t min_mapq, require, exclude;
+};
+static inline bool tcmi_filter_on(const tcmi_read_filter &f) { return (f.min_mapq | f.require | f.exclude) != 0; }
+static inline bool tcmi_filter_pass(const tcmi_read_filter &f, uint32_t flag, uint32_t mapq)
+{
+    return mapq >= f.min_mapq && (flag & f.require) == f.require && (flag & f.exclude) == 0;
+}
+// ... as the kernels take it, two uniform words of their arguments (pk_index has no scalar register to spare): the flag bits that are
+// tested and the value they must have — (flag & mask) == want with mask = require | exclude, want = require — and the MAPQ bound; a
+// filter that requires and excludes the same bit passes nothing: MAPQ bound 256.  No filter: both words 0.
+struct tcmi_filter_words {
+    uint32_t flags;                 // mask | want << 16
+    uint32_t min_mapq;
+};
+static inline tcmi_filter_words tcmi_filter_pack(const tcmi_read_filter &f)
+{
+    tcmi_filter_words w;
+    w.flags = ((f.require | f.exclude) & 0xFFFFu) | ((f.require & 0xFFFFu) << 16);
+    w.min_mapq = (f.require & f.exclude) ? 256u : f.min_mapq;
+    return w;
+}
+// the argument check of both entry points: TCMI_OK and *out filled, or TCMI_E_ARG (worded on `ctx`)
+int tcmi_read_filter_build(tcmi_ctx *ctx, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, tcmi_read_filter *out);
+
 // ---- device read layout -------------------------------------------------------------
 // Only reads that pile up (mapped, tid == 0, pos >= 0, reference span > 0)
 // are kept, in two sets:
@@ -122,6 +150,10 @@ struct tcmi_readset {
     uint64_t lay_gen = 0;           // the context's layout generation at the upload (the device table is rewritten by the next layout)
     std::vector<int64_t> ref_ext;
     int64_t n_dropped = 0;          // mapped reads on references without a slot (tcmi_readset_dropped)
+    // built from a device-decoded record stream: the context's read filter at that time (the insert-candidate kernels apply it to the
+    // resident stream whatever the context is set to later) and the records that failed it (tcmi_readset_filtered)
+    tcmi_read_filter flt = {0, 0, 0};
+    int64_t n_filtered = 0;
     const uint32_t *d_gen_idx = nullptr;   // records of reads too long for the packed set (s_reads of them): tally_stream_kernel walks them in the stream
     int64_t s_reads = 0;
     // a read set of a block RANGE of a file (tcmi_readset_from_bamfile_blocks): where its first record starts when the range began
@@ -193,6 +225,7 @@ struct tcmi_ctx {
     size_t h_pin_cap = 0;
     char *h_desc = nullptr;          // pinned: the re-based block table of a block range on its way to the device (bam_device.hip: decode_enqueue)
     size_t h_desc_cap = 0;
+    tcmi_read_filter flt = {0, 0, 0};   // tcmi_ctx_set_read_filter: governs the read sets built from device-decoded record streams
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
@@ -292,6 +325,8 @@ struct tcmi_pack_src {
     // a contig layout (tcmi_ctx_set_layout; n_lay = 0: none, reference 0 at pos_shift): lay[t] = shift of reference t (< 0: dropped),
     // lay[n_lay + t] = the end of its slot; lay_ext[t]: the kept reads' max end on reference t, in its own coordinates (atomicMax)
     const int32_t *lay; int32_t *lay_ext; int32_t n_lay;
+    // the read filter (mode 1; zero for flat arrays, which carry no MAPQ)
+    tcmi_filter_words flt;
 };
 // one read on one insert-candidate column, as the device kernel hands it to the host (ins_entries.hip -> insert_tokens.cpp)
 struct tcmi_dev_entry {

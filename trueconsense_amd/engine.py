@@ -17,6 +17,14 @@ from . import _ffi
 from ._ffi import check, lib, ptr
 
 
+def read_filter_args(read_filter):
+    """None or (min_mapq, require_flags, exclude_flags) -> three ints (None: 0, 0, 0, which passes everything)."""
+    if read_filter is None:
+        return 0, 0, 0
+    q, f, F = read_filter
+    return int(q), int(f), int(F)
+
+
 class ReadSet:
     def __init__(self, ctx, handle, keep):
         self.ctx, self.handle, self._keep = ctx, handle, keep
@@ -31,6 +39,9 @@ class ReadSet:
         # a block range of a file: where its first record starts (a range in the middle of the file; nothing in front vouches for it)
         # and where the first record behind it starts, offsets into the file's inflated stream (-1: none) — distributed.check_range_anchors
         self.range_anchors = (a.value, b.value)
+        n = C.c_int64(0)
+        check(lib().tcmi_readset_filtered(handle, C.byref(n)))
+        self.filtered = n.value                     # records that failed the read filter the set was built under (Context.set_read_filter)
 
     def ref_extents(self, n_ref):
         """Uploaded under a contig layout of n_ref references: per reference the kept reads' max end in its own coordinates."""
@@ -111,6 +122,12 @@ class Context:
         ms, n = C.c_double(0), C.c_int64(0)
         check(lib().tcmi_profile_get(self.handle, kernel, C.byref(ms), C.byref(n)), self.handle)
         return ms.value, n.value
+
+    def set_read_filter(self, min_mapq=0, require_flags=0, exclude_flags=0):
+        """Read filter (tcmi_ctx_set_read_filter; samtools view -q / -f / -F): from now on every read set this context builds from a
+        device-decoded file ignores the records that fail it, as it ignores unmapped ones.  No arguments: no filter."""
+        check(lib().tcmi_ctx_set_read_filter(self.handle, int(min_mapq), int(require_flags), int(exclude_flags)), self.handle)
+        self.read_filter = (int(min_mapq), int(require_flags), int(exclude_flags))
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
@@ -461,12 +478,19 @@ def _header_refs(fn, h, n_ref):
 
 
 class BamFile:
-    """A BAM decoded by libtcmi (tcmi_bam_load): pysam.AlignmentFile's role for this path."""
+    """A BAM decoded by libtcmi (tcmi_bam_load): pysam.AlignmentFile's role for this path.  read_filter = (min_mapq,
+    require_flags, exclude_flags): the records that fail it are removed after the load (tcmi_bam_filter) — n_reads and the arrays
+    are the passing records', n_records stays the file's count, n_removed the difference."""
 
-    def __init__(self, path, threads=0):
+    def __init__(self, path, threads=0, read_filter=None):
         h = C.c_void_p()
         check(lib().tcmi_bam_load(str(path).encode(), int(threads), C.byref(h)))
         self.handle = h
+        n0, gone = C.c_int64(0), C.c_int64(0)
+        check(lib().tcmi_bam_info(h, C.byref(n0), None, None, None, None, None, None))
+        if read_filter is not None:
+            check(lib().tcmi_bam_filter(h, *read_filter_args(read_filter), C.byref(gone)))
+        self.n_records, self.n_removed = n0.value, gone.value
         self.filename = str(path)
         n_ref, name, ln = C.c_int32(0), C.c_char_p(), C.c_int64(0)
         check(lib().tcmi_bam_header(h, C.byref(n_ref), C.byref(name), C.byref(ln)))
@@ -502,7 +526,13 @@ class BamFile:
                 "names": np.ctypeslib.as_array(C.cast(r.names, C.POINTER(C.c_uint8)), shape=(max(1, int(name_off[n]) if n else 1),)),
                 "tid": view(r.tid, n), "cigar_off": cig_off, "cigar": view(r.cigar, max(1, self.n_cigar)),
                 "seq_off": seq_off, "seq": view(r.seq, max(1, int(seq_off[n]) if n else 1)),
-                "qual": view(r.qual, max(1, self.n_qual)), "_owner": self}
+                "qual": view(r.qual, max(1, self.n_qual)), "mapq": self.mapq(), "_owner": self}
+
+    def mapq(self):
+        """MAPQ of every read, uint8 [n_reads] (a copy; struct tcmi_reads carries none)."""
+        p = C.POINTER(C.c_uint8)()
+        check(lib().tcmi_bam_mapq(self.handle, C.byref(p)))
+        return np.ctypeslib.as_array(p, shape=(self.n_reads,)).copy() if self.n_reads else np.zeros(0, np.uint8)
 
     def close(self):
         if self.handle:
@@ -520,12 +550,12 @@ class LazyBam:
     """The decoded BAM for the few callers that need reads on the host (insert tokens, Events.py:47-82): decoded by the
     host reader on first use.  The tally itself never needs it — the device decodes the file."""
 
-    def __init__(self, path, threads=0):
-        self.filename, self._threads, self._bam = str(path), threads, None
+    def __init__(self, path, threads=0, read_filter=None):
+        self.filename, self._threads, self._bam, self.read_filter = str(path), threads, None, read_filter
 
     def get(self):
         if self._bam is None:
-            self._bam = BamFile(self.filename, threads=self._threads)
+            self._bam = BamFile(self.filename, threads=self._threads, read_filter=self.read_filter)
         return self._bam
 
     def close(self):
@@ -593,7 +623,7 @@ class FileRunner:
     A file the device decoder does not take (records straddling BGZF blocks, long reads) is decoded by the host reader
     (tcmi_bam_load, `decode_threads` threads) and packed from its flat arrays.  `seconds` accumulates each stage's busy time."""
 
-    def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2):
+    def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None):
         device = ctx.device if isinstance(ctx, Context) else int(ctx)
         self.mincov, self.amb = int(mincov), bool(include_ambig)
         h = C.c_void_p()
@@ -608,6 +638,9 @@ class FileRunner:
         self.seconds = {"decode": 0.0, "upload": 0.0, "step": 0.0, "walk": 0.0}
         self.decoded_on = {"device": 0, "host": 0}
         self._device = device
+        if read_filter is not None:                 # (every context the same: the runner's host-reader fallbacks take it from them)
+            for c in self.contexts:
+                c.set_read_filter(*read_filter_args(read_filter))
 
     @property
     def contexts(self):

@@ -39,7 +39,9 @@ def Override_index_positions(index, override_data):
 def build_counts(bamfile, ref, ctx=None):
     """BAM (+ reference FASTA, for its length) -> int32 [L,7] count matrix on the GPU path.  A path (or LazyBam) is decoded
     ON THE DEVICE (BGZF inflate, record chain, pack: csrc/bam_device.hip, pack_device.hip); files the device decoder
-    declines, and BamFile objects, go through the host reader's flat arrays."""
+    declines, and BamFile objects, go through the host reader's flat arrays.  A read filter is the context's
+    (Context.set_read_filter): the host reader's fallback applies the same one (a LazyBam's own, if it has one); a BamFile is
+    taken as it is."""
     ref_length = fasta.first_length(ref) if isinstance(ref, str) else int(ref)
     ctx = ctx or _state.default_context()
     if not isinstance(bamfile, BamFile):
@@ -55,16 +57,20 @@ def build_counts(bamfile, ref, ctx=None):
             d.close()
         if rs is not None:
             try:
-                build_counts.last_reads = int(rs.n_reads)
+                build_counts.last_reads, build_counts.last_filtered = int(rs.n_reads), int(rs.filtered)
                 return ctx.step(rs, max(ref_length, rs.max_end, 1), 0, True, want_counts=True)[3]
             finally:
                 rs.free()
-        bamfile = bamfile.get() if isinstance(bamfile, LazyBam) else BamFile(path)
-    build_counts.last_reads = int(bamfile.n_reads)
+        flt = getattr(ctx, "read_filter", None)
+        if isinstance(bamfile, LazyBam) and bamfile.read_filter is None:
+            bamfile.read_filter = flt
+        bamfile = bamfile.get() if isinstance(bamfile, LazyBam) else BamFile(path, read_filter=flt)
+    build_counts.last_reads, build_counts.last_filtered = int(bamfile.n_records), int(bamfile.n_removed)
     return ctx.tally(bamfile, ref_len=ref_length)
 
 
 build_counts.last_reads = 0         # alignment records of the file the last call read (the command line's --stats)
+build_counts.last_filtered = 0      # ... of which failed the read filter
 
 
 def BuildIndex(bamfile, ref):

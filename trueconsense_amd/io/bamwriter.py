@@ -70,6 +70,7 @@ def write_bam(path, reads, ref_name="ref", ref_len=0, level=1, sam_text=None, bl
         nm_off, nm = reads.get("name_off"), reads.get("names")
         nm_b = bytes(bytearray(nm)) if nm is not None else None
         mt, mp, tl = reads.get("next_tid"), reads.get("next_pos"), reads.get("tlen")
+        mq = reads.get("mapq")
         for i in range(n):
             c0, c1 = int(co[i]), int(co[i + 1])
             s0 = int(so[i])
@@ -83,7 +84,7 @@ def write_bam(path, reads, ref_name="ref", ref_len=0, level=1, sam_text=None, bl
             t = int(tid[i]) if tid is not None else 0
             p = int(pos[i])
             q = q_b[int(qoff[i]):int(qoff[i]) + l] if q_b is not None else b"\xff" * l
-            rec = (struct.pack("<iiBBHHHIiii", t, p, len(name), 60, _reg2bin(max(p, 0), max(p, 0) + max(span, 1)), nc,
+            rec = (struct.pack("<iiBBHHHIiii", t, p, len(name), int(mq[i]) if mq is not None else 60, _reg2bin(max(p, 0), max(p, 0) + max(span, 1)), nc,
                                int(flag[i]), l, int(mt[i]) if mt is not None else -1, int(mp[i]) if mp is not None else -1,
                                int(tl[i]) if tl is not None else 0) + name + cg_b[4 * c0:4 * c1] +
                    sq_b[s0:s0 + (l + 1) // 2] + q)
@@ -102,12 +103,12 @@ def write_bam(path, reads, ref_name="ref", ref_len=0, level=1, sam_text=None, bl
 
 
 def write_bam_fast(path, pos, flag, seq_packed, read_len, ref_name="ref", ref_len=0, level=1, qual=30, part=(True, True), first_id=0, names=None,
-                   tid=None, refs=None):
+                   tid=None, refs=None, mapq=60):
     """Vectorised writer for the bench workload: n reads, all `read_len`M, flags from `flag`,
     seq_packed uint8 [n, ceil(read_len/2)] in BAM nibble order, constant quality.  part = (first, last): a large file is written
     in several calls, slice by slice (the header goes with the first, the end-of-file block with the last); first_id numbers the names.
     qual: one value, or uint8 [n, read_len]; names: uint8 [n, k] (k characters each, no NUL) instead of the seven-digit numbers.
-    tid: int32 [n] reference of every read (default 0); refs: [(name, length), ...] for more than one @SQ."""
+    tid: int32 [n] reference of every read (default 0); refs: [(name, length), ...] for more than one @SQ; mapq: one value, or uint8 [n]."""
     n = len(pos)
     nb = (read_len + 1) // 2
     name_len = 8 if names is None else names.shape[1] + 1     # fixed-width names: 7 digits (or the caller's characters) + NUL
@@ -120,7 +121,7 @@ def write_bam_fast(path, pos, flag, seq_packed, read_len, ref_name="ref", ref_le
     put(4, np.zeros(n) if tid is None else tid, "<i4")     # refID
     put(8, pos, "<i4")
     rec[:, 12] = name_len
-    rec[:, 13] = 60
+    rec[:, 13] = mapq
     beg = np.asarray(pos, np.int64)
     end = beg + read_len - 1
     binv = np.zeros(n, np.int64)
