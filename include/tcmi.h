@@ -180,6 +180,27 @@ int  tcmi_readset_dropped(const tcmi_readset *rs, int64_t *n_dropped);
  *   tcmi_readset_filtered     records of the file / block range that failed the filter the read set was built under */
 int  tcmi_ctx_set_read_filter(tcmi_ctx *ctx, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags);
 int  tcmi_readset_filtered(const tcmi_readset *rs, int64_t *n_filtered);
+/* ---- base-quality floor (additive: the reference piles up with min_base_quality = 0, indexing.py:100) --------------------
+ * A pileup TOKEN — one read on one reference column — is SKIPPED iff its quality is below q (samtools mpileup -Q, pysam's
+ * pileup_base_qual_skip): a matched base is tested with its own QUAL byte, a deletion or ref-skip token with the QUAL byte of the
+ * next query base (the query index at which the D / N operation starts); a query index at or beyond l_seq has quality 0 (SEQ "*",
+ * a SEQ shorter than the CIGAR, a D / N with no base behind it); a record without QUAL (bytes 0xFF) has quality 255 and is never
+ * skipped.  A skipped token is absent from its column: nothing for coverage, A/T/C/G, X, or I (the insertion mark belongs to the
+ * token in front of the insertion).  Nothing else about the read changes: the piled-up count, the extent and the per-reference
+ * extents are those of the unfiltered reads, and a column whose tokens are all skipped is a zero row.  The qualities are tested as
+ * the file stores them: pysam's overlap rewrite of mate pairs (ignore_overlaps) is NOT modelled.  q outside 0..255: TCMI_E_ARG;
+ * q = 0 (the default) is no floor and takes the same kernels as before.
+ *   tcmi_ctx_set_min_base_quality  from now on governs every read set the context builds from a record stream decoded on the
+ *                     device (tcmi_readset_from_bamfile[_blocks], tcmi_bamfile_step, tcmi_split_step and its sub-range helper
+ *                     contexts, the file runner's contexts: tcmi_filerunner_ctx), and with it the count matrix and everything
+ *                     derived from it.  It does not touch the insert-candidate sweeps (tcmi_readset_modal_tokens and the like keep
+ *                     their own min_base_quality argument).  While q > 0 whatever would tally WITHOUT the floor refuses with
+ *                     TCMI_E_UNSUPPORTED instead: the flat-array entry points (tcmi_readset_upload[_batch], tcmi_tally,
+ *                     tcmi_pipeline_run[_batched]: flat arrays carry no QUAL) and the file runner's host-reader fallback (the host
+ *                     packer knows no floor; the message says why the file left the device path).
+ *   tcmi_readset_min_base_quality  the floor the read set was built under, whatever the context is set to later */
+int  tcmi_ctx_set_min_base_quality(tcmi_ctx *ctx, int32_t q);
+int  tcmi_readset_min_base_quality(const tcmi_readset *rs, int32_t *q);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
  * "decode_batched" — files (or ranges) whose blocks the device decoder took in batches ("decode_token_mb");

@@ -125,6 +125,9 @@ def GetArgs(givenargs):
     additive.append((("--exclude-flags",), dict(type=_range_arg(parser, "--exclude-flags", 0xFFFF), default=0, metavar="F",
                                                 help="ignore records with any of these FLAG bits, e.g. 0x400 duplicates, 0x900 secondary\n"
                                                      "and supplementary (samtools view -F; decimal or 0x...)")))
+    additive.append((("--min-baseq",), dict(type=_range_arg(parser, "--min-baseq", 255), default=0, metavar="N",
+                                            help="skip pileup tokens (a read on a column) whose base quality is below N in the count matrix\n"
+                                                 "(samtools mpileup -Q; qualities as the file stores them); needs the device decoder")))
     # (is this the --batch form?  asked of a small parser of its own: "--batch=FILE" and argparse's abbreviations count too)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--batch", default=None)
@@ -181,6 +184,8 @@ def _child_argv(a, single):
     for flag, v in (("--require-flags", a.require_flags), ("--exclude-flags", a.exclude_flags)):
         if v:
             out += [flag, "0x%x" % v]
+    if a.min_baseq:                                 # (the base-quality floor, likewise)
+        out += ["--min-baseq", str(a.min_baseq)]
     if single:
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]
         for flag, v in (("-vcf", a.variants), ("-doc", a.depth_of_coverage), ("-ogff", a.output_gff)):
@@ -261,7 +266,8 @@ def run_batch(a):
     cores = max(1, min(int(a.threads), os.cpu_count() or 1))
     runner = FileRunner(int(os.environ.get("TCMI_DEVICE", "0")), gffrows, a.coverage_level, a.noambiguity is False,
                         decoders=min(4, max(1, cores // 4)), decode_threads=max(1, cores // 2), walkers=min(4, max(1, cores // 4)),
-                        gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a))
+                        gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a),
+                        min_baseq=a.min_baseq)
     runner.set_outputs(refID, refseq, vcf_header(date.today().strftime("%Y%m%d"), sys.argv[1:], a.reference, refID), IndexGff.header.raw_text,
                        [gff_row_columns(r) for r in gffrows])
     try:
@@ -277,7 +283,7 @@ def run_batch(a):
     finally:
         if a.stats:
             with open(a.stats, "w") as fh:
-                json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "stage_busy_seconds": runner.seconds,
+                json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "stage_busy_seconds": runner.seconds,
                            "decoded_on": runner.decoded_on, "status": [int(x) for x in getattr(runner, "last_status", [])]}, fh)
         runner.close()
 
@@ -294,7 +300,7 @@ def run_per_contig(a):
         sys.exit(1)
     if a.stats:
         with open(a.stats, "w") as fh:
-            json.dump(dict({"seconds": {"per_contig": time.perf_counter() - t0}}, **info), fh)
+            json.dump(dict({"seconds": {"per_contig": time.perf_counter() - t0}, "min_baseq": a.min_baseq}, **info), fh)
 
 
 def main(args=None):
@@ -331,9 +337,20 @@ def main(args=None):
         return run_per_contig(a)
     t = {"start": time.perf_counter()}
 
-    from .engine import LazyBam, read_filter_args
+    from .engine import read_filter_args
     flt = read_filter_of(a)
     _state.default_context().set_read_filter(*read_filter_args(flt))       # (always: the process's one context may have served another call)
+    # (... and the base-quality floor, for this call only: the flat-array entry points of the same context refuse while it is set)
+    _state.default_context().set_min_base_quality(a.min_baseq)
+    try:
+        _single_sample(a, flt, t)
+    finally:
+        _state.default_context().set_min_base_quality(0)
+
+
+def _single_sample(a, flt, t):
+    """main()'s one-sample flow behind the argument handling (TrueConsense.py:225-264)."""
+    from .engine import LazyBam
     bam = LazyBam(a.input, threads=a.threads, read_filter=flt)      # reads reach the host only if an insert candidate needs its tokens
     t["bam_open"] = time.perf_counter()
     counts = build_counts(bam, a.reference)         # decoded, packed and tallied on the device
@@ -363,6 +380,7 @@ def main(args=None):
             secs = {k: t[k] - t[keys[i - 1]] for i, k in enumerate(keys) if i}
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
+                       "min_baseq": a.min_baseq,
                        "bam_bytes": os.path.getsize(a.input)}, fh)
 
 

@@ -58,6 +58,8 @@ _SIGS = {
     "tcmi_ctx_stat": (_int, [_vp, C.c_char_p, _P(_i64)]),
     "tcmi_ctx_set_read_filter": (_int, [_vp, _i32, _u32, _u32]),
     "tcmi_readset_filtered": (_int, [_vp, _P(_i64)]),
+    "tcmi_ctx_set_min_base_quality": (_int, [_vp, _i32]),
+    "tcmi_readset_min_base_quality": (_int, [_vp, _P(_i32)]),
     "tcmi_profile_enable": (_int, [_vp, _int]),
     "tcmi_profile_reset": (_int, [_vp]),
     "tcmi_profile_get": (_int, [_vp, _int, _P(C.c_double), _P(_i64)]),

@@ -111,15 +111,17 @@ def _name_slot_overrun(err, host, header_names):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None):
+                 info=None, min_baseq=0):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
     exclude_flags): extents, `dropped` and the host BamFile see the passing records only; info (a dict) receives "reads" (the
-    file's records) and "reads_filtered"."""
+    file's records) and "reads_filtered".  min_baseq: the base-quality floor of the count matrix (Context.set_min_base_quality);
+    above 0 a file the device decoder declines is refused (the host packer knows no floor)."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
+    ctx.set_min_base_quality(min_baseq)
     host = None
     try:
         rs = None
@@ -129,6 +131,9 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         except _ffi.TcmiError as e:
             if e.code != _ffi.E_UNSUPPORTED:
                 raise
+            if min_baseq:
+                raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--min-baseq %d needs the device path (the host packer knows no base-quality floor), "
+                                     "which %s left: %s" % (min_baseq, path, e)) from e
         finally:
             d.close()
         if rs is None:
@@ -147,6 +152,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     finally:
         ctx.set_layout()
         ctx.set_read_filter()
+        ctx.set_min_base_quality()
     return plain, alt, flags, counts, ext, dropped, host
 
 
@@ -164,7 +170,8 @@ def run(a):
     ctx = _state.default_context()
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
-                                                                 threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen)
+                                                                 threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
+                                                                 min_baseq=a.min_baseq)
 
     # every contig's slice of the call records (the call is position-local: a slice's records are the split run's)
     per = []

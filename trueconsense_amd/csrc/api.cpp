@@ -323,6 +323,14 @@ int tcmi_ctx_set_read_filter(tcmi_ctx *c, int32_t min_mapq, uint32_t require_fla
     return TCMI_OK;
 }
 
+int tcmi_ctx_set_min_base_quality(tcmi_ctx *c, int32_t q)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    if (q < 0 || q > 255) return tcmi_fail(c, TCMI_E_ARG, "min_base_quality %d is outside 0..255", (int)q);
+    c->min_bq = q;                                              // (a kernel argument of the next upload: nothing queued reads it)
+    return TCMI_OK;
+}
+
 int tcmi_ctx_stat(tcmi_ctx *c, const char *key, int64_t *value)
 {
     if (!c || !key || !value) return tcmi_fail(c, TCMI_E_ARG, "null argument");
@@ -755,7 +763,7 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     for (tcmi_ctx *h : ctx->helpers) {                          // (the caller's decoder options)
         h->verify_crc = ctx->verify_crc; h->decode_token_mb = ctx->decode_token_mb; h->one_sync = ctx->one_sync; h->mid_wait = ctx->mid_wait;
         h->prefix_kernels = ctx->prefix_kernels; h->h2d_pieces = ctx->h2d_pieces; h->sym_scratch_div = ctx->sym_scratch_div; h->prof = false;
-        h->flt = ctx->flt;
+        h->flt = ctx->flt; h->min_bq = ctx->min_bq;
     }
     TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));            // (the matrix is zero before anybody adds to it)
     std::vector<tcmi_readset *> rs((size_t)K, nullptr);
@@ -830,7 +838,7 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     tcmi_readset *sum = new tcmi_readset();
     sum->device = ctx->device; sum->packed_on_device = 2;
     sum->range_first = rs[0]->range_first; sum->range_next = rs[(size_t)K - 1]->range_next;
-    sum->flt = ctx->flt;
+    sum->flt = ctx->flt; sum->min_bq = ctx->min_bq;
     for (int k = 0; k < K; ++k) {
         const tcmi_readset *r = rs[(size_t)k];
         sum->n_reads += r->n_reads; sum->n_piled += r->n_piled; sum->alg_bytes += r->alg_bytes; sum->dev_bytes += r->dev_bytes;

@@ -788,6 +788,7 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
     tcmi_pack_src s = {};
     s.stream = D.d_out; s.rec_off = D.d_rec; s.n = (int64_t)D.n; s.mode = 1; s.pos_shift = 0;
     s.flt = tcmi_filter_pack(ctx->flt);
+    s.min_bq = (uint32_t)ctx->min_bq;
     tcmi_readset *rs = new tcmi_readset();
     rs->uid = g_next_uid.fetch_add(1);
     rs->n_reads = (int64_t)D.n;

@@ -430,20 +430,56 @@ __device__ inline void pair_planes(const uint8_t *p, bool odd, int have, uint32_
     lo &= mask; hi &= mask; ok &= mask;
 }
 
+// ---- the base-quality floor (tcmi_ctx_set_min_base_quality; BQ variants of the plane kernels only) ---------------------------------
+// A token whose quality is below the floor is SKIPPED (pysam's pileup_base_qual_skip): its bit is set in the read set's third plane,
+// "drop" — one word per {lo, hi} pair, in an array of its own indexed by pair —, its lo / hi bits are cleared and it pushes no event
+// word; tally_planes_drop_kernel counts the plane and takes it out of the coverage.
+// bit i: byte i of the 32 QUAL bytes at p (any address) is below q (1 .. 255).  Unsigned bytes: 0xFF, "no QUAL", is below nothing.
+__device__ inline uint32_t qual_below32(const uint8_t *p, uint32_t q)
+{
+    uint32_t d[8];
+    __builtin_memcpy(d, p, 32);
+    const uint32_t H = 0x80808080u, qq = q * 0x01010101u;
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const uint32_t x = d[k];
+        const uint32_t z = (x | H) - (qq & ~H);                  // bit 7 of a byte: its low seven bits are >= q's (no borrow between bytes)
+        const uint32_t lt = ((~x & qq) | (~(x ^ qq) & ~z)) & H;  // x < q: the top bits say so, or they are equal and the low bits do
+        m |= ((((lt >> 7) * 0x01020408u) >> 24) & 0xFu) << (4 * k);      // (the four bits gathered by one multiply: no two partial products meet)
+    }
+    return m;
+}
+// the skipped ones among the nb (<= 32) query bases from y on: below the floor, or at / beyond l_seq (quality 0)
+__device__ inline uint32_t dropped32(const uint8_t *qual, int32_t l_seq, int32_t y, int nb, uint32_t q)
+{
+    const uint32_t nbm = nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u);
+    const int have = min(nb, l_seq - y);
+    if (have <= 0) return nbm;
+    const uint32_t hm = have >= 32 ? 0xFFFFFFFFu : ((1u << have) - 1u);
+    return (qual_below32(qual + y, q) | ~hm) & nbm;             // (the load ends < 32 bytes behind the record: the stream's slack)
+}
+
 // one PROJECTED read (anything but [H][S]M[S][H]) -> its plane pairs (out: 2 * ceil(len / 32) words, then the zero pair) and its event words
-__device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals *tot, uint32_t info, int32_t gpos, uint32_t *out)
+// BQ: and its drop words (dout: one per pair, then the zero word), under the floor Q — a D / N token is tested with the quality of
+// the next query base (the query index at which the op starts), the I mark belongs to the token in front of the insertion
+template <bool BQ>
+__device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals *tot, uint32_t info, int32_t gpos, uint32_t *out, uint32_t *dout, uint32_t Q)
 {
     const int len = (int)(info & 1023u), npair = (len + 31) >> 5;
+    const uint8_t *qual = v.seq + ((size_t)v.l_seq + 1) / 2;
     {
         // Walk the CIGAR: matched bases land on their reference offset (bit-field copies into the pair being built), D / N
         // leave empty positions, and the tokens that are not plain bases become events: X for a deleted base
         // whose token is exactly "*", I on the last reference base before an insertion (also "*+..": I but not X).
         int q_cur = 0;
         uint32_t lo = 0, hi = 0, ok = 0;
+        uint32_t dr = 0;                            // (BQ) the pair's skipped tokens: they are in `ok` too — no OTHER event for them
         auto flush_to = [&](int q_new) {            // store the pairs [q_cur, q_new), all but the first of them empty
             while (q_cur < q_new && q_cur < npair) {
                 const int nb = min(32, len - 32 * q_cur);
                 *reinterpret_cast<uint2 *>(out + 2 * q_cur) = make_uint2(lo, hi);
+                if constexpr (BQ) { dout[q_cur] = dr; dr = 0; }
                 uint32_t miss = (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)) & ~ok;
                 while (miss) {
                     const int b = __builtin_ctz(miss);
@@ -460,6 +496,7 @@ __device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals
             const int oplen = (int)(c >> 4);
             if (consumes_ref(op)) {
                 const bool ins = oplen > 0 && ins_after(v.cigar, v.n_cigar, k);
+                bool skip_last = false;             // (BQ) the op's last token is skipped: no I mark
                 if (is_match(op)) {
                     int t = 0;
                     while (t < oplen) {
@@ -467,14 +504,32 @@ __device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals
                         flush_to(q);
                         uint32_t l, h, g;
                         fetch32(v.seq, v.l_seq, y + t, nb, l, h, g);
+                        if constexpr (BQ) {
+                            const uint32_t d = dropped32(qual, v.l_seq, y + t, nb, Q);
+                            l &= ~d; h &= ~d; g |= d;
+                            dr |= d << b0;
+                            skip_last = (d >> (nb - 1)) & 1u;
+                        }
                         lo |= l << b0; hi |= h << b0; ok |= g << b0;
                         t += nb;
                     }
-                } else if (op == 2) {
-                    const int nx = ins ? oplen - 1 : oplen;
-                    for (int t = 0; t < nx; ++t) push_event(o, tot, (uint32_t)(gpos + x + t) | TCMI_F_EV_X);
+                } else {
+                    if constexpr (BQ) {
+                        skip_last = (y < v.l_seq ? byte_at(qual + y) : 0u) < Q;
+                        for (int t = 0; skip_last && t < oplen;) {   // every column of the op: skipped, and no OTHER event
+                            const int q = (x + t) >> 5, b0 = (x + t) & 31, nb = min(32 - b0, oplen - t);
+                            flush_to(q);
+                            const uint32_t m = (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)) << b0;
+                            dr |= m; ok |= m;
+                            t += nb;
+                        }
+                    }
+                    if (op == 2 && !skip_last) {
+                        const int nx = ins ? oplen - 1 : oplen;
+                        for (int t = 0; t < nx; ++t) push_event(o, tot, (uint32_t)(gpos + x + t) | TCMI_F_EV_X);
+                    }
                 }
-                if (ins) push_event(o, tot, (uint32_t)(gpos + x + oplen - 1) | TCMI_F_EV_I);
+                if (ins && !skip_last) push_event(o, tot, (uint32_t)(gpos + x + oplen - 1) | TCMI_F_EV_I);
                 x += oplen;
             }
             if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) y += oplen;     // (consumes_query, written out: the call changes pk_place's code)
@@ -482,6 +537,7 @@ __device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals
         flush_to(npair);
     }
     *reinterpret_cast<uint2 *>(out + 2 * npair) = make_uint2(0u, 0u);
+    if constexpr (BQ) dout[npair] = 0u;
 }
 
 // dev_slots > 0 (the one-sync path: nobody has read the totals back): n_kept and n_words are taken from `tot`, and the reads per
@@ -631,9 +687,11 @@ __global__ __launch_bounds__(PB) void pk_pack(PackOut o, const int32_t *c_pos, c
 // the other, kept 22 uncoalesced dword loads per lane in flight and the kernel at 16 waves a CU waiting for them).
 // Reads that need their CIGAR walked (INFO_PROJ) are packed by their own lane, as before, straight to where they go.
 constexpr int PL_SLOTS = PB * (TCMI_D_MAXLEN / 32 + 2);      // a read's pairs, its zero pair, and the second one that ends it on 16 bytes
-__global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const uint32_t *c_idx, const int32_t *c_pos, const uint32_t *c_info,
-                                                const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words,
-                                                PackTotals *tot)
+// BQ (pk_planes_bq): under a base-quality floor Q — a pair also gets its word of the drop plane (drop[seq word / 2]): the 32 QUAL bytes
+// behind SEQ compared with Q (dropped32), the skipped bases out of lo / hi and out of the OTHER events
+template <bool BQ>
+__device__ __forceinline__ void planes_body(const PackSrc src, const PackOut o, const uint32_t *c_idx, const int32_t *c_pos, const uint32_t *c_info,
+                                   const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words, PackTotals *tot, uint32_t *drop, uint32_t Q)
 {
     __shared__ uint32_t s_info[PB], s_word[PB];
     __shared__ int32_t s_pos[PB];
@@ -652,7 +710,7 @@ __global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const ui
         const int n_slot = (int)(words_of(info & 1023u) >> 1);
         s_info[tid] = info; s_word[tid] = word; s_pos[tid] = pos; s_seq[tid] = c_seq[g];
         for (int q = 0; q < n_slot; ++q) s_owner[slot0 + q] = own && q <= npair ? (uint16_t)0xFFFFu : (uint16_t)(tid | (q << 8));
-        if (own) pack_read(view(src, c_idx[g]), o, tot, info, pos, o.seq + word);
+        if (own) pack_read<BQ>(view(src, c_idx[g]), o, tot, info, pos, o.seq + word, BQ ? drop + (word >> 1) : nullptr, Q);
     }
     __syncthreads();
     const uint8_t *bytes = src.mode == 0 ? src.seq : src.stream;
@@ -664,12 +722,22 @@ __global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const ui
         const uint32_t info = s_info[t];
         const int len = (int)(info & 1023u), npair = (len + 31) >> 5;
         uint2 *dst = reinterpret_cast<uint2 *>(o.seq + s_word[t]) + q;                  // (even word offsets: 8-byte aligned)
-        if (q >= npair) { *dst = make_uint2(0u, 0u); continue; }
+        if (q >= npair) {
+            *dst = make_uint2(0u, 0u);
+            if constexpr (BQ) drop[(s_word[t] >> 1) + q] = 0u;
+            continue;
+        }
         const uint2 where = s_seq[t];
         const int l_seq = (int)(where.y >> 8), y = (int)(info >> 12) + 32 * q;
         const int nb = min(32, len - 32 * q), have = min(nb, l_seq - y);
         uint32_t lo, hi, ok;
-        pair_planes(bytes + ((((unsigned long long)(where.y & 0xFFu) << 32) | where.x) + (uint32_t)(y >> 1)), y & 1, have, lo, hi, ok);
+        const uint8_t *sq = bytes + (((unsigned long long)(where.y & 0xFFu) << 32) | where.x);
+        pair_planes(sq + (uint32_t)(y >> 1), y & 1, have, lo, hi, ok);
+        if constexpr (BQ) {
+            const uint32_t d = dropped32(sq + ((size_t)l_seq + 1) / 2, l_seq, y, nb, Q);
+            lo &= ~d; hi &= ~d; ok |= d;
+            drop[(s_word[t] >> 1) + q] = d;
+        }
         *dst = make_uint2(lo, hi);
         uint32_t miss = (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)) & ~ok;
         while (miss) {
@@ -678,6 +746,18 @@ __global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const ui
             miss &= miss - 1;
         }
     }
+}
+__global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const uint32_t *c_idx, const int32_t *c_pos, const uint32_t *c_info,
+                                                const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words,
+                                                PackTotals *tot)
+{
+    planes_body<false>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, nullptr, 0u);
+}
+__global__ __launch_bounds__(PB) void pk_planes_bq(PackSrc src, PackOut o, const uint32_t *c_idx, const int32_t *c_pos, const uint32_t *c_info,
+                                                   const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words,
+                                                   PackTotals *tot, uint32_t *drop, uint32_t Q)
+{
+    planes_body<true>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, drop, Q);
 }
 
 
@@ -732,6 +812,8 @@ struct FusedArgs {
     unsigned long long *blk_alg;    // out [n_blocks]: algorithmic bytes | longest span << 48
     int32_t *blk_end;               // out [n_blocks]: max end
     PackTotals *tot;
+    uint32_t *drop;                 // pk_place_bq: the drop plane [word_cap / 2] and the base-quality floor (behind everything else: the
+    uint32_t min_bq;                // other kernels' argument offsets stay)
 };
 
 // the sum of v[0 .. n) over the workgroup (every lane gets it); s4: LDS [PB / 64]
@@ -861,7 +943,9 @@ __global__ __launch_bounds__(PB) void pk_index(FusedArgs a)
     }
 }
 
-__global__ __launch_bounds__(PB) void pk_place(FusedArgs a)
+// BQ (pk_place_bq): as planes_body<true>
+template <bool BQ>
+__device__ __forceinline__ void place_body(const FusedArgs a)
 {
     __shared__ uint2 s_w[PB / 64];
     __shared__ unsigned long long s_sum[2 * (PB / 64)];
@@ -976,7 +1060,7 @@ __global__ __launch_bounds__(PB) void pk_place(FusedArgs a)
             s_info[lk] = word; s_word[lk] = 2u + woff; s_pos[lk] = pos; s_seq[lk] = sq;
             const uint32_t slot0 = lwoff >> 1;
             for (int q = 0; q < (int)(nwords >> 1); ++q) s_owner[slot0 + q] = own && q <= npair ? (uint16_t)0xFFFFu : (uint16_t)(lk | ((uint32_t)q << 8));
-            if (own) pack_read(view_rec(a.stream + a.rec_off[ex_r + t]), a.o, a.tot, word, pos, a.o.seq + 2u + woff);
+            if (own) pack_read<BQ>(view_rec(a.stream + a.rec_off[ex_r + t]), a.o, a.tot, word, pos, a.o.seq + 2u + woff, BQ ? a.drop + ((2u + woff) >> 1) : nullptr, a.min_bq);
         }
         __syncthreads();
         uint2 *dst = reinterpret_cast<uint2 *>(a.o.seq + 2u + w_first);                      // (word offsets are multiples of 4: 8-byte aligned)
@@ -986,12 +1070,22 @@ __global__ __launch_bounds__(PB) void pk_place(FusedArgs a)
             const int tt = (int)(ow & 255u), q = (int)(ow >> 8);
             const uint32_t info = s_info[tt];
             const int len = (int)(info & 1023u), npair = (len + 31) >> 5;
-            if (q >= npair) { dst[k] = make_uint2(0u, 0u); continue; }
+            uint32_t *ddst = BQ ? a.drop + ((2u + w_first) >> 1) : nullptr;     // (the pair at dst[k] has its drop word at ddst[k])
+            if (q >= npair) {
+                dst[k] = make_uint2(0u, 0u);
+                if constexpr (BQ) ddst[k] = 0u;
+                continue;
+            }
             const uint2 where = s_seq[tt];
             const int l_seq = (int)(where.y >> 8), y = (int)(info >> 12) + 32 * q;
             const int nb = min(32, len - 32 * q), have = min(nb, l_seq - y);
             uint32_t lo, hi, ok;
             pair_planes(a.stream + ((((unsigned long long)(where.y & 0xFFu) << 32) | where.x) + (uint32_t)(y >> 1)), y & 1, have, lo, hi, ok);
+            if constexpr (BQ) {
+                const uint32_t dd = dropped32(a.stream + (((unsigned long long)(where.y & 0xFFu) << 32) | where.x) + ((size_t)l_seq + 1) / 2, l_seq, y, nb, a.min_bq);
+                lo &= ~dd; hi &= ~dd; ok |= dd;
+                ddst[k] = dd;
+            }
             dst[k] = make_uint2(lo, hi);
             uint32_t miss = (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)) & ~ok;
             while (miss) {
@@ -1004,6 +1098,8 @@ __global__ __launch_bounds__(PB) void pk_place(FusedArgs a)
         __syncthreads();
     }
 }
+__global__ __launch_bounds__(PB) void pk_place(FusedArgs a) { place_body<false>(a); }
+__global__ __launch_bounds__(PB) void pk_place_bq(FusedArgs a) { place_body<true>(a); }
 
 } // namespace
 
@@ -1025,12 +1121,16 @@ static char *take_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t want)
 }
 
 // one allocation for everything the tally kernel reads: headers | planes | chunk records | runs | events, and 256 bytes of slack
-// behind the last array (pk_pack zeroes them)
-static int carve_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t n_reads, uint32_t word_cap, uint32_t chunk_cap, uint32_t event_cap, PackOut *o)
+// behind the last array (pk_pack zeroes them); under a base-quality floor (drop != nullptr) the drop plane behind the slack: one word
+// per pair of the plane stream, *drop_bytes of them — the caller zeroes it in front of its plane kernel, inside the pack bracket
+// (zero_drop): the pair in front of the first read and the stream's slack stay zero, the packers write every other word
+static int carve_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t n_reads, uint32_t word_cap, uint32_t chunk_cap, uint32_t event_cap, PackOut *o, uint32_t **drop,
+                      size_t *drop_bytes)
 {
     const size_t b_len = tcmi_align256(n_reads * 4), b_seq = tcmi_align256((size_t)word_cap * 4), b_run = b_len,
                  b_chk = tcmi_align256((size_t)chunk_cap * sizeof(tcmi_fast_chunk)), b_ev = tcmi_align256((size_t)event_cap * 4);
-    const size_t want = b_len + b_seq + b_chk + b_run + b_ev + 256;
+    const size_t b_drop = drop ? tcmi_align256(((size_t)word_cap / 2 + 1) * 4) : 0;
+    const size_t want = b_len + b_seq + b_chk + b_run + b_ev + 256 + b_drop;
     char *blob = take_blob(ctx, rs, want);
     if (!blob) return tcmi_fail(ctx, TCMI_E_NOMEM, "hipMalloc(%zu) for the packed read set failed", want + want / 16);
     rs->d_blob = blob;
@@ -1041,12 +1141,19 @@ static int carve_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t n_reads, uint32_t 
     o->events = (uint32_t *)(blob + b_len + b_seq + b_chk + b_run);
     o->word_cap = word_cap; o->chunk_cap = chunk_cap; o->event_cap = event_cap;
     o->slack = reinterpret_cast<uint32_t *>(blob + b_len + b_seq + b_chk + b_run + b_ev);
+    if (drop) { *drop = reinterpret_cast<uint32_t *>(blob + b_len + b_seq + b_chk + b_run + b_ev + 256); *drop_bytes = b_drop; }
     return TCMI_OK;
 }
 
-static void point_at_blob(tcmi_readset *rs, const PackOut &o)       // (the several-kernel packer: only once it has succeeded)
+// (queued like the launches beside it: an error is what hipGetLastError says behind the bracket's end — nothing returns from inside it)
+static void zero_drop(tcmi_ctx *ctx, uint32_t *drop, size_t bytes)
 {
-    rs->d_flenoff = o.lenoff; rs->d_fseq = o.seq; rs->d_fchunk = o.chunks; rs->d_fcovrun = o.covrun; rs->d_fevent = o.events;
+    if (drop) (void)hipMemsetAsync(drop, 0, bytes, ctx->stream);
+}
+
+static void point_at_blob(tcmi_readset *rs, const PackOut &o, uint32_t *drop)       // (the several-kernel packer: only once it has succeeded)
+{
+    rs->d_flenoff = o.lenoff; rs->d_fseq = o.seq; rs->d_fchunk = o.chunks; rs->d_fcovrun = o.covrun; rs->d_fevent = o.events; rs->d_fdrop = drop;
 }
 
 // what the packed set takes of its allocation
@@ -1064,6 +1171,8 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     PackSrc src = *static_cast<const PackSrc *>(src_);
     *why = 0;
     const int64_t n = src.n;
+    const uint32_t min_bq = src.mode == 1 ? src.min_bq : 0u;        // (flat arrays carry no QUAL: their entry points refuse a floor)
+    rs->min_bq = (int32_t)min_bq;
     if (n > 0xFFFFFFF0ll) { *why = PKF_LONG; return TCMI_E_UNSUPPORTED; }
     const int64_t n_blk = (n + PB - 1) / PB;
     uint32_t *info = (uint32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4);
@@ -1139,16 +1248,23 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     uint32_t event_cap = (uint32_t)std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(1 << 20, nf / 2));
     for (int attempt = 0;; ++attempt) {
         PackOut o = {};
-        if (const int rc = carve_blob(ctx, rs, (size_t)nf, word_cap, chunk_cap, event_cap, &o)) return rc;
+        uint32_t *drop = nullptr;
+        size_t drop_bytes = 0;
+        if (const int rc = carve_blob(ctx, rs, (size_t)nf, word_cap, chunk_cap, event_cap, &o, min_bq ? &drop : nullptr, &drop_bytes)) return rc;
         if (attempt > 0) TCMI_HIP(ctx, hipMemsetAsync(&d_tot->n_chunks, 0, 4 * sizeof(uint32_t), ctx->stream));    // n_chunks, n_events, n_runs, word_cursor (the first time: pk_scan)
         (void)hipGetLastError();
         tcmi_prof_begin(ctx, TCMI_K_PACK);
+        zero_drop(ctx, drop, drop_bytes);
         if (attempt == 0)
             hipLaunchKernelGGL(pk_scatter, dim3((unsigned)n_blk), dim3(PB), 0, ctx->stream, src, info, rd_seq, rd_pos, blk_sum, c_idx, c_pos, c_info, c_woff, c_seq);
         hipLaunchKernelGGL(pk_pack, dim3((unsigned)n_wg), dim3(PB), 0, ctx->stream, o, c_pos, c_info, c_woff, (uint32_t)nf,
                            (uint32_t)tot.n_words, (int)C, n_stages, ctx->stage_cap, d_tot, (int64_t)0);
-        hipLaunchKernelGGL(pk_planes, dim3((unsigned)((nf + PB - 1) / PB)), dim3(PB), 0, ctx->stream, src, o, c_idx, c_pos, c_info, c_woff, c_seq,
-                           (uint32_t)nf, (uint32_t)tot.n_words, d_tot);
+        if (min_bq)
+            hipLaunchKernelGGL(pk_planes_bq, dim3((unsigned)((nf + PB - 1) / PB)), dim3(PB), 0, ctx->stream, src, o, c_idx, c_pos, c_info, c_woff, c_seq,
+                               (uint32_t)nf, (uint32_t)tot.n_words, d_tot, drop, min_bq);
+        else
+            hipLaunchKernelGGL(pk_planes, dim3((unsigned)((nf + PB - 1) / PB)), dim3(PB), 0, ctx->stream, src, o, c_idx, c_pos, c_info, c_woff, c_seq,
+                               (uint32_t)nf, (uint32_t)tot.n_words, d_tot);
         tcmi_prof_end(ctx, TCMI_K_PACK);
         TCMI_HIP(ctx, hipGetLastError());
         TCMI_HIP(ctx, hipMemcpyAsync(h_tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
@@ -1164,7 +1280,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
             *why = tot.flags ? tot.flags : (uint32_t)PKF_EVENT_OVF;
             return TCMI_E_UNSUPPORTED;
         }
-        point_at_blob(rs, o);
+        point_at_blob(rs, o, drop);
         if (src.mode == 1) {                    // the stream and the index stay in the arena until this context's next upload
             rs->d_stream = src.stream; rs->d_rec_off = src.rec_off; rs->d_cidx = c_idx; rs->d_cpos = c_pos;
             rs->arena_epoch = ctx->arena_epoch;
@@ -1234,7 +1350,10 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     job->chunk_cap = (uint32_t)std::min<int64_t>(cap, 4 * n_wg + job->len_bound / 128 + 64);
     job->event_cap = (uint32_t)std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(1 << 20, cap / 2));
     PackOut o = {};
-    if (const int rc = carve_blob(ctx, rs, (size_t)cap, job->word_cap, job->chunk_cap, job->event_cap, &o)) return rc;
+    const uint32_t min_bq = (uint32_t)ctx->min_bq;
+    uint32_t *drop = nullptr;
+    size_t drop_bytes = 0;
+    if (const int rc = carve_blob(ctx, rs, (size_t)cap, job->word_cap, job->chunk_cap, job->event_cap, &o, min_bq ? &drop : nullptr, &drop_bytes)) return rc;
     TCMI_HIP(ctx, hipMemsetAsync(d_tot, 0, sizeof(PackTotals), ctx->stream));
     FusedArgs a = {};
     a.stream = job->d_stream; a.stream_len = job->stream_len; a.blocks = static_cast<const BlockDesc *>(job->d_desc);
@@ -1244,6 +1363,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     a.c_idx = job->c_idx; a.c_pos = job->c_pos; a.c_info = c_info; a.c_woff = c_woff; a.c_seq = c_seq; a.gen_idx = job->gen_idx;
     a.o = o; a.blk_alg = blk_alg; a.blk_end = blk_end; a.tot = d_tot;
     a.flt = tcmi_filter_pack(ctx->flt); rs->flt = ctx->flt;
+    a.drop = drop; a.min_bq = min_bq; rs->min_bq = (int32_t)min_bq;
     const size_t pre_n = tcmi_align256(((size_t)nb + 1) * 8) / 8;
     if (prefix) { a.pre_rec = pre; a.pre_k = pre + pre_n; a.pre_w = pre + 2 * pre_n; }
     (void)hipGetLastError();
@@ -1253,11 +1373,13 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     tcmi_prof_end(ctx, TCMI_K_PACK_CLASSIFY);
     TCMI_HIP(ctx, hipGetLastError());
     tcmi_prof_begin(ctx, TCMI_K_PACK);
+    zero_drop(ctx, drop, drop_bytes);
     if (prefix) {
         hipLaunchKernelGGL(pk_prefix, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const uint32_t *>(agg), 2, (int)nb, (int)nb, pre + pre_n);
         hipLaunchKernelGGL(pk_prefix, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const uint32_t *>(agg) + 1, 2, (int)nb, (int)nb, pre + 2 * pre_n);
     }
-    hipLaunchKernelGGL(pk_place, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
+    if (min_bq) hipLaunchKernelGGL(pk_place_bq, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
+    else hipLaunchKernelGGL(pk_place, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
     hipLaunchKernelGGL(pk_pack, dim3((unsigned)n_wg), dim3(PB), 0, ctx->stream, o, job->c_pos, c_info, c_woff, 0u, 0u, 0, n_stages, ctx->stage_cap, d_tot,
                        balance ? slots : (int64_t)1 << 30);
     tcmi_prof_end(ctx, TCMI_K_PACK);
@@ -1266,7 +1388,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     job->d_blk_alg = blk_alg; job->d_blk_end = blk_end;
     // the read set as the tally launch needs it before anyone has read the totals: capacities + where the real counts lie
     rs->packed_on_device = 1;
-    point_at_blob(rs, o);
+    point_at_blob(rs, o, drop);
     rs->f_chunks = job->chunk_cap; rs->f_events = job->event_cap;
     rs->d_dev_counts = &d_tot->n_chunks;
     static_assert(offsetof(PackTotals, n_events) == offsetof(PackTotals, n_chunks) + 4, "the tally kernel reads {n_chunks, n_events}");

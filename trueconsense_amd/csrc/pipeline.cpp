@@ -335,6 +335,10 @@ int tcmi_pipeline_run_batched(tcmi_pipeline *p, int64_t n_items, const tcmi_read
         return tcmi_fail(nullptr, TCMI_E_ARG, "bad argument (stride must be >= L + 1 + inserted bases)");
     if (batch < 1 || (batch > 1 && (pos_stride < L || pos_stride % 256)))
         return tcmi_fail(nullptr, TCMI_E_ARG, "bad batch / position stride");
+    for (const tcmi_ctx *c : p->slots)                          // (read sets uploaded from flat arrays: they know no base-quality floor)
+        if (c->min_bq > 0)
+            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's base-quality floor is %d (--min-baseq): the array pipeline runs read sets "
+                             "uploaded from flat arrays, which carry no QUAL", (int)c->min_bq);
     p->batch = batch;
     p->pos_stride = batch > 1 ? pos_stride : 0;
     const int64_t L_gpu = batch > 1 ? (int64_t)batch * pos_stride : L;   // positions one step covers
@@ -583,7 +587,11 @@ int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, con
                     if (rc == TCMI_E_NOMEM) rc = TCMI_E_UNSUPPORTED;     // (a file whose decode does not fit the device's memory: the host reader streams it)
                 }
                 std::string host_err;
-                if (rc == TCMI_E_UNSUPPORTED) {                  // the host reader takes it
+                if (rc == TCMI_E_UNSUPPORTED && ctx->min_bq > 0) {      // ... but not under a base-quality floor: its packer knows none
+                    const std::string why = it.file ? ctx->err : std::string("it was not read for the device decoder");
+                    rc = tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: --min-baseq %d needs the device path (the host packer knows no base-quality floor), which this "
+                                   "file left: %s", paths[i], (int)ctx->min_bq, why.c_str());
+                } else if (rc == TCMI_E_UNSUPPORTED) {           // the host reader takes it
                     rc = tcmi_bam_load(paths[i], r->host_threads, &hb);
                     if (!rc) rc = tcmi_bam_filter(hb, (int32_t)ctx->flt.min_mapq, ctx->flt.require, ctx->flt.exclude, nullptr);   // (the context's read filter)
                     if (rc) host_err = tcmi_last_error(nullptr); // (its words: it failed without a context)

@@ -192,6 +192,9 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
 {
     if (!ctx || !out || !batch || n_batch < 1) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     *out = nullptr;
+    if (ctx->min_bq > 0)                                        // (never a silently unfiltered result)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's base-quality floor is %d (--min-baseq): flat read arrays carry no QUAL and the host packer "
+                         "knows no floor; only files decoded on the device are tallied under it", (int)ctx->min_bq);
     int rc = TCMI_OK;
     int64_t n_reads_in = 0;
     for (int32_t b = 0; b < n_batch; ++b) {
@@ -656,6 +659,13 @@ int tcmi_readset_dropped(const tcmi_readset *rs, int64_t *n_dropped)
 {
     if (!rs || !n_dropped) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
     *n_dropped = rs->n_dropped;
+    return TCMI_OK;
+}
+
+int tcmi_readset_min_base_quality(const tcmi_readset *rs, int32_t *q)
+{
+    if (!rs || !q) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    *q = rs->min_bq;
     return TCMI_OK;
 }
 

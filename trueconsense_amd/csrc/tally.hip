@@ -210,6 +210,9 @@ __global__ __launch_bounds__(BLOCK) void tally_atomic_kernel(TallyArgs a)
 // each token to the count matrix with a global atomic — the token rules of tally_read_general above: a
 // matched base counts by its letter, a deleted position counts X unless an insertion follows the deletion's last base ("*+.."),
 // the last reference base in front of an insertion counts I, every position from pos to the end counts coverage (M, =, X, D, N).
+// Under a base-quality floor (s.min_bq > 0) a token whose quality is below it is skipped — no coverage, no letter, no X, no I —:
+// a matched base has its own QUAL byte, a D / N token that of the next query base (the query index at which the op starts), a query
+// index at or beyond l_seq quality 0; coverage is then added token by token.
 __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint32_t *gen_idx, uint32_t n_gen, int32_t *counts, int64_t ld, int32_t L)
 {
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -217,6 +220,9 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
     if (w >= n_gen) return;
     const ReadView v = view(s, (int64_t)gen_idx[w]);
     auto add = [&](int col, int32_t p) { if ((uint32_t)p < (uint32_t)L) atomicAdd(&counts[(int64_t)col * ld + p], 1); };
+    const uint32_t Q = s.min_bq;
+    const uint8_t *qual = v.seq + ((size_t)v.l_seq + 1) / 2;
+    auto skipped = [&](int32_t q) { return (q < v.l_seq ? byte_at(qual + q) : 0u) < Q; };     // (Q = 0: nothing is)
     int32_t x = v.pos + shift_of(s, v.tid), y = 0;
     const int32_t x0 = x;
     for (uint32_t k = 0; k < v.n_cigar; ++k) {
@@ -224,22 +230,26 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
         const int32_t len = (int32_t)(c >> 4);
         if (consumes_ref(op)) {
             const bool ins = len > 0 && ins_after(v.cigar, v.n_cigar, k);
+            bool skip_last = false;
+            if (Q && len > 0) skip_last = skipped(is_match(op) ? y + len - 1 : y);
             if (is_match(op)) {
                 for (int32_t j = lane; j < len; j += 64) {
                     const int32_t q = y + j;
+                    if (Q) { if (skipped(q)) continue; add(TCMI_COV, x + j); }
                     const uint32_t nib = q < v.l_seq ? nib_at(v.seq, q) : 15u;          // past SEQ -> 'N'
                     if (__popc(nib) == 1) { const int b = __ffs(nib) - 1; add(b == 0 ? TCMI_A : b == 1 ? TCMI_C : b == 2 ? TCMI_G : TCMI_T, x + j); }
                 }
-            } else if (op == 2) {
+            } else if (!skip_last) {
+                if (Q) for (int32_t j = lane; j < len; j += 64) add(TCMI_COV, x + j);
                 const int32_t nx = ins ? len - 1 : len;                              // "*+.." does not count X
-                for (int32_t j = lane; j < nx; j += 64) add(TCMI_X, x + j);
+                if (op == 2) for (int32_t j = lane; j < nx; j += 64) add(TCMI_X, x + j);
             }
-            if (ins && lane == 0) add(TCMI_I, x + len - 1);
+            if (ins && !skip_last && lane == 0) add(TCMI_I, x + len - 1);
             x += len;
         }
         if (consumes_query(op)) y += len;
     }
-    for (int32_t p = x0 + lane; p < x; p += 64) add(TCMI_COV, p);
+    if (Q == 0) for (int32_t p = x0 + lane; p < x; p += 64) add(TCMI_COV, p);
 }
 
 } // namespace

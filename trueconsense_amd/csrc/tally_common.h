@@ -34,6 +34,9 @@ struct FastArgs {
     const uint32_t *dev_counts;
     int32_t n_tail;                 // tail blocks of the launch (>= 1 when there can be events)
     int32_t n_chunk_blocks;         // blocks that take chunks: block b the chunks b, b + n_chunk_blocks, ..
+    // tally_planes_drop_kernel: the drop plane of a read set packed under a base-quality floor, one word per pair of `seq` (behind
+    // everything else: the other kernel's argument offsets stay)
+    const uint32_t *drop;
 };
 
 constexpr int TILE = FB;            // positions per block of the ride-along call: one lane each

@@ -154,6 +154,9 @@ struct tcmi_readset {
     // resident stream whatever the context is set to later) and the records that failed it (tcmi_readset_filtered)
     tcmi_read_filter flt = {0, 0, 0};
     int64_t n_filtered = 0;
+    // ... and its base-quality floor (tcmi_ctx_set_min_base_quality; 0: none).  Above 0 the aligned set carries a third plane,
+    // d_fdrop: one word per {lo, hi} pair of d_fseq (index = word / 2), bit b set when that read's token on that column is skipped
+    int32_t min_bq = 0;
     const uint32_t *d_gen_idx = nullptr;   // records of reads too long for the packed set (s_reads of them): tally_stream_kernel walks them in the stream
     int64_t s_reads = 0;
     // a read set of a block RANGE of a file (tcmi_readset_from_bamfile_blocks): where its first record starts when the range began
@@ -174,6 +177,7 @@ struct tcmi_readset {
     uint32_t *d_fevent = nullptr;// [f_events] position | TCMI_F_EV_*: tokens that are not plain A/C/G/T bases
     tcmi_fast_chunk *d_fchunk = nullptr;   // [f_chunks]
     uint32_t *d_fcovrun = nullptr;         // coverage runs of all chunks (tcmi_fast_chunk::run0 / n_runs)
+    uint32_t *d_fdrop = nullptr;           // [f_words / 2] the drop plane (min_bq > 0 only; in d_blob behind the events)
     // general set
     int64_t g_reads = 0, n_rounds = 0, n_cigar = 0, n_seqw = 0;
     int32_t *d_pos = nullptr;   // [g_reads]
@@ -226,6 +230,7 @@ struct tcmi_ctx {
     char *h_desc = nullptr;          // pinned: the re-based block table of a block range on its way to the device (bam_device.hip: decode_enqueue)
     size_t h_desc_cap = 0;
     tcmi_read_filter flt = {0, 0, 0};   // tcmi_ctx_set_read_filter: governs the read sets built from device-decoded record streams
+    int32_t min_bq = 0;              // tcmi_ctx_set_min_base_quality: likewise; the flat-array entry points refuse while it is above 0
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
@@ -327,7 +332,10 @@ struct tcmi_pack_src {
     const int32_t *lay; int32_t *lay_ext; int32_t n_lay;
     // the read filter (mode 1; zero for flat arrays, which carry no MAPQ)
     tcmi_filter_words flt;
+    // the base-quality floor (mode 1; in what was the struct's tail padding: no kernel's argument offsets move)
+    uint32_t min_bq;
 };
+static_assert(sizeof(tcmi_pack_src) == 128, "min_bq sits in the tail padding");
 // one read on one insert-candidate column, as the device kernel hands it to the host (ins_entries.hip -> insert_tokens.cpp)
 struct tcmi_dev_entry {
     uint64_t key;               // packed token (insert_tokens.cpp)

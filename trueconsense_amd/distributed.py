@@ -142,12 +142,13 @@ def check_range_anchors(ranges, inflated_bytes):
     return None
 
 
-def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to_root=False, read_filter=None):
+def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to_root=False, read_filter=None, min_baseq=None):
     """BASELINE configs[4] from ONE FILE: every rank opens the same BAM, decodes on its GPU only the alignment records that start
     in its contiguous range of BGZF blocks (engine.Context.upload_bamfile(blocks=...): inflate, record index, pack), tallies
     them into a full-length int32 [7][ld] matrix and the matrices are summed — to every rank, or (to_root) to rank 0 only.
     -> int [L,7] (None on the other ranks with to_root).  No rank ever holds the file's reads, decoded or not.
-    read_filter = (min_mapq, require_flags, exclude_flags): set on the rank's context (every rank the same one)."""
+    read_filter = (min_mapq, require_flags, exclude_flags), min_baseq (Context.set_min_base_quality; 0 sets no floor): set on the
+    rank's context, every rank the same ones; None leaves what the context has."""
     import torch
     from .engine import Context, DeviceBam
     L = int(L)
@@ -158,6 +159,8 @@ def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to
         ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)         # tally and collective on torch's stream
     if read_filter is not None:
         ctx.set_read_filter(*read_filter)
+    if min_baseq is not None:
+        ctx.set_min_base_quality(min_baseq)
     d = DeviceBam(path)
     try:
         import torch.distributed as dist
@@ -333,7 +336,8 @@ def split_reduce_hook_close(comm):
 
 
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
-                            step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None):
+                            step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
+                            min_baseq=None):
     """BASELINE configs[4] all the way: ONE BAM file over `world` ranks -> its consensus FASTA text on rank 0 (None on the others).
     What the ranks jointly replace is the reference's single pile-up pass (indexing.py:96-100), its insert candidates' region
     pile-ups (Events.py:47-82) and the walk (Sequences.py:168-322):
@@ -358,7 +362,9 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     writers need (Outputs.WriteOutputs, Coverage.BuildCoverage).  ctx / dbam: the caller's (kept open: a bench loop); timings: a dict
     that receives the seconds of "step" (tcmi_split_step, reduce included) and "entries" (steps 2-4 up to the vote).
     read_filter = (min_mapq, require_flags, exclude_flags): every rank sets the same one on its context (its read set keeps it for
-    step 3), and rank 0's host sweep of step 4 removes the failing records too."""
+    step 3), and rank 0's host sweep of step 4 removes the failing records too.  min_baseq: the base-quality floor of the count
+    matrix, on every rank's context (Context.set_min_base_quality; 0 sets no floor, None leaves what the context has); the insert
+    tokens keep their own quality rule."""
     import time
     import torch
     import torch.distributed as dist
@@ -385,6 +391,8 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                     d = DeviceBam(path)
                 if read_filter is not None:
                     ctx.set_read_filter(*read_filter)
+                if min_baseq is not None:
+                    ctx.set_min_base_quality(min_baseq)
             except (TcmiError, OSError) as e:                        # this rank cannot even start: it must still meet the others in the reduce
                 err = (getattr(e, "code", _ffi_E_ARG), str(e))
             n_tail = 6 * int(world) + 1                              # TCMI_SPLIT_TAIL_WORDS(world)
@@ -512,7 +520,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
 
 
 def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=True, name="S", device=0, return_parts=False, timings=None,
-                        split_sub=None, read_filter=None):
+                        split_sub=None, read_filter=None, min_baseq=None):
     """BASELINE configs[4] at ANY world size on the ONE GPU there is: the ranks' steps of a `world`-GPU job played one after the other
     on one context — rank world-1 first, rank 0 (the root) last — each through tcmi_split_step exactly as a rank of the real job runs
     it (its own contiguous range of the file's BGZF blocks + the block behind it, the range table and the failure word behind the
@@ -537,6 +545,8 @@ def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=Tr
         ctx.set_option("split_sub", int(split_sub))
     if read_filter is not None:                                      # (every rank the same filter)
         ctx.set_read_filter(*read_filter)
+    if min_baseq is not None:                                        # (... and the same base-quality floor)
+        ctx.set_min_base_quality(min_baseq)
     d = DeviceBam(path)
     n_words = 7 * ld + 6 * world + 1                                 # TCMI_SPLIT_TAIL_WORDS(world)
     acc = torch.zeros(n_words, dtype=torch.int32, device="cuda")

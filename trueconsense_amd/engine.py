@@ -42,6 +42,9 @@ class ReadSet:
         n = C.c_int64(0)
         check(lib().tcmi_readset_filtered(handle, C.byref(n)))
         self.filtered = n.value                     # records that failed the read filter the set was built under (Context.set_read_filter)
+        q = C.c_int32(0)
+        check(lib().tcmi_readset_min_base_quality(handle, C.byref(q)))
+        self.min_base_quality = q.value             # the base-quality floor the set was built under (Context.set_min_base_quality)
 
     def ref_extents(self, n_ref):
         """Uploaded under a contig layout of n_ref references: per reference the kept reads' max end in its own coordinates."""
@@ -69,6 +72,9 @@ class ReadSet:
 
 class Context:
     """One device + stream.  Raises TcmiError(E_NODEVICE) when no gfx950 GPU is usable."""
+
+    read_filter = None              # what set_read_filter / set_min_base_quality last set (a context made by the library starts without either)
+    min_base_quality = 0
 
     def __init__(self, device=0, stream=None):
         """stream: a hipStream_t as an int (0 = the default stream) to run on, e.g. another Context's
@@ -128,6 +134,13 @@ class Context:
         device-decoded file ignores the records that fail it, as it ignores unmapped ones.  No arguments: no filter."""
         check(lib().tcmi_ctx_set_read_filter(self.handle, int(min_mapq), int(require_flags), int(exclude_flags)), self.handle)
         self.read_filter = (int(min_mapq), int(require_flags), int(exclude_flags))
+
+    def set_min_base_quality(self, q=0):
+        """Base-quality floor (tcmi_ctx_set_min_base_quality; samtools mpileup -Q): from now on every read set this context builds
+        from a device-decoded file skips the pileup tokens whose quality is below q — nothing for coverage, a base, X or I.  While
+        q > 0 the flat-array entry points (upload, tally, the array Pipeline) refuse with E_UNSUPPORTED.  No argument: no floor."""
+        check(lib().tcmi_ctx_set_min_base_quality(self.handle, int(q)), self.handle)
+        self.min_base_quality = int(q)
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
@@ -623,7 +636,8 @@ class FileRunner:
     A file the device decoder does not take (records straddling BGZF blocks, long reads) is decoded by the host reader
     (tcmi_bam_load, `decode_threads` threads) and packed from its flat arrays.  `seconds` accumulates each stage's busy time."""
 
-    def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None):
+    def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None,
+                 min_baseq=0):
         device = ctx.device if isinstance(ctx, Context) else int(ctx)
         self.mincov, self.amb = int(mincov), bool(include_ambig)
         h = C.c_void_p()
@@ -641,6 +655,9 @@ class FileRunner:
         if read_filter is not None:                 # (every context the same: the runner's host-reader fallbacks take it from them)
             for c in self.contexts:
                 c.set_read_filter(*read_filter_args(read_filter))
+        if min_baseq:                               # (a file that leaves the device path is then refused, never tallied without the floor)
+            for c in self.contexts:
+                c.set_min_base_quality(min_baseq)
 
     @property
     def contexts(self):

@@ -41,7 +41,8 @@ def build_counts(bamfile, ref, ctx=None):
     ON THE DEVICE (BGZF inflate, record chain, pack: csrc/bam_device.hip, pack_device.hip); files the device decoder
     declines, and BamFile objects, go through the host reader's flat arrays.  A read filter is the context's
     (Context.set_read_filter): the host reader's fallback applies the same one (a LazyBam's own, if it has one); a BamFile is
-    taken as it is."""
+    taken as it is.  Under a base-quality floor (Context.set_min_base_quality) there is no fallback: the host packer knows no
+    floor, and a file the device decoder declines is refused with its reason."""
     ref_length = fasta.first_length(ref) if isinstance(ref, str) else int(ref)
     ctx = ctx or _state.default_context()
     if not isinstance(bamfile, BamFile):
@@ -52,6 +53,10 @@ def build_counts(bamfile, ref, ctx=None):
         except _ffi.TcmiError as e:
             if e.code != _ffi.E_UNSUPPORTED:
                 raise
+            q = ctx.min_base_quality
+            if q:
+                raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--min-baseq %d needs the device path (the host packer knows no base-quality floor), "
+                                     "which %s left: %s" % (q, path, e)) from e
             rs = None
         finally:
             d.close()
