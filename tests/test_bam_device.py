@@ -10,6 +10,8 @@ import pytest
 from oracle import c_oracle
 from tests import fuzz_reads as fz
 from tests import synth_small as ss
+from tests import test_bam_fixture as hand
+from tests import test_bgzf_host as host
 from trueconsense_amd import _ffi, _state, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
@@ -121,6 +123,24 @@ def test_device_inflate_and_record_index_match_zlib(ctx, tmp_path):
     p = str(tmp_path / "empty.bam")
     bamwriter.write_bam(p, empty, "MN908947.3", len(ref))
     check_decode(ctx, p).close()
+
+
+def test_both_readers_report_the_same_container(tmp_path):
+    """tcmi_bamfile_read (the device decoder's front) and tcmi_bam_load (the host reader) parse the BGZF blocks and the BAM header with
+    the same functions (bgzf_host.cpp): block count, inflated bytes, header text and every reference agree — on the hand-assembled
+    file and on a header of several blocks whose first record starts mid-block."""
+    paths = [str(tmp_path / "hand.bam"), str(tmp_path / "long_header.bam")]
+    hand.build(paths[0], straddle=False)
+    refs = host.long_header_bam(paths[1])
+    for p in paths:
+        d, b = engine.DeviceBam(p), engine.BamFile(p)
+        assert (d.n_blocks, d.inflated_bytes, d.file_bytes) == (b.n_blocks, b.inflated_bytes, b.file_bytes)
+        assert d.text == b.text and d.text.startswith("@HD")
+        assert (d.nreferences, d.all_references, d.all_lengths) == (b.nreferences, b.all_references, b.all_lengths)
+        if p == paths[1]:
+            assert (b.nreferences, b.all_references, b.all_lengths) == (300, tuple(r[0] for r in refs), tuple(r[1] for r in refs))
+        d.close()
+        b.close()
 
 
 def test_device_inflate_on_other_deflate_flavours(ctx, tmp_path):
@@ -265,7 +285,7 @@ def test_file_to_counts_all_on_device(ctx, tmp_path):
 def test_records_that_straddle_bgzf_blocks_are_decoded_on_the_device(ctx, tmp_path):
     """Writers other than htslib (htsjdk: Picard, GATK) fill every BGZF block to the brim: records — and their block_size fields —
     run from one block into the next.  Every block finds the first record start in its own bytes, the host checks that the
-    chain closes (bam_device.hip); stream, record index and counts as from a file cut on record boundaries."""
+    chain closes (bgzf_host.h: tcmi_bam_chain_check); stream, record index and counts as from a file cut on record boundaries."""
     ref, _ = sy.make_reference(L=5000, cds=[(10, 600)])
     reads = sy.make_reads(ref, 4000, seed=1)
     p = str(tmp_path / "split.bam")

@@ -1,18 +1,16 @@
 // bam_device.hip — DEVICE: a BAM file's BGZF blocks -> the inflated BAM byte stream + the offset of every alignment
 // record, in HBM, without the host ever decoding the file (pysam / htslib's role for indexing.py:19,96-100; wire format
-// SAM spec §4.1 BGZF, §4.2 BAM, RFC 1951 DEFLATE).
+// SAM spec §4.1 BGZF, §4.2 BAM, RFC 1951 DEFLATE) — and the drivers from a file to a read set and to a step's results.
 //
-// The host only reads the file, walks the gzip member headers (18 bytes per block) and inflates the first block(s) far
-// enough to parse the BAM header; the compressed bytes (a few MB .. tens of MB) cross PCIe once.
+// The file arrives as a tcmi_bamfile (bamfile.cpp reads it into pinned memory; bgzf_host.cpp parses the block table and the BAM
+// header out of it); the compressed bytes (a few MB .. tens of MB) cross PCIe once.
 //
 //   (bgzf_symbols.hip, bgzf_copy.hip)  bgzf_symbols + bgzf_copy: the compressed blocks -> the inflated stream and every block's record starts
 //                  (bgzf_copy also takes every block's CRC-32 against its trailer while it flushes the bytes: no pass of its own)
-//   rec_compact    per-block record lists -> one dense array of record offsets (block scan + copy)
+//   rec_scan       the blocks' record counts -> their places in the dense array (one workgroup)
+//   rec_compact    per-block record lists -> one dense array of record offsets
 //
 // Serial-latency-bound bit / byte work, not HBM-bound and not a contraction: no MFMA.
-#include <unistd.h>
-#include <zlib.h>
-
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -20,11 +18,9 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <string>
-#include <thread>
 #include <vector>
 
+#include "bamfile.h"
 #include "bgzf_device.h"
 
 namespace {
@@ -73,305 +69,7 @@ __global__ __launch_bounds__(256) void rec_compact(const BlockDesc *blocks, cons
     for (uint32_t i = threadIdx.x; i < n; i += 256) rec_off[b0 + i] = u0 + src[i];
 }
 
-inline uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-inline uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
 } // namespace
-
-// ---- host side ------------------------------------------------------------------------------------------------------------
-struct tcmi_bamfile {                           // a BAM file's bytes in pinned host memory + what the host parsed of it
-    uint8_t *bytes = nullptr;                   // hipHostMalloc
-    uint8_t *d_bytes = nullptr;                 // the same `cap` bytes in HBM (tcmi_bamfile_to_device), or null
-    size_t desc_at = 0;                         // the block table (BlockDesc[]) lies behind the file's bytes, at this offset of `bytes` / `d_bytes` (0: it does not)
-    int d_device = -1;
-    size_t n_bytes = 0, cap = 0;                // cap: bytes that go to the device (file + zeroed slack)
-    size_t pool_cap = 0;                        // bytes of the pinned allocation
-    std::vector<BlockDesc> blocks;
-    size_t inflated = 0;                        // bytes of the stream as laid out on the device (blocks padded to 16 bytes)
-    size_t tok_total = 0;                       // tokens reserved for all blocks (bgzf_symbols -> bgzf_copy)
-    uint32_t pay_dwords = 0;                    // the largest block's payload in dwords + slack (bgzf_symbols' dynamic LDS)
-    uint32_t rec_bytes_hint = 0;                // mean bytes of the alignment records behind the header in the blocks the host inflated (0: too few seen)
-    std::string text;
-    std::vector<std::string> ref_name;
-    std::vector<int64_t> ref_len;
-    std::string path;
-};
-
-namespace {
-// pinned file buffers are kept for the next file: hipHostMalloc / hipHostFree cost about as much as reading 8 MB
-struct PinnedPool {
-    std::mutex mu;
-    struct Buf { uint8_t *p; size_t cap; };
-    std::vector<Buf> free_;
-    uint8_t *take(size_t want, size_t *cap)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            for (size_t k = 0; k < free_.size(); ++k)
-                if (free_[k].cap >= want && free_[k].cap <= 2 * want + (1 << 20)) {
-                    uint8_t *p = free_[k].p;
-                    *cap = free_[k].cap;
-                    free_.erase(free_.begin() + (long)k);
-                    return p;
-                }
-        }
-        uint8_t *p = nullptr;
-        const size_t c = want + want / 8;
-        if (hipHostMalloc((void **)&p, c, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        *cap = c;
-        return p;
-    }
-    void give(uint8_t *p, size_t cap)
-    {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            if (free_.size() < 8) { free_.push_back({p, cap}); return; }
-        }
-        (void)hipHostFree(p);
-    }
-};
-PinnedPool &pinned_pool() { static PinnedPool *p = new PinnedPool(); return *p; }   // (never destroyed: the HIP runtime may be gone by then)
-} // namespace
-
-extern "C" {
-
-int tcmi_bamfile_free(tcmi_bamfile *f)
-{
-    if (!f) return TCMI_OK;
-    if (f->bytes) pinned_pool().give(f->bytes, f->pool_cap);
-    if (f->d_bytes) (void)hipFree(f->d_bytes);
-    delete f;
-    return TCMI_OK;
-}
-
-// The file's compressed bytes into HBM, to stay there: tcmi_readset_from_bamfile[_blocks] of this file then starts from device
-// memory (no PCIe copy per call) — the form in which a file arrives that a peer GPU, a NIC or a storage engine wrote into HBM,
-// and the one bench.py's headline times ("inputs resident in HBM when the timed region starts").
-int tcmi_bamfile_to_device(tcmi_ctx *ctx, tcmi_bamfile *f)
-{
-    if (!ctx || !f) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
-    TCMI_HIP(ctx, hipSetDevice(ctx->device));
-    if (f->d_bytes && f->d_device == ctx->device) return TCMI_OK;
-    if (f->d_bytes) { (void)hipFree(f->d_bytes); f->d_bytes = nullptr; }
-    if (hipMalloc((void **)&f->d_bytes, f->cap) != hipSuccess) {
-        (void)hipGetLastError();
-        f->d_bytes = nullptr;
-        return tcmi_fail(ctx, TCMI_E_NOMEM, "hipMalloc(%zu) for the bytes of %s failed", f->cap, f->path.c_str());
-    }
-    f->d_device = ctx->device;
-    TCMI_HIP(ctx, hipMemcpyAsync(f->d_bytes, f->bytes, f->cap, hipMemcpyHostToDevice, ctx->stream));
-    TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return TCMI_OK;
-}
-
-const char *tcmi_bamfile_path(const tcmi_bamfile *f) { return f ? f->path.c_str() : ""; }
-
-// Read the file into pinned memory, walk the BGZF block headers (RFC 1952 + the BC subfield) and parse the BAM header
-// (inflating, with zlib on this thread, only as many leading blocks as the header occupies).
-int tcmi_bamfile_read(const char *path, tcmi_bamfile **out) { return tcmi_bamfile_read_threads(path, 0, out); }
-
-// read_threads: threads that copy the file in (0 = by size: four for a file of several MB, which takes the latency of one file
-// from 1.15 to 0.65 ms; a runner that reads several files at a time passes 1 — its reader threads are parallel already, and more
-// threads only take cores from the ones that feed the GPU: 42.9 vs 41.7 M positions/s)
-int tcmi_bamfile_read_threads(const char *path, int read_threads, tcmi_bamfile **out)
-{
-    if (!path || !out) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
-    *out = nullptr;
-    static const bool timing = std::getenv("TCMI_READ_TIMING") != nullptr;
-    const auto tt0 = std::chrono::steady_clock::now();
-    FILE *fp = std::fopen(path, "rb");
-    if (!fp) return tcmi_fail(nullptr, TCMI_E_IO, "cannot open %s", path);
-    std::fseek(fp, 0, SEEK_END);
-    const long sz = std::ftell(fp);
-    std::fseek(fp, 0, SEEK_SET);
-    if (sz < 0) { std::fclose(fp); return tcmi_fail(nullptr, TCMI_E_IO, "cannot size %s", path); }
-    tcmi_bamfile *f = new tcmi_bamfile();
-    f->path = path;
-    f->n_bytes = (size_t)sz;
-    f->cap = ((size_t)sz + 4096 + 15) & ~(size_t)15;            // slack: the inflate kernel stages its input 1 KiB at a time
-    // (+ room for the block table behind the bytes, so that ONE copy takes both to the device: a block is at least 28 bytes, usually ~ 2 KB and more)
-    const size_t table_room = std::min<size_t>(((size_t)sz / 28 + 2) * sizeof(BlockDesc), ((size_t)sz / 512 + 64) * sizeof(BlockDesc));
-    f->bytes = pinned_pool().take(f->cap + table_room + 1024, &f->pool_cap);
-    if (!f->bytes) {
-        std::fclose(fp);
-        delete f;
-        return tcmi_fail(nullptr, TCMI_E_NOMEM, "hipHostMalloc(%zu) for %s failed (is a GPU present?)", (size_t)sz + 4096, path);
-    }
-    // The file's bytes into the pinned buffer: a page-cache copy runs at ~7 GB/s per thread, which for a file of several MB is
-    // most of what this function costs — so a few threads take a quarter each (pread on the same descriptor).
-    const auto tt1 = std::chrono::steady_clock::now();
-    size_t got = 0;
-    {
-        const int fd = fileno(fp);
-        static const int forced = std::getenv("TCMI_READ_THREADS") ? std::atoi(std::getenv("TCMI_READ_THREADS")) : 0;   // (A/B measurements)
-        const int n_thr = forced > 0 ? std::min(forced, 16) : read_threads > 0 ? std::min(read_threads, 16) : sz > (4l << 20) ? 4 : sz > (1l << 20) ? 2 : 1;
-        std::vector<size_t> part((size_t)n_thr, 0);
-        auto piece = [&](int t) {
-            const size_t lo = (size_t)sz * (size_t)t / (size_t)n_thr, hi = (size_t)sz * (size_t)(t + 1) / (size_t)n_thr;
-            size_t at = lo;
-            while (at < hi) {
-                const ssize_t r = pread(fd, f->bytes + at, hi - at, (off_t)at);
-                if (r <= 0) break;
-                at += (size_t)r;
-            }
-            part[(size_t)t] = at - lo;
-        };
-        std::vector<std::thread> thr;
-        for (int t = 1; t < n_thr; ++t) thr.emplace_back(piece, t);
-        piece(0);
-        for (auto &t : thr) t.join();
-        for (size_t p : part) got += p;
-    }
-    const auto tt2 = std::chrono::steady_clock::now();
-    std::fclose(fp);
-    std::memset(f->bytes + f->n_bytes, 0, f->cap - f->n_bytes);
-    const size_t table_cap = table_room;
-    auto bail = [&](int code, const char *what, size_t at) {
-        tcmi_bamfile_free(f);
-        return tcmi_fail(nullptr, code, "%s: %s at byte %zu", path, what, at);
-    };
-    if (got != (size_t)sz) return bail(TCMI_E_IO, "short read", got);
-    // ---- block headers ----
-    static const bool prefetch_ahead = std::getenv("TCMI_NO_HEADER_PREFETCH") == nullptr;
-    size_t off = 0, uout = 0;
-    while (off < f->n_bytes) {
-        if (f->n_bytes - off < 18) return bail(TCMI_E_FORMAT, "truncated BGZF block header", off);
-        const uint8_t *h = f->bytes + off;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return bail(TCMI_E_FORMAT, "not a BGZF block (is the file a BAM?)", off);
-        const size_t xlen = rd16(h + 10);
-        if (f->n_bytes - off < 12 + xlen) return bail(TCMI_E_FORMAT, "truncated BGZF extra field", off);
-        size_t bsize = 0;
-        for (size_t x = 0; x + 4 <= xlen;) {
-            const uint8_t *s = h + 12 + x;
-            const size_t slen = rd16(s + 2);
-            if (s[0] == 'B' && s[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = (size_t)rd16(s + 4) + 1;
-            x += 4 + slen;
-        }
-        if (bsize < 12 + xlen + 8 || f->n_bytes - off < bsize) return bail(TCMI_E_FORMAT, "bad BGZF block size", off);
-        // (the chain of headers is a chain of cache misses once other threads have copied the file in — each header lies in some
-        //  other core's cache or in memory: ask for the lines where the block after next will probably start; blocks of one file
-        //  are of similar size)
-        if (prefetch_ahead) {
-            const size_t guess = off + 3 * bsize;
-            if (guess + 512 < f->n_bytes && guess > 512)
-                for (size_t x = guess - 384; x < guess + 384; x += 64) __builtin_prefetch(f->bytes + x, 0, 1);
-        }
-        BlockDesc b;
-        b.cin = off + 12 + xlen;
-        b.clen = (uint32_t)(bsize - 12 - xlen - 8);
-        b.ulen = rd32(h + bsize - 4);
-        b.uout = uout;
-        b.entry = -2;                                           // (-2: the block's first record starts where the device finds it)
-        if (b.ulen > 65536) return bail(TCMI_E_FORMAT, "BGZF block inflates to more than 64 KiB", off);
-        // tokens: one per literal / match (each gives >= 1 byte and takes >= 1 bit), one per <= 8 191 stored bytes (a stored
-        // deflate block takes >= 5 bytes)
-        b.tok_cap = std::min(b.ulen, 8u * b.clen) + b.clen / 2 + 8;
-        b.tok = f->tok_total;
-        f->tok_total += (2u * b.tok_cap + 3u) & ~3u;        // (as many again behind them: bgzf_symbols' scratch)
-        f->pay_dwords = std::max(f->pay_dwords, (uint32_t)(((b.cin & 3u) * 8u + b.clen * 8u + 31u) / 32u + 6u));
-        uout += (size_t)b.ulen;                                 // the blocks' outputs follow each other without gaps: the stream as it inflates
-        off += bsize;
-        f->blocks.push_back(b);
-    }
-    f->inflated = uout;
-    if (f->blocks.size() * sizeof(BlockDesc) <= table_cap) f->desc_at = (f->cap + 255) & ~(size_t)255;     // (else: blocks of < 512 bytes — the table goes by a copy of its own)
-    const auto tt3 = std::chrono::steady_clock::now();
-    // ---- BAM header: inflate leading blocks on this thread until it is complete ----
-    std::vector<uint8_t> head;
-    size_t nb = 0;
-    auto more = [&]() -> bool {
-        if (nb >= f->blocks.size()) return false;
-        const BlockDesc &b = f->blocks[nb];
-        const size_t at = head.size();
-        head.resize(at + b.ulen);
-        if (b.ulen) {
-            z_stream zs;
-            std::memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, -15) != Z_OK) return false;
-            zs.next_in = f->bytes + b.cin; zs.avail_in = b.clen;
-            zs.next_out = head.data() + at; zs.avail_out = b.ulen;
-            const int rc = inflate(&zs, Z_FINISH);
-            const bool ok = rc == Z_STREAM_END && zs.total_out == b.ulen;
-            inflateEnd(&zs);
-            if (!ok) return false;
-        }
-        ++nb;
-        return true;
-    };
-    auto need = [&](size_t k) { while (head.size() < k) if (!more()) return false; return true; };
-    if (!need(12) || std::memcmp(head.data(), "BAM\1", 4) != 0) return bail(TCMI_E_FORMAT, "BAM magic missing", 0);
-    const size_t l_text = rd32(head.data() + 4);
-    if (!need(12 + l_text)) return bail(TCMI_E_FORMAT, "truncated header text", 8);
-    f->text.assign((const char *)head.data() + 8, l_text);
-    size_t o = 8 + l_text;
-    const size_t n_ref = rd32(head.data() + o);
-    o += 4;
-    for (size_t r = 0; r < n_ref; ++r) {
-        if (!need(o + 4)) return bail(TCMI_E_FORMAT, "truncated reference list", o);
-        const size_t l_name = rd32(head.data() + o);
-        o += 4;
-        if (!need(o + l_name + 4)) return bail(TCMI_E_FORMAT, "truncated reference name", o);
-        f->ref_name.emplace_back((const char *)head.data() + o, l_name ? l_name - 1 : 0);
-        o += l_name;
-        f->ref_len.push_back((int64_t)rd32(head.data() + o));
-        o += 4;
-    }
-    // records start `o` bytes into the stream: in block k at offset o - (inflated bytes of the blocks before it)
-    size_t before = 0;
-    size_t k = 0;
-    for (; k < f->blocks.size(); ++k) {
-        if (o < before + f->blocks[k].ulen) break;
-        f->blocks[k].entry = -1;                                  // header only (or empty)
-        before += f->blocks[k].ulen;
-    }
-    if (k < f->blocks.size()) f->blocks[k].entry = (int32_t)(o - before);
-    {   // what is left of the inflated bytes behind the header are the file's first records: their mean size sizes the one-sync path's arrays
-        size_t at = o, cnt = 0;
-        while (at + 4 <= head.size()) {
-            const size_t bs = rd32(head.data() + at);
-            if (bs < 32 || bs > (1u << 24) || at + 4 + bs > head.size()) break;
-            at += 4 + bs;
-            ++cnt;
-        }
-        if (cnt >= 16) f->rec_bytes_hint = (uint32_t)((at - o) / cnt);
-    }
-    if (f->desc_at) {
-        std::memcpy(f->bytes + f->desc_at, f->blocks.data(), f->blocks.size() * sizeof(BlockDesc));
-        f->cap = f->desc_at + ((f->blocks.size() * sizeof(BlockDesc) + 255) & ~(size_t)255);      // what goes to the device: bytes, slack, table
-    }
-    if (timing) {
-        const auto tt4 = std::chrono::steady_clock::now();
-        auto us = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
-        std::fprintf(stderr, "[tcmi] bamfile_read %s: open + pinned buffer %ld us, read %ld us, block table %ld us, header %ld us\n", path, us(tt0, tt1), us(tt1, tt2), us(tt2, tt3), us(tt3, tt4));
-    }
-    *out = f;
-    return TCMI_OK;
-}
-
-int tcmi_bamfile_ref(const tcmi_bamfile *f, int32_t i, const char **name, int64_t *len)
-{
-    if (!f || i < 0 || (size_t)i >= f->ref_name.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "no reference %d in the header", i);
-    if (name) *name = f->ref_name[(size_t)i].c_str();
-    if (len) *len = f->ref_len[(size_t)i];
-    return TCMI_OK;
-}
-
-int tcmi_bamfile_info(const tcmi_bamfile *f, int64_t *file_bytes, int64_t *inflated_bytes, int64_t *n_blocks, int32_t *n_ref,
-                      const char **ref0_name, int64_t *ref0_len)
-{
-    if (!f) return tcmi_fail(nullptr, TCMI_E_ARG, "bamfile is NULL");
-    if (file_bytes) *file_bytes = (int64_t)f->n_bytes;
-    if (inflated_bytes) { int64_t s = 0; for (const auto &b : f->blocks) s += b.ulen; *inflated_bytes = s; }
-    if (n_blocks) *n_blocks = (int64_t)f->blocks.size();
-    if (n_ref) *n_ref = (int32_t)f->ref_name.size();
-    if (ref0_name) *ref0_name = f->ref_name.empty() ? "" : f->ref_name[0].c_str();
-    if (ref0_len) *ref0_len = f->ref_len.empty() ? 0 : f->ref_len[0];
-    return TCMI_OK;
-}
-
-const char *tcmi_bamfile_text(const tcmi_bamfile *f) { return f ? f->text.c_str() : ""; }
-
-} // extern "C"
 
 // ---- device decode: H2D of the compressed file, bgzf_symbols + bgzf_copy (all in the context's arena) ---------------------------------
 namespace {
@@ -590,47 +288,10 @@ int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, 
     TCMI_HIP(ctx, hipMemcpyAsync(pin, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
     TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const unsigned long long total = *(const unsigned long long *)pin;
-    for (size_t b = 0; b < nb; ++b)
-        if (stat[b] == ST_BAD_STREAM || stat[b] == ST_BAD_LENGTH)
-            return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: BGZF block %zu failed to inflate (deflate stream or ISIZE damaged)", f->path.c_str(), b);
-    for (size_t b = 0; b < nb; ++b)
-        if (stat[b] == ST_BAD_CRC)
-            return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: CRC32 mismatch in BGZF block %zu", f->path.c_str(), b);
-    // The record chain.  Every block found the first record start in its own bytes by itself — where the header says (the first
-    // record), or the first offset at which a plausible record starts (htslib cuts its blocks on record boundaries: offset 0;
-    // other writers fill them to the brim) — and followed the chain of block_size fields from there.  In block order: if every
-    // block's find is where its predecessor's last record ends, all of them are record starts, by induction from the header.
-    {
-        int64_t expect = -1;                                    // offset in the next block at which a record must start
-        bool open = ranged;                                     // (a range: wherever its first block found one)
-        for (size_t b = 0; b < nb_own; ++b) {
-            const BlockDesc &d = f->blocks[b];
-            if (d.entry == -1) continue;                        // header only
-            if (open && first[b] != 0xFFFFFFFFu) { expect = first[b]; open = false; if (d.entry < 0) Dout->range_first = (int64_t)d.uout + first[b]; }
-            if (open) continue;
-            if (stat[b] == ST_BAD_RECORD)
-                return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: alignment record with an impossible block_size in BGZF block %zu", f->path.c_str(), b);
-            if (d.entry >= 0) expect = d.entry;
-            if (first[b] == 0xFFFFFFFFu) {                      // no record starts in this block: it lies inside one, or is empty
-                if (expect < (int64_t)d.ulen)
-                    return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: no alignment record found where one must start in BGZF block %zu: host reader", f->path.c_str(), b);
-                expect -= d.ulen;
-                continue;
-            }
-            if ((int64_t)first[b] != expect || over[b] < 0)
-                return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the chain of alignment records does not close at BGZF block %zu (found a start at %u, expected %lld): host reader",
-                                 f->path.c_str(), b, first[b], (long long)expect);
-            expect = over[b];
-        }
-        if (!open && nb_own > 0) Dout->range_next = (int64_t)(f->blocks[nb_own - 1].uout + f->blocks[nb_own - 1].ulen) + expect;
-        if (nb_own < nb) {                                      // the range's last record must end in the block taken along
-            if (expect > (int64_t)f->blocks[nb_own].ulen)
-                return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: a record longer than a BGZF block at the end of a block range: host reader", f->path.c_str());
-            expect = 0;
-        }
-        if (expect > 0)
-            return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the last alignment record runs %lld bytes past the end of the file: host reader", f->path.c_str(), (long long)expect);
-    }
+    // the record chain (bgzf_host.h): every block's find is where its predecessor's last record ends
+    const tcmi_chain_verdict v = tcmi_bam_chain_check(f->blocks.data(), nb, nb_own, ranged, stat, first, over);
+    if (v.code) return tcmi_fail(ctx, v.code, "%s: %s", f->path.c_str(), v.what.c_str());
+    Dout->range_first = v.range_first; Dout->range_next = v.range_next;
     if (total > max_rec) return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: impossible record count", f->path.c_str());
     const size_t n = (size_t)total;
     const size_t need_rest = rest_bytes(n, nb);
@@ -935,8 +596,7 @@ int tcmi_bamfile_decode_to_host(tcmi_ctx *ctx, const tcmi_bamfile *f, uint8_t *s
     if (rc) return rc;
     *n_rec = (int64_t)D.n;
     if ((int64_t)D.n > rec_cap && rec_off) return tcmi_fail(ctx, TCMI_E_ARG, "rec_off holds %lld entries, the file has %zu records", (long long)rec_cap, D.n);
-    int64_t inflated = 0;
-    for (const BlockDesc &b : f->blocks) inflated += b.ulen;
+    const int64_t inflated = (int64_t)f->inflated;
     if (inflated > stream_cap) return tcmi_fail(ctx, TCMI_E_ARG, "stream buffer too small");
     if (inflated) TCMI_HIP(ctx, hipMemcpyAsync(stream, D.d_out, (size_t)inflated, hipMemcpyDeviceToHost, ctx->stream));
     if (rec_off && D.n) TCMI_HIP(ctx, hipMemcpyAsync(rec_off, D.d_rec, D.n * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -5,8 +5,6 @@
 // needed: the whole file is inflated (BGZF blocks are independent gzip members, so they are
 // inflated by `n_threads` workers straight into their final place in one buffer) and every
 // record is decoded once into struct-of-arrays form, the layout tcmi_readset_upload consumes.
-#include <zlib.h>
-
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -18,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "bgzf_host.h"
 #include "tcmi_internal.h"
 
 // a buffer that is not zero-filled on allocation: the decode passes write every byte they hand out, and
@@ -49,67 +48,6 @@ struct tcmi_bam {
     int64_t file_bytes = 0, inflated_bytes = 0, n_blocks = 0;
 };
 
-namespace {
-
-struct Block { size_t cin, clen, uout, ulen; uint32_t crc; };
-
-inline uint16_t rd16(const uint8_t *p) { return (uint16_t)(p[0] | (p[1] << 8)); }
-inline uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
-
-// Walk the gzip member headers (RFC 1952 + the BC extra subfield of SAM spec §4.1).
-int scan_blocks(const std::vector<uint8_t> &f, std::vector<Block> &blocks, size_t *total)
-{
-    size_t off = 0, out = 0;
-    while (off < f.size()) {
-        if (f.size() - off < 18) return tcmi_fail(nullptr, TCMI_E_FORMAT, "truncated BGZF block header at byte %zu", off);
-        const uint8_t *h = f.data() + off;
-        if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4))
-            return tcmi_fail(nullptr, TCMI_E_FORMAT, "not a BGZF block at byte %zu (is the file a BAM?)", off);
-        const size_t xlen = rd16(h + 10);
-        if (f.size() - off < 12 + xlen) return tcmi_fail(nullptr, TCMI_E_FORMAT, "truncated BGZF extra field at byte %zu", off);
-        size_t bsize = 0;
-        for (size_t x = 0; x + 4 <= xlen;) {
-            const uint8_t *s = h + 12 + x;
-            const size_t slen = rd16(s + 2);
-            if (s[0] == 'B' && s[1] == 'C' && slen == 2 && x + 6 <= xlen) bsize = (size_t)rd16(s + 4) + 1;
-            x += 4 + slen;
-        }
-        if (bsize < 12 + xlen + 8 || f.size() - off < bsize)
-            return tcmi_fail(nullptr, TCMI_E_FORMAT, "bad BGZF block size at byte %zu", off);
-        Block b;
-        b.cin = off + 12 + xlen;
-        b.clen = bsize - 12 - xlen - 8;
-        b.crc = rd32(h + bsize - 8);
-        b.ulen = rd32(h + bsize - 4);
-        b.uout = out;
-        if (b.ulen > 65536) return tcmi_fail(nullptr, TCMI_E_FORMAT, "BGZF block at byte %zu inflates to %zu bytes (> 64 KiB)", off, b.ulen);
-        out += b.ulen;
-        off += bsize;
-        blocks.push_back(b);
-    }
-    *total = out;
-    return TCMI_OK;
-}
-
-bool inflate_block(const uint8_t *in, const Block &b, uint8_t *out)
-{
-    if (b.ulen == 0) return true;
-    z_stream zs;
-    std::memset(&zs, 0, sizeof zs);
-    if (inflateInit2(&zs, -15) != Z_OK) return false;
-    zs.next_in = const_cast<Bytef *>(in + b.cin);
-    zs.avail_in = (uInt)b.clen;
-    zs.next_out = out + b.uout;
-    zs.avail_out = (uInt)b.ulen;
-    const int rc = inflate(&zs, Z_FINISH);
-    const bool ok = rc == Z_STREAM_END && zs.total_out == b.ulen;
-    inflateEnd(&zs);
-    if (!ok) return false;
-    return (uint32_t)crc32(crc32(0L, Z_NULL, 0), out + b.uout, (uInt)b.ulen) == b.crc;
-}
-
-} // namespace
-
 extern "C" {
 
 int tcmi_bam_load(const char *path, int n_threads, tcmi_bam **out)
@@ -136,10 +74,10 @@ int tcmi_bam_load(const char *path, int n_threads, tcmi_bam **out)
         if (got != (size_t)sz) return tcmi_fail(nullptr, TCMI_E_IO, "short read on %s", path);
     }
     const auto t_read = now();
-    std::vector<Block> blocks;
+    std::vector<tcmi_bgzf_member> blocks;
     size_t total = 0;
-    int rc = scan_blocks(file, blocks, &total);
-    if (rc) return rc;
+    tcmi_parse_error e = tcmi_bgzf_walk(file.data(), file.size(), &total, [&blocks](const tcmi_bgzf_member &m) { blocks.push_back(m); });
+    if (e.code) return tcmi_fail(nullptr, e.code, "%s: %s at byte %zu", path, e.what, e.at);
     RawBuf<uint8_t> raw;
     raw.alloc(total + 8);
 
@@ -154,7 +92,7 @@ int tcmi_bam_load(const char *path, int n_threads, tcmi_bam **out)
             if (b0 >= blocks.size() || bad.load() >= 0) return;
             const size_t b1 = b0 + 64 < blocks.size() ? b0 + 64 : blocks.size();
             for (size_t b = b0; b < b1; ++b)
-                if (!inflate_block(file.data(), blocks[b], raw.data())) { bad.store((long long)b); return; }
+                if (!tcmi_bgzf_inflate(file.data() + blocks[b].cin, blocks[b].clen, raw.data() + blocks[b].uout, blocks[b].ulen, &blocks[b].crc)) { bad.store((long long)b); return; }
         }
     };
     if (n_threads == 1) worker();
@@ -164,40 +102,27 @@ int tcmi_bam_load(const char *path, int n_threads, tcmi_bam **out)
         for (auto &t : th) t.join();
     }
     if (bad.load() >= 0)
-        return tcmi_fail(nullptr, TCMI_E_FORMAT, "BGZF block %lld failed to inflate or its CRC32 does not match", bad.load());
+        return tcmi_fail(nullptr, TCMI_E_FORMAT, "%s: BGZF block %lld failed to inflate or its CRC32 does not match", path, bad.load());
 
     const auto t_inflate = now();
     // ---- BAM header (SAM spec §4.2) ----
     const uint8_t *p = raw.data();
     const size_t N = total;
-    size_t o = 0;
+    tcmi_stream_front all = {p, N, nullptr};                        // (everything is inflated already)
+    tcmi_bam_head head;
+    e = tcmi_bam_header_parse(&all, &head);
+    if (e.code) return tcmi_fail(nullptr, e.code, "%s: %s at byte %zu", path, e.what, e.at);
+    size_t o = head.first_record;
     auto need = [&](size_t k) { return N - o >= k; };
-    if (!need(12) || std::memcmp(p, "BAM\1", 4) != 0) return tcmi_fail(nullptr, TCMI_E_FORMAT, "%s: BAM magic missing", path);
     tcmi_bam *bam = new tcmi_bam();
     bam->file_bytes = (int64_t)file.size();
     bam->inflated_bytes = (int64_t)total;
     bam->n_blocks = (int64_t)blocks.size();
+    bam->text = std::move(head.text); bam->ref_name = std::move(head.ref_name); bam->ref_len = std::move(head.ref_len);
     auto fail = [&](const char *what) {
         delete bam;
         return tcmi_fail(nullptr, TCMI_E_FORMAT, "%s: %s at inflated byte %zu", path, what, o);
     };
-    const size_t l_text = rd32(p + 4);
-    o = 8;
-    if (!need(l_text + 4)) return fail("truncated header text");
-    bam->text.assign((const char *)p + o, l_text);
-    o += l_text;
-    const size_t n_ref = rd32(p + o);
-    o += 4;
-    for (size_t r = 0; r < n_ref; ++r) {
-        if (!need(4)) return fail("truncated reference list");
-        const size_t l_name = rd32(p + o);
-        o += 4;
-        if (!need(l_name + 4)) return fail("truncated reference name");
-        bam->ref_name.emplace_back((const char *)p + o, l_name ? l_name - 1 : 0);
-        o += l_name;
-        bam->ref_len.push_back((int64_t)rd32(p + o));
-        o += 4;
-    }
 
     // ---- records: pass 1 walks the record lengths (sequential, light) and lays out the flat arrays,
     //      pass 2 fills them with `n_threads` workers over disjoint record ranges ----

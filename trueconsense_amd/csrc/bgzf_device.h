@@ -1,4 +1,4 @@
-// bgzf_device.h — what the device BGZF decoder's translation units share (bam_device.hip: host side, CRC-32, record index;
+// bgzf_device.h — what the device BGZF decoder's translation units share (bam_device.hip: the drivers, record index;
 // bgzf_symbols.hip, bgzf_copy.hip: the decode kernels): block descriptors, status words, Huffman table entries and the table
 // builder — and the contract between the two kernels: the token format, the stamp buffer, their launch functions.
 // Wire format: SAM spec §4.1 (BGZF), RFC 1951 (DEFLATE); pysam / htslib's role for indexing.py:19,96-100.
@@ -26,6 +26,7 @@
 //
 // Bit / byte work, bound by instruction issue and the LDS pipe, not by HBM and not a contraction: no MFMA.
 #pragma once
+#include "bgzf_host.h"          // BlockDesc, the blocks' status words ST_*
 #include "tcmi_internal.h"
 
 namespace {
@@ -39,19 +40,6 @@ namespace {
 constexpr int LL_ROOT = TCMI_INFLATE_LL_ROOT, D_ROOT = TCMI_INFLATE_D_ROOT, CL_ROOT = 7;   // root-table bits; longer codes take slow_decode
 static_assert(D_ROOT >= CL_ROOT, "the code-length table borrows the distance table's LDS");
 constexpr int MAX_REC_PER_BLOCK = 65536 / 36 + 2;   // a record is at least 36 bytes (block_size + 32 fixed + 1 name byte ..)
-
-struct BlockDesc {
-    uint64_t cin;        // first byte of the deflate payload in the file
-    uint64_t uout;       // first byte of its output in the inflated stream
-    uint32_t clen;       // payload bytes
-    uint32_t ulen;       // ISIZE
-    int32_t entry;       // offset of the first record start inside this block (>= 0), or -1: no record walk (header blocks)
-    uint32_t tok_cap;    // tokens this block may produce at most (bgzf_symbols)
-    uint64_t tok;        // its first token in the token array
-};
-
-// status word of a block
-enum { ST_OK = 0, ST_BAD_STREAM = 1, ST_BAD_LENGTH = 2, ST_BAD_RECORD = 3, ST_BAD_CRC = 4 };
 
 static __constant__ uint8_t CL_ORDER[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
