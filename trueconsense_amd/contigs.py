@@ -22,10 +22,10 @@ from datetime import date
 import numpy as np
 
 from . import _ffi, _state
-from .engine import BamFile, DeviceBam, modal_tokens, read_filter_args
+from .engine import BamFile, modal_tokens, read_filter_args
 from .Events import _parse_token, candidates_from_flags
 from .io import fasta
-from .indexing import Gffindex
+from .indexing import Gffindex, device_readset
 from .io.gff import GFF3_COLUMNS, GFFDataFrame
 from .Outputs import _VCF_HEAD, _gff_line, vcf_text
 from .Sequences import consensus_from_records
@@ -124,18 +124,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     ctx.set_min_base_quality(min_baseq)
     host = None
     try:
-        rs = None
-        d = DeviceBam(path)
-        try:
-            rs = ctx.upload_bamfile(d)
-        except _ffi.TcmiError as e:
-            if e.code != _ffi.E_UNSUPPORTED:
-                raise
-            if min_baseq:
-                raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--min-baseq %d needs the device path (the host packer knows no base-quality floor), "
-                                     "which %s left: %s" % (min_baseq, path, e)) from e
-        finally:
-            d.close()
+        rs = device_readset(ctx, path)              # (the floor it refuses under is the one just set)
         if rs is None:
             host = BamFile(path, threads=threads, read_filter=read_filter)
             try:

@@ -20,7 +20,9 @@ import numpy as np
 
 from ._ffi import E_ARG as _ffi_E_ARG
 from ._ffi import E_UNSUPPORTED as _ffi_E_UNSUPPORTED
-from ._ffi import check, lib
+from ._ffi import TcmiError, check, lib
+from .engine import (DEFAULT_FLAG_FILTER, DEFAULT_MAX_DEPTH, DEFAULT_MIN_BASE_QUALITY, BamFile, Context, DeviceBam, ReadSet, _grab,
+                     _token_buffer, modal_tokens)
 
 
 def shard_items(n_items, rank, world):
@@ -105,7 +107,6 @@ def tally_split_bam(reads, L, rank, world, device=0, group=None, tally_fn=None):
         part = torch.from_numpy(np.ascontiguousarray(np.asarray(tally_fn(shard, L)).T.astype(np.int32)))   # [7][L]
         allreduce_counts(part, group)
         return np.ascontiguousarray(part.numpy().T)
-    from .engine import Context
     ld = (L + 255) // 256 * 256
     torch.cuda.set_device(device)
     t = torch.zeros((7, ld), dtype=torch.int32, device="cuda")
@@ -150,21 +151,16 @@ def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to
     read_filter = (min_mapq, require_flags, exclude_flags), min_baseq (Context.set_min_base_quality; 0 sets no floor): set on the
     rank's context, every rank the same ones; None leaves what the context has."""
     import torch
-    from .engine import Context, DeviceBam
     L = int(L)
     ld = (L + 255) // 256 * 256
     torch.cuda.set_device(device)
     own = ctx is None
     if own:
         ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)         # tally and collective on torch's stream
-    if read_filter is not None:
-        ctx.set_read_filter(*read_filter)
-    if min_baseq is not None:
-        ctx.set_min_base_quality(min_baseq)
+    ctx.apply(read_filter, min_baseq)
     d = DeviceBam(path)
     try:
         import torch.distributed as dist
-        from ._ffi import TcmiError
         first, count = block_range(d.n_blocks, rank, world)
         # A range can be refused on ONE rank only (a record chain that does not close from a false start, a record longer than a block
         # at the range's end, a read the packer does not take): the ranks agree BEFORE anybody enters the collective — else the others
@@ -208,7 +204,6 @@ def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to
 # --------------------------------------------------------------------------------------------- configs[4], all the way to the consensus
 def _entries_of_readset(ctx, rs, positions):
     """This rank's entries of the candidate columns (tcmi_readset_ins_entries) -> (bytes, ent_off list, long-insertion text bytes)."""
-    from .engine import DEFAULT_FLAG_FILTER
     pos = np.ascontiguousarray(positions, np.int64)
     n = len(pos)
     off = np.zeros(n + 1, np.int64)
@@ -229,7 +224,6 @@ def _entries_of_readset(ctx, rs, positions):
 def _vote(positions, pieces):
     """Rank 0: per column the ranks' pieces concatenated in rank order (= file order), voted on as tcmi_readset_modal_tokens votes
     (tcmi_modal_from_entries: pysam's default filters, Events.py:66).  -> ({pos: token or None}, status flags)."""
-    from .engine import DEFAULT_MAX_DEPTH, DEFAULT_MIN_BASE_QUALITY
     n = len(positions)
     text = b"".join(p[2] for p in pieces)
     base = np.cumsum([0] + [len(p[2]) for p in pieces])
@@ -246,19 +240,11 @@ def _vote(positions, pieces):
         off.append(off[-1] + sum(p[1][k + 1] - p[1][k] for p in pieces))
     allents = np.ascontiguousarray(np.concatenate(cols)) if cols and sum(len(c) for c in cols) else np.zeros(48, np.uint8)
     off = np.ascontiguousarray(off, np.int64)
-    cap = 1 << 16
-    while True:
-        buf = C.create_string_buffer(cap)
-        toff, cnt, st = np.zeros(n + 1, np.int64), np.zeros(n, np.int64), C.c_int32(0)
-        tb = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
-        rc = lib().tcmi_modal_from_entries(n, allents.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), DEFAULT_MIN_BASE_QUALITY, DEFAULT_MAX_DEPTH, 1,
-                                           tb.ctypes.data_as(C.c_void_p), len(text), C.cast(buf, C.c_void_p), cap, toff.ctypes.data_as(C.c_void_p),
-                                           cnt.ctypes.data_as(C.c_void_p), C.byref(st))
-        if rc != 0 and b"token buffer too small" in (lib().tcmi_last_error(None) or b"") and cap < (1 << 30):
-            cap *= 16
-            continue
-        check(rc)
-        break
+    toff, cnt, st = np.zeros(n + 1, np.int64), np.zeros(n, np.int64), C.c_int32(0)
+    tb = np.frombuffer(text, np.uint8) if text else np.zeros(1, np.uint8)
+    buf = _token_buffer(lambda buf, cap: lib().tcmi_modal_from_entries(
+        n, allents.ctypes.data_as(C.c_void_p), off.ctypes.data_as(C.c_void_p), DEFAULT_MIN_BASE_QUALITY, DEFAULT_MAX_DEPTH, 1, tb.ctypes.data_as(C.c_void_p),
+        len(text), C.cast(buf, C.c_void_p), cap, toff.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p), C.byref(st)))
     return {int(positions[k]): (buf.raw[toff[k]:toff[k + 1]].decode("ascii") if cnt[k] else None) for k in range(n)}, st.value
 
 
@@ -335,6 +321,49 @@ def split_reduce_hook_close(comm):
         _ffi.rccl_lib().tcmi_rccl_comm_destroy(comm)
 
 
+def split_words(L, world):
+    """-> (ld, n_words): the leading dimension of the [7][ld] count planes and the int32 words of tcmi_split_step's buffer — the planes
+    and, behind them, the range table and the failure word (TCMI_SPLIT_TAIL_WORDS(world))."""
+    ld = (int(L) + 255) // 256 * 256
+    return ld, 7 * ld + 6 * int(world) + 1
+
+
+def _split_step(ctx, d, rank, world, L, ld, t, mincov, include_ambig, fn, user):
+    """Rank `rank`'s tcmi_split_step over its block range of DeviceBam d, into the int32 tensor t (split_words), the exchange through
+    fn(user, ...).  -> (rc, the rank's ReadSet, the root's (plain, alt, flags)): (rc, None, None) when the step failed — the caller
+    words the failure (tcmi_last_error) —, no record planes on a rank other than 0 (the call kernel runs on the root)."""
+    first, count = block_range(d.n_blocks, rank, world)
+    h, p_, a_, f_ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+    rc = lib().tcmi_split_step(ctx.handle, d.handle, first, count, L, ld, C.c_void_p(t.data_ptr()), int(mincov), int(bool(include_ambig)), fn, user,
+                               int(rank), int(world), C.byref(h), C.byref(p_), C.byref(a_), C.byref(f_))
+    if rc:
+        return rc, None, None
+    return rc, ReadSet(ctx, h, None), tuple(_grab(vp, np.uint8, L) for vp in (p_, a_, f_)) if rank == 0 else None
+
+
+def _tokens_for(path, cand, pieces, host_sweep, read_filter):
+    """The candidate columns' modal tokens -> {pos: token or None}: the vote on the ranks' pieces; a sweep of the whole file on the
+    host (tcmi_bam_load + tcmi_modal_tokens) when the caller says so (a rank could not collect its entries) or the vote meets a pair
+    of mates that only such a sweep resolves (status bit 2)."""
+    toks, st = ({}, 2) if host_sweep else _vote(cand, pieces)
+    if st & 2:
+        bam = BamFile(path, read_filter=read_filter)
+        try:
+            toks = {p: tk for p, (tk, _) in modal_tokens(bam, cand).items()}
+        finally:
+            bam.close()
+    return toks
+
+
+def _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks):
+    """The root's walk (Sequences.py:168-322) over the call records, inserts from the voted tokens -> FASTA text."""
+    from .Events import inserts_from_flags
+    from .Sequences import consensus_from_records
+    _, inserts = inserts_from_flags(flags, _Tokens(toks))
+    cons, _ = consensus_from_records(plain, alt, flags, {i: dict(r) for i, r in enumerate(gff_rows)}, inserts, True)
+    return ">%s mincov=%d\n%s\n" % (name, int(mincov), cons)
+
+
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
                             step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
                             min_baseq=None):
@@ -368,12 +397,9 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     import time
     import torch
     import torch.distributed as dist
-    from ._ffi import TcmiError
-    from .Events import inserts_from_flags
-    from .Sequences import consensus_from_records
     multi = dist.is_initialized() and dist.get_world_size(group) > 1
     L = int(ref_len)
-    ld = (L + 255) // 256 * 256
+    ld, n_words = split_words(L, world)
     root = rank == 0
     plain = alt = flags = counts_root = None
     own_ctx, own_d = ctx is None, dbam is None
@@ -382,21 +408,16 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     t0 = time.perf_counter()
     try:
         if step_fn is None:
-            from .engine import Context, DeviceBam, ReadSet
             torch.cuda.set_device(device)
             try:
                 if ctx is None:
                     ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)
                 if d is None:
                     d = DeviceBam(path)
-                if read_filter is not None:
-                    ctx.set_read_filter(*read_filter)
-                if min_baseq is not None:
-                    ctx.set_min_base_quality(min_baseq)
+                ctx.apply(read_filter, min_baseq)
             except (TcmiError, OSError) as e:                        # this rank cannot even start: it must still meet the others in the reduce
                 err = (getattr(e, "code", _ffi_E_ARG), str(e))
-            n_tail = 6 * int(world) + 1                              # TCMI_SPLIT_TAIL_WORDS(world)
-            t = torch.zeros(7 * ld + n_tail, dtype=torch.int32, device="cuda")
+            t = torch.zeros(n_words, dtype=torch.int32, device="cuda")
             if err is not None:
                 t[-1] = 1
                 if rccl_user is not None:                            # (the others are in ncclReduce on that communicator)
@@ -409,8 +430,6 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                 else:
                     reduce_counts(t, 0, group)
             else:
-                first, count = block_range(d.n_blocks, rank, world)
-
                 @C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
                 def hook(user, ptr, n, stream):                      # (the tensor IS the buffer at `ptr`; torch's collective runs on the context's stream)
                     try:
@@ -423,21 +442,13 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                     fn, user = C.cast(_ffi.rccl_lib().tcmi_rccl_reduce, C.c_void_p), C.cast(C.pointer(rccl_user), C.c_void_p)
                 else:
                     fn, user = hook, None
-                h, p_, a_, f_ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
-                rc = lib().tcmi_split_step(ctx.handle, d.handle, first, count, L, ld, C.c_void_p(t.data_ptr()), int(mincov), int(bool(include_ambig)), fn, user,
-                                           int(rank), int(world), C.byref(h), C.byref(p_), C.byref(a_), C.byref(f_))
+                rc, rs, planes = _split_step(ctx, d, rank, world, L, ld, t, mincov, include_ambig, fn, user)
                 if rc:
                     err = (rc, (lib().tcmi_last_error(ctx.handle) or b"").decode("utf-8", "replace"))
-                else:
-                    rs = ReadSet(ctx, h, None)
-                    if root:
-                        def grab(vp):
-                            out = np.empty(L, np.uint8)
-                            C.memmove(out.ctypes.data, vp, L)
-                            return out
-                        plain, alt, flags = grab(p_), grab(a_), grab(f_)
-                        if return_parts:
-                            counts_root = np.ascontiguousarray(t[:7 * ld].view(7, ld)[:, :L].T.cpu().numpy())
+                elif root:
+                    plain, alt, flags = planes
+                    if return_parts:
+                        counts_root = np.ascontiguousarray(t[:7 * ld].view(7, ld)[:, :L].T.cpu().numpy())
         else:
             d_blocks = step_fn("n_blocks")
             first, count = block_range(d_blocks, rank, world)
@@ -480,29 +491,17 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
             if perr is not None:
                 if perr[0] != _ffi_E_UNSUPPORTED:
                     raise TcmiError(perr[0], "consensus_split_bamfile: insert entries: %s" % perr[1])
-                host_sweep = True                                    # rank 0 sweeps the file on the host, as it does for st & 2 below
+                host_sweep = True                                    # rank 0 sweeps the file on the host, as it does for the vote's status bit 2
             elif multi:
                 pieces = [None] * dist.get_world_size(group) if root else None
                 dist.gather_object(piece, pieces, dst=0, group=group)
         toks = {}
         if root:
             if cand:
-                st = 2
-                if not host_sweep:
-                    toks, st = _vote(cand, pieces)
-                if st & 2:                                          # a pair of mates that only a sweep over the whole file resolves
-                    from .engine import BamFile, modal_tokens
-                    bam = BamFile(path, read_filter=read_filter)
-                    try:
-                        toks = {p: tk for p, (tk, _) in modal_tokens(bam, cand).items()}
-                    finally:
-                        bam.close()
+                toks = _tokens_for(path, cand, pieces, host_sweep, read_filter)
             if timings is not None:
                 timings["entries"] = time.perf_counter() - t1
-            _, inserts = inserts_from_flags(flags, _Tokens(toks))
-            gff = {i: dict(r) for i, r in enumerate(gff_rows)}
-            cons, _ = consensus_from_records(plain, alt, flags, gff, inserts, True)
-            text = ">%s mincov=%d\n%s\n" % (name, int(mincov), cons)
+            text = _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks)
     finally:
         t2 = time.perf_counter()
         if rs is not None:
@@ -532,23 +531,15 @@ def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=Tr
     (Events.py:47-82).  -> FASTA text (return_parts: + counts int32 [L,7] + {column: token})."""
     import time
     import torch
-    from ._ffi import TcmiError
-    from .engine import Context, DeviceBam, ReadSet
-    from .Events import inserts_from_flags
-    from .Sequences import consensus_from_records
     L = int(ref_len)
-    ld = (L + 255) // 256 * 256
     world = int(world)
+    ld, n_words = split_words(L, world)
     torch.cuda.set_device(device)
     ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)
     if split_sub is not None:                                        # (tcmi_split_step's sub-ranges per rank: 0 = auto, 1 = never)
         ctx.set_option("split_sub", int(split_sub))
-    if read_filter is not None:                                      # (every rank the same filter)
-        ctx.set_read_filter(*read_filter)
-    if min_baseq is not None:                                        # (... and the same base-quality floor)
-        ctx.set_min_base_quality(min_baseq)
+    ctx.apply(read_filter, min_baseq)                                # (every rank the same filter and base-quality floor)
     d = DeviceBam(path)
-    n_words = 7 * ld + 6 * world + 1                                 # TCMI_SPLIT_TAIL_WORDS(world)
     acc = torch.zeros(n_words, dtype=torch.int32, device="cuda")
     t = torch.zeros(n_words, dtype=torch.int32, device="cuda")
     state = {"root": False}
@@ -567,22 +558,17 @@ def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=Tr
     plain = alt = flags = None
     try:
         for rank in range(world - 1, -1, -1):
-            first, count = block_range(d.n_blocks, rank, world)
             state["root"] = rank == 0
-            h, p_, a_, f_ = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            rc = lib().tcmi_split_step(ctx.handle, d.handle, first, count, L, ld, C.c_void_p(t.data_ptr()), int(mincov), int(bool(include_ambig)), hook, None,
-                                       rank, world, C.byref(h), C.byref(p_), C.byref(a_), C.byref(f_))
+            rc, sets[rank], planes = _split_step(ctx, d, rank, world, L, ld, t, mincov, include_ambig, hook, None)
             torch.cuda.synchronize()
             secs[rank] = time.perf_counter() - t0
             if rc:
                 raise TcmiError(rc, "split_ranks_in_turn: rank %d of %d: %s" % (rank, world, (lib().tcmi_last_error(ctx.handle) or b"").decode("utf-8", "replace")))
-            sets[rank] = ReadSet(ctx, h, None)
             if rank == 0:
-                grab = lambda vp: np.frombuffer(C.string_at(vp, L), np.uint8).copy()
-                plain, alt, flags = grab(p_), grab(a_), grab(f_)
-            elif rank > 0:                                           # (a context holds ONE resident stream: this rank's entries are collected below, from a decode of their own)
+                plain, alt, flags = planes
+            else:                                                    # (a context holds ONE resident stream: this rank's entries are collected below, from a decode of their own)
                 sets[rank].free()
                 sets[rank] = None
         counts = np.ascontiguousarray(t[:7 * ld].view(7, ld)[:, :L].T.cpu().numpy()) if return_parts else None
@@ -599,17 +585,8 @@ def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=Tr
                 finally:
                     rs.free()
                     sets[rank] = None
-            toks, st = _vote(cand, pieces)
-            if st & 2:
-                from .engine import BamFile, modal_tokens
-                bam = BamFile(path, read_filter=read_filter)
-                try:
-                    toks = {p: tk for p, (tk, _) in modal_tokens(bam, cand).items()}
-                finally:
-                    bam.close()
-        _, inserts = inserts_from_flags(flags, _Tokens(toks))
-        cons, _ = consensus_from_records(plain, alt, flags, {i: dict(r) for i, r in enumerate(gff_rows)}, inserts, True)
-        text = ">%s mincov=%d\n%s\n" % (name, int(mincov), cons)
+            toks = _tokens_for(path, cand, pieces, False, read_filter)
+        text = _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks)
         if timings is not None:
             timings.update(rank_seconds=secs, blocks_per_rank=[block_range(d.n_blocks, r, world)[1] for r in range(world)],
                            n_blocks=d.n_blocks, file_bytes=d.file_bytes, inflated_bytes=d.inflated_bytes,

@@ -25,6 +25,47 @@ def read_filter_args(read_filter):
     return int(q), int(f), int(F)
 
 
+def _grab(vp, dtype, n):
+    """n items of dtype at address vp (memory the library owns) -> a fresh numpy array."""
+    out = np.empty(n, dtype)
+    C.memmove(out.ctypes.data, vp, out.nbytes)
+    return out
+
+
+def _reads_struct(reads):
+    """BamFile or dict of flat arrays (tcmi_reads layout) -> (Reads struct, what keeps its arrays alive)."""
+    return reads.as_struct() if isinstance(reads, BamFile) else _ffi.as_reads(reads)
+
+
+def _borrowed_context(handle, device):
+    """A Context over a tcmi_ctx that a pipeline or file runner owns: close() leaves it alone."""
+    c = Context.__new__(Context)
+    c.handle, c.device = C.c_void_p(handle), device
+    c.close = lambda: None
+    return c
+
+
+def _token_buffer(attempt, ctx=None):
+    """The token buffer of a modal-token call, grown until the tokens fit: attempt(buf, cap) -> rc makes the call; while it answers
+    "token buffer too small" the buffer is tried 16 times as large, up to 1 GiB (csrc/pipeline.cpp does the same for the same calls).
+    -> the filled buffer.  ctx: the context handle any other failure's message is read from (None: the thread's last error)."""
+    cap = 1 << 16
+    while True:
+        buf = C.create_string_buffer(cap)
+        rc = attempt(buf, cap)
+        # (the vote has no context: its refusal is the thread's last error, whichever entry point made the call)
+        if rc == _ffi.E_ARG and b"token buffer too small" in (lib().tcmi_last_error(None) or b"") and cap < (1 << 30):
+            cap *= 16
+            continue
+        check(rc, ctx)
+        return buf
+
+
+def _token_dict(positions, buf, off, cnt):
+    """What a modal-token call filled -> {position: (token or None, n_tokens)}."""
+    return {int(p): (buf.raw[off[k]:off[k + 1]].decode("ascii") if cnt[k] else None, int(cnt[k])) for k, p in enumerate(positions)}
+
+
 class ReadSet:
     def __init__(self, ctx, handle, keep):
         self.ctx, self.handle, self._keep = ctx, handle, keep
@@ -142,6 +183,13 @@ class Context:
         check(lib().tcmi_ctx_set_min_base_quality(self.handle, int(q)), self.handle)
         self.min_base_quality = int(q)
 
+    def apply(self, read_filter=None, min_baseq=None):
+        """A job's read_filter = (min_mapq, require_flags, exclude_flags) and min_baseq onto this context; None leaves what it has."""
+        if read_filter is not None:
+            self.set_read_filter(*read_filter_args(read_filter))
+        if min_baseq is not None:
+            self.set_min_base_quality(min_baseq)
+
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
         slot_len[t] positions.  No arguments: back to reference 0 only."""
@@ -155,7 +203,7 @@ class Context:
     # ---- stage A
     def upload(self, reads):
         """reads: dict of flat arrays (tcmi_reads layout) or BamFile -> ReadSet in HBM."""
-        r, keep = reads.as_struct() if isinstance(reads, BamFile) else _ffi.as_reads(reads)
+        r, keep = _reads_struct(reads)
         h = C.c_void_p()
         check(lib().tcmi_readset_upload(self.handle, C.byref(r), C.byref(h)), self.handle)
         return ReadSet(self, h, keep)
@@ -164,7 +212,7 @@ class Context:
         """Several BAMs in one read set: BAM b's positions are shifted by b * stride (multiple of 256)."""
         structs, keep = [], []
         for r in reads_list:
-            st, k = r.as_struct() if isinstance(r, BamFile) else _ffi.as_reads(r)
+            st, k = _reads_struct(r)
             structs.append(st)
             keep.append(k)
         arr = (C.POINTER(_ffi.Reads) * len(structs))(*[C.pointer(s) for s in structs])
@@ -190,15 +238,10 @@ class Context:
         check(lib().tcmi_bamfile_step(self.handle, dbam.handle, int(ref_len), int(mincov), int(bool(include_ambig)), C.byref(h), C.byref(L),
                                       C.byref(p), C.byref(a), C.byref(f), C.byref(c) if want_counts else None, C.byref(ld)), self.handle)
         n = L.value
-
-        def grab(vp, dt, k):
-            out = np.empty(k, dt)
-            C.memmove(out.ctypes.data, vp, out.nbytes)
-            return out
-        plain, alt, flags = grab(p, np.uint8, n), grab(a, np.uint8, n), grab(f, np.uint8, n)
+        plain, alt, flags = _grab(p, np.uint8, n), _grab(a, np.uint8, n), _grab(f, np.uint8, n)
         counts = None
         if want_counts:
-            counts = np.ascontiguousarray(grab(c, np.int32, 7 * ld.value).reshape(7, ld.value)[:, :n].T)
+            counts = np.ascontiguousarray(_grab(c, np.int32, 7 * ld.value).reshape(7, ld.value)[:, :n].T)
         return ReadSet(self, h, None), plain, alt, flags, counts
 
     def readset_modal_tokens(self, readset, positions, min_base_quality=13, flag_filter=0x4 | 0x100 | 0x200 | 0x400,
@@ -209,19 +252,17 @@ class Context:
         n = len(positions)
         if n == 0:
             return {}
-        cap = 1 << 16
-        buf = C.create_string_buffer(cap)
         off, cnt, st = np.zeros(n + 1, np.int64), np.zeros(n, np.int64), C.c_int32(0)
-        check(lib().tcmi_readset_modal_tokens(self.handle, readset.handle, n, ptr(positions), int(min_base_quality), int(flag_filter),
-                                              int(bool(ignore_orphans)), int(max_depth), int(bool(ignore_overlaps)), C.cast(buf, C.c_void_p), cap,
-                                              ptr(off), ptr(cnt), C.byref(st)), self.handle)
+        buf = _token_buffer(lambda buf, cap: lib().tcmi_readset_modal_tokens(
+            self.handle, readset.handle, n, ptr(positions), int(min_base_quality), int(flag_filter), int(bool(ignore_orphans)), int(max_depth),
+            int(bool(ignore_overlaps)), C.cast(buf, C.c_void_p), cap, ptr(off), ptr(cnt), C.byref(st)), self.handle)
         if st.value & 2:
             raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "overlapping mates with a deletion on an insert-candidate column")
-        return {int(positions[k]): (buf.raw[off[k]:off[k + 1]].decode("ascii") if cnt[k] else None, int(cnt[k])) for k in range(n)}
+        return _token_dict(positions, buf, off, cnt)
 
     def tally(self, reads, L=None, ref_len=0):
         """reads -> int32 [L,7] (coverage,A,T,C,G,X,I); L defaults to max(ref_len, read extent)."""
-        r, keep = reads.as_struct() if isinstance(reads, BamFile) else _ffi.as_reads(reads)
+        r, keep = _reads_struct(reads)
         if L is None:
             L = reads_extent(reads, ref_len)
         counts = np.zeros((int(L), 7), np.int32)
@@ -273,22 +314,17 @@ class Context:
         ld = C.c_int64(0)
         check(lib().tcmi_step_end(self.handle, C.byref(p), C.byref(a), C.byref(f), C.byref(c), C.byref(ld)),
               self.handle)
-
-        def grab(vp, dt, n):
-            out = np.empty(n, dt)
-            C.memmove(out.ctypes.data, vp, out.nbytes)
-            return out
-        plain, alt, flags = grab(p, np.uint8, L), grab(a, np.uint8, L), grab(f, np.uint8, L)
+        plain, alt, flags = _grab(p, np.uint8, L), _grab(a, np.uint8, L), _grab(f, np.uint8, L)
         counts = None
         if want_counts:
-            planes = grab(c, np.int32, 7 * ld.value).reshape(7, ld.value)
+            planes = _grab(c, np.int32, 7 * ld.value).reshape(7, ld.value)
             counts = np.ascontiguousarray(planes[:, :L].T)
         return plain, alt, flags, counts
 
 
 # --------------------------------------------------------------------------- host-only entry points
 def reads_extent(reads, ref_len=0):
-    r, keep = reads.as_struct() if isinstance(reads, BamFile) else _ffi.as_reads(reads)
+    r, keep = _reads_struct(reads)
     out = C.c_int64(0)
     check(lib().tcmi_reads_extent(C.byref(r), int(ref_len), C.byref(out)))
     del keep
@@ -297,6 +333,15 @@ def reads_extent(reads, ref_len=0):
 
 class WalkKeyError(KeyError):
     """The reference raises KeyError here (Sequences.py:47): a deletion walk ran past the last position."""
+
+
+def _check_walk(rc, err, key_error=WalkKeyError):
+    """A walk's return code -> what the reference raises there (key_error(err), ZeroDivisionError), else check()."""
+    if rc == _ffi.E_KEYERROR:
+        raise key_error(err)
+    if rc == _ffi.E_ZERODIV:
+        raise ZeroDivisionError("division by zero")
+    check(rc)
 
 
 def consensus_walk(plain, alt, flags, orf_start, orf_end, orf_is_plus, ins_pos, ins_shift, ins_seqs,
@@ -320,11 +365,7 @@ def consensus_walk(plain, alt, flags, orf_start, orf_end, orf_is_plus, ins_pos, 
     rc = lib().tcmi_consensus_walk(ptr(plain), ptr(alt), ptr(flags), L, len(os_), ptr(os_), ptr(oe), ptr(op),
                                    len(ip), ptr(ip), ptr(ish), blob, ptr(off), int(bool(include_ins)),
                                    C.cast(out, C.c_void_p), cap, C.byref(n_out), ptr(ns), ptr(ne), C.byref(err))
-    if rc == _ffi.E_KEYERROR:
-        raise WalkKeyError(err.value)
-    if rc == _ffi.E_ZERODIV:
-        raise ZeroDivisionError("division by zero")
-    check(rc)
+    _check_walk(rc, err.value)
     return out.raw[:n_out.value].decode("ascii"), ns, ne
 
 
@@ -336,15 +377,10 @@ class Pipeline:
         h = C.c_void_p()
         check(lib().tcmi_pipeline_create(int(device), int(slots), int(walkers), C.byref(h)))
         self.handle, self.slots = h, int(slots)
-        self.ctx = Context.__new__(Context)            # slot 0's context, owned by the pipeline
-        self.ctx.handle, self.ctx.device = C.c_void_p(lib().tcmi_pipeline_ctx(h, 0)), device
-        self.ctx.close = lambda: None
+        self.ctx = _borrowed_context(lib().tcmi_pipeline_ctx(h, 0), device)        # slot 0's context, owned by the pipeline
 
     def slot_context(self, k):
-        c = Context.__new__(Context)
-        c.handle, c.device = C.c_void_p(lib().tcmi_pipeline_ctx(self.handle, k)), self.ctx.device
-        c.close = lambda: None
-        return c
+        return _borrowed_context(lib().tcmi_pipeline_ctx(self.handle, k), self.ctx.device)
 
     def set_orfs(self, start, end, is_plus):
         s_, e_ = np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
@@ -370,7 +406,7 @@ class Pipeline:
                     ptrs.append(None)
                     continue
                 if id(r) not in by_id:
-                    st, k = r.as_struct() if isinstance(r, BamFile) else _ffi.as_reads(r)
+                    st, k = _reads_struct(r)
                     by_id[id(r)] = (st, k, C.pointer(st))
                 ptrs.append(by_id[id(r)][2])
             hr = (C.POINTER(_ffi.Reads) * n)(*ptrs)
@@ -425,11 +461,7 @@ class Walker:
         rc = self._fn(ptr(plain), ptr(alt), ptr(flags), L, n, ptr(self.os), ptr(self.oe), ptr(self.op),
                       0, None, None, b"", ptr(self.off), self.include_ins, C.cast(out, C.c_void_p), L + 1,
                       C.byref(n_out), ptr(ns), ptr(ne), C.byref(err))
-        if rc == _ffi.E_KEYERROR:
-            raise WalkKeyError(err.value)
-        if rc == _ffi.E_ZERODIV:
-            raise ZeroDivisionError("division by zero")
-        check(rc)
+        _check_walk(rc, err.value)
         return out.raw[:n_out.value], ns, ne
 
 
@@ -449,34 +481,23 @@ def modal_tokens(reads, positions, min_base_quality=DEFAULT_MIN_BASE_QUALITY, fl
     n = len(positions)
     if n == 0:
         return {}
-    r, keep = reads.as_struct() if isinstance(reads, BamFile) else _ffi.as_reads(reads)
-    cap = 1 << 16
-    while True:
-        buf = C.create_string_buffer(cap)
-        off = np.zeros(n + 1, np.int64)
-        cnt = np.zeros(n, np.int64)
-        deep = C.c_int32(0)
+    r, keep = _reads_struct(reads)
+    off, cnt, deep = np.zeros(n + 1, np.int64), np.zeros(n, np.int64), C.c_int32(0)
+    if layout is not None:
+        sh, sl = (np.ascontiguousarray(x, np.int64) for x in layout)
+
+    def attempt(buf, cap):
         tail = (int(min_base_quality), int(flag_filter), int(bool(ignore_orphans)), int(max_depth), int(bool(ignore_overlaps)),
                 C.cast(buf, C.c_void_p), cap, ptr(off), ptr(cnt), C.byref(deep))
         if layout is None:
-            rc = lib().tcmi_modal_tokens(C.byref(r), n, ptr(positions), *tail)
-        else:
-            sh, sl = (np.ascontiguousarray(x, np.int64) for x in layout)
-            rc = lib().tcmi_modal_tokens_layout(C.byref(r), len(sh), ptr(sh), ptr(sl), n, ptr(positions), *tail)
-        if rc == _ffi.E_ARG and b"token buffer too small" in (lib().tcmi_last_error(None) or b"") and cap < (1 << 30):
-            cap *= 16
-            continue
-        check(rc)
-        break
+            return lib().tcmi_modal_tokens(C.byref(r), n, ptr(positions), *tail)
+        return lib().tcmi_modal_tokens_layout(C.byref(r), len(sh), ptr(sh), ptr(sl), n, ptr(positions), *tail)
+    buf = _token_buffer(attempt)
     del keep
     if deep.value & 2:
         raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "overlapping mates with a deletion on an insert-candidate column: pysam's overlap "
                                                   "quality tweak there is not modelled")
-    out = {}
-    for k in range(n):
-        tok = buf.raw[off[k]:off[k + 1]].decode("ascii") if cnt[k] else None
-        out[int(positions[k])] = (tok, int(cnt[k]))
-    return out
+    return _token_dict(positions, buf, off, cnt)
 
 
 def _header_refs(fn, h, n_ref):
@@ -652,30 +673,29 @@ class FileRunner:
         self.seconds = {"decode": 0.0, "upload": 0.0, "step": 0.0, "walk": 0.0}
         self.decoded_on = {"device": 0, "host": 0}
         self._device = device
-        if read_filter is not None:                 # (every context the same: the runner's host-reader fallbacks take it from them)
-            for c in self.contexts:
-                c.set_read_filter(*read_filter_args(read_filter))
-        if min_baseq:                               # (a file that leaves the device path is then refused, never tallied without the floor)
-            for c in self.contexts:
-                c.set_min_base_quality(min_baseq)
+        # every context the same: the runner's host-reader fallbacks take the filter from them, and under a floor a file that leaves
+        # the device path is refused, never tallied without it
+        for c in self.contexts:
+            c.apply(read_filter, min_baseq or None)
 
     @property
     def contexts(self):
-        out = []
-        for k in range(self.n_ctx):
-            c = Context.__new__(Context)
-            c.handle, c.device = C.c_void_p(lib().tcmi_filerunner_ctx(self.handle, k)), self._device
-            c.close = lambda: None
-            out.append(c)
-        return out
+        return [_borrowed_context(lib().tcmi_filerunner_ctx(self.handle, k), self._device) for k in range(self.n_ctx)]
 
-    def run(self, paths, names=None, ref_len=0, max_inserted=4096):
-        """-> list of FASTA texts, in input order."""
-        n = len(paths)
+    def _account(self, status, sec, on):
+        """What a run of the native runner reported: every sample's code, the stages' busy seconds, where the files were decoded."""
+        self.last_status = status
+        for k, v in zip(("decode", "upload", "step", "walk"), sec):
+            self.seconds[k] += v
+        self.decoded_on["device"] += on[0]
+        self.decoded_on["host"] += on[1]
+
+    def _text_run(self, fn, c_items, names, ref_len, max_inserted, *mode):
+        """run / run_resident: fn(handle, n, items, names, ref_len, mincov, include_ambig, *mode, out ...) -> list of FASTA texts."""
+        n = len(c_items)
         names = names or ["S%d" % i for i in range(n)]
         if n == 0:
             return []
-        c_paths = (C.c_char_p * n)(*[str(p).encode() for p in paths])
         c_names = (C.c_char_p * n)(*[str(x).encode() for x in names])
         stride = int(ref_len) + int(max_inserted) + max(len(x) for x in names) + 64
         # (positions beyond ref_len that the reads reach lengthen the consensus: the runner reports a too small stride)
@@ -684,40 +704,21 @@ class FileRunner:
         status = np.zeros(n, np.int32)
         sec = (C.c_double * 4)()
         on = (C.c_int64 * 2)()
-        rc = lib().tcmi_filerunner_run(self.handle, n, c_paths, c_names, int(ref_len), self.mincov, int(self.amb), int(bool(self.device_decode)),
-                                       ptr(out), stride, ptr(lens), ptr(status), sec, on)
-        self.last_status = status
-        for k, v in zip(("decode", "upload", "step", "walk"), sec):
-            self.seconds[k] += v
-        self.decoded_on["device"] += on[0]
-        self.decoded_on["host"] += on[1]
+        rc = fn(self.handle, n, c_items, c_names, int(ref_len), self.mincov, int(self.amb), *mode, ptr(out), stride, ptr(lens), ptr(status), sec, on)
+        self._account(status, sec, on)
         check(rc)
         return [out[i * stride:i * stride + int(lens[i])].tobytes().decode("ascii") for i in range(n)]
+
+    def run(self, paths, names=None, ref_len=0, max_inserted=4096):
+        """-> list of FASTA texts, in input order."""
+        c_paths = (C.c_char_p * len(paths))(*[str(p).encode() for p in paths])
+        return self._text_run(lib().tcmi_filerunner_run, c_paths, names, ref_len, max_inserted, int(bool(self.device_decode)))
 
     def run_resident(self, dbams, names=None, ref_len=0, max_inserted=4096):
         """... of DeviceBam objects read before (and, after DeviceBam.to_device, resident in HBM): no read stage, no PCIe copy of
         the file inside the run.  -> list of FASTA texts, in input order."""
-        n = len(dbams)
-        names = names or ["S%d" % i for i in range(n)]
-        if n == 0:
-            return []
-        c_files = (C.c_void_p * n)(*[d.handle for d in dbams])
-        c_names = (C.c_char_p * n)(*[str(x).encode() for x in names])
-        stride = int(ref_len) + int(max_inserted) + max(len(x) for x in names) + 64
-        out = np.empty(n * stride, np.uint8)
-        lens = np.zeros(n, np.int64)
-        status = np.zeros(n, np.int32)
-        sec = (C.c_double * 4)()
-        on = (C.c_int64 * 2)()
-        rc = lib().tcmi_filerunner_run_resident(self.handle, n, c_files, c_names, int(ref_len), self.mincov, int(self.amb), ptr(out), stride,
-                                                ptr(lens), ptr(status), sec, on)
-        self.last_status = status
-        for k, v in zip(("decode", "upload", "step", "walk"), sec):
-            self.seconds[k] += v
-        self.decoded_on["device"] += on[0]
-        self.decoded_on["host"] += on[1]
-        check(rc)
-        return [out[i * stride:i * stride + int(lens[i])].tobytes().decode("ascii") for i in range(n)]
+        c_files = (C.c_void_p * len(dbams))(*[d.handle for d in dbams])
+        return self._text_run(lib().tcmi_filerunner_run_resident, c_files, names, ref_len, max_inserted)
 
     def set_outputs(self, ref_id, ref_seq, vcf_head, gff_head, gff_row_columns):
         """What the native VCF / GFF writers need besides a sample's walk (run_files): the reference's first record, the complete
@@ -743,16 +744,8 @@ class FileRunner:
         on = (C.c_int64 * 2)()
         rc = lib().tcmi_filerunner_run_files(self.handle, n, arr(paths), arr(names), arr(fasta), arr(vcf), arr(gff), arr(doc), int(ref_len),
                                              self.mincov, int(self.amb), int(bool(self.device_decode)), ptr(status), sec, on)
-        self.last_status = status
-        for k, v in zip(("decode", "upload", "step", "walk"), sec):
-            self.seconds[k] += v
-        self.decoded_on["device"] += on[0]
-        self.decoded_on["host"] += on[1]
-        if rc == _ffi.E_KEYERROR:
-            raise KeyError((lib().tcmi_last_error(None) or b"").decode("utf-8", "replace"))
-        if rc == _ffi.E_ZERODIV:
-            raise ZeroDivisionError("division by zero")
-        check(rc)
+        self._account(status, sec, on)
+        _check_walk(rc, (lib().tcmi_last_error(None) or b"").decode("utf-8", "replace"), KeyError)
 
     def close(self):
         if self.handle:

@@ -36,6 +36,25 @@ def Override_index_positions(index, override_data):
     return index
 
 
+def device_readset(ctx, path, blocks=None):
+    """The device path, or why not: the file at `path` (blocks = (first, count): that range of its BGZF blocks) decoded and packed by
+    ctx's device decoder -> ReadSet; None when the decoder declines the file (E_UNSUPPORTED) and the host reader may take it.  Under
+    a base-quality floor (ctx.min_base_quality) the host reader may not: the refusal is raised with its reason."""
+    d = DeviceBam(path)
+    try:
+        return ctx.upload_bamfile(d, blocks)
+    except _ffi.TcmiError as e:
+        if e.code != _ffi.E_UNSUPPORTED:
+            raise
+        q = ctx.min_base_quality
+        if q:
+            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--min-baseq %d needs the device path (the host packer knows no base-quality floor), "
+                                 "which %s left: %s" % (q, path, e)) from e
+        return None
+    finally:
+        d.close()
+
+
 def build_counts(bamfile, ref, ctx=None):
     """BAM (+ reference FASTA, for its length) -> int32 [L,7] count matrix on the GPU path.  A path (or LazyBam) is decoded
     ON THE DEVICE (BGZF inflate, record chain, pack: csrc/bam_device.hip, pack_device.hip); files the device decoder
@@ -47,19 +66,7 @@ def build_counts(bamfile, ref, ctx=None):
     ctx = ctx or _state.default_context()
     if not isinstance(bamfile, BamFile):
         path = bamfile.filename if isinstance(bamfile, LazyBam) else str(bamfile)
-        d = DeviceBam(path)
-        try:
-            rs = ctx.upload_bamfile(d)
-        except _ffi.TcmiError as e:
-            if e.code != _ffi.E_UNSUPPORTED:
-                raise
-            q = ctx.min_base_quality
-            if q:
-                raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--min-baseq %d needs the device path (the host packer knows no base-quality floor), "
-                                     "which %s left: %s" % (q, path, e)) from e
-            rs = None
-        finally:
-            d.close()
+        rs = device_readset(ctx, path)
         if rs is not None:
             try:
                 build_counts.last_reads, build_counts.last_filtered = int(rs.n_reads), int(rs.filtered)
