@@ -202,10 +202,12 @@ int  tcmi_readset_filtered(const tcmi_readset *rs, int64_t *n_filtered);
 int  tcmi_ctx_set_min_base_quality(tcmi_ctx *ctx, int32_t q);
 int  tcmi_readset_min_base_quality(const tcmi_readset *rs, int32_t *q);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
- * several-kernel path; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
+ * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
+ * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
  * "decode_batched" — files (or ranges) whose blocks the device decoder took in batches ("decode_token_mb");
  * "split_sub_taken" — tcmi_split_step calls whose range went through sub-ranges ("split_sub"); "h2d_piped" — decodes whose
- * compressed bytes crossed PCIe in pieces on a copy stream ("h2d_pieces") */
+ * compressed bytes crossed PCIe in pieces on a copy stream ("h2d_pieces"); "compute_units" — the device's CUs, which times the
+ * option "wg_per_cu" is the grid the packer and the tally kernel count on */
 int  tcmi_ctx_stat(tcmi_ctx *ctx, const char *key, int64_t *value);
 
 /* per-kernel device timing (hipEvents on the context's stream); kernel ids below */

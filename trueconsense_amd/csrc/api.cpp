@@ -336,10 +336,12 @@ int tcmi_ctx_stat(tcmi_ctx *c, const char *key, int64_t *value)
     if (!c || !key || !value) return tcmi_fail(c, TCMI_E_ARG, "null argument");
     if (!std::strcmp(key, "one_sync_taken")) { *value = c->stat_one_sync_taken; for (const tcmi_ctx *h : c->helpers) *value += h->stat_one_sync_taken; }
     else if (!std::strcmp(key, "one_sync_declined")) *value = c->stat_one_sync_declined;
+    else if (!std::strcmp(key, "one_sync_retried")) { *value = c->stat_one_sync_retried; for (const tcmi_ctx *h : c->helpers) *value += h->stat_one_sync_retried; }
     else if (!std::strcmp(key, "decode_batched")) { *value = c->stat_decode_batched; for (const tcmi_ctx *h : c->helpers) *value += h->stat_decode_batched; }
     else if (!std::strcmp(key, "split_sub_taken")) *value = c->stat_split_sub;
     else if (!std::strcmp(key, "h2d_piped")) { *value = c->stat_h2d_piped; for (const tcmi_ctx *h : c->helpers) *value += h->stat_h2d_piped; }
     else if (!std::strcmp(key, "one_sync_last_decline_flags")) *value = c->stat_last_decline;
+    else if (!std::strcmp(key, "compute_units")) *value = c->n_cu;
     else return tcmi_fail(c, TCMI_E_ARG, "unknown statistic %s", key);
     return TCMI_OK;
 }

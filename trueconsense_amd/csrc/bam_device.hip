@@ -95,7 +95,8 @@ inline size_t rest_bytes(size_t n_rec, size_t nb) { return al256(n_rec * 8 + 8) 
 // blocks [first, first + count) of the file (count < 0: to the end): the records that START in them.  A range that does not end
 // with the file takes one block more along — the last record may run into it — whose own records are left out.
 // Queues the copies and the three kernels on the context's stream; waits for nothing.
-int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t first_blk = 0, int64_t count = -1)
+// (worst_case: the arena reserved for as many records as the stream can hold — 36 bytes each —, not for records of 64 bytes)
+int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t first_blk = 0, int64_t count = -1, bool worst_case = false)
 {
     if (whole->blocks.empty()) return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: no BGZF blocks", whole->path.c_str());
     const int64_t all = (int64_t)whole->blocks.size();
@@ -155,7 +156,7 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
     const size_t b_file = resident ? 256 : tcmi_align256(f->cap), b_desc = tcmi_align256(nb * sizeof(BlockDesc)),
                  b_out = tcmi_align256(f->inflated + 128), b_slot = tcmi_align256(nb * (size_t)MAX_REC_PER_BLOCK * 4),
                  b_small = b_nb4 * 5 + b_nb8 + tcmi_align256(nb * 512) + 256, b_tok = tcmi_align256(tok_words * 4 + 256);
-    D.b_rest = rest_bytes(D.guess_rec, nb);
+    D.b_rest = rest_bytes(worst_case ? D.max_rec : D.guess_rec, nb);
     if (tcmi_arena_reserve(ctx, b_file + b_desc + b_out + b_slot + b_small + b_tok + D.b_rest + 16 * 256)) return TCMI_E_NOMEM;
     uint8_t *d_file = (uint8_t *)tcmi_arena_take(ctx, b_file);
     D.d_desc = (BlockDesc *)tcmi_arena_take(ctx, b_desc);
@@ -259,10 +260,10 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
 
 // The several-kernel path behind decode_enqueue: the block verdicts and the record chain come back to the host (one wait), which
 // words every refusal; then the dense record offsets.
-int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, int64_t first_blk = 0, int64_t count = -1)
+int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, int64_t first_blk = 0, int64_t count = -1, bool worst_case = false)
 {
     Decoded D;
-    int rc = decode_enqueue(ctx, whole, D, first_blk, count);
+    int rc = decode_enqueue(ctx, whole, D, first_blk, count, worst_case);
     if (rc) return rc;
     const tcmi_bamfile *f = D.f;
     const size_t nb = D.nb, nb_own = D.nb_own;
@@ -295,6 +296,9 @@ int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, 
     if (total > max_rec) return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: impossible record count", f->path.c_str());
     const size_t n = (size_t)total;
     const size_t need_rest = rest_bytes(n, nb);
+    // records of fewer than 64 bytes on average (single-base reads with one-letter names): the arena cannot grow under live data, but
+    // the host has just waited and nothing is in flight — the file is decoded once more into an arena reserved for the worst case
+    if (need_rest > b_rest && !worst_case) return decode_on_device(ctx, whole, Dout, first_blk, count, true);
     if (need_rest > b_rest)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: %zu very short records need more device scratch than was reserved: host reader", f->path.c_str(), n);
     uint64_t *d_rec = (uint64_t *)tcmi_arena_take(ctx, tcmi_align256(n * 8 + 8));
@@ -436,7 +440,7 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
         }
         tcmi_readset_free(ctx, rs);
         if (rc != TCMI_E_UNSUPPORTED) return rc;
-        if (attempt == 0 && (why & 0x800u)) { ctx->rec_bytes_seen = 0; continue; }     // (PKF_REC_OVF: records shorter than the hint said — once more, sized for the worst case)
+        if (attempt == 0 && (why & 0x800u)) { ctx->rec_bytes_seen = 0; ++ctx->stat_one_sync_retried; continue; }     // (PKF_REC_OVF: records shorter than the hint said — once more, sized for the worst case)
         ++ctx->stat_one_sync_declined; ctx->stat_last_decline = why;
         if (timing) std::fprintf(stderr, "[tcmi bamfile] one-sync path declined (flags 0x%x): the several-kernel path\n", why);
         break;
@@ -568,7 +572,7 @@ int tcmi_bamfile_step(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t ref_len, int
         }
         tcmi_readset_free(ctx, rs);
         if (rc != TCMI_E_UNSUPPORTED) return rc;
-        if (attempt == 0 && (why & 0x800u)) { ctx->rec_bytes_seen = 0; continue; }     // (PKF_REC_OVF: once more, sized for the worst case)
+        if (attempt == 0 && (why & 0x800u)) { ctx->rec_bytes_seen = 0; ++ctx->stat_one_sync_retried; continue; }     // (PKF_REC_OVF: once more, sized for the worst case)
         ++ctx->stat_one_sync_declined; ctx->stat_last_decline = why;
         break;
     }

@@ -69,6 +69,7 @@ constexpr uint32_t INFO_PROJ = 1u << 10, INFO_KEPT = 1u << 11;
 // flags raised for the host
 enum { PKF_LONG = 1, PKF_FARPOS = 2, PKF_BADREAD = 4, PKF_EVENT_OVF = 8, PKF_CHUNK_OVF = 16, PKF_HEADER_OVF = 32, PKF_WORD_OVF = 64,
        PKF_MULTIREF = 128, PKF_SLOT_OVF = 1u << 13 /* a kept read ends past its contig's slot (tcmi_ctx_set_layout) */ };
+constexpr uint32_t PKF_CHAIN = 256, PKF_STAT = 512, PKF_REC_OVF = 2048;       // (the one-sync path's: pk_index, pk_place)
 
 struct PackTotals {                 // device scalars, copied back to the host
     unsigned long long alg_bytes;
@@ -549,6 +550,11 @@ __global__ __launch_bounds__(PB) void pk_pack(PackOut o, const int32_t *c_pos, c
 {
     if (dev_slots > 0) {
         n_kept = (uint32_t)min(tot->n_kept, (unsigned long long)0xFFFFFFF0u);
+        // A file beyond the record or word capacity: pk_place left the entries of the blocks without room unwritten, and the kept
+        // reads may outnumber c_pos / c_info / c_woff, lenoff and covrun.  No chunk is cut from such entries — the tally kernel that
+        // tcmi_bamfile_step has queued behind this one takes a chunk's word0, P0 and run0 on trust — and nothing is stored past an
+        // array's end; the host declines the file after its wait.  (The two bits are pk_index's and pk_place's, launches ago.)
+        if (tot->flags & (PKF_REC_OVF | (uint32_t)PKF_WORD_OVF)) n_kept = 0u;
         n_words = (uint32_t)min(tot->n_words, (unsigned long long)o.word_cap - 18ull);
         int64_t C = 2048;                                       // (the twin of tcmi_pack_on_device's rule: one shared function changes this kernel's code)
         if (dev_slots < (1ll << 30)) {
@@ -784,7 +790,6 @@ constexpr long long CH_BIAS = 1ll << 44;
 __device__ inline unsigned long long ch_pack(int kind, long long v) { return ((unsigned long long)kind << 56) | (unsigned long long)(v + CH_BIAS); }
 __device__ inline int ch_kind(unsigned long long p) { return (int)((p >> 56) & 3u); }
 __device__ inline long long ch_val(unsigned long long p) { return (long long)(p & ((1ull << 56) - 1ull)) - CH_BIAS; }
-constexpr uint32_t PKF_CHAIN = 256, PKF_STAT = 512, PKF_REC_OVF = 2048;
 
 struct FusedArgs {
     const uint8_t *stream;
