@@ -166,6 +166,34 @@ def test_device_packer_against_host_packer_and_oracle(ctx):
     assert all(a == b for a, b in seen.values()), seen              # kept reads, algorithmic bytes, extent: same from both packers
 
 
+def test_host_packer_program_and_library_report_the_same_read_set(ctx, tmp_path):
+    """tests/test_host_pack.py checks the host packer on the CPU, in a program of its own (tests/host_pack_main.cpp).  Here the library
+    packs two of that file's inputs with device_pack = 0 and the context's own options: what it says of the read set it uploaded is what
+    the program reports for the same input and options, and the counts are the oracle's."""
+    from tests import test_host_pack as hp
+    prog = hp.build_program(str(tmp_path / "host_pack_main"), sanitize=False)
+    opt = dict(threads=8, slots=ctx.stat("compute_units") * 4)      # host_threads and wg_per_cu as a context starts with them
+    try:
+        ctx.set_option("device_pack", 0)
+        for name, reads in (hp.fuzz_cases()[0], ("reads per lane", hp.short_reads())):
+            d = hp.run(prog, tmp_path, reads, **opt)
+            T = d["totals"]
+            dev = sum(a.nbytes for k, a in d.items() if k[:2] == "f_" or (k[:2] == "g_" and T["g_reads"]))     # every array it copies
+            L = engine.reads_extent(reads, 0)
+            rs = ctx.upload(reads)
+            sets = [C.c_int64(0) for _ in range(3)]
+            _ffi.check(_ffi.lib().tcmi_readset_sets(rs.handle, *[C.byref(v) for v in sets]), ctx.handle)
+            assert not rs.packed_on_device, name
+            assert (rs.n_reads, rs.n_piled, rs.algorithmic_bytes, rs.max_end) == (T["n_reads"], T["n_piled"], T["alg"], T["max_end"]), name
+            assert rs.device_bytes == dev, name
+            assert [v.value for v in sets] == [T["f_reads"], T["f_chunks"], T["g_reads"]], name
+            got = ctx.step(rs, L, 30, True)[3]
+            rs.free()
+            assert np.array_equal(got, c_oracle.tally(reads, L)), (name, np.argwhere(got != c_oracle.tally(reads, L))[:5])
+    finally:
+        ctx.set_option("device_pack", 1)
+
+
 def test_tally_accumulate_split_readsets(ctx):
     """cfg 5 shape: one BAM split into contiguous read ranges, partial matrices summed."""
     ref, _ = sy.make_reference(L=8000, cds=[(10, 900)])

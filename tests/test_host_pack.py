@@ -1,0 +1,456 @@
+"""CPU: the host packer (csrc/host_pack.h, host_pack.cpp: select, plan_chunks, pack_aligned, pack_general) in a program of its own —
+tests/host_pack_main.cpp, built here with AddressSanitizer + UBSan and run as a child process — against a restatement of the packed
+layout (csrc/readset_layout.h) in this file: the packed arrays are decoded with numpy back into a count matrix that must equal the
+oracle's bit for bit, every chunk must keep what tally_planes_kernel takes on trust, every refusal must come with its code and text,
+and no sanitizer may report (a report ends the program with a non-zero status)."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from oracle import c_oracle
+from tests import fuzz_reads as fz
+from tests import synth_small as ss
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+E_ARG, E_UNSUPPORTED = -3, -9
+# csrc/readset_layout.h, restated
+ROUND, F_BLOCK, F_MAXW, F_MAXSPAN, F_SEG, F_SEQCAP, F_MAXSTAGE, P_NPL, P_SUB = 256, 256, 96, 600, 512, 6144, 8, 8, 512
+EVPOS, EV_OTHER, EV_X, EV_I = 1 << 29, 1 << 29, 1 << 30, 1 << 31
+CHUNK = np.dtype([("read0", "<i8"), ("word0", "<i8"), ("n_reads", "<i4"), ("P0", "<i4"), ("Wn", "<i4"), ("sub_reads", "<i4"),
+                  ("stage_end", "<i4", (F_MAXSTAGE,)), ("run0", "<i8"), ("n_runs", "<i4"), ("reserved", "<i4")])
+assert CHUNK.itemsize == 80
+TOTALS = ("n_reads", "n_piled", "alg", "max_end", "n_dropped", "f_reads", "f_chunks", "f_words", "f_events", "g_reads", "n_rounds", "n_cigar", "n_seqw")
+OUT_TYPES = {"totals": "<i8", "ref_ext": "<i8", "f_lenoff": "<u4", "f_event": "<u4", "f_seq": "<u4", "f_chunk": CHUNK, "f_covrun": "<u4",
+             "g_pos": "<i4", "g_meta": "<u4", "g_lseq": "<i4", "g_cigar": "<u4", "g_seq": "<u4", "g_round_cig": "<i8", "g_round_seq": "<i8"}
+DEFAULTS = dict(threads=8, slots=1024, stride=0, layout=None, project_reads=1, use_fast=1, chunk_stages=0, stage_cap=0)
+
+
+# ---- the program -----------------------------------------------------------------------------------------------------------------------
+def build_program(out, sanitize=True):
+    """tests/host_pack_main.cpp + csrc/host_pack.cpp and nothing else -> the program `out`"""
+    src = [os.path.join(ROOT, "tests", "host_pack_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "host_pack.cpp")]
+    rocm_clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"] if sanitize else []
+    tried = []
+    for cxx in (rocm_clang, shutil.which("g++"), shutil.which("clang++")):
+        if not cxx or not os.path.exists(cxx):
+            continue
+        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + san + ["-o", out] + src + ["-lpthread"], capture_output=True, text=True)
+        if r.returncode == 0:
+            return out
+        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
+    pytest.fail("no C++ compiler built the program:\n" + "\n".join(tried))
+
+
+@pytest.fixture(scope="module")
+def prog(tmp_path_factory):
+    return build_program(str(tmp_path_factory.mktemp("host_pack") / "host_pack_main"))
+
+
+def _record(name, a):
+    raw = np.ascontiguousarray(a).tobytes()
+    return name.encode().ljust(16, b"\0") + np.uint64(len(raw)).tobytes() + raw
+
+
+def write_dump(path, batch):
+    """the read dicts of the tests -> the flat dump the program reads"""
+    with open(path, "wb") as f:
+        f.write(_record("n_batch", np.int64(len(batch))))
+        for r in batch:
+            n = int(r["n_reads"])
+            f.write(_record("n_reads", np.int64(n)))
+            tid = r.get("tid")
+            for name, a, t in (("pos", r["pos"], "<i4"), ("flag", r["flag"], "<u2"), ("l_qseq", r["l_qseq"], "<i4"),
+                               ("tid", np.zeros(n, np.int32) if tid is None else tid, "<i4"), ("cigar_off", r["cigar_off"], "<u8"),
+                               ("cigar", r["cigar"], "<u4"), ("seq_off", r["seq_off"], "<u8"), ("seq", r["seq"], "u1")):
+                f.write(_record(name, np.asarray(a).astype(t)))
+
+
+def read_dump(path):
+    raw, out, at = open(path, "rb").read(), {}, 0
+    while at < len(raw):
+        name = raw[at:at + 16].rstrip(b"\0").decode()
+        n = int(np.frombuffer(raw, "<u8", 1, at + 16)[0])
+        out[name] = np.frombuffer(raw, OUT_TYPES[name], n // np.dtype(OUT_TYPES[name]).itemsize, at + 24)
+        at += 24 + n
+    assert list(out) == list(OUT_TYPES)
+    out["totals"] = dict(zip(TOTALS, (int(v) for v in out["totals"])))
+    return out
+
+
+def run(prog, tmp, batch, raw=False, **opt):
+    """-> the decoded output dump (raw: its bytes), or ("refused", code, text)"""
+    o = dict(DEFAULTS, **opt)
+    src, dst = os.path.join(str(tmp), "in.dump"), os.path.join(str(tmp), "out.dump")
+    write_dump(src, batch if isinstance(batch, (list, tuple)) else [batch])
+    if os.path.exists(dst):
+        os.remove(dst)
+    args = [prog, src, dst]
+    for k in ("threads", "slots", "stride", "project_reads", "use_fast", "chunk_stages", "stage_cap"):
+        args += ["--" + k.replace("_", "-"), str(o[k])]
+    if o["layout"]:
+        args += ["--layout", ",".join("%d:%d" % sl for sl in o["layout"])]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run(args, capture_output=True, text=True, env=env)
+    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    if r.stdout.startswith("refused "):
+        _, code, text = r.stdout.rstrip("\n").split(" ", 2)
+        assert not os.path.exists(dst)
+        return "refused", int(code), text
+    assert r.stdout == "packed\n", r.stdout
+    return open(dst, "rb").read() if raw else read_dump(dst)
+
+
+# ---- the restatement: csrc/readset_layout.h ----------------------------------------------------------------------------------------------
+def slices_of(Wn):
+    return F_BLOCK // max(2, (Wn * 8 + 31) // 32)
+
+
+def read_words(length):
+    return 2 * ((length + 31) // 32) + 2
+
+
+def stage_reads(Wn, maxnw, stage_cap):
+    S = slices_of(Wn)
+    cap = min(P_SUB, (F_SEQCAP - 16 - 2) // read_words(maxnw * 8))
+    if stage_cap > 0:
+        cap = min(cap, max(stage_cap, S * 4))
+    sub = S * 4 * max(1, cap // (S * 4))
+    return sub if sub <= cap else max(S, cap // S * S)
+
+
+def chunk_reads(sub, Wn, n_stages, balanced_cap):
+    return min(max(sub, min(((1 << P_NPL) - 1) * slices_of(Wn), n_stages * sub) // sub * sub), balanced_cap)
+
+
+def balanced_chunk(nf, slots):
+    longest = F_MAXSTAGE * 400
+    k = max(1, -(-nf // (slots * longest)))
+    return max(64, -(-nf // (k * slots)))
+
+
+def _bits(words, n):
+    return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:n].astype(np.int32)
+
+
+def decode(d, L, base=0, **opt):
+    """The packed read set -> its count matrix [L, 7] over positions [base, base + L), by the layout comment alone; asserts on the way
+    what tally_planes_kernel takes on trust of every chunk."""
+    o = dict(DEFAULTS, **opt)
+    T, ch, lenoff, seq, runs, ev = d["totals"], d["f_chunk"], d["f_lenoff"], d["f_seq"], d["f_covrun"], d["f_event"]
+    assert (T["f_reads"], T["f_chunks"], T["f_words"], T["f_events"]) == (len(lenoff), len(ch), len(seq), len(ev))
+    assert T["n_piled"] == T["f_reads"] + T["g_reads"] and T["f_words"] % 4 == 0
+    n_stages = min(o["chunk_stages"], F_MAXSTAGE) if o["chunk_stages"] > 0 else F_MAXSTAGE
+    cap = balanced_chunk(len(lenoff), o["slots"]) if o["chunk_stages"] == 0 else 1 << 62
+    m = np.zeros((L + 1, 7), np.int64)
+    cov = np.zeros(L + 2, np.int64)
+    read_at, run_at, word_at, largest = 0, 0, 0, 0
+    for c in ch:
+        n, P0, Wn, sub, word0 = int(c["n_reads"]), int(c["P0"]), int(c["Wn"]), int(c["sub_reads"]), int(c["word0"])
+        S = slices_of(Wn)
+        assert c["read0"] == read_at and c["run0"] == run_at and n >= 1 and c["reserved"] == 0          # reads and runs tile their arrays
+        assert word0 % 4 == 0 and word0 >= word_at and P0 % 8 == 0 and 1 <= Wn <= F_MAXW and 1 <= sub <= P_SUB
+        assert n <= ((1 << P_NPL) - 1) * S and n <= F_MAXSTAGE * sub and n <= n_stages * sub and n <= cap
+        n_st = -(-n // sub)
+        ends = [int(e) for e in c["stage_end"]]
+        assert all(a < b for a, b in zip(ends[:n_st - 1], ends[1:n_st])) and not any(ends[n_st:])
+        assert all((ends[i] - (ends[i - 1] - 2 if i else 0)) <= F_SEQCAP - 16 for i in range(n_st))
+        # coverage: the run words, a difference array
+        rw = runs[run_at:run_at + int(c["n_runs"])].astype(np.int64)
+        r_rel, r_len, r_cnt = rw & 1023, (rw >> 10) & 1023, rw >> 20
+        assert len(rw) >= 1 and r_cnt.min() >= 1 and r_cnt.max() <= 4095 and r_cnt.sum() == n
+        np.add.at(cov, P0 + r_rel - base, r_cnt)
+        np.add.at(cov, P0 + r_rel + r_len - base, -r_cnt)
+        hd = lenoff[read_at:read_at + n].astype(np.int64)
+        rel, ln, pair = hd & 1023, (hd >> 10) & 1023, hd >> 20
+        assert np.array_equal(np.repeat(rw & 0xFFFFF, r_cnt), hd & 0xFFFFF)                            # the runs are the reads, in order
+        assert ln.min() >= 1 and (rel + ln).max() <= Wn * 8
+        assert sub == stage_reads(Wn, int((ln.max() + 7) // 8), o["stage_cap"])
+        largest = max(largest, n)
+        cursor = word0 + 2
+        for j in range(n):
+            st = j // sub
+            start = word0 + (ends[st - 1] - 2 if st else 0)
+            a, nwords = start + 2 * int(pair[j]), 2 * ((int(ln[j]) + 31) // 32)
+            assert a == cursor and not seq[a - 2] and not seq[a - 1]                                   # packed back to back, a zero pair in front
+            assert a + nwords + 2 <= word0 + ends[st]
+            planes = seq[a:a + nwords].reshape(-1, 2)
+            code = _bits(planes[:, 0], int(ln[j])) + 2 * _bits(planes[:, 1], int(ln[j]))
+            p = P0 + int(rel[j]) - base
+            for k, col in ((1, 3), (2, 4), (3, 2)):                                                    # C, G, T in the oracle's columns
+                m[p:p + int(ln[j]), col] += code == k
+            cursor = a + nwords + 2
+            if (j + 1) % sub == 0 or j + 1 == n:
+                assert ends[st] == cursor - word0 and not seq[cursor - 2] and not seq[cursor - 1]      # ... and one behind the stage's last
+        read_at, run_at, word_at = read_at + n, run_at + int(c["n_runs"]), cursor
+    assert read_at == len(lenoff) and run_at == len(runs) and word_at <= len(seq)
+    m[:, 0] = np.cumsum(cov)[:L + 1]
+    e = ev.astype(np.int64)
+    assert len(e) == 0 or ((e >> 29).min() >= 1 and (e & (EVPOS - 1)).max() < T["max_end"])           # a kind, and a position below 2^29
+    other = np.zeros(L + 1, np.int64)
+    for bit, into in ((EV_OTHER, other), (EV_X, m[:, 5]), (EV_I, m[:, 6])):
+        np.add.at(into, (e[(e & bit) != 0] & (EVPOS - 1)) - base, 1)
+    m[:, 1] = m[:, 0] - m[:, 2] - m[:, 3] - m[:, 4] - other                                            # A by subtraction
+    assert not m[L].any()
+    # the general set: back into a read dict, tallied by the oracle
+    ng = T["g_reads"]
+    if ng:
+        nc, lq = (d["g_meta"] & 0xFFFF).astype(np.uint64), d["g_lseq"].astype(np.int64)
+        coff, soff = np.concatenate([[0], np.cumsum(nc)]).astype(np.uint64), np.concatenate([[0], np.cumsum((lq + 7) // 8)]).astype(np.uint64)
+        assert T["n_rounds"] == -(-ng // ROUND) and (T["n_cigar"], T["n_seqw"]) == (int(coff[-1]), int(soff[-1]))
+        at = list(range(0, ng, ROUND)) + [ng]
+        assert np.array_equal(d["g_round_cig"], coff[at].astype(np.int64)) and np.array_equal(d["g_round_seq"], soff[at].astype(np.int64))
+        b = d["g_seq"].view(np.uint8)
+        g = {"n_reads": ng, "pos": (d["g_pos"].astype(np.int64) - base).astype(np.int32), "flag": (d["g_meta"] >> 16).astype(np.uint16),
+             "l_qseq": d["g_lseq"].astype(np.int32), "cigar_off": coff, "cigar": np.ascontiguousarray(d["g_cigar"]), "seq_off": soff * np.uint64(4),
+             "seq": np.ascontiguousarray((b << 4) | (b >> 4)), "tid": None}
+        m[:L] += c_oracle.tally(g, L)
+    else:
+        assert (T["n_rounds"], T["n_cigar"], T["n_seqw"]) == (0, 0, 0)
+    return m[:L], largest
+
+
+def algorithmic_bytes(reads, keep):
+    nc = np.diff(reads["cigar_off"].astype(np.int64))
+    return int((12 + 4 * nc + (reads["l_qseq"].astype(np.int64) + 1) // 2)[keep].sum())
+
+
+def check(prog, tmp, reads, L=None, **opt):
+    """pack, decode, compare with the oracle -> (the dump, the largest chunk's reads)"""
+    L = L or c_oracle.extent(reads, 0)
+    d = run(prog, tmp, reads, **opt)
+    assert isinstance(d, dict), d
+    got, largest = decode(d, L, **opt)
+    want = c_oracle.tally(reads, L)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
+    assert d["totals"]["n_reads"] == reads["n_reads"] and d["totals"]["max_end"] == L
+    return d, largest
+
+
+# ---- the inputs --------------------------------------------------------------------------------------------------------------------------
+def plain_reads(rng, starts, lens, cigars=None):
+    """reads of the given starts and lengths ("<len>M" unless cigars says otherwise), random bases"""
+    cigars = cigars or ["%dM" % n for n in lens]
+    return ss.reads_from_spec({"reads": [{"pos": int(p), "flag": 0, "cigar": c, "seq": "".join("ACGT"[k] for k in rng.integers(0, 4, int(n)))}
+                                         for p, n, c in zip(starts, lens, cigars)]})
+
+
+def concat(parts, tids):
+    """several read dicts as one, part k on reference tids[k]"""
+    out = {"n_reads": sum(p["n_reads"] for p in parts)}
+    for k in ("pos", "flag", "l_qseq", "cigar", "seq"):
+        out[k] = np.concatenate([p[k] for p in parts])
+    out["tid"] = np.concatenate([np.full(p["n_reads"], t, np.int32) for p, t in zip(parts, tids)])
+    for k, v in (("cigar_off", "cigar"), ("seq_off", "seq")):
+        shift = np.cumsum([0] + [len(p[v]) for p in parts[:-1]])
+        out[k] = np.concatenate([parts[0][k][:1]] + [p[k][1:] + np.uint64(s) for p, s in zip(parts, shift)]).astype(np.uint64)
+    return out
+
+
+def fuzz_cases():
+    rng = np.random.default_rng(2024)
+    return [("sorted", fz.random_reads(rng, 3000, 1500)), ("unsorted", fz.random_reads(rng, 3000, 1500, sort=False)),
+            ("long", fz.random_reads(rng, 400, 20000, long_reads=True))]
+
+
+def short_reads():
+    """6 000 reads of 20-40 bases on sorted starts in [0, 700): one window, S = 10 depth slices"""
+    rng = np.random.default_rng(7)
+    starts, lens = np.sort(rng.integers(0, 700, 6000)), rng.integers(20, 41, 6000)
+    starts[0], starts[-1], lens[-1] = 0, 699, 40                    # (all of [0, 739): 93 grid words, 24 lane groups)
+    return plain_reads(rng, starts, lens)
+
+
+@pytest.fixture(scope="module")
+def fuzz():
+    return fuzz_cases()
+
+
+@pytest.fixture(scope="module")
+def short():
+    return short_reads()
+
+
+# ---- the tests ---------------------------------------------------------------------------------------------------------------------------
+def test_every_cigar_op_sorted_unsorted_and_long_reads(prog, tmp_path, fuzz):
+    for name, reads in fuzz:
+        d, _ = check(prog, tmp_path, reads)
+        T = d["totals"]
+        assert T["g_reads"] == 0 and T["f_events"] > 0, name
+        spans = np.array([sum(l for op, l in zip(reads["cigar"][a:b] & 15, reads["cigar"][a:b] >> 4) if op in (0, 2, 3, 7, 8))
+                          for a, b in zip(reads["cigar_off"][:-1].astype(int), reads["cigar_off"][1:].astype(int))])
+        keep = (reads["flag"] & 4 == 0) & (reads["tid"] == 0) & (spans > 0)
+        assert T["alg"] == algorithmic_bytes(reads, keep), name
+        if name == "long":                                            # pieces of F_SEG positions, re-sorted: more entries than reads
+            as_it_is = np.array([re.fullmatch("5*4*[078]+4*5*", "".join(str(op) for op in reads["cigar"][a:b] & 15)) is not None
+                                 for a, b in zip(reads["cigar_off"][:-1].astype(int), reads["cigar_off"][1:].astype(int))]) & (spans <= F_MAXSPAN)
+            pieces = np.where(as_it_is, 1, -(-spans // F_SEG))
+            assert spans[keep].max() > 2 * F_SEG and T["n_piled"] == T["f_reads"] == pieces[keep].sum() > keep.sum()
+            starts = np.concatenate([c["P0"] + (d["f_lenoff"][c["read0"]:c["read0"] + c["n_reads"]] & 1023) for c in d["f_chunk"]])
+            assert np.all(np.diff(starts.astype(np.int64)) >= 0)
+        else:
+            assert T["n_piled"] == T["f_reads"] == keep.sum(), name
+
+
+def test_reads_per_lane_rule_caps_a_chunk_before_its_stages_do(prog, tmp_path, short):
+    # chunk_stages = 8 is the default's eight stages without the balanced cap.  Sorted starts: a chunk's window is as wide as its own reads
+    # reach, the first one's below 512 positions (S = 17), and its eight stages fill up before a lane has seen 255 reads (the chunk closes
+    # on the size the window WITH the next read would allow, so it may end a little short of eight full stages)
+    d, largest = check(prog, tmp_path, short, chunk_stages=8)
+    c = d["f_chunk"][0]
+    S, sub = slices_of(int(c["Wn"])), int(c["sub_reads"])
+    assert 8 * sub < 255 * S and 7 * sub < largest == c["n_reads"] <= 8 * sub
+    # the same reads in any order: every chunk's window spans all of them, S = 10, and 255 reads per lane x 10 slices < 8 stages of 480 reads
+    order = np.random.default_rng(70).permutation(6000)
+    mixed = dict(short, pos=short["pos"][order], l_qseq=short["l_qseq"][order], cigar=short["cigar"][order])
+    mixed["seq_off"] = np.concatenate([[0], np.cumsum((mixed["l_qseq"] + 1) // 2)]).astype(np.uint64)
+    mixed["seq"] = np.concatenate([short["seq"][int(a):int(b)] for a, b in zip(short["seq_off"][order], short["seq_off"][order + 1])])
+    d, largest = check(prog, tmp_path, mixed, chunk_stages=8)
+    c = d["f_chunk"][0]
+    S, sub = slices_of(int(c["Wn"])), int(c["sub_reads"])
+    assert S == 10 and sub == 480 and 255 * S < 8 * sub and largest == c["n_reads"] == 255 * S // sub * sub == 2400
+
+
+def test_run_count_field_rolls_over_at_4095(prog, tmp_path):
+    rng = np.random.default_rng(5)
+    one = plain_reads(rng, [33], [150])
+    reads = plain_reads(rng, np.full(5000, 33), np.full(5000, 150))
+    reads["seq"] = np.tile(one["seq"], 5000)
+    d, _ = check(prog, tmp_path, reads, chunk_stages=8)
+    # a window of 150 positions leaves S = 51 slices and stages of 408 reads: a chunk ends at 8 x 408 reads, below the field's limit
+    assert list(d["f_covrun"] >> 20) == [3264, 1736] == [int(c["n_reads"]) for c in d["f_chunk"]]
+    # 100 bases: S = 64, stages of 512, a chunk of 4 096 equal reads — one more than the field counts
+    one = plain_reads(rng, [32], [100])
+    reads = plain_reads(rng, np.full(5000, 32), np.full(5000, 100))
+    reads["seq"] = np.tile(one["seq"], 5000)
+    d, largest = check(prog, tmp_path, reads, chunk_stages=8)
+    assert largest == 4096 and list(d["f_covrun"] >> 20) == [4095, 1, 904]              # a run was split although its reads are equal
+
+
+def test_header_limits_512_513_600_601(prog, tmp_path):
+    rng = np.random.default_rng(6)
+    lens, cigars = [], []
+    for n in (512, 513, 600, 601):
+        lens += [n, n - 1]
+        cigars += ["%dM" % n, "%dM1D%dM" % (n // 2, n - 1 - n // 2)]                # as it is (<= 600), and projected: one piece or two
+    reads = plain_reads(rng, np.sort(rng.integers(0, 3000, 8 * 20)), lens * 20, cigars * 20)
+    d, _ = check(prog, tmp_path, reads)
+    got = set(int(v) for v in (d["f_lenoff"] >> 10) & 1023)
+    assert got == {512, 513, 600, 1, 88, 89}                                          # 601 = 512 + 89, projected 513 = 512 + 1, 600 = 512 + 88
+
+
+def test_balanced_cap_stage_count_and_stage_cap(prog, tmp_path, short):
+    d, largest = check(prog, tmp_path, short, slots=8)
+    assert largest == 750 == balanced_chunk(6000, 8) and [int(c["n_reads"]) for c in d["f_chunk"]] == [750] * 8
+    # 1 024 slots: 6 reads per slot would do, the cap's floor of 64 holds
+    d, largest = check(prog, tmp_path, short, slots=1024)
+    assert largest == 64 == balanced_chunk(6000, 1024) and len(d["f_chunk"]) == -(-6000 // 64)
+    d, largest = check(prog, tmp_path, short, chunk_stages=1)
+    assert all(c["n_reads"] <= c["sub_reads"] and not c["stage_end"][1:].any() for c in d["f_chunk"]) and largest == d["f_chunk"][0]["sub_reads"]
+    d, largest = check(prog, tmp_path, short, stage_cap=64, chunk_stages=8)
+    assert all(c["sub_reads"] <= max(64, 4 * slices_of(int(c["Wn"]))) < stage_reads(int(c["Wn"]), 5, 0) for c in d["f_chunk"])
+    assert len(d["f_chunk"]) > 2 and max(int(c["n_reads"]) // int(c["sub_reads"]) for c in d["f_chunk"]) >= 7
+
+
+def test_batch_of_three_with_stride(prog, tmp_path):
+    rng = np.random.default_rng(8)
+    batch = [fz.random_reads(rng, 300, 1900) for _ in range(3)]
+    assert max(c_oracle.extent(r, 0) for r in batch) <= 2048
+    d = run(prog, tmp_path, batch, stride=2048)
+    got, _ = decode(d, 3 * 2048)
+    assert np.array_equal(got, np.concatenate([c_oracle.tally(r, 2048) for r in batch]))
+    assert d["totals"]["n_reads"] == 900 and d["totals"]["max_end"] == 2 * 2048 + c_oracle.extent(batch[2], 0)
+
+
+def test_contig_layout_drops_counts_and_refuses(prog, tmp_path):
+    rng = np.random.default_rng(9)
+    parts = [fz.random_reads(rng, 300, 900), fz.random_reads(rng, 200, 500), fz.random_reads(rng, 50, 400)]
+    for p in parts:
+        p["pos"][p["tid"] < 0] = -1                                                   # (tid -1 goes: part k lies on reference k)
+    ext = [c_oracle.extent(p, 0) for p in parts]
+    reads = concat(parts, [0, 1, 2])
+    layout = [(0, 1024), (1024 + 256, ext[1]), (-1, 0)]                               # reference 2 has no slot
+    d = run(prog, tmp_path, reads, layout=layout)
+    L = layout[1][0] + ext[1]
+    got, _ = decode(d, L)
+    want = np.zeros((L, 7), np.int64)
+    want[:ext[0]] = c_oracle.tally(parts[0], ext[0])
+    want[layout[1][0]:] = c_oracle.tally(parts[1], ext[1])
+    assert np.array_equal(got, want)
+    mapped2 = int(((parts[2]["flag"] & 4 == 0) & (parts[2]["pos"] >= 0)).sum())
+    assert d["totals"]["n_dropped"] == mapped2 > 0 and list(d["ref_ext"]) == [ext[0], ext[1], 0] and d["totals"]["max_end"] == L
+    # a read past its slot
+    layout[1] = (layout[1][0], ext[1] - 1)
+    ends = parts[1]["pos"].astype(np.int64) + [sum(l for op, l in ss.parse_cigar("".join("%d%s" % (w >> 4, "MIDNSHP=X"[w & 15]) for w in parts[1]["cigar"][a:b]))
+                                                   if op in (0, 2, 3, 7, 8)) for a, b in zip(parts[1]["cigar_off"][:-1].astype(int), parts[1]["cigar_off"][1:].astype(int))]
+    i = int(np.flatnonzero((ends == ext[1]) & (parts[1]["flag"] & 4 == 0))[0])
+    assert run(prog, tmp_path, reads, layout=layout) == ("refused", E_UNSUPPORTED, "read %d on reference 1 ends past the end of its contig's slot (at %d)"
+                                                         % (300 + i, ext[1]))
+
+
+def test_general_set_far_positions_no_projection_no_fast_path(prog, tmp_path, fuzz):
+    # positions around 2^29: the reads that end below it stay in the aligned set, the others go to the general set
+    rng = np.random.default_rng(10)
+    base = EVPOS - 2048
+    near = fz.random_reads(rng, 600, 4000)
+    want = c_oracle.tally(near, 4200)
+    near["pos"] = (near["pos"].astype(np.int64) + base).astype(np.int32)
+    d = run(prog, tmp_path, near)
+    got, _ = decode(d, 4200, base=base)
+    assert np.array_equal(got, want) and d["totals"]["g_reads"] > 50 and d["totals"]["f_reads"] > 50
+    assert d["g_pos"].min() + 1 > EVPOS - 600 and d["totals"]["max_end"] > EVPOS
+    reads = fuzz[0][1]
+    d, _ = check(prog, tmp_path, reads, project_reads=0)                             # only [H][S] M.. [S][H] stays aligned
+    assert d["totals"]["g_reads"] > 500 and d["totals"]["f_reads"] > 100 and d["totals"]["f_events"] > 0
+    assert not (d["f_event"] & (EV_X | EV_I)).any()
+    d, _ = check(prog, tmp_path, reads, use_fast=0)
+    assert d["totals"]["f_reads"] == 0 and d["totals"]["g_reads"] == d["totals"]["n_piled"] and d["totals"]["f_words"] == 0
+
+
+def test_every_refusal_of_select_code_and_text(prog, tmp_path):
+    rng = np.random.default_rng(11)
+    reads = plain_reads(rng, [10, 20, 30], [50, 50, 50])
+    reads["tid"][1] = 1
+    text = ("read 1 is mapped to reference 1: only single-reference alignments are supported (the reference implementation keys columns by "
+            "position only and fails on these)")
+    assert run(prog, tmp_path, reads) == ("refused", E_UNSUPPORTED, text[:159])      # (the text as far as the library's 160-byte buffer holds it)
+    reads = plain_reads(rng, [10, 20, 30], [50, 50, 50])
+    reads["l_qseq"][2] = -1
+    assert run(prog, tmp_path, reads) == ("refused", E_ARG, "read 2 has negative l_qseq")
+    reads = plain_reads(rng, [10, 20, 30], [50, 50, 50])
+    reads["seq_off"][3] -= 1
+    reads["seq"] = reads["seq"][:-1]
+    assert run(prog, tmp_path, reads) == ("refused", E_ARG, "read 2: seq bytes 24 < ceil(l_qseq/2)")
+    batch = [plain_reads(rng, [10], [50]), plain_reads(rng, [10, 2000], [50, 50])]
+    assert run(prog, tmp_path, batch, stride=2048) == ("refused", E_ARG, "read 1 of a batched BAM ends at 2050, beyond the batch stride 2048")
+    reads = plain_reads(rng, [10, (1 << 31) - 4096 - 50], [50, 50])
+    assert run(prog, tmp_path, reads) == ("refused", E_UNSUPPORTED, "read 1 ends beyond 2^31")
+    reads["pos"][1] -= 1                                                              # ... and the last position that is taken
+    assert run(prog, tmp_path, reads)["totals"]["g_reads"] == 1
+
+
+def test_empty_input_and_no_read_that_piles_up(prog, tmp_path):
+    rng = np.random.default_rng(12)
+    empty = ss.reads_from_spec({"reads": []})
+    nothing = plain_reads(rng, [10, 20, -1], [50, 50, 50], ["50M", "50S", "50M"])
+    nothing["flag"][0] = 4
+    for reads, n in ((empty, 0), (nothing, 3)):
+        d = run(prog, tmp_path, reads)
+        assert d["totals"] == dict(dict.fromkeys(TOTALS, 0), n_reads=n)
+        assert all(len(d[k]) == 0 for k in OUT_TYPES if k not in ("totals", "g_round_cig", "g_round_seq")) and list(d["g_round_cig"]) == [0]
+
+
+def test_dump_is_byte_identical_for_1_3_and_8_threads(prog, tmp_path, fuzz):
+    # 22 copies of the sorted case side by side: above 65 536 reads the classification itself runs in slices that are joined in order
+    reads = fuzz[0][1]
+    tiled = concat([reads] * 22, [0] * 22)
+    tiled["tid"] = np.tile(reads["tid"], 22)
+    tiled["pos"] = (np.tile(reads["pos"], 22) + np.repeat(np.arange(22) * 2048, reads["n_reads"])).astype(np.int32)
+    for name, r in fuzz + [("tiled", tiled)]:
+        dumps = [run(prog, tmp_path, r, raw=True, threads=t) for t in (1, 3, 8)]
+        assert dumps[0] == dumps[1] == dumps[2] and len(dumps[0]) > 1000, name

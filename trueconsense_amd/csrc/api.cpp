@@ -191,8 +191,8 @@ int tcmi_ctx_destroy(tcmi_ctx *c)
     for (auto &p : c->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : c->ev_pool) (void)hipEventDestroy(e);
     free_ws(c);
-    tcmi_upload_scratch_free(c->upload_scratch);
-    c->upload_scratch = nullptr;
+    tcmi_host_packed_free(c->host_packed);
+    c->host_packed = nullptr;
     if (c->dev_arena.base) (void)hipFree(c->dev_arena.base);
     if (c->d_lay) (void)hipFree(c->d_lay);
     c->d_lay = nullptr;

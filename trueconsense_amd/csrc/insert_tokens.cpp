@@ -30,41 +30,14 @@
 #include <unordered_map>
 #include <vector>
 
+#include "cigar_host.h"
 #include "tcmi_internal.h"
+
+using namespace tcmi_cigar;
 
 namespace {
 
 const char NT16[] = "=ACMGRSVTWYHKDBN";
-
-inline bool consumes_ref(unsigned op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
-inline bool is_match(unsigned op) { return op == 0 || op == 7 || op == 8; }
-inline bool consumes_query(unsigned op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }
-
-// p->indel of htslib's resolve_cigar2 at the last base of op k
-int64_t indel_after(const uint32_t *cg, int64_t n, int64_t k)
-{
-    if (k + 1 >= n) return 0;
-    const unsigned op = cg[k] & 0xF, op2 = cg[k + 1] & 0xF;
-    int64_t tot = 0;
-    if (op2 == 2 && op != 2) {
-        tot = -(int64_t)(cg[k + 1] >> 4);
-        for (int64_t j = k + 2; j < n && (cg[j] & 0xF) == 2; ++j) tot -= cg[j] >> 4;
-    } else if (op2 == 1) {
-        tot = cg[k + 1] >> 4;
-        for (int64_t j = k + 2; j < n; ++j) {
-            const unsigned o = cg[j] & 0xF;
-            if (o == 1) tot += cg[j] >> 4;
-            else if (o != 6) break;
-        }
-    } else if (op2 == 6 && k + 2 < n) {
-        for (int64_t j = k + 2; j < n; ++j) {
-            const unsigned o = cg[j] & 0xF;
-            if (o == 1) tot += cg[j] >> 4;
-            else if (consumes_ref(o)) break;
-        }
-    }
-    return tot;
-}
 
 // One read on one candidate column, before the filters that depend on the other reads of the column.
 struct Entry {

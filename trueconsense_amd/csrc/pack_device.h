@@ -107,7 +107,7 @@ __device__ inline uint32_t byte_at(const uint8_t *p)
     return (*reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3) >> ((a & 3) * 8)) & 0xFFu;
 }
 
-// CIGAR operations (SAM spec §1.4: M 0, I 1, D 2, N 3, S 4, H 5, P 6, = 7, X 8)
+// CIGAR operations (SAM spec §1.4: M 0, I 1, D 2, N 3, S 4, H 5, P 6, = 7, X 8); the host twins of these and of ins_after: cigar_host.h
 __device__ inline bool consumes_ref(uint32_t op) { return op == 0 || op == 2 || op == 3 || op == 7 || op == 8; }
 __device__ inline bool is_match(uint32_t op) { return op == 0 || op == 7 || op == 8; }
 __device__ inline bool consumes_query(uint32_t op) { return op == 0 || op == 1 || op == 4 || op == 7 || op == 8; }

@@ -40,7 +40,6 @@ namespace {
 
 constexpr int PB = 256;                          // lanes per workgroup of every kernel here
 constexpr int PK_CMAX = 1024;                    // most reads one pk_pack workgroup takes
-constexpr int64_t PK_LONGEST = (int64_t)TCMI_F_MAXSTAGE * 400;     // reads in the longest chunk the balancing rule aims for: TCMI_F_MAXSTAGE stages of 400 reads
 constexpr uint32_t NIB = 0x11111111u;
 
 // does the record carry a CG:B aux field (the real CIGAR of a read with more than 65 535 operations, SAM spec §4.2.2)?
@@ -556,10 +555,10 @@ __global__ __launch_bounds__(PB) void pk_pack(PackOut o, const int32_t *c_pos, c
         // array's end; the host declines the file after its wait.  (The two bits are pk_index's and pk_place's, launches ago.)
         if (tot->flags & (PKF_REC_OVF | (uint32_t)PKF_WORD_OVF)) n_kept = 0u;
         n_words = (uint32_t)min(tot->n_words, (unsigned long long)o.word_cap - 18ull);
-        int64_t C = 2048;                                       // (the twin of tcmi_pack_on_device's rule: one shared function changes this kernel's code)
+        int64_t C = 2048;                                       // (the twin of readset_layout.h's tcmi_balanced_chunk: one shared function changes this kernel's code)
         if (dev_slots < (1ll << 30)) {
             const int64_t nf = n_kept;
-            const int64_t k = max((int64_t)1, (nf + dev_slots * PK_LONGEST - 1) / (dev_slots * PK_LONGEST));
+            const int64_t k = max((int64_t)1, (nf + dev_slots * TCMI_F_LONGEST - 1) / (dev_slots * TCMI_F_LONGEST));
             C = max((int64_t)64, (nf + k * dev_slots - 1) / (k * dev_slots));
         }
         reads_per_wg = (int)min(C, (int64_t)PK_CMAX);
@@ -615,7 +614,8 @@ __global__ __launch_bounds__(PB) void pk_pack(PackOut o, const int32_t *c_pos, c
         mend = s_red[1][0]; mlen = s_red[2][0];
 #pragma unroll
         for (int w = 1; w < PB / 64; ++w) { mend = max(mend, s_red[1][w]); mlen = max(mlen, s_red[2][w]); }
-        // stage and chunk sizes exactly as the tally kernel will derive them from (Wn, sub_reads): readset.cpp's rules
+        // stage and chunk sizes exactly as the tally kernel will derive them from (Wn, sub_reads): the twins of readset_layout.h's
+        // tcmi_stage_reads and tcmi_chunk_reads
         const int Wn = (mend + 7) >> 3;
         const int S = FB / max(2, (Wn * 8 + 31) >> 5);
         int cap = min((int)TCMI_P_SUB, (TCMI_F_SEQCAP - 16 - 2) / (int)words_of((uint32_t)mlen));
@@ -1230,14 +1230,9 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     if (tot.n_words > 0xF0000000ull) { *why = PKF_WORD_OVF; return TCMI_E_UNSUPPORTED; }
 
     const int n_stages = ctx->chunk_stages > 0 ? std::min(ctx->chunk_stages, TCMI_F_MAXSTAGE) : TCMI_F_MAXSTAGE;
-    // reads per pk_pack workgroup: as readset.cpp — long chunks, but a multiple of the resident workgroups of them (its twin: pk_pack, dev_slots > 0)
-    int64_t C = 2048;
-    if (ctx->chunk_stages == 0 && ctx->balance_chunks) {
-        const int64_t slots = (int64_t)ctx->n_cu * ctx->wg_per_cu;
-        const int64_t k = (nf + slots * PK_LONGEST - 1) / (slots * PK_LONGEST);
-        C = std::max<int64_t>(64, (nf + k * slots - 1) / (k * slots));
-    }
-    C = std::min<int64_t>(C, PK_CMAX);
+    // reads per pk_pack workgroup: as the host packer — long chunks, but a multiple of the resident workgroups of them (its twin: pk_pack, dev_slots > 0)
+    const bool balance = ctx->chunk_stages == 0 && ctx->balance_chunks;
+    const int64_t C = std::min<int64_t>(balance ? tcmi_balanced_chunk(nf, (int64_t)ctx->n_cu * ctx->wg_per_cu) : 2048, PK_CMAX);
     const int64_t n_wg = (nf + C - 1) / C;
     // every workgroup opens at least one chunk; more when a window or a lane's 255-read budget runs out
     const uint32_t chunk_cap = (uint32_t)std::min<int64_t>(nf, 4 * n_wg + (int64_t)tot.max_end / 128 + 64);
@@ -1345,7 +1340,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     const bool balance = ctx->chunk_stages == 0 && ctx->balance_chunks;
     // (the grid: at least the workgroups the reads-per-workgroup rule leaves for any number of kept reads up to `cap`; pk_pack works the rule out itself)
     const int64_t slots = (int64_t)ctx->n_cu * ctx->wg_per_cu;
-    const int64_t k_cap = std::max<int64_t>(1, (cap + slots * PK_LONGEST - 1) / (slots * PK_LONGEST));
+    const int64_t k_cap = tcmi_balance_rounds(cap, slots);
     const int64_t n_wg = balance ? std::max<int64_t>(k_cap * slots, (cap + PK_CMAX - 1) / PK_CMAX) : (cap + PK_CMAX - 1) / PK_CMAX + (cap + 2047) / 2048;
     // words: a read of len positions takes <= len / 16 + 7 words, and a read without long deletions / skips has len <= l_seq,
     // each base of which takes 1.5 bytes of the stream (others overflow the capacity: PKF_WORD_OVF, the other path)

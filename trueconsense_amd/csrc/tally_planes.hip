@@ -2,10 +2,10 @@
 // Counterpart of the per-token loop of indexing.py:102-132 for the tokens that are plain bases
 // (SURVEY §8-P2).
 //
-// Data (tcmi_internal.h): per read ONE packed header word and its aligned bases as codes
+// Data (readset_layout.h): per read ONE packed header word and its aligned bases as codes
 // A=0 C=1 G=2 T=3 (anything else 0, listed as an OTHER event), 32 bases per pair of 32-bit words
 // {lo plane, hi plane}, with one zero pair between reads: 52 bytes for a 150-bp read.  The layout is
-// produced on the device by pack_device.hip (default) or on the host by readset.cpp.
+// produced on the device by pack_device.hip (default) or on the host by host_pack.cpp.
 //
 // One workgroup per chunk (<= 8 stages of <= 510 reads), lane (g, s) owns 32 positions g of the
 // window and depth slice s of the reads.  Per read of the slice: one 64-bit LDS header, ONE

@@ -10,22 +10,8 @@
 #include <vector>
 
 #include "../../include/tcmi.h"
+#include "readset_layout.h"          // tcmi_layout, the packed read set (TCMI_F_* / TCMI_P_*, tcmi_fast_chunk), the chunk geometry
 
-// ---- several contigs on one coordinate axis (tcmi_ctx_set_layout) --------------------------------------------------
-// Reference t's reads pile up at pos + shift[t]; shift[t] < 0: they do not pile up (a reference the caller has no record of);
-// a kept read must end at or before end[t] = shift[t] + slot_len[t].  No layout (n() == 0): reference 0 at 0, nothing else.
-// The one rule of the host packer (readset.cpp) and the host insert sweep (insert_tokens.cpp); the kernels read the same
-// table on the device (pack_device.h: shift_of).
-struct tcmi_layout {
-    std::vector<int64_t> shift, end;
-    int32_t n() const { return (int32_t)shift.size(); }
-    int64_t shift_of(int32_t tid) const
-    {
-        if (shift.empty()) return tid == 0 ? 0 : -1;
-        return tid >= 0 && tid < n() ? shift[(size_t)tid] : -1;
-    }
-    int64_t end_of(int32_t tid) const { return shift.empty() ? INT64_MAX : end[(size_t)tid]; }
-};
 // checks n_ref / shift / slot_len (slots in ascending order, disjoint, below TCMI_F_EVPOS) and fills *out; TCMI_OK or TCMI_E_ARG
 int tcmi_layout_build(int32_t n_ref, const int64_t *shift, const int64_t *slot_len, tcmi_layout *out, char *msg, size_t msg_cap);
 
@@ -56,76 +42,6 @@ static inline tcmi_filter_words tcmi_filter_pack(const tcmi_read_filter &f)
 }
 // the argument check of both entry points: TCMI_OK and *out filled, or TCMI_E_ARG (worded on `ctx`)
 int tcmi_read_filter_build(tcmi_ctx *ctx, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, tcmi_read_filter *out);
-
-// ---- device read layout -------------------------------------------------------------
-// Only reads that pile up (mapped, tid == 0, pos >= 0, reference span > 0)
-// are kept, in two sets:
-//
-//  * ALIGNED set (tally_planes.hip) — every read of every BASELINE config.  A read whose CIGAR is one run
-//    of match ops (M / = / X, optionally flanked by S / H clips) is taken as it is; any other CIGAR is
-//    PROJECTED onto the reference while it is packed: matched bases land on their reference offset,
-//    deleted / skipped positions stay empty, inserted and clipped bases are dropped, and the tokens that
-//    are not plain bases ("*", "..+n..") become EVENT words (position | kind) that the tail blocks of the
-//    same launch count.  Per entry ONE packed header word (position - window start | len << 10 | pair
-//    offset from the stage's first word << 20) and the bases as codes A=0 C=1 G=2 T=3 (anything else 0),
-//    32 bases per pair of words {lo plane, hi plane}, one zero pair in front of every read and behind the
-//    last of a chunk: 4 + 8*ceil(l/32) + 8 bytes, 52 for a 150-bp read.
-//    "Anything else" (N, IUPAC, '=', base beyond SEQ, deleted / skipped positions) is exactly what
-//    indexing.py:115-132 puts in no class; those positions are listed as OTHER event words (they
-//    count toward coverage but toward no class).
-//    Consecutive reads are grouped into CHUNKS (window <= TCMI_F_MAXW grid words of 8 positions,
-//    <= 255 reads per lane); one workgroup tallies one chunk in STAGES of <= sub_reads reads.
-//    Packed on the DEVICE from the BAM-native arrays (pack_device.hip: sorted input, entries of
-//    <= TCMI_D_MAXLEN positions) or on the HOST (readset.cpp: anything, long reads in pieces of
-//    TCMI_F_SEG positions, re-sorted).
-//  * GENERAL set (CIGAR-walk kernel, tally.hip): what the aligned path does not take (positions >= 2^29,
-//    reads with indels under option project_reads = 0, or everything under option tally_variant = 1;
-//    the tests use these to cross-check independent implementations), in ROUNDS of TCMI_ROUND reads with
-//    per-round offset tables, raw 4-bit codes.
-//
-// The algorithmic bytes of SURVEY 8-d are 12 + 4*n_cigar + ceil(l/2) per read: 91 for a 150-bp read.
-#define TCMI_ROUND 256
-#ifndef TCMI_F_BLOCK
-#define TCMI_F_BLOCK 256           // lanes per workgroup of the fast kernel (256 or 512; 256 measured faster)
-#endif
-#define TCMI_F_MAXW 96             // max grid words (8 positions each) in a chunk window
-#define TCMI_F_MAXSPAN 600         // longest aligned read the fast kernel takes in one piece
-#define TCMI_F_SEG 512             // projected reads longer than this are cut into pieces of this many positions
-#define TCMI_D_MAXLEN 512          // longest entry the device packer takes (a window holds MAXW * 8 = 768 positions)
-#ifndef TCMI_F_SEQCAP
-#define TCMI_F_SEQCAP 6144         // LDS words for staged bases
-#endif
-#define TCMI_F_MAXSTAGE 8          // stages per chunk
-#ifndef TCMI_P_NPL
-#define TCMI_P_NPL 8               // counter planes per lane: a lane counts <= 2^NPL - 1 reads per chunk
-#endif
-#ifndef TCMI_P_WAVES
-#define TCMI_P_WAVES 4             // workgroups per CU the kernel's register budget is set for
-#endif
-#ifndef TCMI_P_SUB
-#define TCMI_P_SUB 512             // max reads staged in LDS at a time
-#endif
-// event word = reference position | kind; kinds may be combined
-#define TCMI_F_EVPOS   (1u << 29)  // positions must stay below this for the fast path
-#define TCMI_F_EV_OTHER (1u << 29) // a covered position whose token is no A/C/G/T base: was counted as T by subtraction
-#define TCMI_F_EV_X     (1u << 30) // token "*"
-#define TCMI_F_EV_I     (1u << 31) // token carries an insertion
-
-struct tcmi_fast_chunk {           // 80 bytes
-    int64_t read0;                 // first read (index into f_pos / f_lenoff)
-    int64_t word0;                 // first word of the chunk's base stream (multiple of 4)
-    int32_t n_reads;
-    int32_t P0;                    // window start, multiple of 8
-    int32_t Wn;                    // window length in grid words
-    int32_t sub_reads;             // reads per stage (<= TCMI_P_SUB)
-    int32_t stage_end[TCMI_F_MAXSTAGE];   // word offset (from word0) one past stage i, trailing pad included;
-                                          // stage i starts at stage_end[i-1] - pad (0 for i = 0)
-    // the chunk's coverage as runs of reads with equal (position, length), words of d_fcovrun:
-    // position - P0 | len << 10 | (reads in the run, <= 4095) << 20
-    int64_t run0;
-    int32_t n_runs;
-    int32_t reserved_;
-};
 
 struct tcmi_readset {
     uint64_t uid = 0;           // unique per upload (graphs are cached against it, not the pointer)
@@ -198,8 +114,8 @@ struct tcmi_ride {                  // a finished matrix waiting for its call (s
     int32_t *counts; int64_t ld, L; int32_t mincov; int amb; uint8_t *plain, *alt, *flags; bool taken;
 };
 
-struct tcmi_upload_scratch;              // host buffers of tcmi_readset_upload, kept between calls (readset.cpp)
-void tcmi_upload_scratch_free(tcmi_upload_scratch *s);
+struct tcmi_host_packed;                 // what the host packer made of the last upload, its buffers kept between calls (host_pack.h)
+void tcmi_host_packed_free(tcmi_host_packed *p);
 struct tcmi_dev_arena {                  // grow-only device scratch of a context (freed with it): the BAM decoder's and the packers' temporaries (api.cpp)
     char *base = nullptr;
     size_t cap = 0, used = 0;
@@ -207,7 +123,7 @@ struct tcmi_dev_arena {                  // grow-only device scratch of a contex
 
 struct tcmi_ctx {
     int device = -1;
-    tcmi_upload_scratch *upload_scratch = nullptr;
+    tcmi_host_packed *host_packed = nullptr;
     tcmi_dev_arena dev_arena;
     uint64_t arena_epoch = 0;        // bumped whenever the arena is handed out anew
     // device-packed read sets hand their allocation back when they are freed; the next upload of a similar size takes it
