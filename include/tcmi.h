@@ -251,7 +251,14 @@ int tcmi_readset_origin(const tcmi_readset *rs, int32_t *packed_on_device);
 
 /* Device-resident tally.  d_counts: device int32 [7][ld] (plane order TCMI_COV..TCMI_I,
  * plane p at d_counts + p*ld, ld >= L).  Zeroes the planes first when `zero` != 0,
- * otherwise accumulates (used when one BAM is split over several read sets / GPUs). */
+ * otherwise accumulates (used when one BAM is split over several read sets / GPUs).
+ * The matrix is the caller's: any device pointer aligned to 4 bytes (else TCMI_E_ARG) and any ld >= L, odd ones and ld == L
+ * included — a torch tensor shaped (7, L) will do.  Exactly 7 * ld words are touched: `zero` clears all of them, padding
+ * [L, ld) of every plane included; without `zero` the padding is left as it is; nothing in front of d_counts or behind
+ * d_counts + 7 * ld is read or written.  Every (ld, alignment) gives the same counts; the bit-plane kernel adds two adjacent
+ * positions with one 64-bit atomic when ld is even AND d_counts is aligned to 8 bytes, and position by position otherwise
+ * (ld rounded up to 256 on a pointer from hipMalloc, as the library's own workspaces have it, takes the faster form).
+ * The launch is queued on the context's stream: memory another stream wrote (torch's) must be complete before the call. */
 int tcmi_tally_dev(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld,
                    void *d_counts, int zero);
 
@@ -259,7 +266,8 @@ int tcmi_tally_dev(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld,
  * reference's row layout (position p-1 at counts + 7*(p-1)).                      */
 int tcmi_tally(tcmi_ctx *ctx, const tcmi_reads *reads, int64_t L, int32_t *counts);
 
-/* planes [7][ld] on device  <->  rows [L][7] on host                              */
+/* planes [7][ld] on device  <->  rows [L][7] on host; d_counts and ld as for tcmi_tally_dev.  The upload writes all 7 * ld
+ * words (padding [L, ld) as zero); both wait for the context's stream.                                                */
 int tcmi_counts_download(tcmi_ctx *ctx, const void *d_counts, int64_t L, int64_t ld, int32_t *counts);
 int tcmi_counts_upload(tcmi_ctx *ctx, const int32_t *counts, int64_t L, int64_t ld, void *d_counts);
 
@@ -272,6 +280,12 @@ int tcmi_counts_upload(tcmi_ctx *ctx, const int32_t *counts, int64_t L, int64_t 
  *                  ('N' when cov < mincov)
  *        alt[p]    character of the secondary nucleotide (primary == X, Sequences.py:283-290)
  *        flags[p]  TCMI_F_* bits                                                      */
+/* tcmi_call_dev: d_counts as for tcmi_tally_dev (4-byte aligned, any ld >= L); it is only read.  d_plain, d_alt, d_flags:
+ * L bytes each at any byte address; bytes [L, ...) are not written.  d_events / d_event_counts (4-byte aligned; both or
+ * neither, else TCMI_E_ARG): the kernel calls 256 positions per block, b = 0 .. ceil(L/256) - 1; d_event_counts[b] = the positions of
+ * block b with flags & TCMI_EVENT_MASK and d_events[256 * b .. 256 * b + d_event_counts[b]) = those positions, ascending — so
+ * d_events needs ceil(L/256) * 256 words (the rest of a block's 256 is left as it was) and d_event_counts ceil(L/256) words,
+ * and the blocks' lists one after the other are all event positions in ascending order. */
 int tcmi_call_dev(tcmi_ctx *ctx, const void *d_counts, int64_t L, int64_t ld,
                   int32_t mincov, int include_ambig,
                   void *d_plain, void *d_alt, void *d_flags,

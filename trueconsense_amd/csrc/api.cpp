@@ -440,6 +440,7 @@ int tcmi_tally_dev(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld,
 {
     if (!ctx || !rs || !d_counts) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld (L=%lld ld=%lld)", (long long)L, (long long)ld);
+    if (reinterpret_cast<uintptr_t>(d_counts) % 4) return tcmi_fail(ctx, TCMI_E_ARG, "d_counts must be aligned to 4 bytes");
     if (L > INT32_MAX - 1024) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "L too large");
     if (rs->device != ctx->device) return tcmi_fail(ctx, TCMI_E_ARG, "read set lives on device %d, context on %d", rs->device, ctx->device);
     if (rs->max_end > L)
@@ -538,6 +539,8 @@ int tcmi_call_dev(tcmi_ctx *ctx, const void *d_counts, int64_t L, int64_t ld, in
     if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld");
     if ((d_events == nullptr) != (d_event_counts == nullptr))
         return tcmi_fail(ctx, TCMI_E_ARG, "d_events and d_event_counts must both be given or both NULL");
+    if (reinterpret_cast<uintptr_t>(d_counts) % 4 || reinterpret_cast<uintptr_t>(d_events) % 4 || reinterpret_cast<uintptr_t>(d_event_counts) % 4)
+        return tcmi_fail(ctx, TCMI_E_ARG, "d_counts, d_events and d_event_counts must be aligned to 4 bytes");
     TCMI_HIP(ctx, hipSetDevice(ctx->device));
     return tcmi_launch_call(ctx, (int32_t *)const_cast<void *>(d_counts), L, ld, mincov, include_ambig, 0, (uint8_t *)d_plain,
                             (uint8_t *)d_alt, (uint8_t *)d_flags, (int32_t *)d_events, (int32_t *)d_event_counts);
