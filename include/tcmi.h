@@ -201,6 +201,39 @@ int  tcmi_readset_filtered(const tcmi_readset *rs, int64_t *n_filtered);
  *   tcmi_readset_min_base_quality  the floor the read set was built under, whatever the context is set to later */
 int  tcmi_ctx_set_min_base_quality(tcmi_ctx *ctx, int32_t q);
 int  tcmi_readset_min_base_quality(const tcmi_readset *rs, int32_t *q);
+/* ---- amplicon primer mask (additive: what `ivar trim` / `samtools ampliconclip` do to the BAM in front of other callers) ------
+ * A primer is (start, end, reverse): 0-based, end-exclusive, on the count matrix's axis (under a contig layout: shifted by its
+ * contig's slot); reverse 0 is a '+' (left) primer, 1 a '-' (right) primer.  A kept read has a first column p = POS (+ its contig's
+ * shift) and a last column q = p + the CIGAR's reference length - 1 (soft and hard clips do not count).  With slack s:
+ *   head mask   head_end = the largest `end` over the '+' primers with start - s <= p < end (none: p); tokens on columns
+ *               c < head_end are masked
+ *   tail mask   tail_start = the smallest `start` over the '-' primers with start <= q < end + s (none: q + 1); tokens on columns
+ *               c >= tail_start are masked
+ * Both apply to every kept read whatever its own strand (a read-through mate carries the opposite primer at its 3' end); a '+'
+ * primer never masks a tail and a '-' primer never a head.  A masked token is SKIPPED exactly as one below the base-quality floor
+ * is — absent from its column: nothing for coverage, A/T/C/G, X or I —, per column and whatever the token is: a deletion that
+ * crosses the mask's edge loses only its masked columns, and the insertion mark goes iff the token in front of the insertion is
+ * masked.  Nothing else about the read changes: the piled-up count, the extent and the per-reference extents are the unmasked
+ * reads', and a read masked from end to end is piled up and adds nothing.  Together with a floor a token is skipped if either rule
+ * skips it; without a floor (q = 0) a query index at or beyond l_seq is NOT skipped outside the mask.
+ *   tcmi_ctx_set_primers   compiles the table (n = 0 clears it; TCMI_E_ARG: n above 65 536, start < 0, end <= start, a coordinate
+ *                     at or above 2^29, reverse not 0 / 1, slack outside 0..1000) and from now on governs every read set the
+ *                     context builds from a record stream decoded on the device — the entry points the floor governs, sub-range
+ *                     helper contexts included —, and with it the count matrix and everything derived from it.  It does NOT
+ *                     touch the insert-candidate sweeps' own region pileup (tcmi_readset_modal_tokens and kin: a masked read still
+ *                     votes on an insert candidate inside a primer site).  A read set REMEMBERS the table it was built under (it
+ *                     shares the device copy: its long reads are masked at tally time); changing or clearing the context's table
+ *                     later does not change it.  While a table is set whatever would tally WITHOUT it refuses with
+ *                     TCMI_E_UNSUPPORTED and a message naming --primers: the flat-array entry points, the array pipeline, the
+ *                     file runner's host-reader fallback (the host packer knows no mask).  No table: the kernels of before.
+ *   tcmi_readset_primers   the size of the table the read set was built under and its kept reads with a non-empty head or tail mask
+ *   tcmi_primers_compile   (GPU-free) the two segment lists the kernels search, as {a, b, v} triples sorted by a: a read whose p
+ *                     (q) lies in [a, b) of a head (tail) segment has head_end (tail_start) v; seg_cap: room per list, in
+ *                     segments (2 n - 1 suffice); msg (may be NULL) receives the words of a TCMI_E_ARG */
+int  tcmi_ctx_set_primers(tcmi_ctx *ctx, int32_t n, const int64_t *start, const int64_t *end, const int32_t *reverse, int32_t slack);
+int  tcmi_readset_primers(const tcmi_readset *rs, int32_t *n_primers, int64_t *n_masked_reads);
+int  tcmi_primers_compile(int32_t n, const int64_t *start, const int64_t *end, const int32_t *reverse, int32_t slack, int32_t seg_cap,
+                          int32_t *head, int32_t *n_head, int32_t *tail, int32_t *n_tail, char *msg, int64_t msg_cap);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);

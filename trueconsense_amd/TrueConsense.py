@@ -70,6 +70,32 @@ def read_filter_of(a):
     return f if any(f) else None
 
 
+def primers_of(a, layout=None):
+    """The parsed namespace's --primers / --primer-slack -> (rows on the count matrix's axis, slack) as Context.set_primers takes
+    them, or None when no BED was given.  Without a layout the rows whose chrom is the BAM's reference name are used (none: an argument
+    error); layout = (the BAM header's reference names, shift): every row shifted by its contig's slot, rows naming no contig ignored."""
+    if not getattr(a, "primers", None):
+        return None
+    from .io import primers as pb
+    try:
+        bed = pb.read_bed(a.primers)
+    except (OSError, pb.PrimerBedError) as e:
+        print(f"--primers: {e}. Exiting...")
+        sys.exit(1)
+    if layout is not None:
+        return pb.rows_for_layout(bed, *layout), int(a.primer_slack)
+    from .contigs import bam_header_refs
+    names = bam_header_refs(a.input)[0] if getattr(a, "input", None) else []
+    if not names:                                   # (--batch: every sample on the reference the FASTA names)
+        from .io import fasta
+        names = [fasta.read_first_record(a.reference)[0]]
+    rows = pb.rows_for_reference(bed, names[0])
+    if not rows:
+        print(f'--primers: no row of {a.primers} is on the reference "{names[0]}". Exiting...')
+        sys.exit(1)
+    return rows, int(a.primer_slack)
+
+
 def GetArgs(givenargs):
     """Same flags, defaults, required-ness and exit codes as TrueConsense.py:25-209; table-driven."""
     parser = argparse.ArgumentParser(
@@ -128,6 +154,12 @@ def GetArgs(givenargs):
     additive.append((("--min-baseq",), dict(type=_range_arg(parser, "--min-baseq", 255), default=0, metavar="N",
                                             help="skip pileup tokens (a read on a column) whose base quality is below N in the count matrix\n"
                                                  "(samtools mpileup -Q; qualities as the file stores them); needs the device decoder")))
+    additive.append((("--primers",), dict(type=str, default=None, metavar="File",
+                                          help="BED of the amplicon scheme's primers (chrom, start, end, name, pool, strand): a read's tokens\n"
+                                               "inside the primer at its head ('+') or tail ('-') stay out of the count matrix\n"
+                                               "(ivar trim, samtools ampliconclip); needs the device decoder")))
+    additive.append((("--primer-slack",), dict(type=_range_arg(parser, "--primer-slack", 1000), default=0, metavar="N",
+                                               help="a read may start up to N columns in front of a primer (end behind it) and still be masked")))
     # (is this the --batch form?  asked of a small parser of its own: "--batch=FILE" and argparse's abbreviations count too)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--batch", default=None)
@@ -186,6 +218,8 @@ def _child_argv(a, single):
             out += [flag, "0x%x" % v]
     if a.min_baseq:                                 # (the base-quality floor, likewise)
         out += ["--min-baseq", str(a.min_baseq)]
+    if a.primers:                                   # (the primer mask, likewise: both flags or neither)
+        out += ["--primers", a.primers, "--primer-slack", str(a.primer_slack)]
     if single:
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]
         for flag, v in (("-vcf", a.variants), ("-doc", a.depth_of_coverage), ("-ogff", a.output_gff)):
@@ -262,12 +296,13 @@ def run_batch(a):
     IndexGff = Gffindex(a.features)
     gffrows = list(IndexGff.index_dict(seqid="S").values())       # (the runner puts each sample's name there: TrueConsense.py:240)
     refID, refseq = fasta.read_first_record(a.reference)
+    prm = primers_of(a)
     t0 = time.perf_counter()
     cores = max(1, min(int(a.threads), os.cpu_count() or 1))
     runner = FileRunner(int(os.environ.get("TCMI_DEVICE", "0")), gffrows, a.coverage_level, a.noambiguity is False,
                         decoders=min(4, max(1, cores // 4)), decode_threads=max(1, cores // 2), walkers=min(4, max(1, cores // 4)),
                         gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a),
-                        min_baseq=a.min_baseq)
+                        min_baseq=a.min_baseq, primers=prm)
     runner.set_outputs(refID, refseq, vcf_header(date.today().strftime("%Y%m%d"), sys.argv[1:], a.reference, refID), IndexGff.header.raw_text,
                        [gff_row_columns(r) for r in gffrows])
     try:
@@ -283,7 +318,8 @@ def run_batch(a):
     finally:
         if a.stats:
             with open(a.stats, "w") as fh:
-                json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "stage_busy_seconds": runner.seconds,
+                json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "primers": len(prm[0]) if prm else 0,
+                           "stage_busy_seconds": runner.seconds,
                            "decoded_on": runner.decoded_on, "status": [int(x) for x in getattr(runner, "last_status", [])]}, fh)
         runner.close()
 
@@ -342,10 +378,14 @@ def main(args=None):
     _state.default_context().set_read_filter(*read_filter_args(flt))       # (always: the process's one context may have served another call)
     # (... and the base-quality floor, for this call only: the flat-array entry points of the same context refuse while it is set)
     _state.default_context().set_min_base_quality(a.min_baseq)
+    prm = primers_of(a)                             # (... and the primer table)
+    a.primer_rows = len(prm[0]) if prm else 0
+    _state.default_context().set_primers(*(prm or ()))
     try:
         _single_sample(a, flt, t)
     finally:
         _state.default_context().set_min_base_quality(0)
+        _state.default_context().set_primers()
 
 
 def _single_sample(a, flt, t):
@@ -380,7 +420,7 @@ def _single_sample(a, flt, t):
             secs = {k: t[k] - t[keys[i - 1]] for i, k in enumerate(keys) if i}
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
-                       "min_baseq": a.min_baseq,
+                       "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
                        "bam_bytes": os.path.getsize(a.input)}, fh)
 
 

@@ -60,6 +60,9 @@ _SIGS = {
     "tcmi_readset_filtered": (_int, [_vp, _P(_i64)]),
     "tcmi_ctx_set_min_base_quality": (_int, [_vp, _i32]),
     "tcmi_readset_min_base_quality": (_int, [_vp, _P(_i32)]),
+    "tcmi_ctx_set_primers": (_int, [_vp, _i32, _vp, _vp, _vp, _i32]),
+    "tcmi_readset_primers": (_int, [_vp, _P(_i32), _P(_i64)]),
+    "tcmi_primers_compile": (_int, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _P(_i32), _vp, _P(_i32), C.c_char_p, _i64]),
     "tcmi_profile_enable": (_int, [_vp, _int]),
     "tcmi_profile_reset": (_int, [_vp]),
     "tcmi_profile_get": (_int, [_vp, _int, _P(C.c_double), _P(_i64)]),

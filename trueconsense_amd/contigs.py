@@ -111,17 +111,19 @@ def _name_slot_overrun(err, host, header_names):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0):
+                 info=None, min_baseq=0, primers=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
     exclude_flags): extents, `dropped` and the host BamFile see the passing records only; info (a dict) receives "reads" (the
     file's records) and "reads_filtered".  min_baseq: the base-quality floor of the count matrix (Context.set_min_base_quality);
-    above 0 a file the device decoder declines is refused (the host packer knows no floor)."""
+    above 0 a file the device decoder declines is refused (the host packer knows no floor).  primers = (rows on the AXIS, slack)
+    (Context.set_primers; io.primers.rows_for_layout shifts a BED's rows): likewise; info then receives "reads_primer_masked" too."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
     ctx.set_min_base_quality(min_baseq)
+    ctx.set_primers(*(primers or ()))
     host = None
     try:
         rs = device_readset(ctx, path)              # (the floor it refuses under is the one just set)
@@ -135,6 +137,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
             ext, dropped = rs.ref_extents(n_ref), rs.dropped()
             if info is not None:
                 info.update(reads=host.n_records if host is not None else rs.n_reads, reads_filtered=host.n_removed if host is not None else rs.filtered)
+                if primers:                                     # (only under a table: the dict of before otherwise)
+                    info["reads_primer_masked"] = rs.primer_masked_reads
             plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
         finally:
             rs.free()
@@ -142,13 +146,14 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_layout()
         ctx.set_read_filter()
         ctx.set_min_base_quality()
+        ctx.set_primers()
     return plain, alt, flags, counts, ext, dropped, host
 
 
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import read_filter_of
+    from .TrueConsense import primers_of, read_filter_of
     flt, seen = read_filter_of(a), {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -157,10 +162,13 @@ def run(a):
     index = {n: t for t, n in enumerate(hdr_names)}
     gffobj = Gffindex(a.features)
     ctx = _state.default_context()
+    prm = primers_of(a, (hdr_names, shift))
+    seen["primers"] = len(prm[0]) if prm else 0
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
                                                                  threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
-                                                                 min_baseq=a.min_baseq)
+                                                                 min_baseq=a.min_baseq, primers=prm)
+    seen.setdefault("reads_primer_masked", 0)
 
     # every contig's slice of the call records (the call is position-local: a slice's records are the split run's)
     per = []

@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "tcmi_internal.h"
+#include "primer_table.h"
 
 static thread_local std::string g_err;
 
@@ -328,6 +329,27 @@ int tcmi_ctx_set_min_base_quality(tcmi_ctx *c, int32_t q)
     if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
     if (q < 0 || q > 255) return tcmi_fail(c, TCMI_E_ARG, "min_base_quality %d is outside 0..255", (int)q);
     c->min_bq = q;                                              // (a kernel argument of the next upload: nothing queued reads it)
+    return TCMI_OK;
+}
+
+int tcmi_ctx_set_primers(tcmi_ctx *c, int32_t n, const int64_t *start, const int64_t *end, const int32_t *reverse, int32_t slack)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    std::vector<tcmi_pseg> head, tail;
+    char msg[200] = "";
+    if (tcmi_primers_build(n, start, end, reverse, slack, head, tail, msg, sizeof msg)) return tcmi_fail(c, TCMI_E_ARG, "%s", msg);
+    if (n == 0) { c->primers.reset(); return TCMI_OK; }         // (read sets built under the old table keep their share of it)
+    // a table of its own for every call: nothing queued, and no read set, ever sees one rewritten
+    std::vector<int32_t> h(3 * (head.size() + tail.size()) + 1);
+    int32_t *hh = h.data(), *ht = h.data() + 3 * head.size();
+    for (size_t i = 0; i < head.size(); ++i) { hh[i] = head[i].a; hh[head.size() + i] = head[i].b; hh[2 * head.size() + i] = head[i].v; }
+    for (size_t i = 0; i < tail.size(); ++i) { ht[i] = tail[i].a; ht[tail.size() + i] = tail[i].b; ht[2 * tail.size() + i] = tail[i].v; }
+    TCMI_HIP(c, hipSetDevice(c->device));
+    std::shared_ptr<tcmi_primer_dev> dev = std::make_shared<tcmi_primer_dev>();
+    TCMI_HIP(c, hipMalloc((void **)&dev->seg, h.size() * 4));
+    TCMI_HIP(c, hipMemcpy(dev->seg, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+    dev->n_head = (int32_t)head.size(); dev->n_tail = (int32_t)tail.size(); dev->n_primers = n;
+    c->primers = std::move(dev);                                // (a kernel argument of the next upload)
     return TCMI_OK;
 }
 
@@ -768,7 +790,7 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     for (tcmi_ctx *h : ctx->helpers) {                          // (the caller's decoder options)
         h->verify_crc = ctx->verify_crc; h->decode_token_mb = ctx->decode_token_mb; h->one_sync = ctx->one_sync; h->mid_wait = ctx->mid_wait;
         h->prefix_kernels = ctx->prefix_kernels; h->h2d_pieces = ctx->h2d_pieces; h->sym_scratch_div = ctx->sym_scratch_div; h->prof = false;
-        h->flt = ctx->flt; h->min_bq = ctx->min_bq;
+        h->flt = ctx->flt; h->min_bq = ctx->min_bq; h->primers = ctx->primers;
     }
     TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));            // (the matrix is zero before anybody adds to it)
     std::vector<tcmi_readset *> rs((size_t)K, nullptr);
@@ -843,12 +865,12 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     tcmi_readset *sum = new tcmi_readset();
     sum->device = ctx->device; sum->packed_on_device = 2;
     sum->range_first = rs[0]->range_first; sum->range_next = rs[(size_t)K - 1]->range_next;
-    sum->flt = ctx->flt; sum->min_bq = ctx->min_bq;
+    sum->flt = ctx->flt; sum->min_bq = ctx->min_bq; sum->primers = ctx->primers;
     for (int k = 0; k < K; ++k) {
         const tcmi_readset *r = rs[(size_t)k];
         sum->n_reads += r->n_reads; sum->n_piled += r->n_piled; sum->alg_bytes += r->alg_bytes; sum->dev_bytes += r->dev_bytes;
         sum->max_end = std::max(sum->max_end, r->max_end); sum->max_len = std::max(sum->max_len, r->max_len); sum->s_reads += r->s_reads;
-        sum->f_reads += r->f_reads; sum->n_filtered += r->n_filtered;
+        sum->f_reads += r->f_reads; sum->n_filtered += r->n_filtered; sum->n_masked += r->n_masked;
         sum->parts.push_back({k == 0 ? ctx : ctx->helpers[(size_t)k - 1], rs[(size_t)k]});
     }
     *out = sum;

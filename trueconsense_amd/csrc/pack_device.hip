@@ -86,7 +86,9 @@ struct PackTotals {                 // device scalars, copied back to the host
     unsigned long long slot_ovf;    // a contig layout: (read index + 1) << 24 | reference of the last kept read that ends past its slot (0: none)
     unsigned long long n_dropped;   // a contig layout: mapped reads on references without a slot
     uint32_t n_filtered;            // a read filter: records that failed it (records are fewer than 2^31: PKF_REC_OVF)
+    uint32_t n_masked;              // a primer table: kept reads with a non-empty head or tail mask (in what was the struct's tail padding)
 };
+static_assert(sizeof(PackTotals) == 104, "n_masked sits in the tail padding: pk_report copies the struct as before");
 
 // words a read takes in the plane stream: its pairs, the zero pair behind them, and — for an even number of pairs — one more zero pair,
 // so that every read ends on a 16-byte boundary: the reads then lie in ONE contiguous run (a read's place is 2 + the scanned sum of
@@ -460,11 +462,73 @@ __device__ inline uint32_t dropped32(const uint8_t *qual, int32_t l_seq, int32_t
     return (qual_below32(qual + y, q) | ~hm) & nbm;             // (the load ends < 32 bytes behind the record: the stream's slack)
 }
 
+// ---- the primer mask (tcmi_ctx_set_primers; the BQ variants only) -------------------------------------------------------------------
+// A second source of bits for the drop plane, chosen by column and read end instead of by QUAL byte.  Per read, once: two binary
+// searches of the compiled segment lists (primer_table.h) give the masked head length and tail length, clamped to the read's columns
+// (<= 1023) and packed into one word, head | tail << 10; the lanes that make the pairs turn it into bits.
+using PrimerTab = tcmi_primer_tab;
+// Where the searches read the table.  A search is a chain of dependent loads, about log2(n) + 2 per list: some 18 probes per read for
+// an ARTIC-like scheme of a hundred amplicons.  A probe that hits L2 costs 180 - 225 cycles, one of LDS about 50, and a workgroup's 256
+// reads walk the same few entries; staging the table costs the workgroup one coalesced load and one barrier.  So a workgroup stages a
+// table of up to PT_LDS segments (3 KiB: the kernels keep their workgroups per CU) and searches larger ones where they lie.
+constexpr int PT_LDS = 256;
+__device__ inline int32_t seg_find(const int32_t *t, int32_t n, int32_t x, int32_t none)      // (t: a[n] | b[n] | v[n]; host twin: tcmi_pseg_find)
+{
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (t[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo > 0 && x < t[n + lo - 1] ? t[2 * n + lo - 1] : none;
+}
+// a read of `len` columns (1 .. 1023) whose first lies at p
+__device__ inline uint32_t mask_word(const int32_t *t, int32_t n_head, int32_t n_tail, int32_t p, int32_t len)
+{
+    const int32_t q = p + len - 1;
+    const int32_t he = seg_find(t, n_head, p, p), ts = seg_find(t + 3 * n_head, n_tail, q, q + 1);
+    return (uint32_t)min(max(he - p, 0), len) | ((uint32_t)min(max(q + 1 - ts, 0), len) << 10);
+}
+__device__ inline void stage_table(const PrimerTab &pt, int32_t *s_tab)
+{
+    const int n3 = 3 * (pt.n_head + pt.n_tail);
+    if (n3 <= 3 * PT_LDS) for (int i = threadIdx.x; i < n3; i += PB) s_tab[i] = pt.seg[i];
+}
+__device__ inline uint32_t mask_word_of(const PrimerTab &pt, const int32_t *s_tab, int32_t p, int32_t len)
+{
+    if (pt.n_head + pt.n_tail == 0) return 0u;
+    if (pt.n_head + pt.n_tail <= PT_LDS) return mask_word(s_tab, pt.n_head, pt.n_tail, p, len);
+    return mask_word(pt.seg, pt.n_head, pt.n_tail, p, len);
+}
+// one ballot over the lanes that are here and one atomic per wavefront that holds a masked read (as filter_view counts)
+__device__ inline void count_masked(bool masked, PackTotals *tot)
+{
+    const unsigned long long m = __ballot(masked);
+    if (masked && (int)(threadIdx.x & 63) == (int)__builtin_ctzll(m)) atomicAdd(&tot->n_masked, (uint32_t)__popcll(m));
+}
+__device__ inline uint32_t low_bits(int n) { return n <= 0 ? 0u : n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u; }
+// the masked ones among the nb (<= 32) columns from c0 on, of a read of `len` columns under the mask word mw
+__device__ inline uint32_t masked32(uint32_t mw, int len, int c0, int nb)
+{
+    const int head = (int)(mw & 1023u), keep_end = len - (int)(mw >> 10);
+    return (low_bits(head - c0) | ~low_bits(keep_end - c0)) & low_bits(nb);
+}
+// the skipped tokens of nb matched bases: query bases from y on, on columns from c0 on — the floor (Q = 0: none, and then a query
+// index at or beyond l_seq is NOT skipped) or the mask
+__device__ inline uint32_t skipped32(const uint8_t *qual, int32_t l_seq, int32_t y, int nb, uint32_t Q, uint32_t mw, int len, int c0)
+{
+    uint32_t d = Q ? dropped32(qual, l_seq, y, nb, Q) : 0u;
+    if (mw) d |= masked32(mw, len, c0, nb);
+    return d;
+}
+
 // one PROJECTED read (anything but [H][S]M[S][H]) -> its plane pairs (out: 2 * ceil(len / 32) words, then the zero pair) and its event words
 // BQ: and its drop words (dout: one per pair, then the zero word), under the floor Q — a D / N token is tested with the quality of
-// the next query base (the query index at which the op starts), the I mark belongs to the token in front of the insertion
+// the next query base (the query index at which the op starts), the I mark belongs to the token in front of the insertion — and under
+// the read's primer mask mw (mask_word), column by column: a D / N op that crosses the mask's edge loses only its masked columns
 template <bool BQ>
-__device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals *tot, uint32_t info, int32_t gpos, uint32_t *out, uint32_t *dout, uint32_t Q)
+__device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals *tot, uint32_t info, int32_t gpos, uint32_t *out, uint32_t *dout, uint32_t Q,
+                                 [[maybe_unused]] uint32_t mw)
 {
     const int len = (int)(info & 1023u), npair = (len + 31) >> 5;
     const uint8_t *qual = v.seq + ((size_t)v.l_seq + 1) / 2;
@@ -505,7 +569,7 @@ __device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals
                         uint32_t l, h, g;
                         fetch32(v.seq, v.l_seq, y + t, nb, l, h, g);
                         if constexpr (BQ) {
-                            const uint32_t d = dropped32(qual, v.l_seq, y + t, nb, Q);
+                            const uint32_t d = skipped32(qual, v.l_seq, y + t, nb, Q, mw, len, x + t);
                             l &= ~d; h &= ~d; g |= d;
                             dr |= d << b0;
                             skip_last = (d >> (nb - 1)) & 1u;
@@ -515,16 +579,27 @@ __device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals
                     }
                 } else {
                     if constexpr (BQ) {
-                        skip_last = (y < v.l_seq ? byte_at(qual + y) : 0u) < Q;
-                        for (int t = 0; skip_last && t < oplen;) {   // every column of the op: skipped, and no OTHER event
-                            const int q = (x + t) >> 5, b0 = (x + t) & 31, nb = min(32 - b0, oplen - t);
-                            flush_to(q);
-                            const uint32_t m = (nb >= 32 ? 0xFFFFFFFFu : ((1u << nb) - 1u)) << b0;
-                            dr |= m; ok |= m;
-                            t += nb;
+                        // the floor skips every column of the op or none; the mask skips the op's masked columns: no OTHER event, no
+                        // X event and no coverage there, and no I mark when the op's last column is skipped
+                        const bool below = Q && (y < v.l_seq ? byte_at(qual + y) : 0u) < Q;
+                        const int head = (int)(mw & 1023u), keep_end = len - (int)(mw >> 10);
+                        const int x1 = min(x + oplen, len);
+                        if (below || x < head || x1 > keep_end) {
+                            for (int t = 0; x + t < x1;) {
+                                const int q = (x + t) >> 5, b0 = (x + t) & 31, nb = min(32 - b0, x1 - x - t);
+                                flush_to(q);
+                                const uint32_t m = (below ? low_bits(nb) : masked32(mw, len, x + t, nb)) << b0;
+                                dr |= m; ok |= m;
+                                t += nb;
+                            }
                         }
-                    }
-                    if (op == 2 && !skip_last) {
+                        auto gone = [&](int c) { return below || c < head || c >= keep_end; };
+                        skip_last = gone(x + oplen - 1);
+                        if (op == 2) {
+                            const int nx = ins ? oplen - 1 : oplen;
+                            for (int t = 0; t < nx; ++t) if (!gone(x + t)) push_event(o, tot, (uint32_t)(gpos + x + t) | TCMI_F_EV_X);
+                        }
+                    } else if (op == 2) {
                         const int nx = ins ? oplen - 1 : oplen;
                         for (int t = 0; t < nx; ++t) push_event(o, tot, (uint32_t)(gpos + x + t) | TCMI_F_EV_X);
                     }
@@ -694,12 +769,16 @@ __global__ __launch_bounds__(PB) void pk_pack(PackOut o, const int32_t *c_pos, c
 // Reads that need their CIGAR walked (INFO_PROJ) are packed by their own lane, as before, straight to where they go.
 constexpr int PL_SLOTS = PB * (TCMI_D_MAXLEN / 32 + 2);      // a read's pairs, its zero pair, and the second one that ends it on 16 bytes
 // BQ (pk_planes_bq): under a base-quality floor Q — a pair also gets its word of the drop plane (drop[seq word / 2]): the 32 QUAL bytes
-// behind SEQ compared with Q (dropped32), the skipped bases out of lo / hi and out of the OTHER events
+// behind SEQ compared with Q (dropped32), the skipped bases out of lo / hi and out of the OTHER events.  Q = 0: no floor, a primer
+// table alone; pt: the table (every read's lane looks its mask word up once and leaves it in LDS beside s_info)
 template <bool BQ>
 __device__ __forceinline__ void planes_body(const PackSrc src, const PackOut o, const uint32_t *c_idx, const int32_t *c_pos, const uint32_t *c_info,
-                                   const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words, PackTotals *tot, uint32_t *drop, uint32_t Q)
+                                   const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words, PackTotals *tot, uint32_t *drop, uint32_t Q,
+                                   [[maybe_unused]] const PrimerTab pt)
 {
     __shared__ uint32_t s_info[PB], s_word[PB];
+    [[maybe_unused]] __shared__ uint32_t s_mask[BQ ? PB : 1];
+    [[maybe_unused]] __shared__ int32_t s_tab[BQ ? 3 * PT_LDS : 1];
     __shared__ int32_t s_pos[PB];
     __shared__ uint2 s_seq[PB];
     __shared__ uint16_t s_owner[PL_SLOTS];
@@ -707,6 +786,10 @@ __device__ __forceinline__ void planes_body(const PackSrc src, const PackOut o, 
     const uint32_t r0 = (uint32_t)blockIdx.x * PB;
     const int n = (int)min((uint32_t)PB, n_kept - r0);
     const uint32_t w_first = c_woff[r0], w_end = r0 + (uint32_t)n < n_kept ? c_woff[r0 + n] : n_words;
+    [[maybe_unused]] bool masked = false;
+    if constexpr (BQ) {
+        if (pt.n_head + pt.n_tail) { stage_table(pt, s_tab); __syncthreads(); }      // (uniform)
+    }
     if (tid < n) {
         const uint32_t g = r0 + (uint32_t)tid, info = c_info[g], word = 2u + c_woff[g];      // (the read's place in the plane stream)
         const int32_t pos = c_pos[g];
@@ -715,9 +798,12 @@ __device__ __forceinline__ void planes_body(const PackSrc src, const PackOut o, 
         const bool own = (info & INFO_PROJ) != 0;                       // (its lane writes its pairs and the zero pair behind them)
         const int n_slot = (int)(words_of(info & 1023u) >> 1);
         s_info[tid] = info; s_word[tid] = word; s_pos[tid] = pos; s_seq[tid] = c_seq[g];
+        [[maybe_unused]] uint32_t mw = 0u;
+        if constexpr (BQ) { mw = mask_word_of(pt, s_tab, pos, (int32_t)(info & 1023u)); s_mask[tid] = mw; masked = mw != 0u; }
         for (int q = 0; q < n_slot; ++q) s_owner[slot0 + q] = own && q <= npair ? (uint16_t)0xFFFFu : (uint16_t)(tid | (q << 8));
-        if (own) pack_read<BQ>(view(src, c_idx[g]), o, tot, info, pos, o.seq + word, BQ ? drop + (word >> 1) : nullptr, Q);
+        if (own) pack_read<BQ>(view(src, c_idx[g]), o, tot, info, pos, o.seq + word, BQ ? drop + (word >> 1) : nullptr, Q, mw);
     }
+    if constexpr (BQ) { if (pt.n_head + pt.n_tail) count_masked(masked, tot); }
     __syncthreads();
     const uint8_t *bytes = src.mode == 0 ? src.seq : src.stream;
     const uint32_t n_slots = (w_end - w_first) >> 1;
@@ -740,7 +826,7 @@ __device__ __forceinline__ void planes_body(const PackSrc src, const PackOut o, 
         const uint8_t *sq = bytes + (((unsigned long long)(where.y & 0xFFu) << 32) | where.x);
         pair_planes(sq + (uint32_t)(y >> 1), y & 1, have, lo, hi, ok);
         if constexpr (BQ) {
-            const uint32_t d = dropped32(sq + ((size_t)l_seq + 1) / 2, l_seq, y, nb, Q);
+            const uint32_t d = skipped32(sq + ((size_t)l_seq + 1) / 2, l_seq, y, nb, Q, s_mask[t], len, 32 * q);
             lo &= ~d; hi &= ~d; ok |= d;
             drop[(s_word[t] >> 1) + q] = d;
         }
@@ -757,13 +843,15 @@ __global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const ui
                                                 const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words,
                                                 PackTotals *tot)
 {
-    planes_body<false>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, nullptr, 0u);
+    planes_body<false>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, nullptr, 0u, PrimerTab{nullptr, 0, 0});
 }
-__global__ __launch_bounds__(PB) void pk_planes_bq(PackSrc src, PackOut o, const uint32_t *c_idx, const int32_t *c_pos, const uint32_t *c_info,
+// (8 / 5 waves per SIMD asked of the two BQ kernels: what they ran at before they took the table — the mask word would otherwise cost
+//  them a wave each, 67 and 99 vector registers; no scratch and no vector spill either way, scalar spills to lanes: DESIGN 6)
+__global__ __launch_bounds__(PB, 8) void pk_planes_bq(PackSrc src, PackOut o, const uint32_t *c_idx, const int32_t *c_pos, const uint32_t *c_info,
                                                    const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words,
-                                                   PackTotals *tot, uint32_t *drop, uint32_t Q)
+                                                   PackTotals *tot, uint32_t *drop, uint32_t Q, PrimerTab pt)
 {
-    planes_body<true>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, drop, Q);
+    planes_body<true>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, drop, Q, pt);
 }
 
 
@@ -819,6 +907,7 @@ struct FusedArgs {
     PackTotals *tot;
     uint32_t *drop;                 // pk_place_bq: the drop plane [word_cap / 2] and the base-quality floor (behind everything else: the
     uint32_t min_bq;                // other kernels' argument offsets stay)
+    PrimerTab pt;                   // pk_place_bq: the primer table (all zero: none), appended likewise
 };
 
 // the sum of v[0 .. n) over the workgroup (every lane gets it); s4: LDS [PB / 64]
@@ -948,10 +1037,12 @@ __global__ __launch_bounds__(PB) void pk_index(FusedArgs a)
     }
 }
 
-// BQ (pk_place_bq): as planes_body<true>
+// BQ (pk_place_bq): as planes_body<true> — the floor a.min_bq (0: none) and the primer table a.pt, looked up by every kept read's lane
 template <bool BQ>
 __device__ __forceinline__ void place_body(const FusedArgs a)
 {
+    [[maybe_unused]] __shared__ uint32_t s_mask[BQ ? PB : 1];
+    [[maybe_unused]] __shared__ int32_t s_tab[BQ ? 3 * PT_LDS : 1];
     __shared__ uint2 s_w[PB / 64];
     __shared__ unsigned long long s_sum[2 * (PB / 64)];
     __shared__ uint32_t s_info[PB], s_word[PB];
@@ -1042,6 +1133,9 @@ __device__ __forceinline__ void place_body(const FusedArgs a)
         return;
     }
     // ---- the kept reads' entries and their planes ---------------------------------------------------------------------------------------
+    if constexpr (BQ) {
+        if (a.pt.n_head + a.pt.n_tail) { stage_table(a.pt, s_tab); __syncthreads(); }     // (uniform: the workgroups that left above hold no records)
+    }
     uint32_t run_k = 0, run_w = 0;                                  // kept reads / words of the tiles in front of this one
     for (uint32_t t0 = 0; t0 < n; t0 += PB) {
         const uint32_t t = t0 + (uint32_t)tid;
@@ -1054,6 +1148,7 @@ __device__ __forceinline__ void place_body(const FusedArgs a)
         __syncthreads();
         const uint32_t tile_k = s_w[0].x, tile_w = s_w[0].y;
         const uint32_t w_first = (uint32_t)ex_w + run_w;            // the tile's first word offset (its reads are contiguous from there)
+        [[maybe_unused]] bool masked = false;
         if (word) {
             const uint32_t lk = incl.x - 1u, lwoff = incl.y - nwords;    // the read's place among the tile's kept reads; its first word, from the tile's
             const uint32_t j = (uint32_t)ex_k + run_k + lk, woff = w_first + lwoff;
@@ -1063,10 +1158,13 @@ __device__ __forceinline__ void place_body(const FusedArgs a)
             const int npair = (int)((word & 1023u) + 31u) >> 5;
             const bool own = (word & INFO_PROJ) != 0;               // (its lane writes its pairs and the zero pair behind them)
             s_info[lk] = word; s_word[lk] = 2u + woff; s_pos[lk] = pos; s_seq[lk] = sq;
+            [[maybe_unused]] uint32_t mw = 0u;
+            if constexpr (BQ) { mw = mask_word_of(a.pt, s_tab, pos, (int32_t)(word & 1023u)); s_mask[lk] = mw; masked = mw != 0u; }
             const uint32_t slot0 = lwoff >> 1;
             for (int q = 0; q < (int)(nwords >> 1); ++q) s_owner[slot0 + q] = own && q <= npair ? (uint16_t)0xFFFFu : (uint16_t)(lk | ((uint32_t)q << 8));
-            if (own) pack_read<BQ>(view_rec(a.stream + a.rec_off[ex_r + t]), a.o, a.tot, word, pos, a.o.seq + 2u + woff, BQ ? a.drop + ((2u + woff) >> 1) : nullptr, a.min_bq);
+            if (own) pack_read<BQ>(view_rec(a.stream + a.rec_off[ex_r + t]), a.o, a.tot, word, pos, a.o.seq + 2u + woff, BQ ? a.drop + ((2u + woff) >> 1) : nullptr, a.min_bq, mw);
         }
+        if constexpr (BQ) { if (a.pt.n_head + a.pt.n_tail) count_masked(masked, a.tot); }
         __syncthreads();
         uint2 *dst = reinterpret_cast<uint2 *>(a.o.seq + 2u + w_first);                      // (word offsets are multiples of 4: 8-byte aligned)
         for (uint32_t k = tid; k < (tile_w >> 1); k += PB) {           // (the twin of pk_planes' loop: one shared function reorders this kernel's code)
@@ -1087,7 +1185,8 @@ __device__ __forceinline__ void place_body(const FusedArgs a)
             uint32_t lo, hi, ok;
             pair_planes(a.stream + ((((unsigned long long)(where.y & 0xFFu) << 32) | where.x) + (uint32_t)(y >> 1)), y & 1, have, lo, hi, ok);
             if constexpr (BQ) {
-                const uint32_t dd = dropped32(a.stream + (((unsigned long long)(where.y & 0xFFu) << 32) | where.x) + ((size_t)l_seq + 1) / 2, l_seq, y, nb, a.min_bq);
+                const uint32_t dd = skipped32(a.stream + (((unsigned long long)(where.y & 0xFFu) << 32) | where.x) + ((size_t)l_seq + 1) / 2, l_seq, y, nb, a.min_bq,
+                                              s_mask[tt], len, 32 * q);
                 lo &= ~dd; hi &= ~dd; ok |= dd;
                 ddst[k] = dd;
             }
@@ -1104,7 +1203,30 @@ __device__ __forceinline__ void place_body(const FusedArgs a)
     }
 }
 __global__ __launch_bounds__(PB) void pk_place(FusedArgs a) { place_body<false>(a); }
-__global__ __launch_bounds__(PB) void pk_place_bq(FusedArgs a) { place_body<true>(a); }
+__global__ __launch_bounds__(PB, 5) void pk_place_bq(FusedArgs a) { place_body<true>(a); }
+
+// The long reads of a stream (left to tally_stream_kernel, which masks them tally by tally) with a non-empty head or tail mask, counted
+// once for tcmi_readset_primers: a few workgroups stride over the tot->n_gen records the classifying kernel listed; one lane per read
+// adds up its CIGAR's reference length.  Launched only under a table.
+__global__ __launch_bounds__(PB) void pk_mask_long(PackSrc s, const uint32_t *gen_idx, PackTotals *tot, PrimerTab pt)
+{
+    const uint32_t n = tot->n_gen;
+    for (uint32_t i0 = blockIdx.x * PB; i0 < n; i0 += gridDim.x * PB) {        // (uniform: every lane of a wavefront reaches the ballot)
+        const uint32_t i = i0 + threadIdx.x;
+        bool masked = false;
+        if (i < n) {
+            const ReadView v = view(s, (int64_t)gen_idx[i]);
+            int32_t span = 0;
+            for (uint32_t k = 0; k < v.n_cigar; ++k) {
+                const uint32_t cw = ld_u32(v.cigar + 4 * (size_t)k);
+                if (consumes_ref(cw & 0xFu)) span += (int32_t)(cw >> 4);
+            }
+            const int32_t p = v.pos + shift_of(s, v.tid), q = p + span - 1;
+            masked = seg_find(pt.seg, pt.n_head, p, p) > p || seg_find(pt.seg + 3 * pt.n_head, pt.n_tail, q, q + 1) <= q;
+        }
+        count_masked(masked, tot);
+    }
+}
 
 } // namespace
 
@@ -1126,7 +1248,7 @@ static char *take_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t want)
 }
 
 // one allocation for everything the tally kernel reads: headers | planes | chunk records | runs | events, and 256 bytes of slack
-// behind the last array (pk_pack zeroes them); under a base-quality floor (drop != nullptr) the drop plane behind the slack: one word
+// behind the last array (pk_pack zeroes them); under a base-quality floor or a primer table (drop != nullptr) the drop plane behind the slack: one word
 // per pair of the plane stream, *drop_bytes of them — the caller zeroes it in front of its plane kernel, inside the pack bracket
 // (zero_drop): the pair in front of the first read and the stream's slack stay zero, the packers write every other word
 static int carve_blob(tcmi_ctx *ctx, tcmi_readset *rs, size_t n_reads, uint32_t word_cap, uint32_t chunk_cap, uint32_t event_cap, PackOut *o, uint32_t **drop,
@@ -1178,6 +1300,9 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     const int64_t n = src.n;
     const uint32_t min_bq = src.mode == 1 ? src.min_bq : 0u;        // (flat arrays carry no QUAL: their entry points refuse a floor)
     rs->min_bq = (int32_t)min_bq;
+    if (src.mode == 1) rs->primers = ctx->primers;                  // (... and a primer table likewise)
+    const PrimerTab pt = tcmi_primer_args(rs->primers);
+    const bool drop_on = min_bq || pt.seg;                          // the read set gets a drop plane and the BQ plane kernel
     if (n > 0xFFFFFFF0ll) { *why = PKF_LONG; return TCMI_E_UNSUPPORTED; }
     const int64_t n_blk = (n + PB - 1) / PB;
     uint32_t *info = (uint32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4);
@@ -1204,6 +1329,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
         tcmi_prof_begin(ctx, TCMI_K_PACK_CLASSIFY);
         hipLaunchKernelGGL(pk_classify, dim3((unsigned)n_blk), dim3(PB), 0, ctx->stream, src, info, rd_seq, rd_pos, blk_sum, blk_alg, blk_end, d_tot, gen_idx);
         hipLaunchKernelGGL(pk_scan, dim3(1), dim3(1024), 0, ctx->stream, blk_sum, blk_alg, blk_end, n_blk, d_tot);
+        if (pt.seg && gen_idx) hipLaunchKernelGGL(pk_mask_long, dim3(64), dim3(PB), 0, ctx->stream, src, gen_idx, d_tot, pt);
         tcmi_prof_end(ctx, TCMI_K_PACK_CLASSIFY);
         TCMI_HIP(ctx, hipGetLastError());
     }
@@ -1219,6 +1345,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     const int64_t nf = (int64_t)tot.n_kept;
     rs->n_lay = n_lay; rs->d_lay = src.lay; rs->lay_gen = ctx->lay_gen; rs->n_dropped = (int64_t)tot.n_dropped;
     rs->n_filtered = (int64_t)tot.n_filtered;
+    rs->n_masked = (int64_t)tot.n_masked;                           // (the long reads', so far)
     rs->ref_ext.assign(h_ext.begin(), h_ext.end());
     rs->n_piled = nf + (int64_t)tot.n_gen; rs->f_reads = nf; rs->alg_bytes = (int64_t)tot.alg_bytes; rs->max_end = tot.max_end; rs->max_len = (int32_t)tot.max_len;
     rs->packed_on_device = 1;
@@ -1246,12 +1373,14 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     if (ctx->dev_arena.used > ctx->dev_arena.cap) { return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: pack scratch under-reserved"); }
 
     uint32_t event_cap = (uint32_t)std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(1 << 20, nf / 2));
+    const uint32_t h_masked_long = tot.n_masked;
     for (int attempt = 0;; ++attempt) {
         PackOut o = {};
         uint32_t *drop = nullptr;
         size_t drop_bytes = 0;
-        if (const int rc = carve_blob(ctx, rs, (size_t)nf, word_cap, chunk_cap, event_cap, &o, min_bq ? &drop : nullptr, &drop_bytes)) return rc;
+        if (const int rc = carve_blob(ctx, rs, (size_t)nf, word_cap, chunk_cap, event_cap, &o, drop_on ? &drop : nullptr, &drop_bytes)) return rc;
         if (attempt > 0) TCMI_HIP(ctx, hipMemsetAsync(&d_tot->n_chunks, 0, 4 * sizeof(uint32_t), ctx->stream));    // n_chunks, n_events, n_runs, word_cursor (the first time: pk_scan)
+        if (attempt > 0 && pt.seg) TCMI_HIP(ctx, hipMemcpyAsync(&d_tot->n_masked, &h_masked_long, 4, hipMemcpyHostToDevice, ctx->stream));    // (the plane kernel counts its reads again)
         (void)hipGetLastError();
         tcmi_prof_begin(ctx, TCMI_K_PACK);
         zero_drop(ctx, drop, drop_bytes);
@@ -1259,9 +1388,9 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
             hipLaunchKernelGGL(pk_scatter, dim3((unsigned)n_blk), dim3(PB), 0, ctx->stream, src, info, rd_seq, rd_pos, blk_sum, c_idx, c_pos, c_info, c_woff, c_seq);
         hipLaunchKernelGGL(pk_pack, dim3((unsigned)n_wg), dim3(PB), 0, ctx->stream, o, c_pos, c_info, c_woff, (uint32_t)nf,
                            (uint32_t)tot.n_words, (int)C, n_stages, ctx->stage_cap, d_tot, (int64_t)0);
-        if (min_bq)
+        if (drop_on)
             hipLaunchKernelGGL(pk_planes_bq, dim3((unsigned)((nf + PB - 1) / PB)), dim3(PB), 0, ctx->stream, src, o, c_idx, c_pos, c_info, c_woff, c_seq,
-                               (uint32_t)nf, (uint32_t)tot.n_words, d_tot, drop, min_bq);
+                               (uint32_t)nf, (uint32_t)tot.n_words, d_tot, drop, min_bq, pt);
         else
             hipLaunchKernelGGL(pk_planes, dim3((unsigned)((nf + PB - 1) / PB)), dim3(PB), 0, ctx->stream, src, o, c_idx, c_pos, c_info, c_woff, c_seq,
                                (uint32_t)nf, (uint32_t)tot.n_words, d_tot);
@@ -1286,6 +1415,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
             rs->arena_epoch = ctx->arena_epoch;
         }
         rs->f_chunks = tot.n_chunks; rs->f_words = (int64_t)tot.n_words + 4; rs->f_events = tot.n_events;
+        rs->n_masked = (int64_t)tot.n_masked;
         rs->dev_bytes = packed_bytes(tot);
         return TCMI_OK;
     }
@@ -1351,9 +1481,12 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     job->event_cap = (uint32_t)std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(1 << 20, cap / 2));
     PackOut o = {};
     const uint32_t min_bq = (uint32_t)ctx->min_bq;
+    rs->primers = ctx->primers;
+    const PrimerTab pt = tcmi_primer_args(rs->primers);
+    const bool drop_on = min_bq || pt.seg;
     uint32_t *drop = nullptr;
     size_t drop_bytes = 0;
-    if (const int rc = carve_blob(ctx, rs, (size_t)cap, job->word_cap, job->chunk_cap, job->event_cap, &o, min_bq ? &drop : nullptr, &drop_bytes)) return rc;
+    if (const int rc = carve_blob(ctx, rs, (size_t)cap, job->word_cap, job->chunk_cap, job->event_cap, &o, drop_on ? &drop : nullptr, &drop_bytes)) return rc;
     TCMI_HIP(ctx, hipMemsetAsync(d_tot, 0, sizeof(PackTotals), ctx->stream));
     FusedArgs a = {};
     a.stream = job->d_stream; a.stream_len = job->stream_len; a.blocks = static_cast<const BlockDesc *>(job->d_desc);
@@ -1364,6 +1497,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     a.o = o; a.blk_alg = blk_alg; a.blk_end = blk_end; a.tot = d_tot;
     a.flt = tcmi_filter_pack(ctx->flt); rs->flt = ctx->flt;
     a.drop = drop; a.min_bq = min_bq; rs->min_bq = (int32_t)min_bq;
+    a.pt = pt;
     const size_t pre_n = tcmi_align256(((size_t)nb + 1) * 8) / 8;
     if (prefix) { a.pre_rec = pre; a.pre_k = pre + pre_n; a.pre_w = pre + 2 * pre_n; }
     (void)hipGetLastError();
@@ -1378,8 +1512,13 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
         hipLaunchKernelGGL(pk_prefix, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const uint32_t *>(agg), 2, (int)nb, (int)nb, pre + pre_n);
         hipLaunchKernelGGL(pk_prefix, dim3(1), dim3(1024), 0, ctx->stream, reinterpret_cast<const uint32_t *>(agg) + 1, 2, (int)nb, (int)nb, pre + 2 * pre_n);
     }
-    if (min_bq) hipLaunchKernelGGL(pk_place_bq, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
+    if (drop_on) hipLaunchKernelGGL(pk_place_bq, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
     else hipLaunchKernelGGL(pk_place, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
+    if (pt.seg) {
+        PackSrc ls = {};
+        ls.stream = job->d_stream; ls.rec_off = job->d_rec; ls.mode = 1; ls.n = cap;
+        hipLaunchKernelGGL(pk_mask_long, dim3(64), dim3(PB), 0, ctx->stream, ls, job->gen_idx, d_tot, pt);
+    }
     hipLaunchKernelGGL(pk_pack, dim3((unsigned)n_wg), dim3(PB), 0, ctx->stream, o, job->c_pos, c_info, c_woff, 0u, 0u, 0, n_stages, ctx->stage_cap, d_tot,
                        balance ? slots : (int64_t)1 << 30);
     tcmi_prof_end(ctx, TCMI_K_PACK);
@@ -1440,6 +1579,7 @@ int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs,
     rs->n_piled = nf + (int64_t)tot.n_gen; rs->f_reads = nf; rs->alg_bytes = (int64_t)alg; rs->max_end = mend; rs->max_len = (int32_t)mlen;
     rs->s_reads = (int64_t)tot.n_gen;
     rs->n_filtered = (int64_t)tot.n_filtered;
+    rs->n_masked = (int64_t)tot.n_masked;
     rs->range_first = tot.range_first ? (int64_t)(tot.range_first - 1ull) : -1;
     rs->range_next = tot.range_next ? (int64_t)(tot.range_next - 1ull) : -1;
     rs->f_chunks = nf ? tot.n_chunks : 0; rs->f_words = nf ? (int64_t)tot.n_words + 4 : 0; rs->f_events = tot.n_events;

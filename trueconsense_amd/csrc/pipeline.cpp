@@ -339,6 +339,10 @@ int tcmi_pipeline_run_batched(tcmi_pipeline *p, int64_t n_items, const tcmi_read
         if (c->min_bq > 0)
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's base-quality floor is %d (--min-baseq): the array pipeline runs read sets "
                              "uploaded from flat arrays, which carry no QUAL", (int)c->min_bq);
+    for (const tcmi_ctx *c : p->slots)                          // (... and no primer mask)
+        if (c->primers)
+            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context holds a primer table (--primers): the array pipeline runs read sets uploaded "
+                             "from flat arrays, which the host packer packs without a primer mask");
     p->batch = batch;
     p->pos_stride = batch > 1 ? pos_stride : 0;
     const int64_t L_gpu = batch > 1 ? (int64_t)batch * pos_stride : L;   // positions one step covers
@@ -591,6 +595,10 @@ int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, con
                     const std::string why = it.file ? ctx->err : std::string("it was not read for the device decoder");
                     rc = tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: --min-baseq %d needs the device path (the host packer knows no base-quality floor), which this "
                                    "file left: %s", paths[i], (int)ctx->min_bq, why.c_str());
+                } else if (rc == TCMI_E_UNSUPPORTED && ctx->primers) {   // ... nor under a primer table: its packer knows no mask
+                    const std::string why = it.file ? ctx->err : std::string("it was not read for the device decoder");
+                    rc = tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: --primers needs the device path (the host packer knows no primer mask), which this "
+                                   "file left: %s", paths[i], why.c_str());
                 } else if (rc == TCMI_E_UNSUPPORTED) {           // the host reader takes it
                     rc = tcmi_bam_load(paths[i], r->host_threads, &hb);
                     if (!rc) rc = tcmi_bam_filter(hb, (int32_t)ctx->flt.min_mapq, ctx->flt.require, ctx->flt.exclude, nullptr);   // (the context's read filter)

@@ -84,6 +84,9 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
     if (ctx->min_bq > 0)                                        // (never a silently unfiltered result)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's base-quality floor is %d (--min-baseq): flat read arrays carry no QUAL and the host packer "
                          "knows no floor; only files decoded on the device are tallied under it", (int)ctx->min_bq);
+    if (ctx->primers)                                           // (... nor a silently unmasked one)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context holds a primer table of %d primers (--primers): the host packer knows no primer mask; only "
+                         "files decoded on the device are tallied under it", (int)ctx->primers->n_primers);
     int rc = TCMI_OK;
     for (int32_t b = 0; b < n_batch; ++b) {
         rc = check_reads(ctx, batch[b]);
@@ -209,6 +212,14 @@ int tcmi_readset_min_base_quality(const tcmi_readset *rs, int32_t *q)
 {
     if (!rs || !q) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
     *q = rs->min_bq;
+    return TCMI_OK;
+}
+
+int tcmi_readset_primers(const tcmi_readset *rs, int32_t *n_primers, int64_t *n_masked_reads)
+{
+    if (!rs) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    if (n_primers) *n_primers = rs->primers ? rs->primers->n_primers : 0;
+    if (n_masked_reads) *n_masked_reads = rs->n_masked;
     return TCMI_OK;
 }
 

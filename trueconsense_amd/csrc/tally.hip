@@ -213,7 +213,22 @@ __global__ __launch_bounds__(BLOCK) void tally_atomic_kernel(TallyArgs a)
 // Under a base-quality floor (s.min_bq > 0) a token whose quality is below it is skipped — no coverage, no letter, no X, no I —:
 // a matched base has its own QUAL byte, a D / N token that of the next query base (the query index at which the op starts), a query
 // index at or beyond l_seq quality 0; coverage is then added token by token.
-__global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint32_t *gen_idx, uint32_t n_gen, int32_t *counts, int64_t ld, int32_t L)
+// Under a primer table (pt; tcmi_ctx_set_primers) the read's head_end and tail_start are looked up once — its CIGAR's reference length
+// first, for the last column — and a token on a column outside [head_end, tail_start) is skipped likewise, column by column: a D / N
+// op that crosses the mask's edge loses only its masked columns, the I mark goes with the op's last column.  Coverage token by token
+// then too; without a floor a query index at or beyond l_seq is not skipped outside the mask.
+__device__ inline int32_t stream_seg_find(const int32_t *t, int32_t n, int32_t x, int32_t none)      // (the twin of pack_device.hip's seg_find)
+{
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (t[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo > 0 && x < t[n + lo - 1] ? t[2 * n + lo - 1] : none;
+}
+__global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint32_t *gen_idx, uint32_t n_gen, int32_t *counts, int64_t ld, int32_t L,
+                                                           tcmi_primer_tab pt)
 {
     const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -225,31 +240,47 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
     auto skipped = [&](int32_t q) { return (q < v.l_seq ? byte_at(qual + q) : 0u) < Q; };     // (Q = 0: nothing is)
     int32_t x = v.pos + shift_of(s, v.tid), y = 0;
     const int32_t x0 = x;
+    const bool table = pt.n_head + pt.n_tail != 0;
+    const bool by_token = Q != 0u || table;                     // coverage token by token
+    int32_t keep0 = INT32_MIN, keep1 = INT32_MAX;               // tokens on columns outside [keep0, keep1) are masked
+    if (table) {
+        int32_t span = 0;
+        for (uint32_t k = 0; k < v.n_cigar; ++k) {
+            const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k);
+            if (consumes_ref(c & 0xFu)) span += (int32_t)(c >> 4);
+        }
+        keep0 = stream_seg_find(pt.seg, pt.n_head, x0, x0);
+        keep1 = stream_seg_find(pt.seg + 3 * pt.n_head, pt.n_tail, x0 + span - 1, x0 + span);
+    }
+    auto masked = [&](int32_t col) { return col < keep0 || col >= keep1; };
     for (uint32_t k = 0; k < v.n_cigar; ++k) {
         const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k), op = c & 0xFu;
         const int32_t len = (int32_t)(c >> 4);
         if (consumes_ref(op)) {
             const bool ins = len > 0 && ins_after(v.cigar, v.n_cigar, k);
             bool skip_last = false;
-            if (Q && len > 0) skip_last = skipped(is_match(op) ? y + len - 1 : y);
+            if (by_token && len > 0) skip_last = skipped(is_match(op) ? y + len - 1 : y) || masked(x + len - 1);
             if (is_match(op)) {
                 for (int32_t j = lane; j < len; j += 64) {
                     const int32_t q = y + j;
-                    if (Q) { if (skipped(q)) continue; add(TCMI_COV, x + j); }
+                    if (by_token) { if (skipped(q) || masked(x + j)) continue; add(TCMI_COV, x + j); }
                     const uint32_t nib = q < v.l_seq ? nib_at(v.seq, q) : 15u;          // past SEQ -> 'N'
                     if (__popc(nib) == 1) { const int b = __ffs(nib) - 1; add(b == 0 ? TCMI_A : b == 1 ? TCMI_C : b == 2 ? TCMI_G : TCMI_T, x + j); }
                 }
-            } else if (!skip_last) {
-                if (Q) for (int32_t j = lane; j < len; j += 64) add(TCMI_COV, x + j);
+            } else if (!skipped(y)) {                                                 // (the floor skips a D / N op whole; Q = 0: never)
                 const int32_t nx = ins ? len - 1 : len;                              // "*+.." does not count X
-                if (op == 2) for (int32_t j = lane; j < nx; j += 64) add(TCMI_X, x + j);
+                for (int32_t j = lane; j < len; j += 64) {
+                    if (masked(x + j)) continue;
+                    if (by_token) add(TCMI_COV, x + j);
+                    if (op == 2 && j < nx) add(TCMI_X, x + j);
+                }
             }
             if (ins && !skip_last && lane == 0) add(TCMI_I, x + len - 1);
             x += len;
         }
         if (consumes_query(op)) y += len;
     }
-    if (Q == 0) for (int32_t p = x0 + lane; p < x; p += 64) add(TCMI_COV, p);
+    if (!by_token) for (int32_t p = x0 + lane; p < x; p += 64) add(TCMI_COV, p);
 }
 
 } // namespace
@@ -267,7 +298,7 @@ static int launch_tally_stream(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L,
     (void)hipGetLastError();
     tcmi_prof_begin(ctx, TCMI_K_TALLY_GENERAL);
     hipLaunchKernelGGL(tally_stream_kernel, dim3((unsigned)((rs->s_reads + 3) / 4)), dim3(256), 0, ctx->stream, s, rs->d_gen_idx, (uint32_t)rs->s_reads,
-                       d_counts, ld, (int32_t)L);
+                       d_counts, ld, (int32_t)L, tcmi_primer_args(rs->primers));
     tcmi_prof_end(ctx, TCMI_K_TALLY_GENERAL);
     TCMI_HIP(ctx, hipGetLastError());
     return TCMI_OK;

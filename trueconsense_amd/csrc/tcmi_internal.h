@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <string>
 #include <functional>
+#include <memory>
 #include <vector>
 
 #include "../../include/tcmi.h"
@@ -43,6 +44,27 @@ static inline tcmi_filter_words tcmi_filter_pack(const tcmi_read_filter &f)
 // the argument check of both entry points: TCMI_OK and *out filled, or TCMI_E_ARG (worded on `ctx`)
 int tcmi_read_filter_build(tcmi_ctx *ctx, int32_t min_mapq, uint32_t require_flags, uint32_t exclude_flags, tcmi_read_filter *out);
 
+// ---- amplicon primer mask (tcmi_ctx_set_primers; primer_table.h compiles the table) ----------------------------------------
+// The compiled table on the device, shared by the context that set it, its sub-range helper contexts and every read set built under
+// it (tally_stream_kernel masks a read set's long reads at tally time): freed with its last owner.  seg: int32 [3 * (n_head + n_tail)],
+// the head list as a[n_head] | b[n_head] | v[n_head] (a binary search walks one dense array), the tail list behind it likewise.
+struct tcmi_primer_dev {
+    int32_t *seg = nullptr;
+    int32_t n_head = 0, n_tail = 0, n_primers = 0;
+    ~tcmi_primer_dev() { if (seg) (void)hipFree(seg); }
+};
+// ... as the kernels take it: a trailing kernel argument / the tail of FusedArgs (tcmi_pack_src is full).  No table: all zero.
+struct tcmi_primer_tab {
+    const int32_t *seg;
+    int32_t n_head, n_tail;
+};
+static inline tcmi_primer_tab tcmi_primer_args(const std::shared_ptr<const tcmi_primer_dev> &p)
+{
+    tcmi_primer_tab t = {nullptr, 0, 0};
+    if (p) { t.seg = p->seg; t.n_head = p->n_head; t.n_tail = p->n_tail; }
+    return t;
+}
+
 struct tcmi_readset {
     uint64_t uid = 0;           // unique per upload (graphs are cached against it, not the pointer)
     int64_t n_reads = 0;        // as handed in
@@ -73,6 +95,10 @@ struct tcmi_readset {
     // ... and its base-quality floor (tcmi_ctx_set_min_base_quality; 0: none).  Above 0 the aligned set carries a third plane,
     // d_fdrop: one word per {lo, hi} pair of d_fseq (index = word / 2), bit b set when that read's token on that column is skipped
     int32_t min_bq = 0;
+    // ... and its primer table (tcmi_ctx_set_primers; null: none), which sets bits of the same plane, and the kept reads with a
+    // non-empty head or tail mask (tcmi_readset_primers).  The drop plane is there when either is.
+    std::shared_ptr<const tcmi_primer_dev> primers;
+    int64_t n_masked = 0;
     const uint32_t *d_gen_idx = nullptr;   // records of reads too long for the packed set (s_reads of them): tally_stream_kernel walks them in the stream
     int64_t s_reads = 0;
     // a read set of a block RANGE of a file (tcmi_readset_from_bamfile_blocks): where its first record starts when the range began
@@ -93,7 +119,7 @@ struct tcmi_readset {
     uint32_t *d_fevent = nullptr;// [f_events] position | TCMI_F_EV_*: tokens that are not plain A/C/G/T bases
     tcmi_fast_chunk *d_fchunk = nullptr;   // [f_chunks]
     uint32_t *d_fcovrun = nullptr;         // coverage runs of all chunks (tcmi_fast_chunk::run0 / n_runs)
-    uint32_t *d_fdrop = nullptr;           // [f_words / 2] the drop plane (min_bq > 0 only; in d_blob behind the events)
+    uint32_t *d_fdrop = nullptr;           // [f_words / 2] the drop plane (min_bq > 0 or a primer table; in d_blob behind the events)
     // general set
     int64_t g_reads = 0, n_rounds = 0, n_cigar = 0, n_seqw = 0;
     int32_t *d_pos = nullptr;   // [g_reads]
@@ -147,6 +173,7 @@ struct tcmi_ctx {
     size_t h_desc_cap = 0;
     tcmi_read_filter flt = {0, 0, 0};   // tcmi_ctx_set_read_filter: governs the read sets built from device-decoded record streams
     int32_t min_bq = 0;              // tcmi_ctx_set_min_base_quality: likewise; the flat-array entry points refuse while it is above 0
+    std::shared_ptr<const tcmi_primer_dev> primers;   // tcmi_ctx_set_primers: likewise, and refused likewise while set
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_one_sync_retried = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)

@@ -143,7 +143,7 @@ def check_range_anchors(ranges, inflated_bytes):
     return None
 
 
-def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to_root=False, read_filter=None, min_baseq=None):
+def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to_root=False, read_filter=None, min_baseq=None, primers=None):
     """BASELINE configs[4] from ONE FILE: every rank opens the same BAM, decodes on its GPU only the alignment records that start
     in its contiguous range of BGZF blocks (engine.Context.upload_bamfile(blocks=...): inflate, record index, pack), tallies
     them into a full-length int32 [7][ld] matrix and the matrices are summed — to every rank, or (to_root) to rank 0 only.
@@ -157,7 +157,7 @@ def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to
     own = ctx is None
     if own:
         ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)         # tally and collective on torch's stream
-    ctx.apply(read_filter, min_baseq)
+    ctx.apply(read_filter, min_baseq, primers)
     d = DeviceBam(path)
     try:
         import torch.distributed as dist
@@ -366,7 +366,7 @@ def _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks):
 
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
                             step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
-                            min_baseq=None):
+                            min_baseq=None, primers=None):
     """BASELINE configs[4] all the way: ONE BAM file over `world` ranks -> its consensus FASTA text on rank 0 (None on the others).
     What the ranks jointly replace is the reference's single pile-up pass (indexing.py:96-100), its insert candidates' region
     pile-ups (Events.py:47-82) and the walk (Sequences.py:168-322):
@@ -393,7 +393,8 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     read_filter = (min_mapq, require_flags, exclude_flags): every rank sets the same one on its context (its read set keeps it for
     step 3), and rank 0's host sweep of step 4 removes the failing records too.  min_baseq: the base-quality floor of the count
     matrix, on every rank's context (Context.set_min_base_quality; 0 sets no floor, None leaves what the context has); the insert
-    tokens keep their own quality rule."""
+    tokens keep their own quality rule.  primers = (rows, slack): the primer table of the count matrix, on every rank's context
+    likewise (Context.set_primers; no rows clears it, None leaves what the context has)."""
     import time
     import torch
     import torch.distributed as dist
@@ -414,7 +415,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                     ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)
                 if d is None:
                     d = DeviceBam(path)
-                ctx.apply(read_filter, min_baseq)
+                ctx.apply(read_filter, min_baseq, primers)
             except (TcmiError, OSError) as e:                        # this rank cannot even start: it must still meet the others in the reduce
                 err = (getattr(e, "code", _ffi_E_ARG), str(e))
             t = torch.zeros(n_words, dtype=torch.int32, device="cuda")
@@ -519,7 +520,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
 
 
 def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=True, name="S", device=0, return_parts=False, timings=None,
-                        split_sub=None, read_filter=None, min_baseq=None):
+                        split_sub=None, read_filter=None, min_baseq=None, primers=None):
     """BASELINE configs[4] at ANY world size on the ONE GPU there is: the ranks' steps of a `world`-GPU job played one after the other
     on one context — rank world-1 first, rank 0 (the root) last — each through tcmi_split_step exactly as a rank of the real job runs
     it (its own contiguous range of the file's BGZF blocks + the block behind it, the range table and the failure word behind the
@@ -538,7 +539,7 @@ def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=Tr
     ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)
     if split_sub is not None:                                        # (tcmi_split_step's sub-ranges per rank: 0 = auto, 1 = never)
         ctx.set_option("split_sub", int(split_sub))
-    ctx.apply(read_filter, min_baseq)                                # (every rank the same filter and base-quality floor)
+    ctx.apply(read_filter, min_baseq, primers)                                # (every rank the same filter and base-quality floor)
     d = DeviceBam(path)
     acc = torch.zeros(n_words, dtype=torch.int32, device="cuda")
     t = torch.zeros(n_words, dtype=torch.int32, device="cuda")

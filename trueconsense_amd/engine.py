@@ -86,6 +86,10 @@ class ReadSet:
         q = C.c_int32(0)
         check(lib().tcmi_readset_min_base_quality(handle, C.byref(q)))
         self.min_base_quality = q.value             # the base-quality floor the set was built under (Context.set_min_base_quality)
+        np_, nm = C.c_int32(0), C.c_int64(0)
+        check(lib().tcmi_readset_primers(handle, C.byref(np_), C.byref(nm)))
+        self.primers = np_.value                    # primers of the table the set was built under (Context.set_primers; 0: none) ...
+        self.primer_masked_reads = nm.value         # ... and its kept reads with a non-empty head or tail mask
 
     def ref_extents(self, n_ref):
         """Uploaded under a contig layout of n_ref references: per reference the kept reads' max end in its own coordinates."""
@@ -116,6 +120,7 @@ class Context:
 
     read_filter = None              # what set_read_filter / set_min_base_quality last set (a context made by the library starts without either)
     min_base_quality = 0
+    primers = 0                     # rows of the table set_primers last set
 
     def __init__(self, device=0, stream=None):
         """stream: a hipStream_t as an int (0 = the default stream) to run on, e.g. another Context's
@@ -183,12 +188,28 @@ class Context:
         check(lib().tcmi_ctx_set_min_base_quality(self.handle, int(q)), self.handle)
         self.min_base_quality = int(q)
 
-    def apply(self, read_filter=None, min_baseq=None):
-        """A job's read_filter = (min_mapq, require_flags, exclude_flags) and min_baseq onto this context; None leaves what it has."""
+    def set_primers(self, rows=None, slack=0):
+        """Amplicon primer mask (tcmi_ctx_set_primers; what `ivar trim` does to a BAM): rows = (start, end, reverse) on the count
+        matrix's axis, 0-based and end-exclusive, reverse false for a '+' (left) primer.  From now on every read set this context
+        builds from a device-decoded file skips the tokens a read has inside the primer at its head ('+' primers) or tail ('-'),
+        within `slack` columns of the primer's outer end.  While a table is set the flat-array entry points refuse with
+        E_UNSUPPORTED.  No rows: no table."""
+        rows = list(rows or [])
+        s_ = np.ascontiguousarray([r[0] for r in rows], np.int64)
+        e_ = np.ascontiguousarray([r[1] for r in rows], np.int64)
+        r_ = np.ascontiguousarray([int(r[2]) if isinstance(r[2], (bool, int, np.integer)) else int(r[2] == "-") for r in rows], np.int32)
+        check(lib().tcmi_ctx_set_primers(self.handle, len(rows), ptr(s_), ptr(e_), ptr(r_), int(slack)), self.handle)
+        self.primers = len(rows)
+
+    def apply(self, read_filter=None, min_baseq=None, primers=None):
+        """A job's read_filter = (min_mapq, require_flags, exclude_flags), min_baseq and primers = (rows, slack) (set_primers; no rows
+        clears the table) onto this context; None leaves what it has."""
         if read_filter is not None:
             self.set_read_filter(*read_filter_args(read_filter))
         if min_baseq is not None:
             self.set_min_base_quality(min_baseq)
+        if primers is not None:
+            self.set_primers(*primers)
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
@@ -658,7 +679,7 @@ class FileRunner:
     (tcmi_bam_load, `decode_threads` threads) and packed from its flat arrays.  `seconds` accumulates each stage's busy time."""
 
     def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None,
-                 min_baseq=0):
+                 min_baseq=0, primers=None):
         device = ctx.device if isinstance(ctx, Context) else int(ctx)
         self.mincov, self.amb = int(mincov), bool(include_ambig)
         h = C.c_void_p()
@@ -676,7 +697,7 @@ class FileRunner:
         # every context the same: the runner's host-reader fallbacks take the filter from them, and under a floor a file that leaves
         # the device path is refused, never tallied without it
         for c in self.contexts:
-            c.apply(read_filter, min_baseq or None)
+            c.apply(read_filter, min_baseq or None, primers)
 
     @property
     def contexts(self):

@@ -39,7 +39,7 @@ def Override_index_positions(index, override_data):
 def device_readset(ctx, path, blocks=None):
     """The device path, or why not: the file at `path` (blocks = (first, count): that range of its BGZF blocks) decoded and packed by
     ctx's device decoder -> ReadSet; None when the decoder declines the file (E_UNSUPPORTED) and the host reader may take it.  Under
-    a base-quality floor (ctx.min_base_quality) the host reader may not: the refusal is raised with its reason."""
+    a base-quality floor (ctx.min_base_quality) or a primer table (ctx.primers) the host reader may not: the refusal is raised with its reason."""
     d = DeviceBam(path)
     try:
         return ctx.upload_bamfile(d, blocks)
@@ -50,6 +50,9 @@ def device_readset(ctx, path, blocks=None):
         if q:
             raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--min-baseq %d needs the device path (the host packer knows no base-quality floor), "
                                  "which %s left: %s" % (q, path, e)) from e
+        if getattr(ctx, "primers", 0):              # (a context of before the table has none)
+            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--primers needs the device path (the host packer knows no primer mask), "
+                                 "which %s left: %s" % (path, e)) from e
         return None
     finally:
         d.close()
@@ -70,6 +73,7 @@ def build_counts(bamfile, ref, ctx=None):
         if rs is not None:
             try:
                 build_counts.last_reads, build_counts.last_filtered = int(rs.n_reads), int(rs.filtered)
+                build_counts.last_primer_masked = int(rs.primer_masked_reads)
                 return ctx.step(rs, max(ref_length, rs.max_end, 1), 0, True, want_counts=True)[3]
             finally:
                 rs.free()
@@ -83,6 +87,7 @@ def build_counts(bamfile, ref, ctx=None):
 
 build_counts.last_reads = 0         # alignment records of the file the last call read (the command line's --stats)
 build_counts.last_filtered = 0      # ... of which failed the read filter
+build_counts.last_primer_masked = 0 # piled-up reads with a non-empty primer mask (Context.set_primers)
 
 
 def BuildIndex(bamfile, ref):

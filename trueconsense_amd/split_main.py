@@ -28,7 +28,7 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import GetArgs, read_filter_of
+    from .TrueConsense import GetArgs, primers_of, read_filter_of
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
     torch.cuda.set_device(device)
@@ -50,7 +50,8 @@ def main(argv=None):
         rows = [{"start": int(r["start"]), "end": int(r["end"]), "strand": r.get("strand")} for r in gffdict.values()]
         _, refseq = fasta.read_first_record(a.reference)
         parts = td.consensus_split_bamfile(a.input, len(refseq), rows, a.coverage_level, a.noambiguity is False, a.samplename, rank, world,
-                                           device=device, return_parts=True, rccl_user=user, read_filter=read_filter_of(a), min_baseq=a.min_baseq)
+                                           device=device, return_parts=True, rccl_user=user, read_filter=read_filter_of(a), min_baseq=a.min_baseq,
+                                           primers=primers_of(a))
         if rank == 0:
             _, counts, toks = parts
             index = _state.IndexDict(counts)
