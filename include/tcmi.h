@@ -234,6 +234,54 @@ int  tcmi_ctx_set_primers(tcmi_ctx *ctx, int32_t n, const int64_t *start, const 
 int  tcmi_readset_primers(const tcmi_readset *rs, int32_t *n_primers, int64_t *n_masked_reads);
 int  tcmi_primers_compile(int32_t n, const int64_t *start, const int64_t *end, const int32_t *reverse, int32_t slack, int32_t seg_cap,
                           int32_t *head, int32_t *n_head, int32_t *tail, int32_t *n_tail, char *msg, int64_t msg_cap);
+/* ---- variant table (additive: what `ivar variants` reports; the reference has only the consensus and its -vcf) ---------------
+ * Every non-reference allele of a position at or above a frequency, with its depth, taken from the count matrix where it lies.
+ * All arithmetic is integer.  With the matrix (plane order TCMI_COV..TCMI_I), a reference byte string ref[0..n_ref) on the
+ * matrix's axis, min_af = num / den as a reduced fraction (0 <= num <= den, 1 <= den <= 1 000 000), min_alt_depth in 1..2^31-1
+ * and min_depth in 0..2^31-1:
+ *   position p (0-based) gives NO record when p >= n_ref, when ref[p] is not one of ACGTacgt (N, IUPAC codes, the zero bytes of a
+ *   contig layout's guard, columns beyond the FASTA) or when cov < max(min_depth, 1);
+ *   otherwise allele a of A, T, C, G, X, I that is not the upper-cased reference base gives one record iff
+ *   count[a] >= min_alt_depth and count[a] * den >= num * cov (64-bit products; an exact tie is in).
+ * X and I are never the reference allele: at most 5 records per position.  Records ascend by position, then by allele in plane
+ * order A, T, C, G, X, I; the order is part of the contract (no atomics take part: every run gives the same bytes).
+ * X is per column (a read that deletes this column); I is the insertion mark on the token IN FRONT of the insertion: the table says
+ * how many reads, not which bases (those come from the insert-candidate sweeps, with their own filters).
+ *   tcmi_variants_dev   the matrix and the reference are the caller's device pointers; d_counts as for tcmi_call_dev (4-byte aligned,
+ *                     any ld >= L) and only read; d_ref may be NULL when n_ref = 0.  d_records: room for `cap` records, aligned
+ *                     to 4 bytes, device or pinned host memory.  *n_found = the records the rule yields, whatever cap is; when
+ *                     *n_found > cap the first cap records are written, nothing behind them, and the call returns TCMI_E_ARG (as
+ *                     tcmi_readset_ins_entries does with its buffers); cap = 0 with d_records = NULL only counts.  Waits for the
+ *                     context's stream.
+ *   tcmi_variants       host convenience, shaped like tcmi_call: rows [L][7] and a host reference in, host records out
+ *   tcmi_ctx_set_variants   ref == NULL clears the setting; else the context keeps a device copy of ref[0..n_ref) and from now on
+ *                     every step it queues through tcmi_step_begin (tcmi_step, tcmi_bamfile_step on both of its routes) launches
+ *                     the table's three kernels behind the tally and in front of the call kernel (which may zero the matrix); the
+ *                     records go to pinned memory of the context sized 5 * n_ref, which cannot overflow.  While a setting is in force the
+ *                     array pipeline (tcmi_pipeline_run[_batched], whose steps ride along) refuses with TCMI_E_UNSUPPORTED and a
+ *                     message naming --variant-table, never skipping the table silently.  tcmi_split_step is not governed: its
+ *                     matrix is the caller's (tcmi_variants_dev / tcmi_variants).  No setting: exactly the launches of before.
+ *   tcmi_step_variants  the records of the last step that was ended, valid until the context's next step; TCMI_E_ARG when that step
+ *                     computed none
+ *   tcmi_variants_text  HOST, re-entrant, no GPU (and no error text: the code says it all): the ONE writer of the table's rows.
+ *                     Per record "REGION<TAB>POS<TAB>REF<TAB>ALT<TAB>ALT_DP<TAB>TOTAL_DP<TAB>ALT_FREQ<NL>": POS = pos - pos_offset + 1,
+ *                     REF = ref[pos] upper-cased (ref on the records' axis, n_ref bytes), ALT = the base letter, '*' for X, '+' for I,
+ *                     ALT_FREQ = ALT_DP / TOTAL_DP as a double printed with %.6f.  The header line (TCMI_VARIANTS_HEADER) is the
+ *                     caller's.  *len = the bytes the rows take.  text = NULL with cap = 0 is the sizing call: TCMI_OK and
+ *                     *len.  With a buffer, TCMI_E_ARG when the rows take more than cap (nothing useful is written; *len says how
+ *                     much).  Always TCMI_E_ARG for a record that does not fit the arguments (pos outside [pos_offset, n_ref),
+ *                     allele outside 1..6, cov <= 0).
+ * Argument errors are TCMI_E_ARG: den outside 1..10^6, num outside 0..den, min_alt_depth < 1, min_depth < 0, negative sizes. */
+typedef struct tcmi_variant { int32_t pos /* 0-based */, allele /* TCMI_A..TCMI_I */, count, cov; } tcmi_variant;
+#define TCMI_VARIANTS_HEADER "REGION\tPOS\tREF\tALT\tALT_DP\tTOTAL_DP\tALT_FREQ\n"
+int  tcmi_variants_dev(tcmi_ctx *ctx, const void *d_counts, int64_t L, int64_t ld, const void *d_ref, int64_t n_ref, int64_t num, int64_t den,
+                       int32_t min_alt_depth, int32_t min_depth, void *d_records, int64_t cap, int64_t *n_found);
+int  tcmi_variants(tcmi_ctx *ctx, const int32_t *counts, int64_t L, const uint8_t *ref, int64_t n_ref, int64_t num, int64_t den,
+                   int32_t min_alt_depth, int32_t min_depth, tcmi_variant *records, int64_t cap, int64_t *n_found);
+int  tcmi_ctx_set_variants(tcmi_ctx *ctx, const uint8_t *ref, int64_t n_ref, int64_t num, int64_t den, int32_t min_alt_depth, int32_t min_depth);
+int  tcmi_step_variants(tcmi_ctx *ctx, const tcmi_variant **records, int64_t *n);
+int  tcmi_variants_text(const tcmi_variant *records, int64_t n, const char *region, int64_t pos_offset, const uint8_t *ref, int64_t n_ref,
+                        char *text, int64_t cap, int64_t *len);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -250,7 +298,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_INFLATE = 6 /* device BGZF inflate */, TCMI_K_RECORDS = 7 /* device BAM record walk */,
        TCMI_K_CRC = 8 /* retired (always 0 since ABI 5): the blocks' CRC-32 is taken in bgzf_copy's flush, filed under TCMI_K_INFLATE_COPY */,
        TCMI_K_INFLATE_COPY = 9 /* device BGZF inflate, second kernel: tokens -> bytes (TCMI_K_INFLATE is the first: symbols -> tokens) */,
-       TCMI_K_NKERNELS = 10 };
+       TCMI_K_VARIANTS = 10 /* the variant table's three launches (count, scan, emit) as one bracket */,
+       TCMI_K_NKERNELS = 11 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);
@@ -571,6 +620,14 @@ int tcmi_filerunner_set_outputs(tcmi_filerunner *r, const char *ref_id, const ch
 int tcmi_filerunner_run_files(tcmi_filerunner *r, int64_t n, const char *const *paths, const char *const *names, const char *const *fasta,
                               const char *const *vcf, const char *const *gff, const char *const *doc, int64_t ref_len, int32_t mincov,
                               int include_ambig, int device_decode, int32_t *status, double *stage_seconds, int64_t *decoded_on);
+/* ... and per sample (an array or an entry may be NULL) its variant table.  tcmi_ctx_set_variants on every context of the runner first
+ * (tcmi_filerunner_ctx; the same setting on all, its reference the one of tcmi_filerunner_set_outputs, which also gives the rows
+ * their REGION): the GPU stage copies the step's records next to the call records, the walker writes header + tcmi_variants_text.  A
+ * sample the host reader took gets its table too.  n_variants (may be NULL): per sample the records written. */
+int tcmi_filerunner_run_files_table(tcmi_filerunner *r, int64_t n, const char *const *paths, const char *const *names, const char *const *fasta,
+                                    const char *const *vcf, const char *const *gff, const char *const *doc, const char *const *table, int64_t ref_len,
+                                    int32_t mincov, int include_ambig, int device_decode, int32_t *status, double *stage_seconds, int64_t *decoded_on,
+                                    int64_t *n_variants);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,9 @@
 
 Additive flags (not in the reference): --device N (GPU ordinal), --stats FILE (JSON timings), the read filter
 --min-mapq N / --require-flags F / --exclude-flags F (samtools view -q / -f / -F: a record that fails is ignored as an unmapped
-one is; the reference tallies every mapped record), and
+one is; the reference tallies every mapped record), the variant table --variant-table FILE [--min-af F] [--min-alt-depth N]
+[--variant-min-depth N] (per position every non-reference allele at or above a frequency, from the count matrix the consensus is
+called from; --batch: the manifest's 7th column), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -62,6 +64,75 @@ def _range_arg(parser, flag, hi):
             parser.error(f"{flag} takes an integer from 0 to {hi} (decimal or 0x...), not {color.YELLOW}{text}{color.END}.")
         return v
     return check
+
+
+def _min_af_arg(parser):
+    """argparse `type=` callable of --min-af: text -> fractions.Fraction, exact ("0.03", "3e-2" and "3/100" are one value); refused
+    (parser.error, exit code 2) unless 0 <= F <= 1 with a reduced denominator of at most 10^6."""
+    def check(text):
+        from fractions import Fraction
+        from .engine import min_af_fraction
+        try:
+            return Fraction(*min_af_fraction(text.strip()))
+        except ValueError as e:
+            parser.error(f"--min-af takes a frequency from 0 to 1 (a decimal or a fraction n/d, d up to 1000000): {color.YELLOW}{e}{color.END}.")
+    return check
+
+
+def _count_arg(parser, flag, lo):
+    """argparse `type=` callable: an integer in lo..2^31-1 (else parser.error, exit code 2)."""
+    def check(text):
+        try:
+            v = int(text, 10)
+        except ValueError:
+            v = lo - 1
+        if not lo <= v <= 2 ** 31 - 1:
+            parser.error(f"{flag} takes an integer from {lo} to {2 ** 31 - 1}, not {color.YELLOW}{text}{color.END}.")
+        return v
+    return check
+
+
+def variants_of(a):
+    """The parsed namespace's table thresholds as keyword arguments of Context.variants / set_variants."""
+    return dict(min_af=a.min_af, min_alt_depth=a.min_alt_depth, min_depth=a.variant_min_depth)
+
+
+def write_variant_table(path, parts):
+    """--variant-table: the header line, then for every (records, region, reference on the records' axis, pos_offset) its rows."""
+    from .engine import VARIANTS_HEADER, variants_text
+    text = VARIANTS_HEADER + "".join(variants_text(recs, region, ref, off) for recs, region, ref, off in parts)
+    with open(path, "w") as out:
+        out.write(text)
+
+
+def _names_a_table(line):
+    """does this manifest line's 7th column name a variant table ("-" or empty: none)?"""
+    f = line.rstrip("\n").split("\t")
+    return len(f) > 6 and f[6] not in ("", "-")
+
+
+def read_manifest(a):
+    """--batch: the manifest's samples as [BAM, name, FASTA, VCF, GFF, TSV, variant table] (None: not wanted).  A malformed line, a
+    missing BAM, or table thresholds without any 7th column print why and exit, as the flags' own checks do."""
+    rows = []
+    with open(a.batch) as fh:
+        for ln, line in enumerate(fh, 1):
+            line = line.rstrip("\n")
+            if not line or line.startswith("#"):
+                continue
+            f = line.split("\t")
+            if len(f) < 3:
+                print(f'{a.batch}:{ln}: need at least "BAM<TAB>name<TAB>FASTA". Exiting...')
+                sys.exit(1)
+            f += [""] * (7 - len(f))
+            if not os.path.isfile(f[0]):
+                print(f'"{f[0]}" is not a file. Exiting...')
+                sys.exit(-1)
+            rows.append([f[0], f[1], f[2]] + [None if x in ("", "-") else x for x in f[3:7]])
+    if a.variant_thresholds_given and not any(r[6] for r in rows):
+        print("--min-af / --min-alt-depth / --variant-min-depth need a variant table: no line of the manifest has a 7th column. Exiting...")
+        sys.exit(1)
+    return rows
 
 
 def read_filter_of(a):
@@ -160,6 +231,17 @@ def GetArgs(givenargs):
                                                "(ivar trim, samtools ampliconclip); needs the device decoder")))
     additive.append((("--primer-slack",), dict(type=_range_arg(parser, "--primer-slack", 1000), default=0, metavar="N",
                                                help="a read may start up to N columns in front of a primer (end behind it) and still be masked")))
+    additive.append((("--variant-table",), dict(type=str, default=None, metavar="File",
+                                                help="also write per position every non-reference allele (A, T, C, G, * deletion, + insertion\n"
+                                                     "mark) at or above --min-af, tab-separated: REGION POS REF ALT ALT_DP TOTAL_DP ALT_FREQ\n"
+                                                     "(ivar variants), from the count matrix the consensus is called from")))
+    additive.append((("--min-af",), dict(type=_min_af_arg(parser), default=None, metavar="F",
+                                         help="minimum allele frequency of the variant table, 0..1, a decimal or n/d (default 0.03)")))
+    additive.append((("--min-alt-depth",), dict(type=_count_arg(parser, "--min-alt-depth", 1), default=None, metavar="N",
+                                                help="minimum reads with the allele (default 1)")))
+    additive.append((("--variant-min-depth",), dict(type=_count_arg(parser, "--variant-min-depth", 0), default=None, metavar="N",
+                                                    help="minimum coverage of a position of the variant table (ivar variants -m; default 10;\n"
+                                                         "independent of -cov)")))
     # (is this the --batch form?  asked of a small parser of its own: "--batch=FILE" and argparse's abbreviations count too)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--batch", default=None)
@@ -171,7 +253,17 @@ def GetArgs(givenargs):
             if req:
                 kw["required"] = not (batch and flags[0] in ("--input", "--output", "--samplename"))
             group.add_argument(*flags, **kw)
-    return parser.parse_args(givenargs)
+    a = parser.parse_args(givenargs)
+    from fractions import Fraction
+    a.variant_thresholds_given = any(v is not None for v in (a.min_af, a.min_alt_depth, a.variant_min_depth))
+    if a.batch is not None and a.variant_table is not None:
+        parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
+    if a.batch is None and a.variant_table is None and a.variant_thresholds_given:
+        parser.error("--min-af / --min-alt-depth / --variant-min-depth need --variant-table.")
+    a.min_af = Fraction(3, 100) if a.min_af is None else a.min_af
+    a.min_alt_depth = 1 if a.min_alt_depth is None else a.min_alt_depth
+    a.variant_min_depth = 10 if a.variant_min_depth is None else a.variant_min_depth
+    return a
 
 
 def _spawn(cmds, envs):
@@ -204,10 +296,11 @@ def _spawn(cmds, envs):
     return max((abs(r) for r in rcs), default=0)
 
 
-def _child_argv(a, single):
+def _child_argv(a, single, tables=True):
     """The command line of a --gpus child, built from the PARSED namespace (argparse takes abbreviations, so the spelling the user typed
     cannot be filtered by name): the reference's flags as they were understood, never --gpus / --batch / --device / --stats — the
-    caller adds its own — plus an explicit `--gpus 1`, so that a child can never deal itself out again."""
+    caller adds its own — plus an explicit `--gpus 1`, so that a child can never deal itself out again.  tables: the child writes a
+    variant table (a --batch shard with a 7th column somewhere); one that writes none gets no thresholds, which alone are an error."""
     out = ["-ref", a.reference, "-gff", a.features, "-cov", str(a.coverage_level), "-t", str(a.threads)]
     if a.noambiguity:
         out.append("-noambig")
@@ -220,7 +313,11 @@ def _child_argv(a, single):
         out += ["--min-baseq", str(a.min_baseq)]
     if a.primers:                                   # (the primer mask, likewise: both flags or neither)
         out += ["--primers", a.primers, "--primer-slack", str(a.primer_slack)]
+    if tables and (a.variant_thresholds_given or a.variant_table):     # (the table's thresholds, likewise; --batch children find their tables in the manifest)
+        out += ["--min-af", str(a.min_af), "--min-alt-depth", str(a.min_alt_depth), "--variant-min-depth", str(a.variant_min_depth)]
     if single:
+        if a.variant_table:
+            out += ["--variant-table", a.variant_table]
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]
         for flag, v in (("-vcf", a.variants), ("-doc", a.depth_of_coverage), ("-ogff", a.output_gff)):
             if v is not None:
@@ -240,6 +337,10 @@ def run_gpus(a):
     one_gpu = os.environ.get("TCMI_SPLIT_ONE_GPU") == "1"              # (rehearsal on a one-GPU box: every child on GPU 0)
     if a.batch:
         rows = [ln for ln in open(a.batch).read().split("\n") if ln.strip() and not ln.startswith("#")]
+        # the thresholds without any table: checked once, over the whole manifest, before anything is dealt out (a shard may well name none)
+        if a.variant_thresholds_given and not any(_names_a_table(ln) for ln in rows):
+            print("--min-af / --min-alt-depth / --variant-min-depth need a variant table: no line of the manifest has a 7th column. Exiting...")
+            return 1
         with tempfile.TemporaryDirectory(prefix="tcmi_gpus_") as tmp:
             cmds, envs = [], []
             for k in range(n):
@@ -249,7 +350,8 @@ def run_gpus(a):
                 shard = os.path.join(tmp, "shard%d.tsv" % k)
                 with open(shard, "w") as fh:
                     fh.write("\n".join(mine) + "\n")
-                cmd = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "--batch", shard, "--device", str(0 if one_gpu else k)] + _child_argv(a, False)
+                cmd = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "--batch", shard, "--device", str(0 if one_gpu else k)] + \
+                    _child_argv(a, False, tables=any(_names_a_table(ln) for ln in mine))
                 if a.stats:
                     cmd += ["--stats", "%s.gpu%d" % (a.stats, k)]
                 cmds.append(cmd)
@@ -278,21 +380,8 @@ def run_batch(a):
     if a.index_override:
         print("--index-override goes with a single sample (-i), not with --batch. Exiting...")
         sys.exit(1)
-    rows = []
-    with open(a.batch) as fh:
-        for ln, line in enumerate(fh, 1):
-            line = line.rstrip("\n")
-            if not line or line.startswith("#"):
-                continue
-            f = line.split("\t")
-            if len(f) < 3:
-                print(f'{a.batch}:{ln}: need at least "BAM<TAB>name<TAB>FASTA". Exiting...')
-                sys.exit(1)
-            f += [""] * (6 - len(f))
-            if not os.path.isfile(f[0]):
-                print(f'"{f[0]}" is not a file. Exiting...')
-                sys.exit(-1)
-            rows.append([f[0], f[1], f[2]] + [None if x in ("", "-") else x for x in f[3:6]])
+    rows = read_manifest(a)
+    tables = [r[6] for r in rows] if any(r[6] for r in rows) else None
     IndexGff = Gffindex(a.features)
     gffrows = list(IndexGff.index_dict(seqid="S").values())       # (the runner puts each sample's name there: TrueConsense.py:240)
     refID, refseq = fasta.read_first_record(a.reference)
@@ -302,12 +391,12 @@ def run_batch(a):
     runner = FileRunner(int(os.environ.get("TCMI_DEVICE", "0")), gffrows, a.coverage_level, a.noambiguity is False,
                         decoders=min(4, max(1, cores // 4)), decode_threads=max(1, cores // 2), walkers=min(4, max(1, cores // 4)),
                         gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a),
-                        min_baseq=a.min_baseq, primers=prm)
+                        min_baseq=a.min_baseq, primers=prm, variants=dict(variants_of(a), ref=refseq) if tables else None)
     runner.set_outputs(refID, refseq, vcf_header(date.today().strftime("%Y%m%d"), sys.argv[1:], a.reference, refID), IndexGff.header.raw_text,
                        [gff_row_columns(r) for r in gffrows])
     try:
         runner.run_files([r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows],
-                         [r[5] for r in rows], ref_len=len(refseq))
+                         [r[5] for r in rows], ref_len=len(refseq), table=tables)
     except Exception:                                                # every failed sample is named; the first one's error (what the reference would raise) goes on up: non-zero exit
         failed = [(rows[i][1], int(c)) for i, c in enumerate(getattr(runner, "last_status", [])) if int(c) != 0]
         for nm, code in failed:
@@ -319,7 +408,7 @@ def run_batch(a):
         if a.stats:
             with open(a.stats, "w") as fh:
                 json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "primers": len(prm[0]) if prm else 0,
-                           "stage_busy_seconds": runner.seconds,
+                           "variant_records": int(getattr(runner, "variant_records", 0)), "stage_busy_seconds": runner.seconds,
                            "decoded_on": runner.decoded_on, "status": [int(x) for x in getattr(runner, "last_status", [])]}, fh)
         runner.close()
 
@@ -409,6 +498,13 @@ def _single_sample(a, flt, t):
 
     if a.depth_of_coverage is not None:
         BuildCoverage(indexDict, a.depth_of_coverage)
+    n_variants = 0
+    if a.variant_table is not None:                 # from the counts the consensus is called from (behind --index-override)
+        from .io import fasta
+        refID, refseq = fasta.read_first_record(a.reference)
+        recs = _state.default_context().variants(indexDict.counts, refseq, **variants_of(a))
+        write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
+        n_variants = len(recs)
 
     IncludeAmbig = a.noambiguity is False
     WriteOutputs(a.coverage_level, indexDict, GffDict, bam, IncludeAmbig, a.variants, a.samplename, a.reference,
@@ -421,7 +517,7 @@ def _single_sample(a, flt, t):
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
-                       "bam_bytes": os.path.getsize(a.input)}, fh)
+                       "variant_records": n_variants, "bam_bytes": os.path.getsize(a.input)}, fh)
 
 
 if __name__ == "__main__":

@@ -110,20 +110,35 @@ def _name_slot_overrun(err, host, header_names):
     return ContigError('read "%s" on contig "%s" ends past the end of the contig\'s slot (its length + %d positions)' % (read, contig, GUARD))
 
 
+def axis_reference(records, header_names, shift, axis_len):
+    """The reference on the layout's axis (what the variant table reads): every kept contig's sequence at its shift, zero bytes
+    elsewhere — guard columns and the slots' padding give no record."""
+    index = {n: t for t, n in enumerate(header_names)}
+    ref = np.zeros(max(int(axis_len), 1), np.uint8)
+    for rid, seq in records:
+        s = int(shift[index[rid]])
+        ref[s:s + len(seq)] = np.frombuffer(seq.encode("latin-1"), np.uint8)
+    return ref
+
+
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None):
+                 info=None, min_baseq=0, primers=None, variants=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
     exclude_flags): extents, `dropped` and the host BamFile see the passing records only; info (a dict) receives "reads" (the
     file's records) and "reads_filtered".  min_baseq: the base-quality floor of the count matrix (Context.set_min_base_quality);
     above 0 a file the device decoder declines is refused (the host packer knows no floor).  primers = (rows on the AXIS, slack)
-    (Context.set_primers; io.primers.rows_for_layout shifts a BED's rows): likewise; info then receives "reads_primer_masked" too."""
+    (Context.set_primers; io.primers.rows_for_layout shifts a BED's rows): likewise; info then receives "reads_primer_masked" too.
+    variants = the keyword arguments of Context.set_variants (ref: the reference on the axis, axis_reference): the step also lists
+    the variant table's records, which info receives as "variant_table"."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
     ctx.set_min_base_quality(min_baseq)
     ctx.set_primers(*(primers or ()))
+    if variants:
+        ctx.set_variants(**variants)
     host = None
     try:
         rs = device_readset(ctx, path)              # (the floor it refuses under is the one just set)
@@ -140,6 +155,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
                 if primers:                                     # (only under a table: the dict of before otherwise)
                     info["reads_primer_masked"] = rs.primer_masked_reads
             plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
+            if variants and info is not None:
+                info["variant_table"] = ctx.step_variants()
         finally:
             rs.free()
     finally:
@@ -147,13 +164,15 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_read_filter()
         ctx.set_min_base_quality()
         ctx.set_primers()
+        if variants:
+            ctx.set_variants()
     return plain, alt, flags, counts, ext, dropped, host
 
 
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import primers_of, read_filter_of
+    from .TrueConsense import primers_of, read_filter_of, variants_of, write_variant_table
     flt, seen = read_filter_of(a), {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -165,10 +184,14 @@ def run(a):
     prm = primers_of(a, (hdr_names, shift))
     seen["primers"] = len(prm[0]) if prm else 0
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
+    axis_ref = axis_reference(records, hdr_names, shift, axis_len) if a.variant_table is not None else None
+    var = dict(variants_of(a), ref=axis_ref) if axis_ref is not None else None
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
                                                                  threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
-                                                                 min_baseq=a.min_baseq, primers=prm)
+                                                                 min_baseq=a.min_baseq, primers=prm, variants=var)
     seen.setdefault("reads_primer_masked", 0)
+    table = seen.pop("variant_table", None)
+    seen["variant_records"] = 0 if table is None else len(table)
 
     # every contig's slice of the call records (the call is position-local: a slice's records are the split run's)
     per = []
@@ -225,6 +248,11 @@ def run(a):
     if a.depth_of_coverage is not None:
         with open(a.depth_of_coverage, "w") as out:
             out.write("".join(doc))
+    if table is not None:                           # one file, the contigs in axis order; rows carry the contig's name and its own positions
+        parts = []
+        for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]):
+            parts.append((table[(table["pos"] >= s) & (table["pos"] < s + len(seq))], rid, axis_ref, s))
+        write_variant_table(a.variant_table, parts)
     with open(a.output, "w") as out:
         out.write("".join(fa))
     return dict({"contigs": len(records), "dropped_reads": int(dropped)}, **seen)

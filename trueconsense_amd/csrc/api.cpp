@@ -203,6 +203,10 @@ int tcmi_ctx_destroy(tcmi_ctx *c)
     if (c->tok_host) (void)hipHostFree(c->tok_host);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->h_desc) (void)hipHostFree(c->h_desc);
+    if (c->d_var_ref) (void)hipFree(c->d_var_ref);
+    if (c->d_var_scr) (void)hipFree(c->d_var_scr);
+    if (c->h_var_rec) (void)hipHostFree(c->h_var_rec);
+    if (c->h_var_tot) (void)hipHostFree(c->h_var_tot);
     if (c->step_done) (void)hipEventDestroy(c->step_done);
     if (c->ev_after_sym) (void)hipEventDestroy(c->ev_after_sym);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -611,7 +615,155 @@ int tcmi_call(tcmi_ctx *ctx, const int32_t *counts, int64_t L, int32_t mincov, i
     return rc;
 }
 
-// The launches of one step on ctx->stream: [memset] tally, call.  When the counts are not wanted on the host the
+// ---- variant table (variants.hip) --------------------------------------------------------------
+} // extern "C"
+
+static int var_rule_build(tcmi_ctx *ctx, int64_t num, int64_t den, int32_t min_alt_depth, int32_t min_depth, tcmi_var_rule *out)
+{
+    if (den < 1 || den > 1000000) return tcmi_fail(ctx, TCMI_E_ARG, "variants: the frequency's denominator %lld is outside 1..1000000", (long long)den);
+    if (num < 0 || num > den) return tcmi_fail(ctx, TCMI_E_ARG, "variants: the frequency %lld / %lld is outside 0..1", (long long)num, (long long)den);
+    if (min_alt_depth < 1) return tcmi_fail(ctx, TCMI_E_ARG, "variants: min_alt_depth %d is below 1", (int)min_alt_depth);
+    if (min_depth < 0) return tcmi_fail(ctx, TCMI_E_ARG, "variants: min_depth %d is negative", (int)min_depth);
+    out->num = num; out->den = den; out->min_alt_depth = min_alt_depth; out->min_depth = min_depth;
+    return TCMI_OK;
+}
+
+// blk_cnt | blk_base of the table's launches for `blocks` workgroups, and the pinned words of the totals (grow-only; growing waits
+// for the stream: nothing queued may still use the old scratch)
+static int var_scratch(tcmi_ctx *ctx, int64_t blocks)
+{
+    if (!ctx->h_var_tot) {
+        TCMI_HIP(ctx, hipHostMalloc((void **)&ctx->h_var_tot, 64, hipHostMallocDefault));
+        std::memset(ctx->h_var_tot, 0, 64);
+    }
+    if (blocks <= ctx->var_scr_blocks) return TCMI_OK;
+    if (ctx->d_var_scr) { TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->d_var_scr); ctx->d_var_scr = nullptr; ctx->var_scr_blocks = 0; }
+    TCMI_HIP(ctx, hipMalloc((void **)&ctx->d_var_scr, (size_t)blocks * 12 + 256));
+    ctx->var_scr_blocks = blocks;
+    return TCMI_OK;
+}
+
+static void var_job_scratch(tcmi_ctx *ctx, tcmi_var_job *j)
+{   // (blk_base first: 8-byte words at the head of the allocation)
+    j->blk_base = reinterpret_cast<unsigned long long *>(ctx->d_var_scr);
+    j->blk_cnt = reinterpret_cast<uint32_t *>(ctx->d_var_scr + (size_t)ctx->var_scr_blocks * 8);
+}
+
+// a step's table: the context's matrix, reference and rule; records and total into the context's pinned memory
+static int enqueue_variants(tcmi_ctx *ctx, int64_t L)
+{
+    if (std::min(L, ctx->var_n_ref) <= 0) return TCMI_OK;     // (a setting with an empty reference: nothing to launch, no record)
+    tcmi_var_job j = {};
+    var_job_scratch(ctx, &j);
+    j.counts = ctx->d_counts; j.L = L; j.ld = ctx->ws_ld; j.ref = ctx->d_var_ref; j.n_ref = ctx->var_n_ref; j.rule = ctx->var_rule;
+    j.total = ctx->h_var_tot; j.records = ctx->h_var_rec; j.cap = 5 * ctx->var_n_ref;
+    return tcmi_launch_variants(ctx, j);
+}
+
+extern "C" {
+
+int tcmi_variants_dev(tcmi_ctx *ctx, const void *d_counts, int64_t L, int64_t ld, const void *d_ref, int64_t n_ref, int64_t num, int64_t den,
+                      int32_t min_alt_depth, int32_t min_depth, void *d_records, int64_t cap, int64_t *n_found)
+{
+    if (!ctx || !d_counts || !n_found) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
+    *n_found = 0;
+    if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld");
+    if (L > INT32_MAX - 1024) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "L too large");
+    if (n_ref < 0 || cap < 0 || (n_ref > 0 && !d_ref) || (cap > 0 && !d_records))
+        return tcmi_fail(ctx, TCMI_E_ARG, "variants: negative size, or a size without its buffer (n_ref=%lld cap=%lld)", (long long)n_ref, (long long)cap);
+    if (reinterpret_cast<uintptr_t>(d_counts) % 4 || reinterpret_cast<uintptr_t>(d_records) % 4)
+        return tcmi_fail(ctx, TCMI_E_ARG, "d_counts and d_records must be aligned to 4 bytes");
+    tcmi_var_job j = {};
+    int rc = var_rule_build(ctx, num, den, min_alt_depth, min_depth, &j.rule);
+    if (rc) return rc;
+    const int64_t Lv = std::min(L, n_ref);
+    if (Lv == 0) return TCMI_OK;                              // (no position has a reference base)
+    TCMI_HIP(ctx, hipSetDevice(ctx->device));
+    const int64_t blocks = (Lv + 255) / 256;
+    rc = var_scratch(ctx, blocks);
+    if (rc) return rc;
+    var_job_scratch(ctx, &j);
+    j.counts = (const int32_t *)d_counts; j.L = L; j.ld = ld; j.ref = (const uint8_t *)d_ref; j.n_ref = n_ref;
+    j.total = ctx->h_var_tot + 1; j.records = (tcmi_variant *)d_records; j.cap = cap;
+    rc = tcmi_launch_variants(ctx, j);
+    if (rc) return rc;
+    TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *n_found = (int64_t)ctx->h_var_tot[1];
+    if (*n_found > cap && (cap > 0 || d_records))
+        return tcmi_fail(ctx, TCMI_E_ARG, "variants: %lld records, room for %lld (the first %lld were written)", (long long)*n_found, (long long)cap, (long long)cap);
+    return TCMI_OK;
+}
+
+int tcmi_variants(tcmi_ctx *ctx, const int32_t *counts, int64_t L, const uint8_t *ref, int64_t n_ref, int64_t num, int64_t den,
+                  int32_t min_alt_depth, int32_t min_depth, tcmi_variant *records, int64_t cap, int64_t *n_found)
+{
+    if (!ctx || !counts || !n_found) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
+    *n_found = 0;
+    if (L <= 0) return tcmi_fail(ctx, TCMI_E_ARG, "L must be positive");
+    if (n_ref < 0 || cap < 0 || (n_ref > 0 && !ref) || (cap > 0 && !records))
+        return tcmi_fail(ctx, TCMI_E_ARG, "variants: negative size, or a size without its buffer (n_ref=%lld cap=%lld)", (long long)n_ref, (long long)cap);
+    tcmi_var_rule rule;
+    int rc = var_rule_build(ctx, num, den, min_alt_depth, min_depth, &rule);
+    if (rc) return rc;
+    rc = ensure_ws(ctx, L);
+    if (rc) return rc;
+    ctx->counts_clean = false;
+    rc = tcmi_counts_upload(ctx, counts, L, ctx->ws_ld, ctx->d_counts);
+    if (rc) return rc;
+    const int64_t Lv = std::min(L, n_ref), room = std::min(cap, 5 * Lv);       // (5 per position: more than `room` records means more than cap)
+    uint8_t *d_ref = nullptr;
+    tcmi_variant *d_rec = nullptr;
+    if (Lv > 0) TCMI_HIP(ctx, hipMalloc((void **)&d_ref, (size_t)Lv));
+    hipError_t e = Lv > 0 ? hipMemcpy(d_ref, ref, (size_t)Lv, hipMemcpyHostToDevice) : hipSuccess;
+    if (e == hipSuccess && room > 0) e = hipMalloc((void **)&d_rec, (size_t)room * sizeof(tcmi_variant));
+    if (e != hipSuccess) rc = tcmi_fail(ctx, TCMI_E_HIP, "variants: device buffers: %s", hipGetErrorString(e));
+    if (!rc) rc = tcmi_variants_dev(ctx, ctx->d_counts, L, ctx->ws_ld, d_ref, Lv, num, den, min_alt_depth, min_depth, d_rec, room, n_found);
+    if ((rc == TCMI_OK || (rc == TCMI_E_ARG && *n_found > room)) && room > 0) {
+        e = hipMemcpy(records, d_rec, (size_t)std::min(room, *n_found) * sizeof(tcmi_variant), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = tcmi_fail(ctx, TCMI_E_HIP, "variants: record download failed: %s", hipGetErrorString(e));
+    }
+    if (d_ref) (void)hipFree(d_ref);
+    if (d_rec) (void)hipFree(d_rec);
+    if (rc == TCMI_OK && *n_found > cap && (cap > 0 || records))
+        return tcmi_fail(ctx, TCMI_E_ARG, "variants: %lld records, room for %lld", (long long)*n_found, (long long)cap);
+    return rc;
+}
+
+int tcmi_ctx_set_variants(tcmi_ctx *c, const uint8_t *ref, int64_t n_ref, int64_t num, int64_t den, int32_t min_alt_depth, int32_t min_depth)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    if (c->step_L > 0) return tcmi_fail(c, TCMI_E_ARG, "tcmi_ctx_set_variants between tcmi_step_begin and tcmi_step_end");
+    if (!ref) { c->var_on = false; c->var_valid = false; return TCMI_OK; }       // (the buffers stay for the next setting)
+    tcmi_var_rule rule;
+    const int rc = var_rule_build(c, num, den, min_alt_depth, min_depth, &rule);
+    if (rc) return rc;
+    if (n_ref < 0 || n_ref > INT32_MAX - 1024) return tcmi_fail(c, TCMI_E_ARG, "variants: n_ref %lld is negative or too large", (long long)n_ref);
+    TCMI_HIP(c, hipSetDevice(c->device));
+    TCMI_HIP(c, hipStreamSynchronize(c->stream));             // (nothing queued may still read the reference or write the records)
+    c->var_on = false; c->var_valid = false;
+    if (c->d_var_ref) { (void)hipFree(c->d_var_ref); c->d_var_ref = nullptr; }
+    if (c->h_var_rec) { (void)hipHostFree(c->h_var_rec); c->h_var_rec = nullptr; }
+    c->var_n_ref = 0;
+    const int r2 = var_scratch(c, (n_ref + 255) / 256);
+    if (r2) return r2;
+    TCMI_HIP(c, hipMalloc((void **)&c->d_var_ref, (size_t)n_ref + 1));
+    if (n_ref) TCMI_HIP(c, hipMemcpy(c->d_var_ref, ref, (size_t)n_ref, hipMemcpyHostToDevice));
+    TCMI_HIP(c, hipHostMalloc((void **)&c->h_var_rec, (size_t)(5 * n_ref + 1) * sizeof(tcmi_variant), hipHostMallocDefault));
+    c->var_n_ref = n_ref; c->var_rule = rule; c->var_on = true;
+    return TCMI_OK;
+}
+
+int tcmi_step_variants(tcmi_ctx *c, const tcmi_variant **records, int64_t *n)
+{
+    if (!c || !records || !n) return tcmi_fail(c, TCMI_E_ARG, "null argument");
+    *records = nullptr; *n = 0;
+    if (c->step_L > 0) return tcmi_fail(c, TCMI_E_ARG, "tcmi_step_variants: the context's step has not been ended");
+    if (!c->var_valid) return tcmi_fail(c, TCMI_E_ARG, "tcmi_step_variants: the last step computed no variant table (tcmi_ctx_set_variants)");
+    *records = c->h_var_rec; *n = c->var_n;
+    return TCMI_OK;
+}
+
+// The launches of one step on ctx->stream: [memset] tally, [the variant table's three,] call.  When the counts are not wanted on the host the
 // call kernel zeroes them behind itself and the next step into this workspace needs no memset.  The call records
 // (3 bytes per position) go straight to the pinned host buffer: the kernel's own stores cross PCIe, which saves a
 // separate copy and one launch boundary per step.
@@ -623,6 +775,10 @@ static int enqueue_step(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int32_
     if (memset_first) TCMI_HIP(ctx, hipMemsetAsync(ctx->d_counts, 0, (size_t)ld * TCMI_NCOL * 4, ctx->stream));
     int rc = tcmi_tally_dev(ctx, rs, L, ld, ctx->d_counts, 0);
     if (rc) return rc;
+    if (ctx->var_on) {              // the variant table: behind the tally, in front of the call kernel, which may zero the matrix
+        rc = enqueue_variants(ctx, L);
+        if (rc) return rc;
+    }
     rc = tcmi_launch_call(ctx, ctx->d_counts, L, ld, mincov, include_ambig, want_counts ? 0 : 1, ctx->h_rec, ctx->h_rec + ld,
                           ctx->h_rec + 2 * ld, nullptr, nullptr);
     if (rc) return rc;
@@ -663,6 +819,8 @@ int tcmi_step_begin_deferred(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, i
     if (L <= 0 || rs->max_end > L) return tcmi_fail(ctx, TCMI_E_ARG, "L=%lld does not cover the reads (extent %lld)", (long long)L, (long long)rs->max_end);
     if (rs->device != ctx->device) return tcmi_fail(ctx, TCMI_E_ARG, "read set lives on device %d, context on %d", rs->device, ctx->device);
     if (ctx->step_L > 0 || ctx->call_pending) return tcmi_fail(ctx, TCMI_E_ARG, "tcmi_step_begin: the previous step of this context has not been ended");
+    if (ctx->var_on)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "a variant table (--variant-table, tcmi_ctx_set_variants) is set on this context: the array pipeline's ride-along steps compute none; use tcmi_step or the file runner");
     int rc = ensure_ws(ctx, L);
     if (rc) return rc;
     TCMI_HIP(ctx, hipSetDevice(ctx->device));
@@ -700,6 +858,7 @@ int tcmi_step_begin_deferred(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, i
     ctx->pend_L = L; ctx->pend_mincov = mincov; ctx->pend_amb = include_ambig;
     ctx->step_L = L;
     ctx->step_counts = false;
+    ctx->step_var = false;
     return TCMI_OK;
 }
 
@@ -726,6 +885,7 @@ int tcmi_step_begin(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int32_t mi
     TCMI_HIP(ctx, hipEventRecord(ctx->step_done, ctx->stream));
     ctx->step_L = L;
     ctx->step_counts = want_counts != 0;
+    ctx->step_var = ctx->var_on;
     return TCMI_OK;
 }
 
@@ -745,6 +905,8 @@ int tcmi_step_end(tcmi_ctx *ctx, const uint8_t **plain, const uint8_t **alt, con
     if (flags) *flags = ctx->h_rec + 2 * ld;
     if (counts_planes) *counts_planes = ctx->step_counts ? ctx->h_counts : nullptr;
     if (ld_out) *ld_out = ld;
+    ctx->var_valid = ctx->step_var;
+    if (ctx->step_var) ctx->var_n = std::min(ctx->step_L, ctx->var_n_ref) > 0 ? (int64_t)ctx->h_var_tot[0] : 0;
     ctx->step_L = 0;
     return TCMI_OK;
 }

@@ -343,6 +343,10 @@ int tcmi_pipeline_run_batched(tcmi_pipeline *p, int64_t n_items, const tcmi_read
         if (c->primers)
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context holds a primer table (--primers): the array pipeline runs read sets uploaded "
                              "from flat arrays, which the host packer packs without a primer mask");
+    for (const tcmi_ctx *c : p->slots)                          // (... and no variant table: nobody would fetch its records)
+        if (c->var_on)
+            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries a variant table setting (--variant-table, tcmi_ctx_set_variants): the array "
+                             "pipeline's steps compute none; use tcmi_step or the file runner");
     p->batch = batch;
     p->pos_stride = batch > 1 ? pos_stride : 0;
     const int64_t L_gpu = batch > 1 ? (int64_t)batch * pos_stride : L;   // positions one step covers
@@ -454,6 +458,7 @@ struct FileItem {
     bool on_device = false;
     PreTokens pre;                      // insert tokens resolved on the device while the decoded stream was still resident
     std::vector<int32_t> cov;           // files mode: the coverage column (VCF, coverage TSV)
+    std::vector<tcmi_variant> var;      // files mode: the step's variant records, for a sample whose table is wanted
 };
 
 double seconds_since(std::chrono::steady_clock::time_point t0)
@@ -511,7 +516,11 @@ tcmi_ctx *tcmi_filerunner_ctx(tcmi_filerunner *r, int k) { return (r && k >= 0 &
 } // extern "C"
 
 namespace {
-struct OutFiles { const char *const *fasta, *const *vcf, *const *gff, *const *doc; };     // per item; an entry may be NULL (not wanted)
+struct OutFiles {                       // per item; an entry may be NULL (not wanted)
+    const char *const *fasta, *const *vcf, *const *gff, *const *doc;
+    const char *const *table;           // the variant table (tcmi_filerunner_run_files_table); n_variants: its records per item, or NULL
+    int64_t *n_variants;
+};
 
 int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, const char *const *names, int64_t ref_len,
                     int32_t mincov, int include_ambig, int device_decode, char *out_text, int64_t stride, int64_t *out_len,
@@ -621,6 +630,14 @@ int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, con
                     if (!rc) {
                         it.L = L;
                         if (want_cov) it.cov.assign(planes + (size_t)TCMI_COV * ld, planes + (size_t)TCMI_COV * ld + L);
+                        if (files && files->table && files->table[i]) {      // the step's variant records, next to its call records
+                            const tcmi_variant *vr = nullptr;
+                            int64_t nv = 0;
+                            rc = tcmi_step_variants(ctx, &vr, &nv);
+                            if (!rc) it.var.assign(vr, vr + nv);
+                        }
+                    }
+                    if (!rc) {
                         it.rec.resize((size_t)L * 3);
                         std::memcpy(it.rec.data(), pl, (size_t)L);
                         std::memcpy(it.rec.data() + L, al, (size_t)L);
@@ -719,6 +736,15 @@ int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, con
                         rc = vcf_text(r->vcf_head, r->ref_id, r->ref_seq, extra.cons_noinsert, it.cov.data(), L, mincov, extra, text);
                         if (!rc) rc = write_file(files->vcf[i], text);
                     }
+                    if (!rc && files->table && files->table[i]) {
+                        text.assign(it.var.size() * (r->ref_id.size() + 96) + 1, '\0');
+                        int64_t tl = 0;
+                        rc = tcmi_variants_text(it.var.data(), (int64_t)it.var.size(), r->ref_id.c_str(), 0, reinterpret_cast<const uint8_t *>(r->ref_seq.data()),
+                                                (int64_t)r->ref_seq.size(), &text[0], (int64_t)text.size(), &tl);
+                        if (rc) rc = tcmi_fail(nullptr, rc, "%s: the variant records do not fit the reference of tcmi_filerunner_set_outputs", paths[i]);
+                        else { text.resize((size_t)tl); text.insert(0, TCMI_VARIANTS_HEADER); rc = write_file(files->table[i], text); }
+                        if (!rc && files->n_variants) files->n_variants[i] = (int64_t)it.var.size();
+                    }
                     if (!rc && files->fasta && files->fasta[i]) { own.resize((size_t)out_len[i]); rc = write_file(files->fasta[i], own); }
                 }
                 if (rc) { it.rc = rc; it.err = tcmi_last_error(nullptr); }
@@ -794,7 +820,29 @@ int tcmi_filerunner_run_files(tcmi_filerunner *r, int64_t n, const char *const *
 {
     if (!r || !fasta) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
     if ((vcf || gff) && r->gff_cols.size() != 6 * r->orf_start.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "tcmi_filerunner_set_outputs first");
-    const OutFiles f = {fasta, vcf, gff, doc};
+    const OutFiles f = {fasta, vcf, gff, doc, nullptr, nullptr};
+    return filerunner_core(r, n, paths, names, ref_len, mincov, include_ambig, device_decode, nullptr, 0, nullptr, status, stage_seconds, decoded_on, &f);
+}
+
+// ... and per sample (an array or an entry may be NULL) its variant table: the runner's contexts carry the setting (tcmi_ctx_set_variants
+// through tcmi_filerunner_ctx, the same on all of them), the GPU stage copies the step's records next to the call records, the walker
+// writes the file with tcmi_variants_text — REGION and REF from tcmi_filerunner_set_outputs' reference.  A sample that went to the
+// host-reader fallback gets its table too: its step goes through tcmi_step.  n_variants (may be NULL): the records written per sample.
+int tcmi_filerunner_run_files_table(tcmi_filerunner *r, int64_t n, const char *const *paths, const char *const *names, const char *const *fasta,
+                                    const char *const *vcf, const char *const *gff, const char *const *doc, const char *const *table, int64_t ref_len,
+                                    int32_t mincov, int include_ambig, int device_decode, int32_t *status, double *stage_seconds, int64_t *decoded_on,
+                                    int64_t *n_variants)
+{
+    if (!r || !fasta) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    if ((vcf || gff || table) && r->gff_cols.size() != 6 * r->orf_start.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "tcmi_filerunner_set_outputs first");
+    bool any = false;
+    for (int64_t i = 0; table && i < n; ++i) any = any || table[i];
+    if (any && r->ref_seq.empty())                              // (the rows' REGION and REF; the GFF rows above may be none at all)
+        return tcmi_fail(nullptr, TCMI_E_ARG, "a variant table is asked for: tcmi_filerunner_set_outputs (the reference's id and sequence) first");
+    for (const tcmi_ctx *c : r->ctxs)
+        if (any && !c->var_on) return tcmi_fail(nullptr, TCMI_E_ARG, "a variant table is asked for: tcmi_ctx_set_variants on every context of the runner first");
+    for (int64_t i = 0; n_variants && i < n; ++i) n_variants[i] = 0;
+    const OutFiles f = {fasta, vcf, gff, doc, table, n_variants};
     return filerunner_core(r, n, paths, names, ref_len, mincov, include_ambig, device_decode, nullptr, 0, nullptr, status, stage_seconds, decoded_on, &f);
 }
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/tcmi.h"
+#include "variants_rule.h"           // the variant table's rule (GPU-free; shared with the host checks)
 #include "readset_layout.h"          // tcmi_layout, the packed read set (TCMI_F_* / TCMI_P_*, tcmi_fast_chunk), the chunk geometry
 
 // checks n_ref / shift / slot_len (slots in ascending order, disjoint, below TCMI_F_EVPOS) and fills *out; TCMI_OK or TCMI_E_ARG
@@ -174,6 +175,21 @@ struct tcmi_ctx {
     tcmi_read_filter flt = {0, 0, 0};   // tcmi_ctx_set_read_filter: governs the read sets built from device-decoded record streams
     int32_t min_bq = 0;              // tcmi_ctx_set_min_base_quality: likewise; the flat-array entry points refuse while it is above 0
     std::shared_ptr<const tcmi_primer_dev> primers;   // tcmi_ctx_set_primers: likewise, and refused likewise while set
+    // the variant table (tcmi_ctx_set_variants; variants.hip): the setting — a device copy of the reference on the matrix's axis and
+    // the rule — under which every tcmi_step_begin launches the table's kernels between the tally and the call, their records going
+    // to pinned memory sized 5 * var_n_ref (h_var_rec); h_var_tot (pinned): the totals the scan kernel writes, [0] a step's, [1]
+    // tcmi_variants_dev's; d_var_scr: blk_cnt | blk_base of the launches, grow-only (var_scr_blocks blocks)
+    bool var_on = false;
+    tcmi_var_rule var_rule = {0, 1, 1, 0};
+    uint8_t *d_var_ref = nullptr;
+    int64_t var_n_ref = 0;
+    tcmi_variant *h_var_rec = nullptr;
+    unsigned long long *h_var_tot = nullptr;
+    char *d_var_scr = nullptr;
+    int64_t var_scr_blocks = 0;
+    bool step_var = false;           // the step that is under way (step_L > 0) computes a table
+    bool var_valid = false;          // the last ended step computed one: var_n records in h_var_rec (tcmi_step_variants)
+    int64_t var_n = 0;
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_one_sync_retried = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
@@ -346,6 +362,17 @@ int tcmi_step_flush(tcmi_ctx *ctx);
 int tcmi_launch_call(tcmi_ctx *ctx, int32_t *d_counts, int64_t L, int64_t ld, int32_t mincov,
                      int include_ambig, int clean, uint8_t *d_plain, uint8_t *d_alt, uint8_t *d_flags,
                      int32_t *d_events, int32_t *d_event_counts);
+
+// the variant table's three launches (variants.hip) on the context's stream, over min(L, n_ref) > 0 positions; blk_cnt / blk_base:
+// ceil(min(L, n_ref) / 256) words each; total: a word the host can read once the stream has been waited for
+struct tcmi_var_job {
+    const int32_t *counts; int64_t L, ld;
+    const uint8_t *ref; int64_t n_ref;
+    tcmi_var_rule rule;
+    uint32_t *blk_cnt; unsigned long long *blk_base, *total;
+    tcmi_variant *records; int64_t cap;
+};
+int tcmi_launch_variants(tcmi_ctx *ctx, const tcmi_var_job &job);
 
 static inline int64_t tcmi_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static inline size_t tcmi_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }     // the pieces of device buffers start on 256 bytes

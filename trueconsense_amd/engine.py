@@ -25,6 +25,50 @@ def read_filter_args(read_filter):
     return int(q), int(f), int(F)
 
 
+# struct tcmi_variant: one (position, non-reference allele) of the variant table
+VARIANT_DTYPE = np.dtype([("pos", np.int32), ("allele", np.int32), ("count", np.int32), ("cov", np.int32)])
+VARIANTS_HEADER = "REGION\tPOS\tREF\tALT\tALT_DP\tTOTAL_DP\tALT_FREQ\n"
+
+
+def min_af_fraction(min_af):
+    """min_af (a Fraction, or text / a number Fraction takes: "0.03", "3e-2", "3/100") -> (num, den) of the reduced fraction;
+    ValueError unless 0 <= min_af <= 1 with a denominator of at most 10^6."""
+    from fractions import Fraction
+    try:
+        f = Fraction(min_af if not isinstance(min_af, float) else repr(min_af))
+    except (ValueError, ZeroDivisionError, TypeError):
+        raise ValueError("%r is not a number or a fraction" % (min_af,))
+    if not 0 <= f <= 1:
+        raise ValueError("%s is outside 0..1" % (min_af,))
+    if f.denominator > 1000000:
+        raise ValueError("%s needs a denominator above 10^6 (%d)" % (min_af, f.denominator))
+    return f.numerator, f.denominator
+
+
+def _ref_bytes(ref):
+    """str / bytes / uint8 array -> contiguous uint8 array (the reference on the count matrix's axis)"""
+    if isinstance(ref, str):
+        ref = ref.encode("latin-1")
+    if isinstance(ref, (bytes, bytearray)):
+        return np.frombuffer(bytes(ref), np.uint8)
+    return np.ascontiguousarray(ref, np.uint8)
+
+
+def variants_text(records, region, ref, pos_offset=0):
+    """The table's rows for `records` (tcmi_variants_text, the one writer; HOST): REGION, POS = pos - pos_offset + 1, REF, ALT, ALT_DP,
+    TOTAL_DP, ALT_FREQ.  ref: the reference on the records' axis.  -> str, without the header line (VARIANTS_HEADER)."""
+    records = np.ascontiguousarray(records, VARIANT_DTYPE)
+    ref = _ref_bytes(ref)
+    n = len(records)
+    cap = n * (len(str(region).encode()) + 96) + 1
+    buf = C.create_string_buffer(cap)
+    ln = C.c_int64(0)
+    rc = lib().tcmi_variants_text(ptr(records), n, str(region).encode(), int(pos_offset), ptr(ref), len(ref), C.cast(buf, C.c_void_p), cap, C.byref(ln))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_variants_text: a record does not fit the reference, the offset or the buffer")
+    return buf.raw[:ln.value].decode("latin-1")
+
+
 def _grab(vp, dtype, n):
     """n items of dtype at address vp (memory the library owns) -> a fresh numpy array."""
     out = np.empty(n, dtype)
@@ -210,6 +254,56 @@ class Context:
             self.set_min_base_quality(min_baseq)
         if primers is not None:
             self.set_primers(*primers)
+
+    def set_variants(self, ref=None, min_af="0.03", min_alt_depth=1, min_depth=10):
+        """Variant table (tcmi_ctx_set_variants): from now on every step of this context (step, bamfile_step) also lists, per position
+        of `ref` (the reference on the count matrix's axis), every non-reference allele with count >= min_alt_depth and
+        count / cov >= min_af where cov >= max(min_depth, 1) — step_variants() has them.  The array Pipeline refuses while it is
+        set.  ref None: no table."""
+        if ref is None:
+            check(lib().tcmi_ctx_set_variants(self.handle, None, 0, 0, 1, 1, 0), self.handle)
+            return
+        num, den = min_af_fraction(min_af)
+        ref = _ref_bytes(ref)
+        keep = ref if len(ref) else np.zeros(1, np.uint8)
+        check(lib().tcmi_ctx_set_variants(self.handle, ptr(keep), len(ref), num, den, int(min_alt_depth), int(min_depth)), self.handle)
+
+    def step_variants(self):
+        """The variant records of the last ended step (tcmi_step_variants) as a fresh structured array (VARIANT_DTYPE); raises
+        TcmiError(E_ARG) when that step computed none."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        check(lib().tcmi_step_variants(self.handle, C.byref(p), C.byref(n)), self.handle)
+        return _grab(p, VARIANT_DTYPE, n.value) if n.value else np.zeros(0, VARIANT_DTYPE)
+
+    def variants_dev(self, d_counts, L, ld, d_ref, n_ref, min_af="0.03", min_alt_depth=1, min_depth=10, d_records=0, cap=0):
+        """Device-resident table (tcmi_variants_dev): int32 [7][ld] planes and the reference at device addresses -> the number of
+        records the rule yields; the first `cap` of them are written at `d_records` (device or pinned host address; 0 with cap 0:
+        count only).  Raises TcmiError(E_ARG) when there are more than cap (its .n_found has the number)."""
+        num, den = min_af_fraction(min_af)
+        n = C.c_int64(0)
+        rc = lib().tcmi_variants_dev(self.handle, C.c_void_p(int(d_counts)), int(L), int(ld), C.c_void_p(int(d_ref)) if d_ref else None, int(n_ref),
+                                     num, den, int(min_alt_depth), int(min_depth), C.c_void_p(int(d_records)) if d_records else None, int(cap),
+                                     C.byref(n))
+        try:
+            check(rc, self.handle)
+        except _ffi.TcmiError as e:
+            e.n_found = n.value
+            raise
+        return n.value
+
+    def variants(self, counts, ref, min_af="0.03", min_alt_depth=1, min_depth=10):
+        """counts [L,7] and the reference on their axis -> the table's records, a structured array (VARIANT_DTYPE) ordered by
+        position, then allele A, T, C, G, X, I (tcmi_variants)."""
+        counts = np.ascontiguousarray(counts, np.int32)
+        ref = _ref_bytes(ref)
+        num, den = min_af_fraction(min_af)
+        L = len(counts)
+        cap = 5 * min(L, len(ref))
+        out = np.zeros(max(cap, 1), VARIANT_DTYPE)
+        n = C.c_int64(0)
+        check(lib().tcmi_variants(self.handle, ptr(counts), L, ptr(ref) if len(ref) else None, len(ref), num, den, int(min_alt_depth),
+                                  int(min_depth), ptr(out), cap, C.byref(n)), self.handle)
+        return out[:n.value].copy()
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
@@ -679,7 +773,9 @@ class FileRunner:
     (tcmi_bam_load, `decode_threads` threads) and packed from its flat arrays.  `seconds` accumulates each stage's busy time."""
 
     def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None,
-                 min_baseq=0, primers=None):
+                 min_baseq=0, primers=None, variants=None):
+        """variants: the keyword arguments of Context.set_variants (ref, min_af, min_alt_depth, min_depth), set on every context of the
+        runner: run_files(table=...) then writes each sample's variant table."""
         device = ctx.device if isinstance(ctx, Context) else int(ctx)
         self.mincov, self.amb = int(mincov), bool(include_ambig)
         h = C.c_void_p()
@@ -696,8 +792,11 @@ class FileRunner:
         self._device = device
         # every context the same: the runner's host-reader fallbacks take the filter from them, and under a floor a file that leaves
         # the device path is refused, never tallied without it
+        self.variant_records = 0        # records of the tables run_files wrote
         for c in self.contexts:
             c.apply(read_filter, min_baseq or None, primers)
+            if variants:
+                c.set_variants(**variants)
 
     @property
     def contexts(self):
@@ -749,9 +848,9 @@ class FileRunner:
         check(lib().tcmi_filerunner_set_outputs(self.handle, str(ref_id).encode(), str(ref_seq).encode(), str(vcf_head).encode(),
                                                 str(gff_head).encode(), len(gff_row_columns), arr))
 
-    def run_files(self, paths, names, fasta, vcf=None, gff=None, doc=None, ref_len=0):
-        """BAM files -> per sample its consensus FASTA and (lists, entries may be None) VCF, corrected GFF, coverage TSV, all written
-        by the native runner's walker threads.  Raises what the reference raises (KeyError, ZeroDivisionError) for the first
+    def run_files(self, paths, names, fasta, vcf=None, gff=None, doc=None, ref_len=0, table=None):
+        """BAM files -> per sample its consensus FASTA and (lists, entries may be None) VCF, corrected GFF, coverage TSV and — table,
+        with the runner's `variants` setting — variant table, all written by the native runner's walker threads.  Raises what the reference raises (KeyError, ZeroDivisionError) for the first
         sample that fails; last_status has every sample's code."""
         n = len(paths)
         if n == 0:
@@ -763,8 +862,15 @@ class FileRunner:
         status = np.zeros(n, np.int32)
         sec = (C.c_double * 4)()
         on = (C.c_int64 * 2)()
-        rc = lib().tcmi_filerunner_run_files(self.handle, n, arr(paths), arr(names), arr(fasta), arr(vcf), arr(gff), arr(doc), int(ref_len),
-                                             self.mincov, int(self.amb), int(bool(self.device_decode)), ptr(status), sec, on)
+        if table is None:
+            rc = lib().tcmi_filerunner_run_files(self.handle, n, arr(paths), arr(names), arr(fasta), arr(vcf), arr(gff), arr(doc), int(ref_len),
+                                                 self.mincov, int(self.amb), int(bool(self.device_decode)), ptr(status), sec, on)
+        else:
+            n_var = np.zeros(n, np.int64)
+            rc = lib().tcmi_filerunner_run_files_table(self.handle, n, arr(paths), arr(names), arr(fasta), arr(vcf), arr(gff), arr(doc), arr(table),
+                                                       int(ref_len), self.mincov, int(self.amb), int(bool(self.device_decode)), ptr(status), sec, on,
+                                                       ptr(n_var))
+            self.variant_records += int(n_var.sum())
         self._account(status, sec, on)
         _check_walk(rc, (lib().tcmi_last_error(None) or b"").decode("utf-8", "replace"), KeyError)
 

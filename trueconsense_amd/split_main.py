@@ -28,7 +28,7 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import GetArgs, primers_of, read_filter_of
+    from .TrueConsense import GetArgs, primers_of, read_filter_of, variants_of, write_variant_table
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
     torch.cuda.set_device(device)
@@ -48,7 +48,7 @@ def main(argv=None):
         IndexGff = Gffindex(a.features)
         gffdict = IndexGff.index_dict(seqid=a.samplename)
         rows = [{"start": int(r["start"]), "end": int(r["end"]), "strand": r.get("strand")} for r in gffdict.values()]
-        _, refseq = fasta.read_first_record(a.reference)
+        refID, refseq = fasta.read_first_record(a.reference)
         parts = td.consensus_split_bamfile(a.input, len(refseq), rows, a.coverage_level, a.noambiguity is False, a.samplename, rank, world,
                                            device=device, return_parts=True, rccl_user=user, read_filter=read_filter_of(a), min_baseq=a.min_baseq,
                                            primers=primers_of(a))
@@ -57,6 +57,9 @@ def main(argv=None):
             index = _state.IndexDict(counts)
             if a.depth_of_coverage is not None:
                 BuildCoverage(index, a.depth_of_coverage)
+            if a.variant_table is not None:                          # (from the reduced counts, as the single-GPU command line from its own)
+                recs = _state.default_context().variants(index.counts, refseq, **variants_of(a))
+                write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
             WriteOutputs(a.coverage_level, index, gffdict, td._Tokens(toks), a.noambiguity is False, a.variants, a.samplename, a.reference,
                          a.output_gff, IndexGff.header, a.output)
     except Exception as e:                                           # noqa: BLE001 — every rank must reach the group's teardown
