@@ -2,7 +2,8 @@
 """tools/fuzz_inflate.py [seconds=60] [seed=1] — random BAM files through the device decoder against zlib, byte for byte, and through the
 tally against the oracle's counts: read sets of random size, qualities from random distributions (constant ... uniform: 35 : 1 ... 2 : 1, so
 every bgzf_symbols / bgzf_copy variant comes up), zlib level 1 - 9, strategy default / filtered / RLE / Huffman-only / fixed, memLevel 1 - 9,
-blocks cut on records or filled to the brim, tiny blocks; the lanes' token scratch cut down at random (`sym_scratch_div`: pass B)."""
+blocks cut on records or filled to the brim, tiny blocks; the lanes' token scratch cut down at random (`sym_scratch_div`: pass B).  One file in
+four is rewritten by the tests' own deflate writer (tests/deflate_writer.py: rewrite_bam) with a random recipe — what zlib never writes."""
 import gzip, os, struct, sys, tempfile, time, zlib
 ROOT = os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -10,6 +11,28 @@ import numpy as np
 from oracle import c_oracle
 from trueconsense_amd import engine, synthetic as sy
 from trueconsense_amd.io import bamwriter
+from tests import deflate_writer as dw
+
+
+def random_recipe(rng):
+    """BGZF block size, match policy, code shapes, header encoding, and the kinds of deflate blocks a BGZF block is cut into"""
+    policy = str(rng.choice(["nearest", "farthest", "literals"]))
+    ll = str(rng.choice(["huffman", "deep", "flat"]))
+    d = "none" if policy == "literals" else str(rng.choice(["huffman", "deep"]))
+    clenc = str(rng.choice(["none", "max", "greedy"]))
+    kinds = [str(k) for k in rng.choice(["dynamic", "dynamic", "fixed", "stored"], size=int(rng.integers(1, 9)))]
+    block = int(rng.integers(600, 60000 if ll == "huffman" and set(kinds) == {"dynamic"} else 30000))      # (15-bit literals, stored bytes: a BGZF block holds 64 KB)
+
+    def layout(tokens, k):
+        cuts = sorted(int(c) for c in rng.integers(0, len(tokens) + 1, len(kinds) - 1)) + [len(tokens)]
+        blocks, a = [], 0
+        for kind, b in zip(kinds, cuts):
+            blocks.append(dict(kind=kind, n=b - a))
+            if kind == "dynamic":
+                blocks[-1].update(zip(("ll", "d"), dw.lengths_for(tokens[a:b], ll, d if any(t[0] == "match" for t in tokens[a:b]) else "none")), clenc=clenc)
+            a = b
+        return blocks
+    return dw.plain_recipe(block, policy, layout=layout), (block, policy, ll, d, clenc, kinds)
 
 seconds = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
@@ -41,6 +64,10 @@ try:
             bamwriter.write_bam(p, reads, "ref", L, **kw)
         finally:
             bamwriter.DEFLATE.update(strategy=zlib.Z_DEFAULT_STRATEGY, mem_level=8, flush_every=0)
+        if rng.random() < 0.25 and nr <= 8000:          # (the writer is plain Python: small files)
+            recipe, kw["recipe"] = random_recipe(rng)
+            os.replace(p, p + ".src")
+            dw.rewrite_bam(p + ".src", p, recipe)
         div = int(rng.choice([1, 1, 1, 4, 16, 64]))
         ctx.set_option("sym_scratch_div", div)
         want = np.frombuffer(gzip.decompress(open(p, "rb").read()), np.uint8)
