@@ -282,6 +282,54 @@ int  tcmi_ctx_set_variants(tcmi_ctx *ctx, const uint8_t *ref, int64_t n_ref, int
 int  tcmi_step_variants(tcmi_ctx *ctx, const tcmi_variant **records, int64_t *n);
 int  tcmi_variants_text(const tcmi_variant *records, int64_t n, const char *region, int64_t pos_offset, const uint8_t *ref, int64_t n_ref,
                         char *text, int64_t cap, int64_t *len);
+/* ---- amplicon table (additive: what `samtools ampliconstats` reports as FDEPTH / FPCOV; the reference has only the coverage TSV) ----
+ * Order statistics of the matrix's coverage plane (TCMI_COV; no other plane is read) over n intervals [start[i], end[i]) of the
+ * matrix's axis, 0 <= start <= end <= 2^29, n <= 65 536, and a bound min_depth >= 0.  Intervals may overlap, nest, repeat, be empty
+ * and come in any order.  A position p >= L has depth 0; nothing at or beyond L is read (the padding [L, ld) may hold anything).
+ * Depths are compared as signed int32.  One 32-byte record per interval, in the order given; an empty interval gives
+ * {0, 0, 0, -1, 0, 0, 0}.  All arithmetic is integer and no atomics on memory take part: every run gives the same bytes.
+ *   tcmi_interval_stats_dev  the matrix, the interval arrays (int64) and the records are the caller's device pointers; d_counts as for
+ *                     tcmi_call_dev (4-byte aligned, any ld >= L) and only read; d_records: 4-byte aligned, device or pinned host
+ *                     memory, room for n records; d_start and d_end: 8-byte aligned (TCMI_E_ARG otherwise).  The intervals are checked on the host (the call downloads them: 16 bytes
+ *                     each).  Waits for the context's stream.  n = 0 does nothing.
+ *   tcmi_interval_stats      host convenience, shaped like tcmi_variants: rows [L][7] and host intervals in, host records out
+ *   tcmi_ctx_set_intervals   n = 0 clears the setting; else the context keeps a device copy of the intervals and from now on every
+ *                     step it queues through tcmi_step_begin (tcmi_step, tcmi_bamfile_step on both of its routes) launches the
+ *                     kernel behind the tally and in front of the call kernel (which may zero the matrix), beside the variant
+ *                     table's launches; the records go to pinned memory of the context sized n, and tcmi_step_end's one wait
+ *                     covers them.  While a setting is in force the array pipeline (tcmi_pipeline_run[_batched]) refuses with
+ *                     TCMI_E_UNSUPPORTED and a message naming --amplicon-table.  tcmi_split_step is not governed: its matrix is
+ *                     the caller's (tcmi_interval_stats_dev / tcmi_interval_stats).  No setting: exactly the launches of before.
+ *   tcmi_step_intervals      the records of the last step that was ended, valid until the context's next step or setting;
+ *                     TCMI_E_ARG when that step computed none
+ *   tcmi_amplicons_text      HOST, re-entrant, no GPU (and no error text: the code says it all): the ONE writer of the table's rows.
+ *                     Per record "SAMPLE REGION AMPLICON POOL START END LEN MEAN MEDIAN MIN MIN_POS BELOW", tab-separated:
+ *                     AMPLICON = names[i], POOL = pools[i], START = start[i] - pos_offset + 1 (start: the intervals' starts on the
+ *                     records' axis), END = START + LEN - 1 (inclusive), LEN = n, MEAN = sum / n as a double printed with %.2f,
+ *                     MIN_POS = min_pos - pos_offset + 1.  An empty interval prints END = START - 1, LEN 0, NA for MEAN, MEDIAN,
+ *                     MIN and MIN_POS, BELOW 0.  The header line (TCMI_AMPLICONS_HEADER) is the caller's.  Sizing call, short
+ *                     buffer and *len as for tcmi_variants_text.  TCMI_E_ARG for a record that does not fit the arguments
+ *                     (start[i] < pos_offset, n < 0, n > 0 with min_pos outside [start[i], start[i] + n)).
+ * TCMI_INTERVAL_STAGE: the columns of an interval the kernel stages in LDS (a longer one is selected from memory); for tests.
+ * Argument errors are TCMI_E_ARG: n outside 0..65 536, start < 0, end < start, end > 2^29, min_depth < 0, negative sizes. */
+typedef struct tcmi_interval_stat {
+    int64_t sum;                      /* of the depths; int64: 2^31-1 times thousands of columns */
+    int32_t n;                        /* end - start */
+    int32_t min, min_pos;             /* the smallest depth and the FIRST position that has it */
+    int32_t median;                   /* the LOWER median: the ((n-1)/2)-th smallest, exact */
+    int32_t below;                    /* positions with depth < min_depth */
+    int32_t reserved;                 /* 0 */
+} tcmi_interval_stat;
+#define TCMI_AMPLICONS_HEADER "SAMPLE\tREGION\tAMPLICON\tPOOL\tSTART\tEND\tLEN\tMEAN\tMEDIAN\tMIN\tMIN_POS\tBELOW\n"
+#define TCMI_INTERVAL_STAGE 4096
+int  tcmi_interval_stats_dev(tcmi_ctx *ctx, const void *d_counts, int64_t L, int64_t ld, int64_t n, const void *d_start, const void *d_end,
+                             int32_t min_depth, void *d_records);
+int  tcmi_interval_stats(tcmi_ctx *ctx, const int32_t *counts, int64_t L, int64_t n, const int64_t *start, const int64_t *end,
+                         int32_t min_depth, tcmi_interval_stat *records);
+int  tcmi_ctx_set_intervals(tcmi_ctx *ctx, int64_t n, const int64_t *start, const int64_t *end, int32_t min_depth);
+int  tcmi_step_intervals(tcmi_ctx *ctx, const tcmi_interval_stat **records, int64_t *n);
+int  tcmi_amplicons_text(const tcmi_interval_stat *records, int64_t n, const char *sample, const char *region, const char *const *names,
+                         const char *const *pools, const int64_t *start, int64_t pos_offset, char *text, int64_t cap, int64_t *len);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -299,7 +347,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_CRC = 8 /* retired (always 0 since ABI 5): the blocks' CRC-32 is taken in bgzf_copy's flush, filed under TCMI_K_INFLATE_COPY */,
        TCMI_K_INFLATE_COPY = 9 /* device BGZF inflate, second kernel: tokens -> bytes (TCMI_K_INFLATE is the first: symbols -> tokens) */,
        TCMI_K_VARIANTS = 10 /* the variant table's three launches (count, scan, emit) as one bracket */,
-       TCMI_K_NKERNELS = 11 };
+       TCMI_K_INTERVALS = 11 /* the amplicon table's one launch */,
+       TCMI_K_NKERNELS = 12 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);
@@ -628,6 +677,14 @@ int tcmi_filerunner_run_files_table(tcmi_filerunner *r, int64_t n, const char *c
                                     const char *const *vcf, const char *const *gff, const char *const *doc, const char *const *table, int64_t ref_len,
                                     int32_t mincov, int include_ambig, int device_decode, int32_t *status, double *stage_seconds, int64_t *decoded_on,
                                     int64_t *n_variants);
+/* ... and the amplicon table's records.  tcmi_ctx_set_intervals on every context of the runner first (the same n_intervals intervals
+ * on all): the GPU stage copies the step's records next to the call records, and they land in stats[i * n_intervals ...) for sample
+ * i (zeroes for a sample that failed).  A sample the host reader took gets its records through the same kernel.  The caller writes
+ * the table (tcmi_amplicons_text).  n_intervals = 0 with stats = NULL: tcmi_filerunner_run_files_table. */
+int tcmi_filerunner_run_files_stats(tcmi_filerunner *r, int64_t n, const char *const *paths, const char *const *names, const char *const *fasta,
+                                    const char *const *vcf, const char *const *gff, const char *const *doc, const char *const *table, int64_t ref_len,
+                                    int32_t mincov, int include_ambig, int device_decode, int32_t *status, double *stage_seconds, int64_t *decoded_on,
+                                    int64_t *n_variants, int64_t n_intervals, tcmi_interval_stat *stats);
 
 #ifdef __cplusplus
 }

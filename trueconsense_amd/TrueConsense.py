@@ -7,7 +7,9 @@ Additive flags (not in the reference): --device N (GPU ordinal), --stats FILE (J
 --min-mapq N / --require-flags F / --exclude-flags F (samtools view -q / -f / -F: a record that fails is ignored as an unmapped
 one is; the reference tallies every mapped record), the variant table --variant-table FILE [--min-af F] [--min-alt-depth N]
 [--variant-min-depth N] (per position every non-reference allele at or above a frequency, from the count matrix the consensus is
-called from; --batch: the manifest's 7th column), and
+called from; --batch: the manifest's 7th column), the amplicon table --amplicon-table FILE [--amplicon-scheme BED]
+[--amplicon-region insert|unique|full] (per amplicon of the primer scheme the mean, median and minimum depth of its columns and
+how many lie below -cov, from the same matrix; --batch: one file for all samples), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -135,6 +137,86 @@ def read_manifest(a):
     return rows
 
 
+def amplicons_of(a, layout=None):
+    """The parsed namespace's --amplicon-scheme / --amplicon-region -> [(Amplicon, the shift of its contig's slot on the count matrix's
+    axis)], or None without --amplicon-table.  Without a layout the amplicons on the BAM's reference name (--batch: the one -ref
+    names), shift 0; layout = (the BAM header's reference names, shift): those on contigs the layout holds.  None left, or a scheme
+    that does not parse: an argument error (exit 1)."""
+    if not getattr(a, "amplicon_table", None):
+        return None
+    from .io import primers as pb
+    try:
+        amps = pb.amplicons(pb.read_scheme(a.amplicon_scheme), a.amplicon_region)
+    except (OSError, pb.PrimerBedError) as e:
+        print(f"--amplicon-scheme: {e}. Exiting...")
+        sys.exit(1)
+    if layout is not None:
+        out = pb.amplicons_for_layout(amps, *layout)
+        where = "a contig of the layout"
+    else:
+        from .contigs import bam_header_refs
+        names = bam_header_refs(a.input)[0] if getattr(a, "input", None) else []
+        if not names:
+            from .io import fasta
+            names = [fasta.read_first_record(a.reference)[0]]
+        out = [(m, 0) for m in amps if m.chrom == names[0]]
+        where = 'the reference "%s"' % names[0]
+    if not out:
+        print(f"--amplicon-table: no amplicon of {a.amplicon_scheme} is on {where}. Exiting...")
+        sys.exit(1)
+    if len(out) > 65536:
+        print(f"--amplicon-table: {a.amplicon_scheme} has {len(out)} amplicons, more than 65536. Exiting...")
+        sys.exit(1)
+    return out
+
+
+def amplicon_intervals(amps):
+    """amplicons_of's list -> [(start, end)] on the count matrix's axis, as Context.set_intervals / interval_stats take them."""
+    return [(m.start + sh, m.end + sh) for m, sh in amps]
+
+
+def amplicon_rows(records, sample, amps):
+    """One sample's rows of the amplicon table: records[i] belongs to amps[i]; REGION is the amplicon's contig and the positions are
+    the contig's own (tcmi_amplicons_text, one call per contig)."""
+    from itertools import groupby
+    from .engine import amplicons_text
+    text, i = [], 0
+    for (chrom, sh), grp in groupby(amps, key=lambda x: (x[0].chrom, x[1])):
+        grp = list(grp)
+        text.append(amplicons_text(records[i:i + len(grp)], sample, chrom, [m.name for m, _ in grp], [m.pool for m, _ in grp],
+                                   [m.start + sh for m, _ in grp], sh))
+        i += len(grp)
+    return "".join(text)
+
+
+def write_amplicon_table(path, samples, amps):
+    """--amplicon-table: the header line, then for every (sample name, its records) the sample's rows."""
+    from .engine import AMPLICONS_HEADER
+    text = AMPLICONS_HEADER + "".join(amplicon_rows(recs, name, amps) for name, recs in samples)
+    with open(path, "w") as out:
+        out.write(text)
+
+
+def join_amplicon_parts(path, parts, n_samples, per_sample):
+    """--batch --gpus N: part k (a child's table) holds the rows of samples k, k + N, ... — `per_sample` lines each; -> FILE with
+    every sample's rows in manifest order, and the parts removed."""
+    from .engine import AMPLICONS_HEADER
+    rows = []
+    for part in parts:
+        with open(part) as fh:
+            lines = fh.read().split("\n")[1:]
+        rows.append(lines)
+    n = len(parts)
+    with open(path, "w") as out:
+        out.write(AMPLICONS_HEADER)
+        for i in range(n_samples):
+            k, j = i % n, i // n
+            for line in rows[k][j * per_sample:(j + 1) * per_sample]:
+                out.write(line + "\n")
+    for part in parts:
+        os.remove(part)
+
+
 def read_filter_of(a):
     """The parsed namespace's read filter -> (min_mapq, require_flags, exclude_flags), or None when none was asked for."""
     f = (a.min_mapq, a.require_flags, a.exclude_flags)
@@ -242,6 +324,15 @@ def GetArgs(givenargs):
     additive.append((("--variant-min-depth",), dict(type=_count_arg(parser, "--variant-min-depth", 0), default=None, metavar="N",
                                                     help="minimum coverage of a position of the variant table (ivar variants -m; default 10;\n"
                                                          "independent of -cov)")))
+    additive.append((("--amplicon-table",), dict(type=str, default=None, metavar="File",
+                                                 help="also write per amplicon of the scheme the depth of its columns, tab-separated: SAMPLE REGION\n"
+                                                      "AMPLICON POOL START END LEN MEAN MEDIAN MIN MIN_POS BELOW (BELOW: columns under -cov), from\n"
+                                                      "the count matrix the consensus is called from; --batch: one file, every sample's rows")))
+    additive.append((("--amplicon-scheme",), dict(type=str, default=None, metavar="File",
+                                                  help="BED of the scheme's primers, named {amplicon}_LEFT / _RIGHT[_alt] (default: the file of --primers)")))
+    additive.append((("--amplicon-region",), dict(choices=("insert", "unique", "full"), default=None,
+                                                  help="the columns of an amplicon: between its primers (insert, the default), the insert\n"
+                                                       "outside every other amplicon (unique), or primers included (full)")))
     # (is this the --batch form?  asked of a small parser of its own: "--batch=FILE" and argparse's abbreviations count too)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--batch", default=None)
@@ -260,6 +351,15 @@ def GetArgs(givenargs):
         parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
     if a.batch is None and a.variant_table is None and a.variant_thresholds_given:
         parser.error("--min-af / --min-alt-depth / --variant-min-depth need --variant-table.")
+    if a.amplicon_table is None and (a.amplicon_scheme is not None or a.amplicon_region is not None):
+        parser.error("--amplicon-scheme / --amplicon-region need --amplicon-table.")
+    if a.amplicon_table is not None:
+        if a.amplicon_scheme is None and not a.primers:
+            parser.error("--amplicon-table needs the scheme's BED: --amplicon-scheme, or --primers.")
+        if a.coverage_level < 0:
+            parser.error("--amplicon-table counts the columns below -cov, which cannot be negative.")
+        a.amplicon_scheme = a.primers if a.amplicon_scheme is None else a.amplicon_scheme
+    a.amplicon_region = "insert" if a.amplicon_region is None else a.amplicon_region
     a.min_af = Fraction(3, 100) if a.min_af is None else a.min_af
     a.min_alt_depth = 1 if a.min_alt_depth is None else a.min_alt_depth
     a.variant_min_depth = 10 if a.variant_min_depth is None else a.variant_min_depth
@@ -315,9 +415,13 @@ def _child_argv(a, single, tables=True):
         out += ["--primers", a.primers, "--primer-slack", str(a.primer_slack)]
     if tables and (a.variant_thresholds_given or a.variant_table):     # (the table's thresholds, likewise; --batch children find their tables in the manifest)
         out += ["--min-af", str(a.min_af), "--min-alt-depth", str(a.min_alt_depth), "--variant-min-depth", str(a.variant_min_depth)]
+    if a.amplicon_table:                            # (the amplicon table's scheme; its FILE is the caller's: a --batch child writes a part)
+        out += ["--amplicon-scheme", a.amplicon_scheme, "--amplicon-region", a.amplicon_region]
     if single:
         if a.variant_table:
             out += ["--variant-table", a.variant_table]
+        if a.amplicon_table:
+            out += ["--amplicon-table", a.amplicon_table]
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]
         for flag, v in (("-vcf", a.variants), ("-doc", a.depth_of_coverage), ("-ogff", a.output_gff)):
             if v is not None:
@@ -341,8 +445,9 @@ def run_gpus(a):
         if a.variant_thresholds_given and not any(_names_a_table(ln) for ln in rows):
             print("--min-af / --min-alt-depth / --variant-min-depth need a variant table: no line of the manifest has a 7th column. Exiting...")
             return 1
+        amps = amplicons_of(a)                      # (an unusable scheme ends the run here, before anything is dealt out)
         with tempfile.TemporaryDirectory(prefix="tcmi_gpus_") as tmp:
-            cmds, envs = [], []
+            cmds, envs, parts = [], [], []
             for k in range(n):
                 mine = rows[k::n]
                 if not mine:
@@ -354,9 +459,15 @@ def run_gpus(a):
                     _child_argv(a, False, tables=any(_names_a_table(ln) for ln in mine))
                 if a.stats:
                     cmd += ["--stats", "%s.gpu%d" % (a.stats, k)]
+                if amps:                            # every child a part file of its own beside FILE
+                    parts.append("%s.part%d" % (a.amplicon_table, k))
+                    cmd += ["--amplicon-table", parts[-1]]
                 cmds.append(cmd)
                 envs.append(base_env)
-            return _spawn(cmds, envs)
+            rc = _spawn(cmds, envs)
+            if amps and rc == 0:                    # (all children have exited with status 0: the parts are whole)
+                join_amplicon_parts(a.amplicon_table, parts, len(rows), len(amps))
+            return rc
     if a.index_override:
         print("--index-override goes with one GPU. Exiting...")
         return 1
@@ -386,17 +497,23 @@ def run_batch(a):
     gffrows = list(IndexGff.index_dict(seqid="S").values())       # (the runner puts each sample's name there: TrueConsense.py:240)
     refID, refseq = fasta.read_first_record(a.reference)
     prm = primers_of(a)
+    amps = amplicons_of(a)
+    n_below = 0
     t0 = time.perf_counter()
     cores = max(1, min(int(a.threads), os.cpu_count() or 1))
     runner = FileRunner(int(os.environ.get("TCMI_DEVICE", "0")), gffrows, a.coverage_level, a.noambiguity is False,
                         decoders=min(4, max(1, cores // 4)), decode_threads=max(1, cores // 2), walkers=min(4, max(1, cores // 4)),
                         gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a),
-                        min_baseq=a.min_baseq, primers=prm, variants=dict(variants_of(a), ref=refseq) if tables else None)
+                        min_baseq=a.min_baseq, primers=prm, variants=dict(variants_of(a), ref=refseq) if tables else None,
+                        intervals=(amplicon_intervals(amps), a.coverage_level) if amps else None)
     runner.set_outputs(refID, refseq, vcf_header(date.today().strftime("%Y%m%d"), sys.argv[1:], a.reference, refID), IndexGff.header.raw_text,
                        [gff_row_columns(r) for r in gffrows])
     try:
-        runner.run_files([r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows],
-                         [r[5] for r in rows], ref_len=len(refseq), table=tables)
+        recs = runner.run_files([r[0] for r in rows], [r[1] for r in rows], [r[2] for r in rows], [r[3] for r in rows], [r[4] for r in rows],
+                                [r[5] for r in rows], ref_len=len(refseq), table=tables, stats=bool(amps))
+        if amps:                                    # one file: every sample's rows in manifest order
+            write_amplicon_table(a.amplicon_table, [(r[1], recs[i]) for i, r in enumerate(rows)], amps)
+            n_below = int((recs["below"] > 0).sum())
     except Exception:                                                # every failed sample is named; the first one's error (what the reference would raise) goes on up: non-zero exit
         failed = [(rows[i][1], int(c)) for i, c in enumerate(getattr(runner, "last_status", [])) if int(c) != 0]
         for nm, code in failed:
@@ -408,7 +525,8 @@ def run_batch(a):
         if a.stats:
             with open(a.stats, "w") as fh:
                 json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "primers": len(prm[0]) if prm else 0,
-                           "variant_records": int(getattr(runner, "variant_records", 0)), "stage_busy_seconds": runner.seconds,
+                           "variant_records": int(getattr(runner, "variant_records", 0)),
+                           "amplicons": len(amps) if amps else 0, "amplicons_below": n_below, "stage_busy_seconds": runner.seconds,
                            "decoded_on": runner.decoded_on, "status": [int(x) for x in getattr(runner, "last_status", [])]}, fh)
         runner.close()
 
@@ -506,6 +624,12 @@ def _single_sample(a, flt, t):
         write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
         n_variants = len(recs)
 
+    amps, n_below = amplicons_of(a), 0
+    if amps:                                        # likewise: the matrix behind the read filter, --min-baseq, --primers and --index-override
+        arecs = _state.default_context().interval_stats(indexDict.counts, amplicon_intervals(amps), a.coverage_level)
+        write_amplicon_table(a.amplicon_table, [(a.samplename, arecs)], amps)
+        n_below = int((arecs["below"] > 0).sum())
+
     IncludeAmbig = a.noambiguity is False
     WriteOutputs(a.coverage_level, indexDict, GffDict, bam, IncludeAmbig, a.variants, a.samplename, a.reference,
                  a.output_gff, GffHeader, a.output)
@@ -517,7 +641,8 @@ def _single_sample(a, flt, t):
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
-                       "variant_records": n_variants, "bam_bytes": os.path.getsize(a.input)}, fh)
+                       "variant_records": n_variants, "amplicons": len(amps) if amps else 0, "amplicons_below": n_below,
+                       "bam_bytes": os.path.getsize(a.input)}, fh)
 
 
 if __name__ == "__main__":

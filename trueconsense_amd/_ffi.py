@@ -18,7 +18,7 @@ TCMI_OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_FORMAT, E_IO, E_KEYERROR, E_ZERODIV, E_UNSUPPORTED = range(-1, -10, -1)
 COLS = ("coverage", "A", "T", "C", "G", "X", "I")        # indexing.py:134
 F_LOWCOV, F_PRIMX, F_MINDEL, F_INSCAND, F_COVGT, F_COVZERO, F_AMBIG = 1, 2, 4, 8, 16, 32, 64
-K_TALLY, K_CALL, K_ZERO, K_TALLY_GENERAL, K_PACK_CLASSIFY, K_PACK, K_INFLATE, K_RECORDS, K_CRC, K_INFLATE_COPY, K_VARIANTS = range(11)
+K_TALLY, K_CALL, K_ZERO, K_TALLY_GENERAL, K_PACK_CLASSIFY, K_PACK, K_INFLATE, K_RECORDS, K_CRC, K_INFLATE_COPY, K_VARIANTS, K_INTERVALS = range(12)
 
 
 class TcmiError(RuntimeError):
@@ -68,6 +68,11 @@ _SIGS = {
     "tcmi_ctx_set_variants": (_int, [_vp, _vp, _i64, _i64, _i64, _i32, _i32]),
     "tcmi_step_variants": (_int, [_vp, _P(_vp), _P(_i64)]),
     "tcmi_variants_text": (_int, [_vp, _i64, C.c_char_p, _i64, _vp, _i64, _vp, _i64, _P(_i64)]),
+    "tcmi_interval_stats_dev": (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp]),
+    "tcmi_interval_stats": (_int, [_vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp]),
+    "tcmi_ctx_set_intervals": (_int, [_vp, _i64, _vp, _vp, _i32]),
+    "tcmi_step_intervals": (_int, [_vp, _P(_vp), _P(_i64)]),
+    "tcmi_amplicons_text": (_int, [_vp, _i64, C.c_char_p, C.c_char_p, _vp, _vp, _vp, _i64, _vp, _i64, _P(_i64)]),
     "tcmi_profile_enable": (_int, [_vp, _int]),
     "tcmi_profile_reset": (_int, [_vp]),
     "tcmi_profile_get": (_int, [_vp, _int, _P(C.c_double), _P(_i64)]),
@@ -132,6 +137,7 @@ _SIGS = {
     "tcmi_filerunner_set_outputs": (_int, [_vp, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, _i32, _vp]),
     "tcmi_filerunner_run_files": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _int, _int, _vp, _vp, _vp]),
     "tcmi_filerunner_run_files_table": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _int, _int, _vp, _vp, _vp, _vp]),
+    "tcmi_filerunner_run_files_stats": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _int, _int, _vp, _vp, _vp, _vp, _i64, _vp]),
 }
 
 _lib = None

@@ -122,7 +122,7 @@ def axis_reference(records, header_names, shift, axis_len):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None, variants=None):
+                 info=None, min_baseq=0, primers=None, variants=None, intervals=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
@@ -131,7 +131,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     above 0 a file the device decoder declines is refused (the host packer knows no floor).  primers = (rows on the AXIS, slack)
     (Context.set_primers; io.primers.rows_for_layout shifts a BED's rows): likewise; info then receives "reads_primer_masked" too.
     variants = the keyword arguments of Context.set_variants (ref: the reference on the axis, axis_reference): the step also lists
-    the variant table's records, which info receives as "variant_table"."""
+    the variant table's records, which info receives as "variant_table".  intervals = ([(start, end)] on the axis, min_depth)
+    (Context.set_intervals): the step also computes the amplicon table's records, which info receives as "amplicon_table"."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
@@ -139,6 +140,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     ctx.set_primers(*(primers or ()))
     if variants:
         ctx.set_variants(**variants)
+    if intervals:
+        ctx.set_intervals(*intervals)
     host = None
     try:
         rs = device_readset(ctx, path)              # (the floor it refuses under is the one just set)
@@ -157,6 +160,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
             plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
             if variants and info is not None:
                 info["variant_table"] = ctx.step_variants()
+            if intervals and info is not None:
+                info["amplicon_table"] = ctx.step_intervals()
         finally:
             rs.free()
     finally:
@@ -166,13 +171,15 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_primers()
         if variants:
             ctx.set_variants()
+        if intervals:
+            ctx.set_intervals()
     return plain, alt, flags, counts, ext, dropped, host
 
 
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import primers_of, read_filter_of, variants_of, write_variant_table
+    from .TrueConsense import amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_table, write_variant_table
     flt, seen = read_filter_of(a), {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -184,14 +191,19 @@ def run(a):
     prm = primers_of(a, (hdr_names, shift))
     seen["primers"] = len(prm[0]) if prm else 0
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
+    amps = amplicons_of(a, (hdr_names, shift))      # (each contig's amplicons shifted by its slot; none left: an argument error)
+    seen["amplicons"] = len(amps) if amps else 0
     axis_ref = axis_reference(records, hdr_names, shift, axis_len) if a.variant_table is not None else None
     var = dict(variants_of(a), ref=axis_ref) if axis_ref is not None else None
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
                                                                  threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
-                                                                 min_baseq=a.min_baseq, primers=prm, variants=var)
+                                                                 min_baseq=a.min_baseq, primers=prm, variants=var,
+                                                                 intervals=(amplicon_intervals(amps), mincov) if amps else None)
     seen.setdefault("reads_primer_masked", 0)
     table = seen.pop("variant_table", None)
     seen["variant_records"] = 0 if table is None else len(table)
+    arecs = seen.pop("amplicon_table", None)
+    seen["amplicons_below"] = 0 if arecs is None else int((arecs["below"] > 0).sum())
 
     # every contig's slice of the call records (the call is position-local: a slice's records are the split run's)
     per = []
@@ -253,6 +265,8 @@ def run(a):
         for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]):
             parts.append((table[(table["pos"] >= s) & (table["pos"] < s + len(seq))], rid, axis_ref, s))
         write_variant_table(a.variant_table, parts)
+    if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
+        write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
     with open(a.output, "w") as out:
         out.write("".join(fa))
     return dict({"contigs": len(records), "dropped_reads": int(dropped)}, **seen)

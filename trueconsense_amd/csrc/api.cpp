@@ -5,10 +5,13 @@
 #include <cstring>
 #include <string>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
+#include <new>
 #include <thread>
 
 #include "tcmi_internal.h"
+#include "intervals_rule.h"
 #include "primer_table.h"
 
 static thread_local std::string g_err;
@@ -207,6 +210,8 @@ int tcmi_ctx_destroy(tcmi_ctx *c)
     if (c->d_var_scr) (void)hipFree(c->d_var_scr);
     if (c->h_var_rec) (void)hipHostFree(c->h_var_rec);
     if (c->h_var_tot) (void)hipHostFree(c->h_var_tot);
+    if (c->d_iv) (void)hipFree(c->d_iv);
+    if (c->h_iv_rec) (void)hipHostFree(c->h_iv_rec);
     if (c->step_done) (void)hipEventDestroy(c->step_done);
     if (c->ev_after_sym) (void)hipEventDestroy(c->ev_after_sym);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -763,7 +768,116 @@ int tcmi_step_variants(tcmi_ctx *c, const tcmi_variant **records, int64_t *n)
     return TCMI_OK;
 }
 
-// The launches of one step on ctx->stream: [memset] tally, [the variant table's three,] call.  When the counts are not wanted on the host the
+// ---- amplicon table (intervals.hip) --------------------------------------------------------------
+} // extern "C"
+
+static int iv_check(tcmi_ctx *ctx, int64_t n, const int64_t *start, const int64_t *end, int32_t min_depth)
+{
+    int64_t bad = -1;
+    switch (tcmi_intervals_check(n, start, end, min_depth, &bad)) {
+    case 0: return TCMI_OK;
+    case 1: return tcmi_fail(ctx, TCMI_E_ARG, "intervals: n = %lld is outside 0..%d", (long long)n, (int)TCMI_IV_MAX_N);
+    case 2: return tcmi_fail(ctx, TCMI_E_ARG, "intervals: min_depth %d is negative", (int)min_depth);
+    case 3: return tcmi_fail(ctx, TCMI_E_ARG, "intervals: interval %lld, [%lld, %lld), does not satisfy 0 <= start <= end <= 2^29", (long long)bad,
+                             (long long)start[bad], (long long)end[bad]);
+    default: return tcmi_fail(ctx, TCMI_E_ARG, "intervals: n = %lld without both arrays", (long long)n);
+    }
+}
+
+extern "C" {
+
+int tcmi_interval_stats_dev(tcmi_ctx *ctx, const void *d_counts, int64_t L, int64_t ld, int64_t n, const void *d_start, const void *d_end,
+                            int32_t min_depth, void *d_records)
+{
+    if (!ctx || !d_counts) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
+    if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld");
+    if (L > INT32_MAX - 1024) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "L too large");
+    if (n < 0 || n > TCMI_IV_MAX_N) return tcmi_fail(ctx, TCMI_E_ARG, "intervals: n = %lld is outside 0..%d", (long long)n, (int)TCMI_IV_MAX_N);
+    if (min_depth < 0) return tcmi_fail(ctx, TCMI_E_ARG, "intervals: min_depth %d is negative", (int)min_depth);
+    if (n == 0) return TCMI_OK;
+    if (!d_start || !d_end || !d_records) return tcmi_fail(ctx, TCMI_E_ARG, "intervals: n = %lld without its arrays", (long long)n);
+    if (reinterpret_cast<uintptr_t>(d_counts) % 4 || reinterpret_cast<uintptr_t>(d_records) % 4)
+        return tcmi_fail(ctx, TCMI_E_ARG, "d_counts and d_records must be aligned to 4 bytes");
+    if (reinterpret_cast<uintptr_t>(d_start) % 8 || reinterpret_cast<uintptr_t>(d_end) % 8)
+        return tcmi_fail(ctx, TCMI_E_ARG, "d_start and d_end must be aligned to 8 bytes");
+    TCMI_HIP(ctx, hipSetDevice(ctx->device));
+    // the kernel trusts its intervals: they are looked at here (16 bytes each; the call waits for the stream anyway)
+    const std::unique_ptr<int64_t[]> se(new (std::nothrow) int64_t[(size_t)2 * n]);       // (no exception may cross the C ABI)
+    if (!se) return tcmi_fail(ctx, TCMI_E_NOMEM, "intervals: no host memory for %lld intervals", (long long)n);
+    TCMI_HIP(ctx, hipMemcpy(se.get(), d_start, (size_t)n * 8, hipMemcpyDeviceToHost));
+    TCMI_HIP(ctx, hipMemcpy(se.get() + n, d_end, (size_t)n * 8, hipMemcpyDeviceToHost));
+    int rc = iv_check(ctx, n, se.get(), se.get() + n, min_depth);
+    if (rc) return rc;
+    const tcmi_iv_job j = {(const int32_t *)d_counts, L, ld, n, (const int64_t *)d_start, (const int64_t *)d_end, min_depth, (tcmi_interval_stat *)d_records};
+    rc = tcmi_launch_intervals(ctx, j);
+    if (rc) return rc;
+    TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return TCMI_OK;
+}
+
+int tcmi_interval_stats(tcmi_ctx *ctx, const int32_t *counts, int64_t L, int64_t n, const int64_t *start, const int64_t *end,
+                        int32_t min_depth, tcmi_interval_stat *records)
+{
+    if (!ctx || !counts) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
+    if (L <= 0) return tcmi_fail(ctx, TCMI_E_ARG, "L must be positive");
+    int rc = iv_check(ctx, n, start, end, min_depth);
+    if (rc) return rc;
+    if (n == 0) return TCMI_OK;
+    if (!records) return tcmi_fail(ctx, TCMI_E_ARG, "intervals: n = %lld without room for the records", (long long)n);
+    rc = ensure_ws(ctx, L);
+    if (rc) return rc;
+    ctx->counts_clean = false;
+    rc = tcmi_counts_upload(ctx, counts, L, ctx->ws_ld, ctx->d_counts);
+    if (rc) return rc;
+    int64_t *d_se = nullptr;
+    tcmi_interval_stat *d_rec = nullptr;
+    TCMI_HIP(ctx, hipMalloc((void **)&d_se, (size_t)2 * n * 8));
+    hipError_t e = hipMemcpy(d_se, start, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_se + n, end, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc((void **)&d_rec, (size_t)n * sizeof(tcmi_interval_stat));
+    if (e != hipSuccess) rc = tcmi_fail(ctx, TCMI_E_HIP, "intervals: device buffers: %s", hipGetErrorString(e));
+    if (!rc) rc = tcmi_interval_stats_dev(ctx, ctx->d_counts, L, ctx->ws_ld, n, d_se, d_se + n, min_depth, d_rec);
+    if (!rc) {
+        e = hipMemcpy(records, d_rec, (size_t)n * sizeof(tcmi_interval_stat), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = tcmi_fail(ctx, TCMI_E_HIP, "intervals: record download failed: %s", hipGetErrorString(e));
+    }
+    if (d_se) (void)hipFree(d_se);
+    if (d_rec) (void)hipFree(d_rec);
+    return rc;
+}
+
+int tcmi_ctx_set_intervals(tcmi_ctx *c, int64_t n, const int64_t *start, const int64_t *end, int32_t min_depth)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    if (c->step_L > 0) return tcmi_fail(c, TCMI_E_ARG, "tcmi_ctx_set_intervals between tcmi_step_begin and tcmi_step_end");
+    if (n == 0) { c->iv_on = false; c->iv_valid = false; return TCMI_OK; }       // (the buffers stay until the next setting or the end)
+    const int rc = iv_check(c, n, start, end, min_depth);
+    if (rc) return rc;
+    TCMI_HIP(c, hipSetDevice(c->device));
+    TCMI_HIP(c, hipStreamSynchronize(c->stream));             // (nothing queued may still read the intervals or write the records)
+    c->iv_on = false; c->iv_valid = false;
+    if (c->d_iv) { (void)hipFree(c->d_iv); c->d_iv = nullptr; }
+    if (c->h_iv_rec) { (void)hipHostFree(c->h_iv_rec); c->h_iv_rec = nullptr; }
+    c->iv_n = 0;
+    TCMI_HIP(c, hipMalloc((void **)&c->d_iv, (size_t)2 * n * 8));
+    TCMI_HIP(c, hipMemcpy(c->d_iv, start, (size_t)n * 8, hipMemcpyHostToDevice));
+    TCMI_HIP(c, hipMemcpy(c->d_iv + n, end, (size_t)n * 8, hipMemcpyHostToDevice));
+    TCMI_HIP(c, hipHostMalloc((void **)&c->h_iv_rec, (size_t)n * sizeof(tcmi_interval_stat), hipHostMallocDefault));
+    c->iv_n = n; c->iv_min_depth = min_depth; c->iv_on = true;
+    return TCMI_OK;
+}
+
+int tcmi_step_intervals(tcmi_ctx *c, const tcmi_interval_stat **records, int64_t *n)
+{
+    if (!c || !records || !n) return tcmi_fail(c, TCMI_E_ARG, "null argument");
+    *records = nullptr; *n = 0;
+    if (c->step_L > 0) return tcmi_fail(c, TCMI_E_ARG, "tcmi_step_intervals: the context's step has not been ended");
+    if (!c->iv_valid) return tcmi_fail(c, TCMI_E_ARG, "tcmi_step_intervals: the last step computed no interval records (tcmi_ctx_set_intervals)");
+    *records = c->h_iv_rec; *n = c->iv_n;
+    return TCMI_OK;
+}
+
+// The launches of one step on ctx->stream: [memset] tally, [the variant table's three,] [the amplicon table's one,] call.  When the counts are not wanted on the host the
 // call kernel zeroes them behind itself and the next step into this workspace needs no memset.  The call records
 // (3 bytes per position) go straight to the pinned host buffer: the kernel's own stores cross PCIe, which saves a
 // separate copy and one launch boundary per step.
@@ -777,6 +891,11 @@ static int enqueue_step(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int32_
     if (rc) return rc;
     if (ctx->var_on) {              // the variant table: behind the tally, in front of the call kernel, which may zero the matrix
         rc = enqueue_variants(ctx, L);
+        if (rc) return rc;
+    }
+    if (ctx->iv_on) {               // the amplicon table: the same slot (both only read the matrix)
+        const tcmi_iv_job j = {ctx->d_counts, L, ld, ctx->iv_n, ctx->d_iv, ctx->d_iv + ctx->iv_n, ctx->iv_min_depth, ctx->h_iv_rec};
+        rc = tcmi_launch_intervals(ctx, j);
         if (rc) return rc;
     }
     rc = tcmi_launch_call(ctx, ctx->d_counts, L, ld, mincov, include_ambig, want_counts ? 0 : 1, ctx->h_rec, ctx->h_rec + ld,
@@ -821,6 +940,8 @@ int tcmi_step_begin_deferred(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, i
     if (ctx->step_L > 0 || ctx->call_pending) return tcmi_fail(ctx, TCMI_E_ARG, "tcmi_step_begin: the previous step of this context has not been ended");
     if (ctx->var_on)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "a variant table (--variant-table, tcmi_ctx_set_variants) is set on this context: the array pipeline's ride-along steps compute none; use tcmi_step or the file runner");
+    if (ctx->iv_on)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "an amplicon table (--amplicon-table, tcmi_ctx_set_intervals) is set on this context: the array pipeline's ride-along steps compute none; use tcmi_step or the file runner");
     int rc = ensure_ws(ctx, L);
     if (rc) return rc;
     TCMI_HIP(ctx, hipSetDevice(ctx->device));
@@ -859,6 +980,7 @@ int tcmi_step_begin_deferred(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, i
     ctx->step_L = L;
     ctx->step_counts = false;
     ctx->step_var = false;
+    ctx->step_iv = false;
     return TCMI_OK;
 }
 
@@ -886,6 +1008,7 @@ int tcmi_step_begin(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int32_t mi
     ctx->step_L = L;
     ctx->step_counts = want_counts != 0;
     ctx->step_var = ctx->var_on;
+    ctx->step_iv = ctx->iv_on;
     return TCMI_OK;
 }
 
@@ -906,6 +1029,7 @@ int tcmi_step_end(tcmi_ctx *ctx, const uint8_t **plain, const uint8_t **alt, con
     if (counts_planes) *counts_planes = ctx->step_counts ? ctx->h_counts : nullptr;
     if (ld_out) *ld_out = ld;
     ctx->var_valid = ctx->step_var;
+    ctx->iv_valid = ctx->step_iv;
     if (ctx->step_var) ctx->var_n = std::min(ctx->step_L, ctx->var_n_ref) > 0 ? (int64_t)ctx->h_var_tot[0] : 0;
     ctx->step_L = 0;
     return TCMI_OK;

@@ -347,6 +347,10 @@ int tcmi_pipeline_run_batched(tcmi_pipeline *p, int64_t n_items, const tcmi_read
         if (c->var_on)
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries a variant table setting (--variant-table, tcmi_ctx_set_variants): the array "
                              "pipeline's steps compute none; use tcmi_step or the file runner");
+    for (const tcmi_ctx *c : p->slots)                          // (... and no amplicon table, likewise)
+        if (c->iv_on)
+            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries an amplicon table setting (--amplicon-table, tcmi_ctx_set_intervals): the array "
+                             "pipeline's steps compute none; use tcmi_step or the file runner");
     p->batch = batch;
     p->pos_stride = batch > 1 ? pos_stride : 0;
     const int64_t L_gpu = batch > 1 ? (int64_t)batch * pos_stride : L;   // positions one step covers
@@ -520,6 +524,8 @@ struct OutFiles {                       // per item; an entry may be NULL (not w
     const char *const *fasta, *const *vcf, *const *gff, *const *doc;
     const char *const *table;           // the variant table (tcmi_filerunner_run_files_table); n_variants: its records per item, or NULL
     int64_t *n_variants;
+    int64_t n_intervals;                // the amplicon table (tcmi_filerunner_run_files_stats): item i's records go to stats[i * n_intervals ...)
+    tcmi_interval_stat *stats;
 };
 
 int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, const char *const *names, int64_t ref_len,
@@ -635,6 +641,14 @@ int filerunner_core(tcmi_filerunner *r, int64_t n, const char *const *paths, con
                             int64_t nv = 0;
                             rc = tcmi_step_variants(ctx, &vr, &nv);
                             if (!rc) it.var.assign(vr, vr + nv);
+                        }
+                        if (!rc && files && files->stats) {                  // ... and its amplicon records (one writer per item: no lock)
+                            const tcmi_interval_stat *ir = nullptr;
+                            int64_t ni = 0;
+                            rc = tcmi_step_intervals(ctx, &ir, &ni);
+                            if (!rc && ni != files->n_intervals)
+                                rc = tcmi_fail(ctx, TCMI_E_ARG, "%s: the step computed %lld interval records, the run asked for %lld", paths[i], (long long)ni, (long long)files->n_intervals);
+                            if (!rc) std::memcpy(files->stats + (size_t)i * (size_t)ni, ir, (size_t)ni * sizeof(tcmi_interval_stat));
                         }
                     }
                     if (!rc) {
@@ -820,7 +834,7 @@ int tcmi_filerunner_run_files(tcmi_filerunner *r, int64_t n, const char *const *
 {
     if (!r || !fasta) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
     if ((vcf || gff) && r->gff_cols.size() != 6 * r->orf_start.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "tcmi_filerunner_set_outputs first");
-    const OutFiles f = {fasta, vcf, gff, doc, nullptr, nullptr};
+    const OutFiles f = {fasta, vcf, gff, doc, nullptr, nullptr, 0, nullptr};
     return filerunner_core(r, n, paths, names, ref_len, mincov, include_ambig, device_decode, nullptr, 0, nullptr, status, stage_seconds, decoded_on, &f);
 }
 
@@ -833,6 +847,18 @@ int tcmi_filerunner_run_files_table(tcmi_filerunner *r, int64_t n, const char *c
                                     int32_t mincov, int include_ambig, int device_decode, int32_t *status, double *stage_seconds, int64_t *decoded_on,
                                     int64_t *n_variants)
 {
+    return tcmi_filerunner_run_files_stats(r, n, paths, names, fasta, vcf, gff, doc, table, ref_len, mincov, include_ambig, device_decode, status,
+                                           stage_seconds, decoded_on, n_variants, 0, nullptr);
+}
+
+// ... and the amplicon table's records: the runner's contexts carry the setting (tcmi_ctx_set_intervals, the same n_intervals on all of
+// them), the GPU stage copies the step's records into stats[i * n_intervals ...).  A sample that went to the host-reader fallback gets
+// its records too: its step goes through tcmi_step.  The table's text is the caller's (tcmi_amplicons_text).
+int tcmi_filerunner_run_files_stats(tcmi_filerunner *r, int64_t n, const char *const *paths, const char *const *names, const char *const *fasta,
+                                    const char *const *vcf, const char *const *gff, const char *const *doc, const char *const *table, int64_t ref_len,
+                                    int32_t mincov, int include_ambig, int device_decode, int32_t *status, double *stage_seconds, int64_t *decoded_on,
+                                    int64_t *n_variants, int64_t n_intervals, tcmi_interval_stat *stats)
+{
     if (!r || !fasta) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
     if ((vcf || gff || table) && r->gff_cols.size() != 6 * r->orf_start.size()) return tcmi_fail(nullptr, TCMI_E_ARG, "tcmi_filerunner_set_outputs first");
     bool any = false;
@@ -842,7 +868,12 @@ int tcmi_filerunner_run_files_table(tcmi_filerunner *r, int64_t n, const char *c
     for (const tcmi_ctx *c : r->ctxs)
         if (any && !c->var_on) return tcmi_fail(nullptr, TCMI_E_ARG, "a variant table is asked for: tcmi_ctx_set_variants on every context of the runner first");
     for (int64_t i = 0; n_variants && i < n; ++i) n_variants[i] = 0;
-    const OutFiles f = {fasta, vcf, gff, doc, table, n_variants};
+    if (n_intervals < 0 || (n_intervals > 0) != (stats != nullptr)) return tcmi_fail(nullptr, TCMI_E_ARG, "n_intervals and stats go together");
+    for (const tcmi_ctx *c : r->ctxs)
+        if (stats && (!c->iv_on || c->iv_n != n_intervals))
+            return tcmi_fail(nullptr, TCMI_E_ARG, "amplicon records are asked for: tcmi_ctx_set_intervals with %lld intervals on every context of the runner first", (long long)n_intervals);
+    if (stats && n > 0) std::memset(stats, 0, (size_t)n * (size_t)n_intervals * sizeof(tcmi_interval_stat));
+    const OutFiles f = {fasta, vcf, gff, doc, table, n_variants, n_intervals, stats};
     return filerunner_core(r, n, paths, names, ref_len, mincov, include_ambig, device_decode, nullptr, 0, nullptr, status, stage_seconds, decoded_on, &f);
 }
 

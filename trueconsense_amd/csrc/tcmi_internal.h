@@ -190,6 +190,16 @@ struct tcmi_ctx {
     bool step_var = false;           // the step that is under way (step_L > 0) computes a table
     bool var_valid = false;          // the last ended step computed one: var_n records in h_var_rec (tcmi_step_variants)
     int64_t var_n = 0;
+    // the amplicon table (tcmi_ctx_set_intervals; intervals.hip): the setting — a device copy of iv_n intervals (d_iv: the starts, then
+    // the ends) and the bound — under which every tcmi_step_begin launches the kernel between the tally and the call, its records
+    // going to pinned memory sized iv_n (h_iv_rec)
+    bool iv_on = false;
+    int64_t iv_n = 0;
+    int32_t iv_min_depth = 0;
+    int64_t *d_iv = nullptr;
+    tcmi_interval_stat *h_iv_rec = nullptr;
+    bool step_iv = false;            // the step that is under way (step_L > 0) computes the records
+    bool iv_valid = false;           // the last ended step computed them (tcmi_step_intervals)
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_one_sync_retried = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
@@ -373,6 +383,15 @@ struct tcmi_var_job {
     tcmi_variant *records; int64_t cap;
 };
 int tcmi_launch_variants(tcmi_ctx *ctx, const tcmi_var_job &job);
+
+// the amplicon table's launch (intervals.hip) on the context's stream: one workgroup per interval, 0 < n <= 65 536 checked intervals
+struct tcmi_iv_job {
+    const int32_t *counts; int64_t L, ld;
+    int64_t n; const int64_t *start, *end;
+    int32_t min_depth;
+    tcmi_interval_stat *records;
+};
+int tcmi_launch_intervals(tcmi_ctx *ctx, const tcmi_iv_job &job);
 
 static inline int64_t tcmi_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 static inline size_t tcmi_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }     // the pieces of device buffers start on 256 bytes

@@ -69,6 +69,41 @@ def variants_text(records, region, ref, pos_offset=0):
     return buf.raw[:ln.value].decode("latin-1")
 
 
+# struct tcmi_interval_stat: the amplicon table's record of one interval of the coverage plane
+INTERVAL_DTYPE = np.dtype([("sum", np.int64), ("n", np.int32), ("min", np.int32), ("min_pos", np.int32), ("median", np.int32),
+                           ("below", np.int32), ("reserved", np.int32)])
+AMPLICONS_HEADER = "SAMPLE\tREGION\tAMPLICON\tPOOL\tSTART\tEND\tLEN\tMEAN\tMEDIAN\tMIN\tMIN_POS\tBELOW\n"
+INTERVAL_STAGE = 4096            # TCMI_INTERVAL_STAGE: columns of an interval the kernel stages in LDS
+
+
+def _intervals(intervals):
+    """[(start, end)] or an [n, 2] array -> (int64 starts, int64 ends), contiguous"""
+    iv = np.asarray(intervals, np.int64).reshape(-1, 2)
+    return np.ascontiguousarray(iv[:, 0]), np.ascontiguousarray(iv[:, 1])
+
+
+def amplicons_text(records, sample, region, names, pools, starts, pos_offset=0):
+    """The table's rows for `records` (tcmi_amplicons_text, the one writer; HOST): SAMPLE, REGION, AMPLICON = names[i], POOL =
+    pools[i], START = starts[i] - pos_offset + 1, END, LEN, MEAN, MEDIAN, MIN, MIN_POS, BELOW.  -> str, without the header line
+    (AMPLICONS_HEADER)."""
+    records = np.ascontiguousarray(records, INTERVAL_DTYPE)
+    n = len(records)
+    starts = np.ascontiguousarray(starts, np.int64)
+    if not (len(names) == len(pools) == len(starts) == n):
+        raise ValueError("amplicons_text: %d records, %d names, %d pools, %d starts" % (n, len(names), len(pools), len(starts)))
+    nm = (C.c_char_p * max(n, 1))(*[str(x).encode() for x in names])
+    pl = (C.c_char_p * max(n, 1))(*[str(x).encode() for x in pools])
+    args = (ptr(records) if n else None, n, str(sample).encode(), str(region).encode(), nm, pl, ptr(starts) if n else None, int(pos_offset))
+    ln = C.c_int64(0)
+    rc = lib().tcmi_amplicons_text(*args, None, 0, C.byref(ln))             # the sizing call
+    if not rc:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib().tcmi_amplicons_text(*args, C.cast(buf, C.c_void_p), ln.value, C.byref(ln))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_amplicons_text: a record does not fit its start or the offset")
+    return buf.raw[:ln.value].decode("utf-8", "replace")
+
+
 def _grab(vp, dtype, n):
     """n items of dtype at address vp (memory the library owns) -> a fresh numpy array."""
     out = np.empty(n, dtype)
@@ -304,6 +339,42 @@ class Context:
         check(lib().tcmi_variants(self.handle, ptr(counts), L, ptr(ref) if len(ref) else None, len(ref), num, den, int(min_alt_depth),
                                   int(min_depth), ptr(out), cap, C.byref(n)), self.handle)
         return out[:n.value].copy()
+
+    def set_intervals(self, intervals=None, min_depth=0):
+        """Amplicon table (tcmi_ctx_set_intervals): from now on every step of this context (step, bamfile_step) also computes, per
+        interval [start, end) of the count matrix's axis, the coverage plane's sum, minimum with its first position, lower median and
+        the positions below min_depth — step_intervals() has them.  The array Pipeline refuses while it is set.  None or empty: no
+        table."""
+        if intervals is None or len(intervals) == 0:
+            check(lib().tcmi_ctx_set_intervals(self.handle, 0, None, None, 0), self.handle)
+            return
+        st, en = _intervals(intervals)
+        check(lib().tcmi_ctx_set_intervals(self.handle, len(st), ptr(st), ptr(en), int(min_depth)), self.handle)
+
+    def step_intervals(self):
+        """The interval records of the last ended step (tcmi_step_intervals) as a fresh structured array (INTERVAL_DTYPE); raises
+        TcmiError(E_ARG) when that step computed none."""
+        p, n = C.c_void_p(), C.c_int64(0)
+        check(lib().tcmi_step_intervals(self.handle, C.byref(p), C.byref(n)), self.handle)
+        return _grab(p, INTERVAL_DTYPE, n.value)
+
+    def interval_stats_dev(self, d_counts, L, ld, n, d_start, d_end, min_depth, d_records):
+        """Device-resident records (tcmi_interval_stats_dev): int32 [7][ld] planes, int64 starts and ends at device addresses -> n
+        records at `d_records` (device or pinned host address)."""
+        check(lib().tcmi_interval_stats_dev(self.handle, C.c_void_p(int(d_counts)), int(L), int(ld), int(n), C.c_void_p(int(d_start)) if d_start else None,
+                                            C.c_void_p(int(d_end)) if d_end else None, int(min_depth), C.c_void_p(int(d_records)) if d_records else None),
+              self.handle)
+
+    def interval_stats(self, counts, intervals, min_depth=0):
+        """counts [L,7] and [(start, end)] on their axis -> one record per interval, a structured array (INTERVAL_DTYPE), in the order
+        given (tcmi_interval_stats)."""
+        counts = np.ascontiguousarray(counts, np.int32)
+        st, en = _intervals(intervals)
+        out = np.zeros(len(st), INTERVAL_DTYPE)
+        if len(st) == 0:
+            return out
+        check(lib().tcmi_interval_stats(self.handle, ptr(counts), len(counts), len(st), ptr(st), ptr(en), int(min_depth), ptr(out)), self.handle)
+        return out
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
@@ -773,9 +844,10 @@ class FileRunner:
     (tcmi_bam_load, `decode_threads` threads) and packed from its flat arrays.  `seconds` accumulates each stage's busy time."""
 
     def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None,
-                 min_baseq=0, primers=None, variants=None):
+                 min_baseq=0, primers=None, variants=None, intervals=None):
         """variants: the keyword arguments of Context.set_variants (ref, min_af, min_alt_depth, min_depth), set on every context of the
-        runner: run_files(table=...) then writes each sample's variant table."""
+        runner: run_files(table=...) then writes each sample's variant table.  intervals = ([(start, end)], min_depth)
+        (Context.set_intervals), likewise: run_files(stats=True) then returns every sample's interval records."""
         device = ctx.device if isinstance(ctx, Context) else int(ctx)
         self.mincov, self.amb = int(mincov), bool(include_ambig)
         h = C.c_void_p()
@@ -797,6 +869,9 @@ class FileRunner:
             c.apply(read_filter, min_baseq or None, primers)
             if variants:
                 c.set_variants(**variants)
+            if intervals:
+                c.set_intervals(*intervals)
+        self.n_intervals = len(intervals[0]) if intervals else 0
 
     @property
     def contexts(self):
@@ -848,13 +923,16 @@ class FileRunner:
         check(lib().tcmi_filerunner_set_outputs(self.handle, str(ref_id).encode(), str(ref_seq).encode(), str(vcf_head).encode(),
                                                 str(gff_head).encode(), len(gff_row_columns), arr))
 
-    def run_files(self, paths, names, fasta, vcf=None, gff=None, doc=None, ref_len=0, table=None):
+    def run_files(self, paths, names, fasta, vcf=None, gff=None, doc=None, ref_len=0, table=None, stats=False):
         """BAM files -> per sample its consensus FASTA and (lists, entries may be None) VCF, corrected GFF, coverage TSV and — table,
         with the runner's `variants` setting — variant table, all written by the native runner's walker threads.  Raises what the reference raises (KeyError, ZeroDivisionError) for the first
-        sample that fails; last_status has every sample's code."""
+        sample that fails; last_status has every sample's code.  stats (with the runner's `intervals` setting): -> the samples'
+        interval records, a structured array [n samples, n intervals] (INTERVAL_DTYPE)."""
         n = len(paths)
+        if stats and not self.n_intervals:
+            raise ValueError("run_files(stats=True) needs the runner's intervals= setting")
         if n == 0:
-            return
+            return np.zeros((0, self.n_intervals), INTERVAL_DTYPE) if stats else None
         def arr(xs):
             if xs is None:
                 return None
@@ -862,7 +940,14 @@ class FileRunner:
         status = np.zeros(n, np.int32)
         sec = (C.c_double * 4)()
         on = (C.c_int64 * 2)()
-        if table is None:
+        recs = np.zeros((n, self.n_intervals), INTERVAL_DTYPE) if stats else None
+        if stats:
+            n_var = np.zeros(n, np.int64)
+            rc = lib().tcmi_filerunner_run_files_stats(self.handle, n, arr(paths), arr(names), arr(fasta), arr(vcf), arr(gff), arr(doc), arr(table),
+                                                       int(ref_len), self.mincov, int(self.amb), int(bool(self.device_decode)), ptr(status), sec, on,
+                                                       ptr(n_var), self.n_intervals, ptr(recs))
+            self.variant_records += int(n_var.sum())
+        elif table is None:
             rc = lib().tcmi_filerunner_run_files(self.handle, n, arr(paths), arr(names), arr(fasta), arr(vcf), arr(gff), arr(doc), int(ref_len),
                                                  self.mincov, int(self.amb), int(bool(self.device_decode)), ptr(status), sec, on)
         else:
@@ -873,6 +958,7 @@ class FileRunner:
             self.variant_records += int(n_var.sum())
         self._account(status, sec, on)
         _check_walk(rc, (lib().tcmi_last_error(None) or b"").decode("utf-8", "replace"), KeyError)
+        return recs
 
     def close(self):
         if self.handle:

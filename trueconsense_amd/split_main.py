@@ -28,7 +28,7 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import GetArgs, primers_of, read_filter_of, variants_of, write_variant_table
+    from .TrueConsense import GetArgs, amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_table, write_variant_table
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
     torch.cuda.set_device(device)
@@ -60,6 +60,10 @@ def main(argv=None):
             if a.variant_table is not None:                          # (from the reduced counts, as the single-GPU command line from its own)
                 recs = _state.default_context().variants(index.counts, refseq, **variants_of(a))
                 write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
+            amps = amplicons_of(a)
+            if amps:                                                 # (likewise the amplicon table)
+                arecs = _state.default_context().interval_stats(index.counts, amplicon_intervals(amps), a.coverage_level)
+                write_amplicon_table(a.amplicon_table, [(a.samplename, arecs)], amps)
             WriteOutputs(a.coverage_level, index, gffdict, td._Tokens(toks), a.noambiguity is False, a.variants, a.samplename, a.reference,
                          a.output_gff, IndexGff.header, a.output)
     except Exception as e:                                           # noqa: BLE001 — every rank must reach the group's teardown
