@@ -344,11 +344,11 @@ int tcmi_pipeline_run_batched(tcmi_pipeline *p, int64_t n_items, const tcmi_read
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context holds a primer table (--primers): the array pipeline runs read sets uploaded "
                              "from flat arrays, which the host packer packs without a primer mask");
     for (const tcmi_ctx *c : p->slots)                          // (... and no variant table: nobody would fetch its records)
-        if (c->var_on)
+        if (tcmi_var_table_on(c))
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries a variant table setting (--variant-table, tcmi_ctx_set_variants): the array "
                              "pipeline's steps compute none; use tcmi_step or the file runner");
     for (const tcmi_ctx *c : p->slots)                          // (... and no amplicon table, likewise)
-        if (c->iv_on)
+        if (tcmi_iv_table_on(c))
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries an amplicon table setting (--amplicon-table, tcmi_ctx_set_intervals): the array "
                              "pipeline's steps compute none; use tcmi_step or the file runner");
     p->batch = batch;
@@ -866,11 +866,11 @@ int tcmi_filerunner_run_files_stats(tcmi_filerunner *r, int64_t n, const char *c
     if (any && r->ref_seq.empty())                              // (the rows' REGION and REF; the GFF rows above may be none at all)
         return tcmi_fail(nullptr, TCMI_E_ARG, "a variant table is asked for: tcmi_filerunner_set_outputs (the reference's id and sequence) first");
     for (const tcmi_ctx *c : r->ctxs)
-        if (any && !c->var_on) return tcmi_fail(nullptr, TCMI_E_ARG, "a variant table is asked for: tcmi_ctx_set_variants on every context of the runner first");
+        if (any && !tcmi_var_table_on(c)) return tcmi_fail(nullptr, TCMI_E_ARG, "a variant table is asked for: tcmi_ctx_set_variants on every context of the runner first");
     for (int64_t i = 0; n_variants && i < n; ++i) n_variants[i] = 0;
     if (n_intervals < 0 || (n_intervals > 0) != (stats != nullptr)) return tcmi_fail(nullptr, TCMI_E_ARG, "n_intervals and stats go together");
     for (const tcmi_ctx *c : r->ctxs)
-        if (stats && (!c->iv_on || c->iv_n != n_intervals))
+        if (stats && (!tcmi_iv_table_on(c) || tcmi_iv_table_n(c) != n_intervals))
             return tcmi_fail(nullptr, TCMI_E_ARG, "amplicon records are asked for: tcmi_ctx_set_intervals with %lld intervals on every context of the runner first", (long long)n_intervals);
     if (stats && n > 0) std::memset(stats, 0, (size_t)n * (size_t)n_intervals * sizeof(tcmi_interval_stat));
     const OutFiles f = {fasta, vcf, gff, doc, table, n_variants, n_intervals, stats};

@@ -148,6 +148,34 @@ struct tcmi_dev_arena {                  // grow-only device scratch of a contex
     size_t cap = 0, used = 0;
 };
 
+// ---- the per-step tables (tables.cpp): settings of a context under which every tcmi_step_begin launches the table's kernels between
+// the tally and the call (both only read the matrix), their records going to pinned memory the setting owns, fetched after
+// tcmi_step_end.  on: the setting is set; in_step: the step under way (step_L > 0) computes the table; valid: the last ended step did.
+// release(): the setting's buffers, for the setter that replaces the setting (nothing queued uses them any more) and for teardown.
+// The variant table (variants.hip): a device copy of the reference on the matrix's axis and the rule; h_rec holds 5 * n_ref records,
+// n of them valid.  Kept from setting to setting and shared with tcmi_variants_dev, grow-only: d_scr, blk_base | blk_cnt of the
+// launches for scr_blocks workgroups, and h_tot (pinned), the totals the scan kernel writes, [0] a step's, [1] tcmi_variants_dev's.
+struct tcmi_var_table {
+    bool on = false, in_step = false, valid = false;
+    tcmi_var_rule rule = {0, 1, 1, 0};
+    uint8_t *d_ref = nullptr;
+    int64_t n_ref = 0, n = 0;
+    tcmi_variant *h_rec = nullptr;
+    char *d_scr = nullptr;
+    int64_t scr_blocks = 0;
+    unsigned long long *h_tot = nullptr;
+    void release() { if (d_ref) (void)hipFree(d_ref); if (h_rec) (void)hipHostFree(h_rec); d_ref = nullptr; h_rec = nullptr; n_ref = 0; on = valid = false; }
+};
+// The amplicon table (intervals.hip): a device copy of n intervals (d_iv: the starts, then the ends) and the bound; h_rec holds n records.
+struct tcmi_iv_table {
+    bool on = false, in_step = false, valid = false;
+    int64_t n = 0;
+    int32_t min_depth = 0;
+    int64_t *d_iv = nullptr;
+    tcmi_interval_stat *h_rec = nullptr;
+    void release() { if (d_iv) (void)hipFree(d_iv); if (h_rec) (void)hipHostFree(h_rec); d_iv = nullptr; h_rec = nullptr; n = 0; on = valid = false; }
+};
+
 struct tcmi_ctx {
     int device = -1;
     tcmi_host_packed *host_packed = nullptr;
@@ -175,31 +203,8 @@ struct tcmi_ctx {
     tcmi_read_filter flt = {0, 0, 0};   // tcmi_ctx_set_read_filter: governs the read sets built from device-decoded record streams
     int32_t min_bq = 0;              // tcmi_ctx_set_min_base_quality: likewise; the flat-array entry points refuse while it is above 0
     std::shared_ptr<const tcmi_primer_dev> primers;   // tcmi_ctx_set_primers: likewise, and refused likewise while set
-    // the variant table (tcmi_ctx_set_variants; variants.hip): the setting — a device copy of the reference on the matrix's axis and
-    // the rule — under which every tcmi_step_begin launches the table's kernels between the tally and the call, their records going
-    // to pinned memory sized 5 * var_n_ref (h_var_rec); h_var_tot (pinned): the totals the scan kernel writes, [0] a step's, [1]
-    // tcmi_variants_dev's; d_var_scr: blk_cnt | blk_base of the launches, grow-only (var_scr_blocks blocks)
-    bool var_on = false;
-    tcmi_var_rule var_rule = {0, 1, 1, 0};
-    uint8_t *d_var_ref = nullptr;
-    int64_t var_n_ref = 0;
-    tcmi_variant *h_var_rec = nullptr;
-    unsigned long long *h_var_tot = nullptr;
-    char *d_var_scr = nullptr;
-    int64_t var_scr_blocks = 0;
-    bool step_var = false;           // the step that is under way (step_L > 0) computes a table
-    bool var_valid = false;          // the last ended step computed one: var_n records in h_var_rec (tcmi_step_variants)
-    int64_t var_n = 0;
-    // the amplicon table (tcmi_ctx_set_intervals; intervals.hip): the setting — a device copy of iv_n intervals (d_iv: the starts, then
-    // the ends) and the bound — under which every tcmi_step_begin launches the kernel between the tally and the call, its records
-    // going to pinned memory sized iv_n (h_iv_rec)
-    bool iv_on = false;
-    int64_t iv_n = 0;
-    int32_t iv_min_depth = 0;
-    int64_t *d_iv = nullptr;
-    tcmi_interval_stat *h_iv_rec = nullptr;
-    bool step_iv = false;            // the step that is under way (step_L > 0) computes the records
-    bool iv_valid = false;           // the last ended step computed them (tcmi_step_intervals)
+    tcmi_var_table var;              // tcmi_ctx_set_variants
+    tcmi_iv_table iv;                // tcmi_ctx_set_intervals
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_one_sync_retried = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
@@ -239,7 +244,6 @@ struct tcmi_ctx {
     std::string err;
     // profiling
     bool prof = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     struct Pending { int k; hipEvent_t a, b; };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> ev_pool;
@@ -282,6 +286,32 @@ void *tcmi_ctx_pinned(tcmi_ctx *ctx, size_t bytes);             // >= bytes of t
             return tcmi_fail((ctx), TCMI_E_HIP, "%s failed: %s (%s:%d)", #call,               \
                              hipGetErrorString(e__), __FILE__, __LINE__);                     \
     } while (0)
+
+// a temporary device allocation of a host-buffer convenience: freed on every way out
+struct tcmi_dev_tmp {
+    void *p = nullptr;
+    tcmi_dev_tmp() = default;
+    tcmi_dev_tmp(const tcmi_dev_tmp &) = delete;
+    tcmi_dev_tmp &operator=(const tcmi_dev_tmp &) = delete;
+    ~tcmi_dev_tmp() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+};
+// what api.cpp, tables.cpp, step.cpp and split_step.cpp call of each other stays out of the library's symbol table
+#define TCMI_LOCAL __attribute__((visibility("hidden")))
+// the workspace of tcmi_step and the host-buffer conveniences (api.cpp): _ensure makes it hold L positions (grow-only); _load_counts
+// makes it large enough and loads a host [L][7] matrix into it
+TCMI_LOCAL int tcmi_ws_ensure(tcmi_ctx *ctx, int64_t L);
+TCMI_LOCAL int tcmi_ws_load_counts(tcmi_ctx *ctx, const int32_t *counts, int64_t L);
+// the tables in a step (tables.cpp): _enqueue launches whatever is on over the workspace matrix; _step_begin marks what the step that
+// begins computes (nothing: a ride-along step); _step_end publishes what the step that ends (step_L still set) computed; _release
+// frees all the tables own; the rest: what the refusals of the pipeline and the runner ask
+TCMI_LOCAL int tcmi_tables_enqueue(tcmi_ctx *ctx, int64_t L);
+TCMI_LOCAL void tcmi_tables_step_begin(tcmi_ctx *ctx, bool ride_along);
+TCMI_LOCAL void tcmi_tables_step_end(tcmi_ctx *ctx);
+TCMI_LOCAL void tcmi_tables_release(tcmi_ctx *ctx);
+TCMI_LOCAL bool tcmi_var_table_on(const tcmi_ctx *ctx);
+TCMI_LOCAL bool tcmi_iv_table_on(const tcmi_ctx *ctx);
+TCMI_LOCAL int64_t tcmi_iv_table_n(const tcmi_ctx *ctx);
 
 // profiling brackets (no-ops unless enabled)
 void tcmi_prof_begin(tcmi_ctx *ctx, int k);
@@ -366,7 +396,7 @@ void *tcmi_arena_take(tcmi_ctx *ctx, size_t bytes);
 // kernels (tally.hip / call.hip)
 int tcmi_launch_tally(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts);
 int tcmi_launch_tally_fast(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts);
-// pipeline-internal: a step whose call kernel rides in the NEXT step's tally launch (api.cpp)
+// pipeline-internal: a step whose call kernel rides in the NEXT step's tally launch (step.cpp)
 int tcmi_step_begin_deferred(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int32_t mincov, int include_ambig, tcmi_ctx *prev);
 int tcmi_step_flush(tcmi_ctx *ctx);
 int tcmi_launch_call(tcmi_ctx *ctx, int32_t *d_counts, int64_t L, int64_t ld, int32_t mincov,
