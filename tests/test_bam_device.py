@@ -335,6 +335,89 @@ def test_long_reads_stay_on_the_device(ctx, tmp_path):
     assert runner.decoded_on == {"device": 1, "host": 0}
 
 
+def _block_ulens(path):
+    """ISIZE of every BGZF block of the file"""
+    raw, at, out = open(path, "rb").read(), 0, []
+    while at < len(raw):
+        size = struct.unpack_from("<H", raw, at + 16)[0] + 1
+        out.append(struct.unpack_from("<I", raw, at + size - 4)[0])
+        at += size
+    return out
+
+
+def _false_start_inside_a_record(tmp_path, fake, at):
+    """One read of 1 500 bases among short ones, in 512-byte blocks filled to the brim: its record of 2.3 KB covers whole blocks.
+    `fake` goes into its QUAL (no floor: the counts do not depend on it), at offset `at` (< 0: from the end) of a block that lies
+    wholly inside the record.  Every other QUAL byte is 30 and SEQ holds A / C / G / T only: four such bytes never read as
+    block_size < 2^24, so `fake` is the only place in the long record where the decoder's search for a record start can say yes.
+    -> (path, reads, L, that block's index, the read's index)"""
+    ref, _ = sy.make_reference(L=3000, cds=[(10, 600)])
+    mk = lambda pos, n, name: {"pos": pos, "flag": 0, "cigar": "%dM" % n, "seq": ref[pos:pos + n], "qual": [30] * n, "name": name}
+    specs = [mk(20 + 7 * k, 60, "a%d" % k) for k in range(8)] + [mk(100, 1500, "long")] + [mk(120 + 9 * k, 60, "b%d" % k) for k in range(12)]
+    which = 8
+    path = str(tmp_path / "inside.bam")
+    bamwriter.write_bam(path, ss.reads_from_spec({"reads": specs}), "r", len(ref), block=512, split_records=True)
+    rec = host_stream_and_records(path)[1]
+    qual_at, rec_end = int(rec[which]) + 36 + len("long") + 1 + 4 + 750, int(rec[which + 1])
+    assert rec_end - qual_at == 1500
+    starts = np.concatenate(([0], np.cumsum(_block_ulens(path))))
+    b = next(k for k in range(len(starts) - 1) if starts[k] >= qual_at and starts[k + 1] <= rec_end and starts[k + 1] - starts[k] == 512)
+    where = int(starts[b]) + (at if at >= 0 else 512 + at) - qual_at
+    assert 0 <= at + (512 if at < 0 else 0) <= 512 - len(fake)
+    specs[which]["qual"][where:where + len(fake)] = list(fake)
+    reads = ss.reads_from_spec({"reads": specs})
+    bamwriter.write_bam(path, reads, "r", len(ref), block=512, split_records=True)
+    stream, rec2 = host_stream_and_records(path)
+    assert np.array_equal(rec2, rec) and bytes(stream[int(starts[b]) + at % 512:][:len(fake)]) == bytes(fake)
+    return path, reads, len(ref), b, which
+
+
+def _record_head(block_size):
+    """the fixed fields the search tests, all plausible: refID 0, pos 5, l_read_name 2, one CIGAR op, l_seq 4, no mate (44 bytes needed)"""
+    return struct.pack("<IiiIIIii", block_size, 0, 5, 2, 1, 4, -1, -1)
+
+
+def test_a_false_record_start_in_the_tail_of_a_block_inside_a_record_is_withdrawn(ctx, tmp_path):
+    """In a block's last 39 bytes the search has too few bytes for its tests; with four left, 33 <= block_size < 2^24 is all.  Such
+    four bytes at the end of a block that a long record covers: rec_vouch withdraws the find (the chain says no record starts in
+    that block), both packers take the file, the record list is the true one and the counts are the oracle's."""
+    path, reads, L, b, _ = _false_start_inside_a_record(tmp_path, struct.pack("<I", 64), -4)
+    check_decode(ctx, path).close()
+    want = c_oracle.tally(reads, L)
+    try:
+        for one_sync in (1, 0):
+            ctx.set_option("one_sync", one_sync)
+            d = engine.DeviceBam(path)
+            t0 = ctx.stat("one_sync_taken")
+            rs = ctx.upload_bamfile(d)
+            assert ctx.stat("one_sync_taken") - t0 == one_sync, ctx.stat("one_sync_last_decline_flags")
+            assert rs.n_reads == reads["n_reads"] and np.array_equal(ctx.step(rs, L, 30, True)[3], want), one_sync
+            rs.free()
+            d.close()
+    finally:
+        ctx.set_option("one_sync", 1)
+
+
+@pytest.mark.parametrize("kind", ("its_chain_breaks", "its_chain_leaves_the_block"))
+def test_a_false_record_start_in_the_body_of_a_block_is_still_refused(ctx, tmp_path, kind):
+    """A whole plausible record head in the body of a block that a long record covers (the main search says yes: first + 40 <= ulen).
+    Its chain breaks on an impossible block_size: the block's inflate stopped there, its bytes behind the break are not decoded,
+    and the file is refused as a damaged one.  Or its chain leaves the block: the chain of records does not close.  rec_vouch
+    withdraws neither."""
+    if kind == "its_chain_breaks":
+        fake = _record_head(44) + bytes([30] * 16) + bytes(4)       # the "record" behind it: block_size 0
+        code, words = _ffi.E_FORMAT, "impossible block_size in BGZF block %d"
+    else:
+        fake = _record_head(2000)
+        code, words = _ffi.E_UNSUPPORTED, "the chain of alignment records does not close at BGZF block %d (found a start at 100,"
+    path, _, _, b, _ = _false_start_inside_a_record(tmp_path, fake, 100)
+    d = engine.DeviceBam(path)
+    with pytest.raises(_ffi.TcmiError) as e:
+        ctx.upload_bamfile(d)
+    d.close()
+    assert e.value.code == code and words % b in str(e.value), str(e.value)
+
+
 def test_a_damaged_stream_is_an_error(ctx, tmp_path):
     ref, _ = sy.make_reference(L=5000, cds=[(10, 600)])
     reads = sy.make_reads(ref, 4000, seed=1)

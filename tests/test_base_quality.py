@@ -3,7 +3,8 @@ below Q is skipped: nothing for coverage, A/T/C/G, X or I; nothing else about th
 committed oracle, tally_tokens(pileup_columns(reads, min_base_quality=Q)[c]) per column, zero-padded to c_oracle.extent(reads, L):
 a matched base is tested with its own QUAL byte, a D / N token with that of the next query base, a query index at or beyond l_seq
 has quality 0, a record without QUAL (0xFF) is never skipped.  Both device packers (one-sync, several-kernel), the drop variant of
-the plane tally kernel and the stream-walking kernel of long reads are driven; the flat-array entry points refuse."""
+the plane tally kernel and the stream-walking kernel of long reads are driven (on fuzzed inputs: tests/test_floor_mask_fuzz.py); the
+flat-array entry points refuse."""
 import ctypes as C
 import functools
 import gzip

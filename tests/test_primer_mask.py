@@ -2,7 +2,8 @@
 over the '+' primers that hold its first column) or from tail_start on (the smallest start over the '-' primers that hold its last
 column) are skipped exactly as tokens below the base-quality floor are; nothing else about the read changes.  The yardstick is
 tests/primer_yardstick.py (committed oracle functions only).  Both device packers (one-sync, several-kernel), the drop variant of
-the plane tally kernel and the stream-walking kernel of long reads are driven; the flat-array entry points refuse."""
+the plane tally kernel and the stream-walking kernel of long reads are driven (on fuzzed inputs: tests/test_floor_mask_fuzz.py); the
+flat-array entry points refuse."""
 import ctypes as C
 import functools
 import json

@@ -7,6 +7,7 @@
 //
 //   (bgzf_symbols.hip, bgzf_copy.hip)  bgzf_symbols + bgzf_copy: the compressed blocks -> the inflated stream and every block's record starts
 //                  (bgzf_copy also takes every block's CRC-32 against its trailer while it flushes the bytes: no pass of its own)
+//   rec_vouch      a record start "found" in a block that lies inside one record is withdrawn (one workgroup)
 //   rec_scan       the blocks' record counts -> their places in the dense array (one workgroup)
 //   rec_compact    per-block record lists -> one dense array of record offsets
 //
@@ -57,6 +58,86 @@ __global__ __launch_bounds__(1024) void rec_scan(uint32_t *n_rec, uint64_t *base
     unsigned long long run = s[t] - sum;
     for (int b = b0; b < b1; ++b) { base[b] = run; run += n_rec[b]; }
     if (t == 1023) *total = s[1023];
+}
+
+// rec_vouch: behind bgzf_copy, in front of everything that reads its per-block words (rec_scan, pk_index, pk_place, the host's chain
+// check).  A block finds its first record by plausibility, and in its last 39 bytes there is little to test (with four bytes left:
+// 33 <= block_size < 2^24), so a block that lies wholly inside one long record can "find" a start that is none.  Only the chain knows:
+// if the records in front say that the next one starts at or behind this block's end, whatever the block found is withdrawn — no
+// start, no records, as a block that found nothing.  Only a find of the tail search (first + 40 > ulen) is withdrawn: the block was then
+// inflated to its end, flushed and CRC-checked before its words were written, and its chain cannot have met a second size field.  A
+// find of the main search whose chain broke left the block's bytes undecoded behind the break: that one, like every other break,
+// stays for the chain checks to refuse.  One workgroup.  Fast path (every file whose chain closes): each lane walks a stretch of
+// blocks, the stretches are joined through LDS, and nothing is written.  Only if some find is not where its predecessors end does
+// lane 0 walk the chain once, block by block (dependent loads, a few hundred ns a block: not measured, such a file was refused
+// before), up to the first break that is not a tail find inside a record.
+__device__ inline long long vouch_over(int b, const BlockDesc *blocks, const int32_t *over, const uint32_t *n_rec, const uint32_t *rec_slot, const uint8_t *out)
+{
+    const int32_t o = over[b];
+    if (o != TAIL_UNKNOWN || !n_rec[b]) return o;
+    const uint32_t at = rec_slot[(size_t)b * MAX_REC_PER_BLOCK + n_rec[b] - 1];
+    const uint8_t *q = out + blocks[b].uout + at;
+    const uint32_t bs = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+    return bs - 32u > (1u << 28) - 32u ? -1 : (long long)at + 4 + bs - blocks[b].ulen;
+}
+__global__ __launch_bounds__(1024) void rec_vouch(const BlockDesc *blocks, uint32_t *first, int32_t *over, uint32_t *n_rec,
+                                                  const uint32_t *rec_slot, const uint8_t *out, int32_t n_own, int32_t ranged)
+{
+    __shared__ long long s_out[1024], s_sub[1024];
+    __shared__ int s_has[1024];
+    __shared__ int s_bad;
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    const int t = threadIdx.x;
+    const int per = (n_own + 1023) / 1024, b0 = min(t * per, n_own), b1 = min(b0 + per, n_own);
+    if (t == 0) s_bad = 0;
+    bool has = false, needs = false, bad = false;
+    long long st = 0, sub = 0, need = 0;             // state behind the stretch (has) / bytes of its blocks in front of its first find
+    for (int b = b0; b < b1; ++b) {
+        const int32_t entry = blocks[b].entry;
+        if (entry == -1) continue;
+        const uint32_t f = first[b];
+        if (f != NONE) {
+            if (entry < 0) {
+                if (has) bad = bad || (long long)f != st;
+                else { needs = true; need = (long long)f + sub; }
+            }
+            has = true;
+            st = vouch_over(b, blocks, over, n_rec, rec_slot, out);
+        } else if (entry >= 0) { has = true; st = (long long)entry - (long long)blocks[b].ulen; }
+        else if (has) st -= (long long)blocks[b].ulen;
+        else sub += (long long)blocks[b].ulen;
+    }
+    s_has[t] = has; s_out[t] = st; s_sub[t] = sub;
+    __syncthreads();
+    if (needs) {                                     // the state in front of the stretch: the nearest stretch in front that fixes one
+        long long acc = 0;
+        for (int u = t - 1; u >= 0; --u) {
+            if (s_has[u]) { bad = bad || s_out[u] - acc != need; break; }
+            acc += s_sub[u];
+        }                                            // (none: the file's or the range's first find — nothing in front vouches for it)
+    }
+    if (bad) atomicOr(&s_bad, 1);
+    __syncthreads();
+    if (!s_bad || t != 0) return;
+    long long expect = -1;
+    bool open = ranged != 0;
+    for (int b = 0; b < n_own; ++b) {                // (the host's tcmi_bam_chain_check, with the withdrawal)
+        const int32_t entry = blocks[b].entry;
+        const long long ulen = (long long)blocks[b].ulen;
+        if (entry == -1) continue;
+        const uint32_t f = first[b];
+        if (open && f != NONE) { expect = f; open = false; }
+        if (open) continue;
+        if (entry >= 0) expect = entry;
+        if (f == NONE) { expect -= ulen; continue; }
+        if ((long long)f != expect) {
+            if (entry >= 0 || expect < ulen || (long long)f + 40 <= ulen) return;
+            first[b] = NONE; n_rec[b] = 0; over[b] = 0;
+            expect -= ulen;
+            continue;
+        }
+        expect = vouch_over(b, blocks, over, n_rec, rec_slot, out);
+    }
 }
 
 __global__ __launch_bounds__(256) void rec_compact(const BlockDesc *blocks, const uint32_t *rec_slot, const uint32_t *n_rec,
@@ -255,6 +336,10 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
             ++ctx->stat_decode_batched;
         }
     }
+    // finds inside a record are withdrawn before anything reads the blocks' words
+    hipLaunchKernelGGL(rec_vouch, dim3(1), dim3(1024), 0, ctx->stream, D.d_desc, D.d_first, D.d_over, D.d_nrec, D.d_slot, D.d_out, (int32_t)nb_own,
+                       (int32_t)ranged);
+    TCMI_HIP(ctx, hipGetLastError());
     return TCMI_OK;
 }
 
