@@ -330,6 +330,45 @@ int  tcmi_ctx_set_intervals(tcmi_ctx *ctx, int64_t n, const int64_t *start, cons
 int  tcmi_step_intervals(tcmi_ctx *ctx, const tcmi_interval_stat **records, int64_t *n);
 int  tcmi_amplicons_text(const tcmi_interval_stat *records, int64_t n, const char *sample, const char *region, const char *const *names,
                          const char *const *pools, const int64_t *start, int64_t pos_offset, char *text, int64_t cap, int64_t *len);
+/* ---- amplicon reads (additive: what `samtools ampliconstats` reports as FREADS; the reference has nothing like it) ----------------
+ * How many RECORDS of a device-decoded read set belong to which amplicon of a primer scheme, counted by one HIP kernel over the
+ * inflated record stream the read set left resident on its context.  The count matrix cannot say this: a column's depth does not say
+ * which amplicon its reads came from.  All arithmetic is integer; the sums are the same in every run.
+ *   amplicon i     four numbers on the count matrix's axis (under a contig layout: shifted by its contig's slot): fs[i] the smallest
+ *                  LEFT start, le[i] the largest LEFT end, rs[i] the smallest RIGHT start, fe[i] the largest RIGHT end, with
+ *                  fs < le, rs < fe, fs < fe (le > rs, overlapping primers, is legal).  With slack s in 0..1000 its widened extent
+ *                  is a = fs - s (may be negative), b = fe + s.  Amplicons may overlap, nest and repeat.
+ *   kept record    exactly what the device packer keeps: not FLAG 0x4, passes the read filter the read set was built under, its
+ *                  reference has a slot (shift >= 0), pos >= 0, a consistent record, a reference span > 0.  Its first column is
+ *                  p = pos + shift, its last q = p + (the M, D, N, =, X lengths) - 1.  Records are counted, not templates; a long
+ *                  read that the packed set leaves out counts once.  The primer mask and the base-quality floor skip tokens, not
+ *                  reads: they do not enter.
+ *   containment    the read is contained in amplicon i iff a_i <= p and q < b_i.  In exactly one amplicon i: records[i].reads += 1,
+ *                  and records[i].full += 1 iff also p < le_i and q >= rs_i (it starts in the left primer zone and ends in the right
+ *                  one).  In two or more: records[n].reads += 1 (ambiguous; two identical amplicons make all their reads ambiguous).
+ *                  In none: records[n + 1].reads += 1 (unassigned).  records[n].full = records[n + 1].full = 0.
+ *   invariant      the sum of all n + 2 `reads` equals the number of kept records.
+ *   tcmi_readset_amplicon_reads   records: host, room for n + 2.  The read set must have been decoded on the device and its stream must
+ *                  still be resident on this context — no other upload since (the same arena epoch), the same device, the same
+ *                  layout generation —, else TCMI_E_UNSUPPORTED with words that name the cause.  Long reads and contig layouts are
+ *                  supported (the kernel reads the stream, not the packed set).  A read set of sub-ranges (tcmi_split_step,
+ *                  "split_sub") answers with the sum over its parts, each counted on its own context.  Waits for the stream.  The
+ *                  scratch is the context's, grow-only.
+ *   tcmi_amplicon_reads_compile   (GPU-free) the int32 table the kernel searches, 6 n words, six dense arrays one behind the other:
+ *                  a[n] the widened starts ascending (ties in the order given); bmax[n], idx[n], b2[n]: of the first k + 1 sorted
+ *                  amplicons the largest b, the index (in the order given) of the first that has it, and the second largest b
+ *                  counted with multiplicity (INT32_MIN for k = 0); le[n], rs[n] in the order given.  Lookup (p, q): k = the number
+ *                  of a <= p; none iff k = 0 or bmax[k - 1] <= q; ambiguous iff k >= 2 and b2[k - 1] > q; else idx[k - 1].
+ *                  table_cap: room in words; msg (may be NULL) receives the words of a TCMI_E_ARG.
+ * TCMI_AMPLICON_READS_LDS: the amplicons whose table and counters a workgroup stages in LDS (16 KiB: eight workgroups per compute
+ * unit); a larger table is searched, and counted, in memory; for tests.
+ * Argument errors are TCMI_E_ARG: n outside 1..65 536, a coordinate outside [0, 2^29], the inequalities above, slack outside 0..1000. */
+typedef struct tcmi_amplicon_reads { int64_t reads, full; } tcmi_amplicon_reads;
+#define TCMI_AMPLICON_READS_LDS 512
+int  tcmi_readset_amplicon_reads(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *fs, const int64_t *le, const int64_t *rs_,
+                                 const int64_t *fe, int32_t slack, tcmi_amplicon_reads *records /* host, n + 2 */);
+int  tcmi_amplicon_reads_compile(int64_t n, const int64_t *fs, const int64_t *le, const int64_t *rs_, const int64_t *fe, int32_t slack,
+                                 int32_t *table, int64_t table_cap, char *msg, int64_t msg_cap);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -348,7 +387,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_INFLATE_COPY = 9 /* device BGZF inflate, second kernel: tokens -> bytes (TCMI_K_INFLATE is the first: symbols -> tokens) */,
        TCMI_K_VARIANTS = 10 /* the variant table's three launches (count, scan, emit) as one bracket */,
        TCMI_K_INTERVALS = 11 /* the amplicon table's one launch */,
-       TCMI_K_NKERNELS = 12 };
+       TCMI_K_AMPLICON_READS = 12 /* tcmi_readset_amplicon_reads' one launch */,
+       TCMI_K_NKERNELS = 13 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);

@@ -9,7 +9,10 @@ one is; the reference tallies every mapped record), the variant table --variant-
 [--variant-min-depth N] (per position every non-reference allele at or above a frequency, from the count matrix the consensus is
 called from; --batch: the manifest's 7th column), the amplicon table --amplicon-table FILE [--amplicon-scheme BED]
 [--amplicon-region insert|unique|full] (per amplicon of the primer scheme the mean, median and minimum depth of its columns and
-how many lie below -cov, from the same matrix; --batch: one file for all samples), and
+how many lie below -cov, from the same matrix; --batch: one file for all samples), the reads per amplicon --amplicon-reads FILE
+[--amplicon-reads-slack N] (per amplicon of the scheme the alignment records whose two ends lie inside it and inside no other, and
+how many of them run from its left primer into its right one; records inside several amplicons or inside none are counted as such;
+counted on the device in the decoded record stream; not with --batch), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -137,16 +140,16 @@ def read_manifest(a):
     return rows
 
 
-def amplicons_of(a, layout=None):
-    """The parsed namespace's --amplicon-scheme / --amplicon-region -> [(Amplicon, the shift of its contig's slot on the count matrix's
-    axis)], or None without --amplicon-table.  Without a layout the amplicons on the BAM's reference name (--batch: the one -ref
-    names), shift 0; layout = (the BAM header's reference names, shift): those on contigs the layout holds.  None left, or a scheme
-    that does not parse: an argument error (exit 1)."""
-    if not getattr(a, "amplicon_table", None):
-        return None
+def _scheme_amplicons(a, layout, flag, region):
+    """--amplicon-scheme's amplicons for `flag` (--amplicon-table, --amplicon-reads) -> [(Amplicon, the shift of its contig's slot,
+    (fs, le, rs, fe) in the contig's own coordinates)].  Without a layout the amplicons on the BAM's reference name (--batch: the one
+    -ref names), shift 0; layout = (the BAM header's reference names, shift): those on contigs the layout holds.  None left, or a
+    scheme that does not parse: an argument error (exit 1)."""
     from .io import primers as pb
     try:
-        amps = pb.amplicons(pb.read_scheme(a.amplicon_scheme), a.amplicon_region)
+        rows = pb.read_scheme(a.amplicon_scheme)
+        amps = pb.amplicons(rows, region)
+        zones = dict(zip(((m.chrom, m.name) for m in amps), pb.amplicon_zones(rows)))
     except (OSError, pb.PrimerBedError) as e:
         print(f"--amplicon-scheme: {e}. Exiting...")
         sys.exit(1)
@@ -162,12 +165,49 @@ def amplicons_of(a, layout=None):
         out = [(m, 0) for m in amps if m.chrom == names[0]]
         where = 'the reference "%s"' % names[0]
     if not out:
-        print(f"--amplicon-table: no amplicon of {a.amplicon_scheme} is on {where}. Exiting...")
+        print(f"{flag}: no amplicon of {a.amplicon_scheme} is on {where}. Exiting...")
         sys.exit(1)
     if len(out) > 65536:
-        print(f"--amplicon-table: {a.amplicon_scheme} has {len(out)} amplicons, more than 65536. Exiting...")
+        print(f"{flag}: {a.amplicon_scheme} has {len(out)} amplicons, more than 65536. Exiting...")
         sys.exit(1)
-    return out
+    return [(m, sh, zones[(m.chrom, m.name)]) for m, sh in out]
+
+
+def amplicons_of(a, layout=None):
+    """The parsed namespace's --amplicon-scheme / --amplicon-region -> [(Amplicon, the shift of its contig's slot on the count matrix's
+    axis)], or None without --amplicon-table.  Without a layout the amplicons on the BAM's reference name (--batch: the one -ref
+    names), shift 0; layout = (the BAM header's reference names, shift): those on contigs the layout holds.  None left, or a scheme
+    that does not parse: an argument error (exit 1)."""
+    if not getattr(a, "amplicon_table", None):
+        return None
+    return [(m, sh) for m, sh, _ in _scheme_amplicons(a, layout, "--amplicon-table", a.amplicon_region)]
+
+
+def amplicon_reads_of(a, layout=None):
+    """The parsed namespace's --amplicon-reads -> ([Amplicon] in amplicons_of's order, [(fs, le, rs, fe)] on the count matrix's axis as
+    Context.amplicon_reads takes them, slack), or None without the flag.  The amplicons are chosen as amplicons_of chooses them."""
+    if not getattr(a, "amplicon_reads", None):
+        return None
+    got = _scheme_amplicons(a, layout, "--amplicon-reads", "full")
+    return [m for m, _, _ in got], [tuple(v + sh for v in z) for _, sh, z in got], int(a.amplicon_reads_slack)
+
+
+def amplicon_reads_text(sample, counts, amps):
+    """One sample's rows of --amplicon-reads: counts = Context.amplicon_reads' n + 2 rows (or an [n + 2, 2] array), amps their n
+    amplicons.  REGION is the amplicon's contig; then the two rows of the records inside several amplicons and inside none."""
+    rows = [(int(r[0]), int(r[1])) for r in counts]
+    if len(rows) != len(amps) + 2:
+        raise ValueError("amplicon_reads_text: %d amplicons, %d rows of counts" % (len(amps), len(rows)))
+    text = ["%s\t%s\t%s\t%s\t%d\t%d\n" % (sample, m.chrom, m.name, m.pool, r, f) for m, (r, f) in zip(amps, rows)]
+    text += ["%s\t*\t%s\t*\t%d\t0\n" % (sample, what, rows[len(amps) + k][0]) for k, what in enumerate(("*ambiguous", "*unassigned"))]
+    return "".join(text)
+
+
+def write_amplicon_reads(path, sample, counts, amps):
+    """--amplicon-reads: the header line, then amplicon_reads_text's rows."""
+    from .engine import AMPLICON_READS_HEADER
+    with open(path, "w") as out:
+        out.write(AMPLICON_READS_HEADER + amplicon_reads_text(sample, counts, amps))
 
 
 def amplicon_intervals(amps):
@@ -333,6 +373,14 @@ def GetArgs(givenargs):
     additive.append((("--amplicon-region",), dict(choices=("insert", "unique", "full"), default=None,
                                                   help="the columns of an amplicon: between its primers (insert, the default), the insert\n"
                                                        "outside every other amplicon (unique), or primers included (full)")))
+    additive.append((("--amplicon-reads",), dict(type=str, default=None, metavar="File",
+                                                 help="also write per amplicon of the scheme the alignment records that lie inside it and inside no\n"
+                                                      "other, tab-separated: SAMPLE REGION AMPLICON POOL READS FULL_LENGTH (FULL_LENGTH: those that start\n"
+                                                      "in its left primer and end in its right one), then the records inside several amplicons\n"
+                                                      "(*ambiguous) and inside none (*unassigned); needs the device decoder; not with --batch")))
+    additive.append((("--amplicon-reads-slack",), dict(type=_range_arg(parser, "--amplicon-reads-slack", 1000), default=None, metavar="N",
+                                                       help="a read may reach up to N columns beyond an amplicon's outer primer ends and still lie\n"
+                                                            "inside it (default 5)")))
     # (is this the --batch form?  asked of a small parser of its own: "--batch=FILE" and argparse's abbreviations count too)
     pre = argparse.ArgumentParser(add_help=False)
     pre.add_argument("--batch", default=None)
@@ -351,14 +399,23 @@ def GetArgs(givenargs):
         parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
     if a.batch is None and a.variant_table is None and a.variant_thresholds_given:
         parser.error("--min-af / --min-alt-depth / --variant-min-depth need --variant-table.")
-    if a.amplicon_table is None and (a.amplicon_scheme is not None or a.amplicon_region is not None):
+    if a.amplicon_table is None and (a.amplicon_region is not None or (a.amplicon_scheme is not None and a.amplicon_reads is None)):
         parser.error("--amplicon-scheme / --amplicon-region need --amplicon-table.")
+    if a.amplicon_reads is None and a.amplicon_reads_slack is not None:
+        parser.error("--amplicon-reads-slack needs --amplicon-reads.")
+    if a.amplicon_reads is not None:
+        if a.batch is not None:
+            parser.error("--amplicon-reads goes with a single sample (-i): --batch is refused, its file runner keeps the read sets inside its native threads.")
+        if a.amplicon_scheme is None and not a.primers:
+            parser.error("--amplicon-reads needs the scheme's BED: --amplicon-scheme, or --primers.")
     if a.amplicon_table is not None:
         if a.amplicon_scheme is None and not a.primers:
             parser.error("--amplicon-table needs the scheme's BED: --amplicon-scheme, or --primers.")
         if a.coverage_level < 0:
             parser.error("--amplicon-table counts the columns below -cov, which cannot be negative.")
+    if a.amplicon_table is not None or a.amplicon_reads is not None:
         a.amplicon_scheme = a.primers if a.amplicon_scheme is None else a.amplicon_scheme
+    a.amplicon_reads_slack = 5 if a.amplicon_reads_slack is None else a.amplicon_reads_slack
     a.amplicon_region = "insert" if a.amplicon_region is None else a.amplicon_region
     a.min_af = Fraction(3, 100) if a.min_af is None else a.min_af
     a.min_alt_depth = 1 if a.min_alt_depth is None else a.min_alt_depth
@@ -417,7 +474,11 @@ def _child_argv(a, single, tables=True):
         out += ["--min-af", str(a.min_af), "--min-alt-depth", str(a.min_alt_depth), "--variant-min-depth", str(a.variant_min_depth)]
     if a.amplicon_table:                            # (the amplicon table's scheme; its FILE is the caller's: a --batch child writes a part)
         out += ["--amplicon-scheme", a.amplicon_scheme, "--amplicon-region", a.amplicon_region]
+    elif single and a.amplicon_reads:               # (--amplicon-reads alone: the scheme, no region)
+        out += ["--amplicon-scheme", a.amplicon_scheme]
     if single:
+        if a.amplicon_reads:
+            out += ["--amplicon-reads", a.amplicon_reads, "--amplicon-reads-slack", str(a.amplicon_reads_slack)]
         if a.variant_table:
             out += ["--variant-table", a.variant_table]
         if a.amplicon_table:
@@ -600,7 +661,14 @@ def _single_sample(a, flt, t):
     from .engine import LazyBam
     bam = LazyBam(a.input, threads=a.threads, read_filter=flt)      # reads reach the host only if an insert candidate needs its tokens
     t["bam_open"] = time.perf_counter()
-    counts = build_counts(bam, a.reference)         # decoded, packed and tallied on the device
+    areads, got = amplicon_reads_of(a), {}
+    if areads:                                      # counted behind the step, on the read set the step returned, while its stream is resident
+        def count_reads(ctx, rs):
+            got["counts"] = ctx.amplicon_reads(rs, areads[1], areads[2])
+        counts = build_counts(bam, a.reference, on_readset=count_reads, need_device="--amplicon-reads")
+        write_amplicon_reads(a.amplicon_reads, a.samplename, got["counts"], areads[0])
+    else:
+        counts = build_counts(bam, a.reference)     # decoded, packed and tallied on the device
     IndexGff = Gffindex(a.features)
     t["tally"] = time.perf_counter()
 
@@ -642,6 +710,8 @@ def _single_sample(a, flt, t):
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
                        "variant_records": n_variants, "amplicons": len(amps) if amps else 0, "amplicons_below": n_below,
+                       "amplicon_reads_ambiguous": int(got["counts"]["reads"][-2]) if areads else 0,
+                       "amplicon_reads_unassigned": int(got["counts"]["reads"][-1]) if areads else 0,
                        "bam_bytes": os.path.getsize(a.input)}, fh)
 
 

@@ -122,7 +122,7 @@ def axis_reference(records, header_names, shift, axis_len):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None, variants=None, intervals=None):
+                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, amplicon_reads=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
@@ -132,7 +132,10 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     (Context.set_primers; io.primers.rows_for_layout shifts a BED's rows): likewise; info then receives "reads_primer_masked" too.
     variants = the keyword arguments of Context.set_variants (ref: the reference on the axis, axis_reference): the step also lists
     the variant table's records, which info receives as "variant_table".  intervals = ([(start, end)] on the axis, min_depth)
-    (Context.set_intervals): the step also computes the amplicon table's records, which info receives as "amplicon_table"."""
+    (Context.set_intervals): the step also computes the amplicon table's records, which info receives as "amplicon_table".
+    amplicon_reads = ([(fs, le, rs, fe)] on the axis, slack) (Context.amplicon_reads): behind the step the records of the read set are
+    counted per amplicon in the decoded stream, which info receives as "amplicon_reads"; a file the device decoder declines is
+    refused then (reads decoded on the host leave no stream on the device)."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
@@ -144,7 +147,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_intervals(*intervals)
     host = None
     try:
-        rs = device_readset(ctx, path)              # (the floor it refuses under is the one just set)
+        rs = device_readset(ctx, path, need="--amplicon-reads" if amplicon_reads else None)    # (the floor it refuses under is the one just set)
         if rs is None:
             host = BamFile(path, threads=threads, read_filter=read_filter)
             try:
@@ -162,6 +165,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
                 info["variant_table"] = ctx.step_variants()
             if intervals and info is not None:
                 info["amplicon_table"] = ctx.step_intervals()
+            if amplicon_reads and info is not None:             # (the layout is still set: the read set's shifts are the table's)
+                info["amplicon_reads"] = ctx.amplicon_reads(rs, *amplicon_reads)
         finally:
             rs.free()
     finally:
@@ -179,7 +184,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_table, write_variant_table
+    from .TrueConsense import (amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_reads,
+                               write_amplicon_table, write_variant_table)
     flt, seen = read_filter_of(a), {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -193,12 +199,17 @@ def run(a):
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
     amps = amplicons_of(a, (hdr_names, shift))      # (each contig's amplicons shifted by its slot; none left: an argument error)
     seen["amplicons"] = len(amps) if amps else 0
+    areads = amplicon_reads_of(a, (hdr_names, shift))           # (likewise, for --amplicon-reads)
     axis_ref = axis_reference(records, hdr_names, shift, axis_len) if a.variant_table is not None else None
     var = dict(variants_of(a), ref=axis_ref) if axis_ref is not None else None
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
                                                                  threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
                                                                  min_baseq=a.min_baseq, primers=prm, variants=var,
-                                                                 intervals=(amplicon_intervals(amps), mincov) if amps else None)
+                                                                 intervals=(amplicon_intervals(amps), mincov) if amps else None,
+                                                                 amplicon_reads=areads[1:] if areads else None)
+    rcounts = seen.pop("amplicon_reads", None)
+    seen["amplicon_reads_ambiguous"] = 0 if rcounts is None else int(rcounts["reads"][-2])
+    seen["amplicon_reads_unassigned"] = 0 if rcounts is None else int(rcounts["reads"][-1])
     seen.setdefault("reads_primer_masked", 0)
     table = seen.pop("variant_table", None)
     seen["variant_records"] = 0 if table is None else len(table)
@@ -267,6 +278,8 @@ def run(a):
         write_variant_table(a.variant_table, parts)
     if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
         write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
+    if rcounts is not None:                         # one file: REGION is each amplicon's contig
+        write_amplicon_reads(a.amplicon_reads, name, rcounts, areads[0])
     with open(a.output, "w") as out:
         out.write("".join(fa))
     return dict({"contigs": len(records), "dropped_reads": int(dropped)}, **seen)

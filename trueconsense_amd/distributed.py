@@ -366,7 +366,7 @@ def _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks):
 
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
                             step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
-                            min_baseq=None, primers=None):
+                            min_baseq=None, primers=None, amplicon_reads=None):
     """BASELINE configs[4] all the way: ONE BAM file over `world` ranks -> its consensus FASTA text on rank 0 (None on the others).
     What the ranks jointly replace is the reference's single pile-up pass (indexing.py:96-100), its insert candidates' region
     pile-ups (Events.py:47-82) and the walk (Sequences.py:168-322):
@@ -394,7 +394,10 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     step 3), and rank 0's host sweep of step 4 removes the failing records too.  min_baseq: the base-quality floor of the count
     matrix, on every rank's context (Context.set_min_base_quality; 0 sets no floor, None leaves what the context has); the insert
     tokens keep their own quality rule.  primers = (rows, slack): the primer table of the count matrix, on every rank's context
-    likewise (Context.set_primers; no rows clears it, None leaves what the context has)."""
+    likewise (Context.set_primers; no rows clears it, None leaves what the context has).  amplicon_reads = ([(fs, le, rs, fe)], slack):
+    behind the step every rank counts the records of its own read set per amplicon (Context.amplicon_reads) and the [n + 2, 2] int64
+    counts are summed to rank 0 over the same group — a record starts in exactly one rank's blocks, so the sum is the file's; with
+    return_parts rank 0's tuple then has them as a fourth item."""
     import time
     import torch
     import torch.distributed as dist
@@ -402,7 +405,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     L = int(ref_len)
     ld, n_words = split_words(L, world)
     root = rank == 0
-    plain = alt = flags = counts_root = None
+    plain = alt = flags = counts_root = reads_root = None
     own_ctx, own_d = ctx is None, dbam is None
     d, rs = dbam, None
     err = None
@@ -471,6 +474,25 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
         bad = [v for v in verdict if v]
         if bad:
             raise TcmiError(bad[0][0], "consensus_split_bamfile: %s" % bad[0][1])
+        if amplicon_reads is not None:                               # reads per amplicon: every rank its own records, one sum to rank 0
+            mine, aerr = None, None
+            try:
+                got = ctx.amplicon_reads(rs, *amplicon_reads)
+                mine = np.ascontiguousarray(np.stack([got["reads"], got["full"]], axis=1))
+            except TcmiError as e:
+                aerr = (e.code, str(e))
+            if multi:                                                # nobody enters the reduce unless everybody has counts
+                alla = [None] * dist.get_world_size(group)
+                dist.all_gather_object(alla, aerr, group=group)
+                aerr = next((v for v in alla if v), None)
+            if aerr is not None:
+                raise TcmiError(aerr[0], "consensus_split_bamfile: amplicon reads: %s" % aerr[1])
+            if multi:
+                on_gpu = dist.get_backend(group) == "nccl"
+                tr = torch.from_numpy(mine).cuda() if on_gpu else torch.from_numpy(mine)
+                dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
+                mine = tr.cpu().numpy()
+            reads_root = mine if root else None
         # the insert-candidate columns, from rank 0 to everybody
         cand = [(np.nonzero(flags & 8)[0] + 1).tolist()] if root else [None]
         if multi:
@@ -515,6 +537,8 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
             timings["release"] = time.perf_counter() - t2
             timings["total"] = time.perf_counter() - t0
     if return_parts:
+        if amplicon_reads is not None:
+            return (text, counts_root, toks, reads_root) if root else None
         return (text, counts_root, toks) if root else None
     return text
 

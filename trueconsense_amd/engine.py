@@ -104,6 +104,32 @@ def amplicons_text(records, sample, region, names, pools, starts, pos_offset=0):
     return buf.raw[:ln.value].decode("utf-8", "replace")
 
 
+# struct tcmi_amplicon_reads: the records of one amplicon (--amplicon-reads); rows n and n + 1 of a result: ambiguous, unassigned
+AMPLICON_READS_DTYPE = np.dtype([("reads", np.int64), ("full", np.int64)])
+AMPLICON_READS_HEADER = "SAMPLE\tREGION\tAMPLICON\tPOOL\tREADS\tFULL_LENGTH\n"
+AMPLICON_READS_LDS = 512         # TCMI_AMPLICON_READS_LDS: amplicons whose table and counters the kernel stages in LDS
+
+
+def _amps4(amps4):
+    """[(fs, le, rs, fe)] or an [n, 4] array -> four contiguous int64 arrays"""
+    a = np.asarray(amps4, np.int64).reshape(-1, 4)
+    return tuple(np.ascontiguousarray(a[:, k]) for k in range(4))
+
+
+def amplicon_reads_compile(amps4, slack=0):
+    """The int32 table tcmi_readset_amplicon_reads' kernel searches (tcmi_amplicon_reads_compile; GPU-free) -> int32 [6, n]: the
+    widened starts ascending, the prefix's largest end, whose it is, the second largest end, and le, rs in the order given.
+    Raises TcmiError(E_ARG) with the library's words for a scheme it does not take."""
+    fs, le, rs, fe = _amps4(amps4)
+    n = len(fs)
+    table = np.zeros((6, max(n, 1)), np.int32)
+    msg = C.create_string_buffer(256)
+    rc = lib().tcmi_amplicon_reads_compile(n, ptr(fs), ptr(le), ptr(rs), ptr(fe), int(slack), ptr(table), 6 * n, msg, 256)
+    if rc:
+        raise _ffi.TcmiError(rc, msg.value.decode("utf-8", "replace"))
+    return table[:, :n]
+
+
 def _grab(vp, dtype, n):
     """n items of dtype at address vp (memory the library owns) -> a fresh numpy array."""
     out = np.empty(n, dtype)
@@ -374,6 +400,18 @@ class Context:
         if len(st) == 0:
             return out
         check(lib().tcmi_interval_stats(self.handle, ptr(counts), len(counts), len(st), ptr(st), ptr(en), int(min_depth), ptr(out)), self.handle)
+        return out
+
+    def amplicon_reads(self, readset, amps4, slack=0):
+        """Reads per amplicon (tcmi_readset_amplicon_reads): amps4 = [(fs, le, rs, fe)] on the count matrix's axis, slack in 0..1000
+        -> a structured array (AMPLICON_READS_DTYPE) of n + 2 rows: per amplicon the records contained in it alone and those of them
+        that run from its left primer zone into its right one, then the ambiguous records (contained in two or more), then the
+        unassigned ones; the `reads` add up to the read set's kept records.  The read set must have been decoded on the device and
+        its stream must still be resident on this context (no other upload since), else TcmiError(E_UNSUPPORTED)."""
+        fs, le, rs, fe = _amps4(amps4)
+        out = np.zeros(len(fs) + 2, AMPLICON_READS_DTYPE)
+        check(lib().tcmi_readset_amplicon_reads(self.handle, readset.handle, len(fs), ptr(fs), ptr(le), ptr(rs), ptr(fe), int(slack), ptr(out)),
+              self.handle)
         return out
 
     def set_layout(self, shift=None, slot_len=None):

@@ -36,10 +36,11 @@ def Override_index_positions(index, override_data):
     return index
 
 
-def device_readset(ctx, path, blocks=None):
+def device_readset(ctx, path, blocks=None, need=None):
     """The device path, or why not: the file at `path` (blocks = (first, count): that range of its BGZF blocks) decoded and packed by
     ctx's device decoder -> ReadSet; None when the decoder declines the file (E_UNSUPPORTED) and the host reader may take it.  Under
-    a base-quality floor (ctx.min_base_quality) or a primer table (ctx.primers) the host reader may not: the refusal is raised with its reason."""
+    a base-quality floor (ctx.min_base_quality) or a primer table (ctx.primers) the host reader may not: the refusal is raised with its
+    reason; likewise when the caller names a flag that `need`s the device path (--amplicon-reads counts in the decoded stream)."""
     d = DeviceBam(path)
     try:
         return ctx.upload_bamfile(d, blocks)
@@ -53,34 +54,44 @@ def device_readset(ctx, path, blocks=None):
         if getattr(ctx, "primers", 0):              # (a context of before the table has none)
             raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--primers needs the device path (the host packer knows no primer mask), "
                                  "which %s left: %s" % (path, e)) from e
+        if need:
+            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "%s needs the device path (it counts the records in the stream the device decoded), "
+                                 "which %s left: %s" % (need, path, e)) from e
         return None
     finally:
         d.close()
 
 
-def build_counts(bamfile, ref, ctx=None):
+def build_counts(bamfile, ref, ctx=None, on_readset=None, need_device=None):
     """BAM (+ reference FASTA, for its length) -> int32 [L,7] count matrix on the GPU path.  A path (or LazyBam) is decoded
     ON THE DEVICE (BGZF inflate, record chain, pack: csrc/bam_device.hip, pack_device.hip); files the device decoder
     declines, and BamFile objects, go through the host reader's flat arrays.  A read filter is the context's
     (Context.set_read_filter): the host reader's fallback applies the same one (a LazyBam's own, if it has one); a BamFile is
     taken as it is.  Under a base-quality floor (Context.set_min_base_quality) there is no fallback: the host packer knows no
-    floor, and a file the device decoder declines is refused with its reason."""
+    floor, and a file the device decoder declines is refused with its reason.  on_readset(ctx, read set): called behind the step,
+    while the read set's decoded stream is still resident (Context.amplicon_reads); need_device: the flag on whose behalf a file that
+    leaves the device path — a file the decoder declines, a BamFile — is refused instead (device_readset's `need`)."""
     ref_length = fasta.first_length(ref) if isinstance(ref, str) else int(ref)
     ctx = ctx or _state.default_context()
     if not isinstance(bamfile, BamFile):
         path = bamfile.filename if isinstance(bamfile, LazyBam) else str(bamfile)
-        rs = device_readset(ctx, path)
+        rs = device_readset(ctx, path, need=need_device)
         if rs is not None:
             try:
                 build_counts.last_reads, build_counts.last_filtered = int(rs.n_reads), int(rs.filtered)
                 build_counts.last_primer_masked = int(rs.primer_masked_reads)
-                return ctx.step(rs, max(ref_length, rs.max_end, 1), 0, True, want_counts=True)[3]
+                counts = ctx.step(rs, max(ref_length, rs.max_end, 1), 0, True, want_counts=True)[3]
+                if on_readset is not None:
+                    on_readset(ctx, rs)
+                return counts
             finally:
                 rs.free()
         flt = getattr(ctx, "read_filter", None)
         if isinstance(bamfile, LazyBam) and bamfile.read_filter is None:
             bamfile.read_filter = flt
         bamfile = bamfile.get() if isinstance(bamfile, LazyBam) else BamFile(path, read_filter=flt)
+    if need_device:
+        raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "%s needs the device path: reads decoded on the host have no record stream on the device" % need_device)
     build_counts.last_reads, build_counts.last_filtered = int(bamfile.n_records), int(bamfile.n_removed)
     return ctx.tally(bamfile, ref_len=ref_length)
 

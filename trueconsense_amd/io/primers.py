@@ -145,6 +145,23 @@ def amplicons(rows, region="insert"):
     return out
 
 
+def amplicon_zones(rows):
+    """read_scheme's rows -> [(fs, le, rs, fe)], one per amplicon in amplicons()' order (which does not depend on the region): fs the
+    smallest LEFT start, le the largest LEFT end, rs the smallest RIGHT start, fe the largest RIGHT end — alternates merge as
+    amplicons() merges them, and its errors are this function's.  le > rs (overlapping primers) is legal: what --amplicon-reads
+    matches a read's two ends against."""
+    sides = {}
+    for r in rows:
+        key, side = _side_of(r)
+        z = sides.setdefault((r.chrom, key), {"LEFT": [], "RIGHT": []})
+        z[side].append((r.start, r.end))
+    out = []
+    for m in amplicons(rows, "full"):
+        z = sides[(m.chrom, m.name)]
+        out.append((min(s for s, _ in z["LEFT"]), max(e for _, e in z["LEFT"]), min(s for s, _ in z["RIGHT"]), max(e for _, e in z["RIGHT"])))
+    return out
+
+
 def amplicons_for_layout(amps, names, shift):
     """A contig layout (names[t] starts at shift[t] on the axis; < 0: no slot) -> [(Amplicon, its slot's shift)] for the amplicons on
     contigs the layout holds, in the amplicons' order; the others are ignored (as rows_for_layout ignores their primers)."""

@@ -28,7 +28,8 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import GetArgs, amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_table, write_variant_table
+    from .TrueConsense import (GetArgs, amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, read_filter_of, variants_of,
+                               write_amplicon_reads, write_amplicon_table, write_variant_table)
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
     torch.cuda.set_device(device)
@@ -49,11 +50,14 @@ def main(argv=None):
         gffdict = IndexGff.index_dict(seqid=a.samplename)
         rows = [{"start": int(r["start"]), "end": int(r["end"]), "strand": r.get("strand")} for r in gffdict.values()]
         refID, refseq = fasta.read_first_record(a.reference)
+        areads = amplicon_reads_of(a)                                # (an unusable scheme ends every rank here, before the step)
         parts = td.consensus_split_bamfile(a.input, len(refseq), rows, a.coverage_level, a.noambiguity is False, a.samplename, rank, world,
                                            device=device, return_parts=True, rccl_user=user, read_filter=read_filter_of(a), min_baseq=a.min_baseq,
-                                           primers=primers_of(a))
+                                           primers=primers_of(a), amplicon_reads=areads[1:] if areads else None)
         if rank == 0:
-            _, counts, toks = parts
+            _, counts, toks = parts[:3]
+            if areads:                                               # (the ranks' counts, summed: a record starts in one rank's blocks)
+                write_amplicon_reads(a.amplicon_reads, a.samplename, parts[3], areads[0])
             index = _state.IndexDict(counts)
             if a.depth_of_coverage is not None:
                 BuildCoverage(index, a.depth_of_coverage)
