@@ -369,6 +369,51 @@ int  tcmi_readset_amplicon_reads(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t 
                                  const int64_t *fe, int32_t slack, tcmi_amplicon_reads *records /* host, n + 2 */);
 int  tcmi_amplicon_reads_compile(int64_t n, const int64_t *fs, const int64_t *le, const int64_t *rs_, const int64_t *fe, int32_t slack,
                                  int32_t *table, int64_t table_cap, char *msg, int64_t msg_cap);
+/* ---- strand counts (additive: what `ivar variants` reports as REF_RV / ALT_RV; the reference has nothing like it) -------------------
+ * The count matrix's seven planes at given columns, split by the strand of the record (FLAG 0x10), counted by one HIP kernel over the
+ * inflated record stream a device-decoded read set left resident on its context.  The matrix sums the strands and the packed read set
+ * does not keep the flag: the strand lives in the records only.  All arithmetic is integer; the sums are the same in every run.
+ *   columns        c_0 < c_1 < ... < c_{n-1} on the count matrix's axis (under a contig layout: shifted by the contig's slot), each in
+ *                  [0, 2^29), n in 1..2^20.
+ *   fwd[k], rev[k] for k in plane order TCMI_COV..TCMI_I: the value the count matrix would hold at (k, c_i) had the read set been built
+ *                  from the same records minus those with FLAG 0x10 set (fwd), minus those with it clear (rev) - under the read
+ *                  filter, the base-quality floor, the primer table and the contig layout the read set REMEMBERS, whatever the
+ *                  context is set to later.  The token rule is the count matrix's: a matched base counts by its letter; a deleted
+ *                  column counts X unless it is the last column of a deletion with an insertion behind it; the I mark goes to the
+ *                  last reference column in front of an insertion, iff that token is not skipped; M, =, X, D and N count coverage;
+ *                  the floor and the primer mask skip tokens per column as described above.  Every kept record takes part (what
+ *                  tcmi_readset_amplicon_reads calls kept), packed reads and long reads alike.  A column nobody covers gives zeros.
+ *   invariant      fwd[k] + rev[k] equals the count matrix a step tallies from the read set, at (k, c_i), on all seven planes.
+ *   tcmi_readset_strand_counts   records: host, room for n; pos = c_i, reserved = 0.  Residency as for tcmi_readset_amplicon_reads:
+ *                  decoded on the device, the same arena epoch, device and layout generation, else TCMI_E_UNSUPPORTED with words that
+ *                  name the cause.  A read set of sub-ranges answers with the sum over its parts, each counted on its own context.  A
+ *                  read set without a kept record gives zero records and TCMI_OK.  Waits for the stream.  The scratch is the
+ *                  context's, grow-only.
+ *   tcmi_strand_verdict   HOST, GPU-free, exact integers.  0 PASS, 1 BIAS, 2 LOW.  LOW iff tot_fwd < min_strand_depth or
+ *                  tot_rev < min_strand_depth.  Else with x = alt_fwd * tot_rev, y = alt_rev * tot_fwd (the two strand frequencies
+ *                  cross-multiplied), lo = min(x, y), hi = max(x, y): BIAS iff lo * den < hi * num (an exact tie is PASS; num = 0
+ *                  never gives BIAS).  The products take more than 64 bits: they are formed in 128.  TCMI_E_ARG for a negative
+ *                  count and the range errors below.
+ *   tcmi_variants_strand_text   HOST, re-entrant, no GPU: the writer of --variant-strand's rows.  The first seven fields of a row are
+ *                  byte for byte tcmi_variants_text's for the record; behind them REF_FWD REF_REV (the plane of the upper-cased
+ *                  reference base), ALT_FWD ALT_REV (the record's allele), TOTAL_FWD TOTAL_REV (coverage) and STRAND = PASS, BIAS
+ *                  or LOW.  strand[0..n_cols): the counts at the records' distinct positions, ascending.  TCMI_E_ARG when
+ *                  strand[j].pos is not the records' j-th distinct position (or n_cols is not their number), and when a record has
+ *                  alt_fwd + alt_rev != count or tot_fwd + tot_rev != cov: the two kernels disagree, no table is written.  Sizing
+ *                  call, short buffer and *len as for tcmi_variants_text.  The header line (TCMI_VARIANTS_STRAND_HEADER) is the
+ *                  caller's.
+ * TCMI_STRAND_LDS: the columns whose list and counters a workgroup stages in LDS (15 KiB: ten workgroups per compute unit by LDS);
+ * a longer list is searched, and counted, in memory; for tests.
+ * Range errors are TCMI_E_ARG: min_strand_depth < 1, den outside 1..10^6, num outside 0..den. */
+typedef struct tcmi_strand_counts { int32_t fwd[7], rev[7]; int32_t pos, reserved /* 0 */; } tcmi_strand_counts;   /* 64 bytes */
+#define TCMI_STRAND_LDS 256
+#define TCMI_VARIANTS_STRAND_HEADER "REGION\tPOS\tREF\tALT\tALT_DP\tTOTAL_DP\tALT_FREQ\tREF_FWD\tREF_REV\tALT_FWD\tALT_REV\tTOTAL_FWD\tTOTAL_REV\tSTRAND\n"
+int  tcmi_readset_strand_counts(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *cols /* host */,
+                                tcmi_strand_counts *records /* host, n */);
+int  tcmi_strand_verdict(int32_t alt_fwd, int32_t alt_rev, int32_t tot_fwd, int32_t tot_rev, int32_t min_strand_depth, int64_t num, int64_t den);
+int  tcmi_variants_strand_text(const tcmi_variant *records, int64_t n, const tcmi_strand_counts *strand, int64_t n_cols, /* the records' distinct positions, ascending */
+                               int32_t min_strand_depth, int64_t num, int64_t den, const char *region, int64_t pos_offset,
+                               const uint8_t *ref, int64_t n_ref, char *text, int64_t cap, int64_t *len);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -388,7 +433,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_VARIANTS = 10 /* the variant table's three launches (count, scan, emit) as one bracket */,
        TCMI_K_INTERVALS = 11 /* the amplicon table's one launch */,
        TCMI_K_AMPLICON_READS = 12 /* tcmi_readset_amplicon_reads' one launch */,
-       TCMI_K_NKERNELS = 13 };
+       TCMI_K_STRAND_COUNTS = 13 /* tcmi_readset_strand_counts' one launch */,
+       TCMI_K_NKERNELS = 14 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);

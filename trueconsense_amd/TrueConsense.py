@@ -71,8 +71,8 @@ def _range_arg(parser, flag, hi):
     return check
 
 
-def _min_af_arg(parser):
-    """argparse `type=` callable of --min-af: text -> fractions.Fraction, exact ("0.03", "3e-2" and "3/100" are one value); refused
+def _min_af_arg(parser, flag="--min-af"):
+    """argparse `type=` callable of --min-af (and --strand-ratio): text -> fractions.Fraction, exact ("0.03", "3e-2" and "3/100" are one value); refused
     (parser.error, exit code 2) unless 0 <= F <= 1 with a reduced denominator of at most 10^6."""
     def check(text):
         from fractions import Fraction
@@ -80,7 +80,7 @@ def _min_af_arg(parser):
         try:
             return Fraction(*min_af_fraction(text.strip()))
         except ValueError as e:
-            parser.error(f"--min-af takes a frequency from 0 to 1 (a decimal or a fraction n/d, d up to 1000000): {color.YELLOW}{e}{color.END}.")
+            parser.error(f"{flag} takes a frequency from 0 to 1 (a decimal or a fraction n/d, d up to 1000000): {color.YELLOW}{e}{color.END}.")
     return check
 
 
@@ -108,6 +108,24 @@ def write_variant_table(path, parts):
     text = VARIANTS_HEADER + "".join(variants_text(recs, region, ref, off) for recs, region, ref, off in parts)
     with open(path, "w") as out:
         out.write(text)
+
+
+def strand_of(a):
+    """The parsed namespace's --variant-strand thresholds as keyword arguments of engine.variants_strand_text, or None without the flag."""
+    if not getattr(a, "variant_strand", False):
+        return None
+    return dict(min_strand_depth=int(a.strand_min_depth), strand_ratio=a.strand_ratio)
+
+
+def write_variant_strand_table(path, parts, rule):
+    """--variant-table under --variant-strand: the longer header line, then for every (records, their strand counts, region, reference
+    on the records' axis, pos_offset) its rows.  Nothing is written when a part's counts do not add up to its records (TcmiError).
+    -> (rows with STRAND = BIAS, rows with LOW)."""
+    from .engine import VARIANTS_STRAND_HEADER, variants_strand_text
+    text = "".join(variants_strand_text(recs, strand, region, ref, off, **rule) for recs, strand, region, ref, off in parts)
+    with open(path, "w") as out:
+        out.write(VARIANTS_STRAND_HEADER + text)
+    return text.count("\tBIAS\n"), text.count("\tLOW\n")
 
 
 def _names_a_table(line):
@@ -364,6 +382,16 @@ def GetArgs(givenargs):
     additive.append((("--variant-min-depth",), dict(type=_count_arg(parser, "--variant-min-depth", 0), default=None, metavar="N",
                                                     help="minimum coverage of a position of the variant table (ivar variants -m; default 10;\n"
                                                          "independent of -cov)")))
+    additive.append((("--variant-strand",), dict(action="store_true",
+                                                 help="the variant table's rows also say how the allele's reads split by strand (FLAG 0x10):\n"
+                                                      "REF_FWD REF_REV ALT_FWD ALT_REV TOTAL_FWD TOTAL_REV and STRAND = PASS, BIAS or LOW, counted\n"
+                                                      "in the records the device decoded; needs --variant-table and the device decoder; not with\n"
+                                                      "--batch or --index-override")))
+    additive.append((("--strand-min-depth",), dict(type=_count_arg(parser, "--strand-min-depth", 1), default=None, metavar="N",
+                                                   help="STRAND is LOW when either strand covers the position with fewer than N reads (default 10)")))
+    additive.append((("--strand-ratio",), dict(type=_min_af_arg(parser, "--strand-ratio"), default=None, metavar="F",
+                                               help="STRAND is BIAS when the allele's frequency on one strand is below F times its frequency on\n"
+                                                    "the other, 0..1, a decimal or n/d (default 1/10)")))
     additive.append((("--amplicon-table",), dict(type=str, default=None, metavar="File",
                                                  help="also write per amplicon of the scheme the depth of its columns, tab-separated: SAMPLE REGION\n"
                                                       "AMPLICON POOL START END LEN MEAN MEDIAN MIN MIN_POS BELOW (BELOW: columns under -cov), from\n"
@@ -395,6 +423,16 @@ def GetArgs(givenargs):
     a = parser.parse_args(givenargs)
     from fractions import Fraction
     a.variant_thresholds_given = any(v is not None for v in (a.min_af, a.min_alt_depth, a.variant_min_depth))
+    # --variant-strand: its refusals exit 1 with one line, nothing written
+    for bad, why in ((not a.variant_strand and (a.strand_min_depth is not None or a.strand_ratio is not None), "--strand-min-depth / --strand-ratio need --variant-strand."),
+                     (a.variant_strand and a.batch is not None, "--variant-strand goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
+                     (a.variant_strand and a.batch is None and a.variant_table is None, "--variant-strand needs --variant-table."),
+                     (a.variant_strand and a.index_override is not None, "--variant-strand does not go with --index-override: the overridden matrix no longer equals the reads.")):
+        if bad:
+            print(f"{why} Exiting...")
+            sys.exit(1)
+    a.strand_min_depth = 10 if a.strand_min_depth is None else a.strand_min_depth
+    a.strand_ratio = Fraction(1, 10) if a.strand_ratio is None else a.strand_ratio
     if a.batch is not None and a.variant_table is not None:
         parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
     if a.batch is None and a.variant_table is None and a.variant_thresholds_given:
@@ -481,6 +519,8 @@ def _child_argv(a, single, tables=True):
             out += ["--amplicon-reads", a.amplicon_reads, "--amplicon-reads-slack", str(a.amplicon_reads_slack)]
         if a.variant_table:
             out += ["--variant-table", a.variant_table]
+        if a.variant_strand:
+            out += ["--variant-strand", "--strand-min-depth", str(a.strand_min_depth), "--strand-ratio", str(a.strand_ratio)]
         if a.amplicon_table:
             out += ["--amplicon-table", a.amplicon_table]
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]
@@ -662,11 +702,23 @@ def _single_sample(a, flt, t):
     bam = LazyBam(a.input, threads=a.threads, read_filter=flt)      # reads reach the host only if an insert candidate needs its tokens
     t["bam_open"] = time.perf_counter()
     areads, got = amplicon_reads_of(a), {}
-    if areads:                                      # counted behind the step, on the read set the step returned, while its stream is resident
+    srule = strand_of(a)
+    if areads or srule:                             # counted behind the step, on the read set the step returned, while its stream is resident
         def count_reads(ctx, rs):
-            got["counts"] = ctx.amplicon_reads(rs, areads[1], areads[2])
-        counts = build_counts(bam, a.reference, on_readset=count_reads, need_device="--amplicon-reads")
-        write_amplicon_reads(a.amplicon_reads, a.samplename, got["counts"], areads[0])
+            if areads:
+                got["counts"] = ctx.amplicon_reads(rs, areads[1], areads[2])
+            if srule:                               # (the columns must be known now: the step computed the table's records)
+                got["strand"] = ctx.strand_counts_of(rs, ctx.step_variants())
+        if srule:
+            from .io import fasta
+            _state.default_context().set_variants(fasta.read_first_record(a.reference)[1], **variants_of(a))
+        try:
+            counts = build_counts(bam, a.reference, on_readset=count_reads, need_device="--variant-strand" if srule else "--amplicon-reads")
+        finally:
+            if srule:
+                _state.default_context().set_variants()
+        if areads:
+            write_amplicon_reads(a.amplicon_reads, a.samplename, got["counts"], areads[0])
     else:
         counts = build_counts(bam, a.reference)     # decoded, packed and tallied on the device
     IndexGff = Gffindex(a.features)
@@ -684,12 +736,15 @@ def _single_sample(a, flt, t):
 
     if a.depth_of_coverage is not None:
         BuildCoverage(indexDict, a.depth_of_coverage)
-    n_variants = 0
+    n_variants = n_bias = n_low = 0
     if a.variant_table is not None:                 # from the counts the consensus is called from (behind --index-override)
         from .io import fasta
         refID, refseq = fasta.read_first_record(a.reference)
         recs = _state.default_context().variants(indexDict.counts, refseq, **variants_of(a))
-        write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
+        if srule:                                   # (the writer refuses counts that do not add up to these records)
+            n_bias, n_low = write_variant_strand_table(a.variant_table, [(recs, got["strand"], refID, refseq, 0)], srule)
+        else:
+            write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
         n_variants = len(recs)
 
     amps, n_below = amplicons_of(a), 0
@@ -709,7 +764,8 @@ def _single_sample(a, flt, t):
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
-                       "variant_records": n_variants, "amplicons": len(amps) if amps else 0, "amplicons_below": n_below,
+                       "variant_records": n_variants, "variant_strand_bias": n_bias, "variant_strand_low": n_low,
+                       "amplicons": len(amps) if amps else 0, "amplicons_below": n_below,
                        "amplicon_reads_ambiguous": int(got["counts"]["reads"][-2]) if areads else 0,
                        "amplicon_reads_unassigned": int(got["counts"]["reads"][-1]) if areads else 0,
                        "bam_bytes": os.path.getsize(a.input)}, fh)

@@ -122,7 +122,7 @@ def axis_reference(records, header_names, shift, axis_len):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, amplicon_reads=None):
+                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, amplicon_reads=None, variant_strand=False):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
@@ -135,7 +135,9 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     (Context.set_intervals): the step also computes the amplicon table's records, which info receives as "amplicon_table".
     amplicon_reads = ([(fs, le, rs, fe)] on the axis, slack) (Context.amplicon_reads): behind the step the records of the read set are
     counted per amplicon in the decoded stream, which info receives as "amplicon_reads"; a file the device decoder declines is
-    refused then (reads decoded on the host leave no stream on the device)."""
+    refused then (reads decoded on the host leave no stream on the device).  variant_strand (with variants): behind the step the
+    planes at the table's distinct columns are counted per strand in the decoded stream (Context.strand_counts), which info
+    receives as "variant_strand"; a file the device decoder declines is refused likewise."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
@@ -147,7 +149,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_intervals(*intervals)
     host = None
     try:
-        rs = device_readset(ctx, path, need="--amplicon-reads" if amplicon_reads else None)    # (the floor it refuses under is the one just set)
+        rs = device_readset(ctx, path, need="--variant-strand" if variant_strand else "--amplicon-reads" if amplicon_reads else None)    # (the floor it refuses under is the one just set)
         if rs is None:
             host = BamFile(path, threads=threads, read_filter=read_filter)
             try:
@@ -163,6 +165,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
             plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
             if variants and info is not None:
                 info["variant_table"] = ctx.step_variants()
+                if variant_strand:                              # (one call over all contigs' columns on the shifted axis; the stream is still resident)
+                    info["variant_strand"] = ctx.strand_counts_of(rs, info["variant_table"])
             if intervals and info is not None:
                 info["amplicon_table"] = ctx.step_intervals()
             if amplicon_reads and info is not None:             # (the layout is still set: the read set's shifts are the table's)
@@ -184,8 +188,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_reads,
-                               write_amplicon_table, write_variant_table)
+    from .TrueConsense import (amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, read_filter_of, strand_of, variants_of,
+                               write_amplicon_reads, write_amplicon_table, write_variant_strand_table, write_variant_table)
     flt, seen = read_filter_of(a), {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -206,13 +210,16 @@ def run(a):
                                                                  threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
                                                                  min_baseq=a.min_baseq, primers=prm, variants=var,
                                                                  intervals=(amplicon_intervals(amps), mincov) if amps else None,
-                                                                 amplicon_reads=areads[1:] if areads else None)
+                                                                 amplicon_reads=areads[1:] if areads else None,
+                                                                 variant_strand=strand_of(a) is not None)
     rcounts = seen.pop("amplicon_reads", None)
     seen["amplicon_reads_ambiguous"] = 0 if rcounts is None else int(rcounts["reads"][-2])
     seen["amplicon_reads_unassigned"] = 0 if rcounts is None else int(rcounts["reads"][-1])
     seen.setdefault("reads_primer_masked", 0)
     table = seen.pop("variant_table", None)
     seen["variant_records"] = 0 if table is None else len(table)
+    strand = seen.pop("variant_strand", None)
+    seen["variant_strand_bias"] = seen["variant_strand_low"] = 0
     arecs = seen.pop("amplicon_table", None)
     seen["amplicons_below"] = 0 if arecs is None else int((arecs["below"] > 0).sum())
 
@@ -274,8 +281,14 @@ def run(a):
     if table is not None:                           # one file, the contigs in axis order; rows carry the contig's name and its own positions
         parts = []
         for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]):
-            parts.append((table[(table["pos"] >= s) & (table["pos"] < s + len(seq))], rid, axis_ref, s))
-        write_variant_table(a.variant_table, parts)
+            part = (table[(table["pos"] >= s) & (table["pos"] < s + len(seq))], rid, axis_ref, s)
+            if strand is not None:                  # (each contig's rows with the counts of its own columns)
+                part = part[:1] + (strand[(strand["pos"] >= s) & (strand["pos"] < s + len(seq))],) + part[1:]
+            parts.append(part)
+        if strand is not None:
+            seen["variant_strand_bias"], seen["variant_strand_low"] = write_variant_strand_table(a.variant_table, parts, strand_of(a))
+        else:
+            write_variant_table(a.variant_table, parts)
     if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
         write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
     if rcounts is not None:                         # one file: REGION is each amplicon's contig

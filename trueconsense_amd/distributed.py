@@ -366,7 +366,7 @@ def _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks):
 
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
                             step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
-                            min_baseq=None, primers=None, amplicon_reads=None):
+                            min_baseq=None, primers=None, amplicon_reads=None, variant_strand=None):
     """BASELINE configs[4] all the way: ONE BAM file over `world` ranks -> its consensus FASTA text on rank 0 (None on the others).
     What the ranks jointly replace is the reference's single pile-up pass (indexing.py:96-100), its insert candidates' region
     pile-ups (Events.py:47-82) and the walk (Sequences.py:168-322):
@@ -397,7 +397,11 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     likewise (Context.set_primers; no rows clears it, None leaves what the context has).  amplicon_reads = ([(fs, le, rs, fe)], slack):
     behind the step every rank counts the records of its own read set per amplicon (Context.amplicon_reads) and the [n + 2, 2] int64
     counts are summed to rank 0 over the same group — a record starts in exactly one rank's blocks, so the sum is the file's; with
-    return_parts rank 0's tuple then has them as a fourth item."""
+    return_parts rank 0's tuple then has them as a fourth item.  variant_strand = the keyword arguments of Context.variants (ref,
+    min_af, min_alt_depth, min_depth): behind that, rank 0 lists the variant table's records from the reduced matrix and broadcasts
+    their distinct columns, every rank counts the planes at those columns per strand in its own read set (Context.strand_counts), the
+    ranks agree that everybody has counts, and the [n, 14] int32 counts are summed to rank 0 likewise; with return_parts rank 0's
+    tuple then ends with (records, strand counts)."""
     import time
     import torch
     import torch.distributed as dist
@@ -405,7 +409,9 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     L = int(ref_len)
     ld, n_words = split_words(L, world)
     root = rank == 0
-    plain = alt = flags = counts_root = reads_root = None
+    plain = alt = flags = counts_root = reads_root = strand_root = None
+    if variant_strand is not None and step_fn is not None:
+        raise ValueError("consensus_split_bamfile: variant_strand counts in the stream the device decoded: it does not go with step_fn")
     own_ctx, own_d = ctx is None, dbam is None
     d, rs = dbam, None
     err = None
@@ -451,7 +457,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                     err = (rc, (lib().tcmi_last_error(ctx.handle) or b"").decode("utf-8", "replace"))
                 elif root:
                     plain, alt, flags = planes
-                    if return_parts:
+                    if return_parts or variant_strand is not None:
                         counts_root = np.ascontiguousarray(t[:7 * ld].view(7, ld)[:, :L].T.cpu().numpy())
         else:
             d_blocks = step_fn("n_blocks")
@@ -493,6 +499,34 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                 dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
                 mine = tr.cpu().numpy()
             reads_root = mine if root else None
+        if variant_strand is not None:                               # strand counts at the table's columns: every rank its own records, one sum to rank 0
+            from .engine import STRAND_DTYPE
+            vrecs = ctx.variants(counts_root, **variant_strand) if root else None
+            vcols = [np.unique(vrecs["pos"].astype(np.int64)).tolist() if root else None]
+            if multi:
+                dist.broadcast_object_list(vcols, src=0, group=group)
+            vcols = np.asarray(vcols[0], np.int64)
+            mine, serr = None, None
+            try:
+                got = ctx.strand_counts_of(rs, cols=vcols)
+                mine = np.ascontiguousarray(np.concatenate([got["fwd"], got["rev"]], axis=1).reshape(len(vcols), 14))
+            except TcmiError as e:
+                serr = (e.code, str(e))
+            if multi:                                                # nobody enters the reduce unless everybody has counts
+                alls = [None] * dist.get_world_size(group)
+                dist.all_gather_object(alls, serr, group=group)
+                serr = next((v for v in alls if v), None)
+            if serr is not None:
+                raise TcmiError(serr[0], "consensus_split_bamfile: strand counts: %s" % serr[1])
+            if multi and len(vcols):
+                on_gpu = dist.get_backend(group) == "nccl"
+                tr = torch.from_numpy(mine).cuda() if on_gpu else torch.from_numpy(mine)
+                dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
+                mine = tr.cpu().numpy()
+            if root:
+                strand = np.zeros(len(vcols), STRAND_DTYPE)
+                strand["fwd"], strand["rev"], strand["pos"] = mine[:, :7], mine[:, 7:], vcols
+                strand_root = (vrecs, strand)
         # the insert-candidate columns, from rank 0 to everybody
         cand = [(np.nonzero(flags & 8)[0] + 1).tolist()] if root else [None]
         if multi:
@@ -537,9 +571,8 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
             timings["release"] = time.perf_counter() - t2
             timings["total"] = time.perf_counter() - t0
     if return_parts:
-        if amplicon_reads is not None:
-            return (text, counts_root, toks, reads_root) if root else None
-        return (text, counts_root, toks) if root else None
+        parts = (text, counts_root, toks) + ((reads_root,) if amplicon_reads is not None else ()) + ((strand_root,) if variant_strand is not None else ())
+        return parts if root else None
     return text
 
 

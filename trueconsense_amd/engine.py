@@ -130,6 +130,47 @@ def amplicon_reads_compile(amps4, slack=0):
     return table[:, :n]
 
 
+# struct tcmi_strand_counts: the count matrix's seven planes at one column, split by the record's strand (--variant-strand)
+STRAND_DTYPE = np.dtype([("fwd", np.int32, (7,)), ("rev", np.int32, (7,)), ("pos", np.int32), ("reserved", np.int32)])
+VARIANTS_STRAND_HEADER = "REGION\tPOS\tREF\tALT\tALT_DP\tTOTAL_DP\tALT_FREQ\tREF_FWD\tREF_REV\tALT_FWD\tALT_REV\tTOTAL_FWD\tTOTAL_REV\tSTRAND\n"
+STRAND_LDS = 256                 # TCMI_STRAND_LDS: columns whose list and counters the kernel stages in LDS
+STRAND_MAX_COLS = 1 << 20        # the columns of one tcmi_readset_strand_counts call
+STRAND_VERDICTS = ("PASS", "BIAS", "LOW")
+
+
+def strand_verdict(alt_fwd, alt_rev, tot_fwd, tot_rev, min_strand_depth=10, strand_ratio="1/10"):
+    """tcmi_strand_verdict (HOST, exact integers) -> 0 PASS, 1 BIAS, 2 LOW: LOW iff a strand's depth is below min_strand_depth, else
+    BIAS iff the smaller of the two strand frequencies is below strand_ratio times the larger (a tie is PASS)."""
+    num, den = min_af_fraction(strand_ratio)
+    rc = lib().tcmi_strand_verdict(int(alt_fwd), int(alt_rev), int(tot_fwd), int(tot_rev), int(min_strand_depth), num, den)
+    if rc < 0:
+        raise _ffi.TcmiError(rc, "tcmi_strand_verdict: a negative count, min_strand_depth < 1 or a ratio outside 0..1")
+    return rc
+
+
+def variants_strand_text(records, strand, region, ref, pos_offset=0, min_strand_depth=10, strand_ratio="1/10"):
+    """--variant-strand's rows for `records` (tcmi_variants_strand_text; HOST): variants_text's seven fields, then REF_FWD, REF_REV,
+    ALT_FWD, ALT_REV, TOTAL_FWD, TOTAL_REV and STRAND.  strand: Context.strand_counts at the records' distinct positions, ascending.
+    -> str, without the header line (VARIANTS_STRAND_HEADER).  TcmiError(E_ARG) when the counts do not belong to the records or do
+    not add up to them."""
+    records = np.ascontiguousarray(records, VARIANT_DTYPE)
+    strand = np.ascontiguousarray(strand, STRAND_DTYPE)
+    ref = _ref_bytes(ref)
+    num, den = min_af_fraction(strand_ratio)
+    args = (ptr(records) if len(records) else None, len(records), ptr(strand) if len(strand) else None, len(strand), int(min_strand_depth), num, den,
+            str(region).encode(), int(pos_offset), ptr(ref) if len(ref) else None, len(ref))
+    ln = C.c_int64(0)
+    buf = None
+    rc = lib().tcmi_variants_strand_text(*args, None, 0, C.byref(ln))       # the sizing call
+    if not rc:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib().tcmi_variants_strand_text(*args, C.cast(buf, C.c_void_p), ln.value, C.byref(ln))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_variants_strand_text: the strand counts do not belong to the records or do not add up to them "
+                                 "(or a record does not fit the reference, the offset or the thresholds)")
+    return buf.raw[:ln.value].decode("latin-1")
+
+
 def _grab(vp, dtype, n):
     """n items of dtype at address vp (memory the library owns) -> a fresh numpy array."""
     out = np.empty(n, dtype)
@@ -413,6 +454,26 @@ class Context:
         check(lib().tcmi_readset_amplicon_reads(self.handle, readset.handle, len(fs), ptr(fs), ptr(le), ptr(rs), ptr(fe), int(slack), ptr(out)),
               self.handle)
         return out
+
+    def strand_counts(self, readset, cols):
+        """The count matrix's planes at `cols`, split by strand (tcmi_readset_strand_counts): cols strictly ascending on the count
+        matrix's axis, 1..2^20 of them -> a structured array (STRAND_DTYPE): fwd and rev as [n, 7] in plane order (the records without
+        and with FLAG 0x10), pos; fwd + rev is the matrix a step tallies from the read set.  The read set must have been decoded on
+        the device and its stream must still be resident on this context (no other upload since), else TcmiError(E_UNSUPPORTED)."""
+        cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
+        out = np.zeros(len(cols), STRAND_DTYPE)
+        check(lib().tcmi_readset_strand_counts(self.handle, readset.handle, len(cols), ptr(cols) if len(cols) else None, ptr(out) if len(cols) else None),
+              self.handle)
+        return out
+
+    def strand_counts_of(self, readset, records=None, cols=None):
+        """strand_counts at the distinct positions of variant `records` (or at `cols`, ascending), in pieces of 2^20 columns -> a
+        structured array (STRAND_DTYPE), empty without columns"""
+        if cols is None:
+            cols = np.unique(np.ascontiguousarray(records, VARIANT_DTYPE)["pos"].astype(np.int64))
+        cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
+        parts = [self.strand_counts(readset, cols[k:k + STRAND_MAX_COLS]) for k in range(0, len(cols), STRAND_MAX_COLS)]
+        return np.concatenate(parts) if parts else np.zeros(0, STRAND_DTYPE)
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
