@@ -2,12 +2,14 @@
 // stream the packer left in the context's arena, counted per amplicon of a scheme (include/tcmi.h: tcmi_readset_amplicon_reads; the
 // rule, the compiled table and the lookup: amplicon_reads_rule.h).
 //
+// Here: the kernel and the entry that compiles the table and unpacks the sums.  Which record is kept and where it lies on the axis:
+// pack_device.h's kept_span; the residency refusals, the scratch, the launch shape, the download and the sub-ranges: stream_count.h.
+//
 // One launch, one lane per record, 256-lane workgroups that stride over the records: the grid is min(ceil(records / 256), compute
 // units x 8).  Eight workgroups per CU is what the kernel's LDS (16 KiB: the table and the counters of up to TCMI_AMPLICON_READS_LDS
 // amplicons) and its wavefront slots admit; striding instead of one workgroup per 256 records lets a workgroup stage the table once and
 // hand its counters to memory once, whatever the file's size.  No workgroup waits for another.
-//   per record   the fixed fields (view_rec: two unaligned loads), the read filter the set was built under (passes), the contig's
-//                shift (shift_of), one walk over the CIGAR for the reference span — unaligned dword loads, no base is read —, then
+//   per record   kept_span (the fixed fields, the read filter, the contig's shift, one walk over the CIGAR for the reference span), then
 //                the lookup: a binary search over the widened starts and three more words.
 //   the table    staged in LDS while n <= TCMI_AMPLICON_READS_LDS; a larger one is searched where it lies (L2).
 //   counters     a sorted BAM puts a wavefront's 64 reads into one or two amplicons: the lanes that hit the same counter are joined
@@ -15,18 +17,15 @@
 //                to the workgroup's counters in LDS while the table is staged, else straight to memory.  At its end a workgroup
 //                hands every non-zero LDS counter to memory with one atomic add.
 // The sums are integers: their order does not matter and every run gives the same numbers.  The stream is only read.
-#include <algorithm>
-#include <cstring>
 #include <vector>
 
-#include "pack_device.h"
+#include "stream_count.h"
 #include "amplicon_reads_rule.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = SC_BLOCK;
 constexpr int LDS_N = TCMI_AMPLICON_READS_LDS;
-constexpr int WG_PER_CU = 8;
 
 struct ArArgs {
     PackSrc src;                    // the resident stream, the read set's filter and layout
@@ -39,18 +38,9 @@ struct ArArgs {
 __device__ inline int32_t slot_of(const ArArgs &a, const tcmi_ar_table &tab, int64_t i, bool *full)
 {
     *full = false;
-    const ReadView v = view_rec(a.src.stream + a.src.rec_off[i]);
-    // kept exactly when the device packer keeps it (pack_device.hip: classify_view)
-    if ((v.flag & 0x4u) || !passes(a.src.flt, v) || v.bad || v.pos < 0) return -1;
-    const int32_t shift = shift_of(a.src, v.tid);
-    if (shift < 0) return -1;
-    int64_t span = 0;
-    for (uint32_t k = 0; k < v.n_cigar; ++k) {
-        const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k);
-        if (consumes_ref(c & 0xFu)) span += c >> 4;
-    }
-    if (span <= 0) return -1;
-    const int64_t p = (int64_t)v.pos + shift, q = p + span - 1;
+    ReadView v;
+    int64_t p, q;
+    if (!kept_span(a.src, i, v, p, q)) return -1;
     // (the packer refuses a file with a read that ends at or beyond 2^29; a column up there is beyond every amplicon all the same)
     const int32_t hit = tcmi_ar_lookup(tab, (int32_t)(p < INT32_MAX ? p : INT32_MAX), (int32_t)(q < INT32_MAX ? q : INT32_MAX), full);
     return hit >= 0 ? hit : hit == TCMI_AR_AMBIGUOUS ? a.n : a.n + 1;
@@ -103,54 +93,6 @@ __global__ __launch_bounds__(BLOCK) void amplicon_reads_kernel(ArArgs a)
     }
 }
 
-// one read set on its own context: the compiled table (host, 6 n words) -> sums[2 * (n + 2)] ADDED to
-int count_one(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n, const int32_t *table, int64_t *sums)
-{
-    if (rs->packed_on_device != 2)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "amplicon reads: the read set was not decoded on the device (flat arrays or the host reader): there is no record stream to count in");
-    if (rs->n_piled == 0) return TCMI_OK;                   // (no kept record: nothing to add; such a set may hold no stream at all)
-    if (rs->device != ctx->device)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "amplicon reads: the read set lives on device %d, this context on device %d", rs->device, ctx->device);
-    if (!rs->d_stream || !rs->d_rec_off || rs->arena_epoch != ctx->arena_epoch)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "amplicon reads: the read set's decoded stream is no longer resident on this context (another upload happened on it)");
-    if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "amplicon reads: the context's contig layout changed since the read set was uploaded");
-    TCMI_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t b_tab = tcmi_align256((size_t)TCMI_AR_WORDS * n * 4), b_cnt = tcmi_align256((size_t)2 * (n + 2) * 8);
-    // scratch of the context, grow-only (no hipMalloc / hipFree per call: hipFree waits for the whole device)
-    if (ctx->ar_dev_cap < b_tab + b_cnt) {
-        if (ctx->ar_dev) { TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->ar_dev); ctx->ar_dev = nullptr; ctx->ar_dev_cap = 0; }
-        const size_t want = b_tab + b_cnt + (64u << 10);
-        if (hipMalloc((void **)&ctx->ar_dev, want) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "amplicon reads: device scratch (%zu bytes)", want);
-        ctx->ar_dev_cap = want;
-    }
-    char *pin = static_cast<char *>(tcmi_ctx_pinned(ctx, b_tab + b_cnt));
-    if (!pin) return tcmi_fail(ctx, TCMI_E_NOMEM, "amplicon reads: pinned scratch");
-    std::memcpy(pin, table, (size_t)TCMI_AR_WORDS * n * 4);
-    ArArgs a;
-    a.src = stream_src(rs);
-    a.src.lay = rs->d_lay; a.src.n_lay = rs->n_lay;
-    a.table = reinterpret_cast<const int32_t *>(ctx->ar_dev);
-    a.counts = reinterpret_cast<unsigned long long *>(ctx->ar_dev + b_tab);
-    a.n = n;
-    TCMI_HIP(ctx, hipMemcpyAsync(ctx->ar_dev, pin, (size_t)TCMI_AR_WORDS * n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TCMI_HIP(ctx, hipMemsetAsync(a.counts, 0, (size_t)2 * (n + 2) * 8, ctx->stream));
-    if (rs->n_reads > 0) {
-        const int64_t blocks = (rs->n_reads + BLOCK - 1) / BLOCK;
-        const int64_t grid = std::min<int64_t>(blocks, (int64_t)std::max(ctx->n_cu, 1) * WG_PER_CU);
-        (void)hipGetLastError();                            // drop any stale error of this thread
-        tcmi_prof_begin(ctx, TCMI_K_AMPLICON_READS);
-        hipLaunchKernelGGL(amplicon_reads_kernel, dim3((unsigned)grid), dim3(BLOCK), 0, ctx->stream, a);
-        tcmi_prof_end(ctx, TCMI_K_AMPLICON_READS);
-        TCMI_HIP(ctx, hipGetLastError());
-    }
-    TCMI_HIP(ctx, hipMemcpyAsync(pin + b_tab, a.counts, (size_t)2 * (n + 2) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int64_t *got = reinterpret_cast<const int64_t *>(pin + b_tab);
-    for (int64_t k = 0; k < 2 * ((int64_t)n + 2); ++k) sums[k] += got[k];
-    return TCMI_OK;
-}
-
 } // namespace
 
 extern "C" int tcmi_readset_amplicon_reads(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *fs, const int64_t *le, const int64_t *rs_,
@@ -166,17 +108,20 @@ extern "C" int tcmi_readset_amplicon_reads(tcmi_ctx *ctx, const tcmi_readset *rs
         return tcmi_fail(ctx, TCMI_E_NOMEM, "amplicon reads: no host memory for %lld amplicons", (long long)n);
     }
     if (tcmi_amplicon_reads_build(n, fs, le, rs_, fe, slack, table.data(), msg, sizeof msg)) return tcmi_fail(ctx, TCMI_E_ARG, "amplicon reads: %s", msg);
-    if (!rs->parts.empty()) {
-        // a read set of sub-ranges (tcmi_split_step, "split_sub"): every record starts in exactly one part — the sum over the parts,
-        // each counted on its own context, where its stream lives
-        for (const tcmi_readset::Part &pt : rs->parts) {
-            const int rc = count_one(pt.cx, pt.rs, (int32_t)n, table.data(), sums.data());
-            if (rc) return tcmi_fail(ctx, rc, "%s", pt.cx->err.c_str());
-        }
-    } else {
-        const int rc = count_one(ctx, rs, (int32_t)n, table.data(), sums.data());
-        if (rc) return rc;
-    }
+    // the compiled table (6 n words) in, {reads, full} of n + 2 slots out
+    const int rc = tcmi_stream_count_parts(
+        ctx, rs, "amplicon reads", table.data(), table.size() * 4, sums.size() * 8,
+        [n](tcmi_ctx *cx, const tcmi_readset *, const PackSrc &src, const char *d_in, char *d_cnt, unsigned grid) {
+            const ArArgs a = {src, reinterpret_cast<const int32_t *>(d_in), reinterpret_cast<unsigned long long *>(d_cnt), (int32_t)n};
+            tcmi_prof_begin(cx, TCMI_K_AMPLICON_READS);
+            hipLaunchKernelGGL(amplicon_reads_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
+            tcmi_prof_end(cx, TCMI_K_AMPLICON_READS);
+        },
+        [s = sums.data(), m = sums.size()](const char *counts) {
+            const int64_t *got = reinterpret_cast<const int64_t *>(counts);
+            for (size_t k = 0; k < m; ++k) s[k] += got[k];
+        });
+    if (rc) return rc;
     for (int64_t i = 0; i < n + 2; ++i) { records[i].reads = sums[(size_t)(2 * i)]; records[i].full = sums[(size_t)(2 * i + 1)]; }
     return TCMI_OK;
 }

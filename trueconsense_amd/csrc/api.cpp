@@ -111,7 +111,7 @@ static void ctx_release(tcmi_ctx *c)
     for (auto &b : c->blob_pool) (void)hipFree(b.p);
     if (c->tok_dev) (void)hipFree(c->tok_dev);
     if (c->tok_host) (void)hipHostFree(c->tok_host);
-    if (c->ar_dev) (void)hipFree(c->ar_dev);
+    if (c->count_dev) (void)hipFree(c->count_dev);
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     if (c->h_desc) (void)hipHostFree(c->h_desc);
     tcmi_tables_release(c);

@@ -7,7 +7,7 @@
 #include <cstring>
 #include <vector>
 
-#include "pack_device.h"
+#include "stream_count.h"
 
 namespace {
 
@@ -227,7 +227,7 @@ static int collect_ins_entries(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n_
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "long reads lie outside the packed set: their tokens are not looked at here (host sweep)");
     if (rs->n_lay > 0)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set was uploaded under a contig layout: host sweep (tcmi_modal_tokens_layout)");
-    if (!rs->d_stream || rs->arena_epoch != ctx->arena_epoch || rs->device != ctx->device)
+    if (tcmi_stream_gone(ctx, rs))
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set's decoded stream is no longer (or never was) resident on this context: host sweep");
     for (int32_t k = 1; k < n_pos; ++k)
         if (positions[k] <= positions[k - 1]) return tcmi_fail(ctx, TCMI_E_ARG, "positions must ascend");
@@ -239,18 +239,11 @@ static int collect_ins_entries(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n_
     // binary search on the device; what comes back is two numbers per column.  Scratch (device + pinned host) belongs to the
     // context and only grows: hipMalloc / hipFree per file cost more than the kernels (hipFree waits for the whole device).
     auto scratch = [&](size_t dev_bytes, size_t host_bytes) -> int {
-        if (ctx->tok_dev_cap < dev_bytes) {
-            if (ctx->tok_dev) { (void)hipStreamSynchronize(ctx->stream); (void)hipFree(ctx->tok_dev); ctx->tok_dev = nullptr; ctx->tok_dev_cap = 0; }
-            const size_t want = dev_bytes + dev_bytes / 4 + (1 << 20);
-            if (hipMalloc((void **)&ctx->tok_dev, want) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "insert-token scratch (%zu bytes)", want);
-            ctx->tok_dev_cap = want;
-        }
-        if (ctx->tok_host_cap < host_bytes) {
-            if (ctx->tok_host) { (void)hipStreamSynchronize(ctx->stream); (void)hipHostFree(ctx->tok_host); ctx->tok_host = nullptr; ctx->tok_host_cap = 0; }
-            const size_t want = host_bytes + host_bytes / 4 + (1 << 20);
-            if (hipHostMalloc((void **)&ctx->tok_host, want, hipHostMallocDefault) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "insert-token host scratch (%zu bytes)", want);
-            ctx->tok_host_cap = want;
-        }
+        const size_t dev_slack = dev_bytes / 4 + (1 << 20), host_slack = host_bytes / 4 + (1 << 20);
+        if (!tcmi_grow_dev(ctx, ctx->tok_dev, ctx->tok_dev_cap, dev_bytes, dev_slack))
+            return tcmi_fail(ctx, TCMI_E_NOMEM, "insert-token scratch (%zu bytes)", dev_bytes + dev_slack);
+        if (!tcmi_grow_pinned(ctx, ctx->tok_host, ctx->tok_host_cap, host_bytes, host_slack))
+            return tcmi_fail(ctx, TCMI_E_NOMEM, "insert-token host scratch (%zu bytes)", host_bytes + host_slack);
         return TCMI_OK;
     };
     std::vector<int32_t> cols((size_t)n_pos);

@@ -1,6 +1,7 @@
 // pack_device.h — DEVICE (.hip files only): one read as every kernel that goes to the reads themselves sees it, whether it lies in the
 // flat arrays of struct tcmi_reads or in the inflated BAM stream (SAM spec §4.2) — the packers (pack_device.hip), the insert-candidate
-// kernels (ins_entries.hip) and the long-read tally (tally.hip: tally_stream_kernel).  What only the packers use stays in pack_device.hip.
+// kernels (ins_entries.hip), the long-read tally (tally.hip: tally_stream_kernel) and the counting kernels (amplicon_reads.hip,
+// strand_counts.hip; their host side: stream_count.h).  What only the packers use stays in pack_device.hip.
 #pragma once
 #include "tcmi_internal.h"
 
@@ -142,5 +143,57 @@ __device__ inline bool ins_after(const uint8_t *cg, uint32_t n, uint32_t k)
     }
     return tot > 0;
 }
+
+// ---- what the kernels that walk the records where they lie share (tally.hip: tally_stream_kernel; amplicon_reads.hip; strand_counts.hip) ----
+// the reference span of a read: the sum of its reference-consuming ops (unaligned dword loads, no base is read)
+__device__ inline int64_t ref_span(const ReadView &v)
+{
+    int64_t span = 0;
+    for (uint32_t k = 0; k < v.n_cigar; ++k) {
+        const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k);
+        if (consumes_ref(c & 0xFu)) span += c >> 4;
+    }
+    return span;
+}
+
+// Record i of a stream source: true exactly when the device packer keeps it, with its first and last column [p, q] on the one axis.
+// THE kept-record rule outside the packer: mapped, through the read filter the set was built under, consistent, on a reference that
+// piles up, with a reference span.  The packer's own copy is pack_device.hip's classify_view (one walk that also decides `simple`, at
+// pk_index's register ceiling): a rule changed here is changed there, and the other way round.
+__device__ inline bool kept_span(const PackSrc &s, int64_t i, ReadView &v, int64_t &p, int64_t &q)
+{
+    v = view_rec(s.stream + s.rec_off[i]);
+    if ((v.flag & 0x4u) || !passes(s.flt, v) || v.bad || v.pos < 0) return false;
+    const int32_t shift = shift_of(s, v.tid);
+    if (shift < 0) return false;
+    const int64_t span = ref_span(v);
+    if (span <= 0) return false;
+    p = (int64_t)v.pos + shift;
+    q = p + span - 1;
+    return true;
+}
+
+// the lookup in a compiled primer segment list (primer_table.h; t: a[n] | b[n] | v[n]): the value of the segment that holds x, or `none`
+// (host twin: primer_table.cpp's tcmi_pseg_find)
+__device__ inline int32_t seg_find(const int32_t *t, int32_t n, int32_t x, int32_t none)
+{
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (t[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo > 0 && x < t[n + lo - 1] ? t[2 * n + lo - 1] : none;
+}
+
+// leaves of the token rule: the count matrix's plane of a one-letter SEQ nibble (A 1, C 2, G 4, T 8), and the quality of query index
+// qi — 0 at or beyond l_seq (QUAL lies behind SEQ; the first form is for a kernel that holds the pointer across a loop)
+__device__ inline int base_plane(uint32_t nib)
+{
+    const int b = __ffs(nib) - 1;
+    return b == 0 ? TCMI_A : b == 1 ? TCMI_C : b == 2 ? TCMI_G : TCMI_T;
+}
+__device__ inline uint32_t qual_at(const uint8_t *qual, int32_t l_seq, int32_t qi) { return qi < l_seq ? byte_at(qual + qi) : 0u; }
+__device__ inline uint32_t qual_at(const ReadView &v, int32_t qi) { return qual_at(v.seq + ((size_t)v.l_seq + 1) / 2, v.l_seq, qi); }
 
 } // namespace

@@ -158,6 +158,7 @@ __device__ inline void ref_extent_max(int32_t *ext, int32_t t, int32_t e)
 // `shift`: where the read's reference starts on the axis (< 0: not piled up), `slot_end`: where its slot ends, `layout`: a contig
 // layout is set (reads on other references are not an error then).  The read filter: the callers hand a failing record in with FLAG
 // 0x4 set (filter_view) — it is ignored in the three places below, and in pk_classify's `dropped`, exactly as an unmapped record is
+// The kernels that count in the stream afterwards ask pack_device.h's kept_span which records are kept here: the two hold the same rule
 __device__ inline Classified classify_view(const ReadView &v, int32_t mode, int32_t shift, int32_t slot_end, bool layout, const uint8_t *rec,
                                            bool stream_long_ok, PackTotals *tot)
 {
@@ -471,17 +472,7 @@ using PrimerTab = tcmi_primer_tab;
 // an ARTIC-like scheme of a hundred amplicons.  A probe that hits L2 costs 180 - 225 cycles, one of LDS about 50, and a workgroup's 256
 // reads walk the same few entries; staging the table costs the workgroup one coalesced load and one barrier.  So a workgroup stages a
 // table of up to PT_LDS segments (3 KiB: the kernels keep their workgroups per CU) and searches larger ones where they lie.
-constexpr int PT_LDS = 256;
-__device__ inline int32_t seg_find(const int32_t *t, int32_t n, int32_t x, int32_t none)      // (t: a[n] | b[n] | v[n]; host twin: tcmi_pseg_find)
-{
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (t[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo > 0 && x < t[n + lo - 1] ? t[2 * n + lo - 1] : none;
-}
+constexpr int PT_LDS = 256;                 // (the search itself: pack_device.h's seg_find)
 // a read of `len` columns (1 .. 1023) whose first lies at p
 __device__ inline uint32_t mask_word(const int32_t *t, int32_t n_head, int32_t n_tail, int32_t p, int32_t len)
 {
@@ -581,7 +572,7 @@ __device__ inline void pack_read(const ReadView &v, const PackOut &o, PackTotals
                     if constexpr (BQ) {
                         // the floor skips every column of the op or none; the mask skips the op's masked columns: no OTHER event, no
                         // X event and no coverage there, and no I mark when the op's last column is skipped
-                        const bool below = Q && (y < v.l_seq ? byte_at(qual + y) : 0u) < Q;
+                        const bool below = Q && (y < v.l_seq ? byte_at(qual + y) : 0u) < Q;     // (qual_at written out: the call changes the two BQ kernels' code)
                         const int head = (int)(mw & 1023u), keep_end = len - (int)(mw >> 10);
                         const int x1 = min(x + oplen, len);
                         if (below || x < head || x1 > keep_end) {

@@ -2,12 +2,15 @@
 // (FLAG 0x10), counted in the inflated BAM stream a device-decoded read set left in the context's arena (include/tcmi.h:
 // tcmi_readset_strand_counts).  The matrix sums the strands and the packed set does not keep the flag: only the records have it.
 //
+// Here: the kernel, its per-column walk, and the entry that checks and narrows the columns and unpacks the sums.  Which record is kept
+// and where it lies on the axis (kept_span), the primer table's lookup (seg_find) and the leaves of the token rule (base_plane,
+// qual_at): pack_device.h; the residency refusals, the scratch, the launch shape, the download and the sub-ranges: stream_count.h.
+//
 // One launch, one lane per record, 256-lane workgroups that stride over the records: the grid is min(ceil(records / 256), compute
-// units x 8), as amplicon_reads.hip's.  LDS: the columns and [n][14] counters of up to TCMI_STRAND_LDS columns, 15 KiB.
-//   per record   the fixed fields (view_rec), the read filter the set was built under (passes), the contig's shift (shift_of), one walk
-//                over the CIGAR for the reference span [p, q], the primer table's head_end / tail_start when the set has one, then a
-//                binary search for the first queried column >= p.  A record without a queried column in [p, q] — nearly every record
-//                of a sparse query — is done here.
+// units x 8).  LDS: the columns and [n][14] counters of up to TCMI_STRAND_LDS columns, 15 KiB.
+//   per record   kept_span for [p, q], the primer table's head_end / tail_start when the set has one, then a binary search for the
+//                first queried column >= p.  A record without a queried column in [p, q] — nearly every record of a sparse query —
+//                is done here.
 //   the walk     the others visit their queried columns in ascending order with ONE incremental walk of the CIGAR (the op index, the
 //                op's first column and query index are kept between columns).  Per column the token rule of tally_stream_kernel
 //                (tally.hip), restated for one column: a matched base counts coverage and its letter; a D column coverage and X,
@@ -20,17 +23,14 @@
 //                the popcount — to the workgroup's counters in LDS while the columns are staged, else to memory.  At its end a
 //                workgroup hands every non-zero LDS counter to memory with one atomic add.
 // The sums are integers: their order does not matter and every run gives the same numbers.  The stream is only read.
-#include <algorithm>
-#include <cstring>
 #include <vector>
 
-#include "pack_device.h"
+#include "stream_count.h"
 
 namespace {
 
-constexpr int BLOCK = 256;
+constexpr int BLOCK = SC_BLOCK;
 constexpr int LDS_N = TCMI_STRAND_LDS;
-constexpr int WG_PER_CU = 8;
 constexpr int NK = 14;                  // counters per column: fwd[7] | rev[7] in plane order
 constexpr int64_t MAX_N = 1 << 20;
 constexpr int64_t MAX_COL = 1 << 29;
@@ -43,18 +43,6 @@ struct ScArgs {
     int32_t n;
 };
 
-// (the twin of tally.hip's stream_seg_find)
-__device__ inline int32_t seg_value(const int32_t *t, int32_t n, int32_t x, int32_t none)
-{
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (t[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo > 0 && x < t[n + lo - 1] ? t[2 * n + lo - 1] : none;
-}
-
 // a kept record between its queried columns
 struct Walk {
     ReadView v;
@@ -64,28 +52,18 @@ struct Walk {
     int32_t keep0, keep1;               // tokens on columns outside [keep0, keep1) are masked
 };
 
-// record i: kept exactly when the device packer keeps it (amplicon_reads.hip: slot_of) -> its walk at the head of the CIGAR
+// record i, when it is kept -> its walk at the head of the CIGAR
 __device__ inline bool open_walk(const ScArgs &a, int64_t i, Walk &w)
 {
-    w.v = view_rec(a.src.stream + a.src.rec_off[i]);
-    const ReadView &v = w.v;
-    if ((v.flag & 0x4u) || !passes(a.src.flt, v) || v.bad || v.pos < 0) return false;
-    const int32_t shift = shift_of(a.src, v.tid);
-    if (shift < 0) return false;
-    int64_t span = 0;
-    for (uint32_t k = 0; k < v.n_cigar; ++k) {
-        const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k);
-        if (consumes_ref(c & 0xFu)) span += c >> 4;
-    }
-    if (span <= 0) return false;
-    const int64_t p = (int64_t)v.pos + shift, q = p + span - 1;
+    int64_t p, q;
+    if (!kept_span(a.src, i, w.v, p, q)) return false;
     if (p >= MAX_COL) return false;                         // (beyond every column that can be asked for)
     w.x = (int32_t)p; w.y = 0; w.k = 0;
     w.q = (int32_t)(q < MAX_COL ? q : MAX_COL);
     w.keep0 = INT32_MIN; w.keep1 = INT32_MAX;
     if (a.pt.n_head + a.pt.n_tail != 0) {
-        w.keep0 = seg_value(a.pt.seg, a.pt.n_head, w.x, w.x);
-        w.keep1 = seg_value(a.pt.seg + 3 * a.pt.n_head, a.pt.n_tail, w.q, w.q + 1);
+        w.keep0 = seg_find(a.pt.seg, a.pt.n_head, w.x, w.x);
+        w.keep1 = seg_find(a.pt.seg + 3 * a.pt.n_head, a.pt.n_tail, w.q, w.q + 1);
     }
     return true;
 }
@@ -109,14 +87,13 @@ __device__ inline uint32_t token_at(Walk &w, int32_t c, uint32_t Q)
     }
     if (c < w.keep0 || c >= w.keep1) return 0u;             // masked: nothing, the I mark included
     const int32_t j = c - w.x;
-    const uint8_t *qual = v.seq + ((size_t)v.l_seq + 1) / 2;
     const int32_t qi = is_match(op) ? w.y + j : w.y;       // a D / N token is tested with the query index at which its op starts
-    if (Q != 0u && (qi < v.l_seq ? byte_at(qual + qi) : 0u) < Q) return 0u;      // below the floor (Q = 0: nothing is, and QUAL is not read)
+    if (Q != 0u && qual_at(v, qi) < Q) return 0u;          // below the floor (Q = 0: nothing is, and QUAL is not read)
     const bool ins = j == len - 1 && ins_after(v.cigar, v.n_cigar, w.k);
     uint32_t bits = 1u << TCMI_COV;                         // M, =, X, D and N all count coverage
     if (is_match(op)) {
         const uint32_t nib = qi < v.l_seq ? nib_at(v.seq, qi) : 15u;           // past SEQ -> 'N'
-        if (__popc(nib) == 1) { const int b = __ffs(nib) - 1; bits |= 1u << (b == 0 ? TCMI_A : b == 1 ? TCMI_C : b == 2 ? TCMI_G : TCMI_T); }
+        if (__popc(nib) == 1) bits |= 1u << base_plane(nib);
     } else if (op == 2 && !ins) bits |= 1u << TCMI_X;       // "*+.." does not count X
     if (ins) bits |= 1u << TCMI_I;
     return bits;
@@ -193,55 +170,6 @@ __global__ __launch_bounds__(BLOCK) void strand_counts_kernel(ScArgs a)
     }
 }
 
-// one read set on its own context: the columns (host, int32) -> sums[14 * n] ADDED to
-int count_one(tcmi_ctx *ctx, const tcmi_readset *rs, int32_t n, const int32_t *cols, int64_t *sums)
-{
-    if (rs->packed_on_device != 2)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "strand counts: the read set was not decoded on the device (flat arrays or the host reader): there is no record stream to count in");
-    if (rs->n_piled == 0) return TCMI_OK;                   // (no kept record: nothing to add; such a set may hold no stream at all)
-    if (rs->device != ctx->device)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "strand counts: the read set lives on device %d, this context on device %d", rs->device, ctx->device);
-    if (!rs->d_stream || !rs->d_rec_off || rs->arena_epoch != ctx->arena_epoch)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "strand counts: the read set's decoded stream is no longer resident on this context (another upload happened on it)");
-    if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "strand counts: the context's contig layout changed since the read set was uploaded");
-    TCMI_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t b_col = tcmi_align256((size_t)n * 4), b_cnt = tcmi_align256((size_t)NK * n * 4);
-    // scratch of the context, grow-only and shared with tcmi_readset_amplicon_reads (both wait for the stream before they return)
-    if (ctx->ar_dev_cap < b_col + b_cnt) {
-        if (ctx->ar_dev) { TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->ar_dev); ctx->ar_dev = nullptr; ctx->ar_dev_cap = 0; }
-        const size_t want = b_col + b_cnt + (64u << 10);
-        if (hipMalloc((void **)&ctx->ar_dev, want) != hipSuccess) return tcmi_fail(ctx, TCMI_E_NOMEM, "strand counts: device scratch (%zu bytes)", want);
-        ctx->ar_dev_cap = want;
-    }
-    char *pin = static_cast<char *>(tcmi_ctx_pinned(ctx, b_col + b_cnt));
-    if (!pin) return tcmi_fail(ctx, TCMI_E_NOMEM, "strand counts: pinned scratch");
-    std::memcpy(pin, cols, (size_t)n * 4);
-    ScArgs a;
-    a.src = stream_src(rs);
-    a.src.lay = rs->d_lay; a.src.n_lay = rs->n_lay;
-    a.pt = tcmi_primer_args(rs->primers);
-    a.cols = reinterpret_cast<const int32_t *>(ctx->ar_dev);
-    a.counts = reinterpret_cast<int32_t *>(ctx->ar_dev + b_col);
-    a.n = n;
-    TCMI_HIP(ctx, hipMemcpyAsync(ctx->ar_dev, pin, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    TCMI_HIP(ctx, hipMemsetAsync(a.counts, 0, (size_t)NK * n * 4, ctx->stream));
-    if (rs->n_reads > 0) {
-        const int64_t blocks = (rs->n_reads + BLOCK - 1) / BLOCK;
-        const int64_t grid = std::min<int64_t>(blocks, (int64_t)std::max(ctx->n_cu, 1) * WG_PER_CU);
-        (void)hipGetLastError();                            // drop any stale error of this thread
-        tcmi_prof_begin(ctx, TCMI_K_STRAND_COUNTS);
-        hipLaunchKernelGGL(strand_counts_kernel, dim3((unsigned)grid), dim3(BLOCK), 0, ctx->stream, a);
-        tcmi_prof_end(ctx, TCMI_K_STRAND_COUNTS);
-        TCMI_HIP(ctx, hipGetLastError());
-    }
-    TCMI_HIP(ctx, hipMemcpyAsync(pin + b_col, a.counts, (size_t)NK * n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const int32_t *got = reinterpret_cast<const int32_t *>(pin + b_col);
-    for (int64_t k = 0; k < (int64_t)NK * n; ++k) sums[k] += got[k];
-    return TCMI_OK;
-}
-
 } // namespace
 
 extern "C" int tcmi_readset_strand_counts(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *cols, tcmi_strand_counts *records)
@@ -264,17 +192,20 @@ extern "C" int tcmi_readset_strand_counts(tcmi_ctx *ctx, const tcmi_readset *rs,
     } catch (...) {                                         // (no exception may cross the C ABI)
         return tcmi_fail(ctx, TCMI_E_NOMEM, "strand counts: no host memory for %lld columns", (long long)n);
     }
-    if (!rs->parts.empty()) {
-        // a read set of sub-ranges (tcmi_split_step, "split_sub"): every record starts in exactly one part — the sum over the parts,
-        // each counted on its own context, where its stream lives
-        for (const tcmi_readset::Part &pt : rs->parts) {
-            const int rc = count_one(pt.cx, pt.rs, (int32_t)n, c32.data(), sums.data());
-            if (rc) return tcmi_fail(ctx, rc, "%s", pt.cx->err.c_str());
-        }
-    } else {
-        const int rc = count_one(ctx, rs, (int32_t)n, c32.data(), sums.data());
-        if (rc) return rc;
-    }
+    // the columns (int32) in, [n][14] int32 counters out; the primer table is the one each part was built under
+    const int rc = tcmi_stream_count_parts(
+        ctx, rs, "strand counts", c32.data(), c32.size() * 4, sums.size() * 4,
+        [n](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, char *d_cnt, unsigned grid) {
+            const ScArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), reinterpret_cast<int32_t *>(d_cnt), (int32_t)n};
+            tcmi_prof_begin(cx, TCMI_K_STRAND_COUNTS);
+            hipLaunchKernelGGL(strand_counts_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
+            tcmi_prof_end(cx, TCMI_K_STRAND_COUNTS);
+        },
+        [s = sums.data(), m = sums.size()](const char *counts) {
+            const int32_t *got = reinterpret_cast<const int32_t *>(counts);
+            for (size_t k = 0; k < m; ++k) s[k] += got[k];
+        });
+    if (rc) return rc;
     for (int64_t i = 0; i < n; ++i) {
         for (int k = 0; k < TCMI_NCOL; ++k) {
             records[i].fwd[k] = (int32_t)sums[(size_t)(NK * i + k)];

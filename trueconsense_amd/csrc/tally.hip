@@ -19,7 +19,7 @@
 // to global atomics: always correct, only slower.
 //
 // Integer work, HBM-streaming: no MFMA anywhere (BASELINE.json north_star).
-#include "pack_device.h"
+#include "stream_count.h"
 
 namespace {
 
@@ -217,16 +217,6 @@ __global__ __launch_bounds__(BLOCK) void tally_atomic_kernel(TallyArgs a)
 // first, for the last column — and a token on a column outside [head_end, tail_start) is skipped likewise, column by column: a D / N
 // op that crosses the mask's edge loses only its masked columns, the I mark goes with the op's last column.  Coverage token by token
 // then too; without a floor a query index at or beyond l_seq is not skipped outside the mask.
-__device__ inline int32_t stream_seg_find(const int32_t *t, int32_t n, int32_t x, int32_t none)      // (the twin of pack_device.hip's seg_find)
-{
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (t[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo > 0 && x < t[n + lo - 1] ? t[2 * n + lo - 1] : none;
-}
 __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint32_t *gen_idx, uint32_t n_gen, int32_t *counts, int64_t ld, int32_t L,
                                                            tcmi_primer_tab pt)
 {
@@ -237,20 +227,16 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
     auto add = [&](int col, int32_t p) { if ((uint32_t)p < (uint32_t)L) atomicAdd(&counts[(int64_t)col * ld + p], 1); };
     const uint32_t Q = s.min_bq;
     const uint8_t *qual = v.seq + ((size_t)v.l_seq + 1) / 2;
-    auto skipped = [&](int32_t q) { return (q < v.l_seq ? byte_at(qual + q) : 0u) < Q; };     // (Q = 0: nothing is)
+    auto skipped = [&](int32_t q) { return qual_at(qual, v.l_seq, q) < Q; };                  // (Q = 0: nothing is)
     int32_t x = v.pos + shift_of(s, v.tid), y = 0;
     const int32_t x0 = x;
     const bool table = pt.n_head + pt.n_tail != 0;
     const bool by_token = Q != 0u || table;                     // coverage token by token
     int32_t keep0 = INT32_MIN, keep1 = INT32_MAX;               // tokens on columns outside [keep0, keep1) are masked
     if (table) {
-        int32_t span = 0;
-        for (uint32_t k = 0; k < v.n_cigar; ++k) {
-            const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k);
-            if (consumes_ref(c & 0xFu)) span += (int32_t)(c >> 4);
-        }
-        keep0 = stream_seg_find(pt.seg, pt.n_head, x0, x0);
-        keep1 = stream_seg_find(pt.seg + 3 * pt.n_head, pt.n_tail, x0 + span - 1, x0 + span);
+        const int32_t span = (int32_t)ref_span(v);
+        keep0 = seg_find(pt.seg, pt.n_head, x0, x0);
+        keep1 = seg_find(pt.seg + 3 * pt.n_head, pt.n_tail, x0 + span - 1, x0 + span);
     }
     auto masked = [&](int32_t col) { return col < keep0 || col >= keep1; };
     for (uint32_t k = 0; k < v.n_cigar; ++k) {
@@ -265,7 +251,7 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
                     const int32_t q = y + j;
                     if (by_token) { if (skipped(q) || masked(x + j)) continue; add(TCMI_COV, x + j); }
                     const uint32_t nib = q < v.l_seq ? nib_at(v.seq, q) : 15u;          // past SEQ -> 'N'
-                    if (__popc(nib) == 1) { const int b = __ffs(nib) - 1; add(b == 0 ? TCMI_A : b == 1 ? TCMI_C : b == 2 ? TCMI_G : TCMI_T, x + j); }
+                    if (__popc(nib) == 1) add(base_plane(nib), x + j);
                 }
             } else if (!skipped(y)) {                                                 // (the floor skips a D / N op whole; Q = 0: never)
                 const int32_t nx = ins ? len - 1 : len;                              // "*+.." does not count X
@@ -289,7 +275,7 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
 static int launch_tally_stream(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L, int64_t ld, int32_t *d_counts)
 {
     if (rs->s_reads <= 0) return TCMI_OK;
-    if (!rs->d_stream || rs->arena_epoch != ctx->arena_epoch || rs->device != ctx->device)
+    if (tcmi_stream_gone(ctx, rs))
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the read set's long reads lie in a decoded stream that is gone (another upload on this context): upload it again");
     PackSrc s = stream_src(rs);
     if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
