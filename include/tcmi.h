@@ -414,6 +414,57 @@ int  tcmi_strand_verdict(int32_t alt_fwd, int32_t alt_rev, int32_t tot_fwd, int3
 int  tcmi_variants_strand_text(const tcmi_variant *records, int64_t n, const tcmi_strand_counts *strand, int64_t n_cols, /* the records' distinct positions, ascending */
                                int32_t min_strand_depth, int64_t num, int64_t den, const char *region, int64_t pos_offset,
                                const uint8_t *ref, int64_t n_ref, char *text, int64_t cap, int64_t *len);
+/* ---- link counts (additive: are two nearby alleles on the same molecules?  the reference has nothing like it) ----------------------
+ * For pairs of nearby queried columns, the number of kept records by the class of their token at the first column AND at the second,
+ * counted by one HIP kernel over the inflated record stream a device-decoded read set left resident on its context.  The count matrix
+ * forgets which read a token came from: every row of the variant table stands alone, and only the records can say whether two minority
+ * alleles are one haplotype (cis), two populations (trans) or a multi-nucleotide change inside a codon.  All arithmetic is integer;
+ * the sums are the same in every run.  RECORDS are counted, not templates: the two mates of a pair are two records, each with its own
+ * columns, as for tcmi_readset_amplicon_reads.
+ *   columns        c_0 < c_1 < ... < c_{n-1} on the count matrix's axis (under a contig layout: shifted by the contig's slot), each in
+ *                  [0, 2^29); k neighbours in 1..7; n >= 1 and n * k <= 2^17.
+ *   records        host, room for n * k.  records[i * k + d - 1] (d in 1..k) is the pair (c_i, c_{i+d}): a = c_i, b = c_{i+d},
+ *                  reserved = 0; b = -1 and j all zero when i + d >= n.
+ *   class          of a kept record at a column: 0 no token (the column lies outside the record's columns [p, q], the token is masked
+ *                  by the primer table or lies below the base-quality floor); 1..4 a matched base counted on plane A, T, C, G; 5 a
+ *                  deleted column that counts X; 6 a token that counts coverage and none of the planes 1..5 (an N or ambiguity
+ *                  nibble, a query index past SEQ, a reference skip, a deletion's last column with an insertion behind it).  The
+ *                  token rule is the count matrix's, as for tcmi_readset_strand_counts, under the read filter, the floor, the primer
+ *                  table and the layout the read set REMEMBERS.  The I mark takes no part.
+ *   j[x][y]        the kept records with class x at a and class y at b.  j[0][0] is always 0.
+ *   invariant      for every pair with b >= 0: sum_y j[x][y] is the count matrix at (plane x, a) for x in 1..5 and cov minus the planes
+ *                  1..5 at a for x = 6; the column sums sum_x j[x][y] are the same at b.
+ *   tcmi_readset_link_counts   residency, sub-ranges, an empty read set, the wait and the scratch as for tcmi_readset_strand_counts.
+ *   tcmi_link_phase   HOST, GPU-free, exact integers.  0 CIS, 1 TRANS, 2 MIXED, 3 NONE, 4 LOW.  LOW iff span < min_depth.  Else with
+ *                  m = min(both + only_a, both + only_b): NONE iff m = 0; CIS iff both * den >= num * m; TRANS iff
+ *                  both * den <= (den - num) * m; else MIXED.  num / den lies in (1/2, 1], so CIS and TRANS exclude each other.  The
+ *                  counts stay below 2^31 and den at or below 10^6: the products fit 64 bits.  TCMI_E_ARG for a negative count and
+ *                  the range errors below.
+ *   tcmi_variants_links_text   HOST, re-entrant, no GPU: the writer of --variant-links' rows, one per pair of variant records (r1, r2)
+ *                  where r2's position is among the next k distinct positions behind r1's and both alleles are in planes A..X ('+'
+ *                  records are not linked: the I mark says that an insertion follows, not which).  All records of one call are one
+ *                  region.  links[0 .. n_cols * k): the link counts at the records' distinct positions, ascending.  Row:
+ *                  REGION POS_A REF_A ALT_A POS_B REF_B ALT_B SPAN BOTH ONLY_A ONLY_B NEITHER PHASE, alleles spelled as
+ *                  tcmi_variants_text spells them; with A, B the two alleles' planes SPAN = sum_{x,y >= 1} j[x][y] (the records with a
+ *                  token at both columns), BOTH = j[A][B], ONLY_A = sum_{y >= 1, y != B} j[A][y], ONLY_B = sum_{x >= 1, x != A}
+ *                  j[x][B], NEITHER = SPAN - BOTH - ONLY_A - ONLY_B, PHASE = tcmi_link_phase's word.  TCMI_E_ARG, and no text, when
+ *                  links[jx * k + d - 1].a is not the jx-th distinct position or .b not the (jx + d)-th (behind the last one: -1 or
+ *                  any column beyond it, the next region's), when n_cols is not the number of distinct positions, and when the
+ *                  invariant fails against a record's count or cov in any pair with b >= 0 its position takes part in: the two
+ *                  kernels disagree, no table is written.  Sizing call, short buffer and *len as for tcmi_variants_text.  The header
+ *                  line (TCMI_VARIANTS_LINKS_HEADER) is the caller's.
+ * TCMI_LINKS_LDS: the pairs (n * k) whose counters, with the columns, a workgroup stages in LDS (80 x 49 counters + 80 columns = 16 000
+ * bytes: ten workgroups per compute unit by LDS, eight by the launch shape); more pairs are counted with atomics in memory; for tests.
+ * Range errors are TCMI_E_ARG: min_depth < 1, den outside 1..10^6, num > den or 2 * num <= den. */
+typedef struct tcmi_link_counts { int32_t j[7][7]; int32_t a, b /* -1: no such pair */, reserved /* 0 */; } tcmi_link_counts;   /* 208 bytes */
+#define TCMI_LINKS_LDS 80
+#define TCMI_VARIANTS_LINKS_HEADER "REGION\tPOS_A\tREF_A\tALT_A\tPOS_B\tREF_B\tALT_B\tSPAN\tBOTH\tONLY_A\tONLY_B\tNEITHER\tPHASE\n"
+int  tcmi_readset_link_counts(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *cols /* host */, int32_t k,
+                              tcmi_link_counts *records /* host, n * k */);
+int  tcmi_link_phase(int32_t both, int32_t only_a, int32_t only_b, int32_t span, int32_t min_depth, int64_t num, int64_t den);
+int  tcmi_variants_links_text(const tcmi_variant *records, int64_t n, const tcmi_link_counts *links, int64_t n_cols, /* the records' distinct positions, ascending */
+                              int32_t k, int32_t min_depth, int64_t num, int64_t den, const char *region, int64_t pos_offset,
+                              const uint8_t *ref, int64_t n_ref, char *text, int64_t cap, int64_t *len);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -434,7 +485,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_INTERVALS = 11 /* the amplicon table's one launch */,
        TCMI_K_AMPLICON_READS = 12 /* tcmi_readset_amplicon_reads' one launch */,
        TCMI_K_STRAND_COUNTS = 13 /* tcmi_readset_strand_counts' one launch */,
-       TCMI_K_NKERNELS = 14 };
+       TCMI_K_LINK_COUNTS = 14 /* tcmi_readset_link_counts' one launch */,
+       TCMI_K_NKERNELS = 15 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);

@@ -1,0 +1,576 @@
+"""--variant-links on the GPU (csrc/link_counts.hip; tcmi_readset_link_counts, Context.link_counts): every comparison is exact equality.
+The yardstick is tests/links_yardstick — the class of a record at a column read off tests/primer_yardstick.counts of that record alone,
+the joint counts accumulated in Python —, the invariant is that the classes at either column of every pair add up to the matrix the
+step tallied from the same read set.  The inputs are those of tests/test_floor_mask_fuzz.py (tests/fuzz_masked.specs: every CIGAR op,
+SEQ '*', short SEQ, no QUAL, long reads, planted insertion sites) and hand-made records.  The host record buffer lies between guard
+words that are checked after every call.  The rule, the writer and the argument handling are checked without a GPU in
+tests/test_links_rule.py."""
+import ctypes as C
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+
+from tests import links_yardstick as ly
+from tests import primer_yardstick as py
+from tests import test_base_quality as bq
+from tests import test_floor_mask_fuzz as ff
+from tests import test_matrix_abi as ma
+from tests import test_read_filter as rf
+from tests import test_strand_counts as sc
+from tests import variant_yardstick as vy
+from trueconsense_amd import TrueConsense as cli
+from trueconsense_amd import _ffi, contigs, engine
+from trueconsense_amd import distributed as td
+from trueconsense_amd import synthetic as syn
+from trueconsense_amd.io import bamwriter
+from trueconsense_amd.io import primers as pbed
+
+pytestmark = pytest.mark.gpu
+L = ff.L
+LDS = engine.LINKS_LDS
+G = 64                                                                          # guard words on either side of the records
+W = 52                                                                          # int32 words of a record
+KS = (1, 2, 7)
+uploaded = sc.uploaded
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    with engine.Context(0) as c:
+        yield c
+
+
+def device_links(ctx, rs, cols, k):
+    """tcmi_readset_link_counts into a host buffer between guards -> the records (LINK_DTYPE); a, b and reserved are checked here, and
+    Context.link_counts must give the same bytes (run after run)"""
+    cols = np.ascontiguousarray(cols, np.int64)
+    n = len(cols)
+    buf = ma.sentinel(2 * G + W * n * k, np.int32, salt=11).copy()
+    before = buf.copy()
+    rc = _ffi.lib().tcmi_readset_link_counts(ctx.handle, rs.handle, n, _ffi.ptr(cols), k, C.c_void_p(buf.ctypes.data + 4 * G))
+    _ffi.check(rc, ctx.handle)
+    assert np.array_equal(buf[:G], before[:G]) and np.array_equal(buf[-G:], before[-G:]), "a guard around the records was written"
+    got = buf[G:-G].view(engine.LINK_DTYPE).copy()
+    want = ly.records(cols.tolist(), k, np.zeros((n * k, 7, 7), np.int32))
+    assert np.array_equal(got["a"], want["a"]) and np.array_equal(got["b"], want["b"]) and not got["reserved"].any()
+    assert not got["j"][got["b"] < 0].any() and not got["j"][:, 0, 0].any()
+    again = ctx.link_counts(rs, cols, k)
+    assert again.tobytes() == got.tobytes()
+    return got
+
+
+def differ(got, want_j, label):
+    """'' when the records' counts equal the yardstick's; else the first differing pairs with both matrices"""
+    if np.array_equal(got["j"], want_j):
+        return ""
+    rows = []
+    for p in np.unique(np.argwhere(got["j"] != want_j)[:, 0])[:4].tolist():
+        rows.append("pair (%d, %d): got\n%r\nwant\n%r" % (got["a"][p], got["b"][p], got["j"][p], want_j[p]))
+    return "%r (classes none, A, T, C, G, X, coverage only)\n%s" % (label, "\n".join(rows))
+
+
+@functools.lru_cache(maxsize=None)
+def classes_of(seed, mode, window=None):
+    """-> (class matrix [passing records, n_pos], n_pos, the yardstick's count matrix) of a fuzz seed under a mode"""
+    tabled, slack, q, f = ff.MODES[mode]
+    _, rd = ff.passing(seed, None, window, f)
+    whole = ff.yardstick(seed, None, window, f, tabled, q, slack)[0]
+    return ly.classes(rd, L, ff.table_of(seed) if tabled else (), q, slack, n_pos=len(whole)), len(whole), whole
+
+
+def sparse_columns(seed, n_pos, n=24, edges=8):
+    """24 random columns and columns on both sides of mask edges of the seed's table: at most 40, staged with one and two neighbours"""
+    rng = np.random.default_rng(700 + seed)
+    cols = set(int(c) for c in rng.choice(n_pos, n, replace=False))
+    for s, e, rev in ff.table_of(seed)[:edges]:
+        edge = s if rev else e
+        cols.update(c for c in (edge - 1, edge) if 0 <= c < n_pos)
+    assert len(cols) * 2 <= LDS
+    return sorted(cols)
+
+
+def window_columns(whole, width=300):
+    """every column of the 300-column window with the most coverage"""
+    cov = np.convolve(whole[:, 0].astype(np.int64), np.ones(width, np.int64), "valid")
+    s = int(np.argmax(cov))
+    return list(range(s, s + width))
+
+
+def long_read_over(specs, cols, at_least=3):
+    """does a long read (one the tally leaves to its per-token kernel) lie over several of the queried columns?"""
+    return any(ff._piles_up(r) and ff._span(r) > ff.LONG and sum(r["pos"] <= c < r["pos"] + ff._span(r) for c in cols) >= at_least for r in specs)
+
+
+def not_vacuous(j, label):
+    """on the yardstick, before the device runs: a pair with an off-diagonal count among the classes 1..6, records that reach only the
+    first column of a pair and records that reach only the second"""
+    off = j[:, 1:, 1:].sum(0)
+    assert (off - np.diag(np.diag(off))).any(), label
+    assert j[:, 1:, 0].any() and j[:, 0, 1:].any(), label
+
+
+# ---- 1. both packers, three modes, three neighbour counts, both routes ----------------------------------------------------------------
+@pytest.mark.parametrize("one_sync", (1, 0))
+@pytest.mark.parametrize("mode", sorted(ff.MODES))
+@pytest.mark.parametrize("seed", ff.SEEDS)
+def test_fuzz_equals_the_yardstick_and_adds_up_to_the_matrix(ctx, tmp_path, seed, mode, one_sync):
+    tabled, slack, q, f = ff.MODES[mode]
+    specs, _ = ff.passing(seed, None, None, f)
+    cls, n_pos, whole = classes_of(seed, mode)
+    sparse, dense = sparse_columns(seed, n_pos), window_columns(whole)
+    cases = [(cols, k, ly.joint(cls, cols, k)) for cols in (sparse, dense) for k in KS]
+    for cols, k, want in cases:
+        not_vacuous(want, (seed, mode, len(cols), k))
+    assert long_read_over(specs, dense) and long_read_over(specs, sparse, 2), (seed, mode)
+    routes = {len(cols) * k <= LDS for cols, k, _ in cases}
+    assert routes == {True, False}
+    path = ff.write(tmp_path, ff.fuzz(seed))
+    with uploaded(ctx, path, ff.table_of(seed) if tabled else (), q, f, slack, one_sync) as rs:
+        matrix = ctx.step(rs, n_pos, 0, True)[3]
+        assert np.array_equal(matrix, whole)
+        for cols, k, want in cases:
+            got = device_links(ctx, rs, cols, k)
+            msg = differ(got, want, (seed, mode, one_sync, len(cols), k))
+            assert not msg, msg
+            assert not ly.invariant(got, k, matrix), (seed, mode, one_sync, len(cols), k, ly.invariant(got, k, matrix))
+
+
+# ---- 2. sizes around the staging capacity ----------------------------------------------------------------------------------------------
+def test_one_column_two_columns_and_the_staging_edge(ctx, tmp_path):
+    seed = ff.SEEDS[1]
+    cls, n_pos, whole = classes_of(seed, "floor")
+    dense = window_columns(whole, LDS + 1)                                       # 81 neighbouring columns: every pair is covered
+    spread = sorted(int(c) for c in np.random.default_rng(9).choice(n_pos, LDS // 2 + 1, replace=False))
+    path = ff.write(tmp_path, ff.fuzz(seed))
+    with uploaded(ctx, path, (), 13) as rs:
+        matrix = ctx.step(rs, n_pos, 0, True)[3]
+        for k in KS:                                                            # n = 1: nothing but b = -1 records, all zero
+            got = device_links(ctx, rs, dense[40:41], k)
+            assert len(got) == k and (got["b"] == -1).all() and not got["j"].any()
+            got = device_links(ctx, rs, dense[40:42], k)                        # n = 2: one pair
+            want = ly.joint(cls, dense[40:42], k)
+            assert not differ(got, want, ("n = 2", k)) and want[0, 1:, 1:].any() and (got["b"] == -1).sum() == 2 * k - 1
+            assert not ly.invariant(got, k, matrix)
+        for cols, k in ((dense, 1), (spread, 2)):                               # n * k = 80 staged, 81 / 82 in memory: the same leading pairs
+            n_at = LDS // k
+            assert n_at * k == LDS and len(cols) == n_at + 1
+            staged, memory = device_links(ctx, rs, cols[:n_at], k), device_links(ctx, rs, cols, k)
+            want = ly.joint(cls, cols, k)
+            not_vacuous(want, ("edge", k))
+            assert not differ(memory, want, ("memory", k)) and not differ(staged, ly.joint(cls, cols[:n_at], k), ("staged", k))
+            same = [p for p in range(n_at * k) if staged["b"][p] >= 0]
+            assert len(same) == n_at * k - k * (k + 1) // 2 and np.array_equal(staged["j"][same], memory["j"][same])
+            assert not ly.invariant(staged, k, matrix) and not ly.invariant(memory, k, matrix)
+
+
+# ---- 3. small and ragged ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_rec", (1, 63, 65, 257))
+def test_small_files(ctx, tmp_path, n_rec):
+    """1, 63, 65 and 257 records (fewer than a wavefront, one more, one more than a workgroup); a column beyond every read; the same
+    records under a filter that all of them fail: zeros, and TCMI_OK"""
+    every = [r for r in ff.fuzz(ff.SEEDS[2]) if ff._piles_up(r)]
+    step = len(every) // n_rec
+    specs = every[::step][:n_rec] if n_rec > 1 else [next(r for r in every if ff._span(r) > 20)]
+    assert len(specs) == n_rec
+    rd = rf.arrays(specs)
+    whole = py.counts(rd, L, (), 13)[0]
+    n_pos = len(whole)
+    cls = ly.classes(rd, L, (), 13, n_pos=n_pos)
+    beyond = n_pos + 700
+    if n_rec == 1:
+        p = specs[0]["pos"]
+        sparse = [p + 2, p + 9, p + 15, beyond]
+    else:
+        sparse = sorted(set(int(c) for c in np.random.default_rng(n_rec).choice(n_pos, 30, replace=False)) | {int(np.argmax(whole[:, 0]))}) + [beyond]
+    dense = window_columns(whole, 120) + [beyond]
+    path = ff.write(tmp_path, specs)
+    with uploaded(ctx, path, (), 13) as rs:
+        assert rs.n_reads == n_rec
+        matrix = ctx.step(rs, n_pos, 0, True)[3]
+        for cols in (sparse, dense):
+            for k in (2, 7):
+                want = ly.joint(cls, cols, k)
+                assert want.any()
+                got = device_links(ctx, rs, cols, k)
+                msg = differ(got, want, (n_rec, len(cols), k))
+                assert not msg, msg
+                assert not ly.invariant(got, k, matrix)
+    with uploaded(ctx, path, (), 13, (0, 0x1000, 0)) as rs:                     # a FLAG bit no record has is required: every record fails
+        assert rs.n_reads == n_rec and rs.n_piled == 0 and rs.filtered == n_rec
+        assert not device_links(ctx, rs, sparse, 2)["j"].any()
+
+
+# ---- 4. depth --------------------------------------------------------------------------------------------------------------------------
+def test_many_lanes_on_one_counter(ctx, tmp_path):
+    """every random read starts inside a window of 50 columns: more than 255 records on one counter of one pair, the sums stay exact"""
+    seed, window = ff.DEEP_SEED, ff.DEEP_WINDOW
+    tabled, slack, q, f = ff.MODES["table"]                                      # (no filter, no floor: the most records)
+    cls, n_pos, whole = classes_of(seed, "table", window)
+    sparse = list(range(window[0] - 10, window[1] + 50, 5))[:LDS // 2]
+    dense = window_columns(whole, 150)
+    path = ff.write(tmp_path, ff.fuzz(seed, None, window))
+    with uploaded(ctx, path, ff.table_of(seed), q, f, slack) as rs:
+        matrix = ctx.step(rs, n_pos, 0, True)[3]
+        for cols, k in ((sparse, 2), (sparse, 7), (dense, 1), (dense, 7)):
+            want = ly.joint(cls, cols, k)
+            assert want.max() >= 256 and want.sum((1, 2)).max() >= 256
+            not_vacuous(want, ("deep", len(cols), k))
+            got = device_links(ctx, rs, cols, k)
+            msg = differ(got, want, ("deep", len(cols), k))
+            assert not msg, msg
+            assert not ly.invariant(got, k, matrix)
+
+
+# ---- 5. hand-made records --------------------------------------------------------------------------------------------------------------
+HL = 400
+A_COL, B_COL = 100, 130
+
+
+def hand_specs():
+    """records over the columns 100 and 130 of a 400-column reference, all bases A unless said: which columns they reach and what
+    token they carry there"""
+    def rec(name, pos, cigar, seq=None, qual=30, flag=0):
+        qlen = sum(n for op, n in ff._ops({"cigar": cigar}) if op in (0, 1, 4, 7, 8))
+        return {"pos": pos, "flag": flag, "cigar": cigar, "seq": "A" * qlen if seq is None else seq, "name": name, "tid": 0, "qual": qual, "mapq": 60}
+    at = lambda pos, col, base, n: "A" * (col - pos) + base + "A" * (n - (col - pos) - 1)
+    low = lambda pos, col, n: [30] * (col - pos) + [5] + [30] * (n - (col - pos) - 1)
+    out = [rec("both", 90, "60M"),                                              # A at both
+           rec("first_only", 60, "50M", at(60, A_COL, "C", 50)),                # C at 100, ends at 109
+           rec("second_only", 120, "50M", at(120, B_COL, "G", 50)),             # starts behind 100, G at 130
+           rec("neither", 200, "50M"),
+           rec("del_first", 80, "15M10D40M"),                                   # columns 95..104 deleted: X at 100, A at 130
+           rec("skip_second", 90, "30M20N30M"),                                 # columns 120..139 skipped: A at 100, coverage only at 130
+           rec("n_base", 90, "60M", at(90, B_COL, "N", 60)),                    # N at 130: coverage only
+           rec("del_then_ins", 80, "15M6D3I40M"),                               # columns 95..100 deleted, an insertion behind column 100: coverage only there
+           rec("del_inside_ins", 80, "15M8D3I40M"),                             # columns 95..102 deleted: column 100 is not the last, X
+           rec("low_second", 90, "60M", qual=low(90, B_COL, 60)),               # below the floor at 130: nothing there, A at 100
+           rec("low_first", 90, "60M", at(90, A_COL, "T", 60), qual=low(90, A_COL, 60)),       # below the floor at 100: nothing there
+           rec("masked_first", 96, "60M", at(96, A_COL, "G", 60), flag=0),      # starts inside the '+' primer [96, 104): masked up to 103
+           rec("masked_second", 75, "60M", flag=16),                            # ends at 134 inside the '-' primer [128, 136): masked from 128 on
+           rec("short_seq", 90, "60M", "A" * 20)]                               # SEQ ends at column 109: past SEQ at 130, quality 0, below the floor
+    return sorted(out, key=lambda r: r["pos"])
+
+
+HAND_TABLE = ((96, 104, False), (128, 136, True))
+
+
+def test_hand_made_records(ctx, tmp_path):
+    specs = hand_specs()
+    rd = rf.arrays(specs)
+    whole = py.counts(rd, HL, HAND_TABLE, 13)[0]
+    cls = ly.classes(rd, HL, HAND_TABLE, 13, n_pos=len(whole))
+    at = {r["name"]: (int(cls[i, A_COL]), int(cls[i, B_COL])) for i, r in enumerate(specs)}
+    # the yardstick sees what the records were made for
+    assert at == {"both": (1, 1), "first_only": (3, 0), "second_only": (0, 4), "neither": (0, 0), "del_first": (5, 1), "skip_second": (1, 6), "n_base": (1, 6),
+                  "del_then_ins": (6, 1), "del_inside_ins": (5, 1), "low_second": (1, 0), "low_first": (0, 1), "masked_first": (0, 1), "masked_second": (1, 0),
+                  "short_seq": (1, 0)}, at
+    want = np.zeros((7, 7), np.int32)
+    for x, y in at.values():
+        if x or y:
+            want[x][y] += 1
+    path = str(tmp_path / "H.bam")
+    bamwriter.write_bam(path, rd, ref_len=HL, block=4096)
+    with uploaded(ctx, path, HAND_TABLE, 13) as rs:
+        matrix = ctx.step(rs, len(whole), 0, True)[3]
+        assert np.array_equal(matrix, whole)
+        for k in KS:
+            got = device_links(ctx, rs, [A_COL, B_COL], k)
+            assert np.array_equal(got["j"][0], want), (k, got["j"][0], want)
+            assert not ly.invariant(got, k, matrix)
+        cols = [94, 95, A_COL, 101, 102, 104, 109, 119, 120, 127, 128, B_COL, 134, 139, 140, 149]
+        for k in (2, 7):
+            got = device_links(ctx, rs, cols, k)
+            msg = differ(got, ly.joint(cls, cols, k), ("hand", k))
+            assert not msg, msg
+            assert not ly.invariant(got, k, matrix)
+
+
+# ---- 6. a contig layout ----------------------------------------------------------------------------------------------------------------
+def test_two_contigs_under_a_layout(ctx, tmp_path):
+    """columns in both slots and one in the guard between them; each contig under its own table, floor 13 and the read filter: a pair
+    across the contigs holds nothing but [x][0] and [0][y]"""
+    parts, specs = ff.contig_case()
+    refs = [(name, ln) for name, ln, _ in ff.CONTIGS]
+    names = [n for n, _ in refs]
+    path = str(tmp_path / "A.bam")
+    bamwriter.write_bam(path, rf.arrays(specs), refs=refs, block=4096)
+    recs = [(name, syn.make_reference(seed=3, L=ln, cds=[])[0]) for name, ln in refs]
+    shift, slot, axis = contigs.layout_for(recs, names, [ln for _, ln in refs])
+    rows = pbed.rows_for_layout([(name, s, e, rev) for name, _, table, _ in parts for s, e, rev in table], names, shift)
+    guard = int(shift[1]) - 1
+    assert guard >= int(shift[0]) + refs[0][1]
+    blocks = []
+    for t, (name, ln, table, part) in enumerate(parts):                         # every contig's classes, placed at its slot on the axis
+        kept = [dict(r, tid=0) for r in rf.kept(part, ff.F)[0]]
+        own = ly.classes(rf.arrays(kept), ln, table, 13, n_pos=ln)
+        on_axis = np.zeros((len(own), axis), np.uint8)
+        on_axis[:, int(shift[t]):int(shift[t]) + ln] = own
+        blocks.append(on_axis)
+    cls = np.concatenate(blocks)
+    end0 = int(shift[0]) + refs[0][1]
+    dense = list(range(end0 - 120, end0)) + [guard] + list(range(int(shift[1]), int(shift[1]) + 120))
+    sparse = dense[100:120:2] + [guard] + dense[121:141:2]
+    try:
+        ctx.set_layout(shift, slot)
+        with uploaded(ctx, path, rows, 13, ff.F) as rs:
+            matrix = ctx.step(rs, axis, 0, True)[3]
+            for cols, k in ((dense, 2), (dense, 7), (sparse, 2), (sparse, 7)):
+                want = ly.joint(cls, cols, k)
+                not_vacuous(want, ("layout", len(cols), k))
+                got = device_links(ctx, rs, cols, k)
+                msg = differ(got, want, ("layout", len(cols), k))
+                assert not msg, msg
+                assert not ly.invariant(got, k, matrix)
+                across = (got["a"] < end0) & (got["b"] >= int(shift[1]))
+                assert across.sum() == k * (k - 1) // 2 and got["j"][across].any()      # (the guard column lies between the two) and not got["j"][across][:, 1:, 1:].any()
+                assert len(cols) * k > LDS or cols is sparse
+            ctx.set_layout()                                                    # cleared: the read set still answers
+            assert not differ(device_links(ctx, rs, dense, 2), ly.joint(cls, dense, 2), "layout cleared")
+            ctx.set_layout(shift, slot)                                         # set once more: another generation
+            with pytest.raises(_ffi.TcmiError) as e:
+                ctx.link_counts(rs, dense, 2)
+            assert e.value.code == _ffi.E_UNSUPPORTED and "layout" in str(e.value)
+    finally:
+        ctx.set_layout()
+
+
+# ---- 7. block ranges -------------------------------------------------------------------------------------------------------------------
+def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
+    """records that straddle 4 096-byte BGZF blocks: three block ranges taken in turn add up to the whole file's counts, and a read set
+    of two sub-ranges (tcmi_split_step, "split_sub") answers with the same"""
+    import torch
+    seed = ff.SEEDS[3]
+    tabled, slack, q, f = ff.MODES["all"]
+    cls, n_pos, whole = classes_of(seed, "all")
+    table = ff.table_of(seed)
+    path = ff.write(tmp_path, ff.fuzz(seed), block=4096, split_records=True)
+    queries = ((sparse_columns(seed, n_pos), 2), (window_columns(whole, 120), 7))
+    for cols, k in queries:
+        want = ly.joint(cls, cols, k)
+        not_vacuous(want, (seed, len(cols), k))
+        with uploaded(ctx, path, table, q, f, slack) as rs:
+            assert not differ(device_links(ctx, rs, cols, k), want, "straddled")
+        d = engine.DeviceBam(path)
+        n_blocks = d.n_blocks
+        d.close()
+        assert n_blocks > 60
+        total, n_reads = np.zeros_like(want), 0
+        for rank in range(3):
+            with uploaded(ctx, path, table, q, f, slack, blocks=td.block_range(n_blocks, rank, 3)) as rs:
+                total += device_links(ctx, rs, cols, k)["j"]
+                n_reads += rs.n_reads
+        assert n_reads == len(ff.fuzz(seed)) and np.array_equal(total, want), "three ranges"
+    # (sub-ranges want at least 64 blocks a piece: the same records four times over in 1 024-byte blocks, four times the counts)
+    big = sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in ff.fuzz(seed)], key=lambda r: r["pos"])
+    path4 = str(tmp_path / "A4.bam")
+    bamwriter.write_bam(path4, rf.arrays(big), ref_len=L, block=1024)
+    c = engine.Context(0, stream=torch.cuda.current_stream().cuda_stream)
+    d = engine.DeviceBam(path4)
+    try:
+        c.set_option("split_sub", 2)
+        c.apply(f, q, (table, slack))
+        ld, n_words = td.split_words(n_pos, 1)
+        t = torch.zeros(n_words, dtype=torch.int32, device="cuda")
+        hook = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)(lambda user, p, n, stream: 0)
+        rc, rs, _ = td._split_step(c, d, 0, 1, n_pos, ld, t, 10, True, hook, None)
+        assert rc == 0 and c.stat("split_sub_taken") == 1
+        for cols, k in queries:
+            assert not differ(device_links(c, rs, cols, k), 4 * ly.joint(cls, cols, k), "sub-ranges")
+        rs.free()
+    finally:
+        d.close()
+        c.close()
+
+
+# ---- 8. refusals -----------------------------------------------------------------------------------------------------------------------
+def test_refusals(ctx, tmp_path):
+    specs = ff.fuzz(ff.SEEDS[0])
+    pa = ff.write(tmp_path, specs[:400])
+    pb_ = str(tmp_path / "B.bam")
+    bamwriter.write_bam(pb_, rf.arrays(specs[400:700]), ref_len=L, block=4096)
+    da, db = engine.DeviceBam(pa), engine.DeviceBam(pb_)
+    try:
+        ra = ctx.upload_bamfile(da)
+        assert ctx.link_counts(ra, [10, 500, 1500], 2)["j"].any()
+        guarded = ma.sentinel(2 * G + W * 4 * 7, np.int32, salt=3).copy()
+        for bad, k, word in (([5, 5], 2, "strictly ascending"), ([7, 5], 2, "strictly ascending"), ([1, 2, 2, 9], 1, "strictly ascending"), ([], 2, "pairs are allowed"),
+                             (np.arange((1 << 17) + 1), 1, "pairs are allowed"), (np.arange((1 << 16) + 1), 2, "pairs are allowed"), ([3, 1 << 29], 2, "2^29"),
+                             ([-1, 4], 2, "2^29"), ([1, 4], 0, "1..7"), ([1, 4], 8, "1..7"), ([1, 4], -1, "1..7")):
+            with pytest.raises(_ffi.TcmiError) as e:
+                ctx.link_counts(ra, bad, k)
+            assert e.value.code == _ffi.E_ARG and word in str(e.value), (bad[:4], k, str(e.value))
+            if 0 < len(bad) <= 4:                                               # ... and nothing is written when the call refuses
+                before = guarded.copy()
+                rc = _ffi.lib().tcmi_readset_link_counts(ctx.handle, ra.handle, len(bad), _ffi.ptr(np.ascontiguousarray(bad, np.int64)), k,
+                                                         C.c_void_p(guarded.ctypes.data + 4 * G))
+                assert rc == _ffi.E_ARG and np.array_equal(guarded, before)
+        assert len(ctx.link_counts(ra, np.arange(1 << 17), 1)) == 1 << 17                                           # the most pairs of one call
+        rb = ctx.upload_bamfile(db)                                             # another upload on the context: ra's stream is displaced
+        with pytest.raises(_ffi.TcmiError) as e:
+            ctx.link_counts(ra, [10, 500], 2)
+        assert e.value.code == _ffi.E_UNSUPPORTED and "no longer resident" in str(e.value) and "link counts" in str(e.value)
+        assert ctx.link_counts(rb, [10, 500, 1500], 2)["j"].any()               # the newer one answers
+        ra.free()
+        rb.free()
+    finally:
+        da.close()
+        db.close()
+    bam = engine.BamFile(pa)
+    flat = ctx.upload(bam)                                                      # flat arrays: packed, but no record stream
+    with pytest.raises(_ffi.TcmiError) as e:
+        ctx.link_counts(flat, [10, 500], 2)
+    assert e.value.code == _ffi.E_UNSUPPORTED and "not decoded on the device" in str(e.value)
+    flat.free()
+    bam.close()
+
+
+def test_the_launch_is_profiled_and_nothing_runs_without_the_call(ctx, tmp_path):
+    path = ff.write(tmp_path, ff.fuzz(ff.SEEDS[0])[:500])
+    try:
+        ctx.profile(True)
+        with uploaded(ctx, path) as rs:
+            ctx.set_variants(b"A" * L)
+            try:
+                ctx.step(rs, L, 10, True)
+            finally:
+                ctx.set_variants()
+            ctx.strand_counts(rs, [100, 900])
+            assert ctx.profile_get(_ffi.K_LINK_COUNTS)[1] == 0
+            ctx.link_counts(rs, [100, 900], 2)
+            ctx.link_counts(rs, np.arange(LDS + 1), 1)
+            ms, n = ctx.profile_get(_ffi.K_LINK_COUNTS)
+            assert n == 2 and ms > 0 and ctx.profile_get(_ffi.K_STRAND_COUNTS)[1] == 1
+    finally:
+        ctx.profile(False)
+
+
+# ---- 9. the command line ---------------------------------------------------------------------------------------------------------------
+CL = 1200
+CIS, TRANS, MIXED, LOW = (300, 330), (600, 640), (800, 830), (1000, 1095)       # the planted pairs' 0-based columns
+
+
+@functools.lru_cache(maxsize=None)
+def cli_case():
+    """-> (reference, GFF rows, records): 100-base reads at about 60x over 1 200 columns.  Of the reads over a planted pair a third
+    carry another base at both columns of CIS; three in ten at the first column of TRANS only and three in ten at its second only; a
+    quarter at both columns of MIXED, a quarter at its first only, a quarter at its second only; four in ten at either column of LOW,
+    which only the reads that start in five columns span"""
+    rng = np.random.default_rng(78)
+    ref, orfs = syn.make_reference(seed=3, L=CL, cds=[(100, 900)])
+    other = {"A": "C", "C": "G", "G": "T", "T": "A"}
+    specs = []
+    for k in range(720):
+        pos = int(rng.integers(0, CL - 100 + 1))
+        seq = list(ref[pos:pos + 100])
+        r = rng.random(4)
+        hits = ((CIS[0], r[0] < 0.33), (CIS[1], r[0] < 0.33), (TRANS[0], r[1] < 0.3), (TRANS[1], 0.3 <= r[1] < 0.6), (MIXED[0], r[2] < 0.5),
+                (MIXED[1], r[2] < 0.25 or 0.5 <= r[2] < 0.75), (LOW[0], r[3] < 0.4), (LOW[1], r[3] < 0.4))
+        for col, hit in hits:
+            if hit and pos <= col < pos + 100:
+                seq[col - pos] = other[ref[col].upper()]
+        specs.append({"pos": pos, "flag": 16 if k % 2 else 0, "cigar": "100M", "seq": "".join(seq), "name": "r%d" % k, "tid": 0, "qual": 30, "mapq": 60})
+    specs.sort(key=lambda r: r["pos"])
+    return ref, orfs, specs
+
+
+def cli_yardstick(specs, ref, k=2):
+    """-> (the records, {(pos_a, pos_b): counts}, the link array) of the yardsticks at the command line's default thresholds"""
+    rd = rf.arrays(specs)
+    whole = py.counts(rd, CL)[0]
+    recs = vy.records(whole, ref.encode(), 3, 100, 1, 10)
+    cols = sorted({p for p, *_ in recs})
+    j = ly.joint(ly.classes(rd, CL, n_pos=len(whole)), cols, k)
+    arr = ly.records(cols, k, j)
+    assert not ly.invariant(arr, k, whole)
+    return recs, {(int(r["a"]), int(r["b"])): r["j"] for r in arr if r["b"] >= 0}, arr
+
+
+def phases_of(text):
+    return {(int(f[1]) - 1, int(f[4]) - 1): f[-1] for f in (ln.split("\t") for ln in text.splitlines())}
+
+
+def test_cli_single_sample_per_contig_and_split(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)
+    ref, orfs, specs = cli_case()
+    recs, links, arr = cli_yardstick(specs, ref)
+    assert sorted({p for p, *_ in recs}) == sorted(CIS + TRANS + MIXED + LOW)
+    want = engine.variants_links_text(vy.as_array(recs), arr, 2, "ref", ref)
+    assert want == ly.text(recs, links, 2, "ref", ref.encode(), 10, 9, 10)
+    seen = phases_of(want)
+    assert (seen[CIS], seen[TRANS], seen[MIXED], seen[LOW]) == ("CIS", "TRANS", "MIXED", "LOW"), seen
+    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=CL, block=4096)
+    common = bq._setup_cli(tmp_path, ref, orfs)
+    out = lambda t: ["-o", t + ".fa", "-vcf", t + ".vcf", "-ogff", t + ".gff", "-doc", t + ".tsv"]
+    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--variant-table", "a.var", "--variant-links", "a.lnk", "--stats", "a.json"])
+    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--variant-table", "b.var", "--stats", "b.json"])
+    assert open("a.lnk").read() == engine.VARIANTS_LINKS_HEADER + want and not os.path.exists("b.lnk")
+    assert open("a.var").read() == open("b.var").read() and rf._outputs("a") == rf._outputs("b")       # every other output byte for byte
+    sa, sb = json.load(open("a.json")), json.load(open("b.json"))
+    stats = cli.link_stats(want)
+    assert {k: sa[k] for k in stats} == stats and stats["variant_link_rows"] == len(want.splitlines()) > 0
+    assert all(stats["variant_links_" + w] > 0 for w in ("cis", "trans", "mixed", "low"))
+    assert {k: sb[k] for k in stats} == cli.link_stats() and sa["variant_records"] == sb["variant_records"] == len(recs)
+    # other thresholds
+    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "c.fa", "--variant-table", "c.var", "--variant-links", "c.lnk", "--link-neighbours", "1",
+                                                                      "--link-min-depth", "2", "--link-ratio", "0.6"])
+    recs1, links1, arr1 = cli_yardstick(specs, ref, 1)
+    assert open("c.lnk").read() == engine.VARIANTS_LINKS_HEADER + ly.text(recs1, links1, 1, "ref", ref.encode(), 2, 3, 5)
+    assert phases_of(open("c.lnk").read().split("\n", 1)[1])[LOW] != "LOW" and open("c.var").read() == open("b.var").read()
+    # together with --variant-strand: the strand table as without --variant-links, the links as without --variant-strand
+    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "d.fa", "--variant-table", "d.var", "--variant-strand", "--variant-links", "d.lnk"])
+    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "e.fa", "--variant-table", "e.var", "--variant-strand"])
+    assert open("d.lnk").read() == open("a.lnk").read() and open("d.var").read() == open("e.var").read()
+    assert open("d.var").read().startswith(engine.VARIANTS_STRAND_HEADER)
+
+    # --per-contig: the same records on two references of the same sequence: the same rows per region, no pair across the two
+    two = sorted([dict(r, tid=t, name="%s_%d" % (r["name"], t)) for t in (0, 1) for r in specs], key=lambda r: (r["tid"], r["pos"]))
+    bamwriter.write_bam("P.bam", rf.arrays(two), refs=[("c0", CL), ("c1", CL)], block=4096)
+    with open("p.fa", "w") as fh:
+        fh.write(">c0\n%s\n>c1\n%s\n" % (ref, ref))
+    with open("p.gff", "w") as fh:
+        fh.write("##gff-version 3\n" + syn.gff_text(orfs, seqid="c0")[1] + syn.gff_text(orfs, seqid="c1")[1])
+    rf._run_cli(monkeypatch, ["-i", "P.bam", "-ref", "p.fa", "-gff", "p.gff", "-cov", "10", "-name", "S", "--per-contig", "-o", "p.fa.out", "--variant-table", "p.var",
+                              "--variant-links", "p.lnk", "--stats", "p.json"])
+    assert open("p.lnk").read() == engine.VARIANTS_LINKS_HEADER + want.replace("ref\t", "c0\t") + want.replace("ref\t", "c1\t")
+    sp = json.load(open("p.json"))
+    assert {k: sp[k] for k in stats} == {k: 2 * v for k, v in stats.items()} and sp["variant_records"] == 2 * len(recs)
+
+    # one file through consensus_split_bamfile at world 1
+    parts = td.consensus_split_bamfile("A.bam", CL, rf._gff(orfs), 10, True, "S", 0, 1, return_parts=True,
+                                       variant_links=(dict(ref=ref, min_af="0.03", min_alt_depth=1, min_depth=10), 2))
+    vrecs, vlinks = parts[-1]
+    assert engine.variants_links_text(vrecs, vlinks, 2, "ref", ref) == want and len(parts) == 4
+
+    # refused: exit 1, nothing written
+    man = tmp_path / "m.tsv"
+    man.write_text("A.bam\tS0\to0.fa\t-\t-\t-\tt0.var\n")
+    bq._write_override("o.csv.gz", py.counts(rf.arrays(specs), CL)[0])
+    before = sorted(os.listdir(tmp_path))
+    for argv in (["--batch", str(man)] + common + ["--variant-links", "x.lnk"],
+                 ["-i", "A.bam", "-name", "S"] + common + ["-o", "x.fa", "--variant-table", "x.var", "--variant-links", "x.lnk", "--index-override", "o.csv.gz"]):
+        with pytest.raises(SystemExit) as e:
+            cli.main(argv)
+        assert e.value.code == 1
+    assert sorted(os.listdir(tmp_path)) == before
+
+
+def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
+    """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange): rank 0 lists the records and broadcasts their columns, every
+    rank counts its own records, rank 0 writes the sum: the rows of the single-GPU run"""
+    import subprocess
+    import sys
+    monkeypatch.chdir(tmp_path)
+    ref, orfs, specs = cli_case()
+    recs, links, arr = cli_yardstick(specs, ref)
+    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=CL, block=4096, split_records=True)
+    common = bq._setup_cli(tmp_path, ref, orfs)
+    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=rf.ROOT)
+    argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", "A.bam", "-name", "S"] + common + ["-o", "a.fa", "--variant-table", "a.var", "--variant-strand",
+                                                                                                       "--variant-links", "a.lnk", "--link-min-depth", "12", "--gpus", "2"]
+    r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-1500:]
+    assert open("a.lnk").read() == engine.VARIANTS_LINKS_HEADER + engine.variants_links_text(vy.as_array(recs), arr, 2, "ref", ref, min_depth=12)
+    assert open("a.var").read().startswith(engine.VARIANTS_STRAND_HEADER)

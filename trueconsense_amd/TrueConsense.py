@@ -12,7 +12,10 @@ called from; --batch: the manifest's 7th column), the amplicon table --amplicon-
 how many lie below -cov, from the same matrix; --batch: one file for all samples), the reads per amplicon --amplicon-reads FILE
 [--amplicon-reads-slack N] (per amplicon of the scheme the alignment records whose two ends lie inside it and inside no other, and
 how many of them run from its left primer into its right one; records inside several amplicons or inside none are counted as such;
-counted on the device in the decoded record stream; not with --batch), and
+counted on the device in the decoded record stream; not with --batch), the links between the variant table's rows --variant-links FILE
+[--link-neighbours K] [--link-min-depth N] [--link-ratio F] (for every two rows at most K distinct positions apart how many alignment
+records carry both alleles, one of them or neither, and the phase CIS / TRANS / MIXED / NONE / LOW; counted likewise; needs
+--variant-table; not with --batch or --index-override), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -84,6 +87,31 @@ def _min_af_arg(parser, flag="--min-af"):
     return check
 
 
+def _link_ratio_arg(parser):
+    """argparse `type=` callable of --link-ratio: parsed as --min-af is, then refused (parser.error, exit code 2) unless 1/2 < F <= 1."""
+    inner = _min_af_arg(parser, "--link-ratio")
+
+    def check(text):
+        f = inner(text)
+        if not 2 * f > 1:
+            parser.error(f"--link-ratio takes a ratio above 1/2 and up to 1, not {color.YELLOW}{text}{color.END}.")
+        return f
+    return check
+
+
+def _neighbours_arg(parser):
+    """argparse `type=` callable of --link-neighbours: an integer in 1..7 (else parser.error, exit code 2)."""
+    def check(text):
+        try:
+            v = int(text, 10)
+        except ValueError:
+            v = 0
+        if not 1 <= v <= 7:
+            parser.error(f"--link-neighbours takes an integer from 1 to 7, not {color.YELLOW}{text}{color.END}.")
+        return v
+    return check
+
+
 def _count_arg(parser, flag, lo):
     """argparse `type=` callable: an integer in lo..2^31-1 (else parser.error, exit code 2)."""
     def check(text):
@@ -126,6 +154,35 @@ def write_variant_strand_table(path, parts, rule):
     with open(path, "w") as out:
         out.write(VARIANTS_STRAND_HEADER + text)
     return text.count("\tBIAS\n"), text.count("\tLOW\n")
+
+
+def links_of(a):
+    """The parsed namespace's --variant-links settings as (file, neighbours, keyword arguments of engine.variants_links_text), or None
+    without the flag."""
+    if getattr(a, "variant_links", None) is None:
+        return None
+    return a.variant_links, int(a.link_neighbours), dict(min_depth=int(a.link_min_depth), ratio=a.link_ratio)
+
+
+def write_variant_links(path, parts, links):
+    """--variant-links: the header line, then for every (records, their link counts, region, reference on the records' axis,
+    pos_offset) one row per pair of its records at most `neighbours` distinct positions apart.  Pairs across parts never appear.
+    Nothing is written when a part's counts do not add up to its records (TcmiError).  -> {"variant_link_rows": n,
+    "variant_links_cis": .., "_trans", "_mixed", "_none", "_low"}."""
+    from .engine import VARIANTS_LINKS_HEADER, variants_links_text
+    _, k, rule = links
+    text = "".join(variants_links_text(recs, lk, k, region, ref, off, **rule) for recs, lk, region, ref, off in parts)
+    with open(path, "w") as out:
+        out.write(VARIANTS_LINKS_HEADER + text)
+    return link_stats(text)
+
+
+def link_stats(text=""):
+    """the --stats counters of --variant-links' rows (no rows: zeros)"""
+    from .engine import LINK_PHASES
+    out = {"variant_link_rows": text.count("\n")}
+    out.update({"variant_links_" + w.lower(): text.count("\t%s\n" % w) for w in LINK_PHASES})
+    return out
 
 
 def _names_a_table(line):
@@ -392,6 +449,19 @@ def GetArgs(givenargs):
     additive.append((("--strand-ratio",), dict(type=_min_af_arg(parser, "--strand-ratio"), default=None, metavar="F",
                                                help="STRAND is BIAS when the allele's frequency on one strand is below F times its frequency on\n"
                                                     "the other, 0..1, a decimal or n/d (default 1/10)")))
+    additive.append((("--variant-links",), dict(type=str, default=None, metavar="File",
+                                                help="also write, for every two rows of the variant table at most K distinct positions apart, how\n"
+                                                     "many alignment records carry both alleles, one of them or neither: REGION POS_A REF_A ALT_A\n"
+                                                     "POS_B REF_B ALT_B SPAN BOTH ONLY_A ONLY_B NEITHER PHASE (CIS, TRANS, MIXED, NONE or LOW),\n"
+                                                     "counted in the records the device decoded; needs --variant-table and the device decoder;\n"
+                                                     "not with --batch or --index-override; '+' rows are not linked")))
+    additive.append((("--link-neighbours",), dict(type=_neighbours_arg(parser), default=None, metavar="K",
+                                                  help="link a row's position with the next K distinct positions of the table, 1..7 (default 2)")))
+    additive.append((("--link-min-depth",), dict(type=_count_arg(parser, "--link-min-depth", 1), default=None, metavar="N",
+                                                 help="PHASE is LOW when fewer than N records have a token at both positions (default 10)")))
+    additive.append((("--link-ratio",), dict(type=_link_ratio_arg(parser), default=None, metavar="F",
+                                             help="PHASE is CIS when BOTH is at least F of the rarer allele's records among those that span\n"
+                                                  "both positions, TRANS when at most 1 - F; above 1/2 up to 1, a decimal or n/d (default 9/10)")))
     additive.append((("--amplicon-table",), dict(type=str, default=None, metavar="File",
                                                  help="also write per amplicon of the scheme the depth of its columns, tab-separated: SAMPLE REGION\n"
                                                       "AMPLICON POOL START END LEN MEAN MEDIAN MIN MIN_POS BELOW (BELOW: columns under -cov), from\n"
@@ -432,6 +502,19 @@ def GetArgs(givenargs):
             print(f"{why} Exiting...")
             sys.exit(1)
     a.strand_min_depth = 10 if a.strand_min_depth is None else a.strand_min_depth
+    # --variant-links likewise
+    linked = a.variant_links is not None
+    for bad, why in ((not linked and any(v is not None for v in (a.link_neighbours, a.link_min_depth, a.link_ratio)),
+                      "--link-neighbours / --link-min-depth / --link-ratio need --variant-links."),
+                     (linked and a.batch is not None, "--variant-links goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
+                     (linked and a.batch is None and a.variant_table is None, "--variant-links needs --variant-table."),
+                     (linked and a.index_override is not None, "--variant-links does not go with --index-override: the overridden matrix no longer equals the reads.")):
+        if bad:
+            print(f"{why} Exiting...")
+            sys.exit(1)
+    a.link_neighbours = 2 if a.link_neighbours is None else a.link_neighbours
+    a.link_min_depth = 10 if a.link_min_depth is None else a.link_min_depth
+    a.link_ratio = Fraction(9, 10) if a.link_ratio is None else a.link_ratio
     a.strand_ratio = Fraction(1, 10) if a.strand_ratio is None else a.strand_ratio
     if a.batch is not None and a.variant_table is not None:
         parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
@@ -521,6 +604,9 @@ def _child_argv(a, single, tables=True):
             out += ["--variant-table", a.variant_table]
         if a.variant_strand:
             out += ["--variant-strand", "--strand-min-depth", str(a.strand_min_depth), "--strand-ratio", str(a.strand_ratio)]
+        if a.variant_links:
+            out += ["--variant-links", a.variant_links, "--link-neighbours", str(a.link_neighbours), "--link-min-depth", str(a.link_min_depth),
+                    "--link-ratio", str(a.link_ratio)]
         if a.amplicon_table:
             out += ["--amplicon-table", a.amplicon_table]
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]
@@ -702,20 +788,23 @@ def _single_sample(a, flt, t):
     bam = LazyBam(a.input, threads=a.threads, read_filter=flt)      # reads reach the host only if an insert candidate needs its tokens
     t["bam_open"] = time.perf_counter()
     areads, got = amplicon_reads_of(a), {}
-    srule = strand_of(a)
-    if areads or srule:                             # counted behind the step, on the read set the step returned, while its stream is resident
+    srule, links = strand_of(a), links_of(a)
+    if areads or srule or links:                    # counted behind the step, on the read set the step returned, while its stream is resident
         def count_reads(ctx, rs):
             if areads:
                 got["counts"] = ctx.amplicon_reads(rs, areads[1], areads[2])
             if srule:                               # (the columns must be known now: the step computed the table's records)
                 got["strand"] = ctx.strand_counts_of(rs, ctx.step_variants())
-        if srule:
+            if links:                               # (likewise, while the stream is resident)
+                got["links"] = ctx.link_counts_of(rs, ctx.step_variants(), links[1])
+        if srule or links:
             from .io import fasta
             _state.default_context().set_variants(fasta.read_first_record(a.reference)[1], **variants_of(a))
         try:
-            counts = build_counts(bam, a.reference, on_readset=count_reads, need_device="--variant-strand" if srule else "--amplicon-reads")
+            counts = build_counts(bam, a.reference, on_readset=count_reads,
+                                  need_device="--variant-strand" if srule else "--variant-links" if links else "--amplicon-reads")
         finally:
-            if srule:
+            if srule or links:
                 _state.default_context().set_variants()
         if areads:
             write_amplicon_reads(a.amplicon_reads, a.samplename, got["counts"], areads[0])
@@ -737,6 +826,7 @@ def _single_sample(a, flt, t):
     if a.depth_of_coverage is not None:
         BuildCoverage(indexDict, a.depth_of_coverage)
     n_variants = n_bias = n_low = 0
+    lstats = link_stats()
     if a.variant_table is not None:                 # from the counts the consensus is called from (behind --index-override)
         from .io import fasta
         refID, refseq = fasta.read_first_record(a.reference)
@@ -745,6 +835,8 @@ def _single_sample(a, flt, t):
             n_bias, n_low = write_variant_strand_table(a.variant_table, [(recs, got["strand"], refID, refseq, 0)], srule)
         else:
             write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
+        if links:                                   # (its writer refuses likewise)
+            lstats = write_variant_links(links[0], [(recs, got["links"], refID, refseq, 0)], links)
         n_variants = len(recs)
 
     amps, n_below = amplicons_of(a), 0
@@ -764,7 +856,7 @@ def _single_sample(a, flt, t):
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
-                       "variant_records": n_variants, "variant_strand_bias": n_bias, "variant_strand_low": n_low,
+                       "variant_records": n_variants, "variant_strand_bias": n_bias, "variant_strand_low": n_low, **lstats,
                        "amplicons": len(amps) if amps else 0, "amplicons_below": n_below,
                        "amplicon_reads_ambiguous": int(got["counts"]["reads"][-2]) if areads else 0,
                        "amplicon_reads_unassigned": int(got["counts"]["reads"][-1]) if areads else 0,

@@ -122,7 +122,7 @@ def axis_reference(records, header_names, shift, axis_len):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, amplicon_reads=None, variant_strand=False):
+                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, amplicon_reads=None, variant_strand=False, variant_links=0):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
@@ -137,7 +137,9 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     counted per amplicon in the decoded stream, which info receives as "amplicon_reads"; a file the device decoder declines is
     refused then (reads decoded on the host leave no stream on the device).  variant_strand (with variants): behind the step the
     planes at the table's distinct columns are counted per strand in the decoded stream (Context.strand_counts), which info
-    receives as "variant_strand"; a file the device decoder declines is refused likewise."""
+    receives as "variant_strand"; a file the device decoder declines is refused likewise.  variant_links = K > 0 (with variants):
+    behind the step the joint token classes of the records at every table column and its next K are counted in the decoded stream
+    (Context.link_counts), which info receives as "variant_links"; refused likewise."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
@@ -149,7 +151,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_intervals(*intervals)
     host = None
     try:
-        rs = device_readset(ctx, path, need="--variant-strand" if variant_strand else "--amplicon-reads" if amplicon_reads else None)    # (the floor it refuses under is the one just set)
+        rs = device_readset(ctx, path, need="--variant-strand" if variant_strand else "--variant-links" if variant_links else "--amplicon-reads" if amplicon_reads else None)    # (the floor it refuses under is the one just set)
         if rs is None:
             host = BamFile(path, threads=threads, read_filter=read_filter)
             try:
@@ -167,6 +169,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
                 info["variant_table"] = ctx.step_variants()
                 if variant_strand:                              # (one call over all contigs' columns on the shifted axis; the stream is still resident)
                     info["variant_strand"] = ctx.strand_counts_of(rs, info["variant_table"])
+                if variant_links:                               # (likewise; the pairs across two contigs are dropped by the writer's caller)
+                    info["variant_links"] = ctx.link_counts_of(rs, info["variant_table"], variant_links)
             if intervals and info is not None:
                 info["amplicon_table"] = ctx.step_intervals()
             if amplicon_reads and info is not None:             # (the layout is still set: the read set's shifts are the table's)
@@ -188,8 +192,9 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, read_filter_of, strand_of, variants_of,
-                               write_amplicon_reads, write_amplicon_table, write_variant_strand_table, write_variant_table)
+    from .TrueConsense import (amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, link_stats, links_of, read_filter_of, strand_of,
+                               variants_of, write_amplicon_reads, write_amplicon_table, write_variant_links, write_variant_strand_table,
+                               write_variant_table)
     flt, seen = read_filter_of(a), {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -211,7 +216,8 @@ def run(a):
                                                                  min_baseq=a.min_baseq, primers=prm, variants=var,
                                                                  intervals=(amplicon_intervals(amps), mincov) if amps else None,
                                                                  amplicon_reads=areads[1:] if areads else None,
-                                                                 variant_strand=strand_of(a) is not None)
+                                                                 variant_strand=strand_of(a) is not None,
+                                                                 variant_links=links_of(a)[1] if links_of(a) else 0)
     rcounts = seen.pop("amplicon_reads", None)
     seen["amplicon_reads_ambiguous"] = 0 if rcounts is None else int(rcounts["reads"][-2])
     seen["amplicon_reads_unassigned"] = 0 if rcounts is None else int(rcounts["reads"][-1])
@@ -220,6 +226,8 @@ def run(a):
     seen["variant_records"] = 0 if table is None else len(table)
     strand = seen.pop("variant_strand", None)
     seen["variant_strand_bias"] = seen["variant_strand_low"] = 0
+    links = seen.pop("variant_links", None)
+    seen.update(link_stats())
     arecs = seen.pop("amplicon_table", None)
     seen["amplicons_below"] = 0 if arecs is None else int((arecs["below"] > 0).sum())
 
@@ -289,6 +297,12 @@ def run(a):
             seen["variant_strand_bias"], seen["variant_strand_low"] = write_variant_strand_table(a.variant_table, parts, strand_of(a))
         else:
             write_variant_table(a.variant_table, parts)
+        if links is not None:                       # the writer once per contig, with the link counts of its own columns: no pair across two contigs
+            lparts = []
+            for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]):
+                mine = (links["a"] >= s) & (links["a"] < s + len(seq))
+                lparts.append((table[(table["pos"] >= s) & (table["pos"] < s + len(seq))], links[mine], rid, axis_ref, s))
+            seen.update(write_variant_links(links_of(a)[0], lparts, links_of(a)))
     if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
         write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
     if rcounts is not None:                         # one file: REGION is each amplicon's contig

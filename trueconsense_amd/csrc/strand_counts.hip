@@ -2,9 +2,10 @@
 // (FLAG 0x10), counted in the inflated BAM stream a device-decoded read set left in the context's arena (include/tcmi.h:
 // tcmi_readset_strand_counts).  The matrix sums the strands and the packed set does not keep the flag: only the records have it.
 //
-// Here: the kernel, its per-column walk, and the entry that checks and narrows the columns and unpacks the sums.  Which record is kept
-// and where it lies on the axis (kept_span), the primer table's lookup (seg_find) and the leaves of the token rule (base_plane,
-// qual_at): pack_device.h; the residency refusals, the scratch, the launch shape, the download and the sub-ranges: stream_count.h.
+// Here: the kernel and the entry that checks and narrows the columns and unpacks the sums.  The per-column walk and the token rule
+// (open_walk, token_at, first_at_or_above), shared with link_counts.hip: stream_walk.h; which record is kept and where it lies on the
+// axis (kept_span), the primer table's lookup (seg_find) and the leaves of the token rule (base_plane, qual_at): pack_device.h; the
+// residency refusals, the scratch, the launch shape, the download and the sub-ranges: stream_count.h.
 //
 // One launch, one lane per record, 256-lane workgroups that stride over the records: the grid is min(ceil(records / 256), compute
 // units x 8).  LDS: the columns and [n][14] counters of up to TCMI_STRAND_LDS columns, 15 KiB.
@@ -26,6 +27,7 @@
 #include <vector>
 
 #include "stream_count.h"
+#include "stream_walk.h"
 
 namespace {
 
@@ -33,7 +35,7 @@ constexpr int BLOCK = SC_BLOCK;
 constexpr int LDS_N = TCMI_STRAND_LDS;
 constexpr int NK = 14;                  // counters per column: fwd[7] | rev[7] in plane order
 constexpr int64_t MAX_N = 1 << 20;
-constexpr int64_t MAX_COL = 1 << 29;
+constexpr int64_t MAX_COL = WALK_MAX_COL;
 
 struct ScArgs {
     PackSrc src;                        // the resident stream, the read set's filter, floor and layout
@@ -42,73 +44,6 @@ struct ScArgs {
     int32_t *counts;                    // [n][14]
     int32_t n;
 };
-
-// a kept record between its queried columns
-struct Walk {
-    ReadView v;
-    int32_t x, y;                       // the first column and the query index of op k
-    uint32_t k;
-    int32_t q;                          // the last column
-    int32_t keep0, keep1;               // tokens on columns outside [keep0, keep1) are masked
-};
-
-// record i, when it is kept -> its walk at the head of the CIGAR
-__device__ inline bool open_walk(const ScArgs &a, int64_t i, Walk &w)
-{
-    int64_t p, q;
-    if (!kept_span(a.src, i, w.v, p, q)) return false;
-    if (p >= MAX_COL) return false;                         // (beyond every column that can be asked for)
-    w.x = (int32_t)p; w.y = 0; w.k = 0;
-    w.q = (int32_t)(q < MAX_COL ? q : MAX_COL);
-    w.keep0 = INT32_MIN; w.keep1 = INT32_MAX;
-    if (a.pt.n_head + a.pt.n_tail != 0) {
-        w.keep0 = seg_find(a.pt.seg, a.pt.n_head, w.x, w.x);
-        w.keep1 = seg_find(a.pt.seg + 3 * a.pt.n_head, a.pt.n_tail, w.q, w.q + 1);
-    }
-    return true;
-}
-
-// the planes the record's token on column c adds to (bit TCMI_COV..TCMI_I), c in [w.x, w.q] and not below an earlier call's
-__device__ inline uint32_t token_at(Walk &w, int32_t c, uint32_t Q)
-{
-    const ReadView &v = w.v;
-    uint32_t op = 0;
-    int32_t len = 0;
-    for (;; ++w.k) {                                        // on to the op that holds column c
-        if (w.k >= v.n_cigar) return 0u;
-        const uint32_t cw = ld_u32(v.cigar + 4 * (size_t)w.k);
-        op = cw & 0xFu;
-        len = (int32_t)(cw >> 4);
-        if (consumes_ref(op)) {
-            if (c - w.x < len) break;
-            w.x += len;
-        }
-        if (consumes_query(op)) w.y += len;
-    }
-    if (c < w.keep0 || c >= w.keep1) return 0u;             // masked: nothing, the I mark included
-    const int32_t j = c - w.x;
-    const int32_t qi = is_match(op) ? w.y + j : w.y;       // a D / N token is tested with the query index at which its op starts
-    if (Q != 0u && qual_at(v, qi) < Q) return 0u;          // below the floor (Q = 0: nothing is, and QUAL is not read)
-    const bool ins = j == len - 1 && ins_after(v.cigar, v.n_cigar, w.k);
-    uint32_t bits = 1u << TCMI_COV;                         // M, =, X, D and N all count coverage
-    if (is_match(op)) {
-        const uint32_t nib = qi < v.l_seq ? nib_at(v.seq, qi) : 15u;           // past SEQ -> 'N'
-        if (__popc(nib) == 1) bits |= 1u << base_plane(nib);
-    } else if (op == 2 && !ins) bits |= 1u << TCMI_X;       // "*+.." does not count X
-    if (ins) bits |= 1u << TCMI_I;
-    return bits;
-}
-
-__device__ inline int32_t first_at_or_above(const int32_t *cols, int32_t n, int32_t p)
-{
-    int32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const int32_t mid = (lo + hi) >> 1;
-        if (cols[mid] < p) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(BLOCK) void strand_counts_kernel(ScArgs a)
 {
@@ -129,7 +64,7 @@ __global__ __launch_bounds__(BLOCK) void strand_counts_kernel(ScArgs a)
         const int64_t i = base + tid;
         Walk w;
         int32_t ci = 0;
-        bool have = i < a.src.n && open_walk(a, i, w);
+        bool have = i < a.src.n && open_walk(a.src, a.pt, i, w);
         if (have) {
             ci = first_at_or_above(cols, a.n, w.x);
             have = ci < a.n && cols[ci] <= w.q;

@@ -2,7 +2,7 @@
 // its context's arena: is the stream still there (tally.hip's long reads, ins_entries.hip, the counting calls), grow-only scratch of a
 // context, and the driver of a COUNTING call — one kernel over the records, one lane per record, that turns a small input (a table, a
 // list of columns) into integer counters: tcmi_readset_amplicon_reads (amplicon_reads.hip), tcmi_readset_strand_counts
-// (strand_counts.hip).  Which record such a kernel counts: pack_device.h's kept_span.
+// (strand_counts.hip), tcmi_readset_link_counts (link_counts.hip).  Which record such a kernel counts: pack_device.h's kept_span.
 #pragma once
 #include <algorithm>
 #include <cstring>

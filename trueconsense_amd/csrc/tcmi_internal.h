@@ -195,8 +195,8 @@ struct tcmi_ctx {
     char *tok_dev = nullptr, *tok_host = nullptr;
     size_t tok_dev_cap = 0, tok_host_cap = 0;
     // scratch that the counting calls over the record stream share (stream_count.h; tcmi_readset_amplicon_reads: the compiled table, the
-    // counters; tcmi_readset_strand_counts: the columns, the counters): device, grow-only; its host side is h_pin.  Every such call
-    // waits for the stream before it returns.
+    // counters; tcmi_readset_strand_counts and tcmi_readset_link_counts: the columns, the counters): device, grow-only; its host side is
+    // h_pin.  Every such call waits for the stream before it returns.
     char *count_dev = nullptr;
     size_t count_dev_cap = 0;
     // small read-backs of the cold path (block verdicts, packer totals) land in pinned memory of the context: a copy into pageable

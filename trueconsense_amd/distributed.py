@@ -366,7 +366,7 @@ def _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks):
 
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
                             step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
-                            min_baseq=None, primers=None, amplicon_reads=None, variant_strand=None):
+                            min_baseq=None, primers=None, amplicon_reads=None, variant_strand=None, variant_links=None):
     """BASELINE configs[4] all the way: ONE BAM file over `world` ranks -> its consensus FASTA text on rank 0 (None on the others).
     What the ranks jointly replace is the reference's single pile-up pass (indexing.py:96-100), its insert candidates' region
     pile-ups (Events.py:47-82) and the walk (Sequences.py:168-322):
@@ -401,7 +401,10 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     min_af, min_alt_depth, min_depth): behind that, rank 0 lists the variant table's records from the reduced matrix and broadcasts
     their distinct columns, every rank counts the planes at those columns per strand in its own read set (Context.strand_counts), the
     ranks agree that everybody has counts, and the [n, 14] int32 counts are summed to rank 0 likewise; with return_parts rank 0's
-    tuple then ends with (records, strand counts)."""
+    tuple then has (records, strand counts).  variant_links = (the same keyword arguments, K): likewise every rank counts the joint
+    token classes of its own records at the root's columns and their next K (Context.link_counts) and the [n * K, 49] int32 counts are
+    summed to rank 0 — a record is one rank's, so the sum is the file's; with return_parts rank 0's tuple then ends with (records, link
+    counts)."""
     import time
     import torch
     import torch.distributed as dist
@@ -409,9 +412,11 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     L = int(ref_len)
     ld, n_words = split_words(L, world)
     root = rank == 0
-    plain = alt = flags = counts_root = reads_root = strand_root = None
+    plain = alt = flags = counts_root = reads_root = strand_root = links_root = None
     if variant_strand is not None and step_fn is not None:
         raise ValueError("consensus_split_bamfile: variant_strand counts in the stream the device decoded: it does not go with step_fn")
+    if variant_links is not None and step_fn is not None:
+        raise ValueError("consensus_split_bamfile: variant_links counts in the stream the device decoded: it does not go with step_fn")
     own_ctx, own_d = ctx is None, dbam is None
     d, rs = dbam, None
     err = None
@@ -457,7 +462,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                     err = (rc, (lib().tcmi_last_error(ctx.handle) or b"").decode("utf-8", "replace"))
                 elif root:
                     plain, alt, flags = planes
-                    if return_parts or variant_strand is not None:
+                    if return_parts or variant_strand is not None or variant_links is not None:
                         counts_root = np.ascontiguousarray(t[:7 * ld].view(7, ld)[:, :L].T.cpu().numpy())
         else:
             d_blocks = step_fn("n_blocks")
@@ -527,6 +532,35 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                 strand = np.zeros(len(vcols), STRAND_DTYPE)
                 strand["fwd"], strand["rev"], strand["pos"] = mine[:, :7], mine[:, 7:], vcols
                 strand_root = (vrecs, strand)
+        if variant_links is not None:                                # link counts at the table's columns: every rank its own records, one sum to rank 0
+            from .engine import LINK_DTYPE
+            lkw, lk = variant_links
+            vrecs = ctx.variants(counts_root, **lkw) if root else None
+            vcols = [np.unique(vrecs["pos"].astype(np.int64)).tolist() if root else None]
+            if multi:
+                dist.broadcast_object_list(vcols, src=0, group=group)
+            vcols = np.asarray(vcols[0], np.int64)
+            got, lerr = None, None
+            try:
+                got = ctx.link_counts(rs, vcols, lk) if len(vcols) else np.zeros(0, LINK_DTYPE)
+            except TcmiError as e:
+                lerr = (e.code, str(e))
+            if multi:                                                # nobody enters the reduce unless everybody has counts
+                alll = [None] * dist.get_world_size(group)
+                dist.all_gather_object(alll, lerr, group=group)
+                lerr = next((v for v in alll if v), None)
+            if lerr is not None:
+                raise TcmiError(lerr[0], "consensus_split_bamfile: link counts: %s" % lerr[1])
+            mine = np.ascontiguousarray(got["j"].reshape(len(got), 49))
+            if multi and len(vcols):
+                on_gpu = dist.get_backend(group) == "nccl"
+                tr = torch.from_numpy(mine).cuda() if on_gpu else torch.from_numpy(mine)
+                dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
+                mine = tr.cpu().numpy()
+            if root:
+                got = got.copy()                                     # (a and b are the same on every rank: the columns are the root's)
+                got["j"] = mine.reshape(len(got), 7, 7)
+                links_root = (vrecs, got)
         # the insert-candidate columns, from rank 0 to everybody
         cand = [(np.nonzero(flags & 8)[0] + 1).tolist()] if root else [None]
         if multi:
@@ -571,7 +605,8 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
             timings["release"] = time.perf_counter() - t2
             timings["total"] = time.perf_counter() - t0
     if return_parts:
-        parts = (text, counts_root, toks) + ((reads_root,) if amplicon_reads is not None else ()) + ((strand_root,) if variant_strand is not None else ())
+        parts = (text, counts_root, toks) + ((reads_root,) if amplicon_reads is not None else ()) + ((strand_root,) if variant_strand is not None else ()) + \
+            ((links_root,) if variant_links is not None else ())
         return parts if root else None
     return text
 

@@ -171,6 +171,51 @@ def variants_strand_text(records, strand, region, ref, pos_offset=0, min_strand_
     return buf.raw[:ln.value].decode("latin-1")
 
 
+# struct tcmi_link_counts: the kept records by token class at the two columns of a pair (--variant-links)
+LINK_DTYPE = np.dtype([("j", np.int32, (7, 7)), ("a", np.int32), ("b", np.int32), ("reserved", np.int32)])
+VARIANTS_LINKS_HEADER = "REGION\tPOS_A\tREF_A\tALT_A\tPOS_B\tREF_B\tALT_B\tSPAN\tBOTH\tONLY_A\tONLY_B\tNEITHER\tPHASE\n"
+LINKS_LDS = 80                   # TCMI_LINKS_LDS: pairs (columns x neighbours) whose counters the kernel stages in LDS
+LINKS_MAX_PAIRS = 1 << 17        # columns x neighbours of one tcmi_readset_link_counts call
+LINK_PHASES = ("CIS", "TRANS", "MIXED", "NONE", "LOW")
+
+
+def link_phase(both, only_a, only_b, span, min_depth=10, ratio="9/10"):
+    """tcmi_link_phase (HOST, exact integers) -> 0 CIS, 1 TRANS, 2 MIXED, 3 NONE, 4 LOW: LOW iff span < min_depth; else with m the
+    smaller of both + only_a and both + only_b: NONE iff m = 0, CIS iff both >= ratio * m, TRANS iff both <= (1 - ratio) * m, else
+    MIXED.  ratio in (1/2, 1]."""
+    num, den = min_af_fraction(ratio)
+    rc = lib().tcmi_link_phase(int(both), int(only_a), int(only_b), int(span), int(min_depth), num, den)
+    if rc < 0:
+        raise _ffi.TcmiError(rc, "tcmi_link_phase: a negative count, min_depth < 1 or a ratio outside (1/2, 1]")
+    return rc
+
+
+def variants_links_text(records, links, k, region, ref, pos_offset=0, min_depth=10, ratio="9/10"):
+    """--variant-links' rows for `records` (tcmi_variants_links_text; HOST): one per pair of records whose positions are at most k
+    distinct positions apart, both alleles in A, T, C, G, *.  links: Context.link_counts at the records' distinct positions,
+    ascending, with the same k.  -> str, without the header line (VARIANTS_LINKS_HEADER).  TcmiError(E_ARG) when the counts do not
+    belong to the records or do not add up to them."""
+    records = np.ascontiguousarray(records, VARIANT_DTYPE)
+    links = np.ascontiguousarray(links, LINK_DTYPE)
+    ref = _ref_bytes(ref)
+    num, den = min_af_fraction(ratio)
+    k = int(k)
+    if k < 1 or len(links) % k:
+        raise _ffi.TcmiError(_ffi.E_ARG, "tcmi_variants_links_text: %d link records are not a multiple of k = %d" % (len(links), k))
+    args = (ptr(records) if len(records) else None, len(records), ptr(links) if len(links) else None, len(links) // k, k, int(min_depth), num, den,
+            str(region).encode(), int(pos_offset), ptr(ref) if len(ref) else None, len(ref))
+    ln = C.c_int64(0)
+    buf = None
+    rc = lib().tcmi_variants_links_text(*args, None, 0, C.byref(ln))        # the sizing call
+    if not rc:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib().tcmi_variants_links_text(*args, C.cast(buf, C.c_void_p), ln.value, C.byref(ln))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_variants_links_text: the link counts do not belong to the records or do not add up to them "
+                                 "(or a record does not fit the reference, the offset or the thresholds)")
+    return buf.raw[:ln.value].decode("latin-1")
+
+
 def _grab(vp, dtype, n):
     """n items of dtype at address vp (memory the library owns) -> a fresh numpy array."""
     out = np.empty(n, dtype)
@@ -474,6 +519,24 @@ class Context:
         cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
         parts = [self.strand_counts(readset, cols[k:k + STRAND_MAX_COLS]) for k in range(0, len(cols), STRAND_MAX_COLS)]
         return np.concatenate(parts) if parts else np.zeros(0, STRAND_DTYPE)
+
+    def link_counts(self, readset, cols, k):
+        """Joint token classes of the kept records at pairs of nearby columns (tcmi_readset_link_counts): cols strictly ascending on
+        the count matrix's axis, k neighbours in 1..7, len(cols) * k in 1..2^17 -> a structured array (LINK_DTYPE) of len(cols) * k
+        records: record i * k + d - 1 is the pair (cols[i], cols[i + d]) with j[x][y] the records of class x at a and y at b (0 no
+        token, 1..4 A T C G, 5 a deleted column, 6 coverage only); b = -1 where cols has no such column.  The read set must have
+        been decoded on the device and its stream must still be resident on this context, else TcmiError(E_UNSUPPORTED)."""
+        cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
+        k = int(k)
+        out = np.zeros(len(cols) * max(k, 0), LINK_DTYPE)
+        check(lib().tcmi_readset_link_counts(self.handle, readset.handle, len(cols), ptr(cols) if len(cols) else None, k, ptr(out) if len(out) else None),
+              self.handle)
+        return out
+
+    def link_counts_of(self, readset, records, k):
+        """link_counts at the distinct positions of variant `records` -> a structured array (LINK_DTYPE), empty without records"""
+        cols = np.unique(np.ascontiguousarray(records, VARIANT_DTYPE)["pos"].astype(np.int64))
+        return self.link_counts(readset, cols, k) if len(cols) else np.zeros(0, LINK_DTYPE)
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of

@@ -28,8 +28,9 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import (GetArgs, amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, read_filter_of, strand_of, variants_of,
-                               write_amplicon_reads, write_amplicon_table, write_variant_strand_table, write_variant_table)
+    from .TrueConsense import (GetArgs, amplicon_intervals, amplicon_reads_of, amplicons_of, links_of, primers_of, read_filter_of, strand_of,
+                               variants_of, write_amplicon_reads, write_amplicon_table, write_variant_links, write_variant_strand_table,
+                               write_variant_table)
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
     torch.cuda.set_device(device)
@@ -50,12 +51,13 @@ def main(argv=None):
         gffdict = IndexGff.index_dict(seqid=a.samplename)
         rows = [{"start": int(r["start"]), "end": int(r["end"]), "strand": r.get("strand")} for r in gffdict.values()]
         refID, refseq = fasta.read_first_record(a.reference)
-        srule = strand_of(a)
+        srule, links = strand_of(a), links_of(a)
         areads = amplicon_reads_of(a)                                # (an unusable scheme ends every rank here, before the step)
         parts = td.consensus_split_bamfile(a.input, len(refseq), rows, a.coverage_level, a.noambiguity is False, a.samplename, rank, world,
                                            device=device, return_parts=True, rccl_user=user, read_filter=read_filter_of(a), min_baseq=a.min_baseq,
                                            primers=primers_of(a), amplicon_reads=areads[1:] if areads else None,
-                                           variant_strand=dict(variants_of(a), ref=refseq) if srule else None)
+                                           variant_strand=dict(variants_of(a), ref=refseq) if srule else None,
+                                           variant_links=(dict(variants_of(a), ref=refseq), links[1]) if links else None)
         if rank == 0:
             _, counts, toks = parts[:3]
             if areads:                                               # (the ranks' counts, summed: a record starts in one rank's blocks)
@@ -65,11 +67,14 @@ def main(argv=None):
                 BuildCoverage(index, a.depth_of_coverage)
             if a.variant_table is not None:                          # (from the reduced counts, as the single-GPU command line from its own)
                 if srule:                                            # (the records the root listed behind the reduce, the ranks' strand counts summed)
-                    recs, strand = parts[-1]
+                    recs, strand = parts[-2 if links else -1]
                     write_variant_strand_table(a.variant_table, [(recs, strand, refID, refseq, 0)], srule)
                 else:
                     recs = _state.default_context().variants(index.counts, refseq, **variants_of(a))
                     write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
+                if links:                                            # (likewise the ranks' link counts, summed)
+                    lrecs, lcounts = parts[-1]
+                    write_variant_links(links[0], [(lrecs, lcounts, refID, refseq, 0)], links)
             amps = amplicons_of(a)
             if amps:                                                 # (likewise the amplicon table)
                 arecs = _state.default_context().interval_stats(index.counts, amplicon_intervals(amps), a.coverage_level)
