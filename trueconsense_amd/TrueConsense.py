@@ -185,6 +185,74 @@ def link_stats(text=""):
     return out
 
 
+class StreamCounts:
+    """What the command line counts behind the step, in the record stream the device decoder leaves resident: --amplicon-reads,
+    --variant-strand and --variant-links of the parsed namespace (layout: amplicon_reads_of's).  False when none is asked for.  A
+    further count of this kind is one more line in each method here, and one _sum_to_root call in distributed.consensus_split_bamfile."""
+    KEYS = ("amplicon_reads", "variant_strand", "variant_links")    # count's keys; the order of consensus_split_bamfile's extra parts
+
+    def __init__(self, a, layout=None):
+        self.areads, self.srule, self.links = amplicon_reads_of(a, layout), strand_of(a), links_of(a)
+        self.lists_records = bool(self.srule or self.links)          # must the step list the variant table's records?
+        self.variants = variants_of(a) if self.lists_records else None
+        # the flag named when the file leaves the device path (indexing.device_readset's `need`)
+        self.need = "--variant-strand" if self.srule else "--variant-links" if self.links else "--amplicon-reads" if self.areads else None
+
+    def __bool__(self):
+        return self.need is not None
+
+    def count(self, ctx, rs, records=None):
+        """The counts asked for on read set rs, resident on ctx, under KEYS; records: the variant table's records of the step (fetched
+        from the context when not given)."""
+        got = {}
+        if self.areads:
+            got["amplicon_reads"] = ctx.amplicon_reads(rs, *self.areads[1:])
+        if self.lists_records and records is None:
+            records = ctx.step_variants()
+        if self.srule:
+            got["variant_strand"] = ctx.strand_counts_of(rs, records)
+        if self.links:
+            got["variant_links"] = ctx.link_counts_of(rs, records, self.links[1])
+        return got
+
+    def split_kwargs(self, ref):
+        """distributed.consensus_split_bamfile's keyword arguments of the counts, the file being aligned to the sequence `ref`"""
+        var = dict(self.variants, ref=ref) if self.lists_records else None
+        return dict(amplicon_reads=self.areads[1:] if self.areads else None, variant_strand=var if self.srule else None,
+                    variant_links=(var, self.links[1]) if self.links else None)
+
+    def from_parts(self, parts):
+        """rank 0's return_parts tuple of consensus_split_bamfile(**split_kwargs) -> (count's dict, the records the root listed or None)"""
+        got = dict(zip([k for k, on in zip(self.KEYS, (self.areads, self.srule, self.links)) if on], parts[3:]))
+        records = None
+        for k in self.KEYS[1:]:
+            if k in got:
+                records, got[k] = got[k]
+        return got, records
+
+    def stats(self, got=None):
+        """the --stats keys of --amplicon-reads (write_variant_tables returns those of the other two)"""
+        r = got["amplicon_reads"]["reads"] if got and "amplicon_reads" in got else (0, 0)
+        return {"amplicon_reads_ambiguous": int(r[-2]), "amplicon_reads_unassigned": int(r[-1])}
+
+
+def write_variant_tables(a, parts, want):
+    """--variant-table — with the strand columns under --variant-strand — and then --variant-links: parts = [(records, their strand
+    counts or None, their link counts or None, region, reference on the records' axis, pos_offset)], want = StreamCounts(a).  -> their
+    --stats keys (zeros for what was not asked for; no --variant-table: nothing written, all zeros)."""
+    stats = dict(variant_records=0, variant_strand_bias=0, variant_strand_low=0, **link_stats())
+    if a.variant_table is None:
+        return stats
+    stats["variant_records"] = sum(len(p[0]) for p in parts)
+    if want.srule:                                  # (the writer refuses counts that do not add up to the records)
+        stats["variant_strand_bias"], stats["variant_strand_low"] = write_variant_strand_table(a.variant_table, [p[:2] + p[3:] for p in parts], want.srule)
+    else:
+        write_variant_table(a.variant_table, [p[:1] + p[3:] for p in parts])
+    if want.links:                                  # (its writer refuses likewise)
+        stats.update(write_variant_links(want.links[0], [p[:1] + p[2:] for p in parts], want.links))
+    return stats
+
+
 def _names_a_table(line):
     """does this manifest line's 7th column name a variant table ("-" or empty: none)?"""
     f = line.rstrip("\n").split("\t")
@@ -493,29 +561,17 @@ def GetArgs(givenargs):
     a = parser.parse_args(givenargs)
     from fractions import Fraction
     a.variant_thresholds_given = any(v is not None for v in (a.min_af, a.min_alt_depth, a.variant_min_depth))
-    # --variant-strand: its refusals exit 1 with one line, nothing written
-    for bad, why in ((not a.variant_strand and (a.strand_min_depth is not None or a.strand_ratio is not None), "--strand-min-depth / --strand-ratio need --variant-strand."),
-                     (a.variant_strand and a.batch is not None, "--variant-strand goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
-                     (a.variant_strand and a.batch is None and a.variant_table is None, "--variant-strand needs --variant-table."),
-                     (a.variant_strand and a.index_override is not None, "--variant-strand does not go with --index-override: the overridden matrix no longer equals the reads.")):
-        if bad:
-            print(f"{why} Exiting...")
-            sys.exit(1)
-    a.strand_min_depth = 10 if a.strand_min_depth is None else a.strand_min_depth
-    # --variant-links likewise
-    linked = a.variant_links is not None
-    for bad, why in ((not linked and any(v is not None for v in (a.link_neighbours, a.link_min_depth, a.link_ratio)),
-                      "--link-neighbours / --link-min-depth / --link-ratio need --variant-links."),
-                     (linked and a.batch is not None, "--variant-links goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
-                     (linked and a.batch is None and a.variant_table is None, "--variant-links needs --variant-table."),
-                     (linked and a.index_override is not None, "--variant-links does not go with --index-override: the overridden matrix no longer equals the reads.")):
-        if bad:
-            print(f"{why} Exiting...")
-            sys.exit(1)
-    a.link_neighbours = 2 if a.link_neighbours is None else a.link_neighbours
-    a.link_min_depth = 10 if a.link_min_depth is None else a.link_min_depth
-    a.link_ratio = Fraction(9, 10) if a.link_ratio is None else a.link_ratio
-    a.strand_ratio = Fraction(1, 10) if a.strand_ratio is None else a.strand_ratio
+    # the flags that count behind the step, with their dependant options: their refusals exit 1 with one line, nothing written
+    for flag, on, deps in (("--variant-strand", a.variant_strand, ("strand_min_depth", "strand_ratio")),
+                           ("--variant-links", a.variant_links is not None, ("link_neighbours", "link_min_depth", "link_ratio"))):
+        names = " / ".join("--" + d.replace("_", "-") for d in deps)
+        for bad, why in ((not on and any(getattr(a, d) is not None for d in deps), f"{names} need {flag}."),
+                         (on and a.batch is not None, f"{flag} goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
+                         (on and a.batch is None and a.variant_table is None, f"{flag} needs --variant-table."),
+                         (on and a.index_override is not None, f"{flag} does not go with --index-override: the overridden matrix no longer equals the reads.")):
+            if bad:
+                print(f"{why} Exiting...")
+                sys.exit(1)
     if a.batch is not None and a.variant_table is not None:
         parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
     if a.batch is None and a.variant_table is None and a.variant_thresholds_given:
@@ -536,11 +592,10 @@ def GetArgs(givenargs):
             parser.error("--amplicon-table counts the columns below -cov, which cannot be negative.")
     if a.amplicon_table is not None or a.amplicon_reads is not None:
         a.amplicon_scheme = a.primers if a.amplicon_scheme is None else a.amplicon_scheme
-    a.amplicon_reads_slack = 5 if a.amplicon_reads_slack is None else a.amplicon_reads_slack
-    a.amplicon_region = "insert" if a.amplicon_region is None else a.amplicon_region
-    a.min_af = Fraction(3, 100) if a.min_af is None else a.min_af
-    a.min_alt_depth = 1 if a.min_alt_depth is None else a.min_alt_depth
-    a.variant_min_depth = 10 if a.variant_min_depth is None else a.variant_min_depth
+    for key, default in dict(strand_min_depth=10, strand_ratio=Fraction(1, 10), link_neighbours=2, link_min_depth=10, link_ratio=Fraction(9, 10),
+                             amplicon_reads_slack=5, amplicon_region="insert", min_af=Fraction(3, 100), min_alt_depth=1, variant_min_depth=10).items():
+        if getattr(a, key) is None:                 # (None until here: the checks above ask whether the option was given)
+            setattr(a, key, default)
     return a
 
 
@@ -787,27 +842,18 @@ def _single_sample(a, flt, t):
     from .engine import LazyBam
     bam = LazyBam(a.input, threads=a.threads, read_filter=flt)      # reads reach the host only if an insert candidate needs its tokens
     t["bam_open"] = time.perf_counter()
-    areads, got = amplicon_reads_of(a), {}
-    srule, links = strand_of(a), links_of(a)
-    if areads or srule or links:                    # counted behind the step, on the read set the step returned, while its stream is resident
-        def count_reads(ctx, rs):
-            if areads:
-                got["counts"] = ctx.amplicon_reads(rs, areads[1], areads[2])
-            if srule:                               # (the columns must be known now: the step computed the table's records)
-                got["strand"] = ctx.strand_counts_of(rs, ctx.step_variants())
-            if links:                               # (likewise, while the stream is resident)
-                got["links"] = ctx.link_counts_of(rs, ctx.step_variants(), links[1])
-        if srule or links:
+    want, got = StreamCounts(a), {}
+    if want:                                        # counted behind the step, on the read set the step returned, while its stream is resident
+        if want.lists_records:                      # (the columns must be known then: the step computes the table's records)
             from .io import fasta
-            _state.default_context().set_variants(fasta.read_first_record(a.reference)[1], **variants_of(a))
+            _state.default_context().set_variants(fasta.read_first_record(a.reference)[1], **want.variants)
         try:
-            counts = build_counts(bam, a.reference, on_readset=count_reads,
-                                  need_device="--variant-strand" if srule else "--variant-links" if links else "--amplicon-reads")
+            counts = build_counts(bam, a.reference, on_readset=lambda ctx, rs: got.update(want.count(ctx, rs)), need_device=want.need)
         finally:
-            if srule or links:
+            if want.lists_records:
                 _state.default_context().set_variants()
-        if areads:
-            write_amplicon_reads(a.amplicon_reads, a.samplename, got["counts"], areads[0])
+        if want.areads:
+            write_amplicon_reads(a.amplicon_reads, a.samplename, got["amplicon_reads"], want.areads[0])
     else:
         counts = build_counts(bam, a.reference)     # decoded, packed and tallied on the device
     IndexGff = Gffindex(a.features)
@@ -825,19 +871,13 @@ def _single_sample(a, flt, t):
 
     if a.depth_of_coverage is not None:
         BuildCoverage(indexDict, a.depth_of_coverage)
-    n_variants = n_bias = n_low = 0
-    lstats = link_stats()
+    vparts = []
     if a.variant_table is not None:                 # from the counts the consensus is called from (behind --index-override)
         from .io import fasta
         refID, refseq = fasta.read_first_record(a.reference)
         recs = _state.default_context().variants(indexDict.counts, refseq, **variants_of(a))
-        if srule:                                   # (the writer refuses counts that do not add up to these records)
-            n_bias, n_low = write_variant_strand_table(a.variant_table, [(recs, got["strand"], refID, refseq, 0)], srule)
-        else:
-            write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
-        if links:                                   # (its writer refuses likewise)
-            lstats = write_variant_links(links[0], [(recs, got["links"], refID, refseq, 0)], links)
-        n_variants = len(recs)
+        vparts = [(recs, got.get("variant_strand"), got.get("variant_links"), refID, refseq, 0)]
+    vstats = write_variant_tables(a, vparts, want)
 
     amps, n_below = amplicons_of(a), 0
     if amps:                                        # likewise: the matrix behind the read filter, --min-baseq, --primers and --index-override
@@ -856,10 +896,7 @@ def _single_sample(a, flt, t):
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
-                       "variant_records": n_variants, "variant_strand_bias": n_bias, "variant_strand_low": n_low, **lstats,
-                       "amplicons": len(amps) if amps else 0, "amplicons_below": n_below,
-                       "amplicon_reads_ambiguous": int(got["counts"]["reads"][-2]) if areads else 0,
-                       "amplicon_reads_unassigned": int(got["counts"]["reads"][-1]) if areads else 0,
+                       **vstats, "amplicons": len(amps) if amps else 0, "amplicons_below": n_below, **want.stats(got),
                        "bam_bytes": os.path.getsize(a.input)}, fh)
 
 

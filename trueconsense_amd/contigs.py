@@ -122,7 +122,7 @@ def axis_reference(records, header_names, shift, axis_len):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, amplicon_reads=None, variant_strand=False, variant_links=0):
+                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, on_readset=None, need_device=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
@@ -133,13 +133,9 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     variants = the keyword arguments of Context.set_variants (ref: the reference on the axis, axis_reference): the step also lists
     the variant table's records, which info receives as "variant_table".  intervals = ([(start, end)] on the axis, min_depth)
     (Context.set_intervals): the step also computes the amplicon table's records, which info receives as "amplicon_table".
-    amplicon_reads = ([(fs, le, rs, fe)] on the axis, slack) (Context.amplicon_reads): behind the step the records of the read set are
-    counted per amplicon in the decoded stream, which info receives as "amplicon_reads"; a file the device decoder declines is
-    refused then (reads decoded on the host leave no stream on the device).  variant_strand (with variants): behind the step the
-    planes at the table's distinct columns are counted per strand in the decoded stream (Context.strand_counts), which info
-    receives as "variant_strand"; a file the device decoder declines is refused likewise.  variant_links = K > 0 (with variants):
-    behind the step the joint token classes of the records at every table column and its next K are counted in the decoded stream
-    (Context.link_counts), which info receives as "variant_links"; refused likewise."""
+    on_readset(ctx, read set): called behind the step — info's tables are filled, the layout is still set — while the read set's
+    decoded stream is resident; need_device: the flag on whose behalf a file the device decoder declines is refused then (reads
+    decoded on the host leave no stream on the device), as indexing.build_counts takes them."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
@@ -151,7 +147,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_intervals(*intervals)
     host = None
     try:
-        rs = device_readset(ctx, path, need="--variant-strand" if variant_strand else "--variant-links" if variant_links else "--amplicon-reads" if amplicon_reads else None)    # (the floor it refuses under is the one just set)
+        rs = device_readset(ctx, path, need=need_device)    # (the floor it refuses under is the one just set)
         if rs is None:
             host = BamFile(path, threads=threads, read_filter=read_filter)
             try:
@@ -167,14 +163,10 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
             plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
             if variants and info is not None:
                 info["variant_table"] = ctx.step_variants()
-                if variant_strand:                              # (one call over all contigs' columns on the shifted axis; the stream is still resident)
-                    info["variant_strand"] = ctx.strand_counts_of(rs, info["variant_table"])
-                if variant_links:                               # (likewise; the pairs across two contigs are dropped by the writer's caller)
-                    info["variant_links"] = ctx.link_counts_of(rs, info["variant_table"], variant_links)
             if intervals and info is not None:
                 info["amplicon_table"] = ctx.step_intervals()
-            if amplicon_reads and info is not None:             # (the layout is still set: the read set's shifts are the table's)
-                info["amplicon_reads"] = ctx.amplicon_reads(rs, *amplicon_reads)
+            if on_readset is not None:                          # (the layout is still set: the read set's shifts are the tables')
+                on_readset(ctx, rs)
         finally:
             rs.free()
     finally:
@@ -192,10 +184,9 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (amplicon_intervals, amplicon_reads_of, amplicons_of, primers_of, link_stats, links_of, read_filter_of, strand_of,
-                               variants_of, write_amplicon_reads, write_amplicon_table, write_variant_links, write_variant_strand_table,
-                               write_variant_table)
-    flt, seen = read_filter_of(a), {}
+    from .TrueConsense import (StreamCounts, amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_reads,
+                               write_amplicon_table, write_variant_tables)
+    flt, seen, got = read_filter_of(a), {}, {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
     hdr_names, hdr_lens = bam_header_refs(a.input)
@@ -208,26 +199,18 @@ def run(a):
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
     amps = amplicons_of(a, (hdr_names, shift))      # (each contig's amplicons shifted by its slot; none left: an argument error)
     seen["amplicons"] = len(amps) if amps else 0
-    areads = amplicon_reads_of(a, (hdr_names, shift))           # (likewise, for --amplicon-reads)
+    want = StreamCounts(a, (hdr_names, shift))      # (likewise, for --amplicon-reads; one call each over all contigs' columns on the shifted axis)
     axis_ref = axis_reference(records, hdr_names, shift, axis_len) if a.variant_table is not None else None
     var = dict(variants_of(a), ref=axis_ref) if axis_ref is not None else None
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
                                                                  threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
                                                                  min_baseq=a.min_baseq, primers=prm, variants=var,
                                                                  intervals=(amplicon_intervals(amps), mincov) if amps else None,
-                                                                 amplicon_reads=areads[1:] if areads else None,
-                                                                 variant_strand=strand_of(a) is not None,
-                                                                 variant_links=links_of(a)[1] if links_of(a) else 0)
-    rcounts = seen.pop("amplicon_reads", None)
-    seen["amplicon_reads_ambiguous"] = 0 if rcounts is None else int(rcounts["reads"][-2])
-    seen["amplicon_reads_unassigned"] = 0 if rcounts is None else int(rcounts["reads"][-1])
+                                                                 on_readset=lambda c, rs: got.update(want.count(c, rs, seen.get("variant_table"))),
+                                                                 need_device=want.need)
+    seen.update(want.stats(got))
     seen.setdefault("reads_primer_masked", 0)
-    table = seen.pop("variant_table", None)
-    seen["variant_records"] = 0 if table is None else len(table)
-    strand = seen.pop("variant_strand", None)
-    seen["variant_strand_bias"] = seen["variant_strand_low"] = 0
-    links = seen.pop("variant_links", None)
-    seen.update(link_stats())
+    table, strand, links = seen.pop("variant_table", None), got.get("variant_strand"), got.get("variant_links")
     arecs = seen.pop("amplicon_table", None)
     seen["amplicons_below"] = 0 if arecs is None else int((arecs["below"] > 0).sum())
 
@@ -286,27 +269,16 @@ def run(a):
     if a.depth_of_coverage is not None:
         with open(a.depth_of_coverage, "w") as out:
             out.write("".join(doc))
-    if table is not None:                           # one file, the contigs in axis order; rows carry the contig's name and its own positions
-        parts = []
-        for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]):
-            part = (table[(table["pos"] >= s) & (table["pos"] < s + len(seq))], rid, axis_ref, s)
-            if strand is not None:                  # (each contig's rows with the counts of its own columns)
-                part = part[:1] + (strand[(strand["pos"] >= s) & (strand["pos"] < s + len(seq))],) + part[1:]
-            parts.append(part)
-        if strand is not None:
-            seen["variant_strand_bias"], seen["variant_strand_low"] = write_variant_strand_table(a.variant_table, parts, strand_of(a))
-        else:
-            write_variant_table(a.variant_table, parts)
-        if links is not None:                       # the writer once per contig, with the link counts of its own columns: no pair across two contigs
-            lparts = []
-            for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]):
-                mine = (links["a"] >= s) & (links["a"] < s + len(seq))
-                lparts.append((table[(table["pos"] >= s) & (table["pos"] < s + len(seq))], links[mine], rid, axis_ref, s))
-            seen.update(write_variant_links(links_of(a)[0], lparts, links_of(a)))
+    vparts = []                                     # one file, the contigs in axis order; rows carry the contig's name and its own positions
+    for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]) if table is not None else ():
+        # (each contig's rows with the strand and link counts of its own columns: no pair across two contigs)
+        mine = [None if x is None else x[(x[key] >= s) & (x[key] < s + len(seq))] for x, key in ((table, "pos"), (strand, "pos"), (links, "a"))]
+        vparts.append((*mine, rid, axis_ref, s))
+    seen.update(write_variant_tables(a, vparts, want))
     if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
         write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
-    if rcounts is not None:                         # one file: REGION is each amplicon's contig
-        write_amplicon_reads(a.amplicon_reads, name, rcounts, areads[0])
+    if want.areads:                                 # one file: REGION is each amplicon's contig
+        write_amplicon_reads(a.amplicon_reads, name, got["amplicon_reads"], want.areads[0])
     with open(a.output, "w") as out:
         out.write("".join(fa))
     return dict({"contigs": len(records), "dropped_reads": int(dropped)}, **seen)

@@ -364,6 +364,50 @@ def _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks):
     return ">%s mincov=%d\n%s\n" % (name, int(mincov), cons)
 
 
+def _agree(err, group, multi):
+    """Every rank's err = (code, text) or None -> the first rank's that has one, or None: the same answer on every rank, so that all
+    raise or all go on into the next collective together.  Not multi: err itself."""
+    if not multi:
+        return err
+    import torch.distributed as dist
+    allv = [None] * dist.get_world_size(group)
+    dist.all_gather_object(allv, err, group=group)
+    return next((v for v in allv if v), None)
+
+
+def _sum_to_root(what, count, group, multi):
+    """A count behind the step: count() -> this rank's contiguous 2-D integer array (or TcmiError); nobody enters the reduce unless
+    everybody has counts — else every rank raises TcmiError "consensus_split_bamfile: <what>: ..." with the first failing rank's code
+    and words —; then one sum to rank 0 over the group (on the device under "nccl", on the host otherwise; nothing to sum for an empty
+    array).  -> the array: on rank 0 the sum."""
+    mine, err = None, None
+    try:
+        mine = count()
+    except TcmiError as e:
+        err = (e.code, str(e))
+    err = _agree(err, group, multi)
+    if err is not None:
+        raise TcmiError(err[0], "consensus_split_bamfile: %s: %s" % (what, err[1]))
+    if multi and mine.size:
+        import torch
+        import torch.distributed as dist
+        tr = torch.from_numpy(mine).cuda() if dist.get_backend(group) == "nccl" else torch.from_numpy(mine)
+        dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
+        mine = tr.cpu().numpy()
+    return mine
+
+
+def _root_columns(ctx, counts_root, variants, root, group, multi):
+    """Rank 0 lists the variant table's records from the reduced matrix (variants: the keyword arguments of Context.variants) and
+    everybody gets their distinct columns -> (records, None on the other ranks; int64 columns, ascending)."""
+    import torch.distributed as dist
+    recs = ctx.variants(counts_root, **variants) if root else None
+    cols = [np.unique(recs["pos"].astype(np.int64)).tolist() if root else None]
+    if multi:
+        dist.broadcast_object_list(cols, src=0, group=group)
+    return recs, np.asarray(cols[0], np.int64)
+
+
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
                             step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
                             min_baseq=None, primers=None, amplicon_reads=None, variant_strand=None, variant_links=None):
@@ -394,17 +438,13 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     step 3), and rank 0's host sweep of step 4 removes the failing records too.  min_baseq: the base-quality floor of the count
     matrix, on every rank's context (Context.set_min_base_quality; 0 sets no floor, None leaves what the context has); the insert
     tokens keep their own quality rule.  primers = (rows, slack): the primer table of the count matrix, on every rank's context
-    likewise (Context.set_primers; no rows clears it, None leaves what the context has).  amplicon_reads = ([(fs, le, rs, fe)], slack):
-    behind the step every rank counts the records of its own read set per amplicon (Context.amplicon_reads) and the [n + 2, 2] int64
-    counts are summed to rank 0 over the same group — a record starts in exactly one rank's blocks, so the sum is the file's; with
-    return_parts rank 0's tuple then has them as a fourth item.  variant_strand = the keyword arguments of Context.variants (ref,
-    min_af, min_alt_depth, min_depth): behind that, rank 0 lists the variant table's records from the reduced matrix and broadcasts
-    their distinct columns, every rank counts the planes at those columns per strand in its own read set (Context.strand_counts), the
-    ranks agree that everybody has counts, and the [n, 14] int32 counts are summed to rank 0 likewise; with return_parts rank 0's
-    tuple then has (records, strand counts).  variant_links = (the same keyword arguments, K): likewise every rank counts the joint
-    token classes of its own records at the root's columns and their next K (Context.link_counts) and the [n * K, 49] int32 counts are
-    summed to rank 0 — a record is one rank's, so the sum is the file's; with return_parts rank 0's tuple then ends with (records, link
-    counts)."""
+    likewise (Context.set_primers; no rows clears it, None leaves what the context has).  Three counts behind the step, each taken by
+    every rank in its own read set and summed to rank 0 over the same group (_sum_to_root), each one more item of rank 0's return_parts
+    tuple, in this order: amplicon_reads = ([(fs, le, rs, fe)], slack): the records per amplicon (Context.amplicon_reads) -> the
+    [n + 2, 2] int64 counts; variant_strand = the keyword arguments of Context.variants (ref, min_af, min_alt_depth, min_depth): rank 0
+    lists the variant table's records from the reduced matrix and broadcasts their distinct columns (_root_columns), the planes at those
+    columns per strand (Context.strand_counts) -> (records, strand counts); variant_links = (the same keyword arguments, K): the joint
+    token classes at the root's columns and their next K (Context.link_counts) -> (records, link counts)."""
     import time
     import torch
     import torch.distributed as dist
@@ -477,90 +517,41 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
             timings["step"] = time.perf_counter() - t0
         t1 = time.perf_counter()
         # every rank learns whether the step held everywhere (a failed rank took part in the reduce: no deadlock, but no consensus either)
-        verdict = [err]
-        if multi:
-            allv = [None] * dist.get_world_size(group)
-            dist.all_gather_object(allv, err, group=group)
-            verdict = allv
-        bad = [v for v in verdict if v]
-        if bad:
-            raise TcmiError(bad[0][0], "consensus_split_bamfile: %s" % bad[0][1])
-        if amplicon_reads is not None:                               # reads per amplicon: every rank its own records, one sum to rank 0
-            mine, aerr = None, None
-            try:
+        err = _agree(err, group, multi)
+        if err:
+            raise TcmiError(err[0], "consensus_split_bamfile: %s" % err[1])
+        # behind the step: every rank counts in its own records, one sum to rank 0 (a record starts in one rank's blocks: the sum is the file's)
+        if amplicon_reads is not None:
+            def count():
                 got = ctx.amplicon_reads(rs, *amplicon_reads)
-                mine = np.ascontiguousarray(np.stack([got["reads"], got["full"]], axis=1))
-            except TcmiError as e:
-                aerr = (e.code, str(e))
-            if multi:                                                # nobody enters the reduce unless everybody has counts
-                alla = [None] * dist.get_world_size(group)
-                dist.all_gather_object(alla, aerr, group=group)
-                aerr = next((v for v in alla if v), None)
-            if aerr is not None:
-                raise TcmiError(aerr[0], "consensus_split_bamfile: amplicon reads: %s" % aerr[1])
-            if multi:
-                on_gpu = dist.get_backend(group) == "nccl"
-                tr = torch.from_numpy(mine).cuda() if on_gpu else torch.from_numpy(mine)
-                dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
-                mine = tr.cpu().numpy()
+                return np.ascontiguousarray(np.stack([got["reads"], got["full"]], axis=1))
+            mine = _sum_to_root("amplicon reads", count, group, multi)
             reads_root = mine if root else None
-        if variant_strand is not None:                               # strand counts at the table's columns: every rank its own records, one sum to rank 0
+        if variant_strand is not None:
             from .engine import STRAND_DTYPE
-            vrecs = ctx.variants(counts_root, **variant_strand) if root else None
-            vcols = [np.unique(vrecs["pos"].astype(np.int64)).tolist() if root else None]
-            if multi:
-                dist.broadcast_object_list(vcols, src=0, group=group)
-            vcols = np.asarray(vcols[0], np.int64)
-            mine, serr = None, None
-            try:
+            vrecs, vcols = _root_columns(ctx, counts_root, variant_strand, root, group, multi)
+
+            def count():
                 got = ctx.strand_counts_of(rs, cols=vcols)
-                mine = np.ascontiguousarray(np.concatenate([got["fwd"], got["rev"]], axis=1).reshape(len(vcols), 14))
-            except TcmiError as e:
-                serr = (e.code, str(e))
-            if multi:                                                # nobody enters the reduce unless everybody has counts
-                alls = [None] * dist.get_world_size(group)
-                dist.all_gather_object(alls, serr, group=group)
-                serr = next((v for v in alls if v), None)
-            if serr is not None:
-                raise TcmiError(serr[0], "consensus_split_bamfile: strand counts: %s" % serr[1])
-            if multi and len(vcols):
-                on_gpu = dist.get_backend(group) == "nccl"
-                tr = torch.from_numpy(mine).cuda() if on_gpu else torch.from_numpy(mine)
-                dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
-                mine = tr.cpu().numpy()
+                return np.ascontiguousarray(np.concatenate([got["fwd"], got["rev"]], axis=1).reshape(len(vcols), 14))
+            mine = _sum_to_root("strand counts", count, group, multi)
             if root:
                 strand = np.zeros(len(vcols), STRAND_DTYPE)
                 strand["fwd"], strand["rev"], strand["pos"] = mine[:, :7], mine[:, 7:], vcols
                 strand_root = (vrecs, strand)
-        if variant_links is not None:                                # link counts at the table's columns: every rank its own records, one sum to rank 0
+        if variant_links is not None:
             from .engine import LINK_DTYPE
-            lkw, lk = variant_links
-            vrecs = ctx.variants(counts_root, **lkw) if root else None
-            vcols = [np.unique(vrecs["pos"].astype(np.int64)).tolist() if root else None]
-            if multi:
-                dist.broadcast_object_list(vcols, src=0, group=group)
-            vcols = np.asarray(vcols[0], np.int64)
-            got, lerr = None, None
-            try:
-                got = ctx.link_counts(rs, vcols, lk) if len(vcols) else np.zeros(0, LINK_DTYPE)
-            except TcmiError as e:
-                lerr = (e.code, str(e))
-            if multi:                                                # nobody enters the reduce unless everybody has counts
-                alll = [None] * dist.get_world_size(group)
-                dist.all_gather_object(alll, lerr, group=group)
-                lerr = next((v for v in alll if v), None)
-            if lerr is not None:
-                raise TcmiError(lerr[0], "consensus_split_bamfile: link counts: %s" % lerr[1])
-            mine = np.ascontiguousarray(got["j"].reshape(len(got), 49))
-            if multi and len(vcols):
-                on_gpu = dist.get_backend(group) == "nccl"
-                tr = torch.from_numpy(mine).cuda() if on_gpu else torch.from_numpy(mine)
-                dist.reduce(tr, dst=0, op=dist.ReduceOp.SUM, group=group)
-                mine = tr.cpu().numpy()
+            vrecs, vcols = _root_columns(ctx, counts_root, variant_links[0], root, group, multi)
+            got = []                                                 # (a and b are the same on every rank: the columns are the root's)
+
+            def count():
+                got.append(ctx.link_counts(rs, vcols, variant_links[1]) if len(vcols) else np.zeros(0, LINK_DTYPE))
+                return np.ascontiguousarray(got[0]["j"].reshape(len(got[0]), 49))
+            mine = _sum_to_root("link counts", count, group, multi)
             if root:
-                got = got.copy()                                     # (a and b are the same on every rank: the columns are the root's)
-                got["j"] = mine.reshape(len(got), 7, 7)
-                links_root = (vrecs, got)
+                links = got[0].copy()
+                links["j"] = mine.reshape(len(links), 7, 7)
+                links_root = (vrecs, links)
         # the insert-candidate columns, from rank 0 to everybody
         cand = [(np.nonzero(flags & 8)[0] + 1).tolist()] if root else [None]
         if multi:
@@ -575,10 +566,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
             except TcmiError as e:                                   # e.g. TCMI_E_UNSUPPORTED: a read of more than 512 positions in this rank's range
                 perr = (e.code, str(e))
             pieces = [piece]
-            if multi:                                                # nobody enters the gather unless everybody has a piece
-                allp = [None] * dist.get_world_size(group)
-                dist.all_gather_object(allp, perr, group=group)
-                perr = next((v for v in allp if v), None)
+            perr = _agree(perr, group, multi)                        # nobody enters the gather unless everybody has a piece
             if perr is not None:
                 if perr[0] != _ffi_E_UNSUPPORTED:
                     raise TcmiError(perr[0], "consensus_split_bamfile: insert entries: %s" % perr[1])

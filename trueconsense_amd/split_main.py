@@ -28,9 +28,8 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import (GetArgs, amplicon_intervals, amplicon_reads_of, amplicons_of, links_of, primers_of, read_filter_of, strand_of,
-                               variants_of, write_amplicon_reads, write_amplicon_table, write_variant_links, write_variant_strand_table,
-                               write_variant_table)
+    from .TrueConsense import (GetArgs, StreamCounts, amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of,
+                               write_amplicon_reads, write_amplicon_table, write_variant_tables)
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
     torch.cuda.set_device(device)
@@ -51,30 +50,22 @@ def main(argv=None):
         gffdict = IndexGff.index_dict(seqid=a.samplename)
         rows = [{"start": int(r["start"]), "end": int(r["end"]), "strand": r.get("strand")} for r in gffdict.values()]
         refID, refseq = fasta.read_first_record(a.reference)
-        srule, links = strand_of(a), links_of(a)
-        areads = amplicon_reads_of(a)                                # (an unusable scheme ends every rank here, before the step)
+        want = StreamCounts(a)                                       # (an unusable scheme ends every rank here, before the step)
         parts = td.consensus_split_bamfile(a.input, len(refseq), rows, a.coverage_level, a.noambiguity is False, a.samplename, rank, world,
                                            device=device, return_parts=True, rccl_user=user, read_filter=read_filter_of(a), min_baseq=a.min_baseq,
-                                           primers=primers_of(a), amplicon_reads=areads[1:] if areads else None,
-                                           variant_strand=dict(variants_of(a), ref=refseq) if srule else None,
-                                           variant_links=(dict(variants_of(a), ref=refseq), links[1]) if links else None)
+                                           primers=primers_of(a), **want.split_kwargs(refseq))
         if rank == 0:
             _, counts, toks = parts[:3]
-            if areads:                                               # (the ranks' counts, summed: a record starts in one rank's blocks)
-                write_amplicon_reads(a.amplicon_reads, a.samplename, parts[3], areads[0])
+            got, recs = want.from_parts(parts)                       # (the ranks' counts, summed: a record starts in one rank's blocks)
+            if want.areads:
+                write_amplicon_reads(a.amplicon_reads, a.samplename, got["amplicon_reads"], want.areads[0])
             index = _state.IndexDict(counts)
             if a.depth_of_coverage is not None:
                 BuildCoverage(index, a.depth_of_coverage)
             if a.variant_table is not None:                          # (from the reduced counts, as the single-GPU command line from its own)
-                if srule:                                            # (the records the root listed behind the reduce, the ranks' strand counts summed)
-                    recs, strand = parts[-2 if links else -1]
-                    write_variant_strand_table(a.variant_table, [(recs, strand, refID, refseq, 0)], srule)
-                else:
+                if recs is None:                                     # (else the records the root listed behind the reduce, for the ranks' counts)
                     recs = _state.default_context().variants(index.counts, refseq, **variants_of(a))
-                    write_variant_table(a.variant_table, [(recs, refID, refseq, 0)])
-                if links:                                            # (likewise the ranks' link counts, summed)
-                    lrecs, lcounts = parts[-1]
-                    write_variant_links(links[0], [(lrecs, lcounts, refID, refseq, 0)], links)
+                write_variant_tables(a, [(recs, got.get("variant_strand"), got.get("variant_links"), refID, refseq, 0)], want)
             amps = amplicons_of(a)
             if amps:                                                 # (likewise the amplicon table)
                 arecs = _state.default_context().interval_stats(index.counts, amplicon_intervals(amps), a.coverage_level)
