@@ -224,6 +224,32 @@ def test_many_lanes_on_one_counter(ctx, tmp_path):
             assert not ly.invariant(got, k, matrix)
 
 
+# ---- 4b. the join's worst case ---------------------------------------------------------------------------------------------------------
+def test_a_wavefront_on_64_columns_and_a_ragged_one_behind_it(ctx, tmp_path):
+    """test_strand_counts.one_column_a_record: 64 records of one wavefront on 64 columns of their own (64 distinct counters a round),
+    a 65th on record 0's columns in a second, ragged wavefront; one queried column per record with one neighbour, staged, and the same
+    query padded past the LDS capacity with columns beyond every read, counted in memory"""
+    specs, cols = sc.one_column_a_record()
+    rd = rf.arrays(specs)
+    n_pos = len(py.counts(rd, L)[0])
+    cls = ly.classes(rd, L, n_pos=n_pos)
+    padded = cols + [n_pos + 700 + j for j in range(LDS + 1 - len(cols))]
+    assert len(specs) == 65 and len(cols) == 64 <= LDS < len(padded) and cols[-1] < n_pos
+    want = ly.joint(cls, padded, 1)
+    # every record has a token at its one column and none at the neighbours: [x][0] of its pair, [0][x] of the pair in front
+    assert want[0].sum() == 3 and want[1:63].sum((1, 2)).tolist() == [2] * 62 and want[63].sum() == 1 and not want[64:].any()
+    assert not want[:, 1:, 1:].any()
+    path = ff.write(tmp_path, specs)
+    with uploaded(ctx, path) as rs:
+        assert rs.n_reads == 65 and rs.n_piled == 65
+        matrix = ctx.step(rs, n_pos, 0, True)[3]
+        for route, q in (("LDS", cols), ("memory", padded)):
+            got = device_links(ctx, rs, q, 1)
+            msg = differ(got, ly.joint(cls, q, 1), ("one column a record", route))
+            assert not msg, msg
+            assert np.array_equal(got["j"][:63], want[:63]) and not ly.invariant(got, 1, matrix)
+
+
 # ---- 5. hand-made records --------------------------------------------------------------------------------------------------------------
 HL = 400
 A_COL, B_COL = 100, 130

@@ -241,6 +241,41 @@ def test_many_lanes_on_one_counter(ctx, tmp_path):
             assert np.array_equal(got[0] + got[1], matrix[cols])
 
 
+# ---- 5b. the join's worst case ---------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def one_column_a_record():
+    """-> (specs, cols): 65 kept records, 6 all-match bases each.  Record r < 64 starts at column 100 + 10 r, so no two of them share
+    a column: the first wavefront holds 64 distinct counters a round, one pass of the join per lane.  Record 64 lies on record 0's
+    columns, on the other strand, alone in a second, ragged wavefront.  cols: one queried column per record (also used by
+    test_link_counts)"""
+    def rec(r, pos, flag):
+        return {"pos": pos, "flag": flag, "cigar": "6M", "seq": "ACGT"[r % 4] * 6, "name": "j%d" % r, "tid": 0, "qual": 30, "mapq": 60}
+    specs = [rec(r, 100 + 10 * r, 16 if r % 3 == 0 else 0) for r in range(64)] + [rec(64, 100, 0)]
+    return specs, [100 + 10 * r + r % 6 for r in range(64)]
+
+
+def test_a_wavefront_on_64_columns_and_a_ragged_one_behind_it(ctx, tmp_path):
+    """the records of one_column_a_record at one column per record, staged; and the same query padded past the LDS capacity with
+    columns beyond every read, counted in memory"""
+    specs, cols = one_column_a_record()
+    rd = rf.arrays(specs)
+    n_pos = len(py.counts(rd, L)[0])
+    padded = cols + [n_pos + 700 + j for j in range(LDS + 1 - len(cols))]
+    assert len(specs) == 65 and len(cols) == 64 <= LDS < len(padded) and cols[-1] < n_pos
+    want = sy.counts(rd, padded, L)
+    cov = (want[0] + want[1])[:, 0].tolist()
+    assert cov == [2] + [1] * 63 + [0] * (len(padded) - 64) and want[0][0, 0] == 1 and want[1][0, 0] == 1, cov
+    path = ff.write(tmp_path, specs)
+    with uploaded(ctx, path) as rs:
+        assert rs.n_reads == 65 and rs.n_piled == 65
+        matrix = ctx.step(rs, n_pos, 0, True)[3]
+        for route, q in (("LDS", cols), ("memory", padded)):
+            got = device_counts(ctx, rs, q)
+            msg = differ(got, (want[0][:len(q)], want[1][:len(q)]), q, ("one column a record", route))
+            assert not msg, msg
+            assert np.array_equal((got[0] + got[1])[:64], matrix[cols]) and not got[0][64:].any() and not got[1][64:].any()
+
+
 # ---- 6. a contig layout ----------------------------------------------------------------------------------------------------------------
 def test_two_contigs_under_a_layout(ctx, tmp_path):
     """columns in both slots and one in the guard between them; each contig under its own table, floor 13 and the read filter"""

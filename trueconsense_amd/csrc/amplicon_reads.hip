@@ -13,9 +13,8 @@
 //                the lookup: a binary search over the widened starts and three more words.
 //   the table    staged in LDS while n <= TCMI_AMPLICON_READS_LDS; a larger one is searched where it lies (L2).
 //   counters     a sorted BAM puts a wavefront's 64 reads into one or two amplicons: the lanes that hit the same counter are joined
-//                first (a ballot loop over the distinct ids: one pass per id the wavefront holds), and one lane adds the popcount —
-//                to the workgroup's counters in LDS while the table is staged, else straight to memory.  At its end a workgroup
-//                hands every non-zero LDS counter to memory with one atomic add.
+//                first (pack_device.h's wave_join), and the group's leader adds two popcounts, `reads` and, when any, `full` — through
+//                the workgroup's counter frame (stream_count.h's CountFrame: LDS while the table is staged, else memory).
 // The sums are integers: their order does not matter and every run gives the same numbers.  The stream is only read.
 #include <vector>
 
@@ -51,46 +50,26 @@ __global__ __launch_bounds__(BLOCK) void amplicon_reads_kernel(ArArgs a)
     __shared__ int32_t s_tab[TCMI_AR_WORDS * LDS_N];
     __shared__ uint32_t s_cnt[2 * (LDS_N + 2)];
     const int tid = threadIdx.x, lane = tid & 63;
-    const bool staged = a.n <= LDS_N;                       // (uniform)
+    const CountFrame<unsigned long long> cnt = {s_cnt, a.counts, a.n <= LDS_N};
     const int n_cnt = 2 * (a.n + 2);
-    if (staged) {
+    if (cnt.staged) {
         for (int k = tid; k < TCMI_AR_WORDS * a.n; k += BLOCK) s_tab[k] = a.table[k];
-        for (int k = tid; k < n_cnt; k += BLOCK) s_cnt[k] = 0u;
+        cnt.zero(n_cnt);
         __syncthreads();
     }
-    const tcmi_ar_table tab = tcmi_ar_view(staged ? s_tab : a.table, a.n);
-    // (the bound is uniform over the workgroup: every lane of a wavefront takes part in every ballot)
-    for (int64_t base = (int64_t)blockIdx.x * BLOCK; base < a.src.n; base += (int64_t)gridDim.x * BLOCK) {
-        const int64_t i = base + tid;
+    const tcmi_ar_table tab = tcmi_ar_view(cnt.staged ? s_tab : a.table, a.n);
+    each_record(a.src.n, [&](int64_t i) {
         bool full = false;
         const int32_t slot = i < a.src.n ? slot_of(a, tab, i, &full) : -1;
-        bool todo = slot >= 0;
-        for (;;) {                                          // one pass per distinct counter the wavefront's reads hit
-            const unsigned long long m = __ballot(todo);
-            if (!m) break;
-            const int lead = (int)__builtin_ctzll(m);
-            const int32_t ls = __shfl(slot, lead, 64);
-            const bool same = todo && slot == ls;
+        wave_join(slot >= 0, slot, [&](int lead, int32_t ls, bool same) {   // one pass per distinct counter the wavefront's reads hit
             const unsigned long long ms = __ballot(same), mf = __ballot(same && full);
             if (lane == lead) {
-                if (staged) {
-                    atomicAdd(&s_cnt[2 * ls], (uint32_t)__popcll(ms));
-                    if (mf) atomicAdd(&s_cnt[2 * ls + 1], (uint32_t)__popcll(mf));
-                } else {
-                    atomicAdd(&a.counts[2 * (int64_t)ls], (unsigned long long)__popcll(ms));
-                    if (mf) atomicAdd(&a.counts[2 * (int64_t)ls + 1], (unsigned long long)__popcll(mf));
-                }
+                cnt.add(2 * (int64_t)ls, __popcll(ms));
+                if (mf) cnt.add(2 * (int64_t)ls + 1, __popcll(mf));
             }
-            if (same) todo = false;
-        }
-    }
-    if (staged) {
-        __syncthreads();
-        for (int k = tid; k < n_cnt; k += BLOCK) {
-            const uint32_t c = s_cnt[k];
-            if (c) atomicAdd(&a.counts[k], (unsigned long long)c);
-        }
-    }
+        });
+    });
+    cnt.flush(n_cnt);
 }
 
 } // namespace
@@ -109,17 +88,11 @@ extern "C" int tcmi_readset_amplicon_reads(tcmi_ctx *ctx, const tcmi_readset *rs
     }
     if (tcmi_amplicon_reads_build(n, fs, le, rs_, fe, slack, table.data(), msg, sizeof msg)) return tcmi_fail(ctx, TCMI_E_ARG, "amplicon reads: %s", msg);
     // the compiled table (6 n words) in, {reads, full} of n + 2 slots out
-    const int rc = tcmi_stream_count_parts(
-        ctx, rs, "amplicon reads", table.data(), table.size() * 4, sums.size() * 8,
-        [n](tcmi_ctx *cx, const tcmi_readset *, const PackSrc &src, const char *d_in, char *d_cnt, unsigned grid) {
-            const ArArgs a = {src, reinterpret_cast<const int32_t *>(d_in), reinterpret_cast<unsigned long long *>(d_cnt), (int32_t)n};
-            tcmi_prof_begin(cx, TCMI_K_AMPLICON_READS);
+    const int rc = tcmi_stream_count_parts<unsigned long long>(
+        ctx, rs, "amplicon reads", TCMI_K_AMPLICON_READS, table.data(), table.size() * 4, sums,
+        [n](tcmi_ctx *cx, const tcmi_readset *, const PackSrc &src, const char *d_in, unsigned long long *d_cnt, unsigned grid) {
+            const ArArgs a = {src, reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n};
             hipLaunchKernelGGL(amplicon_reads_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
-            tcmi_prof_end(cx, TCMI_K_AMPLICON_READS);
-        },
-        [s = sums.data(), m = sums.size()](const char *counts) {
-            const int64_t *got = reinterpret_cast<const int64_t *>(counts);
-            for (size_t k = 0; k < m; ++k) s[k] += got[k];
         });
     if (rc) return rc;
     for (int64_t i = 0; i < n + 2; ++i) { records[i].reads = sums[(size_t)(2 * i)]; records[i].full = sums[(size_t)(2 * i + 1)]; }

@@ -23,9 +23,9 @@
 //                zero).  Behind the last queried column <= q the lane goes on over up to K more columns with t = 0 (while ci < n and
 //                the register is not zero): the pairs whose second column lies beyond the record get their [x][0].
 //   counters     a sorted BAM puts a wavefront's 64 records on the same few pairs and most of them on one class pair: per round and d
-//                the lanes with the same (pair, prev, t) are joined by a ballot loop over the distinct keys and one lane adds the
-//                popcount — to the workgroup's counters in LDS while n * K <= TCMI_LINKS_LDS, else to memory.  At its end a workgroup
-//                hands every non-zero LDS counter to memory with one atomic add.
+//                the lanes with the same (pair, prev, t) are joined (pack_device.h's wave_join) and the group's leader adds the
+//                popcount — through the workgroup's counter frame (stream_count.h's CountFrame: LDS while n * K <= TCMI_LINKS_LDS,
+//                else memory).
 // The sums are integers: their order does not matter and every run gives the same numbers.  The stream is only read.
 #include <vector>
 
@@ -66,18 +66,16 @@ __global__ __launch_bounds__(BLOCK) void link_counts_kernel(LcArgs a)
     const int tid = threadIdx.x, lane = tid & 63;
     const int K = a.K;
     const int n_cnt = NJ * a.n * K;                         // (n * K <= 2^17: below 2^23)
-    const bool staged = a.n * K <= LDS_P;                   // (uniform)
-    if (staged) {
+    const CountFrame<int32_t> cnt = {s_cnt, a.counts, a.n * K <= LDS_P};
+    if (cnt.staged) {
         for (int k = tid; k < a.n; k += BLOCK) s_cols[k] = a.cols[k];
-        for (int k = tid; k < n_cnt; k += BLOCK) s_cnt[k] = 0u;
+        cnt.zero(n_cnt);
         __syncthreads();
     }
-    const int32_t *cols = staged ? s_cols : a.cols;
+    const int32_t *cols = cnt.staged ? s_cols : a.cols;
     const uint32_t Q = a.src.min_bq;
     const uint32_t keep = (1u << (4 * K)) - 1u;             // the K <= 7 nibbles the register holds
-    // (the bound is uniform over the workgroup: every lane of a wavefront takes part in every ballot)
-    for (int64_t base = (int64_t)blockIdx.x * BLOCK; base < a.src.n; base += (int64_t)gridDim.x * BLOCK) {
-        const int64_t i = base + tid;
+    each_record(a.src.n, [&](int64_t i) {
         Walk w;
         int32_t ci = 0;
         bool have = i < a.src.n && open_walk(a.src, a.pt, i, w);
@@ -90,23 +88,14 @@ __global__ __launch_bounds__(BLOCK) void link_counts_kernel(LcArgs a)
         bool live = have;
         while (__ballot(live)) {                            // one round per column of the wavefront's busiest record
             const uint32_t t = have ? class_of(token_at(w, cols[ci], Q)) : 0u;
-            for (int d = 1; d <= K; ++d) {
+            for (int d = 1; d <= K; ++d) {                  // (K is uniform)
                 const uint32_t prev = (hist >> (4 * (d - 1))) & 15u;
-                bool todo = live && ci >= d && (prev | t) != 0u;
-                const uint32_t key = (uint32_t)(((ci - d) * K + d - 1) * NJ) + prev * NC + t;     // (only read when todo)
-                for (;;) {                                  // one pass per distinct (pair, prev, t)
-                    const unsigned long long m = __ballot(todo);
-                    if (!m) break;
-                    const int lead = (int)__builtin_ctzll(m);
-                    const uint32_t lk = __shfl(key, lead, 64);
-                    const bool same = todo && key == lk;
+                const uint32_t key = (uint32_t)(((ci - d) * K + d - 1) * NJ) + prev * NC + t;     // (only read by a lane that counts)
+                // one pass per distinct (pair, prev, t)
+                wave_join(live && ci >= d && (prev | t) != 0u, key, [&](int lead, uint32_t lk, bool same) {
                     const unsigned long long ms = __ballot(same);
-                    if (lane == lead) {
-                        if (staged) atomicAdd(&s_cnt[lk], (uint32_t)__popcll(ms));
-                        else atomicAdd(&a.counts[lk], (int32_t)__popcll(ms));
-                    }
-                    if (same) todo = false;
-                }
+                    if (lane == lead) cnt.add(lk, __popcll(ms));
+                });
             }
             if (live) {
                 hist = ((hist << 4) | t) & keep;
@@ -118,14 +107,8 @@ __global__ __launch_bounds__(BLOCK) void link_counts_kernel(LcArgs a)
                 live = have || (tail > 0 && ci < a.n && hist != 0u);
             }
         }
-    }
-    if (staged) {
-        __syncthreads();
-        for (int k = tid; k < n_cnt; k += BLOCK) {
-            const uint32_t c = s_cnt[k];
-            if (c) atomicAdd(&a.counts[k], (int32_t)c);
-        }
-    }
+    });
+    cnt.flush(n_cnt);
 }
 
 } // namespace
@@ -137,34 +120,21 @@ extern "C" int tcmi_readset_link_counts(tcmi_ctx *ctx, const tcmi_readset *rs, i
     if (n < 1 || n * k > MAX_PAIRS)
         return tcmi_fail(ctx, TCMI_E_ARG, "link counts: %lld columns with %d neighbours each: 1..131072 pairs are allowed", (long long)n, (int)k);
     if (!cols || !records) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
-    for (int64_t i = 0; i < n; ++i) {
-        if (cols[i] < 0 || cols[i] >= WALK_MAX_COL)
-            return tcmi_fail(ctx, TCMI_E_ARG, "link counts: column %lld (%lld) lies outside [0, 2^29)", (long long)i, (long long)cols[i]);
-        if (i && cols[i] <= cols[i - 1])
-            return tcmi_fail(ctx, TCMI_E_ARG, "link counts: the columns are not strictly ascending at index %lld (%lld after %lld)", (long long)i,
-                             (long long)cols[i], (long long)cols[i - 1]);
-    }
     const size_t n_pairs = (size_t)n * (size_t)k;
     std::vector<int32_t> c32;
     std::vector<int64_t> sums;
+    if (const int rc = tcmi_count_columns(ctx, "link counts", n, cols, c32)) return rc;
     try {
-        c32.assign(cols, cols + n);
         sums.assign((size_t)NJ * n_pairs, 0);
     } catch (...) {                                         // (no exception may cross the C ABI)
         return tcmi_fail(ctx, TCMI_E_NOMEM, "link counts: no host memory for %lld columns", (long long)n);
     }
     // the columns (int32) in, [n * K][49] int32 counters out; the primer table is the one each part was built under
-    const int rc = tcmi_stream_count_parts(
-        ctx, rs, "link counts", c32.data(), c32.size() * 4, sums.size() * 4,
-        [n, k](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, char *d_cnt, unsigned grid) {
-            const LcArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), reinterpret_cast<int32_t *>(d_cnt), (int32_t)n, k};
-            tcmi_prof_begin(cx, TCMI_K_LINK_COUNTS);
+    const int rc = tcmi_stream_count_parts<int32_t>(
+        ctx, rs, "link counts", TCMI_K_LINK_COUNTS, c32.data(), c32.size() * 4, sums,
+        [n, k](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, int32_t *d_cnt, unsigned grid) {
+            const LcArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n, k};
             hipLaunchKernelGGL(link_counts_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
-            tcmi_prof_end(cx, TCMI_K_LINK_COUNTS);
-        },
-        [s = sums.data(), m = sums.size()](const char *counts) {
-            const int32_t *got = reinterpret_cast<const int32_t *>(counts);
-            for (size_t j = 0; j < m; ++j) s[j] += got[j];
         });
     if (rc) return rc;
     for (int64_t i = 0; i < n; ++i) {

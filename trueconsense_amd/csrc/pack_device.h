@@ -1,7 +1,8 @@
 // pack_device.h — DEVICE (.hip files only): one read as every kernel that goes to the reads themselves sees it, whether it lies in the
 // flat arrays of struct tcmi_reads or in the inflated BAM stream (SAM spec §4.2) — the packers (pack_device.hip), the insert-candidate
 // kernels (ins_entries.hip), the long-read tally (tally.hip: tally_stream_kernel) and the counting kernels (amplicon_reads.hip,
-// strand_counts.hip; their host side: stream_count.h).  What only the packers use stays in pack_device.hip.
+// strand_counts.hip, link_counts.hip; their host side and their frame: stream_count.h) — and the wave join, which the packer uses too.
+// What only the packers use stays in pack_device.hip.
 #pragma once
 #include "tcmi_internal.h"
 
@@ -144,7 +145,30 @@ __device__ inline bool ins_after(const uint8_t *cg, uint32_t n, uint32_t k)
     return tot > 0;
 }
 
-// ---- what the kernels that walk the records where they lie share (tally.hip: tally_stream_kernel; amplicon_reads.hip; strand_counts.hip) ----
+// ---- THE wave join ------------------------------------------------------------------------------------------------------------------
+// The lanes of a wavefront whose `todo` is set, grouped by equal key: per distinct key ONE call f(lead, lk, same) — lead the group's
+// lowest lane, lk its key, same whether this lane is of the group — that every lane of the wavefront makes together, so f may ballot and
+// shuffle; what it adds or stores, it does on lane `lead` alone.  One pass per distinct key: a sorted BAM puts a wavefront's 64 records
+// on one or two.  THE RULE: every lane of the wavefront calls wave_join, with todo = false when it has nothing — the ballots and the
+// shuffle see all 64 lanes; so the loop around a call has a bound that is uniform over the wavefront.
+template <class K, class F> __device__ inline void wave_join(bool todo, K key, F f)
+{
+    for (;;) {
+        const unsigned long long m = __ballot(todo);
+        if (!m) break;
+        const int lead = (int)__builtin_ctzll(m);
+        const K lk = __shfl(key, lead, 64);
+        const bool same = todo && key == lk;
+        f(lead, lk, same);
+        if (same) todo = false;
+    }
+}
+
+// ---- what the kernels that walk the records where they lie share (tally.hip: tally_stream_kernel; amplicon_reads.hip; strand_counts.hip;
+// link_counts.hip) ----
+// the columns of the one axis lie in [0, 2^29): what a counting call can be asked for (stream_count.h) and where a walk ends (stream_walk.h)
+constexpr int64_t WALK_MAX_COL = 1 << 29;
+
 // the reference span of a read: the sum of its reference-consuming ops (unaligned dword loads, no base is read)
 __device__ inline int64_t ref_span(const ReadView &v)
 {

@@ -140,19 +140,12 @@ __device__ inline int32_t slot_end_of(const PackSrc &s, int32_t tid) { return s.
 // wavefront holds reads of (one or two in a sorted file)
 __device__ inline void ref_extent_max(int32_t *ext, int32_t t, int32_t e)
 {
-    bool todo = t >= 0 && e > 0;
-    for (;;) {
-        const unsigned long long m = __ballot(todo);
-        if (!m) break;
-        const int lead = (int)__builtin_ctzll(m);
-        const int32_t lt = __shfl(t, lead, 64);
-        const bool same = todo && t == lt;
+    wave_join(t >= 0 && e > 0, t, [&](int lead, int32_t lt, bool same) {
         int32_t v = same ? e : 0;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
         if ((int)(threadIdx.x & 63) == lead) atomicMax(ext + lt, v);
-        if (same) todo = false;
-    }
+    });
 }
 
 // `shift`: where the read's reference starts on the axis (< 0: not piled up), `slot_end`: where its slot ends, `layout`: a contig

@@ -20,9 +20,9 @@
 //                token by that of the query index at which its op starts, a query index at or beyond l_seq quality 0) or on a column
 //                outside [head_end, tail_start) adds nothing at all, the I mark included.
 //   counters     a sorted BAM puts a wavefront's 64 records on the same few columns: per round (each lane's next column) the lanes
-//                that hit the same (column, strand) are joined by a ballot loop over the distinct keys, and per plane one lane adds
-//                the popcount — to the workgroup's counters in LDS while the columns are staged, else to memory.  At its end a
-//                workgroup hands every non-zero LDS counter to memory with one atomic add.
+//                that hit the same (column, strand) are joined (pack_device.h's wave_join), and per plane the group's leader adds
+//                the popcount — through the workgroup's counter frame (stream_count.h's CountFrame: LDS while the columns are
+//                staged, else memory).
 // The sums are integers: their order does not matter and every run gives the same numbers.  The stream is only read.
 #include <vector>
 
@@ -35,7 +35,6 @@ constexpr int BLOCK = SC_BLOCK;
 constexpr int LDS_N = TCMI_STRAND_LDS;
 constexpr int NK = 14;                  // counters per column: fwd[7] | rev[7] in plane order
 constexpr int64_t MAX_N = 1 << 20;
-constexpr int64_t MAX_COL = WALK_MAX_COL;
 
 struct ScArgs {
     PackSrc src;                        // the resident stream, the read set's filter, floor and layout
@@ -50,18 +49,16 @@ __global__ __launch_bounds__(BLOCK) void strand_counts_kernel(ScArgs a)
     __shared__ int32_t s_cols[LDS_N];
     __shared__ uint32_t s_cnt[NK * LDS_N];
     const int tid = threadIdx.x, lane = tid & 63;
-    const bool staged = a.n <= LDS_N;                       // (uniform)
+    const CountFrame<int32_t> cnt = {s_cnt, a.counts, a.n <= LDS_N};
     const int n_cnt = NK * a.n;
-    if (staged) {
+    if (cnt.staged) {
         for (int k = tid; k < a.n; k += BLOCK) s_cols[k] = a.cols[k];
-        for (int k = tid; k < n_cnt; k += BLOCK) s_cnt[k] = 0u;
+        cnt.zero(n_cnt);
         __syncthreads();
     }
-    const int32_t *cols = staged ? s_cols : a.cols;
+    const int32_t *cols = cnt.staged ? s_cols : a.cols;
     const uint32_t Q = a.src.min_bq;
-    // (the bound is uniform over the workgroup: every lane of a wavefront takes part in every ballot)
-    for (int64_t base = (int64_t)blockIdx.x * BLOCK; base < a.src.n; base += (int64_t)gridDim.x * BLOCK) {
-        const int64_t i = base + tid;
+    each_record(a.src.n, [&](int64_t i) {
         Walk w;
         int32_t ci = 0;
         bool have = i < a.src.n && open_walk(a.src, a.pt, i, w);
@@ -72,37 +69,21 @@ __global__ __launch_bounds__(BLOCK) void strand_counts_kernel(ScArgs a)
         const uint32_t strand = have && (w.v.flag & 0x10u) ? 1u : 0u;
         while (__ballot(have)) {                            // one round per queried column of the wavefront's busiest record
             const uint32_t bits = have ? token_at(w, cols[ci], Q) : 0u;
-            const uint32_t key = 2u * (uint32_t)ci + strand;
-            bool todo = bits != 0u;
-            for (;;) {                                      // one pass per distinct (column, strand) the round's tokens hit
-                const unsigned long long m = __ballot(todo);
-                if (!m) break;
-                const int lead = (int)__builtin_ctzll(m);
-                const uint32_t lk = __shfl(key, lead, 64);
-                const bool same = todo && key == lk;
+            // one pass per distinct (column, strand) the round's tokens hit
+            wave_join(bits != 0u, 2u * (uint32_t)ci + strand, [&](int lead, uint32_t lk, bool same) {
 #pragma unroll
                 for (int pl = 0; pl < TCMI_NCOL; ++pl) {
                     const unsigned long long mp = __ballot(same && ((bits >> pl) & 1u));
-                    if (lane == lead && mp) {
-                        if (staged) atomicAdd(&s_cnt[(NK / 2) * lk + pl], (uint32_t)__popcll(mp));
-                        else atomicAdd(&a.counts[(int64_t)(NK / 2) * lk + pl], (int32_t)__popcll(mp));
-                    }
+                    if (lane == lead && mp) cnt.add((int64_t)(NK / 2) * lk + pl, __popcll(mp));
                 }
-                if (same) todo = false;
-            }
+            });
             if (have) {
                 ++ci;
                 have = ci < a.n && cols[ci] <= w.q;
             }
         }
-    }
-    if (staged) {
-        __syncthreads();
-        for (int k = tid; k < n_cnt; k += BLOCK) {
-            const uint32_t c = s_cnt[k];
-            if (c) atomicAdd(&a.counts[k], (int32_t)c);
-        }
-    }
+    });
+    cnt.flush(n_cnt);
 }
 
 } // namespace
@@ -112,33 +93,20 @@ extern "C" int tcmi_readset_strand_counts(tcmi_ctx *ctx, const tcmi_readset *rs,
     if (!ctx || !rs) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     if (n < 1 || n > MAX_N) return tcmi_fail(ctx, TCMI_E_ARG, "strand counts: %lld columns: 1..1048576 are allowed", (long long)n);
     if (!cols || !records) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
-    for (int64_t i = 0; i < n; ++i) {
-        if (cols[i] < 0 || cols[i] >= MAX_COL)
-            return tcmi_fail(ctx, TCMI_E_ARG, "strand counts: column %lld (%lld) lies outside [0, 2^29)", (long long)i, (long long)cols[i]);
-        if (i && cols[i] <= cols[i - 1])
-            return tcmi_fail(ctx, TCMI_E_ARG, "strand counts: the columns are not strictly ascending at index %lld (%lld after %lld)", (long long)i,
-                             (long long)cols[i], (long long)cols[i - 1]);
-    }
     std::vector<int32_t> c32;
     std::vector<int64_t> sums;
+    if (const int rc = tcmi_count_columns(ctx, "strand counts", n, cols, c32)) return rc;
     try {
-        c32.assign(cols, cols + n);
         sums.assign((size_t)NK * (size_t)n, 0);
     } catch (...) {                                         // (no exception may cross the C ABI)
         return tcmi_fail(ctx, TCMI_E_NOMEM, "strand counts: no host memory for %lld columns", (long long)n);
     }
     // the columns (int32) in, [n][14] int32 counters out; the primer table is the one each part was built under
-    const int rc = tcmi_stream_count_parts(
-        ctx, rs, "strand counts", c32.data(), c32.size() * 4, sums.size() * 4,
-        [n](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, char *d_cnt, unsigned grid) {
-            const ScArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), reinterpret_cast<int32_t *>(d_cnt), (int32_t)n};
-            tcmi_prof_begin(cx, TCMI_K_STRAND_COUNTS);
+    const int rc = tcmi_stream_count_parts<int32_t>(
+        ctx, rs, "strand counts", TCMI_K_STRAND_COUNTS, c32.data(), c32.size() * 4, sums,
+        [n](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, int32_t *d_cnt, unsigned grid) {
+            const ScArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n};
             hipLaunchKernelGGL(strand_counts_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
-            tcmi_prof_end(cx, TCMI_K_STRAND_COUNTS);
-        },
-        [s = sums.data(), m = sums.size()](const char *counts) {
-            const int32_t *got = reinterpret_cast<const int32_t *>(counts);
-            for (size_t k = 0; k < m; ++k) s[k] += got[k];
         });
     if (rc) return rc;
     for (int64_t i = 0; i < n; ++i) {

@@ -8,8 +8,6 @@
 
 namespace {
 
-constexpr int64_t WALK_MAX_COL = 1 << 29;                   // the columns that can be asked for lie in [0, 2^29)
-
 // a kept record between its queried columns
 struct Walk {
     ReadView v;

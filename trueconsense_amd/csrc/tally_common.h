@@ -86,6 +86,7 @@ static __device__ inline int block_scan_incl(int v, int *wave_tot /* LDS [FB / 6
 // (position | kind).  Equal words are counted inside the wave (ballot match), one atomic per distinct word
 // and wave: at an indel site thousands of reads carry the same event.  A covered position without an
 // A/C/G/T base was counted into column A by subtraction in the chunk blocks and is taken out here.
+// (The join is pack_device.h's wave_join written out: it keeps the lanes still to do as a mask, and it sits in the headline tally kernels.)
 static __device__ inline void tally_tail_block(const FastArgs &a, int tail /* which of the n_tail tail blocks */, int64_t n_events)
 {
     const int tid = threadIdx.x, lane = tid & 63;
