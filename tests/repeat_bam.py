@@ -3,12 +3,26 @@ that need more records than a capped grid takes in one trip (tests/test_stream_s
 is exactly R times the count of the small file, which the committed yardsticks can afford.  Python's zlib inflates the source (BGZF is
 concatenated gzip members), trueconsense_amd.io.bamwriter._bgzf_block compresses the result; repeated records compress to under 2 %
 of their size, so 80 MB of them are written in well under a second.  No GPU, no tests in here (tests/test_repeat_bam.py)."""
+import os
+import re
 import struct
 import zlib
 
+from tests.cli_run import ROOT
 from trueconsense_amd.io import bamwriter
 
 BLOCK = 0xFF00
+CSRC = os.path.join(ROOT, "trueconsense_amd", "csrc")
+MASK_LONG_GRID, MASK_LONG_BLOCK = 64, 256                                       # pk_mask_long's launch: tests/test_stream_scale.py's file B
+
+
+def stream_count_caps():
+    """-> (SC_BLOCK, SC_WG_PER_CU) as csrc/stream_count.h states them; the counting kernels' grid is min(ceil(records / SC_BLOCK),
+    compute units * SC_WG_PER_CU)"""
+    text = open(os.path.join(CSRC, "stream_count.h")).read()
+    block, per_cu = (re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text) for name in ("SC_BLOCK", "SC_WG_PER_CU"))
+    assert block and per_cu, "csrc/stream_count.h no longer states SC_BLOCK and SC_WG_PER_CU as constexpr int"
+    return int(block.group(1)), int(per_cu.group(1))
 
 
 def inflate(path):

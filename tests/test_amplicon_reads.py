@@ -1,6 +1,6 @@
 """--amplicon-reads on the GPU (csrc/amplicon_reads.hip; tcmi_readset_amplicon_reads, Context.amplicon_reads): every comparison is
 exact equality with the yardstick (tests/amplicon_reads_yardstick.py: per record a loop over all amplicons) applied to the SAME BAM
-parsed on the host (engine.BamFile).  The host record buffer lies between guards (tests/test_matrix_abi.py's sentinel words) and the
+parsed on the host (engine.BamFile).  The host record buffer lies between guards (tests/device_file.py's sentinel words) and the
 invariant — the reads add up to the kept records — is checked on every call.  Every case runs through both staging routes: the scheme
 as it is (table and counters in LDS) and padded with far-away amplicons to TCMI_AMPLICON_READS_LDS + 1 (table and counters in
 memory).  The rule, the scheme and the argument handling are checked without a GPU in tests/test_amplicon_reads_rule.py."""
@@ -9,28 +9,23 @@ import ctypes as C
 import functools
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import amplicon_reads_yardstick as ry
+from tests import cli_run as cr
 from tests import fuzz_reads as fz
+from tests import read_specs as rsp
+from tests import schemes as sch
 from tests import synth_small as ss
-from tests import test_amplicon_table as at
-from tests import test_base_quality as bq
-from tests import test_matrix_abi as ma
-from tests import test_read_filter as rf
+from tests.amplicon_reads_cases import LDS, device_counts, host_columns, padded, scheme_rows_for, tiled, want_text
 from trueconsense_amd import _ffi, contigs, engine
 from trueconsense_amd import distributed as td
 from trueconsense_amd.io import bamwriter
 
 pytestmark = pytest.mark.gpu
-ROOT = rf.ROOT
-LDS = engine.AMPLICON_READS_LDS
 L = 2400
-FAR = 1 << 20                           # where the padding amplicons lie: beyond every read of these tests
 
 
 @pytest.fixture(scope="module")
@@ -47,16 +42,6 @@ def packer(ctx, one_sync):
         yield
     finally:
         ctx.set_option("one_sync", 1)
-
-
-def tiled(n, first=30, step=300, length=400, primer=24):
-    """n amplicons of `length` columns every `step`: neighbours overlap by length - step"""
-    return [(first + step * k, first + step * k + primer, first + step * k + length - primer, first + step * k + length) for k in range(n)]
-
-
-def padded(amps4, n):
-    """amps4 and far-away amplicons behind them, n in all: the counts of the first ones must not change"""
-    return list(amps4) + [(FAR + 10 * k, FAR + 10 * k + 3, FAR + 10 * k + 5, FAR + 10 * k + 8) for k in range(n - len(amps4))]
 
 
 def specs_for(seed, n, length=L, unmapped=0.02):
@@ -81,34 +66,8 @@ def specs_for(seed, n, length=L, unmapped=0.02):
 def write(path, specs, **kw):
     kw.setdefault("block", 4096)
     kw.setdefault("ref_len", L)
-    bamwriter.write_bam(str(path), rf.arrays(specs), **kw)
+    bamwriter.write_bam(str(path), rsp.arrays(specs), **kw)
     return str(path)
-
-
-def host_columns(path, shift=None, read_filter=None):
-    """the yardstick's kept records of the BAM at `path`, parsed on the host"""
-    bam = engine.BamFile(path)
-    try:
-        rd = bam.arrays()
-        return ry.kept_columns(rd, shift, read_filter, rd["mapq"])
-    finally:
-        bam.close()
-
-
-def device_counts(ctx, rs, amps4, slack):
-    """tcmi_readset_amplicon_reads into a host buffer between guards -> int64 [n + 2, 2]"""
-    n = len(amps4)
-    fs, le, rs_, fe = engine._amps4(amps4)
-    G = 64
-    buf = ma.sentinel(2 * G + 4 * (n + 2), np.int32, salt=5).copy()            # (int32 sentinel words: two per int64)
-    before = buf.copy()
-    rc = _ffi.lib().tcmi_readset_amplicon_reads(ctx.handle, rs.handle, n, _ffi.ptr(fs), _ffi.ptr(le), _ffi.ptr(rs_), _ffi.ptr(fe), int(slack),
-                                                C.c_void_p(buf.ctypes.data + 4 * G))
-    _ffi.check(rc, ctx.handle)
-    assert np.array_equal(buf[:G], before[:G]) and np.array_equal(buf[-G:], before[-G:]), "a guard around the records was written"
-    got = buf[G:-G].view(np.int64).reshape(n + 2, 2).copy()
-    assert np.array_equal(got, np.stack([ctx.amplicon_reads(rs, amps4, slack)[k] for k in ("reads", "full")], axis=1))    # the same numbers run after run
-    return got
 
 
 def check(ctx, rs, columns, amps4, slack, what=(), routes=True):
@@ -276,7 +235,7 @@ def test_the_read_sets_own_filter(ctx, tmp_path, one_sync):
 def test_two_contigs_under_a_layout(ctx, tmp_path):
     """amplicons shifted by their contig's slot; reads on a reference without a slot are not kept; another layout: refused"""
     rng = np.random.default_rng(21)
-    recs, _, specs = bq._two_contigs()
+    recs, _, specs = rsp.two_contigs()
     extra = [fz._read(rng, recs[0][1], 20 * k, [(50, "M")], 0, "x%d" % k, 2) for k in range(30)]           # a reference the layout gives no slot
     for r in extra:
         r["mapq"] = 60
@@ -422,66 +381,46 @@ def test_the_launch_is_profiled_and_nothing_runs_without_the_call(ctx, tmp_path)
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
-def scheme_rows_for(chrom, amps4, pools=("1", "2")):
-    rows = []
-    for k, (fs, le, rs_, fe) in enumerate(amps4):
-        rows += [(chrom, fs, le, "%s_amp_%d_LEFT" % (chrom, k + 1), pools[k % 2], "+"), (chrom, rs_, fe, "%s_amp_%d_RIGHT" % (chrom, k + 1), pools[k % 2], "-")]
-    return rows
-
-
-def want_text(sample, columns, chrom_amps, slack):
-    """the file's text from the yardstick: chrom_amps = [(chrom, [(fs, le, rs, fe)] on the axis)] in the scheme's order"""
-    amps4 = [a for _, amps in chrom_amps for a in amps]
-    chroms = [c for c, amps in chrom_amps for _ in amps]
-    names = ["%s_amp_%d" % (c, k + 1) for c, amps in chrom_amps for k in range(len(amps))]
-    pools = [("1", "2")[k % 2] for _, amps in chrom_amps for k in range(len(amps))]
-    return ry.text(sample, ry.counts(columns, amps4, slack), chroms, names, pools)
 
 
 def test_cli_single_sample(tmp_path, monkeypatch):
     """-i with --amplicon-reads: the file is the writer's text over the yardstick's counts; FASTA, VCF, GFF, TSV and --amplicon-table
     are byte-identical with and without the flag; the read filter is followed; --stats has the two counts"""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=rf.L, block=4096)
-    common = bq._setup_cli(tmp_path, ref, orfs)
+    ref, orfs, specs = rsp.mixed()
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=rsp.L, block=4096)
+    common = cr.setup_cli(ref, orfs)
     amps = tiled(6, 30, 300, 400)
-    at.write_scheme("s.bed", scheme_rows_for("ref", amps) + scheme_rows_for("elsewhere", amps[:1]))
+    sch.write_scheme("s.bed", scheme_rows_for("ref", amps) + scheme_rows_for("elsewhere", amps[:1]))
     table = ["--amplicon-table", "a.amp", "--amplicon-scheme", "s.bed"]
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + at._out("a") + table + ["--amplicon-reads", "a.reads", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + at._out("b") + ["--amplicon-table", "b.amp", "--amplicon-scheme", "s.bed", "--stats", "b.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("a") + table + ["--amplicon-reads", "a.reads", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("b") + ["--amplicon-table", "b.amp", "--amplicon-scheme", "s.bed", "--stats", "b.json"])
     cols = host_columns("A.bam")
     want = want_text("S", cols, [("ref", amps)], 5)
     assert open("a.reads").read() == want and want.count("\n") == 9 and "elsewhere" not in want
-    assert rf._outputs("a") == rf._outputs("b") and open("a.amp").read() == open("b.amp").read() and not os.path.exists("b.reads")
+    assert cr.outputs("a") == cr.outputs("b") and open("a.amp").read() == open("b.amp").read() and not os.path.exists("b.reads")
     sa, sb = json.load(open("a.json")), json.load(open("b.json"))
     cnt = ry.counts(cols, amps, 5)
     assert (sa["amplicon_reads_ambiguous"], sa["amplicon_reads_unassigned"]) == (int(cnt[6, 0]), int(cnt[7, 0])) and cnt[6, 0] > 0 and cnt[7, 0] > 0
     assert (sb["amplicon_reads_ambiguous"], sb["amplicon_reads_unassigned"]) == (0, 0)
     # slack 0 under a read filter, the scheme from --primers' file... which also masks: the counts do not change with the mask
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "c.fa", "--amplicon-reads", "c.reads", "--amplicon-reads-slack", "0", "--primers", "s.bed"] + rf.FLAGS)
-    want0 = want_text("S", host_columns("A.bam", read_filter=rf.FILTERS["all"]), [("ref", amps)], 0)
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "c.fa", "--amplicon-reads", "c.reads", "--amplicon-reads-slack", "0", "--primers", "s.bed"] + rsp.FLAGS)
+    want0 = want_text("S", host_columns("A.bam", read_filter=rsp.FILTERS["all"]), [("ref", amps)], 0)
     assert open("c.reads").read() == want0 != want
 
 
 def test_cli_per_contig(tmp_path, monkeypatch):
     """--per-contig on a two-contig file: one file, REGION per contig, amplicons shifted by their slots; the other outputs unchanged"""
     monkeypatch.chdir(tmp_path)
-    recs, rows, specs = bq._two_contigs()
+    recs, rows, specs = rsp.two_contigs()
     refs = [("c0", 1500), ("c1", 1200)]
-    bamwriter.write_bam("A.bam", rf.arrays(specs), refs=refs, block=4096)
-    with open("r.fa", "w") as fh:
-        for name, ref in recs:
-            fh.write(">%s\n%s\n" % (name, ref))
-    with open("g.gff", "w") as fh:
-        fh.write("##gff-version 3\n")
-        for name, orfs in rows:
-            fh.write(at.pm.sy.gff_text(orfs, seqid=name)[1])
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), refs=refs, block=4096)
+    cr.setup_contigs(recs, rows)
     own = {"c1": tiled(3, 40, 300, 420), "c0": tiled(4, 20, 300, 400)}
-    at.write_scheme("s.bed", scheme_rows_for("c1", own["c1"]) + scheme_rows_for("c0", own["c0"]) + scheme_rows_for("c9", own["c0"][:1]))
+    sch.write_scheme("s.bed", scheme_rows_for("c1", own["c1"]) + scheme_rows_for("c0", own["c0"]) + scheme_rows_for("c9", own["c0"][:1]))
     args = ["-i", "A.bam", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "--per-contig"]
-    rf._run_cli(monkeypatch, args + ["-o", "a.fa", "-doc", "a.tsv", "--amplicon-reads", "a.reads", "--amplicon-scheme", "s.bed", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, args + ["-o", "b.fa", "-doc", "b.tsv"])
+    cr.run_cli(monkeypatch, args + ["-o", "a.fa", "-doc", "a.tsv", "--amplicon-reads", "a.reads", "--amplicon-scheme", "s.bed", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, args + ["-o", "b.fa", "-doc", "b.tsv"])
     shift, slot, axis = contigs.layout_for(recs, [n for n, _ in refs], [ln for _, ln in refs])
     at_ = {"c0": int(shift[0]), "c1": int(shift[1])}
     cols = host_columns("A.bam", shift=shift)
@@ -499,15 +438,12 @@ def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
     """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange): every rank counts its own records, rank 0 writes the sum;
     the other outputs are those of the run without the flag"""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=rf.L, block=4096, split_records=True)
-    common = bq._setup_cli(tmp_path, ref, orfs)
+    ref, orfs, specs = rsp.mixed()
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=rsp.L, block=4096, split_records=True)
+    common = cr.setup_cli(ref, orfs)
     amps = tiled(6, 30, 300, 400)
-    at.write_scheme("s.bed", scheme_rows_for("ref", amps))
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=ROOT)
+    sch.write_scheme("s.bed", scheme_rows_for("ref", amps))
     for tag, extra in (("a", ["--amplicon-reads", "a.reads", "--amplicon-scheme", "s.bed", "--amplicon-reads-slack", "3", "--gpus", "2"]), ("b", ["--gpus", "2"])):
-        argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", "A.bam", "-name", "S"] + common + at._out(tag) + extra
-        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-1500:]
+        cr.run_two_ranks(["-i", "A.bam", "-name", "S"] + common + cr.out_args(tag) + extra)
     assert open("a.reads").read() == want_text("S", host_columns("A.bam"), [("ref", amps)], 3)
-    assert rf._outputs("a") == rf._outputs("b") and not os.path.exists("b.reads")
+    assert cr.outputs("a") == cr.outputs("b") and not os.path.exists("b.reads")

@@ -4,19 +4,18 @@ and under AddressSanitizer + UBSan, and through tcmi_amplicon_reads_compile agai
 scheme's zones (io/primers.amplicon_zones); the writer's text; the command line's argument handling, the --batch refusal included.
 The kernel's tests are tests/test_amplicon_reads.py."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import amplicon_reads_yardstick as ry
-from tests import test_amplicon_scheme as sch
+from tests import host_program
+from tests import schemes as sch
+from tests.cli_run import ROOT, base_args
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, engine, indexing
 from trueconsense_amd.io import primers as pb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = -(1 << 31)
 
 
@@ -58,23 +57,9 @@ def test_yardstick_on_hand_written_cases():
 def test_rule_program(tmp_path, sanitize):
     """tests/amplicon_reads_main.cpp + csrc/amplicon_reads_table.cpp and nothing else, plain and with AddressSanitizer + UBSan, run as a
     program: every (p, q) of a small axis against its own brute force, every argument error"""
-    src = [os.path.join(ROOT, "tests", "amplicon_reads_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "amplicon_reads_table.cpp")]
-    out = str(tmp_path / "amplicon_reads_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"] if sanitize else []
-    tried = []
-    for cxx in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++"), shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + san + ["-o", out] + src, capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    else:
-        pytest.fail("no compiler built the program:\n" + "\n".join(tried))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([out], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    out = host_program.build(["tests/amplicon_reads_main.cpp", "trueconsense_amd/csrc/amplicon_reads_table.cpp"], tmp_path / "amplicon_reads_main", sanitize)
+    r = host_program.run(out)
+    assert r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-4000:])
     assert int(r.stdout.split()[2]) > 1000000
 
 
@@ -140,7 +125,7 @@ def test_the_capacity_and_the_slot_are_the_headers():
 
 # ------------------------------------------------------------------------------------------------------------- the scheme's zones
 def test_scheme_zones(tmp_path):
-    rows = pb.read_scheme(sch.write_bed(tmp_path / "s.bed", sch.SCHEME))
+    rows = pb.read_scheme(sch.write_scheme_bed(tmp_path / "s.bed", sch.AMPLICON_SCHEME))
     zones = pb.amplicon_zones(rows)
     full = pb.amplicons(rows, "full")
     assert zones == [(10, 34, 400, 420), (320, 342, 690, 720), (640, 660, 1000, 1020), (5, 25, 300, 320), (50, 80, 70, 90), (100, 110, 150, 160)]
@@ -148,14 +133,14 @@ def test_scheme_zones(tmp_path):
     assert [(z[1], max(z[1], z[2])) for z in zones] == [(m.start, m.end) for m in pb.amplicons(rows, "insert")]
     assert zones[4][1] > zones[4][2]                                                        # overlapping primers: legal for this rule
     assert engine.amplicon_reads_compile(zones[:3], 5).shape == (6, 3)
-    assert [tuple(a) for a in pb.amplicons(rows, "insert")] == sch.WANT["insert"]           # amplicons() is what it was
+    assert [tuple(a) for a in pb.amplicons(rows, "insert")] == sch.AMPLICON_WANT["insert"]           # amplicons() is what it was
     with pytest.raises(pb.PrimerBedError):
         pb.amplicon_zones(rows[:1])                                                         # an amplicon without its RIGHT side: amplicons()' error
 
 
 # ------------------------------------------------------------------------------------------------------------- the writer
 def test_writer_text(tmp_path):
-    rows = pb.read_scheme(sch.write_bed(tmp_path / "s.bed", sch.SCHEME))
+    rows = pb.read_scheme(sch.write_scheme_bed(tmp_path / "s.bed", sch.AMPLICON_SCHEME))
     amps = pb.amplicons(rows, "full")
     cnt = np.arange(16, dtype=np.int64).reshape(8, 2) * 3
     want = ry.text("S 1", cnt, [m.chrom for m in amps], [m.name for m in amps], [m.pool for m in amps])
@@ -173,8 +158,8 @@ def test_writer_text(tmp_path):
 
 # ------------------------------------------------------------------------------------------------------------- command line
 def test_flags_and_their_errors(tmp_path, capsys):
-    f = sch._files(tmp_path)
-    base = sch._base(f)
+    f = sch.scheme_files(tmp_path)
+    base = base_args(f)
     a = cli.GetArgs(base)
     assert (a.amplicon_reads, a.amplicon_reads_slack) == (None, 5) and cli.amplicon_reads_of(a) is None
     a = cli.GetArgs(base + ["--amplicon-reads", "r.tsv", "--amplicon-scheme", f["s.bed"]])                 # the scheme alone now goes with --amplicon-reads
@@ -203,7 +188,7 @@ def test_flags_and_their_errors(tmp_path, capsys):
 
 
 def test_batch_is_refused(tmp_path, capsys):
-    f = sch._files(tmp_path)
+    f = sch.scheme_files(tmp_path)
     man = tmp_path / "m.tsv"
     man.write_text("%s\tS0\to0.fa\n" % f["x.bam"])
     batch = ["--batch", str(man), "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "12"]
@@ -216,8 +201,8 @@ def test_batch_is_refused(tmp_path, capsys):
 
 
 def test_amplicons_of_the_reference_and_children(tmp_path, capsys):
-    f = sch._files(tmp_path)
-    base = sch._base(f)
+    f = sch.scheme_files(tmp_path)
+    base = base_args(f)
     (tmp_path / "r.fa").write_text(">chrA\nACGT\n")
     a = cli.GetArgs(base + ["--amplicon-reads", "r.tsv", "--amplicon-scheme", f["s.bed"], "--amplicon-reads-slack", "7"])
     a.input = None                                          # (x.bam is no BAM: the reference's name comes from -ref, as for --batch)

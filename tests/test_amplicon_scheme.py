@@ -3,19 +3,22 @@
 (csrc/intervals_rule.h) and row writer (csrc/amplicons_text.cpp) as a program of their own under AddressSanitizer + UBSan, and
 the command line's argument handling with the part-file join of --batch --gpus.  The kernel's tests are tests/test_amplicon_table.py."""
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import amplicon_yardstick as ay
+from tests import host_program
+from tests.cli_run import base_args as _base
+from tests.schemes import AMPLICON_SCHEME as SCHEME
+from tests.schemes import AMPLICON_WANT as WANT
+from tests.schemes import scheme_files as _files
+from tests.schemes import write_scheme_bed as write_bed
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, engine
 from trueconsense_amd.io import primers as pb
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 #            0  1  2  3  4  5  6  7  8  9
 HAND_COV = [5, 3, 9, 3, 7, 0, 0, 8, 2, 2]
@@ -49,40 +52,6 @@ def test_yardstick_on_hand_written_intervals():
 
 
 # ------------------------------------------------------------------------------------------------------------- the scheme rule
-SCHEME = [
-    ("chrA", 10, 30, "nCoV-2019_1_LEFT", "1", "+"),
-    ("chrA", 400, 420, "nCoV-2019_1_RIGHT", "1", "-"),
-    ("chrA", 320, 342, "nCoV-2019_2_LEFT", "2", "+"),
-    ("chrA", 700, 720, "nCoV-2019_2_RIGHT", "2", "-"),
-    ("chrA", 14, 34, "nCoV-2019_1_LEFT_alt1", "9", "+"),        # an alternate: merges into amplicon 1, whose pool stays "1"
-    ("chrA", 690, 712, "nCoV-2019_2_right_ALT", "2", "-"),      # any case; the field behind the side is ignored
-    ("chrA", 640, 660, "nCoV-2019_3_LEFT", "1", "+"),
-    ("chrA", 1000, 1020, "nCoV-2019_3_RIGHT_1", "1", "-"),
-    ("chrB", 5, 25, "seg_LEFT_b_LEFT", "1", "+"),                 # the LAST side field counts: key "seg_LEFT_b"
-    ("chrB", 300, 320, "seg_LEFT_b_RIGHT", "1", "-"),
-    ("chrB", 100, 110, "in_LEFT", "2", "+"),                      # nested in seg_LEFT_b: cuts its unique region in two
-    ("chrB", 150, 160, "in_RIGHT", "2", "-"),
-    ("chrB", 50, 80, "ov_LEFT", "1", "+"),                        # primers that overlap: the insert is empty at its start
-    ("chrB", 70, 90, "ov_RIGHT", "1", "-"),
-]
-WANT = {
-    "full": [("chrA", "nCoV-2019_1", "1", 10, 420), ("chrA", "nCoV-2019_2", "2", 320, 720), ("chrA", "nCoV-2019_3", "1", 640, 1020),
-             ("chrB", "seg_LEFT_b", "1", 5, 320), ("chrB", "ov", "1", 50, 90), ("chrB", "in", "2", 100, 160)],
-    "insert": [("chrA", "nCoV-2019_1", "1", 34, 400), ("chrA", "nCoV-2019_2", "2", 342, 690), ("chrA", "nCoV-2019_3", "1", 660, 1000),
-               ("chrB", "seg_LEFT_b", "1", 25, 300), ("chrB", "ov", "1", 80, 80), ("chrB", "in", "2", 110, 150)],
-    # seg_LEFT_b's insert [25, 300) minus ov [50, 90) and in [100, 160): [25, 50), [90, 100), [160, 300) -> the longest; `in` lies
-    # wholly inside seg_LEFT_b's full: it vanishes
-    "unique": [("chrA", "nCoV-2019_1", "1", 34, 320), ("chrA", "nCoV-2019_2", "2", 420, 640), ("chrA", "nCoV-2019_3", "1", 720, 1000),
-               ("chrB", "seg_LEFT_b", "1", 160, 300), ("chrB", "ov", "1", 80, 80), ("chrB", "in", "2", 110, 110)],
-}
-
-
-def write_bed(path, rows, sep="\t"):
-    with open(path, "w") as fh:
-        fh.write("# a scheme\ntrack name=x\n\n")
-        for r in rows:
-            fh.write(sep.join(str(x) for x in r) + "\n")
-    return str(path)
 
 
 @pytest.mark.parametrize("region", ("insert", "unique", "full"))
@@ -145,19 +114,6 @@ def test_layout_shifts_and_ignores(tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------------------- the program
-def build_program(tmp_path):
-    src = [os.path.join(ROOT, "tests", "amplicons_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "amplicons_text.cpp")]
-    out = str(tmp_path / "amplicons_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
-    tried = []
-    for cxx in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++"), shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + san + ["-o", out] + src, capture_output=True, text=True)
-        if r.returncode == 0:
-            return out
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    pytest.fail("no compiler built the program:\n" + "\n".join(tried))
 
 
 def run_program(prog, tmp_path, tag, cov, intervals, min_depth, sample, region, names, pools, pos_offset=0):
@@ -169,17 +125,15 @@ def run_program(prog, tmp_path, tag, cov, intervals, min_depth, sample, region, 
         fh.write(sample.encode() + region.encode() + nm + pl)
         fh.write(np.array([s for s, _ in intervals], np.int64).tobytes() + np.array([e for _, e in intervals], np.int64).tobytes())
         fh.write(np.ascontiguousarray(cov, np.int32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([prog, inp, rec, txt], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    r = host_program.run(prog, inp, rec, txt)
+    assert r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-4000:])
     return np.fromfile(rec, ay.DTYPE), open(txt).read()
 
 
 def test_checks_rule_and_text_program_under_sanitizers(tmp_path):
     """tests/amplicons_main.cpp + csrc/intervals_rule.h + csrc/amplicons_text.cpp and nothing else, with AddressSanitizer + UBSan, run
     as a program: the argument checks' refusals (inside the program), its records equal the yardstick's, its text the yardstick's"""
-    prog = build_program(tmp_path)
+    prog = host_program.build(["tests/amplicons_main.cpp", "trueconsense_amd/csrc/amplicons_text.cpp"], tmp_path / "amplicons_main")
     iv = [x[0] for x in HAND if x[1] == 1] + [(7, 7), (0, 10), (3, 5000)]
     names = ["amp_%d" % k for k in range(len(iv))]
     pools = [str(1 + k % 2) for k in range(len(iv))]
@@ -226,19 +180,6 @@ def test_text_writer_through_the_abi():
 
 
 # ------------------------------------------------------------------------------------------------------------- command line
-def _files(tmp_path):
-    p = {}
-    for name in ("x.bam", "f.gff", "p.bed"):
-        (tmp_path / name).write_text("x")
-        p[name] = str(tmp_path / name)
-    (tmp_path / "r.fa").write_text(">chrA\nACGT\n")
-    p["r.fa"] = str(tmp_path / "r.fa")
-    p["s.bed"] = write_bed(tmp_path / "s.bed", SCHEME)
-    return p
-
-
-def _base(f):
-    return ["-i", f["x.bam"], "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30", "-name", "S", "-o", "out.fa"]
 
 
 def test_the_four_flags(tmp_path, capsys):

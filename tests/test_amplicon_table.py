@@ -1,32 +1,29 @@
 """The amplicon table on the GPU (csrc/intervals.hip; tcmi_interval_stats_dev, tcmi_interval_stats, tcmi_ctx_set_intervals,
 tcmi_step_intervals, tcmi_filerunner_run_files_stats, --amplicon-table): every comparison is exact equality of record arrays, or of the
 table's text, with the yardstick (tests/amplicon_yardstick.py, plain Python integers).  The matrix, the interval arrays and the record
-buffer lie between guards (tests/test_matrix_abi.py) and are read back whole.  The scheme rule, the row writer and the argument
+buffer lie between guards (tests/device_file.py) and are read back whole.  The scheme rule, the row writer and the argument
 handling are checked without a GPU in tests/test_amplicon_scheme.py."""
 import functools
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import c_oracle
 from tests import amplicon_yardstick as ay
+from tests import cli_run as cr
+from tests import device_file as dvf
 from tests import primer_yardstick as py
-from tests import test_base_quality as bq
-from tests import test_matrix_abi as ma
-from tests import test_primer_mask as pm
-from tests import test_read_filter as rf
+from tests import read_specs as rsp
 from tests import variant_yardstick as vy
+from tests.schemes import write_scheme
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, engine
 from trueconsense_amd.io import bamwriter
 from trueconsense_amd.io import primers as pb
 
 pytestmark = pytest.mark.gpu
-ROOT = rf.ROOT
 CAP = engine.INTERVAL_STAGE             # columns of an interval the kernel stages in LDS; a longer one is selected from memory
 LENS = (0, 1, 2, 63, 64, 65, 255, 256, 257, CAP, CAP + 1, 2 * CAP + 1)
 END = 1 << 29
@@ -40,7 +37,7 @@ def ctx():
 
 
 def test_the_capacity_is_the_headers():
-    text = open(os.path.join(ROOT, "include", "tcmi.h")).read()
+    text = open(os.path.join(cr.ROOT, "include", "tcmi.h")).read()
     assert "#define TCMI_INTERVAL_STAGE %d\n" % CAP in text and CAP >= 512
 
 
@@ -52,12 +49,12 @@ def on_device(ctx, cov, intervals, min_depth, ld=None, off=0, rec_lead=0, seed=5
     ld = L if ld is None else ld
     body = np.random.default_rng(seed).integers(-(1 << 31), 1 << 31, (7, ld), dtype=np.int64).astype(np.int32)
     body[0, :L] = cov
-    m = ma.Matrix(L, ld, off, body)
+    m = dvf.Matrix(L, ld, off, body)
     n = len(intervals)
     iv = np.asarray(intervals, np.int64).reshape(-1, 2)
-    st = ma.Guarded(2 * n, np.int32, 0, np.ascontiguousarray(iv[:, 0]).view(np.int32))
-    en = ma.Guarded(2 * n, np.int32, 0, np.ascontiguousarray(iv[:, 1]).view(np.int32), salt=3)
-    out = ma.Guarded(8 * n, np.int32, rec_lead, salt=77)
+    st = dvf.Guarded(2 * n, np.int32, 0, np.ascontiguousarray(iv[:, 0]).view(np.int32))
+    en = dvf.Guarded(2 * n, np.int32, 0, np.ascontiguousarray(iv[:, 1]).view(np.int32), salt=3)
+    out = dvf.Guarded(8 * n, np.int32, rec_lead, salt=77)
     assert out.ptr % 16 == 4 * rec_lead
     ctx.interval_stats_dev(m.ptr, L, ld, n, st.ptr, en.ptr, min_depth, out.ptr)
     assert m.untouched(), "the matrix was written"
@@ -206,11 +203,11 @@ def test_argument_errors(ctx):
     with pytest.raises(_ffi.TcmiError):                                             # none of them left a setting behind
         ctx.step_intervals()
     # the device entry point looks at the intervals it is given, and writes nothing when it refuses
-    m = ma.Matrix(64, 64, 0, np.ones((7, 64), np.int32))
+    m = dvf.Matrix(64, 64, 0, np.ones((7, 64), np.int32))
     for s, e, _ in cases[:3]:
-        st = ma.Guarded(6, np.int32, 0, s.view(np.int32))
-        en = ma.Guarded(6, np.int32, 0, e.view(np.int32))
-        rec = ma.Guarded(24, np.int32, 0, salt=9)
+        st = dvf.Guarded(6, np.int32, 0, s.view(np.int32))
+        en = dvf.Guarded(6, np.int32, 0, e.view(np.int32))
+        rec = dvf.Guarded(24, np.int32, 0, salt=9)
         with pytest.raises(_ffi.TcmiError) as err:
             ctx.interval_stats_dev(m.ptr, 64, 64, 3, st.ptr, en.ptr, 0, rec.ptr)
         assert err.value.code == _ffi.E_ARG and rec.untouched() and m.untouched()
@@ -220,7 +217,7 @@ def test_argument_errors(ctx):
 
 
 # ---- the step path --------------------------------------------------------------------------------------------------------------
-L = rf.L
+L = rsp.L
 PRIMERS = py.scheme()                   # '+' [s, s + 24), '-' [s + 376, s + 400), s = 30, 330, ...: 6 amplicons that overlap by 100 columns
 
 
@@ -232,22 +229,15 @@ def scheme_rows(chrom="ref", primers=PRIMERS):
     return rows + [(chrom, s + 6, e + 6, "amp_2_LEFT_alt1", "2", "+")]
 
 
-def write_scheme(path, rows):
-    with open(path, "w") as fh:
-        for r in rows:
-            fh.write("\t".join(str(x) for x in r) + "\n")
-    return path
-
-
 def amps_of(region="insert", rows=None):
     return ay.scheme(scheme_rows() if rows is None else rows, region)
 
 
 @functools.lru_cache(maxsize=None)
 def mixed_files():
-    """-> (reads A, reads B = every second record of A) of test_read_filter.mixed()"""
-    specs = rf.mixed()[2]
-    return rf.arrays(specs), rf.arrays(specs[::2])
+    """-> (reads A, reads B = every second record of A) of read_specs.mixed()"""
+    specs = rsp.mixed()[2]
+    return rsp.arrays(specs), rsp.arrays(specs[::2])
 
 
 @pytest.mark.parametrize("one_sync", (1, 0))
@@ -255,7 +245,7 @@ def test_step_path(ctx, tmp_path, one_sync):
     """set_intervals + tcmi_bamfile_step on both routes: the records are the yardstick's over the oracle's matrix, without and with
     --min-baseq 20 --primers, beside the variant setting, and none once the setting is cleared (no launch either)"""
     ra, rb = mixed_files()
-    ref = rf.mixed()[0]
+    ref = rsp.mixed()[0]
     paths = [str(tmp_path / "A.bam"), str(tmp_path / "B.bam")]
     for p, rd in zip(paths, (ra, rb)):
         bamwriter.write_bam(p, rd, ref_len=L, block=4096)
@@ -344,7 +334,7 @@ def test_array_pipeline_refuses(ctx):
 
 def test_file_runner_records_and_the_host_reader_fallback(tmp_path):
     ra, rb = mixed_files()
-    ref = rf.mixed()[0]
+    ref = rsp.mixed()[0]
     paths = []
     for tag, rd in (("A", ra), ("B", rb), ("C", ra)):
         paths.append(str(tmp_path / (tag + ".bam")))
@@ -372,8 +362,6 @@ def test_file_runner_records_and_the_host_reader_fallback(tmp_path):
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
-def _out(t):
-    return ["-o", t + ".fa", "-vcf", t + ".vcf", "-ogff", t + ".gff", "-doc", t + ".tsv"]
 
 
 def table_text(counts, amps, sample="S", region="ref", min_depth=30, header=True):
@@ -386,51 +374,51 @@ def test_cli_single_sample_and_batch(tmp_path, monkeypatch):
     without the flag; --amplicon-region unique; with --min-baseq 20 --primers (the scheme defaults to that file) it follows the masked
     matrix, with --index-override the overridden one; --batch writes one file with every sample's rows in manifest order"""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     rd, rd3 = mixed_files()
     bamwriter.write_bam("A.bam", rd, ref_len=L, block=4096)
     bamwriter.write_bam("A2.bam", rd, ref_len=L, block=4096, split_records=True)
     bamwriter.write_bam("A3.bam", rd3, ref_len=L, block=4096)
-    common = bq._setup_cli(tmp_path, ref, orfs)
+    common = cr.setup_cli(ref, orfs)
     write_scheme("s.bed", scheme_rows() + [("elsewhere", 5, 25, "x_LEFT", "1", "+"), ("elsewhere", 300, 320, "x_RIGHT", "1", "-")])
     counts, counts3 = (c_oracle.tally(r, c_oracle.extent(r, L)) for r in (rd, rd3))
     cov = int(common[common.index("-cov") + 1])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + _out("a") + ["--amplicon-table", "a.amp", "--amplicon-scheme", "s.bed", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + _out("b") + ["--stats", "b.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("a") + ["--amplicon-table", "a.amp", "--amplicon-scheme", "s.bed", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("b") + ["--stats", "b.json"])
     want = table_text(counts, amps_of(), min_depth=cov)
     assert open("a.amp").read() == want and want.count("\n") == 7 and "elsewhere" not in want
-    assert rf._outputs("a") == rf._outputs("b") and not os.path.exists("b.amp")
+    assert cr.outputs("a") == cr.outputs("b") and not os.path.exists("b.amp")
     below = sum(1 for ln in want.split("\n")[1:] if ln and ln.split("\t")[-1] != "0")
     sa, sb = json.load(open("a.json")), json.load(open("b.json"))
     assert (sa["amplicons"], sa["amplicons_below"], sb["amplicons"], sb["amplicons_below"]) == (6, below, 0, 0)
     for region in ("unique", "full"):
-        rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + _out("u") + ["--amplicon-table", "u.amp", "--amplicon-scheme", "s.bed",
+        cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("u") + ["--amplicon-table", "u.amp", "--amplicon-scheme", "s.bed",
                                                                           "--amplicon-region", region])
         got = open("u.amp").read()
         assert got == table_text(counts, amps_of(region), min_depth=cov) != want
-        assert rf._outputs("u") == rf._outputs("b"), region
+        assert cr.outputs("u") == cr.outputs("b"), region
     # the floor and the primer mask: the table follows the masked matrix; the scheme is the file of --primers
     masked = py.counts(rd, L, [(s, e, st == "-") for _, s, e, _, _, st in scheme_rows()], 20)[0]
     write_scheme("p.bed", scheme_rows())
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "q.fa", "--amplicon-table", "q.amp", "--min-baseq", "20", "--primers", "p.bed"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "q.fa", "--amplicon-table", "q.amp", "--min-baseq", "20", "--primers", "p.bed"])
     assert open("q.amp").read() == table_text(masked, amps_of(), min_depth=cov) != want
     # --index-override: the table is taken behind the override
     over = counts.copy()
     over[700:760] = (3, 3, 0, 0, 0, 0, 0)
-    bq._write_override("o.csv.gz", over)
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + _out("o") + ["--amplicon-table", "o.amp", "--amplicon-scheme", "s.bed", "--index-override", "o.csv.gz"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + _out("o2") + ["--index-override", "o.csv.gz"])
+    cr.write_override("o.csv.gz", over)
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("o") + ["--amplicon-table", "o.amp", "--amplicon-scheme", "s.bed", "--index-override", "o.csv.gz"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("o2") + ["--index-override", "o.csv.gz"])
     assert open("o.amp").read() == table_text(over, amps_of(), min_depth=cov) != want
-    assert rf._outputs("o") == rf._outputs("o2") != rf._outputs("b")
+    assert cr.outputs("o") == cr.outputs("o2") != cr.outputs("b")
     # --batch: three samples, one file, manifest order
     for name, tail in (("m", ["--amplicon-table", "m.amp", "--amplicon-scheme", "s.bed", "--stats", "m.json"]), ("n", [])):
         with open(name + ".tsv", "w") as fh:
             for k, bam in enumerate(("A.bam", "A2.bam", "A3.bam")):
                 fh.write("\t".join([bam, "S%d" % k] + ["%s%d.%s" % (name, k, e) for e in ("fa", "vcf", "gff", "tsv")]) + "\n")
-        rf._run_cli(monkeypatch, ["--batch", name + ".tsv"] + common + tail)
+        cr.run_cli(monkeypatch, ["--batch", name + ".tsv"] + common + tail)
     assert open("m.amp").read() == ay.HEADER + "".join(table_text(c, amps_of(), "S%d" % k, min_depth=cov, header=False) for k, c in enumerate((counts, counts, counts3)))
     for k in range(3):
-        assert rf._outputs("m%d" % k) == rf._outputs("n%d" % k), k
+        assert cr.outputs("m%d" % k) == cr.outputs("n%d" % k), k
     assert not os.path.exists("n.amp") and json.load(open("m.json"))["amplicons"] == 6
 
 
@@ -438,27 +426,21 @@ def test_cli_per_contig(tmp_path, monkeypatch):
     """--per-contig on a two-contig file: one table, REGION the contig, positions the contig's own; rows on a chrom the layout does
     not hold are ignored, a scheme that leaves nothing is an argument error"""
     monkeypatch.chdir(tmp_path)
-    recs, rows, specs = bq._two_contigs()
+    recs, rows, specs = rsp.two_contigs()
     refs = [("c0", 1500), ("c1", 1200)]
-    bamwriter.write_bam("A.bam", rf.arrays(specs), refs=refs, block=4096)
-    with open("r.fa", "w") as fh:
-        for name, ref in recs:
-            fh.write(">%s\n%s\n" % (name, ref))
-    with open("g.gff", "w") as fh:
-        fh.write("##gff-version 3\n")
-        for name, orfs in rows:
-            fh.write(pm.sy.gff_text(orfs, seqid=name)[1])
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), refs=refs, block=4096)
+    cr.setup_contigs(recs, rows)
     bed = scheme_rows("c1", py.scheme(n=3)) + scheme_rows("c0", py.scheme(first=100, n=4))[:-1] + [("c9", 5, 25, "x_LEFT", "1", "+"), ("c9", 300, 320, "x_RIGHT", "1", "-")]
     bed = [r[:3] + (r[0] + r[3],) + r[4:] for r in bed]                             # (keys are per scheme: the contig's name in front)
     write_scheme("s.bed", bed)
     args = ["-i", "A.bam", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "--per-contig"]
-    rf._run_cli(monkeypatch, args + ["-o", "a.fa", "-doc", "a.tsv", "--amplicon-table", "a.amp", "--amplicon-scheme", "s.bed", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, args + ["-o", "b.fa", "-doc", "b.tsv"])
+    cr.run_cli(monkeypatch, args + ["-o", "a.fa", "-doc", "a.tsv", "--amplicon-table", "a.amp", "--amplicon-scheme", "s.bed", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, args + ["-o", "b.fa", "-doc", "b.tsv"])
     amps = ay.scheme(bed)
     want = ay.HEADER
     for name, ln in (refs[1], refs[0]):                                             # chroms in the order of the scheme's file
         t = [n for n, _ in refs].index(name)
-        rd = rf.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
+        rd = rsp.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
         part = table_text(c_oracle.tally(rd, c_oracle.extent(rd, ln)), [a for a in amps if a[0] == name], region=name, min_depth=10, header=False)
         assert part.count("\n") >= 3
         want += part
@@ -469,7 +451,7 @@ def test_cli_per_contig(tmp_path, monkeypatch):
     assert st["amplicons"] == 7 and st["amplicons_below"] == sum(1 for ln in got.split("\n")[1:] if ln and ln.split("\t")[-1] != "0")
     write_scheme("none.bed", bed[-2:])
     with pytest.raises(SystemExit) as e:
-        rf._run_cli(monkeypatch, args + ["-o", "c.fa", "--amplicon-table", "c.amp", "--amplicon-scheme", "none.bed"])
+        cr.run_cli(monkeypatch, args + ["-o", "c.fa", "--amplicon-table", "c.amp", "--amplicon-scheme", "none.bed"])
     assert e.value.code == 1 and not os.path.exists("c.amp") and not os.path.exists("c.fa")
 
 
@@ -477,19 +459,16 @@ def test_cli_split_worker_at_world_one(tmp_path, monkeypatch):
     """`-i --gpus N`'s worker (trueconsense_amd.split_main) as one rank: rank 0 takes the table from the reduced counts; the other
     four outputs are those of the worker without the flag"""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     rd = mixed_files()[0]
     bamwriter.write_bam("A.bam", rd, ref_len=L, block=4096, split_records=True)
-    common = bq._setup_cli(tmp_path, ref, orfs)
+    common = cr.setup_cli(ref, orfs)
     write_scheme("s.bed", scheme_rows())
-    env = {k: v for k, v in os.environ.items() if k not in ("TCMI_SPLIT_ONE_GPU", "TCMI_SPLIT_BACKEND")}
-    env.update(PYTHONPATH=ROOT, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    worker = [sys.executable, "-m", "trueconsense_amd.split_main", "-i", "A.bam", "-name", "S"] + common
-    for argv in (worker + _out("w") + ["--amplicon-table", "w.amp", "--amplicon-scheme", "s.bed", "--amplicon-region", "unique", "--gpus", "1"],
-                 worker + _out("x") + ["--gpus", "1"]):
-        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-1500:]
-    assert rf._outputs("w") == rf._outputs("x") and not os.path.exists("x.amp")
+    worker = ["-i", "A.bam", "-name", "S"] + common
+    for args in (worker + cr.out_args("w") + ["--amplicon-table", "w.amp", "--amplicon-scheme", "s.bed", "--amplicon-region", "unique", "--gpus", "1"],
+                 worker + cr.out_args("x") + ["--gpus", "1"]):
+        cr.run_split_worker(args)
+    assert cr.outputs("w") == cr.outputs("x") and not os.path.exists("x.amp")
     cov = int(common[common.index("-cov") + 1])
     assert open("w.amp").read() == table_text(c_oracle.tally(rd, c_oracle.extent(rd, L)), amps_of("unique"), min_depth=cov)
     assert cli.amplicon_intervals([(pb.Amplicon(*a), 0) for a in amps_of("unique")])[0] == (54, 330)

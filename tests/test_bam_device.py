@@ -1,6 +1,5 @@
 """GPU: the device BAM decoder (bam_device.hip: BGZF inflate, record chain) against zlib and a plain Python record
 walk, and the whole file -> device -> counts path against the oracle.  Byte / index work: bit-exact."""
-import gzip
 import os
 import struct
 
@@ -10,8 +9,8 @@ import pytest
 from oracle import c_oracle
 from tests import fuzz_reads as fz
 from tests import synth_small as ss
-from tests import test_bam_fixture as hand
-from tests import test_bgzf_host as host
+from tests import hand_bam as hand
+from tests.device_file import check_counts, check_decode, host_stream_and_records
 from trueconsense_amd import _ffi, _state, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
@@ -22,45 +21,6 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(scope="module")
 def ctx():
     return _state.default_context()
-
-
-def host_stream_and_records(path):
-    """zlib (gzip.decompress walks every member) + a Python walk of the block_size chain."""
-    raw = gzip.decompress(open(path, "rb").read())
-    l_text = struct.unpack_from("<i", raw, 4)[0]
-    o = 8 + l_text
-    n_ref = struct.unpack_from("<i", raw, o)[0]
-    o += 4
-    for _ in range(n_ref):
-        l_name = struct.unpack_from("<i", raw, o)[0]
-        o += 4 + l_name + 4
-    rec = []
-    while o < len(raw):
-        rec.append(o)
-        o += 4 + struct.unpack_from("<i", raw, o)[0]
-    return np.frombuffer(raw, np.uint8), np.array(rec, np.uint64)
-
-
-def check_decode(ctx, path):
-    want_stream, want_rec = host_stream_and_records(path)
-    d = engine.DeviceBam(path)
-    assert d.inflated_bytes == len(want_stream)
-    stream, rec = d.decode_to_host(ctx)
-    assert np.array_equal(stream, want_stream), np.argwhere(stream != want_stream)[:5]
-    assert np.array_equal(rec, want_rec)
-    return d
-
-
-def check_counts(ctx, path, L):
-    reads = c_oracle.read_bam(path)
-    want = c_oracle.tally(reads, L)
-    d = engine.DeviceBam(path)
-    rs = ctx.upload_bamfile(d)
-    assert rs.n_reads == reads["n_reads"]
-    got = ctx.step(rs, L, 30, True)[3]
-    assert np.array_equal(got, want), np.argwhere(got != want)[:5]
-    rs.free()
-    d.close()
 
 
 def test_device_inflate_and_record_index_match_zlib(ctx, tmp_path):
@@ -131,7 +91,7 @@ def test_both_readers_report_the_same_container(tmp_path):
     file and on a header of several blocks whose first record starts mid-block."""
     paths = [str(tmp_path / "hand.bam"), str(tmp_path / "long_header.bam")]
     hand.build(paths[0], straddle=False)
-    refs = host.long_header_bam(paths[1])
+    refs = hand.long_header_bam(paths[1])
     for p in paths:
         d, b = engine.DeviceBam(p), engine.BamFile(p)
         assert (d.n_blocks, d.inflated_bytes, d.file_bytes) == (b.n_blocks, b.inflated_bytes, b.file_bytes)

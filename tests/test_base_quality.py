@@ -7,49 +7,36 @@ the plane tally kernel and the stream-walking kernel of long reads are driven (o
 flat-array entry points refuse."""
 import ctypes as C
 import functools
-import gzip
 import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import c_oracle
-from oracle import tc_oracle as orc
+from tests import cli_run as cr
 from tests import fuzz_reads as fz
-from tests import test_read_filter as rf
+from tests import read_specs as rsp
+from tests.device_file import PACKERS, uploaded
+from tests.read_specs import L, mk, oracle_counts, seq_starts, two_contigs
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, contigs, distributed, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
 
-ROOT = rf.ROOT
-L = rf.L
-PACKERS = ("one_sync", "several_kernels")
-
-
-def oracle_counts(rd, q, n_pos):
-    """the yardstick: int32 [n_pos, 7] (coverage, A, T, C, G, X, I)"""
-    out = np.zeros((n_pos, 7), np.int32)
-    for c, toks in orc.pileup_columns(rd, min_base_quality=q).items():
-        out[c] = orc.tally_tokens(toks)
-    return out
-
 
 @functools.lru_cache(maxsize=None)
 def mixed_oracle(q):
-    """test_read_filter.mixed() (qualities clustered at 12 / 13, reads without QUAL, insertions, deletions, clips) under floor q"""
-    rd = rf.arrays(rf.mixed()[2])
+    """read_specs.mixed() (qualities clustered at 12 / 13, reads without QUAL, insertions, deletions, clips) under floor q"""
+    rd = rsp.arrays(rsp.mixed()[2])
     n_pos = c_oracle.extent(rd, L)
     return oracle_counts(rd, q, n_pos), n_pos
 
 
 # ------------------------------------------------------------------------------------------------------------------------ CPU
 def test_cli_parses_min_baseq(tmp_path):
-    base = rf._files(tmp_path)
+    base = cr.base_args(cr.stub_files(tmp_path), "o.fa")
     assert cli.GetArgs(base).min_baseq == 0
     for text, v in (("0", 0), ("13", 13), ("255", 255)):
         assert cli.GetArgs(base + ["--min-baseq", text]).min_baseq == v
@@ -60,7 +47,7 @@ def test_cli_parses_min_baseq(tmp_path):
 
 
 def test_gpus_children_get_min_baseq_only_when_it_is_set(tmp_path):
-    base = rf._files(tmp_path)
+    base = cr.base_args(cr.stub_files(tmp_path), "o.fa")
     for single in (True, False):
         assert "--min-baseq" not in cli._child_argv(cli.GetArgs(base), single)
         assert "--min-baseq" not in cli._child_argv(cli.GetArgs(base + ["--min-baseq", "0"]), single)
@@ -70,7 +57,7 @@ def test_gpus_children_get_min_baseq_only_when_it_is_set(tmp_path):
 
 
 def test_header_declares_and_library_exports_the_two_symbols():
-    text = open(os.path.join(ROOT, "include", "tcmi.h")).read()
+    text = open(os.path.join(cr.ROOT, "include", "tcmi.h")).read()
     assert re.search(r"int\s+tcmi_ctx_set_min_base_quality\(tcmi_ctx \*ctx, int32_t q\);", text)
     assert re.search(r"int\s+tcmi_readset_min_base_quality\(const tcmi_readset \*rs, int32_t \*q\);", text)
     assert "#define TCMI_ABI_VERSION 5" in text
@@ -88,24 +75,8 @@ def ctx():
 
 def through(ctx, how, path, q, n_pos, f=(0, 0, 0)):
     """the file under floor q on one packer -> (counts, n_piled, max_end, the read set's floor)"""
-    try:
-        ctx.set_option("one_sync", int(how == "one_sync"))
-        ctx.set_read_filter(*f)
-        ctx.set_min_base_quality(q)
-        d = engine.DeviceBam(path)
-        try:
-            t0 = ctx.stat("one_sync_taken")
-            rs = ctx.upload_bamfile(d)
-            assert ctx.stat("one_sync_taken") - t0 == int(how == "one_sync"), (how, ctx.stat("one_sync_last_decline_flags"))
-            out = (ctx.step(rs, n_pos, 0, True)[3], rs.n_piled, rs.max_end, rs.min_base_quality)
-            rs.free()
-            return out
-        finally:
-            d.close()
-    finally:
-        ctx.set_option("one_sync", 1)
-        ctx.set_read_filter()
-        ctx.set_min_base_quality()
+    with uploaded(ctx, path, q=q, f=f, how=how) as rs:
+        return ctx.step(rs, n_pos, 0, True)[3], rs.n_piled, rs.max_end, rs.min_base_quality
 
 
 def check_file(ctx, path, rd, q, want=None, f=(0, 0, 0)):
@@ -125,8 +96,8 @@ def check_file(ctx, path, rd, q, want=None, f=(0, 0, 0)):
 @pytest.mark.parametrize("q", (1, 13, 20, 42, 255))
 @pytest.mark.parametrize("split_records", (False, True))
 def test_counts_equal_the_oracle(ctx, tmp_path, q, split_records):
-    specs = rf.mixed()[2]
-    rd = rf.arrays(specs)
+    specs = rsp.mixed()[2]
+    rd = rsp.arrays(specs)
     want, n_pos = mixed_oracle(q)
     base, _ = mixed_oracle(0)
     share = want[:, 0].sum() / base[:, 0].sum()
@@ -135,17 +106,6 @@ def test_counts_equal_the_oracle(ctx, tmp_path, q, split_records):
     path = str(tmp_path / "A.bam")
     bamwriter.write_bam(path, rd, ref_len=L, block=4096, split_records=split_records)
     check_file(ctx, path, rd, q, want)
-
-
-def _mk(rng, pos, cig, qual, name, seq=None, flag=0):
-    n = sum(k for k, op in cig if op in "MIS=X")
-    if seq is None:
-        seq = "".join("ACGT"[int(k)] for k in rng.integers(0, 4, n))
-    if qual is None:
-        qual = [int(x) for x in rng.choice((12, 13, 30, 2, 41), len(seq))]
-    qual = list(qual) if seq != "*" else []
-    assert seq == "*" or len(qual) == len(seq)
-    return {"pos": int(pos), "flag": flag, "cigar": "".join("%d%s" % t for t in cig), "seq": seq, "qual": qual, "name": name, "tid": 0, "mapq": 60}
 
 
 def _one_low(n, at, low=12):
@@ -159,7 +119,7 @@ def edge_reads():
     out, pos = [], [10]
 
     def add(cig, qual=None, seq=None, step=23):
-        out.append(_mk(rng, pos[0], cig, qual, "e%d" % len(out), seq))
+        out.append(mk(rng, pos[0], cig, qual, "e%d" % len(out), seq))
         pos[0] += step
     for n in (1, 31, 32, 33, 63, 64, 65, 150):                                  # lengths around the 32-base pair
         add([(n, "M")])
@@ -187,28 +147,17 @@ def edge_reads():
     return out
 
 
-def _seq_starts(rd, inflated):
-    """byte offset of every record's SEQ in the inflated stream (the header takes what the records do not)"""
-    sizes = [rf._record_bytes(rd, i) for i in range(int(rd["n_reads"]))]
-    at = inflated - sum(sizes)
-    out = []
-    for i, n in enumerate(sizes):
-        out.append(at + 36 + int(rd["name_off"][i + 1] - rd["name_off"][i]) + 1 + 4 * int(rd["cigar_off"][i + 1] - rd["cigar_off"][i]))
-        at += n
-    return out
-
-
 @pytest.mark.gpu
 def test_constructed_edges(ctx, tmp_path):
     specs = edge_reads()
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     want = None
     for tag, kw in (("whole", dict(block=4096)), ("split", dict(block=512, split_records=True))):
         path = str(tmp_path / (tag + ".bam"))
         bamwriter.write_bam(path, rd, ref_len=L, **kw)
         if tag == "split":                                                      # a 150-base read whose first pair (16 bytes of SEQ) straddles a BGZF block boundary
             d = engine.DeviceBam(path)
-            starts = _seq_starts(rd, d.inflated_bytes)
+            starts = seq_starts(rd, d.inflated_bytes)
             d.close()
             assert any(s // 512 != (s + 15) // 512 for i, s in enumerate(starts) if int(rd["l_qseq"][i]) == 150)
         want = check_file(ctx, path, rd, 13, want)
@@ -221,12 +170,12 @@ def test_depth_of_three_thousand(ctx, tmp_path):
     """3 000 copies of one read on one position (the fourth counter's carry ripple, several stages, more than one chunk): one base
     Q12, its neighbour Q13; a few reads at neighbouring offsets around them."""
     rng = np.random.default_rng(5)
-    one = _mk(rng, 500, [(150, "M")], [30] * 70 + [12, 13] + [30] * 78, "deep")
-    specs = [_mk(rng, 470 + 4 * k, [(int(rng.integers(40, 151)), "M")], None, "n%d" % k) for k in range(7)]
+    one = mk(rng, 500, [(150, "M")], [30] * 70 + [12, 13] + [30] * 78, "deep")
+    specs = [mk(rng, 470 + 4 * k, [(int(rng.integers(40, 151)), "M")], None, "n%d" % k) for k in range(7)]
     specs += [dict(one, name="deep%d" % k) for k in range(3000)]
-    specs += [_mk(rng, 501 + 5 * k, [(int(rng.integers(40, 151)), "M")], None, "m%d" % k) for k in range(7)]
+    specs += [mk(rng, 501 + 5 * k, [(int(rng.integers(40, 151)), "M")], None, "m%d" % k) for k in range(7)]
     specs.sort(key=lambda r: r["pos"])
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     path = str(tmp_path / "deep.bam")
     bamwriter.write_bam(path, rd, ref_len=L, block=0xFF00)
     want = check_file(ctx, path, rd, 13)
@@ -239,14 +188,14 @@ def test_long_reads(ctx, tmp_path):
     what the packed set leaves out), among short reads"""
     rng = np.random.default_rng(11)
     ref, _ = sy.make_reference(seed=3, L=L, cds=[])
-    specs = rf._background(rng, ref, 200)
+    specs = rsp.background(rng, ref, 200)
     for k, span in enumerate((520, 555, 599, 700, 700)):
         a, b = int(rng.integers(100, 250)), 7
         specs.append(fz._read(rng, ref, 50 + 90 * k, [(a, "M"), (3, "I"), (120, "M"), (b, "D"), (span - a - 120 - b, "M")], 16 * (k & 1), "long%d" % k))
     for r in specs:
         r["mapq"] = 60
     specs.sort(key=lambda r: r["pos"])
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     path = str(tmp_path / "long.bam")
     bamwriter.write_bam(path, rd, ref_len=L, block=4096)
     want = check_file(ctx, path, rd, 13)
@@ -277,7 +226,7 @@ def test_long_reads(ctx, tmp_path):
 
 @pytest.mark.gpu
 def test_floor_zero_and_the_read_set_remembers(ctx, tmp_path):
-    rd = rf.arrays(rf.mixed()[2])
+    rd = rsp.arrays(rsp.mixed()[2])
     want13, n_pos = mixed_oracle(13)
     path = str(tmp_path / "A.bam")
     bamwriter.write_bam(path, rd, ref_len=L, block=4096)
@@ -312,11 +261,11 @@ def test_floor_zero_and_the_read_set_remembers(ctx, tmp_path):
 @pytest.mark.gpu
 def test_together_with_the_read_filter(ctx, tmp_path):
     f = (20, 0, 0x400)
-    specs = rf.mixed()[2]
-    b, n_fail = rf.kept(specs, f)
-    rb = rf.arrays(b)
+    specs = rsp.mixed()[2]
+    b, n_fail = rsp.kept(specs, f)
+    rb = rsp.arrays(b)
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(specs), ref_len=L, block=4096)
+    bamwriter.write_bam(path, rsp.arrays(specs), ref_len=L, block=4096)
     n_pos = c_oracle.extent(rb, L)
     want = oracle_counts(rb, 13, n_pos)                                         # the oracle on the records that pass
     for how in PACKERS:
@@ -330,49 +279,34 @@ def test_together_with_the_read_filter(ctx, tmp_path):
 def test_one_file_over_three_ranks(tmp_path, split_sub):
     """split_ranks_in_turn(world = 3, min_baseq = 13): the ranges in one piece, and as two sub-ranges each (the helper contexts take
     the floor along).  The sub-range file holds every record four times: its oracle is four times the fixture's."""
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     want, n_pos = mixed_oracle(13)
     times = 1 if split_sub == 1 else 4
     big = specs if times == 1 else sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in specs], key=lambda r: r["pos"])
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(big), ref_len=L, block=1024 if split_sub == 2 else 4096)
+    bamwriter.write_bam(path, rsp.arrays(big), ref_len=L, block=1024 if split_sub == 2 else 4096)
     tm = {}
-    ta = distributed.split_ranks_in_turn(path, n_pos, rf._gff(orfs), 10, 3, return_parts=True, min_baseq=13, split_sub=split_sub, timings=tm)
-    tb = distributed.split_ranks_in_turn(path, n_pos, rf._gff(orfs), 10, 1, return_parts=True, min_baseq=13, split_sub=1)
+    ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, min_baseq=13, split_sub=split_sub, timings=tm)
+    tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, min_baseq=13, split_sub=1)
     assert np.array_equal(ta[1], times * want)
     assert ta[0] == tb[0] and np.array_equal(ta[1], tb[1]) and ta[2] == tb[2]
     assert (tm["split_sub_taken"] > 0) == (split_sub == 2)
 
 
-def _two_contigs():
-    rng = np.random.default_rng(8)
-    recs, rows, specs = [], [], []
-    for t, (name, ln) in enumerate((("c0", 1500), ("c1", 1200))):
-        ref, orfs = sy.make_reference(seed=30 + t, L=ln, cds=[(100, 700)])
-        recs.append((name, ref))
-        rows.append((name, orfs))
-        part = rf._background(rng, ref, 500, tid=t, tag=name)
-        part += fz._site(rng, ref, ln, 800, name, t, 100, "MI", 3, False)
-        specs += sorted(part, key=lambda r: r["pos"])
-    for r in specs:
-        r["mapq"] = 60
-    return recs, rows, specs
-
-
 @pytest.mark.gpu
 def test_two_reference_contig_layout(ctx, tmp_path):
     """the several-kernel packer under a contig layout: every contig's slice of the matrix equals the oracle on that contig's reads"""
-    recs, _, specs = _two_contigs()
+    recs, _, specs = two_contigs()
     refs = [("c0", 1500), ("c1", 1200)]
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(specs), refs=refs, block=4096)
+    bamwriter.write_bam(path, rsp.arrays(specs), refs=refs, block=4096)
     shift, slot, axis = contigs.layout_for(recs, [n for n, _ in refs], [ln for _, ln in refs])
     t0 = ctx.stat("one_sync_taken")
     counts = contigs.step_contigs(ctx, path, shift, slot, axis, 10, True, [n for n, _ in refs], want_counts=True, min_baseq=13)[3]
     assert ctx.stat("one_sync_taken") == t0
     seen = np.zeros(axis, bool)
     for t, (_, ln) in enumerate(refs):
-        rd = rf.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
+        rd = rsp.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
         n_pos = c_oracle.extent(rd, ln)
         want = oracle_counts(rd, 13, n_pos)
         assert 0.3 < want[:, 0].sum() / oracle_counts(rd, 0, n_pos)[:, 0].sum() < 0.95
@@ -383,7 +317,7 @@ def test_two_reference_contig_layout(ctx, tmp_path):
 
 @pytest.mark.gpu
 def test_flat_array_entry_points_refuse(ctx):
-    rd = rf.arrays(rf.mixed()[2][:300])
+    rd = rsp.arrays(rsp.mixed()[2][:300])
     n_pos = c_oracle.extent(rd, L)
     p = engine.Pipeline(device=0, slots=2, walkers=1)
     try:
@@ -406,23 +340,6 @@ def test_flat_array_entry_points_refuse(ctx):
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
-def _write_override(path, counts):
-    """gzipped CSV (position, coverage, A, T, C, G, X, I) over every position"""
-    with gzip.open(path, "wt") as fh:
-        fh.write("," + ",".join(_ffi.COLS) + "\n")
-        for i, row in enumerate(counts, 1):
-            fh.write("%d,%s\n" % (i, ",".join(str(int(v)) for v in row)))
-
-
-def _doc_column(path):
-    return [int(ln.split("\t")[1]) for ln in open(path).read().split("\n") if ln.strip()]
-
-
-def _setup_cli(tmp_path, ref, orfs, seqid="ref"):
-    open("r.fa", "w").write(">%s x\n%s\n" % (seqid, ref))
-    head, body = sy.gff_text(orfs, seqid=seqid)
-    open("g.gff", "w").write(head + body)
-    return ["-ref", "r.fa", "-gff", "g.gff", "-cov", "10"]
 
 
 @pytest.mark.gpu
@@ -430,28 +347,28 @@ def test_cli_single_sample_and_batch(tmp_path, monkeypatch):
     """-i with --min-baseq 13: -doc is the oracle's coverage column; FASTA, VCF and GFF equal the run WITHOUT the flag whose counts
     --index-override replaces, at every position, by the oracle's Q 13 matrix (downstream code only).  --batch equals -i."""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     want, n_pos = mixed_oracle(13)
     assert n_pos == L
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     bamwriter.write_bam("A.bam", rd, ref_len=L, block=4096)
     bamwriter.write_bam("A2.bam", rd, ref_len=L, block=4096, split_records=True)
-    common = _setup_cli(tmp_path, ref, orfs)
-    _write_override("o.csv.gz", want)
+    common = cr.setup_cli(ref, orfs)
+    cr.write_override("o.csv.gz", want)
     out = lambda t: ["-o", t + ".fa", "-vcf", t + ".vcf", "-ogff", t + ".gff", "-doc", t + ".tsv"]
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--min-baseq", "13", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--index-override", "o.csv.gz", "--stats", "b.json"])
-    assert _doc_column("a.tsv") == want[:, 0].tolist()
-    assert rf._outputs("a") == rf._outputs("b")
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--min-baseq", "13", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--index-override", "o.csv.gz", "--stats", "b.json"])
+    assert cr.doc_column("a.tsv") == want[:, 0].tolist()
+    assert cr.outputs("a") == cr.outputs("b")
     assert json.load(open("a.json"))["min_baseq"] == 13 and json.load(open("b.json"))["min_baseq"] == 0
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "raw.fa", "-doc", "raw.tsv"])   # (the process's context is back at no floor)
-    assert _doc_column("raw.tsv") == mixed_oracle(0)[0][:, 0].tolist() and open("raw.fa").read() != open("a.fa").read()
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "raw.fa", "-doc", "raw.tsv"])   # (the process's context is back at no floor)
+    assert cr.doc_column("raw.tsv") == mixed_oracle(0)[0][:, 0].tolist() and open("raw.fa").read() != open("a.fa").read()
     with open("m.tsv.in", "w") as fh:
         for k, bam in enumerate(("A.bam", "A2.bam")):
             fh.write("\t".join([bam, "S"] + ["m%d.%s" % (k, e) for e in ("fa", "vcf", "gff", "tsv")]) + "\n")
-    rf._run_cli(monkeypatch, ["--batch", "m.tsv.in"] + common + ["--min-baseq", "13"])
+    cr.run_cli(monkeypatch, ["--batch", "m.tsv.in"] + common + ["--min-baseq", "13"])
     for k in (0, 1):
-        assert rf._outputs("m%d" % k) == rf._outputs("a"), k
+        assert cr.outputs("m%d" % k) == cr.outputs("a"), k
 
 
 @pytest.mark.gpu
@@ -459,18 +376,14 @@ def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
     """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange) refuses --index-override: -doc is the oracle's coverage
     and every output equals the single-GPU run of the same file under the same floor."""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     want, _ = mixed_oracle(13)
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=L, block=4096, split_records=True)
-    common = _setup_cli(tmp_path, ref, orfs)
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=ROOT)
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=L, block=4096, split_records=True)
+    common = cr.setup_cli(ref, orfs)
     for tag, extra in (("a", ["--gpus", "2"]), ("b", [])):
-        argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", "A.bam", "-name", "S"] + common + \
-            ["-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv", "--min-baseq", "13"] + extra
-        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-1500:]
-    assert _doc_column("a.tsv") == want[:, 0].tolist()
-    assert rf._outputs("a") == rf._outputs("b")
+        cr.run_two_ranks(["-i", "A.bam", "-name", "S"] + common + cr.out_args(tag) + ["--min-baseq", "13"] + extra)
+    assert cr.doc_column("a.tsv") == want[:, 0].tolist()
+    assert cr.outputs("a") == cr.outputs("b")
 
 
 @pytest.mark.gpu
@@ -478,29 +391,23 @@ def test_cli_per_contig(tmp_path, monkeypatch):
     """--per-contig refuses --index-override: per contig, -doc is the oracle's coverage and the FASTA record equals the single run
     of that contig's reads alone under the same floor."""
     monkeypatch.chdir(tmp_path)
-    recs, rows, specs = _two_contigs()
+    recs, rows, specs = two_contigs()
     refs = [("c0", 1500), ("c1", 1200)]
-    bamwriter.write_bam("A.bam", rf.arrays(specs), refs=refs, block=4096)
-    with open("r.fa", "w") as fh:
-        for name, ref in recs:
-            fh.write(">%s\n%s\n" % (name, ref))
-    with open("g.gff", "w") as fh:
-        fh.write("##gff-version 3\n")
-        for name, orfs in rows:
-            fh.write(sy.gff_text(orfs, seqid=name)[1])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "-o", "a.fa", "-doc", "a.tsv",
-                              "--per-contig", "--min-baseq", "13", "--stats", "a.json"])
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), refs=refs, block=4096)
+    cr.setup_contigs(recs, rows)
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "-o", "a.fa", "-doc", "a.tsv",
+                             "--per-contig", "--min-baseq", "13", "--stats", "a.json"])
     assert json.load(open("a.json"))["min_baseq"] == 13
     want_fa, want_tsv = "", ""
     for t, (name, ln) in enumerate(refs):
-        rd = rf.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
+        rd = rsp.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
         want = oracle_counts(rd, 13, c_oracle.extent(rd, ln))
         bamwriter.write_bam("one%d.bam" % t, rd, refs=[(name, ln)], block=4096)
         open("r%d.fa" % t, "w").write(">%s\n%s\n" % recs[t])
         open("g%d.gff" % t, "w").write("##gff-version 3\n" + sy.gff_text(rows[t][1], seqid=name)[1])
-        rf._run_cli(monkeypatch, ["-i", "one%d.bam" % t, "-ref", "r%d.fa" % t, "-gff", "g%d.gff" % t, "-cov", "10", "-name", "S_" + name,
-                                  "-o", "one%d.fa" % t, "-doc", "one%d.tsv" % t, "--min-baseq", "13"])
-        assert _doc_column("one%d.tsv" % t) == want[:, 0].tolist()
+        cr.run_cli(monkeypatch, ["-i", "one%d.bam" % t, "-ref", "r%d.fa" % t, "-gff", "g%d.gff" % t, "-cov", "10", "-name", "S_" + name,
+                                 "-o", "one%d.fa" % t, "-doc", "one%d.tsv" % t, "--min-baseq", "13"])
+        assert cr.doc_column("one%d.tsv" % t) == want[:, 0].tolist()
         want_fa += open("one%d.fa" % t).read()
         want_tsv += "".join("%s\t%s" % (name, line) for line in open("one%d.tsv" % t))
     assert open("a.fa").read() == want_fa and want_fa.count(">") == 2

@@ -2,47 +2,28 @@
 header, the record-chain rule) in a program of its own — tests/bgzf_host_main.cpp, built here with AddressSanitizer + UBSan and run
 as a child process — against a restatement of the format in this file (struct + zlib), on intact files and on damaged ones: the same
 verdict, the same tables, and no report from either sanitizer (a report ends the program with a non-zero status)."""
-import os
-import shutil
 import struct
-import subprocess
 import zlib
 
 import numpy as np
 import pytest
 
-from tests import test_bam_fixture as hand
+from tests import hand_bam as hand
+from tests import host_program
+from tests.hand_bam import EOF_BLOCK, long_header_bam, small_reads
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 E_FORMAT = -5
-EOF_BLOCK = hand.EOF_BLOCK
 
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("bgzf_host") / "bgzf_host_main")
-    src = [os.path.join(ROOT, "tests", "bgzf_host_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "bgzf_host.cpp")]
-    rocm_clang = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++")
-    tried = []
-    for cxx in (rocm_clang, shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
-                            "-Wall", "-Wextra", "-o", out] + src + ["-lz"], capture_output=True, text=True)
-        if r.returncode == 0:
-            return out
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    pytest.fail("no C++ compiler built the program:\n" + "\n".join(tried))
+    return host_program.build(["tests/bgzf_host_main.cpp", "trueconsense_amd/csrc/bgzf_host.cpp"], tmp_path_factory.mktemp("bgzf_host") / "bgzf_host_main", libs=["-lz"])
 
 
 def run(prog, *args):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([prog] + list(args), capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
-    return r.stdout
+    return host_program.run(prog, *args).stdout
 
 
 def split_output(text):
@@ -179,19 +160,6 @@ def compare(prog, mode, paths):
         assert got[p] == want, (p, [(g, w) for g, w in zip(got[p], want) if g != w][:3], len(got[p]), len(want))
         verdicts.append(want[0].split()[0])
     return out, verdicts
-
-
-def small_reads(n=400, seed=3):
-    ref, _ = sy.make_reference()
-    return sy.make_reads(ref[:3000], n, seed=seed, indel_sites=None)
-
-
-def long_header_bam(path):
-    """A header of several blocks (300 @SQ with long names, block = 700) whose first record starts in the middle of a block."""
-    refs = [("contig_%04d_with_a_rather_long_name_as_assemblies_have_them" % k, 1000 + k) for k in range(300)]
-    refs[0] = (refs[0][0], 3000)
-    bamwriter.write_bam(path, small_reads(), block=700, split_records=True, refs=refs)
-    return refs
 
 
 def test_block_table_and_header_match_the_restatement(prog, tmp_path):

@@ -2,15 +2,12 @@
 No GPU: only argument handling runs."""
 import pytest
 
+from tests.cli_run import ROOT, stub_files
 from trueconsense_amd import TrueConsense as cli
 
 
 def _files(tmp_path):
-    p = {}
-    for name in ("x.bam", "r.fa", "r.fasta", "f.gff", "o.csv.gz", "bad.txt"):
-        (tmp_path / name).write_text("x")
-        p[name] = str(tmp_path / name)
-    return p
+    return stub_files(tmp_path, ("x.bam", "r.fa", "r.fasta", "f.gff", "o.csv.gz", "bad.txt"))
 
 
 def test_all_flags_parse(tmp_path):
@@ -98,8 +95,7 @@ def test_console_scripts_of_the_reference_are_declared():
     import importlib
     import os
     import tomli
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    with open(os.path.join(root, "pyproject.toml"), "rb") as fh:
+    with open(os.path.join(ROOT, "pyproject.toml"), "rb") as fh:
         scripts = tomli.load(fh)["project"]["scripts"]
     assert set(scripts) == {"trueconsense", "TrueConsense"}
     for target in scripts.values():

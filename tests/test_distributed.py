@@ -9,6 +9,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests.consensus_case import consensus_case, oracle_fasta
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -36,32 +38,13 @@ def _worker(rank, world, port, use_gpu, q):
         dist.destroy_process_group()
 
 
-def _consensus_case():
-    """An indel-carrier read set whose insert-candidate columns lie around the middle of the file (where two ranks' ranges meet):
-    accepted insertions of 1, 2 and 14 bases (the last too long for an entry's key: its bases travel as text), a rejected one."""
-    from trueconsense_amd import synthetic as sy
-    ref, orfs = sy.make_reference(L=4000, cds=[(100, 1900), (2100, 3900)])
-    sites = [(1900, "I", "A", 0.9), (1990, "I", "GT", 0.7), (2005, "I", "ACGTACGTACGTAC", 0.8), (2010, "D", 3, 0.6), (2100, "I", "C", 0.4), (3000, "I", "TT", 0.95)]
-    reads = sy.make_reads(ref, 6000, seed=91, indel_sites=sites)
-    return ref, orfs, reads
-
-
-def _oracle_fasta(reads, orfs, L, mincov):
-    from oracle import c_oracle
-    from oracle import tc_oracle as orc
-    counts = c_oracle.tally(reads, L)
-    has, ins = orc.list_inserts(counts, mincov, lambda pos1: orc.region_tokens(reads, pos1))
-    cons, _ = orc.build_consensus(mincov, counts.astype(np.int64), [dict(o) for o in orfs], True, ins if has else None, True)
-    return orc.fasta_text("S", mincov, cons), ins if has else {}
-
-
 def _work_consensus(rank, world, use_gpu, td, c_oracle):
     """configs[4] to the consensus: two ranks, candidate columns on both sides of the boundary; FASTA = the oracle chain's on the whole file."""
     import torch.distributed as dist
-    ref, orfs, reads = _consensus_case()
+    ref, orfs, reads = consensus_case()
     L = len(ref)
     rows = [{"start": o["start"], "end": o["end"], "strand": "+"} for o in orfs]
-    want, ins = _oracle_fasta(reads, orfs, L, 30)
+    want, ins = oracle_fasta(reads, orfs, L, 30)
     assert len(ins) >= 4 and any(len(next(iter(v.values()))) > 12 for v in ins.values())
     if use_gpu:
         import tempfile
@@ -345,8 +328,8 @@ def test_configs4_eight_ranks_in_turn_on_one_gpu(tmp_path):
     cons, _ = orc.build_consensus(30, want, [dict(o) for o in orfs], True, ins if has else None, True)
     assert text == orc.fasta_text("S", 30, cons)
     # (2)
-    ref2, orfs2, reads2 = _consensus_case()
-    want2, ins2 = _oracle_fasta(reads2, orfs2, len(ref2), 30)
+    ref2, orfs2, reads2 = consensus_case()
+    want2, ins2 = oracle_fasta(reads2, orfs2, len(ref2), 30)
     assert len(ins2) >= 4
     bamwriter.write_bam(path, reads2, "r", len(ref2), level=6, block=3000, split_records=True)
     rows2 = [{"start": o["start"], "end": o["end"], "strand": "+"} for o in orfs2]

@@ -4,127 +4,24 @@ random long reads (the by_token branch of tally_stream_kernel), random primer ta
 slack), tables of more than 256 segments (the packer kernels then search the table in global memory, not their LDS copy), depth
 past 255 with a different drop word per read, records that straddle BGZF blocks, block ranges, a contig layout.  The yardstick
 everywhere is tests/primer_yardstick.counts on the records that pass the read filter; the device is driven through
-test_primer_mask.through (both packers).  The constructed edges live in test_base_quality.py and test_primer_mask.py."""
+tests/device_file.through (both packers).  The constructed edges live in test_base_quality.py and test_primer_mask.py."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
 from oracle import c_oracle
+from tests import cli_run as cr
+from tests import device_file as dvf
 from tests import fuzz_masked as fm
 from tests import primer_yardstick as py
-from tests import synth_small as ss
-from tests import test_base_quality as bq
-from tests import test_primer_mask as pm
-from tests import test_read_filter as rf
+from tests import read_specs as rsp
+from tests import schemes as sch
+from tests.fuzz_masked import CONTIGS, DEEP_SEED, DEEP_WINDOW, MODES, SEEDS, F, L, NONE, contig_case, differ, fuzz, n_long, passing, profile, table_of, write, yardstick
 from trueconsense_amd import _ffi, contigs, distributed, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
 from trueconsense_amd.io import primers as pbed
-
-L = rf.L
-SEEDS = (1, 2, 3, 4)
-DEEP_SEED, DEEP_WINDOW = 5, (975, 1025)                                          # (narrowed from (900, 1100) until the depth passes 255)
-F = (20, 0, 0x800)
-NONE = (0, 0, 0)
-LONG = 512                                                                      # a read of more columns is left to tally_stream_kernel
-# mode -> (under the seed's table?, slack, floor, read filter)
-MODES = {"floor": (False, 0, 13, NONE), "table": (True, 0, 0, NONE), "all": (True, 3, 13, F)}
-CONTIGS = (("c0", 1500, 11), ("c1", 1200, 12))                                  # name, columns, seed
-
-
-# ------------------------------------------------------------------------------------------------------------------------ inputs
-@functools.lru_cache(maxsize=None)
-def table_of(key):
-    """key: a seed's random table, or ("dense", n, plus_only)"""
-    return tuple(fm.dense_table(*key[1:])) if isinstance(key, tuple) else tuple(fm.primers(key))
-
-
-@functools.lru_cache(maxsize=None)
-def fuzz(seed, key=None, window=None):
-    """the records of a seed, their insertion sites planted on the mask edges of table_of(key) (key None: the seed's own table)"""
-    return fm.specs(seed, table=table_of(seed if key is None else key), window=window)
-
-
-@functools.lru_cache(maxsize=None)
-def passing(seed, key=None, window=None, f=NONE):
-    """-> (the records that pass f, their arrays)"""
-    specs = fuzz(seed, key, window)
-    b = rf.kept(specs, f)[0] if f != NONE else specs
-    return b, rf.arrays(b)
-
-
-@functools.lru_cache(maxsize=None)
-def yardstick(seed, key=None, window=None, f=NONE, table=False, q=0, slack=0):
-    return py.counts(passing(seed, key, window, f)[1], L, table_of(seed if key is None else key) if table else (), q, slack)
-
-
-def _ops(r):
-    return ss.parse_cigar(r["cigar"])                                           # [(op index in "MIDNSHP=X", length)]
-
-
-def _span(r):
-    return sum(n for op, n in _ops(r) if op in (0, 2, 3, 7, 8))
-
-
-def _piles_up(r):
-    return not r["flag"] & 4 and r.get("tid", 0) >= 0 and _span(r) > 0
-
-
-def covering(specs, c):
-    """name, POS, CIGAR and len(SEQ) of every piled-up record over 0-based column c"""
-    return [(r["name"], r["pos"], r["cigar"], 0 if r["seq"] == "*" else len(r["seq"])) for r in specs
-            if _piles_up(r) and r["pos"] <= c < r["pos"] + _span(r)]
-
-
-def differ(got, want, specs, label):
-    """'' when the matrices are equal; else what a failure is analysed from without another run: the label (seed, mode, packer), the
-    first eight differing columns with both rows, and every passing record over the first of them"""
-    if got.shape == want.shape and np.array_equal(got, want):
-        return ""
-    if got.shape != want.shape:
-        return "%r: shape %r, the yardstick's %r" % (label, got.shape, want.shape)
-    cols = np.unique(np.argwhere(got != want)[:, 0])[:8].tolist()
-    rows = ["column %d: got %r want %r" % (c, got[c].tolist(), want[c].tolist()) for c in cols]
-    reads = ["%s POS %d %s len(seq) %d" % t for t in covering(specs, cols[0])]
-    return "%r (coverage, A, T, C, G, X, I)\n%s\nrecords over column %d:\n%s" % (label, "\n".join(rows), cols[0], "\n".join(reads))
-
-
-def profile(specs, table, slack):
-    """what the non-vacuity conditions count, on records that all pass the filter"""
-    ops, lead = set(), dict.fromkeys("DNIP", 0)
-    n_long = n_long_masked = n_masked = crossing = star = short = noqual = 0
-    for r in specs:
-        if not _piles_up(r):
-            continue
-        cig = _ops(r)
-        ops.update("MIDNSHP=X"[op] for op, _ in cig)
-        first = next("MIDNSHP=X"[op] for op, _ in cig if op not in (4, 5))
-        if first in lead:
-            lead[first] += 1
-        p, span = r["pos"], _span(r)
-        he, ts = py.read_mask(p, p + span - 1, table, slack)
-        masked = he > p or ts <= p + span - 1
-        n_masked += masked
-        if span > LONG:
-            n_long += 1
-            n_long_masked += masked
-        x = p
-        for op, n in cig:
-            if op in (2, 3):
-                crossing += x < he < x + n or x < ts < x + n
-            if op in (0, 2, 3, 7, 8):
-                x += n
-        qlen = sum(n for op, n in cig if op in (0, 1, 4, 7, 8))
-        star += r["seq"] == "*"
-        short += r["seq"] != "*" and len(r["seq"]) < qlen
-        noqual += bool(r["qual"]) and r["qual"][0] == 255
-    return dict(ops=ops, lead=lead, long=n_long, long_masked=n_long_masked, masked=n_masked, crossing=crossing, star=star, short=short, noqual=noqual)
-
-
-def n_long(specs):
-    return sum(_piles_up(r) and _span(r) > LONG for r in specs)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ CPU
@@ -135,7 +32,7 @@ def test_the_yardsticks_agree_on_the_fuzz(seed):
     specs, rd = passing(seed)
     n_pos = c_oracle.extent(rd, L)
     for q in (1, 13, 42, 255):
-        msg = differ(py.counts(rd, L, (), q)[0], bq.oracle_counts(rd, q, n_pos), specs, (seed, "q", q))
+        msg = differ(py.counts(rd, L, (), q)[0], rsp.oracle_counts(rd, q, n_pos), specs, (seed, "q", q))
         assert not msg, msg
     msg = differ(yardstick(seed)[0], c_oracle.tally(rd, n_pos), specs, (seed, "q", 0))
     assert not msg, msg
@@ -144,7 +41,7 @@ def test_the_yardsticks_agree_on_the_fuzz(seed):
 @pytest.mark.parametrize("seed", SEEDS)
 def test_the_inputs_are_not_vacuous(seed):
     """conditions on the generator, per seed, on the records that pass the filter, under the seed's table with slack 3 and floor 13"""
-    specs, rd = passing(seed, f=F)                                              # (rf.kept: 20 - 60 % of the records fail)
+    specs, rd = passing(seed, f=F)                                              # (read_specs.kept: 20 - 60 % of the records fail)
     table = table_of(seed)
     got = profile(specs, table, 3)
     assert got["ops"] == set("MIDNSHP=X"), got
@@ -160,9 +57,9 @@ def test_the_inputs_are_not_vacuous(seed):
 
 def test_dense_tables_compile_to_the_segment_counts_the_device_tests_rely_on():
     for n, plus_only, want in ((256, False, 256), (257, False, 257), (300, False, 300)):
-        rc, head, tail, msg = pm._compile(fm.dense_table(n, plus_only), 0)
+        rc, head, tail, msg = sch.compile_primers(fm.dense_table(n, plus_only), 0)
         assert rc == 0 and len(head) + len(tail) == want and len(head) == (n + 1) // 2, (n, msg)
-    rc, head, tail, msg = pm._compile(fm.dense_table(257, plus_only=True), 0)
+    rc, head, tail, msg = sch.compile_primers(fm.dense_table(257, plus_only=True), 0)
     assert rc == 0 and (len(head), len(tail)) == (257, 0), msg
 
 
@@ -173,20 +70,13 @@ def ctx():
         yield c
 
 
-def write(tmp_path, specs, **kw):
-    path = str(tmp_path / "A.bam")
-    kw.setdefault("block", 4096)
-    bamwriter.write_bam(path, rf.arrays(specs), ref_len=L, **kw)
-    return path
-
-
 def check(ctx, path, specs, want, label, primers=(), q=0, f=NONE, slack=0):
     """test_primer_mask.check_file with a message a failure is analysed from: both packers equal the yardstick `want` (on `specs`, the
     records that pass f); the piled-up count and the extent are those of the same file without a table"""
     n_pos = len(want[0])
-    for how in pm.PACKERS:
-        got, piled, end, n_prim, n_masked = pm.through(ctx, how, path, primers, n_pos, q, f, slack)
-        _, piled0, end0, n_prim0, n_masked0 = pm.through(ctx, how, path, (), n_pos, q, f)
+    for how in dvf.PACKERS:
+        got, piled, end, n_prim, n_masked = dvf.through(ctx, how, path, primers, n_pos, q, f, slack)
+        _, piled0, end0, n_prim0, n_masked0 = dvf.through(ctx, how, path, (), n_pos, q, f)
         msg = differ(got, want[0], specs, label + (how,))
         assert not msg, msg
         assert (piled, end, n_prim, n_masked, n_prim0, n_masked0) == (piled0, end0, len(primers), want[1], 0, 0), label + (how,)
@@ -204,7 +94,7 @@ def check_mode(ctx, path, seed, mode, key=None, window=None, q=None):
 def check_routing(ctx, path, seed, specs, want):
     """the combined mode: every piled-up read of more than 512 columns is left out of the packed set and walked by tally_stream_kernel,
     one launch in the general-tally bracket and one of the plane kernel per step (as test_primer_mask.test_long_reads asserts it)"""
-    for how in pm.PACKERS:
+    for how in dvf.PACKERS:
         try:
             ctx.set_option("one_sync", int(how == "one_sync"))
             ctx.set_read_filter(*F)
@@ -266,10 +156,10 @@ def test_short_records_that_straddle_small_blocks(ctx, tmp_path):
     block boundaries, on random CIGARs"""
     seed, (_, slack, q, f) = SEEDS[1], MODES["all"]
     table = table_of(seed)
-    kept = rf.kept(fm.specs(seed, n_long=0, table=table), f)[0]
+    kept = rsp.kept(fm.specs(seed, n_long=0, table=table), f)[0]
     assert n_long(kept) == 0 and profile(kept, table, slack)["masked"] >= 100
     path = write(tmp_path, fm.specs(seed, n_long=0, table=table), block=512, split_records=True)
-    check(ctx, path, kept, py.counts(rf.arrays(kept), L, table, q, slack), (seed, "all, short reads", q), table, q, f, slack)
+    check(ctx, path, kept, py.counts(rsp.arrays(kept), L, table, q, slack), (seed, "all, short reads", q), table, q, f, slack)
 
 
 @pytest.mark.gpu
@@ -322,8 +212,8 @@ def test_block_ranges_over_three_ranks(tmp_path, split_sub):
     path = write(tmp_path, big, block=1024 if split_sub == 2 else 4096)
     tm = {}
     kw = dict(return_parts=True, primers=(table, 3), min_baseq=13, read_filter=F)
-    ta = distributed.split_ranks_in_turn(path, n_pos, rf._gff(orfs), 10, 3, split_sub=split_sub, timings=tm, **kw)
-    tb = distributed.split_ranks_in_turn(path, n_pos, rf._gff(orfs), 10, 1, split_sub=1, **kw)
+    ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, split_sub=split_sub, timings=tm, **kw)
+    tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, split_sub=1, **kw)
     msg = differ(ta[1], times * want, kept, (seed, "all", "three ranks", split_sub))
     assert not msg, msg
     msg = differ(ta[1], tb[1], kept, (seed, "all", "three ranks against one", split_sub))
@@ -331,21 +221,9 @@ def test_block_ranges_over_three_ranks(tmp_path, split_sub):
     assert (tm["split_sub_taken"] > 0) == (split_sub == 2)
 
 
-@functools.lru_cache(maxsize=None)
-def contig_case():
-    """-> ([(name, columns, that contig's table, its records with tid = its index)], every record in file order)"""
-    parts, specs = [], []
-    for t, (name, ln, seed) in enumerate(CONTIGS):
-        table = fm.primers(seed, L=ln, n=30)
-        part = fm.specs(seed, n_short=800, n_long=150, L=ln, refname_tid=t, table=table)
-        parts.append((name, ln, table, part))
-        specs += part
-    return parts, specs
-
-
 def test_the_contig_inputs_are_not_vacuous():
     for name, ln, table, part in contig_case()[0]:
-        got = profile(rf.kept(part, F)[0], table, 0)
+        got = profile(rsp.kept(part, F)[0], table, 0)
         assert got["long"] >= 3 and got["long_masked"] >= 1 and got["masked"] >= 30, (name, got)
 
 
@@ -357,7 +235,7 @@ def test_two_reference_contig_layout(ctx, tmp_path):
     refs = [(name, ln) for name, ln, _ in CONTIGS]
     names = [n for n, _ in refs]
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(specs), refs=refs, block=4096)
+    bamwriter.write_bam(path, rsp.arrays(specs), refs=refs, block=4096)
     recs = [(name, sy.make_reference(seed=3, L=ln, cds=[])[0]) for name, ln in refs]
     shift, slot, axis = contigs.layout_for(recs, names, [ln for _, ln in refs])
     rows = pbed.rows_for_layout([(name, s, e, rev) for name, _, table, _ in parts for s, e, rev in table], names, shift)
@@ -367,9 +245,9 @@ def test_two_reference_contig_layout(ctx, tmp_path):
     seen = np.zeros(axis, bool)
     n_masked = 0
     for t, (name, ln, table, part) in enumerate(parts):
-        kept = [dict(r, tid=0) for r in rf.kept(part, F)[0]]
+        kept = [dict(r, tid=0) for r in rsp.kept(part, F)[0]]
         assert n_long(kept) >= 3
-        want = py.counts(rf.arrays(kept), ln, table, 13)
+        want = py.counts(rsp.arrays(kept), ln, table, 13)
         n_pos = len(want[0])
         n_masked += want[1]
         msg = differ(counts[int(shift[t]):int(shift[t]) + n_pos], want[0], kept, (name, "contig layout"))

@@ -11,6 +11,8 @@ import pytest
 
 from oracle import c_oracle
 from oracle import tc_oracle as orc
+from tests import cli_run
+from tests import host_pack_program as hp
 from tests import synth_small as ss
 from trueconsense_amd import Events, Sequences, _ffi, _state, engine, indexing
 from trueconsense_amd import synthetic as sy
@@ -167,10 +169,9 @@ def test_device_packer_against_host_packer_and_oracle(ctx):
 
 
 def test_host_packer_program_and_library_report_the_same_read_set(ctx, tmp_path):
-    """tests/test_host_pack.py checks the host packer on the CPU, in a program of its own (tests/host_pack_main.cpp).  Here the library
+    """tests/test_host_pack.py checks the host packer on the CPU, in a program of its own (tests/host_pack_main.cpp, run through tests/host_pack_program.py).  Here the library
     packs two of that file's inputs with device_pack = 0 and the context's own options: what it says of the read set it uploaded is what
     the program reports for the same input and options, and the counts are the oracle's."""
-    from tests import test_host_pack as hp
     prog = hp.build_program(str(tmp_path / "host_pack_main"), sanitize=False)
     opt = dict(threads=8, slots=ctx.stat("compute_units") * 4)      # host_threads and wg_per_cu as a context starts with them
     try:
@@ -510,8 +511,6 @@ def test_cli_gpus_n_batch_shards_and_one_bam_split(ctx, tmp_path, monkeypatch):
     call.  --batch: the manifest dealt round-robin to N runners (configs[3]); -i: ONE BAM file shared by N ranks, a reduce of the count
     matrix, entries of the insert candidates gathered to rank 0 (configs[4]).  Rehearsed with N = 2 on this one GPU (gloo for the
     exchange): every output file byte-identical to the golden text / to the single-GPU command line."""
-    import subprocess
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     monkeypatch.chdir(tmp_path)
     case = next(c for c in load("outputs") if "raises" not in c["runs"]["amb1"] and c["runs"]["amb1"]["fa"].count("\n") == 2)
     spec, run = case["spec"], case["runs"]["amb1"]
@@ -525,9 +524,7 @@ def test_cli_gpus_n_batch_shards_and_one_bam_split(ctx, tmp_path, monkeypatch):
     with open("m.tsv", "w") as fh:
         for k in range(5):
             fh.write("in.bam\tSAMPLE\ts%d.fa\ts%d.vcf\ts%d.gff\ts%d.tsv\n" % (k, k, k, k))
-    base = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-ref", "ref.fa", "-gff", "f.gff", "-cov", str(spec["mincov"])]
-    r = subprocess.run(base + ["--batch=m.tsv", "--gpus", "2"], env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-1500:]
+    cli_run.run_two_ranks(["-ref", "ref.fa", "-gff", "f.gff", "-cov", str(spec["mincov"]), "--batch=m.tsv", "--gpus", "2"])
     for k in range(5):
         assert open("s%d.fa" % k).read() == run["fa"] and open("s%d.tsv" % k).read() == run["tsv"]
         assert open("s%d.gff" % k).read() == run["gff_cli"]
@@ -545,19 +542,13 @@ def test_cli_gpus_n_batch_shards_and_one_bam_split(ctx, tmp_path, monkeypatch):
         fh.write(head + body)
     outs = {}
     for tag, extra in (("one", []), ("two", ["--gpus", "2"])):
-        argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", "one.bam", "-ref", "r2.fa", "-gff", "g2.gff", "-cov", "30", "-name", "S",
-                "-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv"] + extra
-        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-1500:]
+        cli_run.run_two_ranks(["-i", "one.bam", "-ref", "r2.fa", "-gff", "g2.gff", "-cov", "30", "-name", "S"] + cli_run.out_args(tag) + extra)
         vcf = open(tag + ".vcf").read().split("\n")
         outs[tag] = (open(tag + ".fa").read(), open(tag + ".gff").read(), open(tag + ".tsv").read(), vcf[:1] + vcf[3:])
     assert outs["one"] == outs["two"]
     # ... and the split worker itself with the exchange it uses on a node of GPUs: the C hook over an RCCL communicator (one rank here)
-    argv = [sys.executable, "-m", "trueconsense_amd.split_main", "-i", "one.bam", "-ref", "r2.fa", "-gff", "g2.gff", "-cov", "30", "-name", "S",
-            "-o", "hook.fa", "-vcf", "hook.vcf", "-ogff", "hook.gff", "-doc", "hook.tsv", "--gpus", "1"]
-    env1 = {k: v for k, v in env.items() if k not in ("TCMI_SPLIT_ONE_GPU", "TCMI_SPLIT_BACKEND")}
-    r = subprocess.run(argv, env=dict(env1, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", TCMI_SPLIT_VERBOSE="1"), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-1500:]
+    r = cli_run.run_split_worker(["-i", "one.bam", "-ref", "r2.fa", "-gff", "g2.gff", "-cov", "30", "-name", "S"] + cli_run.out_args("hook") + ["--gpus", "1"],
+                                 env_extra={"TCMI_SPLIT_VERBOSE": "1"})
     assert "tcmi_rccl_reduce: ncclReduce" in r.stderr, r.stderr[-1500:]
     vcf = open("hook.vcf").read().split("\n")
     assert (open("hook.fa").read(), open("hook.gff").read(), open("hook.tsv").read(), vcf[:1] + vcf[3:]) == outs["one"]
@@ -583,7 +574,7 @@ def test_two_streams_per_context_give_the_same_outputs(tmp_path, monkeypatch):
         with open("m.tsv", "w") as fh:
             for k in range(6):
                 fh.write("in.bam\tSAMPLE\tm%s_%d.fa\tm%s_%d.vcf\tm%s_%d.gff\tm%s_%d.tsv\n" % ((mode, k) * 4))
-        env = dict(os.environ, TCMI_STREAM_SPLIT=mode, PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        env = dict(os.environ, TCMI_STREAM_SPLIT=mode, PYTHONPATH=cli_run.ROOT)
         r = subprocess.run([sys.executable, "-m", "trueconsense_amd.TrueConsense", "--batch", "m.tsv", "-ref", "ref.fa", "-gff", "f.gff", "-cov", str(spec["mincov"])],
                            env=env, capture_output=True, text=True, timeout=300)
         assert r.returncode == 0, (mode, r.stderr[-1500:])
@@ -926,7 +917,7 @@ def test_configs0_python_standin_beside_the_command_line(tmp_path):
     (TrueConsense.py:212-264 — oracle/tc_oracle.py end to end: per-token tally loop, ListInserts with region pile-ups, both BuildConsensus
     walks, the writers) beside the product's command line on the same BAM file: FASTA text, VCF records, corrected ORF coordinates and
     coverage TSV must be the same.  (bench.py's `configs0` leg, at its own size.)"""
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    sys.path.insert(0, cli_run.ROOT)
     import bench
     ref, orfs = sy.make_reference()
     r = bench.configs0_leg(np, sy, ref, orfs, len(ref), str(tmp_path), 30)

@@ -17,7 +17,7 @@ import pytest
 from oracle import c_oracle
 from tests import foreign_files as ff
 from tests import refused_streams as rf
-from tests.test_bam_device import check_counts, check_decode
+from tests.device_file import check_counts, check_decode
 from trueconsense_amd import _ffi, _state, engine
 
 pytestmark = pytest.mark.gpu

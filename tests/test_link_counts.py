@@ -6,21 +6,22 @@ SEQ '*', short SEQ, no QUAL, long reads, planted insertion sites) and hand-made 
 words that are checked after every call.  The rule, the writer and the argument handling are checked without a GPU in
 tests/test_links_rule.py."""
 import ctypes as C
-import functools
 import json
 import os
 
 import numpy as np
 import pytest
 
+from tests import cli_run as cr
+from tests import device_file as dvf
+from tests import fuzz_masked as fm
 from tests import links_yardstick as ly
 from tests import primer_yardstick as py
-from tests import test_base_quality as bq
-from tests import test_floor_mask_fuzz as ff
-from tests import test_matrix_abi as ma
-from tests import test_read_filter as rf
-from tests import test_strand_counts as sc
+from tests import read_specs as rsp
+from tests import strand_cases as stc
 from tests import variant_yardstick as vy
+from tests.device_file import uploaded
+from tests.link_cases import CIS, CL, LDS, LOW, MIXED, TRANS, G, L, W, classes_of, cli_case, device_links, differ, long_read_over, not_vacuous, sparse_columns, window_columns
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, contigs, engine
 from trueconsense_amd import distributed as td
@@ -29,12 +30,7 @@ from trueconsense_amd.io import bamwriter
 from trueconsense_amd.io import primers as pbed
 
 pytestmark = pytest.mark.gpu
-L = ff.L
-LDS = engine.LINKS_LDS
-G = 64                                                                          # guard words on either side of the records
-W = 52                                                                          # int32 words of a record
 KS = (1, 2, 7)
-uploaded = sc.uploaded
 
 
 @pytest.fixture(scope="module")
@@ -43,82 +39,13 @@ def ctx():
         yield c
 
 
-def device_links(ctx, rs, cols, k):
-    """tcmi_readset_link_counts into a host buffer between guards -> the records (LINK_DTYPE); a, b and reserved are checked here, and
-    Context.link_counts must give the same bytes (run after run)"""
-    cols = np.ascontiguousarray(cols, np.int64)
-    n = len(cols)
-    buf = ma.sentinel(2 * G + W * n * k, np.int32, salt=11).copy()
-    before = buf.copy()
-    rc = _ffi.lib().tcmi_readset_link_counts(ctx.handle, rs.handle, n, _ffi.ptr(cols), k, C.c_void_p(buf.ctypes.data + 4 * G))
-    _ffi.check(rc, ctx.handle)
-    assert np.array_equal(buf[:G], before[:G]) and np.array_equal(buf[-G:], before[-G:]), "a guard around the records was written"
-    got = buf[G:-G].view(engine.LINK_DTYPE).copy()
-    want = ly.records(cols.tolist(), k, np.zeros((n * k, 7, 7), np.int32))
-    assert np.array_equal(got["a"], want["a"]) and np.array_equal(got["b"], want["b"]) and not got["reserved"].any()
-    assert not got["j"][got["b"] < 0].any() and not got["j"][:, 0, 0].any()
-    again = ctx.link_counts(rs, cols, k)
-    assert again.tobytes() == got.tobytes()
-    return got
-
-
-def differ(got, want_j, label):
-    """'' when the records' counts equal the yardstick's; else the first differing pairs with both matrices"""
-    if np.array_equal(got["j"], want_j):
-        return ""
-    rows = []
-    for p in np.unique(np.argwhere(got["j"] != want_j)[:, 0])[:4].tolist():
-        rows.append("pair (%d, %d): got\n%r\nwant\n%r" % (got["a"][p], got["b"][p], got["j"][p], want_j[p]))
-    return "%r (classes none, A, T, C, G, X, coverage only)\n%s" % (label, "\n".join(rows))
-
-
-@functools.lru_cache(maxsize=None)
-def classes_of(seed, mode, window=None):
-    """-> (class matrix [passing records, n_pos], n_pos, the yardstick's count matrix) of a fuzz seed under a mode"""
-    tabled, slack, q, f = ff.MODES[mode]
-    _, rd = ff.passing(seed, None, window, f)
-    whole = ff.yardstick(seed, None, window, f, tabled, q, slack)[0]
-    return ly.classes(rd, L, ff.table_of(seed) if tabled else (), q, slack, n_pos=len(whole)), len(whole), whole
-
-
-def sparse_columns(seed, n_pos, n=24, edges=8):
-    """24 random columns and columns on both sides of mask edges of the seed's table: at most 40, staged with one and two neighbours"""
-    rng = np.random.default_rng(700 + seed)
-    cols = set(int(c) for c in rng.choice(n_pos, n, replace=False))
-    for s, e, rev in ff.table_of(seed)[:edges]:
-        edge = s if rev else e
-        cols.update(c for c in (edge - 1, edge) if 0 <= c < n_pos)
-    assert len(cols) * 2 <= LDS
-    return sorted(cols)
-
-
-def window_columns(whole, width=300):
-    """every column of the 300-column window with the most coverage"""
-    cov = np.convolve(whole[:, 0].astype(np.int64), np.ones(width, np.int64), "valid")
-    s = int(np.argmax(cov))
-    return list(range(s, s + width))
-
-
-def long_read_over(specs, cols, at_least=3):
-    """does a long read (one the tally leaves to its per-token kernel) lie over several of the queried columns?"""
-    return any(ff._piles_up(r) and ff._span(r) > ff.LONG and sum(r["pos"] <= c < r["pos"] + ff._span(r) for c in cols) >= at_least for r in specs)
-
-
-def not_vacuous(j, label):
-    """on the yardstick, before the device runs: a pair with an off-diagonal count among the classes 1..6, records that reach only the
-    first column of a pair and records that reach only the second"""
-    off = j[:, 1:, 1:].sum(0)
-    assert (off - np.diag(np.diag(off))).any(), label
-    assert j[:, 1:, 0].any() and j[:, 0, 1:].any(), label
-
-
 # ---- 1. both packers, three modes, three neighbour counts, both routes ----------------------------------------------------------------
 @pytest.mark.parametrize("one_sync", (1, 0))
-@pytest.mark.parametrize("mode", sorted(ff.MODES))
-@pytest.mark.parametrize("seed", ff.SEEDS)
+@pytest.mark.parametrize("mode", sorted(fm.MODES))
+@pytest.mark.parametrize("seed", fm.SEEDS)
 def test_fuzz_equals_the_yardstick_and_adds_up_to_the_matrix(ctx, tmp_path, seed, mode, one_sync):
-    tabled, slack, q, f = ff.MODES[mode]
-    specs, _ = ff.passing(seed, None, None, f)
+    tabled, slack, q, f = fm.MODES[mode]
+    specs, _ = fm.passing(seed, None, None, f)
     cls, n_pos, whole = classes_of(seed, mode)
     sparse, dense = sparse_columns(seed, n_pos), window_columns(whole)
     cases = [(cols, k, ly.joint(cls, cols, k)) for cols in (sparse, dense) for k in KS]
@@ -127,8 +54,8 @@ def test_fuzz_equals_the_yardstick_and_adds_up_to_the_matrix(ctx, tmp_path, seed
     assert long_read_over(specs, dense) and long_read_over(specs, sparse, 2), (seed, mode)
     routes = {len(cols) * k <= LDS for cols, k, _ in cases}
     assert routes == {True, False}
-    path = ff.write(tmp_path, ff.fuzz(seed))
-    with uploaded(ctx, path, ff.table_of(seed) if tabled else (), q, f, slack, one_sync) as rs:
+    path = fm.write(tmp_path, fm.fuzz(seed))
+    with uploaded(ctx, path, fm.table_of(seed) if tabled else (), q, f, slack, one_sync) as rs:
         matrix = ctx.step(rs, n_pos, 0, True)[3]
         assert np.array_equal(matrix, whole)
         for cols, k, want in cases:
@@ -140,11 +67,11 @@ def test_fuzz_equals_the_yardstick_and_adds_up_to_the_matrix(ctx, tmp_path, seed
 
 # ---- 2. sizes around the staging capacity ----------------------------------------------------------------------------------------------
 def test_one_column_two_columns_and_the_staging_edge(ctx, tmp_path):
-    seed = ff.SEEDS[1]
+    seed = fm.SEEDS[1]
     cls, n_pos, whole = classes_of(seed, "floor")
     dense = window_columns(whole, LDS + 1)                                       # 81 neighbouring columns: every pair is covered
     spread = sorted(int(c) for c in np.random.default_rng(9).choice(n_pos, LDS // 2 + 1, replace=False))
-    path = ff.write(tmp_path, ff.fuzz(seed))
+    path = fm.write(tmp_path, fm.fuzz(seed))
     with uploaded(ctx, path, (), 13) as rs:
         matrix = ctx.step(rs, n_pos, 0, True)[3]
         for k in KS:                                                            # n = 1: nothing but b = -1 records, all zero
@@ -171,11 +98,11 @@ def test_one_column_two_columns_and_the_staging_edge(ctx, tmp_path):
 def test_small_files(ctx, tmp_path, n_rec):
     """1, 63, 65 and 257 records (fewer than a wavefront, one more, one more than a workgroup); a column beyond every read; the same
     records under a filter that all of them fail: zeros, and TCMI_OK"""
-    every = [r for r in ff.fuzz(ff.SEEDS[2]) if ff._piles_up(r)]
+    every = [r for r in fm.fuzz(fm.SEEDS[2]) if fm._piles_up(r)]
     step = len(every) // n_rec
-    specs = every[::step][:n_rec] if n_rec > 1 else [next(r for r in every if ff._span(r) > 20)]
+    specs = every[::step][:n_rec] if n_rec > 1 else [next(r for r in every if fm._span(r) > 20)]
     assert len(specs) == n_rec
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     whole = py.counts(rd, L, (), 13)[0]
     n_pos = len(whole)
     cls = ly.classes(rd, L, (), 13, n_pos=n_pos)
@@ -186,7 +113,7 @@ def test_small_files(ctx, tmp_path, n_rec):
     else:
         sparse = sorted(set(int(c) for c in np.random.default_rng(n_rec).choice(n_pos, 30, replace=False)) | {int(np.argmax(whole[:, 0]))}) + [beyond]
     dense = window_columns(whole, 120) + [beyond]
-    path = ff.write(tmp_path, specs)
+    path = fm.write(tmp_path, specs)
     with uploaded(ctx, path, (), 13) as rs:
         assert rs.n_reads == n_rec
         matrix = ctx.step(rs, n_pos, 0, True)[3]
@@ -206,13 +133,13 @@ def test_small_files(ctx, tmp_path, n_rec):
 # ---- 4. depth --------------------------------------------------------------------------------------------------------------------------
 def test_many_lanes_on_one_counter(ctx, tmp_path):
     """every random read starts inside a window of 50 columns: more than 255 records on one counter of one pair, the sums stay exact"""
-    seed, window = ff.DEEP_SEED, ff.DEEP_WINDOW
-    tabled, slack, q, f = ff.MODES["table"]                                      # (no filter, no floor: the most records)
+    seed, window = fm.DEEP_SEED, fm.DEEP_WINDOW
+    tabled, slack, q, f = fm.MODES["table"]                                      # (no filter, no floor: the most records)
     cls, n_pos, whole = classes_of(seed, "table", window)
     sparse = list(range(window[0] - 10, window[1] + 50, 5))[:LDS // 2]
     dense = window_columns(whole, 150)
-    path = ff.write(tmp_path, ff.fuzz(seed, None, window))
-    with uploaded(ctx, path, ff.table_of(seed), q, f, slack) as rs:
+    path = fm.write(tmp_path, fm.fuzz(seed, None, window))
+    with uploaded(ctx, path, fm.table_of(seed), q, f, slack) as rs:
         matrix = ctx.step(rs, n_pos, 0, True)[3]
         for cols, k in ((sparse, 2), (sparse, 7), (dense, 1), (dense, 7)):
             want = ly.joint(cls, cols, k)
@@ -229,8 +156,8 @@ def test_a_wavefront_on_64_columns_and_a_ragged_one_behind_it(ctx, tmp_path):
     """test_strand_counts.one_column_a_record: 64 records of one wavefront on 64 columns of their own (64 distinct counters a round),
     a 65th on record 0's columns in a second, ragged wavefront; one queried column per record with one neighbour, staged, and the same
     query padded past the LDS capacity with columns beyond every read, counted in memory"""
-    specs, cols = sc.one_column_a_record()
-    rd = rf.arrays(specs)
+    specs, cols = stc.one_column_a_record()
+    rd = rsp.arrays(specs)
     n_pos = len(py.counts(rd, L)[0])
     cls = ly.classes(rd, L, n_pos=n_pos)
     padded = cols + [n_pos + 700 + j for j in range(LDS + 1 - len(cols))]
@@ -239,7 +166,7 @@ def test_a_wavefront_on_64_columns_and_a_ragged_one_behind_it(ctx, tmp_path):
     # every record has a token at its one column and none at the neighbours: [x][0] of its pair, [0][x] of the pair in front
     assert want[0].sum() == 3 and want[1:63].sum((1, 2)).tolist() == [2] * 62 and want[63].sum() == 1 and not want[64:].any()
     assert not want[:, 1:, 1:].any()
-    path = ff.write(tmp_path, specs)
+    path = fm.write(tmp_path, specs)
     with uploaded(ctx, path) as rs:
         assert rs.n_reads == 65 and rs.n_piled == 65
         matrix = ctx.step(rs, n_pos, 0, True)[3]
@@ -259,7 +186,7 @@ def hand_specs():
     """records over the columns 100 and 130 of a 400-column reference, all bases A unless said: which columns they reach and what
     token they carry there"""
     def rec(name, pos, cigar, seq=None, qual=30, flag=0):
-        qlen = sum(n for op, n in ff._ops({"cigar": cigar}) if op in (0, 1, 4, 7, 8))
+        qlen = sum(n for op, n in fm._ops({"cigar": cigar}) if op in (0, 1, 4, 7, 8))
         return {"pos": pos, "flag": flag, "cigar": cigar, "seq": "A" * qlen if seq is None else seq, "name": name, "tid": 0, "qual": qual, "mapq": 60}
     at = lambda pos, col, base, n: "A" * (col - pos) + base + "A" * (n - (col - pos) - 1)
     low = lambda pos, col, n: [30] * (col - pos) + [5] + [30] * (n - (col - pos) - 1)
@@ -285,7 +212,7 @@ HAND_TABLE = ((96, 104, False), (128, 136, True))
 
 def test_hand_made_records(ctx, tmp_path):
     specs = hand_specs()
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     whole = py.counts(rd, HL, HAND_TABLE, 13)[0]
     cls = ly.classes(rd, HL, HAND_TABLE, 13, n_pos=len(whole))
     at = {r["name"]: (int(cls[i, A_COL]), int(cls[i, B_COL])) for i, r in enumerate(specs)}
@@ -318,11 +245,11 @@ def test_hand_made_records(ctx, tmp_path):
 def test_two_contigs_under_a_layout(ctx, tmp_path):
     """columns in both slots and one in the guard between them; each contig under its own table, floor 13 and the read filter: a pair
     across the contigs holds nothing but [x][0] and [0][y]"""
-    parts, specs = ff.contig_case()
-    refs = [(name, ln) for name, ln, _ in ff.CONTIGS]
+    parts, specs = fm.contig_case()
+    refs = [(name, ln) for name, ln, _ in fm.CONTIGS]
     names = [n for n, _ in refs]
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(specs), refs=refs, block=4096)
+    bamwriter.write_bam(path, rsp.arrays(specs), refs=refs, block=4096)
     recs = [(name, syn.make_reference(seed=3, L=ln, cds=[])[0]) for name, ln in refs]
     shift, slot, axis = contigs.layout_for(recs, names, [ln for _, ln in refs])
     rows = pbed.rows_for_layout([(name, s, e, rev) for name, _, table, _ in parts for s, e, rev in table], names, shift)
@@ -330,8 +257,8 @@ def test_two_contigs_under_a_layout(ctx, tmp_path):
     assert guard >= int(shift[0]) + refs[0][1]
     blocks = []
     for t, (name, ln, table, part) in enumerate(parts):                         # every contig's classes, placed at its slot on the axis
-        kept = [dict(r, tid=0) for r in rf.kept(part, ff.F)[0]]
-        own = ly.classes(rf.arrays(kept), ln, table, 13, n_pos=ln)
+        kept = [dict(r, tid=0) for r in rsp.kept(part, fm.F)[0]]
+        own = ly.classes(rsp.arrays(kept), ln, table, 13, n_pos=ln)
         on_axis = np.zeros((len(own), axis), np.uint8)
         on_axis[:, int(shift[t]):int(shift[t]) + ln] = own
         blocks.append(on_axis)
@@ -341,7 +268,7 @@ def test_two_contigs_under_a_layout(ctx, tmp_path):
     sparse = dense[100:120:2] + [guard] + dense[121:141:2]
     try:
         ctx.set_layout(shift, slot)
-        with uploaded(ctx, path, rows, 13, ff.F) as rs:
+        with uploaded(ctx, path, rows, 13, fm.F) as rs:
             matrix = ctx.step(rs, axis, 0, True)[3]
             for cols, k in ((dense, 2), (dense, 7), (sparse, 2), (sparse, 7)):
                 want = ly.joint(cls, cols, k)
@@ -368,11 +295,11 @@ def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
     """records that straddle 4 096-byte BGZF blocks: three block ranges taken in turn add up to the whole file's counts, and a read set
     of two sub-ranges (tcmi_split_step, "split_sub") answers with the same"""
     import torch
-    seed = ff.SEEDS[3]
-    tabled, slack, q, f = ff.MODES["all"]
+    seed = fm.SEEDS[3]
+    tabled, slack, q, f = fm.MODES["all"]
     cls, n_pos, whole = classes_of(seed, "all")
-    table = ff.table_of(seed)
-    path = ff.write(tmp_path, ff.fuzz(seed), block=4096, split_records=True)
+    table = fm.table_of(seed)
+    path = fm.write(tmp_path, fm.fuzz(seed), block=4096, split_records=True)
     queries = ((sparse_columns(seed, n_pos), 2), (window_columns(whole, 120), 7))
     for cols, k in queries:
         want = ly.joint(cls, cols, k)
@@ -388,11 +315,11 @@ def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
             with uploaded(ctx, path, table, q, f, slack, blocks=td.block_range(n_blocks, rank, 3)) as rs:
                 total += device_links(ctx, rs, cols, k)["j"]
                 n_reads += rs.n_reads
-        assert n_reads == len(ff.fuzz(seed)) and np.array_equal(total, want), "three ranges"
+        assert n_reads == len(fm.fuzz(seed)) and np.array_equal(total, want), "three ranges"
     # (sub-ranges want at least 64 blocks a piece: the same records four times over in 1 024-byte blocks, four times the counts)
-    big = sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in ff.fuzz(seed)], key=lambda r: r["pos"])
+    big = sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in fm.fuzz(seed)], key=lambda r: r["pos"])
     path4 = str(tmp_path / "A4.bam")
-    bamwriter.write_bam(path4, rf.arrays(big), ref_len=L, block=1024)
+    bamwriter.write_bam(path4, rsp.arrays(big), ref_len=L, block=1024)
     c = engine.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     d = engine.DeviceBam(path4)
     try:
@@ -413,15 +340,15 @@ def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
 
 # ---- 8. refusals -----------------------------------------------------------------------------------------------------------------------
 def test_refusals(ctx, tmp_path):
-    specs = ff.fuzz(ff.SEEDS[0])
-    pa = ff.write(tmp_path, specs[:400])
+    specs = fm.fuzz(fm.SEEDS[0])
+    pa = fm.write(tmp_path, specs[:400])
     pb_ = str(tmp_path / "B.bam")
-    bamwriter.write_bam(pb_, rf.arrays(specs[400:700]), ref_len=L, block=4096)
+    bamwriter.write_bam(pb_, rsp.arrays(specs[400:700]), ref_len=L, block=4096)
     da, db = engine.DeviceBam(pa), engine.DeviceBam(pb_)
     try:
         ra = ctx.upload_bamfile(da)
         assert ctx.link_counts(ra, [10, 500, 1500], 2)["j"].any()
-        guarded = ma.sentinel(2 * G + W * 4 * 7, np.int32, salt=3).copy()
+        guarded = dvf.sentinel(2 * G + W * 4 * 7, np.int32, salt=3).copy()
         for bad, k, word in (([5, 5], 2, "strictly ascending"), ([7, 5], 2, "strictly ascending"), ([1, 2, 2, 9], 1, "strictly ascending"), ([], 2, "pairs are allowed"),
                              (np.arange((1 << 17) + 1), 1, "pairs are allowed"), (np.arange((1 << 16) + 1), 2, "pairs are allowed"), ([3, 1 << 29], 2, "2^29"),
                              ([-1, 4], 2, "2^29"), ([1, 4], 0, "1..7"), ([1, 4], 8, "1..7"), ([1, 4], -1, "1..7")):
@@ -454,7 +381,7 @@ def test_refusals(ctx, tmp_path):
 
 
 def test_the_launch_is_profiled_and_nothing_runs_without_the_call(ctx, tmp_path):
-    path = ff.write(tmp_path, ff.fuzz(ff.SEEDS[0])[:500])
+    path = fm.write(tmp_path, fm.fuzz(fm.SEEDS[0])[:500])
     try:
         ctx.profile(True)
         with uploaded(ctx, path) as rs:
@@ -474,37 +401,11 @@ def test_the_launch_is_profiled_and_nothing_runs_without_the_call(ctx, tmp_path)
 
 
 # ---- 9. the command line ---------------------------------------------------------------------------------------------------------------
-CL = 1200
-CIS, TRANS, MIXED, LOW = (300, 330), (600, 640), (800, 830), (1000, 1095)       # the planted pairs' 0-based columns
-
-
-@functools.lru_cache(maxsize=None)
-def cli_case():
-    """-> (reference, GFF rows, records): 100-base reads at about 60x over 1 200 columns.  Of the reads over a planted pair a third
-    carry another base at both columns of CIS; three in ten at the first column of TRANS only and three in ten at its second only; a
-    quarter at both columns of MIXED, a quarter at its first only, a quarter at its second only; four in ten at either column of LOW,
-    which only the reads that start in five columns span"""
-    rng = np.random.default_rng(78)
-    ref, orfs = syn.make_reference(seed=3, L=CL, cds=[(100, 900)])
-    other = {"A": "C", "C": "G", "G": "T", "T": "A"}
-    specs = []
-    for k in range(720):
-        pos = int(rng.integers(0, CL - 100 + 1))
-        seq = list(ref[pos:pos + 100])
-        r = rng.random(4)
-        hits = ((CIS[0], r[0] < 0.33), (CIS[1], r[0] < 0.33), (TRANS[0], r[1] < 0.3), (TRANS[1], 0.3 <= r[1] < 0.6), (MIXED[0], r[2] < 0.5),
-                (MIXED[1], r[2] < 0.25 or 0.5 <= r[2] < 0.75), (LOW[0], r[3] < 0.4), (LOW[1], r[3] < 0.4))
-        for col, hit in hits:
-            if hit and pos <= col < pos + 100:
-                seq[col - pos] = other[ref[col].upper()]
-        specs.append({"pos": pos, "flag": 16 if k % 2 else 0, "cigar": "100M", "seq": "".join(seq), "name": "r%d" % k, "tid": 0, "qual": 30, "mapq": 60})
-    specs.sort(key=lambda r: r["pos"])
-    return ref, orfs, specs
 
 
 def cli_yardstick(specs, ref, k=2):
     """-> (the records, {(pos_a, pos_b): counts}, the link array) of the yardsticks at the command line's default thresholds"""
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     whole = py.counts(rd, CL)[0]
     recs = vy.records(whole, ref.encode(), 3, 100, 1, 10)
     cols = sorted({p for p, *_ in recs})
@@ -527,45 +428,45 @@ def test_cli_single_sample_per_contig_and_split(tmp_path, monkeypatch):
     assert want == ly.text(recs, links, 2, "ref", ref.encode(), 10, 9, 10)
     seen = phases_of(want)
     assert (seen[CIS], seen[TRANS], seen[MIXED], seen[LOW]) == ("CIS", "TRANS", "MIXED", "LOW"), seen
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=CL, block=4096)
-    common = bq._setup_cli(tmp_path, ref, orfs)
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=CL, block=4096)
+    common = cr.setup_cli(ref, orfs)
     out = lambda t: ["-o", t + ".fa", "-vcf", t + ".vcf", "-ogff", t + ".gff", "-doc", t + ".tsv"]
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--variant-table", "a.var", "--variant-links", "a.lnk", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--variant-table", "b.var", "--stats", "b.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--variant-table", "a.var", "--variant-links", "a.lnk", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--variant-table", "b.var", "--stats", "b.json"])
     assert open("a.lnk").read() == engine.VARIANTS_LINKS_HEADER + want and not os.path.exists("b.lnk")
-    assert open("a.var").read() == open("b.var").read() and rf._outputs("a") == rf._outputs("b")       # every other output byte for byte
+    assert open("a.var").read() == open("b.var").read() and cr.outputs("a") == cr.outputs("b")       # every other output byte for byte
     sa, sb = json.load(open("a.json")), json.load(open("b.json"))
     stats = cli.link_stats(want)
     assert {k: sa[k] for k in stats} == stats and stats["variant_link_rows"] == len(want.splitlines()) > 0
     assert all(stats["variant_links_" + w] > 0 for w in ("cis", "trans", "mixed", "low"))
     assert {k: sb[k] for k in stats} == cli.link_stats() and sa["variant_records"] == sb["variant_records"] == len(recs)
     # other thresholds
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "c.fa", "--variant-table", "c.var", "--variant-links", "c.lnk", "--link-neighbours", "1",
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "c.fa", "--variant-table", "c.var", "--variant-links", "c.lnk", "--link-neighbours", "1",
                                                                       "--link-min-depth", "2", "--link-ratio", "0.6"])
     recs1, links1, arr1 = cli_yardstick(specs, ref, 1)
     assert open("c.lnk").read() == engine.VARIANTS_LINKS_HEADER + ly.text(recs1, links1, 1, "ref", ref.encode(), 2, 3, 5)
     assert phases_of(open("c.lnk").read().split("\n", 1)[1])[LOW] != "LOW" and open("c.var").read() == open("b.var").read()
     # together with --variant-strand: the strand table as without --variant-links, the links as without --variant-strand
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "d.fa", "--variant-table", "d.var", "--variant-strand", "--variant-links", "d.lnk"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "e.fa", "--variant-table", "e.var", "--variant-strand"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "d.fa", "--variant-table", "d.var", "--variant-strand", "--variant-links", "d.lnk"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "e.fa", "--variant-table", "e.var", "--variant-strand"])
     assert open("d.lnk").read() == open("a.lnk").read() and open("d.var").read() == open("e.var").read()
     assert open("d.var").read().startswith(engine.VARIANTS_STRAND_HEADER)
 
     # --per-contig: the same records on two references of the same sequence: the same rows per region, no pair across the two
     two = sorted([dict(r, tid=t, name="%s_%d" % (r["name"], t)) for t in (0, 1) for r in specs], key=lambda r: (r["tid"], r["pos"]))
-    bamwriter.write_bam("P.bam", rf.arrays(two), refs=[("c0", CL), ("c1", CL)], block=4096)
+    bamwriter.write_bam("P.bam", rsp.arrays(two), refs=[("c0", CL), ("c1", CL)], block=4096)
     with open("p.fa", "w") as fh:
         fh.write(">c0\n%s\n>c1\n%s\n" % (ref, ref))
     with open("p.gff", "w") as fh:
         fh.write("##gff-version 3\n" + syn.gff_text(orfs, seqid="c0")[1] + syn.gff_text(orfs, seqid="c1")[1])
-    rf._run_cli(monkeypatch, ["-i", "P.bam", "-ref", "p.fa", "-gff", "p.gff", "-cov", "10", "-name", "S", "--per-contig", "-o", "p.fa.out", "--variant-table", "p.var",
-                              "--variant-links", "p.lnk", "--stats", "p.json"])
+    cr.run_cli(monkeypatch, ["-i", "P.bam", "-ref", "p.fa", "-gff", "p.gff", "-cov", "10", "-name", "S", "--per-contig", "-o", "p.fa.out", "--variant-table", "p.var",
+                             "--variant-links", "p.lnk", "--stats", "p.json"])
     assert open("p.lnk").read() == engine.VARIANTS_LINKS_HEADER + want.replace("ref\t", "c0\t") + want.replace("ref\t", "c1\t")
     sp = json.load(open("p.json"))
     assert {k: sp[k] for k in stats} == {k: 2 * v for k, v in stats.items()} and sp["variant_records"] == 2 * len(recs)
 
     # one file through consensus_split_bamfile at world 1
-    parts = td.consensus_split_bamfile("A.bam", CL, rf._gff(orfs), 10, True, "S", 0, 1, return_parts=True,
+    parts = td.consensus_split_bamfile("A.bam", CL, cr.gff_rows(orfs), 10, True, "S", 0, 1, return_parts=True,
                                        variant_links=(dict(ref=ref, min_af="0.03", min_alt_depth=1, min_depth=10), 2))
     vrecs, vlinks = parts[-1]
     assert engine.variants_links_text(vrecs, vlinks, 2, "ref", ref) == want and len(parts) == 4
@@ -573,7 +474,7 @@ def test_cli_single_sample_per_contig_and_split(tmp_path, monkeypatch):
     # refused: exit 1, nothing written
     man = tmp_path / "m.tsv"
     man.write_text("A.bam\tS0\to0.fa\t-\t-\t-\tt0.var\n")
-    bq._write_override("o.csv.gz", py.counts(rf.arrays(specs), CL)[0])
+    cr.write_override("o.csv.gz", py.counts(rsp.arrays(specs), CL)[0])
     before = sorted(os.listdir(tmp_path))
     for argv in (["--batch", str(man)] + common + ["--variant-links", "x.lnk"],
                  ["-i", "A.bam", "-name", "S"] + common + ["-o", "x.fa", "--variant-table", "x.var", "--variant-links", "x.lnk", "--index-override", "o.csv.gz"]):
@@ -586,17 +487,12 @@ def test_cli_single_sample_per_contig_and_split(tmp_path, monkeypatch):
 def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
     """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange): rank 0 lists the records and broadcasts their columns, every
     rank counts its own records, rank 0 writes the sum: the rows of the single-GPU run"""
-    import subprocess
-    import sys
     monkeypatch.chdir(tmp_path)
     ref, orfs, specs = cli_case()
     recs, links, arr = cli_yardstick(specs, ref)
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=CL, block=4096, split_records=True)
-    common = bq._setup_cli(tmp_path, ref, orfs)
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=rf.ROOT)
-    argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", "A.bam", "-name", "S"] + common + ["-o", "a.fa", "--variant-table", "a.var", "--variant-strand",
-                                                                                                       "--variant-links", "a.lnk", "--link-min-depth", "12", "--gpus", "2"]
-    r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-1500:]
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=CL, block=4096, split_records=True)
+    common = cr.setup_cli(ref, orfs)
+    cr.run_two_ranks(["-i", "A.bam", "-name", "S"] + common + ["-o", "a.fa", "--variant-table", "a.var", "--variant-strand", "--variant-links", "a.lnk",
+                                                               "--link-min-depth", "12", "--gpus", "2"])
     assert open("a.lnk").read() == engine.VARIANTS_LINKS_HEADER + engine.variants_links_text(vy.as_array(recs), arr, 2, "ref", ref, min_depth=12)
     assert open("a.var").read().startswith(engine.VARIANTS_STRAND_HEADER)

@@ -3,49 +3,34 @@ their own (tests/links_main.cpp), built plain and under AddressSanitizer + UBSan
 (tests/links_yardstick.py); the same writer through the ABI; the yardstick's marginals against the yardstick of the count matrix; and
 the command line's argument handling.  The kernel's tests are tests/test_link_counts.py."""
 import os
-import shutil
 import struct
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from tests import fuzz_masked as ff
+from tests import host_program
 from tests import links_yardstick as ly
-from tests import test_floor_mask_fuzz as ff
 from tests import variant_yardstick as vy
+from tests.cli_run import base_args as _base
+from tests.cli_run import stub_files
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, engine
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
 TOP = (1 << 31) - 1
-
-
-def _build(out, flags):
-    src = [os.path.join(ROOT, "tests", "links_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "variants_links_text.cpp")]
-    tried = []
-    for cxx in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++"), shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + flags + ["-o", out] + src, capture_output=True, text=True)
-        if r.returncode == 0:
-            return out
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    pytest.fail("no compiler built the program:\n" + "\n".join(tried))
 
 
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
     d = tmp_path_factory.mktemp("links_main")
-    return {"plain": _build(str(d / "links_main"), []), "sanitized": _build(str(d / "links_main_san"), SAN)}
+    src = ["tests/links_main.cpp", "trueconsense_amd/csrc/variants_links_text.cpp"]
+    return {"plain": host_program.build(src, d / "links_main", sanitize=False), "sanitized": host_program.build(src, d / "links_main_san")}
 
 
 def _run(prog, mode, inp, out):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([prog, mode, inp, out], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    r = host_program.run(prog, mode, inp, out)
+    assert r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-4000:])
 
 
 # ---- the rule -----------------------------------------------------------------------------------------------------------------------
@@ -302,20 +287,10 @@ def test_the_marginals_are_the_yardstick_of_the_count_matrix(seed):
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------------
-def _files(tmp_path):
-    p = {}
-    for name in ("x.bam", "r.fa", "f.gff", "o.csv.gz"):
-        (tmp_path / name).write_text("x")
-        p[name] = str(tmp_path / name)
-    return p
-
-
-def _base(f):
-    return ["-i", f["x.bam"], "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30", "-name", "S", "-o", "out.fa"]
 
 
 def test_flags_defaults_and_children(tmp_path):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     a = cli.GetArgs(_base(f) + ["--variant-table", "t.tsv", "--variant-links", "l.tsv"])
     assert (a.variant_links, a.link_neighbours, a.link_min_depth, a.link_ratio) == ("l.tsv", 2, 10, Fraction(9, 10))
     assert cli.links_of(a) == ("l.tsv", 2, dict(min_depth=10, ratio=Fraction(9, 10)))
@@ -338,7 +313,7 @@ def test_flags_defaults_and_children(tmp_path):
 @pytest.mark.parametrize("extra", (["--link-min-depth", "0"], ["--link-min-depth", "x"], ["--link-ratio", "1.5"], ["--link-ratio", "1/2"], ["--link-ratio", "0.3"],
                                    ["--link-ratio", "2000001/3000001"], ["--link-neighbours", "0"], ["--link-neighbours", "8"], ["--link-neighbours", "x"]))
 def test_bad_link_thresholds_are_refused(tmp_path, capsys, extra):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     with pytest.raises(SystemExit) as e:
         cli.GetArgs(_base(f) + ["--variant-table", "t.tsv", "--variant-links", "l.tsv"] + extra)
     assert e.value.code == 2 and extra[0] in capsys.readouterr().err
@@ -346,7 +321,7 @@ def test_bad_link_thresholds_are_refused(tmp_path, capsys, extra):
 
 def test_refusals_exit_1_with_one_line_and_write_nothing(tmp_path, capsys, monkeypatch):
     monkeypatch.chdir(tmp_path)
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     man = tmp_path / "m.tsv"
     man.write_text("%s\tS0\to0.fa\t-\t-\t-\tt0.tsv\n" % f["x.bam"])
     batch = ["--batch", str(man), "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30"]

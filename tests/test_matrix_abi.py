@@ -31,17 +31,15 @@ import pytest
 from oracle import c_oracle
 from tests import call_rows
 from tests import fuzz_reads as fz
+from tests import read_specs as rsp
 from tests import synth_small as ss
-from tests import test_base_quality as tb
-from tests import test_read_filter as rf
+from tests.device_file import PACKERS, Guarded, Matrix
 from trueconsense_amd import _ffi, engine
 from trueconsense_amd.io import bamwriter
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
 LS = (1, 2, 7, 8, 9, 255, 256, 257, 1001, 1536)
-PACKERS = tb.PACKERS
 OPTIONS = {"tally_variant": 0, "project_reads": 1, "balance_chunks": 1, "stage_cap": 0, "device_pack": 1}      # a context's defaults
 
 
@@ -49,65 +47,9 @@ def geometries(L):
     return [(ld, off) for ld in sorted({L, L + 1, L + (L & 1), (L + 255) // 256 * 256}) for off in (0, 1)]
 
 
-def sentinel(n, dtype=np.int32, salt=0):
-    """distinct, far from any count: int32 words at or above 2^30, bytes at or above 0x80"""
-    k = np.arange(n, dtype=np.int64) + salt
-    if dtype == np.uint8:
-        return (0x80 | (k * 37 + 11) % 128).astype(np.uint8)
-    return (0x40000000 | (k * 2654435761) % 0x3FFFFFFF).astype(np.int32)
-
-
 def prefill(L, ld, seed):
     """known counts below 2^20 for a whole [7][ld] matrix, padding included"""
     return np.random.default_rng(seed).integers(0, 1 << 20, (7, ld)).astype(np.int32)
-
-
-class Guarded:
-    """`n` items of `dtype` between two guards inside one torch buffer, `lead` items into it (lead: one int32 word for a pointer
-    that is 4 mod 8, one byte for an odd address); body = what the items hold before the call (default: sentinel too)"""
-
-    def __init__(self, n, dtype=np.int32, lead=0, body=None, salt=0):
-        import torch
-        self.n, self.lo = n, GUARD + lead
-        self.init = sentinel(self.lo + n + GUARD, dtype, salt)
-        if body is not None:
-            self.init[self.lo:self.lo + n] = np.asarray(body, dtype).reshape(-1)
-        self.t = torch.from_numpy(self.init.copy()).to("cuda")
-        torch.cuda.synchronize()                                # torch's stream is not the context's
-        item = self.init.itemsize
-        assert self.t.data_ptr() % 64 == 0
-        self.ptr = self.t.data_ptr() + item * self.lo
-        assert self.ptr % 8 == (4 * lead if dtype == np.int32 else lead) % 8
-
-    def read(self):
-        """-> the body; both guards (and the lead) must hold the sentinel word for word"""
-        a = self.t.cpu().numpy()
-        assert np.array_equal(a[:self.lo], self.init[:self.lo]), "the guard in front was written"
-        assert np.array_equal(a[self.lo + self.n:], self.init[self.lo + self.n:]), "the guard behind was written"
-        return a[self.lo:self.lo + self.n]
-
-    def untouched(self):
-        return np.array_equal(self.read(), self.init[self.lo:self.lo + self.n])
-
-
-class Matrix(Guarded):
-    """int32 [7][ld] at `off` words past an 8-byte boundary"""
-
-    def __init__(self, L, ld, off, fill=None):
-        super().__init__(7 * ld, np.int32, off, fill)
-        self.L, self.ld, self.off = L, ld, off
-        self.before = self.init[self.lo:self.lo + 7 * ld].reshape(7, ld).copy()
-
-    def check(self, want, zero, what=()):
-        """want: int32 [L, 7] rows.  zero: the call cleared the matrix first (padding 0), else it added to what was there."""
-        got = self.read().reshape(7, self.ld)
-        L = self.L
-        exp = np.zeros_like(self.before) if zero else self.before.copy()
-        exp[:, :L] += np.ascontiguousarray(want, np.int32).T
-        what = (L, self.ld, self.off, zero) + tuple(what)
-        bad = np.argwhere(got[:, :L] != exp[:, :L])
-        assert len(bad) == 0, (what, "planes", len(bad), bad[:6].tolist(), got[:, :L][tuple(bad[:6].T)].tolist(), exp[:, :L][tuple(bad[:6].T)].tolist())
-        assert np.array_equal(got[:, L:], exp[:, L:]), (what, "padding", np.argwhere(got[:, L:] != exp[:, L:])[:6].tolist())
 
 
 @pytest.fixture(scope="module")
@@ -209,7 +151,7 @@ def specs_for(L, n_plain, long_reads=False):
 def flat(L):
     """-> (arrays, oracle counts, the plain reads' indices): the flat-array read set of L"""
     specs, plain = specs_for(L, 3000)
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     assert c_oracle.extent(rd, 0) <= L
     want = c_oracle.tally(rd, L)
     want.setflags(write=False)
@@ -308,9 +250,9 @@ def test_plain_reads_against_a_numpy_tally(ctx, L):
 @functools.lru_cache(maxsize=None)
 def bam_reads(L):
     specs, _ = specs_for(L, 500, True)
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     n_long = sum(1 for r in specs if sum(n for op, n in ss.parse_cigar(r["cigar"]) if op in (0, 2, 3, 7, 8)) > 512)
-    want = {0: c_oracle.tally(rd, L), 13: tb.oracle_counts(rd, 13, L)}
+    want = {0: c_oracle.tally(rd, L), 13: rsp.oracle_counts(rd, 13, L)}
     return rd, want, n_long
 
 

@@ -3,7 +3,7 @@ device arrays for before it has seen the file (tests/capacity_files.py; tests/te
 the retry sized for the worst case, the declines to the several-kernel path with their flags, the event re-pack of
 tcmi_pack_on_device from files and from flat arrays, a context's state after a declined step, block ranges, and the same files under
 a base-quality floor and a read filter.  Integer work: counts and call records equal the oracle's bit for bit (c_oracle.tally /
-c_oracle.call; under a floor the pileup oracle of tests/test_base_quality.py), and the read sets' figures equal those of the
+c_oracle.call; under a floor the pileup oracle of tests/read_specs.oracle_counts), and the read sets' figures equal those of the
 several-kernel path.  What the reference computes here is indexing.BuildIndex (indexing.py:75-154) and the position-local part of
 BuildConsensus (Sequences.py:119-165)."""
 import contextlib
@@ -13,8 +13,8 @@ import pytest
 
 from oracle import c_oracle
 from tests import capacity_files as cf
+from tests import read_specs as rsp
 from tests import synth_small as ss
-from tests import test_base_quality as bq
 from trueconsense_amd import distributed as td
 from trueconsense_amd import engine
 from trueconsense_amd import synthetic as sy
@@ -257,14 +257,14 @@ def test_wide_skips_under_a_base_quality_floor(ctx, lab, tmp_path):
     # checked against the oracle itself on the file's first 800 reads
     want = np.zeros((L, 7), np.int32)
     for q in (12, 13, 30):
-        unit = bq.oracle_counts(ss.reads_from_spec({"reads": [dict(specs[0], pos=0, qual=q)]}), 13, 502)
+        unit = rsp.oracle_counts(ss.reads_from_spec({"reads": [dict(specs[0], pos=0, qual=q)]}), 13, 502)
         assert unit[:, 0].sum() == (0 if q < 13 else 502)
         want += superposed(unit, reads["pos"][quals == q], L)
     head = ss.reads_from_spec({"reads": specs[:800]})
-    direct = bq.oracle_counts(head, 13, L)
+    direct = rsp.oracle_counts(head, 13, L)
     part = np.zeros((L, 7), np.int32)
     for q in (12, 13, 30):
-        unit = bq.oracle_counts(ss.reads_from_spec({"reads": [dict(specs[0], pos=0, qual=q)]}), 13, 502)
+        unit = rsp.oracle_counts(ss.reads_from_spec({"reads": [dict(specs[0], pos=0, qual=q)]}), 13, 502)
         part += superposed(unit, head["pos"][quals[:800] == q], L)
     same(part, direct, "superposition against the pileup oracle")
     case = lab.add("wide_skips+floor", cf.write_reads(tmp_path / "c_q.bam", reads, "wide_skips"))
@@ -286,7 +286,7 @@ def test_all_n_under_a_base_quality_floor(ctx, lab, tmp_path):
     assert n_events == 562_500
     fits = n_events <= cf.EVENT_FLOOR
     L = c_oracle.extent(reads, REF_LEN)
-    want = bq.oracle_counts(reads, 20, L)
+    want = rsp.oracle_counts(reads, 20, L)
     assert want[:, 0].sum() == n_events and want[:, 1:].sum() == 0
     # (the name's first part says which statistics to expect: those of an ordinary file if the events fit)
     case = lab.add(("ordinary" if fits else "all_n") + "+floor", cf.write_reads(tmp_path / "e_q.bam", reads, "all_n"))

@@ -10,11 +10,10 @@ import sys
 import numpy as np
 import pytest
 
+from tests.cli_run import ROOT, run_cli
 from trueconsense_amd import _ffi, contigs, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter, fasta
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def concat(parts):
@@ -288,20 +287,14 @@ def test_insert_tokens_with_a_layout(ctx, tmp_path):
     host.close()
 
 
-def _run_cli(monkeypatch, args):
-    from trueconsense_amd import TrueConsense as cli
-    monkeypatch.setattr(sys, "argv", ["TrueConsense", "ARGS"])
-    cli.main(args)
-
-
 @pytest.mark.gpu
 def test_cli_per_contig_equals_split_runs(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)
     reads, refs, records, gff_rows, bam = fixture(tmp_path)
     write_fasta("flu.fa", records)
     write_gff("flu.gff", gff_rows, ["A", "B", "C"])
-    _run_cli(monkeypatch, ["-i", bam, "-ref", "flu.fa", "-gff", "flu.gff", "-cov", "10", "-name", "S", "-o", "S.fa", "-vcf", "S.vcf",
-                           "-ogff", "S.gff", "-doc", "S.tsv", "--per-contig", "--stats", "S.json"])
+    run_cli(monkeypatch, ["-i", bam, "-ref", "flu.fa", "-gff", "flu.gff", "-cov", "10", "-name", "S", "-o", "S.fa", "-vcf", "S.vcf",
+                          "-ogff", "S.gff", "-doc", "S.tsv", "--per-contig", "--stats", "S.json"])
     import json
     stats = json.load(open("S.json"))
     assert stats["contigs"] == 3 and stats["dropped_reads"] == 200      # (the reads on X, which the FASTA does not name)
@@ -314,8 +307,8 @@ def test_cli_per_contig_equals_split_runs(tmp_path, monkeypatch):
         bamwriter.write_bam("%s.bam" % name, sub, refs=[(name, dict(refs)[name])])
         write_fasta("%s.fa" % name, [(name, seq)])
         write_gff("%s.gff" % name, gff_rows, [name])
-        _run_cli(monkeypatch, ["-i", "%s.bam" % name, "-ref", "%s.fa" % name, "-gff", "%s.gff" % name, "-cov", "10", "-name", "S_%s" % name,
-                               "-o", "o_%s.fa" % name, "-vcf", "o_%s.vcf" % name, "-ogff", "o_%s.gff" % name, "-doc", "o_%s.tsv" % name])
+        run_cli(monkeypatch, ["-i", "%s.bam" % name, "-ref", "%s.fa" % name, "-gff", "%s.gff" % name, "-cov", "10", "-name", "S_%s" % name,
+                              "-o", "o_%s.fa" % name, "-vcf", "o_%s.vcf" % name, "-ogff", "o_%s.gff" % name, "-doc", "o_%s.tsv" % name])
         want_fa += open("o_%s.fa" % name).read()
         want_vcf += "".join(ln for ln in open("o_%s.vcf" % name) if not ln.startswith("#"))
         want_gff += open("o_%s.gff" % name).read()[len("##gff-version 3\n"):]
@@ -352,8 +345,8 @@ def test_read_past_its_slot_is_refused(ctx, tmp_path, monkeypatch, capsys):
         ctx.set_layout()
     (tmp_path / "f.gff").write_text("##gff-version 3\n")
     with pytest.raises(SystemExit) as e:
-        _run_cli(monkeypatch, ["-i", "in.bam", "-ref", "r.fa", "-gff", "f.gff", "-cov", "5", "-name", "S", "-o", "S.fa", "-vcf", "S.vcf",
-                               "--per-contig"])
+        run_cli(monkeypatch, ["-i", "in.bam", "-ref", "r.fa", "-gff", "f.gff", "-cov", "5", "-name", "S", "-o", "S.fa", "-vcf", "S.vcf",
+                              "--per-contig"])
     assert e.value.code == 1
     assert 'read "r49" on contig "A" ends past the end' in capsys.readouterr().err
     assert not (tmp_path / "S.fa").exists() and not (tmp_path / "S.vcf").exists()
@@ -389,7 +382,7 @@ def test_default_path_unchanged(tmp_path, monkeypatch):
     write_fasta("flu.fa", records)
     write_gff("flu.gff", gff_rows, ["A", "B", "C"])
     with pytest.raises(_ffi.TcmiError) as e:                        # without the flag a multi-contig file is refused, as before
-        _run_cli(monkeypatch, ["-i", bam, "-ref", "flu.fa", "-gff", "flu.gff", "-cov", "10", "-name", "S", "-o", "S.fa"])
+        run_cli(monkeypatch, ["-i", bam, "-ref", "flu.fa", "-gff", "flu.gff", "-cov", "10", "-name", "S", "-o", "S.fa"])
     assert e.value.code == _ffi.E_UNSUPPORTED
     # a single-contig file: --per-contig gives today's outputs under -name S_A, plus the contig column of the TSV
     sub = split_reads(reads, 0)
@@ -397,8 +390,8 @@ def test_default_path_unchanged(tmp_path, monkeypatch):
     write_fasta("A.fa", [records[0]])
     write_gff("A.gff", gff_rows, ["A"])
     common = ["-i", "A.bam", "-ref", "A.fa", "-gff", "A.gff", "-cov", "10"]
-    _run_cli(monkeypatch, common + ["-name", "S_A", "-o", "d.fa", "-vcf", "d.vcf", "-ogff", "d.gff", "-doc", "d.tsv"])
-    _run_cli(monkeypatch, common + ["-name", "S", "-o", "p.fa", "-vcf", "p.vcf", "-ogff", "p.gff", "-doc", "p.tsv", "--per-contig"])
+    run_cli(monkeypatch, common + ["-name", "S_A", "-o", "d.fa", "-vcf", "d.vcf", "-ogff", "d.gff", "-doc", "d.tsv"])
+    run_cli(monkeypatch, common + ["-name", "S", "-o", "p.fa", "-vcf", "p.vcf", "-ogff", "p.gff", "-doc", "p.tsv", "--per-contig"])
     assert open("p.fa").read() == open("d.fa").read()
     assert open("p.gff").read() == open("d.gff").read()
     assert open("p.vcf").read() == open("d.vcf").read()          # (sys.argv is the same placeholder in both runs)

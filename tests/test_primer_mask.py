@@ -9,74 +9,48 @@ import functools
 import json
 import os
 import re
-import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import c_oracle
 from oracle import tc_oracle as orc
+from tests import cli_run as cr
 from tests import fuzz_reads as fz
+from tests import host_program
 from tests import primer_yardstick as py
-from tests import test_base_quality as bq
-from tests import test_read_filter as rf
+from tests import read_specs as rsp
+from tests.device_file import PACKERS, through
+from tests.read_specs import L
+from tests.schemes import PRIMER_SCHEME as SCHEME
+from tests.schemes import compile_primers, write_primer_bed
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, contigs, distributed, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
 from trueconsense_amd.io import primers as pbed
 
-ROOT = rf.ROOT
-L = rf.L
-PACKERS = ("one_sync", "several_kernels")
-SCHEME = py.scheme()                # '+' [s, s + 24), '-' [s + 376, s + 400), s = 30, 330, ...: 12 primers
-
 
 @functools.lru_cache(maxsize=None)
 def mixed_yardstick(primed=True, q=0):
-    """test_read_filter.mixed() under the scheme (or no table) and floor q -> (counts, masked reads, tokens kept, tokens)"""
-    return py.counts(rf.arrays(rf.mixed()[2]), L, SCHEME if primed else (), q)
-
-
-def write_bed(path, primers, chrom="ref", extra=()):
-    with open(path, "w") as fh:
-        fh.write("# scheme\ntrack name=primers\n\n")
-        for k, (s, e, rev) in enumerate(primers):
-            fh.write("%s\t%d\t%d\tp%d_%s\t%d\t%s\n" % (chrom, s, e, k, "RIGHT" if rev else "LEFT", 1 + k % 2, "-" if rev else "+"))
-        for line in extra:
-            fh.write(line + "\n")
-    return path
+    """read_specs.mixed() under the scheme (or no table) and floor q -> (counts, masked reads, tokens kept, tokens)"""
+    return py.counts(rsp.arrays(rsp.mixed()[2]), L, SCHEME if primed else (), q)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ CPU
 def test_yardstick_without_primers_is_the_committed_oracle():
-    rd = rf.arrays(rf.mixed()[2])
+    rd = rsp.arrays(rsp.mixed()[2])
     got = mixed_yardstick(False)
     assert np.array_equal(got[0], c_oracle.tally(rd, c_oracle.extent(rd, L))) and got[1] == 0 and got[2] == got[3]
-    assert np.array_equal(mixed_yardstick(False, 13)[0], bq.oracle_counts(rd, 13, len(got[0])))      # pileup_columns(min_base_quality=13)
+    assert np.array_equal(mixed_yardstick(False, 13)[0], rsp.oracle_counts(rd, 13, len(got[0])))      # pileup_columns(min_base_quality=13)
 
 
 def test_yardstick_on_the_mixed_fixture():
-    rd = rf.arrays(rf.mixed()[2])
+    rd = rsp.arrays(rsp.mixed()[2])
     base, (want, n_masked, kept, total) = mixed_yardstick(False)[0], mixed_yardstick()
     assert len(SCHEME) == 12 and sum(orc.read_piles_up(rd, i) for i in range(int(rd["n_reads"]))) == 2960 and n_masked == 625
     assert round(100.0 * kept / total, 1) == 96.5
     assert (int(base[:, 5].sum()), int(want[:, 5].sum())) == (719, 716) and (int(base[:, 6].sum()), int(want[:, 6].sum())) == (825, 818)
-
-
-def _compile(primers, slack, cap=None):
-    n = len(primers)
-    s = np.ascontiguousarray([p[0] for p in primers], np.int64)
-    e = np.ascontiguousarray([p[1] for p in primers], np.int64)
-    r = np.ascontiguousarray([int(p[2]) for p in primers], np.int32)
-    cap = 2 * n + 1 if cap is None else cap
-    head, tail = np.zeros((cap, 3), np.int32), np.zeros((cap, 3), np.int32)
-    nh, nt = C.c_int32(0), C.c_int32(0)
-    msg = C.create_string_buffer(200)
-    rc = _ffi.lib().tcmi_primers_compile(n, _ffi.ptr(s), _ffi.ptr(e), _ffi.ptr(r), slack, cap, _ffi.ptr(head), C.byref(nh), _ffi.ptr(tail), C.byref(nt), msg, 200)
-    return rc, head[:nh.value], tail[:nt.value], msg.value.decode()
 
 
 def _find(seg, x, none):
@@ -95,7 +69,7 @@ def test_compiled_table_equals_brute_force(slack):
             if prim and k % 5 == 0:
                 s = prim[-1][0]                                                 # an alternative primer: the same start
             prim.append((s, s + int(rng.integers(1, 120 if k % 4 == 0 else 30)), bool(rng.integers(0, 2))))
-        rc, head, tail, msg = _compile(prim, slack)
+        rc, head, tail, msg = compile_primers(prim, slack)
         assert rc == 0, msg
         for seg in (head, tail):
             assert (seg[:, 0] < seg[:, 1]).all() and (seg[1:, 0] >= seg[:-1, 1]).all()
@@ -107,38 +81,24 @@ def test_compiled_table_equals_brute_force(slack):
 
 def test_compile_argument_errors():
     ok = [(10, 34, False), (300, 324, True)]
-    assert _compile(ok, 0)[0] == 0 and _compile([], 0)[0] == 0 and _compile(ok, 1000)[0] == 0
+    assert compile_primers(ok, 0)[0] == 0 and compile_primers([], 0)[0] == 0 and compile_primers(ok, 1000)[0] == 0
     for prim, slack, word in (([(-1, 5, False)], 0, "interval"), ([(10, 10, True)], 0, "interval"), ([(10, 9, False)], 0, "interval"),
                               ([(1 << 29, (1 << 29) + 5, False)], 0, "2^29"), ([(10, 1 << 29, True)], 0, "2^29"), ([(10, 34, 2)], 0, "strand"),
                               (ok, -1, "slack"), (ok, 1001, "slack"), ([(k, k + 5, False) for k in range(65537)], 0, "65536")):
-        rc, _, _, msg = _compile(prim, slack, cap=4)
+        rc, _, _, msg = compile_primers(prim, slack, cap=4)
         assert rc == _ffi.E_ARG and word in msg, (prim[:2], slack, msg)
-    assert _compile([(k * 10, k * 10 + 5, False) for k in range(8)], 0, cap=4)[0] == _ffi.E_ARG       # no room
+    assert compile_primers([(k * 10, k * 10 + 5, False) for k in range(8)], 0, cap=4)[0] == _ffi.E_ARG       # no room
 
 
 def test_primer_table_program_under_sanitizers(tmp_path):
     """tests/primer_table_main.cpp + csrc/primer_table.cpp and nothing else, with AddressSanitizer + UBSan, run as a program"""
-    src = [os.path.join(ROOT, "tests", "primer_table_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "primer_table.cpp")]
-    out = str(tmp_path / "primer_table_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
-    tried = []
-    for cxx in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++"), shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + san + ["-o", out] + src, capture_output=True, text=True)
-        if r.returncode == 0:
-            break
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    else:
-        pytest.fail("no compiler built the program:\n" + "\n".join(tried))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([out], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    out = host_program.build(["tests/primer_table_main.cpp", "trueconsense_amd/csrc/primer_table.cpp"], tmp_path / "primer_table_main")
+    r = host_program.run(out)
+    assert r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-4000:])
 
 
 def test_bed_reader(tmp_path):
-    path = write_bed(str(tmp_path / "p.bed"), SCHEME, extra=["browser position ref:1-100", "other 5 29 x 1 +", "ref\t7\t9\tshort\t2\t-\tACGT"])
+    path = write_primer_bed(str(tmp_path / "p.bed"), SCHEME, extra=["browser position ref:1-100", "other 5 29 x 1 +", "ref\t7\t9\tshort\t2\t-\tACGT"])
     rows = pbed.read_bed(path)
     assert len(rows) == 14 and rows[:2] == [("ref", 30, 54, False), ("ref", 406, 430, True)] and rows[12] == ("other", 5, 29, False)
     assert pbed.rows_for_reference(rows, "ref") == list(SCHEME) + [(7, 9, True)] and pbed.rows_for_reference(rows, "nope") == []
@@ -153,7 +113,7 @@ def test_bed_reader(tmp_path):
 
 
 def test_cli_parses_primers_and_children_get_them_only_when_set(tmp_path, capsys):
-    base = rf._files(tmp_path)
+    base = cr.base_args(cr.stub_files(tmp_path), "o.fa")
     a = cli.GetArgs(base)
     assert a.primers is None and a.primer_slack == 0 and cli.primers_of(a) is None
     a = cli.GetArgs(base + ["--primers", "p.bed", "--primer-slack", "5"])
@@ -177,12 +137,12 @@ def test_cli_parses_primers_and_children_get_them_only_when_set(tmp_path, capsys
 
 def test_cli_rows_of_the_bams_reference(tmp_path, capsys):
     """without --per-contig: the rows whose chrom is the BAM's reference name; none is an argument error, and so is a bad BED"""
-    rd = rf.arrays(rf.mixed()[2][:20])
+    rd = rsp.arrays(rsp.mixed()[2][:20])
     bam = str(tmp_path / "A.bam")
     bamwriter.write_bam(bam, rd, ref_len=L)
-    base = rf._files(tmp_path)
+    base = cr.base_args(cr.stub_files(tmp_path), "o.fa")
     base[1] = bam
-    bed = write_bed(str(tmp_path / "p.bed"), SCHEME, extra=["other\t5\t29\tx\t1\t+"])
+    bed = write_primer_bed(str(tmp_path / "p.bed"), SCHEME, extra=["other\t5\t29\tx\t1\t+"])
     rows, slack = cli.primers_of(cli.GetArgs(base + ["--primers", bed, "--primer-slack", "3"]))
     assert rows == list(SCHEME) and slack == 3
     for text in ("other\t5\t29\tx\t1\t+\n", "ref\t5\t29\tx\t1\n"):
@@ -193,7 +153,7 @@ def test_cli_rows_of_the_bams_reference(tmp_path, capsys):
 
 
 def test_header_declares_and_library_exports_the_symbols():
-    text = open(os.path.join(ROOT, "include", "tcmi.h")).read()
+    text = open(os.path.join(cr.ROOT, "include", "tcmi.h")).read()
     assert re.search(r"int\s+tcmi_ctx_set_primers\(tcmi_ctx \*ctx, int32_t n, const int64_t \*start, const int64_t \*end, const int32_t \*reverse, int32_t slack\);", text)
     assert re.search(r"int\s+tcmi_readset_primers\(const tcmi_readset \*rs, int32_t \*n_primers, int64_t \*n_masked_reads\);", text)
     assert re.search(r"int\s+tcmi_primers_compile\(", text)
@@ -209,30 +169,6 @@ def test_header_declares_and_library_exports_the_symbols():
 def ctx():
     with engine.Context(0) as c:
         yield c
-
-
-def through(ctx, how, path, primers, n_pos, q=0, f=(0, 0, 0), slack=0):
-    """the file under the table (and floor q, filter f) on one packer -> (counts, n_piled, max_end, the read set's table size, its masked reads)"""
-    try:
-        ctx.set_option("one_sync", int(how == "one_sync"))
-        ctx.set_read_filter(*f)
-        ctx.set_min_base_quality(q)
-        ctx.set_primers(primers, slack)
-        d = engine.DeviceBam(path)
-        try:
-            t0 = ctx.stat("one_sync_taken")
-            rs = ctx.upload_bamfile(d)
-            assert ctx.stat("one_sync_taken") - t0 == int(how == "one_sync"), (how, ctx.stat("one_sync_last_decline_flags"))
-            out = (ctx.step(rs, n_pos, 0, True)[3], rs.n_piled, rs.max_end, rs.primers, rs.primer_masked_reads)
-            rs.free()
-            return out
-        finally:
-            d.close()
-    finally:
-        ctx.set_option("one_sync", 1)
-        ctx.set_read_filter()
-        ctx.set_min_base_quality()
-        ctx.set_primers()
 
 
 def check_file(ctx, path, rd, primers, q=0, want=None, f=(0, 0, 0), slack=0):
@@ -251,7 +187,7 @@ def check_file(ctx, path, rd, primers, q=0, want=None, f=(0, 0, 0), slack=0):
 @pytest.mark.gpu
 @pytest.mark.parametrize("split_records", (False, True))
 def test_mixed_fixture_equals_the_yardstick(ctx, tmp_path, split_records):
-    rd = rf.arrays(rf.mixed()[2])
+    rd = rsp.arrays(rsp.mixed()[2])
     want, base = mixed_yardstick(), mixed_yardstick(False)
     assert 0.90 <= want[2] / want[3] <= 0.99                                    # (non-vacuity: conditions on the fixture)
     assert want[0][:, 5].sum() != base[0][:, 5].sum() and want[0][:, 6].sum() != base[0][:, 6].sum() and want[1] > 0
@@ -273,7 +209,7 @@ def edge_reads():
     out = []
 
     def add(pos, cig, qual=None, seq=None):
-        out.append(bq._mk(rng, pos, cig, qual, "e%03d" % len(out), seq))
+        out.append(rsp.mk(rng, pos, cig, qual, "e%03d" % len(out), seq))
     for start in (100, 400, 700):                                               # head masks that end 31, 32 and 33 columns in; reads shorter than
         for n in (1, 31, 32, 33, 64, 65, 150):                                  # their primer; with the '-' primers: masks that meet (100 + 64 columns)
             add(start, [(n, "M")])                                              # and overlap (400 + 32 .. 65 columns)
@@ -315,7 +251,7 @@ def edge_reads():
 @pytest.mark.gpu
 def test_constructed_edges(ctx, tmp_path):
     specs = edge_reads()
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     want = py.counts(rd, L, EDGE_PRIMERS)
     base = py.counts(rd, L)
     assert (want[0][:, 0] < base[0][:, 0]).any() and want[0][:, 5].sum() < base[0][:, 5].sum() and want[0][:, 6].sum() < base[0][:, 6].sum()
@@ -326,7 +262,7 @@ def test_constructed_edges(ctx, tmp_path):
         bamwriter.write_bam(path, rd, ref_len=L, **kw)
         if tag == "split":                                                      # a masked 150-base read whose first pair (16 bytes of SEQ) straddles a BGZF block boundary
             d = engine.DeviceBam(path)
-            starts = bq._seq_starts(rd, d.inflated_bytes)
+            starts = rsp.seq_starts(rd, d.inflated_bytes)
             d.close()
             assert any(s // 512 != (s + 15) // 512 for i, s in enumerate(starts)
                        if int(rd["l_qseq"][i]) == 150 and py.read_mask(int(rd["pos"][i]), int(rd["pos"][i]) + 149, EDGE_PRIMERS) != (int(rd["pos"][i]), int(rd["pos"][i]) + 150))
@@ -338,7 +274,7 @@ def test_constructed_edges(ctx, tmp_path):
 def _long_specs():
     rng = np.random.default_rng(12)
     ref, _ = sy.make_reference(seed=3, L=L, cds=[])
-    specs = rf._background(rng, ref, 200)
+    specs = rsp.background(rng, ref, 200)
     primers = list(SCHEME)
     for k, span in enumerate((520, 555, 599, 700, 700)):
         a, b, pos = int(rng.integers(100, 250)), 7, 50 + 90 * k
@@ -358,7 +294,7 @@ def test_long_reads(ctx, tmp_path):
     """spans of 520 - 700 that start in a '+' primer and end in a '-' primer, each with an insertion and a deletion
     (tally_stream_kernel walks what the packed set leaves out), among short reads"""
     specs, primers = _long_specs()
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     path = str(tmp_path / "long.bam")
     bamwriter.write_bam(path, rd, ref_len=L, block=4096)
     want = check_file(ctx, path, rd, primers)
@@ -390,11 +326,11 @@ def test_long_reads(ctx, tmp_path):
 @pytest.mark.gpu
 def test_together_with_the_floor_and_the_read_filter(ctx, tmp_path):
     f = (20, 0, 0x400)
-    specs = rf.mixed()[2]
-    b, _ = rf.kept(specs, f)
-    rb = rf.arrays(b)
+    specs = rsp.mixed()[2]
+    b, _ = rsp.kept(specs, f)
+    rb = rsp.arrays(b)
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(specs), ref_len=L, block=4096)
+    bamwriter.write_bam(path, rsp.arrays(specs), ref_len=L, block=4096)
     want = py.counts(rb, L, SCHEME, 13)                                         # the yardstick on the records that pass
     assert want[2] < mixed_yardstick()[2] and want[1] > 0
     check_file(ctx, path, rb, SCHEME, q=13, want=want, f=f)
@@ -402,7 +338,7 @@ def test_together_with_the_floor_and_the_read_filter(ctx, tmp_path):
 
 @pytest.mark.gpu
 def test_no_table_and_the_read_set_remembers(ctx, tmp_path):
-    rd = rf.arrays(rf.mixed()[2])
+    rd = rsp.arrays(rsp.mixed()[2])
     want, base = mixed_yardstick(), mixed_yardstick(False)
     n_pos = len(want[0])
     path = str(tmp_path / "A.bam")
@@ -446,7 +382,7 @@ def test_no_table_and_the_read_set_remembers(ctx, tmp_path):
 def test_a_read_masked_from_end_to_end_and_long_read_counts(ctx, tmp_path):
     """one '+' primer over the whole axis: every read is piled up and adds nothing; the masked-read count takes the long reads along"""
     specs, _ = _long_specs()
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     path = str(tmp_path / "long.bam")
     bamwriter.write_bam(path, rd, ref_len=L, block=4096)
     whole = [(0, L + 100, False)]
@@ -457,7 +393,7 @@ def test_a_read_masked_from_end_to_end_and_long_read_counts(ctx, tmp_path):
 
 @pytest.mark.gpu
 def test_flat_array_entry_points_refuse(ctx):
-    rd = rf.arrays(rf.mixed()[2][:300])
+    rd = rsp.arrays(rsp.mixed()[2][:300])
     n_pos = c_oracle.extent(rd, L)
     p = engine.Pipeline(device=0, slots=2, walkers=1)
     try:
@@ -484,16 +420,16 @@ def test_flat_array_entry_points_refuse(ctx):
 def test_one_file_over_three_ranks(tmp_path, split_sub):
     """split_ranks_in_turn(world = 3): the ranges in one piece, and as two sub-ranges each (the helper contexts take the table along).
     The sub-range file holds every record four times: its yardstick is four times the fixture's."""
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     want = mixed_yardstick()[0]
     n_pos = len(want)
     times = 1 if split_sub == 1 else 4
     big = specs if times == 1 else sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in specs], key=lambda r: r["pos"])
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(big), ref_len=L, block=1024 if split_sub == 2 else 4096)
+    bamwriter.write_bam(path, rsp.arrays(big), ref_len=L, block=1024 if split_sub == 2 else 4096)
     tm = {}
-    ta = distributed.split_ranks_in_turn(path, n_pos, rf._gff(orfs), 10, 3, return_parts=True, primers=(SCHEME, 0), split_sub=split_sub, timings=tm)
-    tb = distributed.split_ranks_in_turn(path, n_pos, rf._gff(orfs), 10, 1, return_parts=True, primers=(SCHEME, 0), split_sub=1)
+    ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, primers=(SCHEME, 0), split_sub=split_sub, timings=tm)
+    tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, primers=(SCHEME, 0), split_sub=1)
     assert np.array_equal(ta[1], times * want)
     assert ta[0] == tb[0] and np.array_equal(ta[1], tb[1]) and ta[2] == tb[2]
     assert (tm["split_sub_taken"] > 0) == (split_sub == 2)
@@ -515,11 +451,11 @@ def _contig_bed(path):
 def test_two_reference_contig_layout(ctx, tmp_path):
     """the several-kernel packer under a contig layout, a BED that names both contigs (and one the BAM lacks): every contig's slice
     of the matrix equals the yardstick on that contig's reads under that contig's rows"""
-    recs, _, specs = bq._two_contigs()
+    recs, _, specs = rsp.two_contigs()
     refs = [("c0", 1500), ("c1", 1200)]
     names = [n for n, _ in refs]
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(specs), refs=refs, block=4096)
+    bamwriter.write_bam(path, rsp.arrays(specs), refs=refs, block=4096)
     shift, slot, axis = contigs.layout_for(recs, names, [ln for _, ln in refs])
     rows = pbed.rows_for_layout(pbed.read_bed(_contig_bed(str(tmp_path / "p.bed"))), names, shift)
     assert len(rows) == 8
@@ -529,7 +465,7 @@ def test_two_reference_contig_layout(ctx, tmp_path):
     seen = np.zeros(axis, bool)
     n_masked = 0
     for t, (name, ln) in enumerate(refs):
-        rd = rf.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
+        rd = rsp.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
         want = py.counts(rd, ln, CONTIG_PRIMERS[name])
         n_pos = len(want[0])
         n_masked += want[1]
@@ -545,33 +481,33 @@ def test_cli_single_sample_and_batch(tmp_path, monkeypatch):
     """-i with --primers: -doc is the yardstick's coverage column; FASTA, VCF and GFF equal the run WITHOUT the flag whose counts
     --index-override replaces, at every position, by the yardstick's matrix (downstream code only).  --batch equals -i."""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     want, n_masked = mixed_yardstick()[:2]
     assert len(want) == L
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     bamwriter.write_bam("A.bam", rd, ref_len=L, block=4096)
     bamwriter.write_bam("A2.bam", rd, ref_len=L, block=4096, split_records=True)
-    common = bq._setup_cli(tmp_path, ref, orfs)
-    write_bed("p.bed", SCHEME, extra=["other\t5\t29\tx\t1\t+"])
-    bq._write_override("o.csv.gz", want)
+    common = cr.setup_cli(ref, orfs)
+    write_primer_bed("p.bed", SCHEME, extra=["other\t5\t29\tx\t1\t+"])
+    cr.write_override("o.csv.gz", want)
     out = lambda t: ["-o", t + ".fa", "-vcf", t + ".vcf", "-ogff", t + ".gff", "-doc", t + ".tsv"]
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--primers", "p.bed", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--index-override", "o.csv.gz", "--stats", "b.json"])
-    assert bq._doc_column("a.tsv") == want[:, 0].tolist()
-    assert rf._outputs("a") == rf._outputs("b")
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--primers", "p.bed", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--index-override", "o.csv.gz", "--stats", "b.json"])
+    assert cr.doc_column("a.tsv") == want[:, 0].tolist()
+    assert cr.outputs("a") == cr.outputs("b")
     sa, sb = json.load(open("a.json")), json.load(open("b.json"))
     assert (sa["primers"], sa["reads_primer_masked"], sb["primers"], sb["reads_primer_masked"]) == (12, n_masked, 0, 0)
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "raw.fa", "-doc", "raw.tsv"])   # (the process's context is back at no table)
-    assert bq._doc_column("raw.tsv") == mixed_yardstick(False)[0][:, 0].tolist()
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "raw.fa", "-doc", "raw.tsv"])   # (the process's context is back at no table)
+    assert cr.doc_column("raw.tsv") == mixed_yardstick(False)[0][:, 0].tolist()
     both = py.counts(rd, L, SCHEME, 13, 5)[0]                                   # with the floor and a slack
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "q.fa", "-doc", "q.tsv", "--primers", "p.bed", "--primer-slack", "5", "--min-baseq", "13"])
-    assert bq._doc_column("q.tsv") == both[:, 0].tolist()
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "q.fa", "-doc", "q.tsv", "--primers", "p.bed", "--primer-slack", "5", "--min-baseq", "13"])
+    assert cr.doc_column("q.tsv") == both[:, 0].tolist()
     with open("m.tsv.in", "w") as fh:
         for k, bam in enumerate(("A.bam", "A2.bam")):
             fh.write("\t".join([bam, "S"] + ["m%d.%s" % (k, e) for e in ("fa", "vcf", "gff", "tsv")]) + "\n")
-    rf._run_cli(monkeypatch, ["--batch", "m.tsv.in"] + common + ["--primers", "p.bed", "--stats", "m.json"])
+    cr.run_cli(monkeypatch, ["--batch", "m.tsv.in"] + common + ["--primers", "p.bed", "--stats", "m.json"])
     for k in (0, 1):
-        assert rf._outputs("m%d" % k) == rf._outputs("a"), k
+        assert cr.outputs("m%d" % k) == cr.outputs("a"), k
     assert json.load(open("m.json"))["primers"] == 12
 
 
@@ -580,19 +516,15 @@ def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
     """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange): -doc is the yardstick's coverage and every output equals
     the single-GPU run of the same file under the same table."""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
+    ref, orfs, specs = rsp.mixed()
     want = mixed_yardstick()[0]
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=L, block=4096, split_records=True)
-    common = bq._setup_cli(tmp_path, ref, orfs)
-    write_bed("p.bed", SCHEME)
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=ROOT)
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=L, block=4096, split_records=True)
+    common = cr.setup_cli(ref, orfs)
+    write_primer_bed("p.bed", SCHEME)
     for tag, extra in (("a", ["--gpus", "2"]), ("b", [])):
-        argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", "A.bam", "-name", "S"] + common + \
-            ["-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv", "--primers", "p.bed"] + extra
-        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-1500:]
-    assert bq._doc_column("a.tsv") == want[:, 0].tolist()
-    assert rf._outputs("a") == rf._outputs("b")
+        cr.run_two_ranks(["-i", "A.bam", "-name", "S"] + common + cr.out_args(tag) + ["--primers", "p.bed"] + extra)
+    assert cr.doc_column("a.tsv") == want[:, 0].tolist()
+    assert cr.outputs("a") == cr.outputs("b")
 
 
 @pytest.mark.gpu
@@ -600,30 +532,24 @@ def test_cli_per_contig(tmp_path, monkeypatch):
     """--per-contig: every BED row shifted by its contig's slot; per contig, -doc is the yardstick's coverage and the FASTA record
     equals the single run of that contig's reads alone under the same BED."""
     monkeypatch.chdir(tmp_path)
-    recs, rows, specs = bq._two_contigs()
+    recs, rows, specs = rsp.two_contigs()
     refs = [("c0", 1500), ("c1", 1200)]
-    bamwriter.write_bam("A.bam", rf.arrays(specs), refs=refs, block=4096)
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), refs=refs, block=4096)
     _contig_bed("p.bed")
-    with open("r.fa", "w") as fh:
-        for name, ref in recs:
-            fh.write(">%s\n%s\n" % (name, ref))
-    with open("g.gff", "w") as fh:
-        fh.write("##gff-version 3\n")
-        for name, orfs in rows:
-            fh.write(sy.gff_text(orfs, seqid=name)[1])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "-o", "a.fa", "-doc", "a.tsv",
-                              "--per-contig", "--primers", "p.bed", "--stats", "a.json"])
+    cr.setup_contigs(recs, rows)
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "-o", "a.fa", "-doc", "a.tsv",
+                             "--per-contig", "--primers", "p.bed", "--stats", "a.json"])
     want_fa, want_tsv, n_masked = "", "", 0
     for t, (name, ln) in enumerate(refs):
-        rd = rf.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
+        rd = rsp.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
         want = py.counts(rd, ln, CONTIG_PRIMERS[name])
         n_masked += want[1]
         bamwriter.write_bam("one%d.bam" % t, rd, refs=[(name, ln)], block=4096)
         open("r%d.fa" % t, "w").write(">%s\n%s\n" % recs[t])
         open("g%d.gff" % t, "w").write("##gff-version 3\n" + sy.gff_text(rows[t][1], seqid=name)[1])
-        rf._run_cli(monkeypatch, ["-i", "one%d.bam" % t, "-ref", "r%d.fa" % t, "-gff", "g%d.gff" % t, "-cov", "10", "-name", "S_" + name,
-                                  "-o", "one%d.fa" % t, "-doc", "one%d.tsv" % t, "--primers", "p.bed"])
-        assert bq._doc_column("one%d.tsv" % t) == want[0][:, 0].tolist()
+        cr.run_cli(monkeypatch, ["-i", "one%d.bam" % t, "-ref", "r%d.fa" % t, "-gff", "g%d.gff" % t, "-cov", "10", "-name", "S_" + name,
+                                 "-o", "one%d.fa" % t, "-doc", "one%d.tsv" % t, "--primers", "p.bed"])
+        assert cr.doc_column("one%d.tsv" % t) == want[0][:, 0].tolist()
         want_fa += open("one%d.fa" % t).read()
         want_tsv += "".join("%s\t%s" % (name, line) for line in open("one%d.tsv" % t))
     assert open("a.fa").read() == want_fa and want_fa.count(">") == 2

@@ -133,11 +133,11 @@ def test_modal_tokens_grows_its_buffer_for_many_columns_beyond_64_kib():
 def test_consensus_split_at_world_1_sweeps_the_host_when_the_entries_are_refused(tmp_path):
     """consensus_split_bamfile with no process group: the one rank's entries_fn refuses (E_UNSUPPORTED: a read the entry kernel does not
     take), so the tokens come from the host sweep of the file, and the FASTA is the oracle chain's."""
-    from tests.test_distributed import _consensus_case, _oracle_fasta
+    from tests.consensus_case import consensus_case, oracle_fasta
     from trueconsense_amd import distributed as td
-    ref, orfs, reads = _consensus_case()
+    ref, orfs, reads = consensus_case()
     L = len(ref)
-    want, ins = _oracle_fasta(reads, orfs, L, 30)
+    want, ins = oracle_fasta(reads, orfs, L, 30)
     assert len(ins) >= 4
     path = str(tmp_path / "one.bam")
     bamwriter.write_bam(path, reads, "r", L, level=1)

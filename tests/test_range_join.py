@@ -2,17 +2,14 @@
 tests/range_join_main.cpp and nothing else, built with AddressSanitizer + UBSan and run once over every range table that
 tests/test_distributed.py puts to the Python twin, distributed.check_range_anchors — the verdicts must agree — and over three
 tables of the sub-range use (inflated = -1: no end of a stream to check), which the twin does not have."""
-import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
+from tests import host_program
 from tests.range_chains import random_chains
 from trueconsense_amd.distributed import check_range_anchors
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOTAL = 10_000
 HAND = [                        # the tables of test_check_range_anchors_joins_the_ranks_ranges_into_one_chain
     [(0, 4, -1, 2500), (4, 4, 2500, 5200), (8, 4, 5200, TOTAL)],
@@ -63,23 +60,6 @@ def py_verdict(ranges, inflated):
     raise AssertionError("check_range_anchors says something this test does not know: %r" % why)
 
 
-def build_program(tmp_path):
-    src = os.path.join(ROOT, "tests", "range_join_main.cpp")
-    out = str(tmp_path / "range_join_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
-    tried = []
-    for cxx in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++"), shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + san + ["-o", out, src], capture_output=True, text=True)
-        if r.returncode == 0:
-            return out
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    if not tried:
-        pytest.skip("no C++ compiler")
-    pytest.fail("no compiler built the program:\n" + "\n".join(tried))
-
-
 @pytest.fixture(scope="module")
 def tables():
     """every table as (ranges, inflated, what it is), in the order the program sees them"""
@@ -96,12 +76,9 @@ def tables():
 @pytest.fixture(scope="module")
 def verdicts(tables, tmp_path_factory):
     """the program's output lines, one per table: ONE run of the program, which must end clean under both sanitizers"""
-    prog = build_program(tmp_path_factory.mktemp("range_join"))
+    prog = host_program.build(["tests/range_join_main.cpp"], tmp_path_factory.mktemp("range_join") / "range_join_main", skip_without_compiler=True)
     text = "".join("%d %d\n" % (len(r), inflated) + "".join("%d %d %d %d\n" % tuple(x) for x in r) for r, inflated, _ in tables)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([prog], input=text, capture_output=True, text=True, env=env)
-    assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    r = host_program.run(prog, input=text)
     lines = r.stdout.split("\n")
     assert lines[-1] == "" and len(lines) - 1 == len(tables), (len(lines), len(tables))
     return lines[:-1]

@@ -18,14 +18,14 @@ pytestmark = pytest.mark.gpu
 
 def test_split_step_reduces_through_rccl_on_a_one_rank_communicator(tmp_path):
     import torch
-    from tests.test_distributed import _consensus_case, _oracle_fasta
+    from tests.consensus_case import consensus_case, oracle_fasta
     from trueconsense_amd import _ffi
     from trueconsense_amd import distributed as td
     from trueconsense_amd.io import bamwriter
-    ref, orfs, reads = _consensus_case()
+    ref, orfs, reads = consensus_case()
     L = len(ref)
     rows = [{"start": o["start"], "end": o["end"], "strand": "+"} for o in orfs]
-    want, ins = _oracle_fasta(reads, orfs, L, 30)
+    want, ins = oracle_fasta(reads, orfs, L, 30)
     assert len(ins) >= 4
     path = str(tmp_path / "one.bam")
     bamwriter.write_bam(path, reads, "r", L, level=6, block=3000, split_records=True)

@@ -6,112 +6,24 @@ refusals, the four output files.  Every fixture asserts that 20 - 60 % of A's re
 import ctypes as C
 import functools
 import json
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import c_oracle
+from tests import cli_run as cr
 from tests import fuzz_reads as fz
-from tests import synth_small as ss
+from tests.device_file import uploaded
+from tests.read_specs import FILTERS, FLAGS, MAPQS, L, arrays, background, mixed, passes, randomise, record_bytes, write_pair
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, distributed, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-L = 2000
-MAPQS = (0, 1, 19, 20, 21, 60, 255)
-BITS = ((0x100, 0.1), (0x200, 0.1), (0x400, 0.25), (0x800, 0.1), (0x2, 0.75))      # FLAG bit, how often it is ORed in
-FILTERS = {"mapq": (20, 0, 0), "require": (0, 0x2, 0), "exclude": (0, 0, 0x500), "all": (1, 0x2, 0x400)}
-
-
-def passes(r, f):
-    return r["mapq"] >= f[0] and (r["flag"] & f[1]) == f[1] and (r["flag"] & f[2]) == 0
-
-
-def randomise(rng, specs):
-    """MAPQ from MAPQS and random filterable FLAG bits onto every record"""
-    for r in specs:
-        r["mapq"] = int(rng.choice(MAPQS))
-        for bit, p in BITS:
-            if rng.random() < p:
-                r["flag"] |= bit
-    return specs
-
-
-def arrays(specs):
-    d = ss.reads_from_spec({"reads": specs})
-    d["mapq"] = np.array([r["mapq"] for r in specs], np.uint8)
-    return d
-
-
-def kept(specs, f):
-    """B's records and the number that failed; the fixture's condition: 20 - 60 % fail, both classes there"""
-    b = [r for r in specs if passes(r, f)]
-    n_fail = len(specs) - len(b)
-    assert b and n_fail and 0.2 <= n_fail / len(specs) <= 0.6, (n_fail, len(specs))
-    return b, n_fail
-
-
-def _background(rng, ref, n, tid=0, tag=""):
-    """reads of 30 - 150 bases: plain, with an insertion, a deletion or soft clips; a few unmapped (FLAG 0x4) ones among them"""
-    out = []
-    for k in range(n):
-        ln = int(rng.integers(30, 151))
-        pos = int(rng.integers(0, len(ref) - ln - 8))
-        a = int(rng.integers(5, ln - 10))
-        shape = rng.random()
-        if shape < 0.7:
-            cig = [(ln, "M")]
-        elif shape < 0.8:
-            cig = [(a, "M"), (int(rng.integers(1, 4)), "I"), (ln - a, "M")]
-        elif shape < 0.9:
-            cig = [(a, "M"), (int(rng.integers(1, 6)), "D"), (ln - a, "M")]
-        else:
-            cig = [(3, "S"), (ln, "M"), (2, "S")]
-        flag = (16 if rng.random() < 0.5 else 0) | (4 if rng.random() < 0.02 else 0)
-        out.append(fz._read(rng, ref, pos, cig, flag, "%sr%d" % (tag, k), tid))
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def mixed():
-    """-> (reference, GFF rows, A's records): ~3 000 background reads on L = 2 000 and three planted insertions (insert candidates)"""
-    rng = np.random.default_rng(20240)
-    ref, orfs = sy.make_reference(seed=3, L=L, cds=[(100, 900), (1100, 1900)])
-    specs = _background(rng, ref, 2400)
-    for c, n_ins in ((400, 2), (1000, 13), (1500, 5)):
-        specs += fz._site(rng, ref, L, c, "", 0, 200, "MI", n_ins, False)
-    specs.sort(key=lambda r: r["pos"])
-    return ref, orfs, randomise(rng, specs)
-
-
-def write_pair(tmp_path, specs, f, tag="", **kw):
-    """A and B as files -> (path A, path B, B's arrays, failing records)"""
-    b, n_fail = kept(specs, f)
-    pa, pb = str(tmp_path / (tag + "A.bam")), str(tmp_path / (tag + "B.bam"))
-    kw.setdefault("block", 4096)
-    kw.setdefault("ref_len", L)
-    bamwriter.write_bam(pa, arrays(specs), **kw)
-    rb = arrays(b)
-    bamwriter.write_bam(pb, rb, **kw)
-    return pa, pb, rb, n_fail
-
 
 # ------------------------------------------------------------------------------------------------------------------------ CPU
-def _files(tmp_path):
-    p = {}
-    for name in ("x.bam", "r.fa", "f.gff"):
-        (tmp_path / name).write_text("x")
-        p[name] = str(tmp_path / name)
-    return ["-i", p["x.bam"], "-ref", p["r.fa"], "-gff", p["f.gff"], "-cov", "30", "-name", "S", "-o", "o.fa"]
-
-
 def test_cli_parses_the_three_flags(tmp_path):
-    base = _files(tmp_path)
+    base = cr.base_args(cr.stub_files(tmp_path), "o.fa")
     a = cli.GetArgs(base)
     assert (a.min_mapq, a.require_flags, a.exclude_flags) == (0, 0, 0) and cli.read_filter_of(a) is None
     a = cli.GetArgs(base + ["--min-mapq", "20", "--require-flags", "0x2", "--exclude-flags", "3840"])
@@ -126,7 +38,7 @@ def test_cli_parses_the_three_flags(tmp_path):
 
 
 def test_gpus_children_get_the_filter_only_when_it_is_set(tmp_path):
-    base = _files(tmp_path)
+    base = cr.base_args(cr.stub_files(tmp_path), "o.fa")
     for single in (True, False):
         argv = cli._child_argv(cli.GetArgs(base), single)
         assert not any(x.startswith(("--min-mapq", "--require", "--exclude")) for x in argv)
@@ -187,7 +99,7 @@ def test_host_reader_filter_takes_sortedness_and_the_span_again(tmp_path):
     after it — as B is.  A filter that fails everything leaves an empty, sorted file; the zero filter changes nothing."""
     rng = np.random.default_rng(5)
     ref, _ = sy.make_reference(seed=3, L=L, cds=[])
-    specs = sorted(_background(rng, ref, 300), key=lambda r: r["pos"])
+    specs = sorted(background(rng, ref, 300), key=lambda r: r["pos"])
     for r in specs:
         r["mapq"] = 60 if rng.random() < 0.7 else 0
     stray = fz._read(rng, ref, 5, [(40, "M")], 0, "stray")
@@ -294,22 +206,10 @@ def through(ctx, how, path, f, n_pos):
             rs.free()
             bam.close()
             return out
-        ctx.set_option("one_sync", int(how != "several_kernels"))
-        ctx.set_read_filter(*f)
-        d = engine.DeviceBam(path)
-        try:
-            t0 = ctx.stat("one_sync_taken")
-            rs = ctx.upload_bamfile(d)
-            assert ctx.stat("one_sync_taken") - t0 == int(how != "several_kernels"), (how, ctx.stat("one_sync_last_decline_flags"))
-            out = (ctx.step(rs, n_pos, 0, True)[3], rs.n_piled, rs.max_end, rs.filtered, rs.n_reads)
-            rs.free()
-            return out
-        finally:
-            d.close()
+        with uploaded(ctx, path, f=f, how="several_kernels" if how == "several_kernels" else "one_sync") as rs:
+            return ctx.step(rs, n_pos, 0, True)[3], rs.n_piled, rs.max_end, rs.filtered, rs.n_reads
     finally:
-        ctx.set_option("one_sync", 1)
         ctx.set_option("tally_variant", 0)
-        ctx.set_read_filter()
 
 
 def check_pair(ctx, pa, pb, rb, f, n_fail, n_a, hows=PATHS):
@@ -338,25 +238,20 @@ def test_counts_of_filtered_a_equal_b_and_the_oracle(ctx, tmp_path, name, split_
     check_pair(ctx, pa, pb, rb, f, n_fail, len(specs))
 
 
-def _record_bytes(rd, i):
-    return 36 + int(rd["name_off"][i + 1] - rd["name_off"][i]) + 1 + 4 * int(rd["cigar_off"][i + 1] - rd["cigar_off"][i]) + \
-        (int(rd["l_qseq"][i]) + 1) // 2 + int(rd["l_qseq"][i])
-
-
 @pytest.mark.gpu
 def test_failing_records_at_block_edges(ctx, tmp_path):
     """By hand: a failing record that is the first of its BGZF block, one that is the last of its block, a block of nothing but
     failing records, and the file's last record failing (bamwriter cuts a block when the next record does not fit: replayed here)."""
     rng = np.random.default_rng(9)
     ref, _ = sy.make_reference(seed=3, L=L, cds=[])
-    specs = sorted(_background(rng, ref, 1500), key=lambda r: r["pos"])
+    specs = sorted(background(rng, ref, 1500), key=lambda r: r["pos"])
     for r in specs:
         r["flag"] &= ~4
         r["mapq"] = int(rng.choice((0, 19, 20, 21, 60, 255)))
     rd = arrays(specs)
     block, fill, blocks = 4096, 0, [[]]
     for i in range(len(specs)):
-        n = _record_bytes(rd, i)
+        n = record_bytes(rd, i)
         if fill and fill + n > block:
             blocks.append([])
             fill = 0
@@ -400,7 +295,7 @@ def test_supplementary_records_on_a_second_reference(ctx, tmp_path):
     exclude_flags = 0x800 — on both packers and by the host reader — and equal to B."""
     rng = np.random.default_rng(6)
     ref, _ = sy.make_reference(seed=3, L=L, cds=[])
-    specs = sorted(_background(rng, ref, 600), key=lambda r: r["pos"])
+    specs = sorted(background(rng, ref, 600), key=lambda r: r["pos"])
     for r in specs:
         r["mapq"] = int(rng.choice(MAPQS))
         r["flag"] = (r["flag"] & ~4) | (0x800 if rng.random() < 0.3 else 0)
@@ -479,10 +374,6 @@ def test_device_tokens_of_filtered_a_equal_b_and_the_read_set_remembers(ctx, tmp
     ctx.set_option("one_sync", 1)
 
 
-def _gff(orfs, seqid="S"):
-    return [{"start": o["start"], "end": o["end"], "strand": o["strand"]} for o in orfs]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("split_sub", (1, 2))
 def test_one_file_over_three_ranks(tmp_path, split_sub):
@@ -496,24 +387,11 @@ def test_one_file_over_three_ranks(tmp_path, split_sub):
     pa, pb, rb, n_fail = write_pair(tmp_path, big, f, block=1024 if split_sub == 2 else 4096)
     n_pos = c_oracle.extent(rb, L)
     tm = {}
-    ta = distributed.split_ranks_in_turn(pa, n_pos, _gff(orfs), 10, 3, return_parts=True, read_filter=f, split_sub=split_sub, timings=tm)
-    tb = distributed.split_ranks_in_turn(pb, n_pos, _gff(orfs), 10, 1, return_parts=True, split_sub=1)
+    ta = distributed.split_ranks_in_turn(pa, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, read_filter=f, split_sub=split_sub, timings=tm)
+    tb = distributed.split_ranks_in_turn(pb, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, split_sub=1)
     assert ta[0] == tb[0] and np.array_equal(ta[1], tb[1]) and ta[2] == tb[2]
     assert np.array_equal(ta[1], c_oracle.tally(rb, n_pos)) and len(ta[2]) >= 1
     assert (tm["split_sub_taken"] > 0) == (split_sub == 2)
-
-
-def _outputs(tag):
-    vcf = [ln for ln in open(tag + ".vcf") if not ln.startswith("##")]
-    return open(tag + ".fa").read(), open(tag + ".gff").read(), open(tag + ".tsv").read(), vcf
-
-
-def _run_cli(monkeypatch, args):
-    monkeypatch.setattr(sys, "argv", ["TrueConsense", "ARGS"])
-    cli.main(args)
-
-
-FLAGS = ["--min-mapq", "1", "--require-flags", "0x2", "--exclude-flags", "1024"]       # FILTERS["all"]
 
 
 @pytest.mark.gpu
@@ -530,9 +408,9 @@ def test_cli_single_sample_and_batch(tmp_path, monkeypatch):
     open("g.gff", "w").write(head + body)
     common = ["-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S"]
     for tag, bam, extra in (("a", pa, FLAGS), ("b", pb, [])):
-        _run_cli(monkeypatch, ["-i", bam] + common + ["-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv",
-                                                      "--stats", tag + ".json"] + extra)
-    assert _outputs("a") == _outputs("b") and len(open("a.fa").read().split("\n")[1]) > L       # (a planted insertion was taken)
+        cr.run_cli(monkeypatch, ["-i", bam] + common + ["-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv",
+                                                        "--stats", tag + ".json"] + extra)
+    assert cr.outputs("a") == cr.outputs("b") and len(open("a.fa").read().split("\n")[1]) > L       # (a planted insertion was taken)
     sa, sb = json.load(open("a.json")), json.load(open("b.json"))
     assert (sa["reads"], sa["reads_filtered"]) == (len(specs), n_fail) and (sb["reads"], sb["reads_filtered"]) == (len(specs) - n_fail, 0)
     assert open("a.tsv").read() != _unfiltered(monkeypatch, pa, common)
@@ -540,14 +418,14 @@ def test_cli_single_sample_and_batch(tmp_path, monkeypatch):
         with open(tag + ".tsv.in", "w") as fh:
             for k, bam in enumerate(bams):
                 fh.write("\t".join([bam, "S"] + ["%s%d.%s" % (tag, k, e) for e in ("fa", "vcf", "gff", "tsv")]) + "\n")
-        _run_cli(monkeypatch, ["--batch", tag + ".tsv.in", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10"] + extra)
+        cr.run_cli(monkeypatch, ["--batch", tag + ".tsv.in", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10"] + extra)
     for k in (0, 1):
-        assert _outputs("ma%d" % k) == _outputs("mb%d" % k) == _outputs("b"), k
+        assert cr.outputs("ma%d" % k) == cr.outputs("mb%d" % k) == cr.outputs("b"), k
 
 
 def _unfiltered(monkeypatch, bam, common):
     """(the process's one context is back at no filter for a run without the flags)"""
-    _run_cli(monkeypatch, ["-i", bam] + common + ["-o", "raw.fa", "-doc", "raw.tsv"])
+    cr.run_cli(monkeypatch, ["-i", bam] + common + ["-o", "raw.fa", "-doc", "raw.tsv"])
     return open("raw.tsv").read()
 
 
@@ -561,13 +439,9 @@ def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
     open("r.fa", "w").write(">ref x\n" + ref + "\n")
     head, body = sy.gff_text(orfs, seqid="ref")
     open("g.gff", "w").write(head + body)
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=ROOT)
     for tag, bam, extra in (("a", pa, FLAGS + ["--gpus", "2"]), ("b", pb, [])):
-        argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", bam, "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S",
-                "-o", tag + ".fa", "-vcf", tag + ".vcf", "-ogff", tag + ".gff", "-doc", tag + ".tsv"] + extra
-        r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0, r.stderr[-1500:]
-    assert _outputs("a") == _outputs("b")
+        cr.run_two_ranks(["-i", bam, "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S"] + cr.out_args(tag) + extra)
+    assert cr.outputs("a") == cr.outputs("b")
 
 
 @pytest.mark.gpu
@@ -581,23 +455,17 @@ def test_cli_per_contig(tmp_path, monkeypatch):
         ref, orfs = sy.make_reference(seed=30 + t, L=ln, cds=[(100, 700)])
         recs.append((name, ref))
         rows.append((name, orfs))
-        part = _background(rng, ref, 900, tid=t, tag=name)
+        part = background(rng, ref, 900, tid=t, tag=name)
         part += fz._site(rng, ref, ln, 800, name, t, 200, "MI", 3, False)
         specs += sorted(part, key=lambda r: r["pos"])
     extra = [fz._read(rng, recs[0][1], 20 * k, [(50, "M")], 0, "x%d" % k, 2) for k in range(30)]       # a reference the FASTA does not name
     specs = randomise(rng, specs + extra)
     pa, pb, rb, n_fail = write_pair(tmp_path, specs, f, refs=[("c0", 1500), ("c1", 1200), ("X", 900)])
-    with open("r.fa", "w") as fh:
-        for name, ref in recs:
-            fh.write(">%s\n%s\n" % (name, ref))
-    with open("g.gff", "w") as fh:
-        fh.write("##gff-version 3\n")
-        for name, orfs in rows:
-            fh.write(sy.gff_text(orfs, seqid=name)[1])
+    cr.setup_contigs(recs, rows)
     for tag, bam, more in (("a", pa, FLAGS), ("b", pb, [])):
-        _run_cli(monkeypatch, ["-i", bam, "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "-o", tag + ".fa", "-vcf", tag + ".vcf",
-                               "-ogff", tag + ".gff", "-doc", tag + ".tsv", "--per-contig", "--stats", tag + ".json"] + more)
-    assert _outputs("a") == _outputs("b") and open("a.fa").read().count(">") == 2
+        cr.run_cli(monkeypatch, ["-i", bam, "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "-o", tag + ".fa", "-vcf", tag + ".vcf",
+                                 "-ogff", tag + ".gff", "-doc", tag + ".tsv", "--per-contig", "--stats", tag + ".json"] + more)
+    assert cr.outputs("a") == cr.outputs("b") and open("a.fa").read().count(">") == 2
     sa, sb = json.load(open("a.json")), json.load(open("b.json"))
     assert sa["dropped_reads"] == sb["dropped_reads"] == sum(1 for r in extra if passes(r, f) and not r["flag"] & 4) > 0
     assert (sa["reads"], sa["reads_filtered"], sb["reads_filtered"]) == (len(specs), n_fail, 0)

@@ -10,54 +10,43 @@ import numpy as np
 import pytest
 
 from oracle import c_oracle
+from tests import amplicon_reads_cases as arc
 from tests import amplicon_reads_yardstick as ry
+from tests import device_file as dvf
 from tests import fixed_reads as fx
+from tests import fuzz_masked as fm
+from tests import link_cases as lkc
 from tests import links_yardstick as ly
 from tests import primer_yardstick as py
+from tests import read_specs as rsp
 from tests import repeat_bam as rb
+from tests import schemes as sch
 from tests import strand_yardstick as sy
-from tests import test_amplicon_reads as ar
-from tests import test_floor_mask_fuzz as ff
-from tests import test_link_counts as ln
-from tests import test_primer_mask as pm
-from tests import test_read_filter as rf
 
-L = ff.L
+L = fm.L
 R = 3
 SEED = 1
-CSRC = os.path.join(rf.ROOT, "trueconsense_amd", "csrc")
 PER_READ = ("pos", "flag", "l_qseq", "tid", "mapq")
 RAGGED = (("cigar_off", "cigar"), ("seq_off", "seq"), ("qual_off", "qual"))
 
 
 # ------------------------------------------------------------------------------------------------------------------------ the caps
-def stream_count_caps():
-    """-> (SC_BLOCK, SC_WG_PER_CU) as csrc/stream_count.h states them; the counting kernels' grid is min(ceil(records / SC_BLOCK),
-    compute units * SC_WG_PER_CU)"""
-    text = open(os.path.join(CSRC, "stream_count.h")).read()
-    block, per_cu = (re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text) for name in ("SC_BLOCK", "SC_WG_PER_CU"))
-    assert block and per_cu, "csrc/stream_count.h no longer states SC_BLOCK and SC_WG_PER_CU as constexpr int"
-    return int(block.group(1)), int(per_cu.group(1))
-
-
-MASK_LONG_GRID, MASK_LONG_BLOCK = 64, 256                                       # pk_mask_long's launch: tests/test_stream_scale.py's file B
-PKF_EVENT_OVF = 8                                                               # the one-sync packer's "more events than room" in one_sync_last_decline_flags
 
 
 def test_the_two_caps_stand_in_the_source_where_the_scale_tests_read_them():
     """a change of either launch moves the record counts at which tests/test_stream_scale.py reaches a second trip: SC_BLOCK and
     SC_WG_PER_CU are read from the header (the test moves with them); pk_mask_long's 64 x 256 is restated there, so it is pinned here"""
-    block, per_cu = stream_count_caps()
+    block, per_cu = rb.stream_count_caps()
     assert block > 0 and block % 64 == 0 and per_cu > 0
-    text = open(os.path.join(CSRC, "stream_count.h")).read()
+    text = open(os.path.join(rb.CSRC, "stream_count.h")).read()
     assert re.search(r"std::min<int64_t>\(blocks,\s*\(int64_t\)std::max\(ctx->n_cu,\s*1\)\s*\*\s*SC_WG_PER_CU\)", text), "the counting kernels' grid is no longer capped at compute units * SC_WG_PER_CU"
     assert "base += (int64_t)gridDim.x * SC_BLOCK" in text, "each_record no longer strides by the grid"
-    pack = open(os.path.join(CSRC, "pack_device.hip")).read()
+    pack = open(os.path.join(rb.CSRC, "pack_device.hip")).read()
     launches = re.findall(r"hipLaunchKernelGGL\(pk_mask_long,\s*dim3\((\w+)\),\s*dim3\((\w+)\)", pack)
-    assert launches and set(launches) == {(str(MASK_LONG_GRID), "PB")}, ("pk_mask_long's launch changed: adjust file B of tests/test_stream_scale.py", launches)
-    assert re.search(r"\bPKF_EVENT_OVF\s*=\s*%d\s*," % PKF_EVENT_OVF, pack), "PKF_EVENT_OVF changed: tests/test_stream_scale.py admits that decline by its number"
+    assert launches and set(launches) == {(str(rb.MASK_LONG_GRID), "PB")}, ("pk_mask_long's launch changed: adjust file B of tests/test_stream_scale.py", launches)
+    assert re.search(r"\bPKF_EVENT_OVF\s*=\s*%d\s*," % dvf.PKF_EVENT_OVF, pack), "dvf.PKF_EVENT_OVF changed: tests/test_stream_scale.py admits that decline by its number"
     pb = re.search(r"constexpr\s+int\s+PB\s*=\s*(\d+)\s*;", pack)
-    assert pb and int(pb.group(1)) == MASK_LONG_BLOCK, "PB changed: adjust file B of tests/test_stream_scale.py"
+    assert pb and int(pb.group(1)) == rb.MASK_LONG_BLOCK, "PB changed: adjust file B of tests/test_stream_scale.py"
 
 
 # ------------------------------------------------------------------------------------------------------------------------ the helper
@@ -83,11 +72,11 @@ def same_records(got, want, label):
 def files(tmp_path_factory):
     """the fuzz's seed 1 as the fuzz tests write it, and the same with every record three times -> (src, dst, their arrays)"""
     d = tmp_path_factory.mktemp("repeat")
-    src = ff.write(d, ff.fuzz(SEED))
+    src = fm.write(d, fm.fuzz(SEED))
     dst = str(d / "R.bam")
     n = rb.repeat_records(src, dst, R)
     a, b = c_oracle.read_bam(src), c_oracle.read_bam(dst)
-    assert n == R * len(ff.fuzz(SEED)) == int(b["n_reads"]) and int(a["n_reads"]) == len(ff.fuzz(SEED))
+    assert n == R * len(fm.fuzz(SEED)) == int(b["n_reads"]) and int(a["n_reads"]) == len(fm.fuzz(SEED))
     return src, dst, a, b
 
 
@@ -95,7 +84,7 @@ def test_every_record_three_times_in_place(files):
     src, dst, a, b = files
     n = int(a["n_reads"])
     same_records(take(b, np.arange(R * n)), take(a, np.repeat(np.arange(n), R)), "r0 x 3, r1 x 3, ...")
-    spec = rf.arrays(ff.fuzz(SEED))                                             # ... and the source is what the fuzz wrote
+    spec = rsp.arrays(fm.fuzz(SEED))                                             # ... and the source is what the fuzz wrote
     assert np.array_equal(a["pos"], spec["pos"]) and np.array_equal(a["flag"], spec["flag"]) and np.array_equal(a["mapq"], spec["mapq"])
     header, records = rb.split(rb.inflate(dst))
     assert header == rb.split(rb.inflate(src))[0] and len(records) == R * n
@@ -124,26 +113,26 @@ def test_every_yardstick_is_additive_over_repeated_records(files):
     token counts, the strand halves, the link counts at one and seven neighbours and the reads per amplicon of the repeated file are
     each three times those of the source — what lets the scale tests multiply the yardstick of the small file"""
     _, _, a, b = files
-    tabled, slack, q, f = ff.MODES["all"]
-    table = ff.table_of(SEED)
+    tabled, slack, q, f = fm.MODES["all"]
+    table = fm.table_of(SEED)
     pa, pb = passing(a, f), passing(b, f)
     assert int(pb["n_reads"]) == R * int(pa["n_reads"]) and 0 < int(pa["n_reads"]) < int(a["n_reads"])
     want, got = py.counts(pa, L, table, q, slack), py.counts(pb, L, table, q, slack)
-    assert np.array_equal(want[0], ff.yardstick(SEED, None, None, f, tabled, q, slack)[0])     # (the file read back is the fuzz's records)
+    assert np.array_equal(want[0], fm.yardstick(SEED, None, None, f, tabled, q, slack)[0])     # (the file read back is the fuzz's records)
     assert np.array_equal(got[0], R * want[0]) and tuple(got[1:]) == tuple(R * v for v in want[1:]) and want[1] > 0
     n_pos = len(want[0])
     cols = list(range(n_pos))
     for w, g in zip(sy.counts(pa, cols, L, table, q, slack), sy.counts(pb, cols, L, table, q, slack)):
         assert w.any() and np.array_equal(g, R * w)
     ca, cb = ly.classes(pa, L, table, q, slack, n_pos=n_pos), ly.classes(pb, L, table, q, slack, n_pos=n_pos)
-    for use in (ln.sparse_columns(SEED, n_pos), ln.window_columns(want[0])):
+    for use in (lkc.sparse_columns(SEED, n_pos), lkc.window_columns(want[0])):
         for k in (1, 7):
             w = ly.joint(ca, use, k)
-            ln.not_vacuous(w, (len(use), k))
+            lkc.not_vacuous(w, (len(use), k))
             assert np.array_equal(ly.joint(cb, use, k), R * w)
     ka, kb = (ry.kept_columns(rd, None, f, rd["mapq"]) for rd in (a, b))
     assert len(kb) == R * len(ka) > 0
-    for amps in (ar.tiled(7), ar.padded(ar.tiled(7), ar.LDS + 1)):
+    for amps in (arc.tiled(7), arc.padded(arc.tiled(7), arc.LDS + 1)):
         for s in (0, 5):
             w = ry.counts(ka, amps, s)
             assert w[:7, 0].all() and w[len(amps):, 0].all() and np.array_equal(ry.counts(kb, amps, s), R * w)
@@ -166,9 +155,9 @@ def test_blocks_filled_to_the_brim_hold_the_same_records(files, tmp_path):
 
 def test_keep_gives_exactly_the_kept_records(files, tmp_path):
     src, _, a, _ = files
-    specs = ff.fuzz(SEED)
-    long_ones = [i for i, r in enumerate(specs) if ff._piles_up(r) and ff._span(r) > ff.LONG]
-    assert len(long_ones) == ff.n_long(specs) >= 15
+    specs = fm.fuzz(SEED)
+    long_ones = [i for i, r in enumerate(specs) if fm._piles_up(r) and fm._span(r) > fm.LONG]
+    assert len(long_ones) == fm.n_long(specs) >= 15
     want = take(a, np.repeat(long_ones, 5))
     for how, keep in (("indices", long_ones), ("predicate", lambda i, rec: i in set(long_ones))):
         dst = str(tmp_path / (how + ".bam"))
@@ -205,9 +194,9 @@ def test_the_numpy_restatement_equals_the_committed_yardsticks(tmp_path, which, 
     covered = np.nonzero(c_oracle.tally(back, n_pos)[:, 0])[0]
     window = list(range(int(covered[0]), min(int(covered[0]) + 120, n_pos)))
     sparse = sorted(set(int(c) for c in np.random.default_rng(3).choice(covered, 11, replace=False)))
-    for f, table, slack in ((ff.NONE, (), 0), (fx.MQ, (), 0), (fx.MQ, pm.SCHEME, 3)):
+    for f, table, slack in ((fm.NONE, (), 0), (fx.MQ, (), 0), (fx.MQ, sch.PRIMER_SCHEME, 3)):
         kept = passing(back, f)
-        assert (f == ff.NONE) == (int(kept["n_reads"]) == 2000) and int(kept["n_reads"]) > 500
+        assert (f == fm.NONE) == (int(kept["n_reads"]) == 2000) and int(kept["n_reads"]) > 500
         whole, n_masked = py.counts(kept, fx.L, table, q, slack)[:2]
         assert np.array_equal(fx.matrix(rd, n_pos, q, f, table, slack), whole) and whole[:, 1:5].sum(0).all() and (whole[:, 0] > whole[:, 1:5].sum(1)).any()
         assert fx.masked_reads(rd, f, table, slack) == n_masked and (n_masked > 20) == bool(table)
@@ -222,11 +211,11 @@ def test_the_numpy_restatement_equals_the_committed_yardsticks(tmp_path, which, 
                 want = ly.joint(cls, use, k)
                 assert np.array_equal(fx.links(rd, use, k, q, f, table, slack), want) and (want.any() or len(use) == 2)
         columns = ry.kept_columns(back, None, f, back["mapq"])
-        for amps in (fx.SCHEME, ar.padded(fx.SCHEME, ar.LDS + 1)):
+        for amps in (fx.SCHEME, arc.padded(fx.SCHEME, arc.LDS + 1)):
             for s in (0, 5):
                 want = ry.counts(columns, amps, s)
                 assert np.array_equal(fx.amplicon_reads(rd, amps, s, f), want) and want[:, 0].sum() == len(columns)
-    assert fx.SCHEME[:7] == ar.tiled(7)
+    assert fx.SCHEME[:7] == arc.tiled(7)
     if which == "spread":
         want = ry.counts(ry.kept_columns(back), fx.SCHEME, 0)
         assert want[:8, 0].all() and want[7, 1] > 0 and want[8, 0] > 0 and want[9, 0] > 0     # reads in every amplicon, full-length ones, ambiguous, unassigned

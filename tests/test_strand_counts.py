@@ -5,7 +5,6 @@ device route is the matrix of the same file uploaded under exclude_flags | 0x10 
 tests/test_floor_mask_fuzz.py (tests/fuzz_masked.specs: every CIGAR op, SEQ '*', short SEQ, no QUAL, long reads, planted insertion
 sites, FLAG 16 on a third of the records).  The host record buffer lies between guard words that are checked after every call.  The
 rule, the writer and the argument handling are checked without a GPU in tests/test_strand_rule.py."""
-import contextlib
 import ctypes as C
 import functools
 import json
@@ -14,15 +13,15 @@ import os
 import numpy as np
 import pytest
 
+from tests import cli_run as cr
+from tests import device_file as dvf
 from tests import fuzz_masked as fm
 from tests import primer_yardstick as py
+from tests import read_specs as rsp
 from tests import strand_yardstick as sy
-from tests import test_base_quality as bq
-from tests import test_floor_mask_fuzz as ff
-from tests import test_matrix_abi as ma
-from tests import test_primer_mask as pm
-from tests import test_read_filter as rf
 from tests import variant_yardstick as vy
+from tests.device_file import uploaded
+from tests.strand_cases import LDS, G, L, device_counts, differ, halves, not_vacuous, one_column_a_record, sparse_columns
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, contigs, engine
 from trueconsense_amd import distributed as td
@@ -31,9 +30,6 @@ from trueconsense_amd.io import bamwriter
 from trueconsense_amd.io import primers as pbed
 
 pytestmark = pytest.mark.gpu
-L = ff.L
-LDS = engine.STRAND_LDS
-G = 64                                                                          # guard words on either side of the records
 assert fm.FLAGS.count(16) == 2 and len(fm.FLAGS) == 6
 
 
@@ -43,105 +39,20 @@ def ctx():
         yield c
 
 
-@contextlib.contextmanager
-def uploaded(ctx, path, primers=(), q=0, f=ff.NONE, slack=0, one_sync=1, blocks=None):
-    """the file as a device-decoded read set built under the table, the floor and the filter; the context is back at its defaults
-    while the read set is in use (it must remember what it was built under)"""
-    d = engine.DeviceBam(path)
-    try:
-        try:
-            ctx.set_option("one_sync", one_sync)
-            ctx.set_read_filter(*f)
-            ctx.set_min_base_quality(q)
-            ctx.set_primers(primers, slack)
-            rs = ctx.upload_bamfile(d, blocks)
-        finally:
-            ctx.set_option("one_sync", 1)
-            ctx.set_read_filter()
-            ctx.set_min_base_quality()
-            ctx.set_primers()
-        try:
-            yield rs
-        finally:
-            rs.free()
-    finally:
-        d.close()
-
-
-def device_counts(ctx, rs, cols):
-    """tcmi_readset_strand_counts into a host buffer between guards -> (fwd, rev) int32 [n, 7]; pos and reserved are checked here, and
-    Context.strand_counts must give the same numbers (run after run)"""
-    cols = np.ascontiguousarray(cols, np.int64)
-    n = len(cols)
-    buf = ma.sentinel(2 * G + 16 * n, np.int32, salt=7).copy()
-    before = buf.copy()
-    rc = _ffi.lib().tcmi_readset_strand_counts(ctx.handle, rs.handle, n, _ffi.ptr(cols), C.c_void_p(buf.ctypes.data + 4 * G))
-    _ffi.check(rc, ctx.handle)
-    assert np.array_equal(buf[:G], before[:G]) and np.array_equal(buf[-G:], before[-G:]), "a guard around the records was written"
-    got = buf[G:-G].view(engine.STRAND_DTYPE).copy()
-    assert np.array_equal(got["pos"], cols) and not got["reserved"].any()
-    again = ctx.strand_counts(rs, cols)
-    assert np.array_equal(got["fwd"], again["fwd"]) and np.array_equal(got["rev"], again["rev"]) and np.array_equal(again["pos"], cols)
-    return got["fwd"], got["rev"]
-
-
-def differ(got, want, cols, label):
-    """'' when (fwd, rev) equal the yardstick's; else the first differing columns with both rows"""
-    if all(np.array_equal(g, w) for g, w in zip(got, want)):
-        return ""
-    rows = []
-    for name, g, w in zip(("fwd", "rev"), got, want):
-        for k in np.unique(np.argwhere(g != w)[:, 0])[:6].tolist():
-            rows.append("%s column %d: got %r want %r" % (name, cols[k], g[k].tolist(), w[k].tolist()))
-    return "%r (coverage, A, T, C, G, X, I)\n%s" % (label, "\n".join(rows))
-
-
-@functools.lru_cache(maxsize=None)
-def halves(seed, mode, window=None):
-    """-> (fwd, rev) of the yardstick on every column 0..n_pos-1, n_pos: the extent of the yardstick over all passing records"""
-    tabled, slack, q, f = ff.MODES[mode]
-    _, rd = ff.passing(seed, None, window, f)
-    n_pos = len(ff.yardstick(seed, None, window, f, tabled, q, slack)[0])
-    fwd, rev = sy.counts(rd, range(n_pos), L, ff.table_of(seed) if tabled else (), q, slack)
-    return fwd, rev, n_pos
-
-
-def sparse_columns(seed, n_pos, n=40):
-    """40 random columns and the columns on both sides of every mask edge of the seed's table"""
-    rng = np.random.default_rng(500 + seed)
-    cols = set(int(c) for c in rng.choice(n_pos, n, replace=False))
-    for s, e, rev in ff.table_of(seed):
-        edge = s if rev else e
-        cols.update(c for c in (edge - 1, edge) if 0 <= c < n_pos)
-    assert len(cols) <= LDS
-    return sorted(cols)
-
-
-def long_read_covers(specs, cols):
-    return any(ff._piles_up(r) and ff._span(r) > ff.LONG and any(r["pos"] <= c < r["pos"] + ff._span(r) for c in cols) for r in specs)
-
-
-def not_vacuous(specs, fwd, rev, cols, label):
-    """on the yardstick, before the device runs: both strands have a non-zero count in every plane among the queried columns, and a
-    long read covers one of them"""
-    assert fwd.sum(0).all() and rev.sum(0).all(), (label, fwd.sum(0).tolist(), rev.sum(0).tolist())
-    assert long_read_covers(specs, cols), label
-
-
 # ---- 1. both routes, three modes ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("one_sync", (1, 0))
-@pytest.mark.parametrize("mode", sorted(ff.MODES))
-@pytest.mark.parametrize("seed", ff.SEEDS)
+@pytest.mark.parametrize("mode", sorted(fm.MODES))
+@pytest.mark.parametrize("seed", fm.SEEDS)
 def test_both_routes_equal_the_yardstick_and_add_up_to_the_matrix(ctx, tmp_path, seed, mode, one_sync):
-    tabled, slack, q, f = ff.MODES[mode]
-    specs, _ = ff.passing(seed, None, None, f)
+    tabled, slack, q, f = fm.MODES[mode]
+    specs, _ = fm.passing(seed, None, None, f)
     fwd, rev, n_pos = halves(seed, mode)
     sparse, dense = sparse_columns(seed, n_pos), list(range(n_pos))
     assert len(sparse) <= LDS < len(dense)
     for cols in (sparse, dense):
         not_vacuous(specs, fwd[cols], rev[cols], cols, (seed, mode))
-    path = ff.write(tmp_path, ff.fuzz(seed))
-    with uploaded(ctx, path, ff.table_of(seed) if tabled else (), q, f, slack, one_sync) as rs:
+    path = fm.write(tmp_path, fm.fuzz(seed))
+    with uploaded(ctx, path, fm.table_of(seed) if tabled else (), q, f, slack, one_sync) as rs:
         matrix = ctx.step(rs, n_pos, 0, True)[3]
         for route, cols in (("LDS", sparse), ("memory", dense)):
             got = device_counts(ctx, rs, cols)
@@ -152,16 +63,16 @@ def test_both_routes_equal_the_yardstick_and_add_up_to_the_matrix(ctx, tmp_path,
 
 # ---- 2. the independent device route -------------------------------------------------------------------------------------------------
 def test_each_strand_equals_the_matrix_of_the_file_filtered_by_flag_0x10(ctx, tmp_path):
-    seed = ff.SEEDS[0]
-    tabled, slack, q, f = ff.MODES["all"]
-    specs, _ = ff.passing(seed, None, None, f)
+    seed = fm.SEEDS[0]
+    tabled, slack, q, f = fm.MODES["all"]
+    specs, _ = fm.passing(seed, None, None, f)
     fwd, rev, n_pos = halves(seed, "all")
     cols = list(range(n_pos))
     not_vacuous(specs, fwd, rev, cols, seed)
-    path = ff.write(tmp_path, ff.fuzz(seed))
-    table = ff.table_of(seed)
-    only_fwd = pm.through(ctx, "one_sync", path, table, n_pos, q, (f[0], f[1], f[2] | 0x10), slack)[0]
-    only_rev = pm.through(ctx, "one_sync", path, table, n_pos, q, (f[0], f[1] | 0x10, f[2]), slack)[0]
+    path = fm.write(tmp_path, fm.fuzz(seed))
+    table = fm.table_of(seed)
+    only_fwd = dvf.through(ctx, "one_sync", path, table, n_pos, q, (f[0], f[1], f[2] | 0x10), slack)[0]
+    only_rev = dvf.through(ctx, "one_sync", path, table, n_pos, q, (f[0], f[1] | 0x10, f[2]), slack)[0]
     assert only_fwd.any() and only_rev.any() and not np.array_equal(only_fwd, only_rev)
     with uploaded(ctx, path, table, q, f, slack) as rs:
         got = device_counts(ctx, rs, cols)
@@ -171,12 +82,12 @@ def test_each_strand_equals_the_matrix_of_the_file_filtered_by_flag_0x10(ctx, tm
 
 # ---- 3. the staging edge -------------------------------------------------------------------------------------------------------------
 def test_the_largest_staged_query_and_the_smallest_in_memory(ctx, tmp_path):
-    seed = ff.SEEDS[1]
-    specs, _ = ff.passing(seed)
+    seed = fm.SEEDS[1]
+    specs, _ = fm.passing(seed)
     fwd, rev, n_pos = halves(seed, "floor")
     cols = sorted(int(c) for c in np.random.default_rng(9).choice(n_pos, LDS + 1, replace=False))
     not_vacuous(specs, fwd[cols[:LDS]], rev[cols[:LDS]], cols[:LDS], seed)
-    path = ff.write(tmp_path, ff.fuzz(seed))
+    path = fm.write(tmp_path, fm.fuzz(seed))
     with uploaded(ctx, path, (), 13) as rs:
         staged, memory = device_counts(ctx, rs, cols[:LDS]), device_counts(ctx, rs, cols)
     assert not differ(staged, (fwd[cols[:LDS]], rev[cols[:LDS]]), cols, "staged")
@@ -189,11 +100,11 @@ def test_the_largest_staged_query_and_the_smallest_in_memory(ctx, tmp_path):
 def test_small_files(ctx, tmp_path, n_rec):
     """1, 63, 65 and 257 records (fewer than a wavefront, one more, one more than a workgroup); a column nobody covers, a column beyond
     every read; the same records under a filter that all of them fail: zeros, and TCMI_OK"""
-    every = [r for r in ff.fuzz(ff.SEEDS[2]) if ff._piles_up(r)]
+    every = [r for r in fm.fuzz(fm.SEEDS[2]) if fm._piles_up(r)]
     step = len(every) // n_rec
-    specs = every[::step][:n_rec] if n_rec > 1 else [next(r for r in every if r["flag"] & 16 and ff._span(r) > 20)]
+    specs = every[::step][:n_rec] if n_rec > 1 else [next(r for r in every if r["flag"] & 16 and fm._span(r) > 20)]
     assert len(specs) == n_rec
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     whole = py.counts(rd, L, (), 13)[0]
     n_pos = len(whole)
     beyond = n_pos + 700
@@ -202,7 +113,7 @@ def test_small_files(ctx, tmp_path, n_rec):
     dense = list(range(n_pos)) + [beyond]
     sparse = sorted(set(int(c) for c in np.random.default_rng(n_rec).choice(n_pos, 60, replace=False)) | {bare[0], int(np.argmax(whole[:, 0])), beyond})
     want = sy.counts(rd, dense, L, (), 13)
-    path = ff.write(tmp_path, specs)
+    path = fm.write(tmp_path, specs)
     with uploaded(ctx, path, (), 13) as rs:
         assert rs.n_reads == n_rec
         matrix = ctx.step(rs, n_pos, 0, True)[3]
@@ -223,16 +134,16 @@ def test_small_files(ctx, tmp_path, n_rec):
 # ---- 5. depth ------------------------------------------------------------------------------------------------------------------------
 def test_many_lanes_on_one_counter(ctx, tmp_path):
     """every random read starts inside a window of 50 columns: depth past 255 on one column, the sums stay exact"""
-    seed, window = ff.DEEP_SEED, ff.DEEP_WINDOW
-    tabled, slack, q, f = ff.MODES["all"]
-    specs, _ = ff.passing(seed, None, window, f)
+    seed, window = fm.DEEP_SEED, fm.DEEP_WINDOW
+    tabled, slack, q, f = fm.MODES["all"]
+    specs, _ = fm.passing(seed, None, window, f)
     fwd, rev, n_pos = halves(seed, "all", window)
     sparse = sorted(set(range(window[0] - 20, window[1] + 60, 3)) | set(sparse_columns(seed, n_pos, 20)))[:LDS]
     dense = list(range(n_pos))
     assert (fwd[sparse, 0] + rev[sparse, 0]).max() >= 256 and min(fwd[sparse, 0].max(), rev[sparse, 0].max()) >= 64
     not_vacuous(specs, fwd[sparse], rev[sparse], sparse, "deep")
-    path = ff.write(tmp_path, ff.fuzz(seed, None, window))
-    with uploaded(ctx, path, ff.table_of(seed), q, f, slack) as rs:
+    path = fm.write(tmp_path, fm.fuzz(seed, None, window))
+    with uploaded(ctx, path, fm.table_of(seed), q, f, slack) as rs:
         matrix = ctx.step(rs, n_pos, 0, True)[3]
         for cols in (sparse, dense):
             got = device_counts(ctx, rs, cols)
@@ -242,30 +153,20 @@ def test_many_lanes_on_one_counter(ctx, tmp_path):
 
 
 # ---- 5b. the join's worst case ---------------------------------------------------------------------------------------------------------
-@functools.lru_cache(maxsize=None)
-def one_column_a_record():
-    """-> (specs, cols): 65 kept records, 6 all-match bases each.  Record r < 64 starts at column 100 + 10 r, so no two of them share
-    a column: the first wavefront holds 64 distinct counters a round, one pass of the join per lane.  Record 64 lies on record 0's
-    columns, on the other strand, alone in a second, ragged wavefront.  cols: one queried column per record (also used by
-    test_link_counts)"""
-    def rec(r, pos, flag):
-        return {"pos": pos, "flag": flag, "cigar": "6M", "seq": "ACGT"[r % 4] * 6, "name": "j%d" % r, "tid": 0, "qual": 30, "mapq": 60}
-    specs = [rec(r, 100 + 10 * r, 16 if r % 3 == 0 else 0) for r in range(64)] + [rec(64, 100, 0)]
-    return specs, [100 + 10 * r + r % 6 for r in range(64)]
 
 
 def test_a_wavefront_on_64_columns_and_a_ragged_one_behind_it(ctx, tmp_path):
     """the records of one_column_a_record at one column per record, staged; and the same query padded past the LDS capacity with
     columns beyond every read, counted in memory"""
     specs, cols = one_column_a_record()
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     n_pos = len(py.counts(rd, L)[0])
     padded = cols + [n_pos + 700 + j for j in range(LDS + 1 - len(cols))]
     assert len(specs) == 65 and len(cols) == 64 <= LDS < len(padded) and cols[-1] < n_pos
     want = sy.counts(rd, padded, L)
     cov = (want[0] + want[1])[:, 0].tolist()
     assert cov == [2] + [1] * 63 + [0] * (len(padded) - 64) and want[0][0, 0] == 1 and want[1][0, 0] == 1, cov
-    path = ff.write(tmp_path, specs)
+    path = fm.write(tmp_path, specs)
     with uploaded(ctx, path) as rs:
         assert rs.n_reads == 65 and rs.n_piled == 65
         matrix = ctx.step(rs, n_pos, 0, True)[3]
@@ -279,11 +180,11 @@ def test_a_wavefront_on_64_columns_and_a_ragged_one_behind_it(ctx, tmp_path):
 # ---- 6. a contig layout ----------------------------------------------------------------------------------------------------------------
 def test_two_contigs_under_a_layout(ctx, tmp_path):
     """columns in both slots and one in the guard between them; each contig under its own table, floor 13 and the read filter"""
-    parts, specs = ff.contig_case()
-    refs = [(name, ln) for name, ln, _ in ff.CONTIGS]
+    parts, specs = fm.contig_case()
+    refs = [(name, ln) for name, ln, _ in fm.CONTIGS]
     names = [n for n, _ in refs]
     path = str(tmp_path / "A.bam")
-    bamwriter.write_bam(path, rf.arrays(specs), refs=refs, block=4096)
+    bamwriter.write_bam(path, rsp.arrays(specs), refs=refs, block=4096)
     recs = [(name, syn.make_reference(seed=3, L=ln, cds=[])[0]) for name, ln in refs]
     shift, slot, axis = contigs.layout_for(recs, names, [ln for _, ln in refs])
     rows = pbed.rows_for_layout([(name, s, e, rev) for name, _, table, _ in parts for s, e, rev in table], names, shift)
@@ -291,9 +192,9 @@ def test_two_contigs_under_a_layout(ctx, tmp_path):
     assert guard >= int(shift[0]) + refs[0][1]
     cols, want_f, want_r = [], [], []
     for t, (name, ln, table, part) in enumerate(parts):
-        kept = [dict(r, tid=0) for r in rf.kept(part, ff.F)[0]]
+        kept = [dict(r, tid=0) for r in rsp.kept(part, fm.F)[0]]
         own = list(range(ln))
-        fwd, rev = sy.counts(rf.arrays(kept), own, ln, table, 13)
+        fwd, rev = sy.counts(rsp.arrays(kept), own, ln, table, 13)
         not_vacuous(kept, fwd, rev, own, name)
         cols += [c + int(shift[t]) for c in own] + ([guard] if t == 0 else [])
         want_f += [fwd] + ([np.zeros((1, 7), np.int32)] if t == 0 else [])
@@ -302,7 +203,7 @@ def test_two_contigs_under_a_layout(ctx, tmp_path):
     want = (np.concatenate(want_f), np.concatenate(want_r))
     try:
         ctx.set_layout(shift, slot)
-        with uploaded(ctx, path, rows, 13, ff.F) as rs:
+        with uploaded(ctx, path, rows, 13, fm.F) as rs:
             matrix = ctx.step(rs, axis, 0, True)[3]
             at = cols.index(guard)
             for use in (cols, cols[at - 100:at + 100]):                         # (the memory route, and a staged query that holds the guard column)
@@ -326,12 +227,12 @@ def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
     """records that straddle 4 096-byte BGZF blocks: three block ranges taken in turn add up to the whole file's counts, and a read set
     of two sub-ranges (tcmi_split_step, "split_sub") answers with the same"""
     import torch
-    seed = ff.SEEDS[3]
-    tabled, slack, q, f = ff.MODES["all"]
-    specs, _ = ff.passing(seed, None, None, f)
+    seed = fm.SEEDS[3]
+    tabled, slack, q, f = fm.MODES["all"]
+    specs, _ = fm.passing(seed, None, None, f)
     fwd, rev, n_pos = halves(seed, "all")
-    table = ff.table_of(seed)
-    path = ff.write(tmp_path, ff.fuzz(seed), block=4096, split_records=True)
+    table = fm.table_of(seed)
+    path = fm.write(tmp_path, fm.fuzz(seed), block=4096, split_records=True)
     for cols in (sparse_columns(seed, n_pos), list(range(n_pos))):
         not_vacuous(specs, fwd[cols], rev[cols], cols, seed)
         with uploaded(ctx, path, table, q, f, slack) as rs:
@@ -348,11 +249,11 @@ def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
                 total[0] += got[0]
                 total[1] += got[1]
                 n_reads += rs.n_reads
-        assert n_reads == len(ff.fuzz(seed)) and not differ(total, whole, cols, "three ranges")
+        assert n_reads == len(fm.fuzz(seed)) and not differ(total, whole, cols, "three ranges")
     # (sub-ranges want at least 64 blocks a piece: the same records four times over in 1 024-byte blocks, four times the counts)
-    big = sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in ff.fuzz(seed)], key=lambda r: r["pos"])
+    big = sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in fm.fuzz(seed)], key=lambda r: r["pos"])
     path4 = str(tmp_path / "A4.bam")
-    bamwriter.write_bam(path4, rf.arrays(big), ref_len=L, block=1024)
+    bamwriter.write_bam(path4, rsp.arrays(big), ref_len=L, block=1024)
     c = engine.Context(0, stream=torch.cuda.current_stream().cuda_stream)
     d = engine.DeviceBam(path4)
     try:
@@ -373,16 +274,16 @@ def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
 
 # ---- 8. refusals -----------------------------------------------------------------------------------------------------------------------
 def test_refusals(ctx, tmp_path):
-    specs = ff.fuzz(ff.SEEDS[0])
-    pa = ff.write(tmp_path, specs[:400])
+    specs = fm.fuzz(fm.SEEDS[0])
+    pa = fm.write(tmp_path, specs[:400])
     pb_ = str(tmp_path / "B.bam")
-    bamwriter.write_bam(pb_, rf.arrays(specs[400:700]), ref_len=L, block=4096)
+    bamwriter.write_bam(pb_, rsp.arrays(specs[400:700]), ref_len=L, block=4096)
     da, db = engine.DeviceBam(pa), engine.DeviceBam(pb_)
     try:
         ra = ctx.upload_bamfile(da)
         ok = ctx.strand_counts(ra, [10, 500, 1500])
         assert ok["fwd"][:, 0].any() and ok["rev"][:, 0].any()
-        guarded = ma.sentinel(2 * G + 16 * 4, np.int32, salt=3).copy()
+        guarded = dvf.sentinel(2 * G + 16 * 4, np.int32, salt=3).copy()
         for bad, word in (([5, 5], "strictly ascending"), ([7, 5], "strictly ascending"), ([1, 2, 2, 9], "strictly ascending"), ([], "1..1048576"),
                           (np.arange((1 << 20) + 1), "1..1048576"), ([3, 1 << 29], "2^29"), ([-1, 4], "2^29")):
             with pytest.raises(_ffi.TcmiError) as e:
@@ -413,7 +314,7 @@ def test_refusals(ctx, tmp_path):
 
 
 def test_the_launch_is_profiled_and_nothing_runs_without_the_call(ctx, tmp_path):
-    path = ff.write(tmp_path, ff.fuzz(ff.SEEDS[0])[:500])
+    path = fm.write(tmp_path, fm.fuzz(fm.SEEDS[0])[:500])
     try:
         ctx.profile(True)
         with uploaded(ctx, path) as rs:
@@ -455,7 +356,7 @@ def cli_case():
 
 def cli_yardstick(specs, ref, rule=(10, 1, 10)):
     """-> (the records, {pos: (fwd, rev)}, the strand array) of the yardsticks at the command line's default thresholds"""
-    rd = rf.arrays(specs)
+    rd = rsp.arrays(specs)
     whole = py.counts(rd, CL)[0]
     recs = vy.records(whole, ref.encode(), 3, 100, 1, 10)
     cols = sorted({p for p, *_ in recs})
@@ -472,40 +373,40 @@ def test_cli_single_sample_per_contig_and_split(tmp_path, monkeypatch):
     assert want == sy.text(recs, strand, "ref", ref.encode(), 10, 1, 10)
     verdict_at = {int(ln.split("\t")[1]) - 1: ln.split("\t")[-1] for ln in want.splitlines()}
     assert (verdict_at[BOTH], verdict_at[FWD_ONLY], verdict_at[LOW_AT]) == ("PASS", "BIAS", "LOW"), verdict_at
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=CL, block=4096)
-    common = bq._setup_cli(tmp_path, ref, orfs)
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=CL, block=4096)
+    common = cr.setup_cli(ref, orfs)
     out = lambda t: ["-o", t + ".fa", "-vcf", t + ".vcf", "-ogff", t + ".gff", "-doc", t + ".tsv"]
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--variant-table", "a.var", "--variant-strand", "--stats", "a.json"])
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--variant-table", "b.var", "--stats", "b.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("a") + ["--variant-table", "a.var", "--variant-strand", "--stats", "a.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + out("b") + ["--variant-table", "b.var", "--stats", "b.json"])
     got, plain = open("a.var").read(), open("b.var").read()
     assert got == engine.VARIANTS_STRAND_HEADER + want
     assert [ln.split("\t")[:7] for ln in got.splitlines()] == [ln.split("\t") for ln in plain.splitlines()] and plain.startswith(engine.VARIANTS_HEADER)
-    assert rf._outputs("a") == rf._outputs("b")
+    assert cr.outputs("a") == cr.outputs("b")
     sa, sb = json.load(open("a.json")), json.load(open("b.json"))
     n_bias, n_low = (sum(v == w for v in (ln.split("\t")[-1] for ln in want.splitlines())) for w in ("BIAS", "LOW"))
     assert (sa["variant_strand_bias"], sa["variant_strand_low"]) == (n_bias, n_low) and n_bias > 0 and n_low > 0
     assert (sb["variant_strand_bias"], sb["variant_strand_low"]) == (0, 0) and sa["variant_records"] == sb["variant_records"] == len(recs)
     # other thresholds
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "c.fa", "--variant-table", "c.var", "--variant-strand", "--strand-min-depth", "35",
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "c.fa", "--variant-table", "c.var", "--variant-strand", "--strand-min-depth", "35",
                                                                       "--strand-ratio", "0.9"])
     assert open("c.var").read() == engine.VARIANTS_STRAND_HEADER + sy.text(recs, strand, "ref", ref.encode(), 35, 9, 10)
     assert [ln.split("\t")[-1] for ln in open("c.var").read().splitlines()[1:]] == ["BIAS", "LOW", "LOW"]
 
     # --per-contig: the same records on two references of the same sequence: the same rows per region
     two = sorted([dict(r, tid=t, name="%s_%d" % (r["name"], t)) for t in (0, 1) for r in specs], key=lambda r: (r["tid"], r["pos"]))
-    bamwriter.write_bam("P.bam", rf.arrays(two), refs=[("c0", CL), ("c1", CL)], block=4096)
+    bamwriter.write_bam("P.bam", rsp.arrays(two), refs=[("c0", CL), ("c1", CL)], block=4096)
     with open("p.fa", "w") as fh:
         fh.write(">c0\n%s\n>c1\n%s\n" % (ref, ref))
     with open("p.gff", "w") as fh:
         fh.write("##gff-version 3\n" + syn.gff_text(orfs, seqid="c0")[1] + syn.gff_text(orfs, seqid="c1")[1])
-    rf._run_cli(monkeypatch, ["-i", "P.bam", "-ref", "p.fa", "-gff", "p.gff", "-cov", "10", "-name", "S", "--per-contig", "-o", "p.fa.out", "--variant-table", "p.var",
-                              "--variant-strand", "--stats", "p.json"])
+    cr.run_cli(monkeypatch, ["-i", "P.bam", "-ref", "p.fa", "-gff", "p.gff", "-cov", "10", "-name", "S", "--per-contig", "-o", "p.fa.out", "--variant-table", "p.var",
+                             "--variant-strand", "--stats", "p.json"])
     assert open("p.var").read() == engine.VARIANTS_STRAND_HEADER + want.replace("ref\t", "c0\t") + want.replace("ref\t", "c1\t")
     sp = json.load(open("p.json"))
     assert (sp["variant_strand_bias"], sp["variant_strand_low"], sp["variant_records"]) == (2 * n_bias, 2 * n_low, 2 * len(recs))
 
     # one file through consensus_split_bamfile at world 1
-    parts = td.consensus_split_bamfile("A.bam", CL, rf._gff(orfs), 10, True, "S", 0, 1, return_parts=True,
+    parts = td.consensus_split_bamfile("A.bam", CL, cr.gff_rows(orfs), 10, True, "S", 0, 1, return_parts=True,
                                        variant_strand=dict(ref=ref, min_af="0.03", min_alt_depth=1, min_depth=10))
     vrecs, vstrand = parts[-1]
     assert engine.variants_strand_text(vrecs, vstrand, "ref", ref) == want and len(parts) == 4
@@ -513,7 +414,7 @@ def test_cli_single_sample_per_contig_and_split(tmp_path, monkeypatch):
     # refused: exit 1, nothing written
     man = tmp_path / "m.tsv"
     man.write_text("A.bam\tS0\to0.fa\t-\t-\t-\tt0.var\n")
-    bq._write_override("o.csv.gz", py.counts(rf.arrays(specs), CL)[0])
+    cr.write_override("o.csv.gz", py.counts(rsp.arrays(specs), CL)[0])
     before = sorted(os.listdir(tmp_path))
     for argv in (["--batch", str(man)] + common + ["--variant-strand"],
                  ["-i", "A.bam", "-name", "S"] + common + ["-o", "x.fa", "--variant-table", "x.var", "--variant-strand", "--index-override", "o.csv.gz"]):
@@ -526,16 +427,10 @@ def test_cli_single_sample_per_contig_and_split(tmp_path, monkeypatch):
 def test_cli_one_file_over_two_gpus(tmp_path, monkeypatch):
     """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange): rank 0 lists the records and broadcasts their columns, every
     rank counts its own records, rank 0 writes the sum: the rows of the single-GPU run"""
-    import subprocess
-    import sys
     monkeypatch.chdir(tmp_path)
     ref, orfs, specs = cli_case()
     recs, strand, strand_arr = cli_yardstick(specs, ref)
-    bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=CL, block=4096, split_records=True)
-    common = bq._setup_cli(tmp_path, ref, orfs)
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=rf.ROOT)
-    argv = [sys.executable, "-m", "trueconsense_amd.TrueConsense", "-i", "A.bam", "-name", "S"] + common + ["-o", "a.fa", "--variant-table", "a.var", "--variant-strand",
-                                                                                                       "--strand-min-depth", "12", "--gpus", "2"]
-    r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-1500:]
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=CL, block=4096, split_records=True)
+    common = cr.setup_cli(ref, orfs)
+    cr.run_two_ranks(["-i", "A.bam", "-name", "S"] + common + ["-o", "a.fa", "--variant-table", "a.var", "--variant-strand", "--strand-min-depth", "12", "--gpus", "2"])
     assert open("a.var").read() == engine.VARIANTS_STRAND_HEADER + engine.variants_strand_text(vy.as_array(recs), strand_arr, "ref", ref, min_strand_depth=12)

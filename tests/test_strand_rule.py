@@ -3,49 +3,34 @@ program of their own (tests/strand_main.cpp), built plain and under AddressSanit
 (tests/strand_yardstick.py); the same writer through the ABI; the yardstick's two halves against the yardstick over all records; and
 the command line's argument handling.  The kernel's tests are tests/test_strand_counts.py."""
 import os
-import shutil
 import struct
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from tests import fuzz_masked as ff
+from tests import host_program
 from tests import strand_yardstick as sy
-from tests import test_floor_mask_fuzz as ff
 from tests import variant_yardstick as vy
+from tests.cli_run import base_args as _base
+from tests.cli_run import stub_files
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, engine
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
 TOP = (1 << 31) - 1
-
-
-def _build(out, flags):
-    src = [os.path.join(ROOT, "tests", "strand_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "variants_strand_text.cpp")]
-    tried = []
-    for cxx in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++"), shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + flags + ["-o", out] + src, capture_output=True, text=True)
-        if r.returncode == 0:
-            return out
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    pytest.fail("no compiler built the program:\n" + "\n".join(tried))
 
 
 @pytest.fixture(scope="module")
 def programs(tmp_path_factory):
     d = tmp_path_factory.mktemp("strand_main")
-    return {"plain": _build(str(d / "strand_main"), []), "sanitized": _build(str(d / "strand_main_san"), SAN)}
+    src = ["tests/strand_main.cpp", "trueconsense_amd/csrc/variants_strand_text.cpp"]
+    return {"plain": host_program.build(src, d / "strand_main", sanitize=False), "sanitized": host_program.build(src, d / "strand_main_san")}
 
 
 def _run(prog, mode, inp, out):
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([prog, mode, inp, out], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    r = host_program.run(prog, mode, inp, out)
+    assert r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-4000:])
 
 
 def sweep():
@@ -223,20 +208,10 @@ def test_the_two_strands_add_up_to_the_yardstick_over_all_records(seed):
 
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------
-def _files(tmp_path):
-    p = {}
-    for name in ("x.bam", "r.fa", "f.gff", "o.csv.gz"):
-        (tmp_path / name).write_text("x")
-        p[name] = str(tmp_path / name)
-    return p
-
-
-def _base(f):
-    return ["-i", f["x.bam"], "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30", "-name", "S", "-o", "out.fa"]
 
 
 def test_flags_defaults_and_children(tmp_path):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     a = cli.GetArgs(_base(f) + ["--variant-table", "t.tsv", "--variant-strand"])
     assert (a.variant_strand, a.strand_min_depth, a.strand_ratio) == (True, 10, Fraction(1, 10))
     assert cli.strand_of(a) == dict(min_strand_depth=10, strand_ratio=Fraction(1, 10))
@@ -251,7 +226,7 @@ def test_flags_defaults_and_children(tmp_path):
 
 @pytest.mark.parametrize("extra", (["--strand-min-depth", "0"], ["--strand-min-depth", "x"], ["--strand-ratio", "1.5"], ["--strand-ratio", "1/3000001"], ["--strand-ratio=-1"]))
 def test_bad_strand_thresholds_are_refused(tmp_path, capsys, extra):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     with pytest.raises(SystemExit) as e:
         cli.GetArgs(_base(f) + ["--variant-table", "t.tsv", "--variant-strand"] + extra)
     assert e.value.code == 2 and extra[0].split("=")[0] in capsys.readouterr().err
@@ -259,7 +234,7 @@ def test_bad_strand_thresholds_are_refused(tmp_path, capsys, extra):
 
 def test_refusals_exit_1_with_one_line_and_write_nothing(tmp_path, capsys, monkeypatch):
     monkeypatch.chdir(tmp_path)
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     man = tmp_path / "m.tsv"
     man.write_text("%s\tS0\to0.fa\t-\t-\t-\tt0.tsv\n" % f["x.bam"])
     batch = ["--batch", str(man), "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30"]

@@ -14,13 +14,17 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from tests import amplicon_reads_cases as arc
+from tests import cli_run as cr
+from tests import link_cases as lkc
+from tests import read_specs as rsp
+from tests import schemes as sch
 from tests import sum_ranks
-from tests import test_amplicon_scheme as sch
 from trueconsense_amd import TrueConsense as cli
-from trueconsense_amd import _ffi
+from trueconsense_amd import _ffi, engine
 from trueconsense_amd import distributed as td
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from trueconsense_amd import synthetic as syn
+from trueconsense_amd.io import bamwriter
 
 
 # ---- the agreement and the sum ------------------------------------------------------------------------------------------------------
@@ -41,8 +45,8 @@ def test_agree_and_sum_to_root_over_gloo():
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    env = dict(os.environ, PYTHONPATH=ROOT)
-    procs = [subprocess.Popen([sys.executable, "-m", "tests.sum_ranks", str(r), str(port)], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+    env = dict(os.environ, PYTHONPATH=cr.ROOT)
+    procs = [subprocess.Popen([sys.executable, "-m", "tests.sum_ranks", str(r), str(port)], env=env, cwd=cr.ROOT, stdout=subprocess.PIPE,
                               stderr=subprocess.PIPE, text=True) for r in (0, 1)]
     try:
         outs = [p.communicate(timeout=60) for p in procs]
@@ -71,7 +75,7 @@ ZERO = dict(variant_records=0, variant_strand_bias=0, variant_strand_low=0, vari
 def _parsed(f, which):
     """-> (the namespace of `which` flags, the namespace a --gpus child parses from it); x.bam is no BAM: the reference's name comes from -ref"""
     table = ["--variant-table", "t.tsv", "--min-af", "1/20"] if which != ("reads",) else []
-    a = cli.GetArgs(sch._base(f) + table + (["--amplicon-scheme", f["s.bed"]] if "reads" in which else []) + [x for w in which for x in FLAGS[w]])
+    a = cli.GetArgs(cr.base_args(f) + table + (["--amplicon-scheme", f["s.bed"]] if "reads" in which else []) + [x for w in which for x in FLAGS[w]])
     back = cli.GetArgs(cli._child_argv(a, True))
     a.input = back.input = None
     return a, back
@@ -79,7 +83,7 @@ def _parsed(f, which):
 
 @pytest.mark.parametrize("which", [c for n in (1, 2, 3) for c in itertools.combinations(("reads", "strand", "links"), n)])
 def test_need_names_one_flag(tmp_path, which):
-    a, back = _parsed(sch._files(tmp_path), which)
+    a, back = _parsed(sch.scheme_files(tmp_path), which)
     for ns in (a, back):
         want = cli.StreamCounts(ns)
         assert want and want.need == ("--variant-strand" if "strand" in which else "--variant-links" if "links" in which else "--amplicon-reads")
@@ -88,7 +92,7 @@ def test_need_names_one_flag(tmp_path, which):
 
 
 def test_the_empty_request(tmp_path):
-    a = cli.GetArgs(sch._base(sch._files(tmp_path)))
+    a = cli.GetArgs(cr.base_args(sch.scheme_files(tmp_path)))
     want = cli.StreamCounts(a)
     assert not want and want.need is None and not want.lists_records
     assert want.stats() == want.stats({}) == dict(amplicon_reads_ambiguous=0, amplicon_reads_unassigned=0)
@@ -102,7 +106,7 @@ def test_the_empty_request(tmp_path):
 
 
 def test_split_keywords_and_parts(tmp_path):
-    a, back = _parsed(sch._files(tmp_path), ("reads", "strand", "links"))
+    a, back = _parsed(sch.scheme_files(tmp_path), ("reads", "strand", "links"))
     for ns in (a, back):
         want, areads = cli.StreamCounts(ns), cli.amplicon_reads_of(ns)
         var = dict(cli.variants_of(ns), ref="ACGT")
@@ -115,9 +119,9 @@ def test_split_keywords_and_parts(tmp_path):
     for which, tail, got in ((("strand",), (("recs", "S"),), dict(variant_strand="S")), (("links",), (("recs", "K"),), dict(variant_links="K")),
                              (("reads", "links"), ("R", ("recs", "K")), dict(amplicon_reads="R", variant_links="K")),
                              (("strand", "links"), (("recs", "S"), ("recs", "K")), dict(variant_strand="S", variant_links="K"))):
-        one = _parsed(sch._files(tmp_path), which)[0]
+        one = _parsed(sch.scheme_files(tmp_path), which)[0]
         assert cli.StreamCounts(one).from_parts(parts[:3] + tail) == (got, "recs")
-    only = _parsed(sch._files(tmp_path), ("reads",))[0]
+    only = _parsed(sch.scheme_files(tmp_path), ("reads",))[0]
     assert cli.StreamCounts(only).from_parts(parts[:4]) == (dict(amplicon_reads="R"), None)
     assert cli.StreamCounts(only).split_kwargs("ACGT") == dict(amplicon_reads=cli.amplicon_reads_of(only)[1:], variant_strand=None, variant_links=None)
 
@@ -160,14 +164,14 @@ LINKS_LINES = ("--link-neighbours / --link-min-depth / --link-ratio need --varia
 @pytest.mark.parametrize("flag, dependant, lines", ((["--variant-strand"], ["--strand-ratio", "1/5"], STRAND_LINES),
                                                     (["--variant-links", "l.tsv"], ["--link-min-depth", "5"], LINKS_LINES)))
 def test_refusals_word_for_word(tmp_path, capsys, flag, dependant, lines):
-    f = sch._files(tmp_path)
+    f = sch.scheme_files(tmp_path)
     (tmp_path / "o.csv.gz").write_text("x")
     man = tmp_path / "m.tsv"
     man.write_text("%s\tS0\to0.fa\t-\t-\t-\tt0.tsv\n" % f["x.bam"])
     batch = ["--batch", str(man), "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30"]
     table = ["--variant-table", "t.tsv"]
-    for argv, line in zip((sch._base(f) + table + dependant, batch + flag, sch._base(f) + flag,
-                           sch._base(f) + table + flag + ["--index-override", str(tmp_path / "o.csv.gz")]), lines):
+    for argv, line in zip((cr.base_args(f) + table + dependant, batch + flag, cr.base_args(f) + flag,
+                           cr.base_args(f) + table + flag + ["--index-override", str(tmp_path / "o.csv.gz")]), lines):
         with pytest.raises(SystemExit) as e:
             cli.GetArgs(argv)
         said = capsys.readouterr()
@@ -175,14 +179,14 @@ def test_refusals_word_for_word(tmp_path, capsys, flag, dependant, lines):
 
 
 def test_strand_is_refused_before_links(tmp_path, capsys):
-    f = sch._files(tmp_path)
+    f = sch.scheme_files(tmp_path)
     for order in ((["--link-min-depth", "5"], ["--strand-min-depth", "5"]), (["--strand-min-depth", "5"], ["--link-min-depth", "5"])):
         with pytest.raises(SystemExit) as e:
-            cli.GetArgs(sch._base(f) + ["--variant-table", "t.tsv"] + order[0] + order[1])
+            cli.GetArgs(cr.base_args(f) + ["--variant-table", "t.tsv"] + order[0] + order[1])
         assert e.value.code == 1 and capsys.readouterr().out == STRAND_LINES[0] + "\n"
     # ... and both before the parser's own errors (exit 2): thresholds of a table that is not asked for
     with pytest.raises(SystemExit) as e:
-        cli.GetArgs(sch._base(f) + ["--min-af", "0.1", "--variant-links", "l.tsv"])
+        cli.GetArgs(cr.base_args(f) + ["--min-af", "0.1", "--variant-links", "l.tsv"])
     assert e.value.code == 1 and capsys.readouterr().out == LINKS_LINES[2] + "\n"
 
 
@@ -192,22 +196,16 @@ OWNED = {"strand": ("variant_strand_bias", "variant_strand_low"), "links": tuple
 
 
 def _cli_case(tmp_path, two_contigs=False, split_records=False):
-    """tests/test_link_counts.cli_case (720 reads of 100 bases over 1 200 columns; its two-contig copy) in the working directory, and a
+    """tests/link_cases.cli_case (720 reads of 100 bases over 1 200 columns; its two-contig copy) in the working directory, and a
     scheme of two overlapping amplicons on every reference -> the command line's common arguments"""
-    from tests import test_amplicon_reads as ar
-    from tests import test_base_quality as bq
-    from tests import test_link_counts as lc
-    from tests import test_read_filter as rf
-    from trueconsense_amd import synthetic as syn
-    from trueconsense_amd.io import bamwriter
-    ref, orfs, specs = lc.cli_case()
-    amps = ar.tiled(2, 30, 500, 650)
-    ar.at.write_scheme("s.bed", [r for chrom in ("ref", "c0", "c1") for r in ar.scheme_rows_for(chrom, amps)])
+    ref, orfs, specs = lkc.cli_case()
+    amps = arc.tiled(2, 30, 500, 650)
+    sch.write_scheme("s.bed", [r for chrom in ("ref", "c0", "c1") for r in arc.scheme_rows_for(chrom, amps)])
     if not two_contigs:
-        bamwriter.write_bam("A.bam", rf.arrays(specs), ref_len=lc.CL, block=4096, split_records=split_records)
-        return ["-i", "A.bam", "-name", "S"] + bq._setup_cli(tmp_path, ref, orfs)
+        bamwriter.write_bam("A.bam", rsp.arrays(specs), ref_len=lkc.CL, block=4096, split_records=split_records)
+        return ["-i", "A.bam", "-name", "S"] + cr.setup_cli(ref, orfs)
     two = sorted([dict(r, tid=t, name="%s_%d" % (r["name"], t)) for t in (0, 1) for r in specs], key=lambda r: (r["tid"], r["pos"]))
-    bamwriter.write_bam("P.bam", rf.arrays(two), refs=[("c0", lc.CL), ("c1", lc.CL)], block=4096)
+    bamwriter.write_bam("P.bam", rsp.arrays(two), refs=[("c0", lkc.CL), ("c1", lkc.CL)], block=4096)
     with open("p.fa", "w") as fh:
         fh.write(">c0\n%s\n>c1\n%s\n" % (ref, ref))
     with open("p.gff", "w") as fh:
@@ -231,7 +229,6 @@ def _asked(tag, which):
 
 def _same_files_as_alone():
     """all.* against strand.var, links.lnk, reads.reads (and the plain table links.var against the strand table's first columns)"""
-    from trueconsense_amd import engine
     read = lambda p: open(p).read()
     assert read("all.var") == read("strand.var") and read("all.var").startswith(engine.VARIANTS_STRAND_HEADER) and read("all.var").count("\n") > 8
     assert read("all.lnk") == read("links.lnk") and read("all.lnk").startswith(engine.VARIANTS_LINKS_HEADER) and read("all.lnk").count("\n") > 8
@@ -245,11 +242,10 @@ def _same_files_as_alone():
 @pytest.mark.parametrize("two_contigs", (False, True))
 def test_three_flags_at_once_in_process(tmp_path, monkeypatch, two_contigs):
     """the single-sample runner, and --per-contig on the two-contig copy"""
-    from tests import test_read_filter as rf
     monkeypatch.chdir(tmp_path)
     common = _cli_case(tmp_path, two_contigs)
     for tag, which in (("all", ("strand", "links", "reads")), ("strand", ("strand",)), ("links", ("links",)), ("reads", ("reads",))):
-        rf._run_cli(monkeypatch, common + _asked(tag, which) + ["--stats", tag + ".json"])
+        cr.run_cli(monkeypatch, common + _asked(tag, which) + ["--stats", tag + ".json"])
     _same_files_as_alone()
     stats = {tag: json.load(open(tag + ".json")) for tag in ("all", "strand", "links", "reads")}
     assert open("all.reads").read().count("\n") == 1 + (4 if two_contigs else 2) + 2       # the header, every contig's two amplicons, *ambiguous and *unassigned
@@ -267,7 +263,7 @@ def test_three_flags_at_once_over_two_gpus(tmp_path, monkeypatch):
     """--gpus 2 (two ranks rehearsed on this one GPU, gloo for the exchange); the four runs side by side: eight ranks on the card"""
     monkeypatch.chdir(tmp_path)
     common = _cli_case(tmp_path, split_records=True)
-    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=ROOT)
+    env = dict(os.environ, TCMI_SPLIT_ONE_GPU="1", TCMI_SPLIT_BACKEND="gloo", PYTHONPATH=cr.ROOT)
     runs = (("all", ("strand", "links", "reads")), ("strand", ("strand",)), ("links", ("links",)), ("reads", ("reads",)))
     procs = [subprocess.Popen([sys.executable, "-m", "trueconsense_amd.TrueConsense"] + common + _asked(tag, which) + ["--gpus", "2", "-t", "2"], env=env,
                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True) for tag, which in runs]

@@ -17,38 +17,37 @@ cap is its 64 workgroups of PB = 256 lanes (pinned in tests/test_repeat_bam.py).
      packer, which the route assertion admits for that one reason only).
 The files are written once per module and every read set answers all of its queries from one upload; the tests of a case then look at
 different parts of what was measured."""
-import contextlib
 import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
+from tests import amplicon_reads_cases as arc
 from tests import amplicon_reads_yardstick as ry
+from tests import device_file as dvf
 from tests import fixed_reads as fx
+from tests import fuzz_masked as fm
+from tests import link_cases as lkc
 from tests import links_yardstick as ly
 from tests import primer_yardstick as py
+from tests import read_specs as rsp
 from tests import repeat_bam as rb
-from tests import test_amplicon_reads as ar
-from tests import test_floor_mask_fuzz as ff
-from tests import test_link_counts as ln
-from tests import test_primer_mask as pm
-from tests import test_read_filter as rf
-from tests import test_repeat_bam as tr
-from tests import test_strand_counts as sc
+from tests import schemes as sch
+from tests import strand_cases as stc
 from trueconsense_amd import _ffi, engine
 
 pytestmark = pytest.mark.gpu
-L = ff.L
-SC_BLOCK, SC_WG_PER_CU = tr.stream_count_caps()
-MASK_LONG_CAP = tr.MASK_LONG_GRID * tr.MASK_LONG_BLOCK
-KEYS = {"seed1": (1, None, False), "seed2": (2, None, False), "deep": (ff.DEEP_SEED, ff.DEEP_WINDOW, False), "seed1_brim": (1, None, True)}
-A_CASES = [(key, mode) for key in ("seed1", "seed2", "deep") for mode in sorted(ff.MODES)] + [("seed1_brim", "all")]
+L = fm.L
+SC_BLOCK, SC_WG_PER_CU = rb.stream_count_caps()
+MASK_LONG_CAP = rb.MASK_LONG_GRID * rb.MASK_LONG_BLOCK
+KEYS = {"seed1": (1, None, False), "seed2": (2, None, False), "deep": (fm.DEEP_SEED, fm.DEEP_WINDOW, False), "seed1_brim": (1, None, True)}
+A_CASES = [(key, mode) for key in ("seed1", "seed2", "deep") for mode in sorted(fm.MODES)] + [("seed1_brim", "all")]
 LINK_KS = (1, 7)
 AMP_SLACKS = (0, 5)
-FULL = ar.tiled(7, primer=190)                                                  # primer zones 20 columns apart: reads do run from one into the other
+FULL = arc.tiled(7, primer=190)                                                  # primer zones 20 columns apart: reads do run from one into the other
 # mode -> (floor, read filter, primer table, slack)
-C_MODES = {"plain": (0, ff.NONE, (), 0), "floor": (13, ff.NONE, (), 0), "floor_mapq": (13, fx.MQ, (), 0), "all": (13, fx.MQ, tuple(pm.SCHEME), 3)}
+C_MODES = {"plain": (0, fm.NONE, (), 0), "floor": (13, fm.NONE, (), 0), "floor_mapq": (13, fx.MQ, (), 0), "all": (13, fx.MQ, tuple(sch.PRIMER_SCHEME), 3)}
 C_SIZES = ("cap", "cap_plus_1", "three_trips")
 
 
@@ -78,28 +77,12 @@ def once(store, key, make):
     return store[key]
 
 
-@contextlib.contextmanager
-def uploaded(ctx, path, how, table=(), q=0, f=ff.NONE, slack=0, events_may_overflow=False):
-    """test_strand_counts.uploaded with the route asserted by name: the packer `how` built the read set (rs.route).  The one-sync packer
-    sizes its event array for max(2^20, records / 2) events and hands a file beyond that to the several-kernel path (PKF_EVENT_OVF;
-    tests/test_pack_capacities.py): events_may_overflow admits that one decline and no other, and rs.route says what happened."""
-    t0, d0 = ctx.stat("one_sync_taken"), ctx.stat("one_sync_declined")
-    with sc.uploaded(ctx, path, table, q, f, slack, int(how == "one_sync")) as rs:
-        taken, declined = ctx.stat("one_sync_taken") - t0, ctx.stat("one_sync_declined") - d0
-        if how == "one_sync" and events_may_overflow and not taken:
-            assert declined == 1 and ctx.stat("one_sync_last_decline_flags") == tr.PKF_EVENT_OVF, (declined, ctx.stat("one_sync_last_decline_flags"))
-        else:
-            assert (taken, declined) == (int(how == "one_sync"), 0), (how, taken, declined, ctx.stat("one_sync_last_decline_flags"))
-        rs.route = "one_sync" if taken else "several_kernels"
-        yield rs
-
-
 def figures(rs):
     return dict(n_reads=rs.n_reads, n_piled=rs.n_piled, filtered=rs.filtered, masked=rs.primer_masked_reads, max_end=rs.max_end)
 
 
 def counts_under_every_mode(r):
-    return ff._piles_up(r) and rf.passes(r, ff.F)
+    return fm._piles_up(r) and rsp.passes(r, fm.F)
 
 
 def tail_from(cap, n, r):
@@ -123,40 +106,40 @@ def times_for(cap, specs):
 def plan_a(seed, window, mode):
     """what the small file gives on the yardsticks and which queries the repeated file is asked, every case non-vacuous as
     test_strand_counts, test_link_counts and test_amplicon_reads ask it of the yardstick — before any device runs"""
-    tabled, slack, q, f = ff.MODES[mode]
-    every = ff.fuzz(seed, None, window)
-    specs, _ = ff.passing(seed, None, window, f)
-    want = ff.yardstick(seed, None, window, f, tabled, q, slack)
-    fwd, rev, n_pos = sc.halves(seed, mode, window)
+    tabled, slack, q, f = fm.MODES[mode]
+    every = fm.fuzz(seed, None, window)
+    specs, _ = fm.passing(seed, None, window, f)
+    want = fm.yardstick(seed, None, window, f, tabled, q, slack)
+    fwd, rev, n_pos = stc.halves(seed, mode, window)
     assert n_pos == len(want[0]) and np.array_equal(fwd + rev, want[0])
     if window is None:
-        strand_sparse, link_sparse = sc.sparse_columns(seed, n_pos), ln.sparse_columns(seed, n_pos, 5, 3)
+        strand_sparse, link_sparse = stc.sparse_columns(seed, n_pos), lkc.sparse_columns(seed, n_pos, 5, 3)
     else:                                                                       # (the columns the two modules query on the deep file)
-        strand_sparse = sorted(set(range(window[0] - 20, window[1] + 60, 3)) | set(sc.sparse_columns(seed, n_pos, 20)))[:sc.LDS]
+        strand_sparse = sorted(set(range(window[0] - 20, window[1] + 60, 3)) | set(stc.sparse_columns(seed, n_pos, 20)))[:stc.LDS]
         link_sparse = list(range(window[0] - 10, window[1] + 50, 5))[:11]
     dense = list(range(n_pos))
-    assert len(strand_sparse) <= sc.LDS < len(dense)
+    assert len(strand_sparse) <= stc.LDS < len(dense)
     for cols in (strand_sparse, dense):
-        sc.not_vacuous(specs, fwd[cols], rev[cols], cols, (seed, mode))
-    cls, n_pos2, whole = ln.classes_of(seed, mode, window)
+        stc.not_vacuous(specs, fwd[cols], rev[cols], cols, (seed, mode))
+    cls, n_pos2, whole = lkc.classes_of(seed, mode, window)
     assert n_pos2 == n_pos and np.array_equal(whole, want[0])
-    link_cases = [(cols, k, ly.joint(cls, cols, k)) for cols in (link_sparse, ln.window_columns(whole)) for k in LINK_KS]
+    link_cases = [(cols, k, ly.joint(cls, cols, k)) for cols in (link_sparse, lkc.window_columns(whole)) for k in LINK_KS]
     for cols, k, j in link_cases:
-        ln.not_vacuous(j, (seed, mode, len(cols), k))
-    assert ln.long_read_over(specs, link_cases[-1][0]) and ln.long_read_over(specs, link_sparse, 2), (seed, mode)
-    assert [len(cols) * k <= ln.LDS for cols, k, _ in link_cases] == [True, True, False, False]
-    rd = rf.arrays(every)
+        lkc.not_vacuous(j, (seed, mode, len(cols), k))
+    assert lkc.long_read_over(specs, link_cases[-1][0]) and lkc.long_read_over(specs, link_sparse, 2), (seed, mode)
+    assert [len(cols) * k <= lkc.LDS for cols, k, _ in link_cases] == [True, True, False, False]
+    rd = rsp.arrays(every)
     columns = ry.kept_columns(rd, None, f, rd["mapq"])
-    assert len(columns) == sum(ff._piles_up(r) for r in specs)
+    assert len(columns) == sum(fm._piles_up(r) for r in specs)
     amp_cases = []
-    for amps in (ar.tiled(7), ar.padded(ar.tiled(7), ar.LDS + 1), FULL):
+    for amps in (arc.tiled(7), arc.padded(arc.tiled(7), arc.LDS + 1), FULL):
         for s in AMP_SLACKS:
             w = ry.counts(columns, amps, s)
             assert w[:, 0].sum() == len(columns) and (w[:, 1] <= w[:, 0]).all() and w[len(amps):, 0].all(), (seed, mode, w[:9].tolist())
             assert w[:7, 0].all() if window is None else (w[:7, 0] > 0).sum() >= 3, (seed, mode, w[:9].tolist())      # (the deep file's reads start in 50 columns)
             assert amps is not FULL or window is not None or (w[:7, 1] > 0).sum() >= 5, (seed, mode, "full-length reads", w[:7].tolist())
             amp_cases.append((amps, s, w))
-    assert [len(a) <= ar.LDS for a, _, _ in amp_cases] == [True, True, False, False, True, True]
+    assert [len(a) <= arc.LDS for a, _, _ in amp_cases] == [True, True, False, False, True, True]
     return dict(specs=specs, want=want, n_pos=n_pos, fwd=fwd, rev=rev, strand={"LDS": strand_sparse, "memory": dense}, links=link_cases, amps=amp_cases,
                 n_small=len(every), n_piled=len(columns), deepest=int(want[0][:, 0].max()))
 
@@ -164,15 +147,15 @@ def plan_a(seed, window, mode):
 def tail_links_of(cap, r, seed, window, mode, n_pos):
     """one more link query, on the records of the second trip: up to eleven columns of the first record there that counts under every
     mode and has tokens on them under this one (a primer can mask a record whole) -> [(columns, k, the small file's joint counts)]"""
-    every = ff.fuzz(seed, None, window)
-    cls = ln.classes_of(seed, mode, window)[0]
+    every = fm.fuzz(seed, None, window)
+    cls = lkc.classes_of(seed, mode, window)[0]
     for x in every[tail_from(cap, len(every), r):]:
         if not counts_under_every_mode(x):
             continue
-        cols = sorted(x["pos"] + d for d in (0, 1, 2, 3, 5, 8, 13, 21, 34, 55, 89) if d < ff._span(x) and x["pos"] + d < n_pos)
+        cols = sorted(x["pos"] + d for d in (0, 1, 2, 3, 5, 8, 13, 21, 34, 55, 89) if d < fm._span(x) and x["pos"] + d < n_pos)
         cases = [(cols, k, ly.joint(cls, cols, k)) for k in LINK_KS]
         if len(cols) >= 2 and all(j.any() for _, _, j in cases):
-            assert len(cols) * max(LINK_KS) <= ln.LDS
+            assert len(cols) * max(LINK_KS) <= lkc.LDS
             return cases
     raise AssertionError("no record of the second trip has tokens to count: %r" % ((seed, mode, r),))
 
@@ -183,8 +166,8 @@ def file_a(store, cap, key):
         seed, window, brim = KEYS[key]
         d = store["dir"] / key
         d.mkdir()
-        specs = ff.fuzz(seed, None, window)
-        src = ff.write(d, specs)
+        specs = fm.fuzz(seed, None, window)
+        src = fm.write(d, specs)
         r = times_for(cap, specs)
         dst = str(d / "R.bam")
         n = rb.repeat_records(src, dst, r, brim=brim)
@@ -197,8 +180,8 @@ def measured_a(ctx, store, cap, key, mode, how):
     def make():
         seed, window, _ = KEYS[key]
         p = plan_a(seed, window, mode)
-        tabled, slack, q, f = ff.MODES[mode]
-        table = ff.table_of(seed) if tabled else ()
+        tabled, slack, q, f = fm.MODES[mode]
+        table = fm.table_of(seed) if tabled else ()
         src, dst, r, n, n_blocks = file_a(store, cap, key)
         tail_links = tail_links_of(cap, r, seed, window, mode, p["n_pos"])
         # two trips of each_record, the second ragged; the single-workgroup scans over the blocks go past one chunk of 1 024
@@ -207,17 +190,17 @@ def measured_a(ctx, store, cap, key, mode, how):
         assert n_blocks > 1024, n_blocks
         if window is not None:                                                  # the deep file: a column of the matrix passes 16 bits
             assert p["deepest"] * r > 65535, (p["deepest"], r)
-        with uploaded(ctx, src, how, table, q, f, slack) as rs:
+        with dvf.uploaded(ctx, src, table, q, f, slack, how=how) as rs:
             small = figures(rs)
         assert small["n_reads"] == p["n_small"] and small["n_piled"] == p["n_piled"] and small["masked"] == p["want"][1]
         out = dict(r=r, small=small, tail_links=tail_links)
-        with uploaded(ctx, dst, how, table, q, f, slack, events_may_overflow=True) as rs:
+        with dvf.uploaded(ctx, dst, table, q, f, slack, how=how, events_may_overflow=True) as rs:
             out["big"], out["route"] = figures(rs), rs.route
             assert rs.n_reads == n > cap and rs.n_reads % 64 != 0 and rs.n_reads - cap < cap
             out["matrix"] = ctx.step(rs, p["n_pos"], 0, True)[3]
-            out["strand"] = {route: sc.device_counts(ctx, rs, cols) for route, cols in p["strand"].items()}
-            out["links"] = [ln.device_links(ctx, rs, cols, k) for cols, k, _ in p["links"] + tail_links]
-            out["amps"] = [ar.device_counts(ctx, rs, amps, s) for amps, s, _ in p["amps"]]
+            out["strand"] = {route: stc.device_counts(ctx, rs, cols) for route, cols in p["strand"].items()}
+            out["links"] = [lkc.device_links(ctx, rs, cols, k) for cols, k, _ in p["links"] + tail_links]
+            out["amps"] = [arc.device_counts(ctx, rs, amps, s) for amps, s, _ in p["amps"]]
         return out
     return once(store, ("A", key, mode, how), make)
 
@@ -228,45 +211,45 @@ def case_a(ctx, store, cap, key, mode, how):
     return plan_a(seed, window, mode), m, (key, mode, how, "built by " + m["route"])
 
 
-@pytest.mark.parametrize("how", pm.PACKERS)
+@pytest.mark.parametrize("how", dvf.PACKERS)
 @pytest.mark.parametrize("key,mode", A_CASES)
 def test_a_the_matrix_and_the_read_sets_figures_are_r_times_the_small_files(ctx, store, cap, key, mode, how):
     """pk_place_bq / pk_planes_bq / tally_planes_drop_kernel and tally_stream_kernel's by_token branch behind more than 1 024 blocks"""
     p, m, label = case_a(ctx, store, cap, key, mode, how)
     r, small, big = m["r"], m["small"], m["big"]
-    msg = ff.differ(m["matrix"], r * p["want"][0], p["specs"], label)
+    msg = fm.differ(m["matrix"], r * p["want"][0], p["specs"], label)
     assert not msg, msg
     assert (big["n_piled"], big["filtered"], big["masked"]) == (r * small["n_piled"], r * small["filtered"], r * small["masked"]), (label, big, small)
     assert big["max_end"] == small["max_end"] and big["masked"] == r * p["want"][1]
-    if ff.MODES[mode][3] != ff.NONE:
+    if fm.MODES[mode][3] != fm.NONE:
         assert small["filtered"] > 0
-    if ff.MODES[mode][0]:
+    if fm.MODES[mode][0]:
         assert small["masked"] > 0
 
 
-@pytest.mark.parametrize("how", pm.PACKERS)
+@pytest.mark.parametrize("how", dvf.PACKERS)
 @pytest.mark.parametrize("key,mode", A_CASES)
 def test_a_strand_counts(ctx, store, cap, key, mode, how):
     p, m, label = case_a(ctx, store, cap, key, mode, how)
     for route, cols in p["strand"].items():
         got = m["strand"][route]
-        msg = sc.differ(got, (m["r"] * p["fwd"][cols], m["r"] * p["rev"][cols]), cols, label + (route,))
+        msg = stc.differ(got, (m["r"] * p["fwd"][cols], m["r"] * p["rev"][cols]), cols, label + (route,))
         assert not msg, msg
         assert np.array_equal(got[0] + got[1], m["matrix"][cols]), label + (route, "the invariant")
 
 
-@pytest.mark.parametrize("how", pm.PACKERS)
+@pytest.mark.parametrize("how", dvf.PACKERS)
 @pytest.mark.parametrize("key,mode", A_CASES)
 def test_a_link_counts(ctx, store, cap, key, mode, how):
     p, m, label = case_a(ctx, store, cap, key, mode, how)
     assert len(m["links"]) == len(p["links"]) + len(m["tail_links"])
     for (cols, k, want), got in zip(p["links"] + m["tail_links"], m["links"]):
-        msg = ln.differ(got, m["r"] * want, label + (len(cols), k))
+        msg = lkc.differ(got, m["r"] * want, label + (len(cols), k))
         assert not msg, msg
         assert not ly.invariant(got, k, m["matrix"]), label + (len(cols), k, ly.invariant(got, k, m["matrix"]))
 
 
-@pytest.mark.parametrize("how", pm.PACKERS)
+@pytest.mark.parametrize("how", dvf.PACKERS)
 @pytest.mark.parametrize("key,mode", A_CASES)
 def test_a_amplicon_reads(ctx, store, cap, key, mode, how):
     p, m, label = case_a(ctx, store, cap, key, mode, how)
@@ -279,13 +262,13 @@ def test_a_amplicon_reads(ctx, store, cap, key, mode, how):
 @functools.lru_cache(maxsize=None)
 def plan_b(slack):
     seed = 1
-    every = ff.fuzz(seed)
-    index = [i for i, r in enumerate(every) if ff._piles_up(r) and ff._span(r) > ff.LONG]
+    every = fm.fuzz(seed)
+    index = [i for i, r in enumerate(every) if fm._piles_up(r) and fm._span(r) > fm.LONG]
     specs = [every[i] for i in index]
-    table = ff.table_of(seed)
-    want = py.counts(rf.arrays(specs), L, table, 0, slack)
-    n_masked = ff.profile(specs, table, slack)["long_masked"]
-    assert len(specs) == ff.n_long(every) >= 15 and n_masked == want[1] >= 5, (len(specs), n_masked, want[1])
+    table = fm.table_of(seed)
+    want = py.counts(rsp.arrays(specs), L, table, 0, slack)
+    n_masked = fm.profile(specs, table, slack)["long_masked"]
+    assert len(specs) == fm.n_long(every) >= 15 and n_masked == want[1] >= 5, (len(specs), n_masked, want[1])
     return dict(index=index, specs=specs, table=table, want=want, n_masked=n_masked)
 
 
@@ -294,7 +277,7 @@ def file_b(store, masked_only=False):
     def make():
         p = plan_b(0)
         index = [i for i, x in zip(p["index"], p["specs"]) if not masked_only or long_is_masked(x, p["table"], 0)]
-        src = ff.write(store["dir"], ff.fuzz(1))
+        src = fm.write(store["dir"], fm.fuzz(1))
         r = MASK_LONG_CAP // len(index) + 2
         dst = str(store["dir"] / ("B%d.bam" % masked_only))
         return dst, r, rb.repeat_records(src, dst, r, keep=index), index
@@ -302,18 +285,18 @@ def file_b(store, masked_only=False):
 
 
 def long_is_masked(x, table, slack):
-    return ff.profile([x], table, slack)["long_masked"] == 1
+    return fm.profile([x], table, slack)["long_masked"] == 1
 
 
-@pytest.mark.parametrize("how", pm.PACKERS)
+@pytest.mark.parametrize("how", dvf.PACKERS)
 @pytest.mark.parametrize("slack", (0, 3))
 def test_b_pk_mask_long_past_one_trip_of_its_grid(ctx, store, slack, how):
     """more long reads than pk_mask_long's 64 x 256 lanes under the seed's table: the masked reads it counts for tcmi_readset_primers
     are R' times those of the 37 records, every one of them is left to tally_stream_kernel, and the matrix is R' times the yardstick"""
     p = plan_b(slack)
     path, r, n, _ = file_b(store)
-    assert n == r * len(p["specs"]) > MASK_LONG_CAP and n - MASK_LONG_CAP < tr.MASK_LONG_BLOCK and (n - MASK_LONG_CAP) % 64 != 0, (n, r)
-    with uploaded(ctx, path, how, p["table"], 0, ff.NONE, slack) as rs:
+    assert n == r * len(p["specs"]) > MASK_LONG_CAP and n - MASK_LONG_CAP < rb.MASK_LONG_BLOCK and (n - MASK_LONG_CAP) % 64 != 0, (n, r)
+    with dvf.uploaded(ctx, path, p["table"], 0, fm.NONE, slack, how=how) as rs:
         aligned, chunks, general = (C.c_int64(0) for _ in range(3))
         _ffi.check(_ffi.lib().tcmi_readset_sets(rs.handle, C.byref(aligned), C.byref(chunks), C.byref(general)))
         assert rs.n_reads == rs.n_piled == n and (rs.n_piled - aligned.value, general.value) == (n, 0), (how, aligned.value, general.value)
@@ -325,11 +308,11 @@ def test_b_pk_mask_long_past_one_trip_of_its_grid(ctx, store, slack, how):
             ctx.profile(False)
         assert n_stream == 1, (how, n_stream)
         assert rs.primer_masked_reads == r * p["n_masked"], (how, slack, rs.primer_masked_reads, r, p["n_masked"])
-        msg = ff.differ(got, r * p["want"][0], p["specs"], ("long reads", slack, how))
+        msg = fm.differ(got, r * p["want"][0], p["specs"], ("long reads", slack, how))
         assert not msg, msg
 
 
-@pytest.mark.parametrize("how", pm.PACKERS)
+@pytest.mark.parametrize("how", dvf.PACKERS)
 @pytest.mark.parametrize("slack", (0, 3))
 def test_b_every_long_read_masked_whatever_order_the_packer_lists_them_in(ctx, store, slack, how):
     """the packers list the long reads in the order their lanes get to it, so which of file B's reads a second trip of pk_mask_long
@@ -339,10 +322,10 @@ def test_b_every_long_read_masked_whatever_order_the_packer_lists_them_in(ctx, s
     specs = [x for i, x in zip(p["index"], p["specs"]) if i in index]
     assert 5 <= len(specs) == p["n_masked"] or slack, (len(specs), p["n_masked"])
     assert all(long_is_masked(x, p["table"], slack) for x in specs) and n == r * len(specs) > MASK_LONG_CAP
-    with uploaded(ctx, path, how, p["table"], 0, ff.NONE, slack) as rs:
+    with dvf.uploaded(ctx, path, p["table"], 0, fm.NONE, slack, how=how) as rs:
         assert rs.n_reads == rs.n_piled == rs.primer_masked_reads == n, (how, slack, rs.n_piled, rs.primer_masked_reads, n)
-        want = py.counts(rf.arrays(specs), L, p["table"], 0, slack)[0]
-        msg = ff.differ(ctx.step(rs, len(want), 0, True)[3], r * want, specs, ("masked long reads", slack, how))
+        want = py.counts(rsp.arrays(specs), L, p["table"], 0, slack)[0]
+        msg = fm.differ(ctx.step(rs, len(want), 0, True)[3], r * want, specs, ("masked long reads", slack, how))
         assert not msg, msg
 
 
@@ -370,25 +353,25 @@ def measured_c(ctx, store, cap, which, mode):
         rd, path = file_c(store, cap, which)
         n = len(rd["pos"])
         assert which != "three_trips" or rb.n_blocks(path) > 1024               # (the one-sync packer's scans over the blocks go past one chunk too)
-        assert n == size_c(cap, which) and len(C_STRAND) <= sc.LDS < fx.L and len(C_LINKS) * max(LINK_KS) <= ln.LDS < len(C_WINDOW)
+        assert n == size_c(cap, which) and len(C_STRAND) <= stc.LDS < fx.L and len(C_LINKS) * max(LINK_KS) <= lkc.LDS < len(C_WINDOW)
         want = dict(matrix=fx.matrix(rd, fx.L, q, f, table, slack), strand={"LDS": C_STRAND, "memory": list(range(fx.L))},
                     links=[(cols, k, fx.links(rd, cols, k, q, f, table, slack)) for cols in (C_LINKS, C_WINDOW) for k in LINK_KS],
                     masked=fx.masked_reads(rd, f, table, slack),
-                    amps=[(amps, s, fx.amplicon_reads(rd, amps, s, f)) for amps in (fx.SCHEME, ar.padded(fx.SCHEME, ar.LDS + 1)) for s in AMP_SLACKS],
+                    amps=[(amps, s, fx.amplicon_reads(rd, amps, s, f)) for amps in (fx.SCHEME, arc.padded(fx.SCHEME, arc.LDS + 1)) for s in AMP_SLACKS],
                     kept=int(fx.kept(rd, f).sum()))
         for _, k, j in want["links"]:
-            ln.not_vacuous(j, (which, mode, k))
+            lkc.not_vacuous(j, (which, mode, k))
         for amps, s, w in want["amps"]:
             assert w[:8, 0].all() and w[7, 1] > 0 and w[len(amps):, 0].all() and w[:, 0].sum() == want["kept"]
-        assert want["matrix"][:, 1:5].sum(0).all() and (f == ff.NONE) == (want["kept"] == n) and (want["masked"] > 1000) == bool(table)
+        assert want["matrix"][:, 1:5].sum(0).all() and (f == fm.NONE) == (want["kept"] == n) and (want["masked"] > 1000) == bool(table)
         got = {}
-        with uploaded(ctx, path, "one_sync", table, q, f, slack) as rs:
+        with dvf.uploaded(ctx, path, table, q, f, slack, how="one_sync") as rs:
             got["figures"] = figures(rs)
             assert rs.n_reads == n
             got["matrix"] = ctx.step(rs, fx.L, 0, True)[3]
-            got["strand"] = {route: sc.device_counts(ctx, rs, cols) for route, cols in want["strand"].items()}
-            got["links"] = [ln.device_links(ctx, rs, cols, k) for cols, k, _ in want["links"]]
-            got["amps"] = [ar.device_counts(ctx, rs, amps, s) for amps, s, _ in want["amps"]]
+            got["strand"] = {route: stc.device_counts(ctx, rs, cols) for route, cols in want["strand"].items()}
+            got["links"] = [lkc.device_links(ctx, rs, cols, k) for cols, k, _ in want["links"]]
+            got["amps"] = [arc.device_counts(ctx, rs, amps, s) for amps, s, _ in want["amps"]]
         return rd, want, got
     return once(store, ("C", which, mode), make)
 
@@ -402,7 +385,7 @@ def test_c_the_matrix_and_the_strand_counts_at_the_bounds_of_each_record(ctx, st
     assert not bad, (which, mode, [(c, got["matrix"][c].tolist(), want["matrix"][c].tolist()) for c in bad])
     assert (got["figures"]["n_piled"], got["figures"]["filtered"], got["figures"]["masked"]) == (want["kept"], len(rd["pos"]) - want["kept"], want["masked"])
     for route, cols in want["strand"].items():
-        msg = sc.differ(got["strand"][route], fx.strand(rd, cols, q, f, table, slack), cols, (which, mode, route))
+        msg = stc.differ(got["strand"][route], fx.strand(rd, cols, q, f, table, slack), cols, (which, mode, route))
         assert not msg, msg
         assert np.array_equal(got["strand"][route][0] + got["strand"][route][1], got["matrix"][cols]), (which, mode, route, "the invariant")
 
@@ -412,7 +395,7 @@ def test_c_the_matrix_and_the_strand_counts_at_the_bounds_of_each_record(ctx, st
 def test_c_link_counts_at_the_bounds_of_each_record(ctx, store, cap, which, mode):
     _, want, got = measured_c(ctx, store, cap, which, mode)
     for (cols, k, j), g in zip(want["links"], got["links"]):
-        msg = ln.differ(g, j, (which, mode, len(cols), k))
+        msg = lkc.differ(g, j, (which, mode, len(cols), k))
         assert not msg, msg
         assert not ly.invariant(g, k, got["matrix"]), (which, mode, len(cols), k, ly.invariant(g, k, got["matrix"]))
 

@@ -1,20 +1,19 @@
 """The variant table without a GPU: the yardstick (tests/variant_yardstick.py) pinned against a hand-written table, the product's rule
 (csrc/variants_rule.h) and row writer (csrc/variants_text.cpp) as a program of their own under AddressSanitizer + UBSan against the
 yardstick, and the command line's argument handling.  The kernels' tests are tests/test_variant_table.py."""
-import os
-import shutil
 import struct
-import subprocess
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
+from tests import host_program
 from tests import variant_yardstick as vy
+from tests.cli_run import base_args as _base
+from tests.cli_run import stub_files
 from trueconsense_amd import TrueConsense as cli
 from trueconsense_amd import _ffi, engine
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # min_af = 1/4, min_alt_depth = 2, min_depth = 10, n_ref = 12 over 13 positions        (coverage, A, T, C, G, X, I)
 HAND_REF = b"AAcNGTTGARtA"
@@ -69,37 +68,20 @@ def random_matrix(n=2000, seed=11):
     return c.astype(np.int32), ref.tobytes()
 
 
-def build_program(tmp_path):
-    src = [os.path.join(ROOT, "tests", "variants_main.cpp"), os.path.join(ROOT, "trueconsense_amd", "csrc", "variants_text.cpp")]
-    out = str(tmp_path / "variants_main")
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g"]
-    tried = []
-    for cxx in (os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bin", "clang++"), shutil.which("g++"), shutil.which("clang++")):
-        if not cxx or not os.path.exists(cxx):
-            continue
-        r = subprocess.run([cxx, "-std=c++17", "-O1", "-Wall", "-Wextra"] + san + ["-o", out] + src, capture_output=True, text=True)
-        if r.returncode == 0:
-            return out
-        tried.append("%s:\n%s" % (cxx, r.stderr[-2000:]))
-    pytest.fail("no compiler built the program:\n" + "\n".join(tried))
-
-
 def run_program(prog, tmp_path, tag, counts, ref, rule, region, pos_offset=0):
     inp, rec, txt = (str(tmp_path / (tag + ext)) for ext in (".in", ".rec", ".txt"))
     with open(inp, "wb") as fh:
         fh.write(struct.pack("<8q", len(counts), len(ref), *rule, pos_offset, len(region.encode())))
         fh.write(region.encode() + ref + np.ascontiguousarray(counts, np.int32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([prog, inp, rec, txt], capture_output=True, text=True, env=env)
-    assert r.returncode == 0 and r.stdout.startswith("ok "), (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, r.stderr[-4000:]
+    r = host_program.run(prog, inp, rec, txt)
+    assert r.stdout.startswith("ok "), (r.stdout[-2000:], r.stderr[-4000:])
     return np.fromfile(rec, vy.DTYPE), open(txt).read()
 
 
 def test_rule_and_text_program_under_sanitizers(tmp_path):
     """tests/variants_main.cpp + csrc/variants_rule.h + csrc/variants_text.cpp and nothing else, with AddressSanitizer + UBSan, run as
     a program: its records equal the yardstick's, its text a Python formatting of the same records"""
-    prog = build_program(tmp_path)
+    prog = host_program.build(["tests/variants_main.cpp", "trueconsense_amd/csrc/variants_text.cpp"], tmp_path / "variants_main")
     got, text = run_program(prog, tmp_path, "hand", HAND_COUNTS, HAND_REF, HAND_RULE, "ctg")
     assert got.tolist() == HAND_WANT and text == HAND_TEXT
     counts, ref = random_matrix()
@@ -133,20 +115,10 @@ def test_text_writer_through_the_abi():
 
 
 # ------------------------------------------------------------------------------------------------------------- command line
-def _files(tmp_path):
-    p = {}
-    for name in ("x.bam", "r.fa", "f.gff", "o.csv.gz"):
-        (tmp_path / name).write_text("x")
-        p[name] = str(tmp_path / name)
-    return p
-
-
-def _base(f):
-    return ["-i", f["x.bam"], "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30", "-name", "S", "-o", "out.fa"]
 
 
 def test_min_af_spellings_and_defaults(tmp_path):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     got = [cli.GetArgs(_base(f) + ["--variant-table", "t.tsv", "--min-af", s]).min_af for s in ("0.03", "3e-2", "3/100")]
     assert got == [Fraction(3, 100)] * 3 and all(isinstance(x, Fraction) for x in got)
     assert engine.min_af_fraction("0.03") == engine.min_af_fraction("3e-2") == engine.min_af_fraction("3/100") == (3, 100)
@@ -164,14 +136,14 @@ def test_min_af_spellings_and_defaults(tmp_path):
 @pytest.mark.parametrize("extra", (["--min-af", "1.5"], ["--min-af=-0.1"], ["--min-af", "1/3000001"], ["--min-af", "abc"], ["--min-af", "1/0"],
                                    ["--min-alt-depth", "0"], ["--variant-min-depth", "-1"], ["--min-alt-depth", "2147483648"]))
 def test_bad_thresholds_are_refused(tmp_path, capsys, extra):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     with pytest.raises(SystemExit) as e:
         cli.GetArgs(_base(f) + ["--variant-table", "t.tsv"] + extra)
     assert e.value.code == 2 and extra[0].split("=")[0] in capsys.readouterr().err
 
 
 def test_thresholds_need_a_table_and_batch_takes_the_manifest(tmp_path, capsys):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     for extra in (["--min-af", "0.1"], ["--min-alt-depth", "3"], ["--variant-min-depth", "20"]):
         with pytest.raises(SystemExit) as e:
             cli.GetArgs(_base(f) + extra)
@@ -195,7 +167,7 @@ def test_thresholds_need_a_table_and_batch_takes_the_manifest(tmp_path, capsys):
 
 
 def test_children_get_the_thresholds_only_when_set(tmp_path):
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     plain = cli._child_argv(cli.GetArgs(_base(f)), True)
     assert not any(x.startswith(("--min-af", "--variant", "--min-alt")) for x in plain)
     a = cli.GetArgs(_base(f) + ["--variant-table", "t.tsv", "--min-af", "3e-2", "--min-alt-depth", "2"])
@@ -214,7 +186,7 @@ def test_batch_over_gpus_with_a_mixed_manifest(tmp_path, monkeypatch, capsys):
     """`--batch m.tsv --gpus 2 --min-af 0.05` where one sample of three names a table: the thresholds-without-a-table check is the
     parent's, over the whole manifest; a shard without a table gets no thresholds and its child's own checks pass; the shard with
     the table gets them"""
-    f = _files(tmp_path)
+    f = stub_files(tmp_path, ("x.bam", "r.fa", "f.gff", "o.csv.gz"))
     man = tmp_path / "m.tsv"
     man.write_text("%s\tS0\to0.fa\n%s\tS1\to1.fa\t-\t-\t-\t%s\n%s\tS2\to2.fa\tv.vcf\t\t\t-\n" % (f["x.bam"], f["x.bam"], tmp_path / "t1.tsv", f["x.bam"]))
     seen = []

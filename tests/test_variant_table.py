@@ -5,25 +5,22 @@ are checked without a GPU in tests/test_variant_rule.py."""
 import functools
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import c_oracle
+from tests import cli_run as cr
+from tests import device_file as dvf
 from tests import primer_yardstick as py
+from tests import read_specs as rsp
+from tests import schemes as sch
 from tests import synth_small as ss
-from tests import test_base_quality as bq
-from tests import test_matrix_abi as ma
-from tests import test_primer_mask as pm
-from tests import test_read_filter as rf
 from tests import variant_yardstick as vy
 from trueconsense_amd import _ffi, contigs, engine
 from trueconsense_amd.io import bamwriter
 
 pytestmark = pytest.mark.gpu
-ROOT = rf.ROOT
 RULE = (1, 10, 2, 5)                # min_af 1/10, min_alt_depth 2, min_depth 5
 KW = dict(min_af="1/10", min_alt_depth=2, min_depth=5)
 REF_BYTES = np.frombuffer(b"ACGTacgtACGTACGTN\0", np.uint8)
@@ -60,10 +57,10 @@ def on_device(ctx, counts, ref, ld=None, off=0, cap=None, rec_lead=0, rule_kw=KW
     buffer of `cap` records -> (records read back, n_found, TcmiError or None); the matrix must be bit-identical afterwards"""
     L = len(counts)
     ld = L if ld is None else ld
-    m = ma.Matrix(L, ld, off, planes(counts, ld))
-    r = ma.Guarded(len(ref), np.uint8, 0, np.frombuffer(ref, np.uint8)) if len(ref) else None
+    m = dvf.Matrix(L, ld, off, planes(counts, ld))
+    r = dvf.Guarded(len(ref), np.uint8, 0, np.frombuffer(ref, np.uint8)) if len(ref) else None
     room = 5 * min(L, len(ref)) if cap is None else cap
-    out = ma.Guarded(4 * room, np.int32, rec_lead, salt=77) if room else None
+    out = dvf.Guarded(4 * room, np.int32, rec_lead, salt=77) if room else None
     err = None
     try:
         n = ctx.variants_dev(m.ptr, L, ld, r.ptr if r else 0, len(ref), d_records=out.ptr if out else 0, cap=room, **rule_kw)
@@ -306,80 +303,70 @@ def table_text(counts, ref, region="ref", rule=CLI_RULE):
     return engine.VARIANTS_HEADER + vy.text(vy.records(counts, ref.encode(), *rule), region, ref.encode())
 
 
-def _out(t):
-    return ["-o", t + ".fa", "-vcf", t + ".vcf", "-ogff", t + ".gff", "-doc", t + ".tsv"]
-
-
 def test_cli_single_sample_and_batch(tmp_path, monkeypatch):
     """-i with --variant-table: the table is the yardstick's over the oracle's matrix, the four other outputs are those of the run
     without the flag; with --min-baseq 20 --primers it follows the masked matrix, with --index-override the overridden one; --batch
     with a 7-column manifest writes each sample's -i table, a 6-column manifest none"""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
-    L = rf.L
-    rd, rd3 = rf.arrays(specs), rf.arrays(specs[::2])
+    ref, orfs, specs = rsp.mixed()
+    L = rsp.L
+    rd, rd3 = rsp.arrays(specs), rsp.arrays(specs[::2])
     bamwriter.write_bam("A.bam", rd, ref_len=L, block=4096)
     bamwriter.write_bam("A2.bam", rd, ref_len=L, block=4096, split_records=True)
     bamwriter.write_bam("A3.bam", rd3, ref_len=L, block=4096)
-    common = bq._setup_cli(tmp_path, ref, orfs)
+    common = cr.setup_cli(ref, orfs)
     counts = c_oracle.tally(rd, c_oracle.extent(rd, L))
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + _out("a") + ["--variant-table", "a.var", "--stats", "a.json"] + FLAGS)
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + _out("b") + ["--stats", "b.json"])
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("a") + ["--variant-table", "a.var", "--stats", "a.json"] + FLAGS)
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + cr.out_args("b") + ["--stats", "b.json"])
     want = table_text(counts, ref)
     assert open("a.var").read() == want and want.count("\n") > 50 and "\t*\t" in want and "\t+\t" in want
-    assert rf._outputs("a") == rf._outputs("b") and not os.path.exists("b.var")
+    assert cr.outputs("a") == cr.outputs("b") and not os.path.exists("b.var")
     assert (json.load(open("a.json"))["variant_records"], json.load(open("b.json"))["variant_records"]) == (want.count("\n") - 1, 0)
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "d.fa", "--variant-table", "d.var"])       # the defaults: 3 %, 1, 10
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "d.fa", "--variant-table", "d.var"])       # the defaults: 3 %, 1, 10
     assert open("d.var").read() == table_text(counts, ref, rule=(3, 100, 1, 10))
     # the floor and the primer mask: the table follows the masked matrix
-    pm.write_bed("p.bed", pm.SCHEME)
-    masked = py.counts(rd, L, pm.SCHEME, 20)[0]
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "q.fa", "--variant-table", "q.var", "--min-baseq", "20", "--primers", "p.bed"] + FLAGS)
+    sch.write_primer_bed("p.bed", sch.PRIMER_SCHEME)
+    masked = py.counts(rd, L, sch.PRIMER_SCHEME, 20)[0]
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "q.fa", "--variant-table", "q.var", "--min-baseq", "20", "--primers", "p.bed"] + FLAGS)
     assert open("q.var").read() == table_text(masked, ref) != want
     # --index-override: the table is taken behind the override
     over = counts.copy()
     over[100:140] = (60, 10, 20, 0, 30, 6, 3)
-    bq._write_override("o.csv.gz", over)
-    rf._run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "o.fa", "--variant-table", "o.var", "--index-override", "o.csv.gz"] + FLAGS)
+    cr.write_override("o.csv.gz", over)
+    cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "o.fa", "--variant-table", "o.var", "--index-override", "o.csv.gz"] + FLAGS)
     assert open("o.var").read() == table_text(over, ref) != want
     # --batch: three samples, the manifest's 7th column
-    rf._run_cli(monkeypatch, ["-i", "A3.bam", "-name", "S"] + common + _out("a3") + ["--variant-table", "a3.var"] + FLAGS)
+    cr.run_cli(monkeypatch, ["-i", "A3.bam", "-name", "S"] + common + cr.out_args("a3") + ["--variant-table", "a3.var"] + FLAGS)
     with open("m7.tsv", "w") as fh:
         for k, bam in enumerate(("A.bam", "A2.bam", "A3.bam")):
             fh.write("\t".join([bam, "S"] + ["m%d.%s" % (k, e) for e in ("fa", "vcf", "gff", "tsv", "var")]) + "\n")
-    rf._run_cli(monkeypatch, ["--batch", "m7.tsv"] + common + FLAGS + ["--stats", "m.json"])
+    cr.run_cli(monkeypatch, ["--batch", "m7.tsv"] + common + FLAGS + ["--stats", "m.json"])
     for k, tag in enumerate(("a", "a", "a3")):
         assert open("m%d.var" % k).read() == open(tag + ".var").read(), k
-        assert rf._outputs("m%d" % k) == rf._outputs(tag), k
+        assert cr.outputs("m%d" % k) == cr.outputs(tag), k
     assert json.load(open("m.json"))["variant_records"] == 2 * (want.count("\n") - 1) + open("a3.var").read().count("\n") - 1
     with open("m6.tsv", "w") as fh:
         for k, bam in enumerate(("A.bam", "A2.bam", "A3.bam")):
             fh.write("\t".join([bam, "S"] + ["s%d.%s" % (k, e) for e in ("fa", "vcf", "gff", "tsv")]) + "\n")
-    rf._run_cli(monkeypatch, ["--batch", "m6.tsv"] + common)
+    cr.run_cli(monkeypatch, ["--batch", "m6.tsv"] + common)
     for k, tag in enumerate(("a", "a", "a3")):
-        assert rf._outputs("s%d" % k) == rf._outputs(tag) and not os.path.exists("s%d.var" % k)
+        assert cr.outputs("s%d" % k) == cr.outputs(tag) and not os.path.exists("s%d.var" % k)
 
 
 def test_cli_per_contig(tmp_path, monkeypatch):
     """--per-contig: one file for both contigs in axis order, rows with the contig's name and its own positions; nothing from the
     guard columns behind a contig's end or from the slots' padding"""
     monkeypatch.chdir(tmp_path)
-    recs, rows, specs = bq._two_contigs()
+    recs, rows, specs = rsp.two_contigs()
     refs = [("c0", 1500), ("c1", 1200)]
-    bamwriter.write_bam("A.bam", rf.arrays(specs), refs=refs, block=4096)
-    with open("r.fa", "w") as fh:
-        for name, ref in recs:
-            fh.write(">%s\n%s\n" % (name, ref))
-    with open("g.gff", "w") as fh:
-        fh.write("##gff-version 3\n")
-        for name, orfs in rows:
-            fh.write(pm.sy.gff_text(orfs, seqid=name)[1])
+    bamwriter.write_bam("A.bam", rsp.arrays(specs), refs=refs, block=4096)
+    cr.setup_contigs(recs, rows)
     args = ["-i", "A.bam", "-ref", "r.fa", "-gff", "g.gff", "-cov", "10", "-name", "S", "--per-contig"]
-    rf._run_cli(monkeypatch, args + ["-o", "a.fa", "-doc", "a.tsv", "--variant-table", "a.var", "--stats", "a.json"] + FLAGS)
-    rf._run_cli(monkeypatch, args + ["-o", "b.fa", "-doc", "b.tsv"])
+    cr.run_cli(monkeypatch, args + ["-o", "a.fa", "-doc", "a.tsv", "--variant-table", "a.var", "--stats", "a.json"] + FLAGS)
+    cr.run_cli(monkeypatch, args + ["-o", "b.fa", "-doc", "b.tsv"])
     want = engine.VARIANTS_HEADER
     for t, (name, ln) in enumerate(refs):
-        rd = rf.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
+        rd = rsp.arrays([dict(r, tid=0) for r in specs if r["tid"] == t])
         counts = c_oracle.tally(rd, c_oracle.extent(rd, ln))
         part = vy.text(vy.records(counts, recs[t][1].encode(), *CLI_RULE), name, recs[t][1].encode())
         assert part.count("\n") > 10
@@ -397,13 +384,9 @@ def test_cli_split_worker_at_world_one(tmp_path, monkeypatch):
     """`-i --gpus N`'s worker (trueconsense_amd.split_main) as one rank: rank 0 takes the table from the reduced counts; the parent
     forwards the flags (tests/test_variant_rule.py checks the children's command line)"""
     monkeypatch.chdir(tmp_path)
-    ref, orfs, specs = rf.mixed()
-    rd = rf.arrays(specs)
-    bamwriter.write_bam("A.bam", rd, ref_len=rf.L, block=4096, split_records=True)
-    common = bq._setup_cli(tmp_path, ref, orfs)
-    env = {k: v for k, v in os.environ.items() if k not in ("TCMI_SPLIT_ONE_GPU", "TCMI_SPLIT_BACKEND")}
-    env.update(PYTHONPATH=ROOT, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    argv = [sys.executable, "-m", "trueconsense_amd.split_main", "-i", "A.bam", "-name", "S"] + common + _out("w") + ["--variant-table", "w.var", "--gpus", "1"] + FLAGS
-    r = subprocess.run(argv, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-1500:]
-    assert open("w.var").read() == table_text(c_oracle.tally(rd, c_oracle.extent(rd, rf.L)), ref)
+    ref, orfs, specs = rsp.mixed()
+    rd = rsp.arrays(specs)
+    bamwriter.write_bam("A.bam", rd, ref_len=rsp.L, block=4096, split_records=True)
+    common = cr.setup_cli(ref, orfs)
+    cr.run_split_worker(["-i", "A.bam", "-name", "S"] + common + cr.out_args("w") + ["--variant-table", "w.var", "--gpus", "1"] + FLAGS)
+    assert open("w.var").read() == table_text(c_oracle.tally(rd, c_oracle.extent(rd, rsp.L)), ref)
