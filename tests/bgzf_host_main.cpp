@@ -11,6 +11,8 @@
 //                                        whole <first record>      (every block inflated: the header once more, from the whole stream, as tcmi_bam_load has it)
 //   bgzf_host_main damaged FILE...   the same, and a last line "damaged: <n> files, <refused> refused, <parsed> parsed"
 //   bgzf_host_main chain             the record-chain rule on a table of hand-made cases; a line per case, exit status 1 if one fails
+//   bgzf_host_main chainfile TABLE   the record-chain rule over windows of a block table read from TABLE (chainfile() says how it is
+//                                    written); a line per window: <code> <block> <range_first> <range_next> <what>
 #include <cstdio>
 #include <fstream>
 #include <memory>
@@ -134,12 +136,53 @@ static int chain()
     return bad ? 1 : 0;
 }
 
+// ---- the record chain over a block table from a file, window by window -----------------------------------------------------------------
+// TABLE: the number of blocks, then per block "entry ulen first over stat"; the number of windows, then per window "first_block nb_own nb
+// ranged".  A window is decoded as a file of its own (bam_device.hip: decode_enqueue): its blocks' places in the stream start at 0, and
+// so do the anchors printed for it.
+static int chainfile(const char *path)
+{
+    std::ifstream in(path);
+    size_t n = 0, n_win = 0;
+    if (!(in >> n)) { std::fprintf(stderr, "%s: no block count\n", path); return 2; }
+    std::vector<Blk> all(n);
+    for (Blk &b : all) {
+        long long entry, ulen, first, over, stat;
+        if (!(in >> entry >> ulen >> first >> over >> stat)) { std::fprintf(stderr, "%s: the block table ends early\n", path); return 2; }
+        b = Blk{(int32_t)entry, (uint32_t)ulen, (uint32_t)stat, (uint32_t)first, (int32_t)over};
+    }
+    if (!(in >> n_win)) { std::fprintf(stderr, "%s: no window count\n", path); return 2; }
+    std::vector<BlockDesc> blocks;
+    std::vector<uint32_t> stat, first;
+    std::vector<int32_t> over;
+    for (size_t w = 0; w < n_win; ++w) {
+        long long fb, nb_own, nb, ranged;
+        if (!(in >> fb >> nb_own >> nb >> ranged) || fb < 0 || nb_own < 0 || nb < nb_own || (size_t)(fb + nb) > n) {
+            std::fprintf(stderr, "%s: window %zu does not lie in the table\n", path, w);
+            return 2;
+        }
+        blocks.assign((size_t)nb, BlockDesc{});
+        stat.assign((size_t)nb, 0); first.assign((size_t)nb, 0); over.assign((size_t)nb, 0);
+        uint64_t uout = 0;
+        for (size_t b = 0; b < (size_t)nb; ++b) {
+            const Blk &s = all[(size_t)fb + b];
+            blocks[b] = BlockDesc{0, uout, 0, s.ulen, s.entry, 0, 0};
+            uout += s.ulen;
+            stat[b] = s.stat; first[b] = s.first; over[b] = s.over;
+        }
+        const tcmi_chain_verdict v = tcmi_bam_chain_check(blocks.data(), (size_t)nb, (size_t)nb_own, ranged != 0, stat.data(), first.data(), over.data());
+        std::printf("%d %zu %lld %lld %s\n", v.code, v.block, (long long)v.range_first, (long long)v.range_next, v.what.c_str());
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     const std::string mode = argc > 1 ? argv[1] : "";
     if (mode == "chain") return chain();
+    if (mode == "chainfile" && argc == 3) return chainfile(argv[2]);
     if (mode != "table" && mode != "damaged") {
-        std::fprintf(stderr, "usage: %s table FILE... | damaged FILE... | chain\n", argv[0]);
+        std::fprintf(stderr, "usage: %s table FILE... | damaged FILE... | chain | chainfile TABLE\n", argv[0]);
         return 2;
     }
     int parsed = 0;

@@ -10,7 +10,9 @@ from oracle import c_oracle
 from tests import fuzz_reads as fz
 from tests import synth_small as ss
 from tests import hand_bam as hand
-from tests.device_file import check_counts, check_decode, host_stream_and_records
+from tests.device_file import check_counts, check_decode
+from tests.long_records import false_start_inside_a_record as _false_start_inside_a_record
+from tests.long_records import record_head as _record_head
 from trueconsense_amd import _ffi, _state, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
@@ -293,48 +295,6 @@ def test_long_reads_stay_on_the_device(ctx, tmp_path):
     runner = engine.FileRunner(ctx, [{"start": 10, "end": 600, "strand": "+"}], 30)
     runner.run([p], names=["S"], ref_len=L)
     assert runner.decoded_on == {"device": 1, "host": 0}
-
-
-def _block_ulens(path):
-    """ISIZE of every BGZF block of the file"""
-    raw, at, out = open(path, "rb").read(), 0, []
-    while at < len(raw):
-        size = struct.unpack_from("<H", raw, at + 16)[0] + 1
-        out.append(struct.unpack_from("<I", raw, at + size - 4)[0])
-        at += size
-    return out
-
-
-def _false_start_inside_a_record(tmp_path, fake, at):
-    """One read of 1 500 bases among short ones, in 512-byte blocks filled to the brim: its record of 2.3 KB covers whole blocks.
-    `fake` goes into its QUAL (no floor: the counts do not depend on it), at offset `at` (< 0: from the end) of a block that lies
-    wholly inside the record.  Every other QUAL byte is 30 and SEQ holds A / C / G / T only: four such bytes never read as
-    block_size < 2^24, so `fake` is the only place in the long record where the decoder's search for a record start can say yes.
-    -> (path, reads, L, that block's index, the read's index)"""
-    ref, _ = sy.make_reference(L=3000, cds=[(10, 600)])
-    mk = lambda pos, n, name: {"pos": pos, "flag": 0, "cigar": "%dM" % n, "seq": ref[pos:pos + n], "qual": [30] * n, "name": name}
-    specs = [mk(20 + 7 * k, 60, "a%d" % k) for k in range(8)] + [mk(100, 1500, "long")] + [mk(120 + 9 * k, 60, "b%d" % k) for k in range(12)]
-    which = 8
-    path = str(tmp_path / "inside.bam")
-    bamwriter.write_bam(path, ss.reads_from_spec({"reads": specs}), "r", len(ref), block=512, split_records=True)
-    rec = host_stream_and_records(path)[1]
-    qual_at, rec_end = int(rec[which]) + 36 + len("long") + 1 + 4 + 750, int(rec[which + 1])
-    assert rec_end - qual_at == 1500
-    starts = np.concatenate(([0], np.cumsum(_block_ulens(path))))
-    b = next(k for k in range(len(starts) - 1) if starts[k] >= qual_at and starts[k + 1] <= rec_end and starts[k + 1] - starts[k] == 512)
-    where = int(starts[b]) + (at if at >= 0 else 512 + at) - qual_at
-    assert 0 <= at + (512 if at < 0 else 0) <= 512 - len(fake)
-    specs[which]["qual"][where:where + len(fake)] = list(fake)
-    reads = ss.reads_from_spec({"reads": specs})
-    bamwriter.write_bam(path, reads, "r", len(ref), block=512, split_records=True)
-    stream, rec2 = host_stream_and_records(path)
-    assert np.array_equal(rec2, rec) and bytes(stream[int(starts[b]) + at % 512:][:len(fake)]) == bytes(fake)
-    return path, reads, len(ref), b, which
-
-
-def _record_head(block_size):
-    """the fixed fields the search tests, all plausible: refID 0, pos 5, l_read_name 2, one CIGAR op, l_seq 4, no mate (44 bytes needed)"""
-    return struct.pack("<IiiIIIii", block_size, 0, 5, 2, 1, 4, -1, -1)
 
 
 def test_a_false_record_start_in_the_tail_of_a_block_inside_a_record_is_withdrawn(ctx, tmp_path):
