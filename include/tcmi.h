@@ -465,6 +465,77 @@ int  tcmi_link_phase(int32_t both, int32_t only_a, int32_t only_b, int32_t span,
 int  tcmi_variants_links_text(const tcmi_variant *records, int64_t n, const tcmi_link_counts *links, int64_t n_cols, /* the records' distinct positions, ascending */
                               int32_t k, int32_t min_depth, int64_t num, int64_t den, const char *region, int64_t pos_offset,
                               const uint8_t *ref, int64_t n_ref, char *text, int64_t cap, int64_t *len);
+/* ---- indel events (additive: what `ivar variants` prints as +ACG / -3; the reference has nothing like it) ----------------------------
+ * The variant table's '+' row says how many records carry the insertion mark, not which bases; its '*' rows are single deleted columns.
+ * Here every insertion and every deletion is ONE event with its length and, for an insertion, its bases — counted by three HIP
+ * launches over the inflated record stream a device-decoded read set left resident on its context, in a keyed table on the device
+ * (the keys are not known before the records are read).  All arithmetic is integer and every result is the same in every run.
+ *   columns        c_0 < c_1 < ... < c_{n-1} on the count matrix's axis, each in [0, 2^29), n in 1..2^20, with cov[i] >= 0 the count
+ *                  matrix's coverage at c_i (the variant records' cov).
+ *   event          of a kept record (what tcmi_readset_amplicon_reads calls kept) at a queried column c, under the read filter, the
+ *                  base-quality floor, the primer table and the layout the read set REMEMBERS:
+ *                  INS (kind 1)  iff the record's token at c carries the I mark, i.e. exactly when it adds 1 to the count matrix's I
+ *                      plane at c.  len = the inserted bases: those of the I ops behind the op that holds c, up to the next op that is
+ *                      neither I nor P when an I op follows directly, up to the next reference-consuming op when a P op follows (S ops
+ *                      between consume query, H and P do not) — htslib's rule, the count matrix's.  The bases are those ops' query
+ *                      nibbles in CIGAR order; a query index at or beyond l_seq (SEQ '*') reads as nibble 15, 'N'.  Two insertions
+ *                      are the same event iff len and every nibble are equal: IUPAC codes are not merged.
+ *                  DEL (kind 2)  iff the op that holds c is a D op, c is its first column, and the record's token at c is counted at
+ *                      all (not masked by the primer table, not below the floor: a D token is tested at the query index at which its op
+ *                      starts).  len = that op's length.  ONE D OP IS ONE EVENT: adjacent D ops ("3D2D", which no aligner writes) are
+ *                      two events, at their own first columns.  A record may give both at one column ("1D" followed by "I").
+ *   totals         per queried column ins_total, del_total: the events of each kind anchored there, reported or not.
+ *   invariant      ins_total[i] equals the count matrix's I plane at c_i.  For deletions only del_total[i] <= cov[i] holds: a "1D" + I
+ *                  token counts I and not X, a primer mask may cut a deletion behind its first column (its later columns are '*' rows
+ *                  without an event), and a column inside a longer deletion counts X without anchoring one.
+ *   reported       an event with `count` records on a column of coverage cov iff cov >= max(min_depth, 1), count >= min_alt_depth and
+ *                  count * den >= num * cov (64-bit products, an exact tie is in): the variant table's rule.  The rule is applied on
+ *                  the device: only reported events are downloaded.  tcmi_indel_passes is its GPU-free twin (1 / 0, TCMI_E_ARG for
+ *                  a negative count or coverage and the range errors below).
+ *   tcmi_readset_indel_events   events: host, room for cap; text: host, room for text_cap letters, one per inserted base from
+ *                  "=ACMGRSVTWYHKDBN"; totals: host, room for n (pos = c_i).  The events come in THE order (pos, kind, len, bases):
+ *                  every run gives the same bytes.  An INS event's bases are text[text_off .. text_off + len); a DEL's text_off is
+ *                  -1.  *n_found and *text_len always say how much there is; when either exceeds its capacity nothing is written to
+ *                  events or text and the call returns TCMI_E_ARG, except for the sizing call (events = text = NULL, cap =
+ *                  text_cap = 0), which returns TCMI_OK.  totals are written either way.  Residency, an empty read set (zero events,
+ *                  TCMI_OK) and the scratch as for tcmi_readset_strand_counts; a read set of sub-ranges is counted part by part, each
+ *                  on its own context without the rule, equal events are merged on the host and the rule is applied there.  Waits for
+ *                  the stream once per attempt and once for the download.
+ *   exactness      an insertion's key in the table is a 34-bit hash of its length and bases; a second pass over the records compares
+ *                  every insertion with its slot's representative (the first record, in file order, that claimed it).  When two
+ *                  different insertions of one column share a key the call starts over with the next of four seeds, then fails with
+ *                  TCMI_E_UNSUPPORTED; when the table (2^"indel_slots" slots, default 2^15) overflows or a probe runs 64 steps it
+ *                  starts over eight times as large, up to 2^24 slots, then fails with TCMI_E_UNSUPPORTED.  A returned result is
+ *                  therefore always exact.  Options, for tests: "indel_slots" (4..24), "indel_hash_bits" (0..34, the rest of the hash
+ *                  is zero); counters: "indel_table_grown", "indel_hash_retried".
+ *   tcmi_indel_hash   HOST: the hash of an insertion, nibbles one code (0..15) per byte, bits in 0..34.
+ *   tcmi_indels_text   HOST, re-entrant, no GPU: the one writer of --indel-table's rows.  All events of one call are one region.  Row:
+ *                  REGION POS TYPE LEN SEQ COUNT TOTAL_DP FREQ.  TYPE is INS or DEL.  POS of an INS is the 1-based position of the
+ *                  base in front of the insertion (the '+' row's POS), of a DEL the first deleted base (the first '*' row's POS).  SEQ
+ *                  of an INS are the inserted bases, of a DEL the deleted reference bases, upper-cased, N beyond the reference.  FREQ =
+ *                  COUNT / TOTAL_DP as a double printed with %.6f.  totals[0..n_cols): the totals at the distinct positions of the
+ *                  '*' and '+' records among `records`, ascending.  TCMI_E_ARG, and no text, when totals[j].pos is not the j-th such
+ *                  position (or n_cols is not their number); when a '+' record's count is not ins_total at its position or
+ *                  del_total exceeds a record's cov there (the stream kernels and the matrix's disagree); when an event lies on no
+ *                  such position, its cov is not the records', its count exceeds its kind's total, its bases lie outside text or
+ *                  are no such letters, or the events are not in THE order.  Sizing call, short buffer and *len as for
+ *                  tcmi_variants_text.  The header line (TCMI_INDELS_HEADER) is the caller's.
+ * TCMI_INDEL_LDS: the columns whose list and totals a workgroup stages in LDS (6 KiB); a longer list is searched, and its totals are
+ * counted, in memory; for tests.
+ * Range errors are TCMI_E_ARG: den outside 1..10^6, num outside 0..den, min_alt_depth < 1, min_depth < 0, a negative cov. */
+typedef struct tcmi_indel_event { int32_t pos, kind /* 1 INS, 2 DEL */, len, count, cov, reserved /* 0 */; int64_t text_off /* INS: into text; DEL: -1 */; } tcmi_indel_event;   /* 32 bytes */
+typedef struct tcmi_indel_totals { int32_t pos, ins_total, del_total, reserved /* 0 */; } tcmi_indel_totals;   /* 16 bytes */
+#define TCMI_INDEL_LDS 512
+#define TCMI_INDELS_HEADER "REGION\tPOS\tTYPE\tLEN\tSEQ\tCOUNT\tTOTAL_DP\tFREQ\n"
+int  tcmi_readset_indel_events(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *cols /* host */, const int32_t *cov /* host, n */,
+                               int64_t num, int64_t den, int32_t min_alt_depth, int32_t min_depth, tcmi_indel_event *events /* host, cap */,
+                               int64_t cap, int64_t *n_found, char *text /* host, text_cap */, int64_t text_cap, int64_t *text_len,
+                               tcmi_indel_totals *totals /* host, n */);
+uint64_t tcmi_indel_hash(uint32_t seed, int32_t len, const uint8_t *nibbles /* one code per byte */, int32_t bits);
+int  tcmi_indel_passes(int32_t count, int32_t cov, int64_t num, int64_t den, int32_t min_alt_depth, int32_t min_depth);
+int  tcmi_indels_text(const tcmi_indel_event *events, int64_t n, const char *text, int64_t text_len, const tcmi_indel_totals *totals,
+                      int64_t n_cols, const tcmi_variant *records, int64_t n_records, const char *region, int64_t pos_offset,
+                      const uint8_t *ref, int64_t n_ref, char *out, int64_t cap, int64_t *len);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -486,7 +557,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_AMPLICON_READS = 12 /* tcmi_readset_amplicon_reads' one launch */,
        TCMI_K_STRAND_COUNTS = 13 /* tcmi_readset_strand_counts' one launch */,
        TCMI_K_LINK_COUNTS = 14 /* tcmi_readset_link_counts' one launch */,
-       TCMI_K_NKERNELS = 15 };
+       TCMI_K_INDEL_EVENTS = 15 /* tcmi_readset_indel_events' launches (count, verify, gather) of one attempt as one bracket */,
+       TCMI_K_NKERNELS = 16 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);

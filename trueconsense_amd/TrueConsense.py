@@ -15,7 +15,9 @@ how many of them run from its left primer into its right one; records inside sev
 counted on the device in the decoded record stream; not with --batch), the links between the variant table's rows --variant-links FILE
 [--link-neighbours K] [--link-min-depth N] [--link-ratio F] (for every two rows at most K distinct positions apart how many alignment
 records carry both alleles, one of them or neither, and the phase CIS / TRANS / MIXED / NONE / LOW; counted likewise; needs
---variant-table; not with --batch or --index-override), and
+--variant-table; not with --batch or --index-override), the indel table --indel-table FILE (one row per insertion or deletion at the
+variant table's '+' and '*' positions, with its length, its bases and the records that carry it, under --min-af / --min-alt-depth /
+--variant-min-depth; counted likewise; needs --variant-table; not with --batch, --index-override or -i --gpus N), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -190,13 +192,17 @@ class StreamCounts:
     --variant-strand and --variant-links of the parsed namespace (layout: amplicon_reads_of's).  False when none is asked for.  A
     further count of this kind is one more line in each method here, and one _sum_to_root call in distributed.consensus_split_bamfile."""
     KEYS = ("amplicon_reads", "variant_strand", "variant_links")    # count's keys; the order of consensus_split_bamfile's extra parts
+    # (--indel-table's "indel_events" is no such part: its lists have no fixed length, and -i --gpus N is refused with it)
+    indels = None                                                   # --indel-table's file
 
     def __init__(self, a, layout=None):
         self.areads, self.srule, self.links = amplicon_reads_of(a, layout), strand_of(a), links_of(a)
-        self.lists_records = bool(self.srule or self.links)          # must the step list the variant table's records?
+        self.indels = getattr(a, "indel_table", None)
+        self.lists_records = bool(self.srule or self.links or self.indels)      # must the step list the variant table's records?
         self.variants = variants_of(a) if self.lists_records else None
         # the flag named when the file leaves the device path (indexing.device_readset's `need`)
-        self.need = "--variant-strand" if self.srule else "--variant-links" if self.links else "--amplicon-reads" if self.areads else None
+        self.need = "--variant-strand" if self.srule else "--variant-links" if self.links else "--indel-table" if self.indels else \
+            "--amplicon-reads" if self.areads else None
 
     def __bool__(self):
         return self.need is not None
@@ -213,6 +219,8 @@ class StreamCounts:
             got["variant_strand"] = ctx.strand_counts_of(rs, records)
         if self.links:
             got["variant_links"] = ctx.link_counts_of(rs, records, self.links[1])
+        if self.indels:
+            got["indel_events"] = ctx.indel_events_of(rs, records, **self.variants)
         return got
 
     def split_kwargs(self, ref):
@@ -251,6 +259,16 @@ def write_variant_tables(a, parts, want):
     if want.links:                                  # (its writer refuses likewise)
         stats.update(write_variant_links(want.links[0], [p[:1] + p[2:] for p in parts], want.links))
     return stats
+
+
+def write_indel_table(path, parts):
+    """--indel-table: the header line, then for every (records, their (events, text, totals), region, reference on the records' axis,
+    pos_offset) one row per reported insertion or deletion.  Nothing is written when a part's insertions do not add up to its '+' rows
+    (TcmiError)."""
+    from .engine import INDELS_HEADER, indels_text
+    text = "".join(indels_text(*found, recs, region, ref, off) for recs, found, region, ref, off in parts)
+    with open(path, "w") as out:
+        out.write(INDELS_HEADER + text)
 
 
 def _names_a_table(line):
@@ -530,6 +548,12 @@ def GetArgs(givenargs):
     additive.append((("--link-ratio",), dict(type=_link_ratio_arg(parser), default=None, metavar="F",
                                              help="PHASE is CIS when BOTH is at least F of the rarer allele's records among those that span\n"
                                                   "both positions, TRANS when at most 1 - F; above 1/2 up to 1, a decimal or n/d (default 9/10)")))
+    additive.append((("--indel-table",), dict(type=str, default=None, metavar="File",
+                                              help="also write every insertion and every deletion at the variant table's '+' and '*' positions as\n"
+                                                   "one row: REGION POS TYPE (INS / DEL) LEN SEQ COUNT TOTAL_DP FREQ (ivar variants' +ACG / -3),\n"
+                                                   "under --min-af / --min-alt-depth / --variant-min-depth, counted in the records the device\n"
+                                                   "decoded; needs --variant-table and the device decoder; not with --batch, --index-override\n"
+                                                   "or -i --gpus N")))
     additive.append((("--amplicon-table",), dict(type=str, default=None, metavar="File",
                                                  help="also write per amplicon of the scheme the depth of its columns, tab-separated: SAMPLE REGION\n"
                                                       "AMPLICON POOL START END LEN MEAN MEDIAN MIN MIN_POS BELOW (BELOW: columns under -cov), from\n"
@@ -563,12 +587,15 @@ def GetArgs(givenargs):
     a.variant_thresholds_given = any(v is not None for v in (a.min_af, a.min_alt_depth, a.variant_min_depth))
     # the flags that count behind the step, with their dependant options: their refusals exit 1 with one line, nothing written
     for flag, on, deps in (("--variant-strand", a.variant_strand, ("strand_min_depth", "strand_ratio")),
-                           ("--variant-links", a.variant_links is not None, ("link_neighbours", "link_min_depth", "link_ratio"))):
+                           ("--variant-links", a.variant_links is not None, ("link_neighbours", "link_min_depth", "link_ratio")),
+                           ("--indel-table", a.indel_table is not None, ())):
         names = " / ".join("--" + d.replace("_", "-") for d in deps)
         for bad, why in ((not on and any(getattr(a, d) is not None for d in deps), f"{names} need {flag}."),
                          (on and a.batch is not None, f"{flag} goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
                          (on and a.batch is None and a.variant_table is None, f"{flag} needs --variant-table."),
-                         (on and a.index_override is not None, f"{flag} does not go with --index-override: the overridden matrix no longer equals the reads.")):
+                         (on and a.index_override is not None, f"{flag} does not go with --index-override: the overridden matrix no longer equals the reads."),
+                         (on and flag == "--indel-table" and a.batch is None and a.gpus and a.gpus > 1,
+                          f"{flag} does not go with -i --gpus N: the ranks' event lists would have to be merged on rank 0, which is not built.")):
             if bad:
                 print(f"{why} Exiting...")
                 sys.exit(1)
@@ -878,6 +905,8 @@ def _single_sample(a, flt, t):
         recs = _state.default_context().variants(indexDict.counts, refseq, **variants_of(a))
         vparts = [(recs, got.get("variant_strand"), got.get("variant_links"), refID, refseq, 0)]
     vstats = write_variant_tables(a, vparts, want)
+    if want.indels:
+        write_indel_table(want.indels, [(recs, got["indel_events"], refID, refseq, 0)])
 
     amps, n_below = amplicons_of(a), 0
     if amps:                                        # likewise: the matrix behind the read filter, --min-baseq, --primers and --index-override

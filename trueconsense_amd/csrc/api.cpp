@@ -269,6 +269,8 @@ int tcmi_ctx_set_option(tcmi_ctx *c, const char *key, int value)
     else if (!std::strcmp(key, "sym_scratch_div")) c->sym_scratch_div = value < 1 ? 1 : value > 64 ? 64 : value;
     else if (!std::strcmp(key, "h2d_pieces")) c->h2d_pieces = value < -1 ? -1 : value > 16 ? 16 : value;
     else if (!std::strcmp(key, "split_sub")) c->split_sub = value < 0 ? 0 : value > 8 ? 8 : value;
+    else if (!std::strcmp(key, "indel_slots")) c->indel_slots = value < 4 ? 4 : value > 24 ? 24 : value;
+    else if (!std::strcmp(key, "indel_hash_bits")) c->indel_hash_bits = value < 0 ? 0 : value > 34 ? 34 : value;
 
     else return tcmi_fail(c, TCMI_E_ARG, "unknown option %s", key);
     return TCMI_OK;
@@ -380,6 +382,8 @@ int tcmi_ctx_stat(tcmi_ctx *c, const char *key, int64_t *value)
     else if (!std::strcmp(key, "one_sync_retried")) { *value = c->stat_one_sync_retried; for (const tcmi_ctx *h : c->helpers) *value += h->stat_one_sync_retried; }
     else if (!std::strcmp(key, "decode_batched")) { *value = c->stat_decode_batched; for (const tcmi_ctx *h : c->helpers) *value += h->stat_decode_batched; }
     else if (!std::strcmp(key, "split_sub_taken")) *value = c->stat_split_sub;
+    else if (!std::strcmp(key, "indel_table_grown")) *value = c->stat_indel_grown;
+    else if (!std::strcmp(key, "indel_hash_retried")) *value = c->stat_indel_retried;
     else if (!std::strcmp(key, "h2d_piped")) { *value = c->stat_h2d_piped; for (const tcmi_ctx *h : c->helpers) *value += h->stat_h2d_piped; }
     else if (!std::strcmp(key, "one_sync_last_decline_flags")) *value = c->stat_last_decline;
     else if (!std::strcmp(key, "compute_units")) *value = c->n_cu;

@@ -3,6 +3,8 @@
 #pragma once
 #include <cstdint>
 
+#include "indel_rule.h"
+
 namespace tcmi_cigar {
 
 // CIGAR operations (SAM spec §1.4: M 0, I 1, D 2, N 3, S 4, H 5, P 6, = 7, X 8)
@@ -46,6 +48,17 @@ inline int64_t indel_after(const uint32_t *cg, int64_t n, int64_t k)
 
 // ... its peek at the last reference base of op k: is an insertion reported there?
 inline bool ins_after(const uint32_t *cg, int64_t n, int64_t k) { return indel_after(cg, n, k) > 0; }
+
+// the insertion ins_after reports behind op k, base by base: f(query index) for every base of exactly the I ops indel_after adds up, in
+// CIGAR order (y: the query index behind op k) -> their number.  The host twin of the kernels' walk (indel_events.hip), over the one
+// iterator of indel_rule.h.
+template <class F> inline int64_t ins_bases(const uint32_t *cg, int64_t n, int64_t k, int64_t y, F f)
+{
+    tcmi_ins_iter it([cg](uint32_t j) { return cg[j]; }, (uint32_t)n, (uint32_t)k, y);
+    int64_t len = 0;
+    for (int64_t qi; (qi = it.next()) >= 0; ++len) f(qi);
+    return len;
+}
 
 // [H]*[S]* (M|=|X)+ [S]*[H]*  ->  query offset of the first aligned base, aligned length (at most max_span)
 inline bool aligned_shape(const uint32_t *cg, int64_t n, int64_t max_span, int64_t *y0, int64_t *len)

@@ -2,9 +2,11 @@
 // arena.  HOST side: is the stream still there (tally.hip's long reads, ins_entries.hip, the counting calls), grow-only scratch of a
 // context, and the driver of a COUNTING call — one kernel over the records, one lane per record, that turns a small input (a table, a
 // list of columns) into integer counters: tcmi_readset_amplicon_reads (amplicon_reads.hip), tcmi_readset_strand_counts
-// (strand_counts.hip), tcmi_readset_link_counts (link_counts.hip) — with the column check of the latter two.  DEVICE side, at the end:
-// the frame such a kernel holds around its counting rule — the workgroup's counters (CountFrame) and the walk over the records
-// (each_record).  Which record such a kernel counts: pack_device.h's kept_span; how its lanes are joined per counter: wave_join there.
+// (strand_counts.hip), tcmi_readset_link_counts (link_counts.hip) — with the column check of the latter two; tcmi_readset_indel_events
+// (indel_events.hip) keeps a driver of its own (a keyed table, attempts) on the same refusals, scratch and launch shape.  DEVICE side,
+// at the end: the frame such a kernel holds around its counting rule — the workgroup's counters (CountFrame) and the walk over the
+// records (each_record).  Which record such a kernel counts: pack_device.h's kept_span; how its lanes are joined per counter:
+// wave_join there.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -63,6 +65,23 @@ inline int tcmi_count_columns(tcmi_ctx *ctx, const char *what, int64_t n, const 
     return TCMI_OK;
 }
 
+// May a call count in the read set's record stream on this context?  TCMI_OK: yes; 1: there is nothing to count (no kept record: such a
+// set may hold no stream at all); < 0: refused, worded on ctx with `what` in front.  The refusals of every counting call, the indel
+// events' (indel_events.hip) included.
+inline int tcmi_stream_countable(tcmi_ctx *ctx, const tcmi_readset *rs, const char *what)
+{
+    if (rs->packed_on_device != 2)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the read set was not decoded on the device (flat arrays or the host reader): there is no record stream to count in", what);
+    if (rs->n_piled == 0) return 1;
+    if (rs->device != ctx->device)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the read set lives on device %d, this context on device %d", what, rs->device, ctx->device);
+    if (tcmi_stream_gone(ctx, rs) || !rs->d_rec_off)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the read set's decoded stream is no longer resident on this context (another upload happened on it)", what);
+    if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the context's contig layout changed since the read set was uploaded", what);
+    return TCMI_OK;
+}
+
 // One read set on its own context.  `in` (in_bytes, host) goes to the device, sums.size() counters of type T are zeroed behind it,
 //   launch(ctx, rs, src, d_in, d_cnt, grid)   enqueues the one kernel on ctx->stream (src: the resident stream with the read set's
 //                                             filter, floor and layout), here between the profiling brackets of `slot`,
@@ -72,15 +91,7 @@ template <class T, class Launch>
 int tcmi_stream_count(tcmi_ctx *ctx, const tcmi_readset *rs, const char *what, int slot, const void *in, size_t in_bytes, std::vector<int64_t> &sums, Launch launch)
 {
     const size_t cnt_bytes = sums.size() * sizeof(T);
-    if (rs->packed_on_device != 2)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the read set was not decoded on the device (flat arrays or the host reader): there is no record stream to count in", what);
-    if (rs->n_piled == 0) return TCMI_OK;                   // (no kept record: nothing to add; such a set may hold no stream at all)
-    if (rs->device != ctx->device)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the read set lives on device %d, this context on device %d", what, rs->device, ctx->device);
-    if (tcmi_stream_gone(ctx, rs) || !rs->d_rec_off)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the read set's decoded stream is no longer resident on this context (another upload happened on it)", what);
-    if (rs->n_lay && rs->lay_gen != ctx->lay_gen)
-        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the context's contig layout changed since the read set was uploaded", what);
+    if (const int rc = tcmi_stream_countable(ctx, rs, what)) return rc < 0 ? rc : TCMI_OK;
     TCMI_HIP(ctx, hipSetDevice(ctx->device));
     const size_t b_in = tcmi_align256(in_bytes), b_cnt = tcmi_align256(cnt_bytes);
     if (!tcmi_grow_dev(ctx, ctx->count_dev, ctx->count_dev_cap, b_in + b_cnt, 64u << 10))

@@ -1,6 +1,7 @@
 // stream_walk.h — DEVICE side (.hip files only) of the kernels that ask a kept record for its token at given columns of the count matrix's
-// axis, in ascending order: strand_counts.hip (the planes per strand) and link_counts.hip (the token classes of a record at two columns
-// together).  One copy of the per-record incremental CIGAR walk and of the count matrix's token rule restated for one column, so both
+// axis, in ascending order: strand_counts.hip (the planes per strand), link_counts.hip (the token classes of a record at two columns
+// together) and indel_events.hip (the insertion behind and the deletion that starts on a column: after token_at, w.k is the op that
+// holds the column).  One copy of the per-record incremental CIGAR walk and of the count matrix's token rule restated for one column, so both
 // kernels count exactly what tally_stream_kernel (tally.hip) counts.  Which record is kept and where it lies (kept_span), the primer
 // table's lookup (seg_find) and the leaves of the rule (base_plane, qual_at): pack_device.h.
 #pragma once

@@ -195,8 +195,9 @@ struct tcmi_ctx {
     char *tok_dev = nullptr, *tok_host = nullptr;
     size_t tok_dev_cap = 0, tok_host_cap = 0;
     // scratch that the counting calls over the record stream share (stream_count.h; tcmi_readset_amplicon_reads: the compiled table, the
-    // counters; tcmi_readset_strand_counts and tcmi_readset_link_counts: the columns, the counters): device, grow-only; its host side is
-    // h_pin.  Every such call waits for the stream before it returns.
+    // counters; tcmi_readset_strand_counts and tcmi_readset_link_counts: the columns, the counters; tcmi_readset_indel_events: the columns,
+    // the totals, the keyed table, the event list and its text): device, grow-only; its host side is h_pin.  Every such call waits for
+    // the stream before it returns.
     char *count_dev = nullptr;
     size_t count_dev_cap = 0;
     // small read-backs of the cold path (block verdicts, packer totals) land in pinned memory of the context: a copy into pageable
@@ -215,7 +216,11 @@ struct tcmi_ctx {
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
     int64_t stat_split_sub = 0;      // tcmi_split_step calls whose range went through sub-ranges
     int64_t stat_decode_batched = 0; // files the device decoder took in batches of blocks (tcmi_ctx_stat "decode_batched")
-    int32_t split_tail[6] = {0, 0, 0, 0, 0, 0};   // tcmi_split_step: this rank's slot of the range table on its way to the device (the copy is asynchronous)
+    // tcmi_readset_indel_events (indel_events.hip): log2 of the device table's first size and the bits of an insertion's hash that are
+    // kept (options "indel_slots", "indel_hash_bits", for tests); attempts that started over with a larger table / the next seed
+    int indel_slots = 15, indel_hash_bits = 34;
+    int64_t stat_indel_grown = 0, stat_indel_retried = 0;
+    int32_t split_tail[6] ={0, 0, 0, 0, 0, 0};   // tcmi_split_step: this rank's slot of the range table on its way to the device (the copy is asynchronous)
     uint32_t rec_bytes_seen = 0;     // mean record size of the last file this context decoded (sizes the next file's arrays when the file's own first blocks say nothing)
     int64_t decode_token_mb = 4096;  // bam_device.hip decode_enqueue: the token scratch's size; files that need more are decoded in batches of blocks
     int prefix_kernels = 0;          // pk_index / pk_place take the sums in front of a block from scan launches: 0 = from 16 384 blocks on, 1 = always, -1 = never

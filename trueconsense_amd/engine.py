@@ -216,6 +216,67 @@ def variants_links_text(records, links, k, region, ref, pos_offset=0, min_depth=
     return buf.raw[:ln.value].decode("latin-1")
 
 
+# struct tcmi_indel_event / tcmi_indel_totals: one insertion or deletion of the records at a column, the events per column (--indel-table)
+INDEL_EVENT_DTYPE = np.dtype([("pos", np.int32), ("kind", np.int32), ("len", np.int32), ("count", np.int32), ("cov", np.int32),
+                              ("reserved", np.int32), ("text_off", np.int64)])
+INDEL_TOTALS_DTYPE = np.dtype([("pos", np.int32), ("ins_total", np.int32), ("del_total", np.int32), ("reserved", np.int32)])
+INDELS_HEADER = "REGION\tPOS\tTYPE\tLEN\tSEQ\tCOUNT\tTOTAL_DP\tFREQ\n"
+INDEL_INS, INDEL_DEL = 1, 2
+INDEL_LDS = 512                  # TCMI_INDEL_LDS: columns whose list and totals the count kernel stages in LDS
+INDEL_MAX_COLS = 1 << 20         # the columns of one tcmi_readset_indel_events call
+INDEL_LETTERS = "=ACMGRSVTWYHKDBN"
+
+
+def indel_hash(seed, nibbles, bits=34):
+    """tcmi_indel_hash (HOST): the `bits` (0..34) low bits of the hash the device table keys an insertion of these SEQ nibbles (codes
+    0..15) with under `seed`"""
+    nib = np.ascontiguousarray(nibbles, np.uint8).reshape(-1)
+    return int(lib().tcmi_indel_hash(int(seed), len(nib), ptr(nib) if len(nib) else None, int(bits)))
+
+
+def indel_passes(count, cov, min_af="0.03", min_alt_depth=1, min_depth=10):
+    """tcmi_indel_passes (HOST, exact integers): is an event of `count` records on a column of coverage `cov` reported — cov >=
+    max(min_depth, 1), count >= min_alt_depth, count / cov >= min_af (a tie is in): the variant table's rule"""
+    num, den = min_af_fraction(min_af)
+    rc = lib().tcmi_indel_passes(int(count), int(cov), num, den, int(min_alt_depth), int(min_depth))
+    if rc < 0:
+        raise _ffi.TcmiError(rc, "tcmi_indel_passes: a negative count or coverage, min_alt_depth < 1, min_depth < 0 or min_af outside 0..1")
+    return bool(rc)
+
+
+def indels_text(events, text, totals, records, region, ref, pos_offset=0):
+    """--indel-table's rows (tcmi_indels_text; HOST): REGION, POS, TYPE (INS / DEL), LEN, SEQ (the inserted bases / the deleted
+    reference bases), COUNT, TOTAL_DP, FREQ.  events, text, totals: Context.indel_events at the distinct positions of the '*' and '+'
+    rows among the variant `records`.  -> str, without the header line (INDELS_HEADER).  TcmiError(E_ARG) when the totals do not belong
+    to the records, the insertions do not add up to a '+' row's depth, or an event does not fit."""
+    events = np.ascontiguousarray(events, INDEL_EVENT_DTYPE)
+    totals = np.ascontiguousarray(totals, INDEL_TOTALS_DTYPE)
+    records = np.ascontiguousarray(records, VARIANT_DTYPE)
+    text = bytes(text) if not isinstance(text, str) else text.encode("latin-1")
+    ref = _ref_bytes(ref)
+    args = (ptr(events) if len(events) else None, len(events), text if len(text) else None, len(text), ptr(totals) if len(totals) else None, len(totals),
+            ptr(records) if len(records) else None, len(records), str(region).encode(), int(pos_offset), ptr(ref) if len(ref) else None, len(ref))
+    ln = C.c_int64(0)
+    buf = None
+    rc = lib().tcmi_indels_text(*args, None, 0, C.byref(ln))                # the sizing call
+    if not rc:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib().tcmi_indels_text(*args, C.cast(buf, C.c_void_p), ln.value, C.byref(ln))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_indels_text: the totals do not belong to the records' '*' and '+' rows, the insertions do not add up "
+                                 "to a '+' row, or an event does not fit the records, the text, the reference or the order")
+    return buf.raw[:ln.value].decode("latin-1")
+
+
+def indel_columns(records):
+    """the columns --indel-table asks about and their coverage: the distinct positions of the '*' and '+' rows of variant `records`
+    -> (int64 columns ascending, int32 coverage)"""
+    records = np.ascontiguousarray(records, VARIANT_DTYPE)
+    mine = records[(records["allele"] == 5) | (records["allele"] == 6)]
+    cols, first = np.unique(mine["pos"].astype(np.int64), return_index=True)
+    return cols, np.ascontiguousarray(mine["cov"][first], np.int32)
+
+
 def _grab(vp, dtype, n):
     """n items of dtype at address vp (memory the library owns) -> a fresh numpy array."""
     out = np.empty(n, dtype)
@@ -537,6 +598,52 @@ class Context:
         """link_counts at the distinct positions of variant `records` -> a structured array (LINK_DTYPE), empty without records"""
         cols = np.unique(np.ascontiguousarray(records, VARIANT_DTYPE)["pos"].astype(np.int64))
         return self.link_counts(readset, cols, k) if len(cols) else np.zeros(0, LINK_DTYPE)
+
+    def _indel_events(self, readset, cols, cov, num, den, min_alt_depth, min_depth):
+        """one tcmi_readset_indel_events call of at most 2^20 columns, with room for what a file usually has; a call that says it
+        found more is made again with room for exactly that"""
+        totals = np.zeros(len(cols), INDEL_TOTALS_DTYPE)
+        n, tl = C.c_int64(0), C.c_int64(0)
+        head = (self.handle, readset.handle, len(cols), ptr(cols), ptr(cov), num, den, int(min_alt_depth), int(min_depth))
+        cap, tcap = 4096, 65536
+        for _ in range(2):
+            events = np.zeros(cap, INDEL_EVENT_DTYPE)
+            text = C.create_string_buffer(tcap)
+            rc = lib().tcmi_readset_indel_events(*head, ptr(events), cap, C.byref(n), C.cast(text, C.c_void_p), tcap, C.byref(tl), ptr(totals))
+            if rc != _ffi.E_ARG or (n.value <= cap and tl.value <= tcap):
+                break
+            cap, tcap = max(n.value, 1), max(tl.value, 1)
+        check(rc, self.handle)
+        return events[:n.value].copy(), text.raw[:tl.value], totals
+
+    def indel_events(self, readset, cols, cov, min_af="0.03", min_alt_depth=1, min_depth=10):
+        """The insertions and deletions of the kept records at `cols` (tcmi_readset_indel_events): cols strictly ascending on the
+        count matrix's axis, cov the matrix's coverage there -> (events, text, totals): events a structured array
+        (INDEL_EVENT_DTYPE) in the order (pos, kind, len, bases) — kind 1 an insertion behind the base at pos, its bases
+        text[text_off : text_off + len], kind 2 a deletion whose first base is pos — of those that pass the variant table's rule; text
+        bytes; totals (INDEL_TOTALS_DTYPE) the events of each kind per column, reported or not: ins_total is the matrix's I plane.
+        Large queries are taken in pieces of 2^20 columns.  The read set must have been decoded on the device and its stream must
+        still be resident on this context (no other upload since), else TcmiError(E_UNSUPPORTED)."""
+        cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
+        cov = np.ascontiguousarray(cov, np.int32).reshape(-1)
+        if len(cols) != len(cov):
+            raise ValueError("indel_events: %d columns, %d coverages" % (len(cols), len(cov)))
+        num, den = min_af_fraction(min_af)
+        ev, tx, tot, off = [], [], [], 0
+        for k in range(0, len(cols), INDEL_MAX_COLS):
+            e, t, s = self._indel_events(readset, cols[k:k + INDEL_MAX_COLS], cov[k:k + INDEL_MAX_COLS], num, den, min_alt_depth, min_depth)
+            e = e.copy()
+            e["text_off"][e["kind"] == INDEL_INS] += off
+            off += len(t)
+            ev.append(e), tx.append(t), tot.append(s)
+        if not ev:
+            return np.zeros(0, INDEL_EVENT_DTYPE), b"", np.zeros(0, INDEL_TOTALS_DTYPE)
+        return np.concatenate(ev), b"".join(tx), np.concatenate(tot)
+
+    def indel_events_of(self, readset, records, **rule):
+        """indel_events at the distinct positions of the '*' and '+' rows of variant `records`, with their coverage"""
+        cols, cov = indel_columns(records)
+        return self.indel_events(readset, cols, cov, **rule)
 
     def set_layout(self, shift=None, slot_len=None):
         """Contig layout (tcmi_ctx_set_layout): reference t's reads pile up at pos + shift[t] (< 0: dropped), in a slot of
