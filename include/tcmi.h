@@ -536,6 +536,56 @@ int  tcmi_indel_passes(int32_t count, int32_t cov, int64_t num, int64_t den, int
 int  tcmi_indels_text(const tcmi_indel_event *events, int64_t n, const char *text, int64_t text_len, const tcmi_indel_totals *totals,
                       int64_t n_cols, const tcmi_variant *records, int64_t n_records, const char *region, int64_t pos_offset,
                       const uint8_t *ref, int64_t n_ref, char *out, int64_t cap, int64_t *len);
+/* ---- allele evidence (additive: `ivar variants`' REF_QUAL / ALT_QUAL, and the mapping-quality and read-position annotations that
+ *      lofreq and GATK filter on; the reference has nothing like it) ------------------------------------------------------------------
+ * Per queried column and plane of the count matrix: how many tokens, and the sums of their base quality, of their records' MAPQ and of
+ * their distance to the nearer end of the read's aligned part — counted by one HIP kernel over the inflated record stream a
+ * device-decoded read set left resident on its context.  The count matrix and the packed read set keep neither QUAL per token, nor MAPQ,
+ * nor the query index: the evidence lives in the records only.  All arithmetic is integer; the sums are the same in every run.
+ *   columns        c_0 < c_1 < ... < c_{n-1} on the count matrix's axis (under a contig layout: shifted by the contig's slot), each in
+ *                  [0, 2^29), n in 1..2^20.
+ *   token          the count matrix's, as for tcmi_readset_strand_counts: a token counts here exactly when it counts in the matrix,
+ *                  under the read filter, the base-quality floor, the primer table and the contig layout the read set REMEMBERS.  For
+ *                  every plane k (TCMI_COV..TCMI_I) the token adds to, four counters of (c_i, k) grow:
+ *   n[k]           by 1: the count matrix at (k, c_i).
+ *   qual[k]        by the token's quality byte as the file stores it: the byte the floor tests, at query index qi — of a matched base
+ *                  its own, of a D / N token the index at which its op starts; an index at or beyond l_seq gives 0, a record without
+ *                  QUAL its stored 0xFF.  The byte is read whatever the floor.
+ *   mapq[k]        by the record's MAPQ as stored (255 included).
+ *   dist[k]        by min(255, max(0, min(qi - a0, a1 - 1 - qi))): [a0, a1) is the aligned part of the query — a0 the total length of the
+ *                  S ops in front of the first op that is neither S nor H, a1 the sum of all query-consuming ops minus the S ops behind
+ *                  the last op that is neither S nor H.  Both come from the CIGAR alone: l_seq plays no part, and neither does the
+ *                  primer table (the distance is to the read's end, not to the mask's).  A D op that starts at a1 gives 0; the cap
+ *                  keeps every token's value in a byte (255 bases from either end is as far as any filter asks).
+ *   invariant      n[k] equals the count matrix a step tallies from the read set, at (k, c_i), on all seven planes.
+ *   tcmi_readset_evidence_counts   records: host, room for n; pos = c_i.  Residency, sub-ranges, an empty read set (zeros, TCMI_OK),
+ *                  the wait and the scratch as for tcmi_readset_strand_counts.
+ *   tcmi_evidence_verdict   HOST, GPU-free, exact integers (128-bit products).  A bit set: 1 LOWQ iff qual < min_qual * n, 2 LOWMQ iff
+ *                  mapq < min_mapq * n, 4 END iff dist < min_dist * n — the mean lies below the threshold.  A threshold of 0 switches
+ *                  its bit off; n = 0 gives 0.  TCMI_E_ARG for a negative count or sum and the range errors below.
+ *   tcmi_variants_evidence_text   HOST, re-entrant, no GPU: the writer of --variant-evidence's rows.  The first seven fields of a row are
+ *                  byte for byte tcmi_variants_text's for the record; behind them REF_QUAL ALT_QUAL REF_MAPQ ALT_MAPQ REF_ENDDIST
+ *                  ALT_ENDDIST — REF the plane of the upper-cased reference base (zeros when it is none of A, T, C, G), ALT the
+ *                  record's allele plane (X for '*' rows, I for '+' rows); each a mean sum / n cut to one decimal in integers,
+ *                  (10 * sum) / n printed as %lld.%lld, 0.0 when n = 0 — and EVIDENCE = PASS, or the failing names of the ALT allele
+ *                  in the order LOWQ, LOWMQ, END, joined by commas.  ev[0..n_cols): the counts at the records' distinct positions,
+ *                  ascending.  TCMI_E_ARG, and NOTHING written (*len = 0), when ev[j].pos is not the records' j-th distinct position
+ *                  (or n_cols is not their number), when n[allele] differs from a record's count or n[TCMI_COV] from its cov (the
+ *                  stream kernel and the matrix's disagree: no table), and when a sum is negative or above 255 * n.  Sizing call and
+ *                  *len as for tcmi_variants_text; a short buffer gets *len, TCMI_E_ARG and nothing written.  The header line (TCMI_VARIANTS_EVIDENCE_HEADER) is the caller's.
+ * TCMI_EVIDENCE_LDS: the columns whose list and [28] counters a workgroup stages in LDS as uint32 (14.5 KiB: eight workgroups per
+ * compute unit, as the launch shape asks); a longer list is searched, and counted, in memory — as is any query on a stream so long
+ * that 255 times the records one workgroup visits could pass 2^32 - 1.  The tests query on both sides of the edge.
+ * Range errors are TCMI_E_ARG: a threshold outside 0..255. */
+typedef struct tcmi_evidence_counts { int64_t qual[7], mapq[7], dist[7]; int32_t n[7]; int32_t pos; } tcmi_evidence_counts;   /* 200 bytes */
+#define TCMI_EVIDENCE_LDS 128
+#define TCMI_VARIANTS_EVIDENCE_HEADER "REGION\tPOS\tREF\tALT\tALT_DP\tTOTAL_DP\tALT_FREQ\tREF_QUAL\tALT_QUAL\tREF_MAPQ\tALT_MAPQ\tREF_ENDDIST\tALT_ENDDIST\tEVIDENCE\n"
+int  tcmi_readset_evidence_counts(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *cols /* host */,
+                                  tcmi_evidence_counts *records /* host, n */);
+int  tcmi_evidence_verdict(int64_t n, int64_t qual, int64_t mapq, int64_t dist, int32_t min_qual, int32_t min_mapq, int32_t min_dist);
+int  tcmi_variants_evidence_text(const tcmi_variant *records, int64_t n, const tcmi_evidence_counts *ev, int64_t n_cols, /* the records' distinct positions, ascending */
+                                 int32_t min_qual, int32_t min_mapq, int32_t min_dist, const char *region, int64_t pos_offset,
+                                 const uint8_t *ref, int64_t n_ref, char *text, int64_t cap, int64_t *len);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -558,7 +608,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_STRAND_COUNTS = 13 /* tcmi_readset_strand_counts' one launch */,
        TCMI_K_LINK_COUNTS = 14 /* tcmi_readset_link_counts' one launch */,
        TCMI_K_INDEL_EVENTS = 15 /* tcmi_readset_indel_events' launches (count, verify, gather) of one attempt as one bracket */,
-       TCMI_K_NKERNELS = 16 };
+       TCMI_K_EVIDENCE_COUNTS = 16 /* tcmi_readset_evidence_counts' one launch */,
+       TCMI_K_NKERNELS = 17 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);

@@ -17,7 +17,10 @@ counted on the device in the decoded record stream; not with --batch), the links
 records carry both alleles, one of them or neither, and the phase CIS / TRANS / MIXED / NONE / LOW; counted likewise; needs
 --variant-table; not with --batch or --index-override), the indel table --indel-table FILE (one row per insertion or deletion at the
 variant table's '+' and '*' positions, with its length, its bases and the records that carry it, under --min-af / --min-alt-depth /
---variant-min-depth; counted likewise; needs --variant-table; not with --batch, --index-override or -i --gpus N), and
+--variant-min-depth; counted likewise; needs --variant-table; not with --batch, --index-override or -i --gpus N), the evidence table
+--variant-evidence FILE [--evidence-min-qual Q] [--evidence-min-mapq Q] [--evidence-min-enddist N] (the variant table's rows with the
+mean base quality, mapping quality and distance to the read's end of the reference's and the allele's tokens, and EVIDENCE = PASS or
+LOWQ, LOWMQ, END; counted likewise; needs --variant-table; not with --batch, --index-override or -i --gpus N), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -187,6 +190,32 @@ def link_stats(text=""):
     return out
 
 
+def evidence_of(a):
+    """The parsed namespace's --variant-evidence settings as (file, keyword arguments of engine.variants_evidence_text), or None without
+    the flag."""
+    if getattr(a, "variant_evidence", None) is None:
+        return None
+    return a.variant_evidence, dict(min_qual=int(a.evidence_min_qual), min_mapq=int(a.evidence_min_mapq), min_enddist=int(a.evidence_min_enddist))
+
+
+def evidence_stats(text=""):
+    """the --stats counters of --variant-evidence's rows (no rows: zeros)"""
+    from .engine import EVIDENCE_NAMES
+    words = [ln.rsplit("\t", 1)[-1].split(",") for ln in text.splitlines()]
+    return {"variant_evidence_" + w.lower(): sum(w in row for row in words) for w in EVIDENCE_NAMES}
+
+
+def write_variant_evidence(path, parts, rule):
+    """--variant-evidence: the header line, then for every (records, their evidence counts, region, reference on the records' axis,
+    pos_offset) its rows.  Nothing is written when a part's counts do not add up to its records (TcmiError).  -> {"variant_evidence_lowq":
+    rows whose EVIDENCE names LOWQ, "_lowmq", "_end"}."""
+    from .engine import VARIANTS_EVIDENCE_HEADER, variants_evidence_text
+    text = "".join(variants_evidence_text(recs, ev, region, ref, off, **rule) for recs, ev, region, ref, off in parts)
+    with open(path, "w") as out:
+        out.write(VARIANTS_EVIDENCE_HEADER + text)
+    return evidence_stats(text)
+
+
 class StreamCounts:
     """What the command line counts behind the step, in the record stream the device decoder leaves resident: --amplicon-reads,
     --variant-strand and --variant-links of the parsed namespace (layout: amplicon_reads_of's).  False when none is asked for.  A
@@ -194,15 +223,18 @@ class StreamCounts:
     KEYS = ("amplicon_reads", "variant_strand", "variant_links")    # count's keys; the order of consensus_split_bamfile's extra parts
     # (--indel-table's "indel_events" is no such part: its lists have no fixed length, and -i --gpus N is refused with it)
     indels = None                                                   # --indel-table's file
+    # (nor is --variant-evidence's "variant_evidence": its sums would reduce like the strand counts, but the split's keywords are fixed)
+    evidence = None                                                 # --variant-evidence's (file, thresholds)
 
     def __init__(self, a, layout=None):
         self.areads, self.srule, self.links = amplicon_reads_of(a, layout), strand_of(a), links_of(a)
         self.indels = getattr(a, "indel_table", None)
-        self.lists_records = bool(self.srule or self.links or self.indels)      # must the step list the variant table's records?
+        self.evidence = evidence_of(a)
+        self.lists_records = bool(self.srule or self.links or self.indels or self.evidence)     # must the step list the variant table's records?
         self.variants = variants_of(a) if self.lists_records else None
         # the flag named when the file leaves the device path (indexing.device_readset's `need`)
         self.need = "--variant-strand" if self.srule else "--variant-links" if self.links else "--indel-table" if self.indels else \
-            "--amplicon-reads" if self.areads else None
+            "--variant-evidence" if self.evidence else "--amplicon-reads" if self.areads else None
 
     def __bool__(self):
         return self.need is not None
@@ -221,6 +253,8 @@ class StreamCounts:
             got["variant_links"] = ctx.link_counts_of(rs, records, self.links[1])
         if self.indels:
             got["indel_events"] = ctx.indel_events_of(rs, records, **self.variants)
+        if self.evidence:
+            got["variant_evidence"] = ctx.evidence_counts_of(rs, records)
         return got
 
     def split_kwargs(self, ref):
@@ -554,6 +588,20 @@ def GetArgs(givenargs):
                                                    "under --min-af / --min-alt-depth / --variant-min-depth, counted in the records the device\n"
                                                    "decoded; needs --variant-table and the device decoder; not with --batch, --index-override\n"
                                                    "or -i --gpus N")))
+    additive.append((("--variant-evidence",), dict(type=str, default=None, metavar="File",
+                                                   help="also write the variant table's rows with what says whether an allele can be trusted: REF_QUAL\n"
+                                                        "ALT_QUAL (mean base quality, ivar variants'), REF_MAPQ ALT_MAPQ (mean mapping quality of the\n"
+                                                        "records), REF_ENDDIST ALT_ENDDIST (mean distance to the nearer end of the read's aligned\n"
+                                                        "part, capped at 255) and EVIDENCE = PASS or LOWQ, LOWMQ, END, counted in the records the\n"
+                                                        "device decoded; needs --variant-table and the device decoder; not with --batch,\n"
+                                                        "--index-override or -i --gpus N")))
+    additive.append((("--evidence-min-qual",), dict(type=_range_arg(parser, "--evidence-min-qual", 255), default=None, metavar="Q",
+                                                    help="EVIDENCE names LOWQ when the allele's mean base quality is below Q; 0: off (default 20)")))
+    additive.append((("--evidence-min-mapq",), dict(type=_range_arg(parser, "--evidence-min-mapq", 255), default=None, metavar="Q",
+                                                    help="EVIDENCE names LOWMQ when the mean MAPQ of the allele's records is below Q; 0: off (default 20)")))
+    additive.append((("--evidence-min-enddist",), dict(type=_range_arg(parser, "--evidence-min-enddist", 255), default=None, metavar="N",
+                                                       help="EVIDENCE names END when the allele sits on average fewer than N bases from its reads'\n"
+                                                            "nearer end; 0: off (default 5)")))
     additive.append((("--amplicon-table",), dict(type=str, default=None, metavar="File",
                                                  help="also write per amplicon of the scheme the depth of its columns, tab-separated: SAMPLE REGION\n"
                                                       "AMPLICON POOL START END LEN MEAN MEDIAN MIN MIN_POS BELOW (BELOW: columns under -cov), from\n"
@@ -588,14 +636,17 @@ def GetArgs(givenargs):
     # the flags that count behind the step, with their dependant options: their refusals exit 1 with one line, nothing written
     for flag, on, deps in (("--variant-strand", a.variant_strand, ("strand_min_depth", "strand_ratio")),
                            ("--variant-links", a.variant_links is not None, ("link_neighbours", "link_min_depth", "link_ratio")),
-                           ("--indel-table", a.indel_table is not None, ())):
+                           ("--indel-table", a.indel_table is not None, ()),
+                           ("--variant-evidence", a.variant_evidence is not None, ("evidence_min_qual", "evidence_min_mapq", "evidence_min_enddist"))):
         names = " / ".join("--" + d.replace("_", "-") for d in deps)
         for bad, why in ((not on and any(getattr(a, d) is not None for d in deps), f"{names} need {flag}."),
                          (on and a.batch is not None, f"{flag} goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
                          (on and a.batch is None and a.variant_table is None, f"{flag} needs --variant-table."),
                          (on and a.index_override is not None, f"{flag} does not go with --index-override: the overridden matrix no longer equals the reads."),
                          (on and flag == "--indel-table" and a.batch is None and a.gpus and a.gpus > 1,
-                          f"{flag} does not go with -i --gpus N: the ranks' event lists would have to be merged on rank 0, which is not built.")):
+                          f"{flag} does not go with -i --gpus N: the ranks' event lists would have to be merged on rank 0, which is not built."),
+                         (on and flag == "--variant-evidence" and a.batch is None and a.gpus and a.gpus > 1,
+                          f"{flag} does not go with -i --gpus N: the ranks' sums would have to be added up on rank 0, which is not built.")):
             if bad:
                 print(f"{why} Exiting...")
                 sys.exit(1)
@@ -620,7 +671,7 @@ def GetArgs(givenargs):
     if a.amplicon_table is not None or a.amplicon_reads is not None:
         a.amplicon_scheme = a.primers if a.amplicon_scheme is None else a.amplicon_scheme
     for key, default in dict(strand_min_depth=10, strand_ratio=Fraction(1, 10), link_neighbours=2, link_min_depth=10, link_ratio=Fraction(9, 10),
-                             amplicon_reads_slack=5, amplicon_region="insert", min_af=Fraction(3, 100), min_alt_depth=1, variant_min_depth=10).items():
+                             amplicon_reads_slack=5, amplicon_region="insert", evidence_min_qual=20, evidence_min_mapq=20, evidence_min_enddist=5, min_af=Fraction(3, 100), min_alt_depth=1, variant_min_depth=10).items():
         if getattr(a, key) is None:                 # (None until here: the checks above ask whether the option was given)
             setattr(a, key, default)
     return a
@@ -904,9 +955,11 @@ def _single_sample(a, flt, t):
         refID, refseq = fasta.read_first_record(a.reference)
         recs = _state.default_context().variants(indexDict.counts, refseq, **variants_of(a))
         vparts = [(recs, got.get("variant_strand"), got.get("variant_links"), refID, refseq, 0)]
-    vstats = write_variant_tables(a, vparts, want)
+    vstats = dict(write_variant_tables(a, vparts, want), **evidence_stats())
     if want.indels:
         write_indel_table(want.indels, [(recs, got["indel_events"], refID, refseq, 0)])
+    if want.evidence:
+        vstats.update(write_variant_evidence(want.evidence[0], [(recs, got["variant_evidence"], refID, refseq, 0)], want.evidence[1]))
 
     amps, n_below = amplicons_of(a), 0
     if amps:                                        # likewise: the matrix behind the read filter, --min-baseq, --primers and --index-override

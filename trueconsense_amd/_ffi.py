@@ -18,7 +18,7 @@ TCMI_OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_FORMAT, E_IO, E_KEYERROR, E_ZERODIV, E_UNSUPPORTED = range(-1, -10, -1)
 COLS = ("coverage", "A", "T", "C", "G", "X", "I")        # indexing.py:134
 F_LOWCOV, F_PRIMX, F_MINDEL, F_INSCAND, F_COVGT, F_COVZERO, F_AMBIG = 1, 2, 4, 8, 16, 32, 64
-K_TALLY, K_CALL, K_ZERO, K_TALLY_GENERAL, K_PACK_CLASSIFY, K_PACK, K_INFLATE, K_RECORDS, K_CRC, K_INFLATE_COPY, K_VARIANTS, K_INTERVALS, K_AMPLICON_READS, K_STRAND_COUNTS, K_LINK_COUNTS, K_INDEL_EVENTS = range(16)
+K_TALLY, K_CALL, K_ZERO, K_TALLY_GENERAL, K_PACK_CLASSIFY, K_PACK, K_INFLATE, K_RECORDS, K_CRC, K_INFLATE_COPY, K_VARIANTS, K_INTERVALS, K_AMPLICON_READS, K_STRAND_COUNTS, K_LINK_COUNTS, K_INDEL_EVENTS, K_EVIDENCE_COUNTS = range(17)
 
 
 class TcmiError(RuntimeError):
@@ -85,6 +85,9 @@ _SIGS = {
     "tcmi_indel_hash": (C.c_uint64, [_u32, _i32, _vp, _i32]),
     "tcmi_indel_passes": (_int, [_i32, _i32, _i64, _i64, _i32, _i32]),
     "tcmi_indels_text": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, C.c_char_p, _i64, _vp, _i64, _vp, _i64, _P(_i64)]),
+    "tcmi_readset_evidence_counts": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "tcmi_evidence_verdict": (_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32]),
+    "tcmi_variants_evidence_text": (_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, C.c_char_p, _i64, _vp, _i64, _vp, _i64, _P(_i64)]),
     "tcmi_profile_enable": (_int, [_vp, _int]),
     "tcmi_profile_reset": (_int, [_vp]),
     "tcmi_profile_get": (_int, [_vp, _int, _P(C.c_double), _P(_i64)]),

@@ -184,8 +184,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (StreamCounts, amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of, write_amplicon_reads,
-                               write_amplicon_table, write_indel_table, write_variant_tables)
+    from .TrueConsense import (StreamCounts, amplicon_intervals, amplicons_of, evidence_stats, primers_of, read_filter_of, variants_of, write_amplicon_reads,
+                               write_amplicon_table, write_indel_table, write_variant_evidence, write_variant_tables)
     flt, seen, got = read_filter_of(a), {}, {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -269,7 +269,7 @@ def run(a):
     if a.depth_of_coverage is not None:
         with open(a.depth_of_coverage, "w") as out:
             out.write("".join(doc))
-    vparts, iparts = [], []                         # one file, the contigs in axis order; rows carry the contig's name and its own positions
+    vparts, iparts, eparts = [], [], []             # one file, the contigs in axis order; rows carry the contig's name and its own positions
     for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]) if table is not None else ():
         # (each contig's rows with the strand and link counts of its own columns: no pair across two contigs)
         mine = [None if x is None else x[(x[key] >= s) & (x[key] < s + len(seq))] for x, key in ((table, "pos"), (strand, "pos"), (links, "a"))]
@@ -278,9 +278,15 @@ def run(a):
             events, text, totals = got["indel_events"]
             found = (events[(events["pos"] >= s) & (events["pos"] < s + len(seq))], text, totals[(totals["pos"] >= s) & (totals["pos"] < s + len(seq))])
             iparts.append((mine[0], found, rid, axis_ref[:s + len(seq)], s))
+        if want.evidence:                           # (... and the evidence counts of its own columns)
+            ev = got["variant_evidence"]
+            eparts.append((mine[0], ev[(ev["pos"] >= s) & (ev["pos"] < s + len(seq))], rid, axis_ref[:s + len(seq)], s))
     seen.update(write_variant_tables(a, vparts, want))
     if want.indels:
         write_indel_table(want.indels, iparts)
+    seen.update(evidence_stats())
+    if want.evidence:
+        seen.update(write_variant_evidence(want.evidence[0], eparts, want.evidence[1]))
     if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
         write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
     if want.areads:                                 # one file: REGION is each amplicon's contig

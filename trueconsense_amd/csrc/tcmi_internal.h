@@ -196,7 +196,7 @@ struct tcmi_ctx {
     size_t tok_dev_cap = 0, tok_host_cap = 0;
     // scratch that the counting calls over the record stream share (stream_count.h; tcmi_readset_amplicon_reads: the compiled table, the
     // counters; tcmi_readset_strand_counts and tcmi_readset_link_counts: the columns, the counters; tcmi_readset_indel_events: the columns,
-    // the totals, the keyed table, the event list and its text): device, grow-only; its host side is h_pin.  Every such call waits for
+    // the totals, the keyed table, the event list and its text; tcmi_readset_evidence_counts: the columns, the counters): device, grow-only; its host side is h_pin.  Every such call waits for
     // the stream before it returns.
     char *count_dev = nullptr;
     size_t count_dev_cap = 0;

@@ -171,6 +171,48 @@ def variants_strand_text(records, strand, region, ref, pos_offset=0, min_strand_
     return buf.raw[:ln.value].decode("latin-1")
 
 
+# struct tcmi_evidence_counts: per plane of the count matrix at one column the tokens and the sums of their base quality, their records'
+# MAPQ and their distance to the read's nearer end (--variant-evidence)
+EVIDENCE_DTYPE = np.dtype([("qual", np.int64, (7,)), ("mapq", np.int64, (7,)), ("dist", np.int64, (7,)), ("n", np.int32, (7,)), ("pos", np.int32)])
+VARIANTS_EVIDENCE_HEADER = ("REGION\tPOS\tREF\tALT\tALT_DP\tTOTAL_DP\tALT_FREQ\tREF_QUAL\tALT_QUAL\tREF_MAPQ\tALT_MAPQ\tREF_ENDDIST\tALT_ENDDIST\t"
+                            "EVIDENCE\n")
+EVIDENCE_LDS = 128               # TCMI_EVIDENCE_LDS: columns whose list and counters the kernel stages in LDS
+EVIDENCE_MAX_COLS = 1 << 20      # the columns of one tcmi_readset_evidence_counts call
+EVIDENCE_LOWQ, EVIDENCE_LOWMQ, EVIDENCE_END = 1, 2, 4
+EVIDENCE_NAMES = ("LOWQ", "LOWMQ", "END")
+
+
+def evidence_verdict(n, qual, mapq, dist, min_qual=20, min_mapq=20, min_enddist=5):
+    """tcmi_evidence_verdict (HOST, exact integers) -> a bit set: 1 LOWQ iff qual < min_qual * n, 2 LOWMQ iff mapq < min_mapq * n, 4 END
+    iff dist < min_enddist * n (the mean of the n tokens lies below the threshold); a threshold of 0 switches its bit off."""
+    rc = lib().tcmi_evidence_verdict(int(n), int(qual), int(mapq), int(dist), int(min_qual), int(min_mapq), int(min_enddist))
+    if rc < 0:
+        raise _ffi.TcmiError(rc, "tcmi_evidence_verdict: a negative count or sum, or a threshold outside 0..255")
+    return rc
+
+
+def variants_evidence_text(records, evidence, region, ref, pos_offset=0, min_qual=20, min_mapq=20, min_enddist=5):
+    """--variant-evidence's rows for `records` (tcmi_variants_evidence_text; HOST): variants_text's seven fields, then REF_QUAL, ALT_QUAL,
+    REF_MAPQ, ALT_MAPQ, REF_ENDDIST, ALT_ENDDIST (means cut to one decimal) and EVIDENCE = PASS or LOWQ, LOWMQ, END joined by commas.
+    evidence: Context.evidence_counts at the records' distinct positions, ascending.  -> str, without the header line
+    (VARIANTS_EVIDENCE_HEADER).  TcmiError(E_ARG) when the counts do not belong to the records or do not add up to them."""
+    records = np.ascontiguousarray(records, VARIANT_DTYPE)
+    evidence = np.ascontiguousarray(evidence, EVIDENCE_DTYPE)
+    ref = _ref_bytes(ref)
+    args = (ptr(records) if len(records) else None, len(records), ptr(evidence) if len(evidence) else None, len(evidence), int(min_qual), int(min_mapq),
+            int(min_enddist), str(region).encode(), int(pos_offset), ptr(ref) if len(ref) else None, len(ref))
+    ln = C.c_int64(0)
+    buf = None
+    rc = lib().tcmi_variants_evidence_text(*args, None, 0, C.byref(ln))     # the sizing call
+    if not rc:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib().tcmi_variants_evidence_text(*args, C.cast(buf, C.c_void_p), ln.value, C.byref(ln))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_variants_evidence_text: the evidence counts do not belong to the records or do not add up to them "
+                                 "(or a record does not fit the reference, the offset or the thresholds)")
+    return buf.raw[:ln.value].decode("latin-1")
+
+
 # struct tcmi_link_counts: the kept records by token class at the two columns of a pair (--variant-links)
 LINK_DTYPE = np.dtype([("j", np.int32, (7, 7)), ("a", np.int32), ("b", np.int32), ("reserved", np.int32)])
 VARIANTS_LINKS_HEADER = "REGION\tPOS_A\tREF_A\tALT_A\tPOS_B\tREF_B\tALT_B\tSPAN\tBOTH\tONLY_A\tONLY_B\tNEITHER\tPHASE\n"
@@ -580,6 +622,27 @@ class Context:
         cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
         parts = [self.strand_counts(readset, cols[k:k + STRAND_MAX_COLS]) for k in range(0, len(cols), STRAND_MAX_COLS)]
         return np.concatenate(parts) if parts else np.zeros(0, STRAND_DTYPE)
+
+    def evidence_counts(self, readset, cols):
+        """Per plane of the count matrix at `cols` the tokens and the sums of their base quality, their records' MAPQ and their
+        distance to the nearer end of the read's aligned part, capped at 255 (tcmi_readset_evidence_counts): cols strictly ascending
+        on the count matrix's axis, 1..2^20 of them -> a structured array (EVIDENCE_DTYPE): qual, mapq, dist (int64) and n as [n, 7]
+        in plane order, pos; n is the matrix a step tallies from the read set.  The read set must have been decoded on the device and
+        its stream must still be resident on this context (no other upload since), else TcmiError(E_UNSUPPORTED)."""
+        cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
+        out = np.zeros(len(cols), EVIDENCE_DTYPE)
+        check(lib().tcmi_readset_evidence_counts(self.handle, readset.handle, len(cols), ptr(cols) if len(cols) else None, ptr(out) if len(cols) else None),
+              self.handle)
+        return out
+
+    def evidence_counts_of(self, readset, records=None, cols=None):
+        """evidence_counts at the distinct positions of variant `records` (or at `cols`, ascending), in pieces of 2^20 columns -> a
+        structured array (EVIDENCE_DTYPE), empty without columns"""
+        if cols is None:
+            cols = np.unique(np.ascontiguousarray(records, VARIANT_DTYPE)["pos"].astype(np.int64))
+        cols = np.ascontiguousarray(cols, np.int64).reshape(-1)
+        parts = [self.evidence_counts(readset, cols[k:k + EVIDENCE_MAX_COLS]) for k in range(0, len(cols), EVIDENCE_MAX_COLS)]
+        return np.concatenate(parts) if parts else np.zeros(0, EVIDENCE_DTYPE)
 
     def link_counts(self, readset, cols, k):
         """Joint token classes of the kept records at pairs of nearby columns (tcmi_readset_link_counts): cols strictly ascending on
