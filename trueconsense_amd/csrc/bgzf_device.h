@@ -27,6 +27,7 @@
 // Bit / byte work, bound by instruction issue and the LDS pipe, not by HBM and not a contraction: no MFMA.
 #pragma once
 #include "bgzf_host.h"          // BlockDesc, the blocks' status words ST_*
+#include "huffman_rule.h"       // limits, slots and entries of a canonical code
 #include "tcmi_internal.h"
 
 namespace {
@@ -79,114 +80,131 @@ __device__ __forceinline__ uint32_t wave_scan_max(uint32_t v)
 }
 
 // Root-table entries (32 bits): code length in bits 0-3 (0: not in the root table — a longer code or none), kind in bits 8-10;
-// a literal in bits 16-23; a distance: extra bits in bits 4-7, base in bits 16-31; a length: see make_entry.  The hot loop needs
-// no arithmetic on symbols.
-constexpr uint32_t E_LIT = 1u << 8, E_BASE = 1u << 9, E_EOB = 1u << 10;
-enum { K_LITLEN = 0, K_DIST = 1, K_CODELEN = 2 };
+// a literal in bits 16-23; a distance: extra bits in bits 4-7, base in bits 16-31; a length: see tcmi_huff_entry (huffman_rule.h).
+// The hot loop needs no arithmetic on symbols.
+constexpr uint32_t E_LIT = TCMI_HUFF_E_LIT, E_BASE = TCMI_HUFF_E_BASE, E_EOB = TCMI_HUFF_E_EOB;
+enum { K_LITLEN = TCMI_HUFF_LITLEN, K_DIST = TCMI_HUFF_DIST, K_CODELEN = TCMI_HUFF_CODELEN };
 
 typedef uint32_t tab_t;             // (16-bit entries with base / extra bits computed per symbol: half the table LDS, measured slower)
 
-__device__ inline uint32_t make_entry(int kind, int sym, int nbits)
+__device__ inline uint32_t make_entry(int kind, int sym, int nbits) { return tcmi_huff_entry(kind, sym, nbits); }
+
+// an inclusive sum over each row of 16 lanes (the per-length counters live in lanes 0 .. 15)
+__device__ __forceinline__ uint32_t row_scan_add(uint32_t v)
 {
-    if (sym < 0) return 0u;
-    if (kind == K_CODELEN) return (uint32_t)nbits | ((uint32_t)sym << 16);
-    if (kind == K_LITLEN) {
-        if (sym < 256) return (uint32_t)nbits | E_LIT | ((uint32_t)sym << 16);
-        if (sym == 256) return (uint32_t)nbits | E_EOB;
-        const int s = sym - 257;
-        if (s > 28) return 0u;                                  // 286, 287: not a symbol
-        int eb = 0, base = 3 + s;
-        if (s == 28) base = 258;
-        else if (s >= 8) { eb = (s >> 2) - 1; base = 3 + ((4 + (s & 3)) << eb); }
-        // a LENGTH entry is laid out for the ISA loop: extra-bit count in bits 16-19 (with the code length in bits 0-3 that is an
-        // s_bfe_u32 operand: entry & 0x000F000F), code + extra bits in bits 11-15, base length in bits 20-28
-        return (uint32_t)nbits | ((uint32_t)(nbits + eb) << 11) | E_BASE | ((uint32_t)eb << 16) | ((uint32_t)base << 20);
-    }
-    if (sym > 29) return 0u;                                    // 30, 31: not a distance
-    int eb = 0, base = 1 + sym;
-    if (sym >= 4) { eb = (sym >> 1) - 1; base = 1 + ((2 + (sym & 1)) << eb); }
-    return (uint32_t)nbits | ((uint32_t)eb << 4) | E_BASE | ((uint32_t)base << 16);
+    v += dpp_shift<0x111, 0xF>(v);
+    v += dpp_shift<0x112, 0xF>(v);
+    v += dpp_shift<0x114, 0xF>(v);
+    v += dpp_shift<0x118, 0xF>(v);
+    return v;
 }
 
-// lens[0 .. n) -> cnt[1 .. 15], canonically ordered symbols, and the root table.  Returns false for an over-subscribed code.
-// The kernel is bound by instruction issue, and a quarter of its instructions were spent here: so the per-length counters,
-// offsets and first codes live in scalar registers (both loops over the 15 lengths are unrolled: the indices are constants),
-// no read-modify-write goes through LDS, and a table slot is decoded by nine compare-and-select steps against those scalars
-// instead of a bit-by-bit walk with an LDS read per bit.  MAXG: groups of 64 symbols (5 for the 286 literal/length codes).
+// lens[0 .. n) -> cnt[1 .. 15], the canonically ordered symbols sym[] with their ready table entries ent[] beside them, and the root
+// table.  Returns false for an over-subscribed code.  huffman_rule.h states the rule; tests/huffman_table_main.cpp holds it against a
+// bit-by-bit decoder.  The kernel is bound by instruction issue, so what counts here is instructions:
+//   the rank    a symbol's place among those of its length.  Per group of 64 symbols, four ballots — one per bit of the length — give
+//               every lane the mask of the lanes whose length equals ITS OWN (bit set: the ballot, else its complement; the four
+//               ANDed): mbcnt of that mask is the lane's rank inside the group, its popcount the group's count for that length.  The
+//               counts of the groups in front come from a 16-entry LDS table that every group reads at its own lengths and then
+//               raises (lanes of one length write one value); after the last group the table IS the histogram.  (One ballot and one
+//               rank per (group, length) pair — 75 pairs for the literal/length code — was 1 832 static instructions.)
+//   the scan    lane len holds cnt[len]: a row scan gives off[len] (into the same 16-entry table: a symbol's slot is off[len] + its
+//               place), a second one over cnt[len] << (15 - len) the left-aligned limits (tcmi_huff_term), whose last says whether
+//               the code is over-subscribed.
+//   an entry    is made once per symbol, with its length, when the symbol is ranked (make_entry on a group's symbols: for four of the
+//               five literal/length groups the compiler knows they are literals), not once per slot.
+//   a slot      needs the length of the code its reversed bits begin with: the number of limits at or below them.  Nobody counts:
+//               the lanes of the lengths that have codes put a key (tcmi_huff_key: length, shift, where the length's entries lie)
+//               where their slots begin, and a running maximum over the reversed indices — a lane takes 2^(ROOT - 6) consecutive
+//               ones, a maximum scan joins the lanes — hands every slot its key; the slot shifts, adds, takes the ready entry
+//               from ent[] and is done: ~ 10 instructions (was: nine steps of shift, subtract, compare and two selects, an LDS read
+//               of sym[] and the whole of make_entry: ~ 110 instructions per 64 slots).
+// MAXG: groups of 64 symbols (5 for the 286 literal/length codes).  ol: 16 words of scratch.  ent: an entry per coded symbol (entry 0 is
+// read, and dropped, by a slot without a code even when there is none); it may lie where the long-code table will: build_long only
+// moves its tail down.  tab serves as scratch on the way (the keys, in reversed-index order) and is written whole.
 template <int MAXG, int ROOT>
-__device__ __forceinline__ bool build_table(const uint8_t *lens, int n, uint16_t *cnt, uint16_t *sym, tab_t *tab, int kind, uint32_t *rs)
+__device__ __forceinline__ bool build_table(const uint8_t *lens, int n, uint16_t *cnt, uint16_t *sym, tab_t *ent, uint32_t *ol, tab_t *tab, int kind, uint32_t *rs)
 {
-    const int lane = threadIdx.x & 63;
+    static_assert(ROOT >= 7 && ROOT <= 14, "a turn of the slot loop is 64 slots");
+    // (the lane, opaque to the compiler: what follows from the lane alone — reversed slot bits, symbol numbers, the literals' entries — is
+    // a few instructions here and would otherwise be kept in registers, or spilled, across the whole loop over a block's headers)
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
     wave_sync();                                // (LDS hand-offs between the lanes of this wavefront)
-    int l[MAXG];
+    uint32_t lp[MAXG];                          // per group: the symbol's length | its place among the symbols of that length << 4
 #pragma unroll
-    for (int g = 0; g < MAXG; ++g) l[g] = g * 64 + lane < n ? (int)lens[g * 64 + lane] : 0;
-    // histogram of the code lengths: one ballot per length and group (wave-uniform counters)
-    int c[16];
-#pragma unroll
-    for (int len = 0; len < 16; ++len) c[len] = 0;
+    for (int g = 0; g < MAXG; ++g) lp[g] = g * 64 + lane < n ? (uint32_t)lens[g * 64 + lane] & 15u : 0u;
+    if (lane < 16) ol[lane] = 0;
+    wave_sync();
 #pragma unroll
     for (int g = 0; g < MAXG; ++g) {
+        const uint32_t len = lp[g];
+        uint32_t eq_lo = ~0u, eq_hi = ~0u;
 #pragma unroll
-        for (int len = 1; len <= 15; ++len) c[len] += (int)__popcll(__ballot(l[g] == len));
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t mine = (uint32_t)((int32_t)(len << (31 - k)) >> 31);     // bit k of the length, on every bit
+            const unsigned long long m = __ballot(mine != 0);
+            eq_lo &= ~((uint32_t)m ^ mine);
+            eq_hi &= ~((uint32_t)(m >> 32) ^ mine);
+        }
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi(eq_hi, __builtin_amdgcn_mbcnt_lo(eq_lo, 0u));
+        const uint32_t before = ol[len];        // of this length in the groups in front
+        lp[g] = len | ((before + below) << 4);
+        asm volatile("" : "+v"(lp[g]));         // (here, not where it is used: the masks need not live that long)
+        wave_sync();
+        ol[len] = before + (uint32_t)__popc(eq_lo) + (uint32_t)__popc(eq_hi);
+        wave_sync();
     }
-    // ... to LDS for the long-code walk (long_code(), slow_decode())
-    {
-        int mine = 0;
+    // lanes 0 .. 15: the histogram (length 0 is no code), offsets, limits
+    const uint32_t c = lane >= 1 && lane < 16 ? ol[lane] : 0u;
+    const uint32_t term = tcmi_huff_term(c, lane & 15);
+    const uint32_t o_incl = row_scan_add(c), lim15 = row_scan_add(term);
+    // (the table in slot-index-reversed order for now: a lane's S slots are consecutive there.  Cleared for the keys.)
+    constexpr int S = 1 << (ROOT - 6);
+    uint32_t *const mine = tab + lane * S;
 #pragma unroll
-        for (int len = 1; len <= 15; ++len) mine = lane == len ? c[len] : mine;
-        if (lane < 16) cnt[lane] = (uint16_t)mine;
+    for (int j = 0; j < S; ++j) mine[j] = 0u;
+    wave_sync();
+    if (lane < 16) {
+        cnt[lane] = (uint16_t)c;                // ... to LDS for the long codes (build_long)
+        ol[lane] = o_incl - c;
     }
-    // offsets of each length in the sorted symbol array, first code of each length; over-subscription check
-    int off[16], first[16];
-    int left = 1, o = 0, f = 0;
-    bool ok = true;
-#pragma unroll
-    for (int len = 1; len <= 15; ++len) {
-        left = (left << 1) - c[len];
-        if (left < 0) ok = false;
-        off[len] = o;
-        first[len] = f;
-        o += c[len];
-        f = (f + c[len]) << 1;
-        if (len == ROOT && lane == 0) { rs[0] = (uint32_t)f; rs[1] = (uint32_t)o; }    // long_code() starts here
+    if (lane == ROOT) { rs[0] = lim15 >> (14 - ROOT); rs[1] = o_incl; }     // the first code longer than ROOT bits, the entries in front of it
+    {   // lane L = 1 .. ROOT + 1: the key of its length where that length's slots begin
+        const uint32_t start = tcmi_huff_key_start(lim15 - term, ROOT);
+        if (lane >= 1 && lane <= ROOT + 1 && (c != 0 || lane == ROOT + 1) && start < (1u << ROOT)) tab[start] = tcmi_huff_key(lane & 15, o_incl - c, lim15 - term, ROOT);
     }
-    // rank of every symbol among those of its length, in symbol order -> its slot in the sorted array
-    {
-        int nx[16];
+    const bool ok = tcmi_huff_fits((uint32_t)__builtin_amdgcn_readlane((int)lim15, 15));
+    wave_sync();
+    // every symbol to its slot in the sorted array, its entry beside it
 #pragma unroll
-        for (int len = 1; len <= 15; ++len) nx[len] = off[len];
-#pragma unroll
-        for (int g = 0; g < MAXG; ++g) {
-#pragma unroll
-            for (int len = 1; len <= 15; ++len) {
-                const unsigned long long m = __ballot(l[g] == len);
-                if (m) {
-                    const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (l[g] == len) sym[nx[len] + below] = (uint16_t)(g * 64 + lane);
-                    nx[len] += (int)__popcll(m);
-                }
-            }
+    for (int g = 0; g < MAXG; ++g) {
+        const uint32_t len = lp[g] & 15u;
+        if (len) {
+            const uint32_t at = ol[len] + (lp[g] >> 4);
+            sym[at] = (uint16_t)(g * 64 + lane);
+            ent[at] = make_entry(kind, g * 64 + lane, (int)len);
         }
     }
-    wave_sync();
-    // root table: slot i holds the symbol whose code is a prefix of the bits of i (first stream bit = bit 0): the code of
-    // length len that the slot starts with is p = reverse(i)'s top len bits; it exists if first[len] <= p < first[len] + c[len]
-    // (for a prefix code at most one length answers)
-    for (int i = lane; i < (1 << ROOT); i += 64) {
-        const uint32_t r = __builtin_bitreverse32((uint32_t)i) >> (32 - ROOT);
-        int L = 0, si = 0;
+    // the key in force at every reversed slot index: the running maximum — inside the lane, then over the lanes in front
+    uint32_t key[S];
 #pragma unroll
-        for (int len = 1; len <= ROOT; ++len) {
-            const uint32_t d = (r >> (ROOT - len)) - (uint32_t)first[len];
-            const bool hit = d < (uint32_t)c[len];
-            L = hit ? len : L;
-            si = hit ? off[len] + (int)d : si;
-        }
-        tab[i] = L ? make_entry(kind, (int)sym[si], L) : 0u;
+    for (int j = 0; j < S; ++j) key[j] = mine[j];
+#pragma unroll
+    for (int j = 1; j < S; ++j) key[j] = max(key[j], key[j - 1]);
+    const uint32_t in_front = dpp_shift<0x138, 0xF>(wave_scan_max(key[S - 1]));      // wave_shr:1 (lane 0: 0)
+    wave_sync();                                // (every lane has its keys, every entry is in place)
+    // root table: slot i holds the symbol whose code is a prefix of the bits of i (first stream bit = bit 0); this lane's
+    // S reversed indices lane * S + j are the slots reverse(lane) + 64 * reverse(j)
+    const uint32_t i0 = __builtin_bitreverse32((uint32_t)lane) >> 26;
+#pragma unroll
+    for (int j = 0; j < S; ++j) {
+        const uint32_t k = max(key[j], in_front);
+        const uint32_t e = ent[tcmi_huff_key_index(k, (uint32_t)(lane * S + j))];        // (no entry: entry 0, dropped)
+        tab[i0 + 64u * (__builtin_bitreverse32((uint32_t)j) >> (38 - ROOT))] = tcmi_huff_key_filled(k, ROOT) ? e : 0u;
     }
     wave_sync();
-    return uni(ok ? 1u : 0u) != 0;
+    return ok;
 }
 
 // ---- between bgzf_symbols and bgzf_copy: the tokens (see the head of this file) ----------------------------------------------------

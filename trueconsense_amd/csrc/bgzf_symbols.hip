@@ -44,6 +44,7 @@ struct HdrScratch {                                 // per block, while its head
     uint16_t sym_ll[288], sym_d[32], sym_cl[20];
     uint16_t cnt_ll[16], cnt_d[16], cnt_cl[16];
     uint32_t rs[6];
+    uint32_t ol[16];                                // build_table: per length, the counts so far; then offset | limit (tcmi_huff_word)
 };
 #ifndef TCMI_SYM_MOVE
 #define TCMI_SYM_MOVE 8                             // bgzf_symbols: tokens a lane has in flight when the tokens are gathered to their places
@@ -106,35 +107,32 @@ __device__ __forceinline__ void peek64(const uint32_t *pay, uint32_t p, uint32_t
 // The codes longer than the root bits: one ready-made table entry per such code, in canonical order.  A lane finds its code
 // without a walk through memory: canonical codes are ordered by length, so the code's first 15 bits, left-aligned, lie below the
 // end of exactly the lengths that are long enough — counting the ends at or below them gives the length.
+// build_table has left every symbol's entry in `out`, in canonical order; those of the long codes are its tail, from rs[1] on, and
+// move down to the front (a turn reads 64 entries before it writes them further down, and later turns read further up).
 template <int ROOT>
-__device__ __forceinline__ void build_long(const uint16_t *cnt, const uint16_t *sym, const uint32_t *rs, int kind, tab_t *out, uint32_t *lim_out,
-                                           uint32_t *fb_out)
+__device__ __forceinline__ void build_long(const uint16_t *cnt, const uint32_t *rs, tab_t *out, uint32_t *lim_out, uint32_t *fb_out)
 {
     const int lane = threadIdx.x & 63;
     uint32_t first = uni(rs[0]);
     const uint32_t at = uni(rs[1]);
     uint32_t n = 0;
-    uint32_t cs[15 - ROOT];
     uint32_t my_lim = 0x10000u, my_fb = 0;                 // (entry 15 - ROOT: above every code)
 #pragma unroll
     for (int len = ROOT + 1; len <= 15; ++len) {
         const uint32_t c = uni(cnt[len]);
-        cs[len - ROOT - 1] = c;
         if (lane == len - ROOT - 1) { my_lim = (first + c) << (15 - len); my_fb = (first & 0xFFFFu) | (n << 16); }
         first = (first + c) << 1;
         n += c;
     }
     if (lane <= 15 - ROOT) { lim_out[lane] = my_lim; fb_out[lane] = my_fb; }
-    for (uint32_t i = (uint32_t)lane; i < n; i += 64) {
-        uint32_t base = 0;
-        int mylen = 15;
-#pragma unroll
-        for (int len = ROOT + 1; len <= 15; ++len) {
-            const uint32_t c = cs[len - ROOT - 1];
-            if (i >= base && i < base + c) mylen = len;
-            base += c;
-        }
-        out[i] = make_entry(kind, (int)sym[at + i], mylen);
+    if (at == 0) return;                                    // (every code is a long one: they lie in place)
+    for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+        const uint32_t i = i0 + (uint32_t)lane;
+        uint32_t e = 0;
+        if (i < n) e = out[at + i];
+        wave_sync();
+        if (i < n) out[i] = e;
+        wave_sync();
     }
 }
 
@@ -227,7 +225,7 @@ __device__ __forceinline__ void block_header(BlkTabs &T, HdrScratch &H, const ui
                 if (lane < 8 && k < ncode) H.cll[CL_ORDER[k]] = (uint8_t)((v >> (3 * lane)) & 7u);
             }
             pos += (uint32_t)ncode * 3u;
-            if (uni(build_table<1, CL_ROOT>(H.cll, 19, H.cnt_cl, H.sym_cl, T.dt, K_CODELEN, H.rs + 4) ? 1u : 0u) == 0u) { err = ST_BAD_STREAM; break; }
+            if (!build_table<1, CL_ROOT>(H.cll, 19, H.cnt_cl, H.sym_cl, T.long_d, H.ol, T.dt, K_CODELEN, H.rs + 4)) { err = ST_BAD_STREAM; break; }
             for (int i = lane; i < 320; i += 64) H.lens[i] = 0;
             // The code-length symbols (0 .. 15: a length; 16: the previous length 3 - 6 times; 17 / 18: 3 - 10 / 11 - 138 zeros) are
             // a serial chain too, but a short one over few bits.  Every bit position of a slab is looked up by some lane (what
@@ -335,10 +333,12 @@ __device__ __forceinline__ void block_header(BlkTabs &T, HdrScratch &H, const ui
         }
         TCMI_STAMP(stamps, blk, 2);
         // ---- tables: the root tables as in bgzf_inflate, the longer codes as ready-made entries ------------------------------------
-        if (uni(build_table<5, LL_ROOT>(H.lens, nlen, H.cnt_ll, H.sym_ll, T.ll, K_LITLEN, H.rs) ? 1u : 0u) == 0u) { err = ST_BAD_STREAM; break; }
-        if (uni(build_table<1, D_ROOT>(H.lens + nlen, ndist, H.cnt_d, H.sym_d, T.dt, K_DIST, H.rs + 2) ? 1u : 0u) == 0u) { err = ST_BAD_STREAM; break; }
-        build_long<LL_ROOT>(H.cnt_ll, H.sym_ll, H.rs, K_LITLEN, T.long_ll, T.lim_ll, T.fb_ll);
-        build_long<D_ROOT>(H.cnt_d, H.sym_d, H.rs + 2, K_DIST, T.long_d, T.lim_d, T.fb_d);
+        // (the sorted entries are made where the long-code tables will be: the doubling table above is done with that LDS)
+        static_assert(sizeof(T.long_ll) >= 288 * sizeof(tab_t) && sizeof(T.long_d) >= 32 * sizeof(tab_t), "an entry per symbol");
+        if (!build_table<5, LL_ROOT>(H.lens, nlen, H.cnt_ll, H.sym_ll, T.long_ll, H.ol, T.ll, K_LITLEN, H.rs)) { err = ST_BAD_STREAM; break; }
+        if (!build_table<1, D_ROOT>(H.lens + nlen, ndist, H.cnt_d, H.sym_d, T.long_d, H.ol, T.dt, K_DIST, H.rs + 2)) { err = ST_BAD_STREAM; break; }
+        build_long<LL_ROOT>(H.cnt_ll, H.rs, T.long_ll, T.lim_ll, T.fb_ll);
+        build_long<D_ROOT>(H.cnt_d, H.rs + 2, T.long_d, T.lim_d, T.fb_d);
         if (pos >= end) { err = ST_BAD_STREAM; break; }
         go = true;
         TCMI_STAMP(stamps, blk, 3);
