@@ -247,6 +247,41 @@ def test_readset_modal_tokens_grows_its_buffer_beyond_64_kib(ctx, tmp_path):
 
 
 @pytest.mark.gpu
+def test_file_runner_refuses_a_file_off_the_device_path_under_a_floor_or_a_mask(ctx, tmp_path):
+    """A FileRunner told not to read its files for the device decoder (device_decode = False) hands every file to the host reader,
+    whose packer knows neither a base-quality floor nor a primer mask: under either the file is refused with the flag's own
+    sentence, the floor's first; without them it is decoded on the host and gives the device path's FASTA."""
+    L = 600
+    ref, orfs = sy.make_reference(L=L, cds=[(50, 500)])
+    path = str(tmp_path / "off.bam")
+    bamwriter.write_bam(path, sy.make_reads(ref, 100, read_len=100, seed=77), "r", L)
+    rows = [{"start": o["start"], "end": o["end"], "strand": "+"} for o in orfs]
+    floor = "--min-baseq 13 needs the device path (the host packer knows no base-quality floor), which this file left: it was not read for the device decoder"
+    mask = "--primers needs the device path (the host packer knows no primer mask), which this file left: it was not read for the device decoder"
+    primers = ([(60, 80, False), (400, 420, True)], 0)
+    for settings, said in ((dict(min_baseq=13), floor), (dict(primers=primers), mask), (dict(min_baseq=13, primers=primers), floor)):
+        runner = engine.FileRunner(ctx, rows, 10, gpu_streams=1, **settings)
+        try:
+            runner.device_decode = False
+            with pytest.raises(_ffi.TcmiError) as e:
+                runner.run([path], names=["s"], ref_len=L)
+            assert e.value.code == _ffi.E_UNSUPPORTED and path in str(e.value) and said in str(e.value), str(e.value)
+            assert list(runner.last_status) == [_ffi.E_UNSUPPORTED] and runner.decoded_on == {"device": 0, "host": 0}
+        finally:
+            runner.close()
+    runner = engine.FileRunner(ctx, rows, 10, gpu_streams=1)
+    try:
+        runner.device_decode = False
+        text = runner.run([path], names=["s"], ref_len=L)
+        assert runner.decoded_on == {"device": 0, "host": 1} and list(runner.last_status) == [0]
+        runner.device_decode = True
+        assert runner.run([path], names=["s"], ref_len=L) == text and runner.decoded_on == {"device": 1, "host": 1}
+        assert text[0].startswith(">s mincov=10\n") and len(text[0]) > L
+    finally:
+        runner.close()
+
+
+@pytest.mark.gpu
 def test_closing_borrowed_contexts_leaves_their_owner_usable(ctx, tmp_path):
     """FileRunner.contexts and Pipeline.ctx / slot_context(k) are the owner's: close() on them (and dropping them) destroys nothing."""
     ref, orfs = sy.make_reference(L=3000, cds=[(100, 1200), (1500, 2900)])

@@ -48,7 +48,7 @@ def _gff_line(row):
 
 
 def gff_row_columns(row):
-    """-> [source, type, score, strand, phase, attributes] of a row: what the native batch writer (csrc/pipeline.cpp) puts around the
+    """-> [source, type, score, strand, phase, attributes] of a row: what the native batch writer (csrc/outputs_text.cpp) puts around the
     sample's name and the corrected start / end."""
     fixed, attrs = _gff_columns(row)
     return [fixed["source"], fixed["type"], fixed["score"], fixed["strand"], fixed["phase"], attrs]

@@ -341,7 +341,7 @@ def _borrowed_context(handle, device):
 
 def _token_buffer(attempt, ctx=None):
     """The token buffer of a modal-token call, grown until the tokens fit: attempt(buf, cap) -> rc makes the call; while it answers
-    "token buffer too small" the buffer is tried 16 times as large, up to 1 GiB (csrc/pipeline.cpp does the same for the same calls).
+    "token buffer too small" the buffer is tried 16 times as large, up to 1 GiB (csrc/walk_records.h does the same for the same calls).
     -> the filled buffer.  ctx: the context handle any other failure's message is read from (None: the thread's last error)."""
     cap = 1 << 16
     while True:
