@@ -188,7 +188,8 @@ int  tcmi_readset_filtered(const tcmi_readset *rs, int64_t *n_filtered);
  * skipped.  A skipped token is absent from its column: nothing for coverage, A/T/C/G, X, or I (the insertion mark belongs to the
  * token in front of the insertion).  Nothing else about the read changes: the piled-up count, the extent and the per-reference
  * extents are those of the unfiltered reads, and a column whose tokens are all skipped is a zero row.  The qualities are tested as
- * the file stores them: pysam's overlap rewrite of mate pairs (ignore_overlaps) is NOT modelled.  q outside 0..255: TCMI_E_ARG;
+ * the file stores them: pysam's overlap rewrite of mate pairs (ignore_overlaps) is NOT modelled (tcmi_ctx_set_mate_overlap removes
+ * the overlap by position instead).  q outside 0..255: TCMI_E_ARG;
  * q = 0 (the default) is no floor and takes the same kernels as before.
  *   tcmi_ctx_set_min_base_quality  from now on governs every read set the context builds from a record stream decoded on the
  *                     device (tcmi_readset_from_bamfile[_blocks], tcmi_bamfile_step, tcmi_split_step and its sub-range helper
@@ -234,6 +235,40 @@ int  tcmi_ctx_set_primers(tcmi_ctx *ctx, int32_t n, const int64_t *start, const 
 int  tcmi_readset_primers(const tcmi_readset *rs, int32_t *n_primers, int64_t *n_masked_reads);
 int  tcmi_primers_compile(int32_t n, const int64_t *start, const int64_t *end, const int32_t *reverse, int32_t slack, int32_t seg_cap,
                           int32_t *head, int32_t *n_head, int32_t *tail, int32_t *n_tail, char *msg, int64_t msg_cap);
+/* ---- mate overlap (additive: what samtools mpileup does by default to the two mates of a pair, and so ivar) -----------------------
+ * A read pair whose mates cover shared columns is one molecule: under this setting it counts ONCE there.  The rule is exact, integer
+ * only, and does not depend on the order of the file (csrc/mate_rule.h holds its text).  It concerns the KEPT records of a device-
+ * decoded stream (mapped, through the read filter, consistent, on a reference that piles up, reference span > 0):
+ *   eligible   FLAG has 0x1 and 0x2, none of 0x8 / 0x100 / 0x800, exactly one of 0x40 / 0x80; next_refID == refID; next_pos >= 0
+ *   key        (read name without its NUL, refID, min(pos, next_pos), max(pos, next_pos)); the eligible records of one key are a group
+ *   pair       a group of exactly two records a, b with a.next_pos == b.pos, b.next_pos == a.pos, one 0x40 and the other 0x80.  Every
+ *              other group is unjoined (one record, three or more — those records count as `ambiguous` —, two firsts, ...).  Strand
+ *              plays no part.
+ *   loser      of a pair, the record with the larger pos; at equal pos the one with 0x80.  The other is the winner.
+ *   clip       with [p, q] a record's first and last column: clip(loser) = max(0, min(q_winner, q_loser) - p_loser + 1), 0 for every
+ *              other record.  p_loser >= p_winner: the shared columns are a prefix of the loser.
+ *   effect     the loser's tokens on its first `clip` columns are skipped exactly as primer-masked tokens are: its head_end becomes
+ *              max(the primer table's head_end, p + clip).  Everything said of a masked column above holds (no coverage, letter, X or
+ *              I; a D / N op across the edge loses only its clipped columns; the I mark goes iff the token in front of the insertion
+ *              is skipped; a record clipped from end to end is piled up and adds nothing; the piled-up count, the extent and the
+ *              per-reference extents are unchanged).  The floor and the primer table combine with it by OR.
+ * Deviations from htslib's tweak_overlap_quality, on purpose: qualities are NOT summed; the winner is chosen by position, not by
+ * quality; a column where the winner's own token is below the floor or primer-masked gets nothing from the template; the insert-
+ * candidate sweeps' region pileup (tcmi_readset_modal_tokens and kin) keeps its own overlap handling (ignore_overlaps) and is not
+ * touched.
+ *   tcmi_ctx_set_mate_overlap   on = 0 / 1 (anything else: TCMI_E_ARG); from now on governs the read sets the floor governs.  A read
+ *                     set REMEMBERS the setting and, while its decoded stream is resident, the clips: the stream-walking calls
+ *                     (strand counts, link counts, indel events, evidence counts, the long reads' tally) count under the rule.
+ *                     While on, whatever would tally WITHOUT the rule, or where a mate may lie outside what is decoded, refuses with
+ *                     TCMI_E_UNSUPPORTED and a message naming --mate-overlap: tcmi_split_step and its sub-range helpers, a block
+ *                     RANGE of a file (tcmi_readset_from_bamfile_blocks on less than the whole file), the flat-array entry points,
+ *                     the array pipeline, the file runner's host-reader fallback.  An unsorted file is fine.  Off: the launches of
+ *                     before.
+ *   tcmi_readset_mate_overlap   the setting the read set was built under and the join's counters: pairs, records with clip > 0, the
+ *                     sum of the clips, records of ambiguous groups (any pointer may be NULL) */
+int  tcmi_ctx_set_mate_overlap(tcmi_ctx *ctx, int32_t on);
+int  tcmi_readset_mate_overlap(const tcmi_readset *rs, int32_t *on, int64_t *pairs, int64_t *clipped_reads, int64_t *clipped_columns,
+                               int64_t *ambiguous);
 /* ---- variant table (additive: what `ivar variants` reports; the reference has only the consensus and its -vcf) ---------------
  * Every non-reference allele of a position at or above a frequency, with its depth, taken from the count matrix where it lies.
  * All arithmetic is integer.  With the matrix (plane order TCMI_COV..TCMI_I), a reference byte string ref[0..n_ref) on the
@@ -609,7 +644,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_LINK_COUNTS = 14 /* tcmi_readset_link_counts' one launch */,
        TCMI_K_INDEL_EVENTS = 15 /* tcmi_readset_indel_events' launches (count, verify, gather) of one attempt as one bracket */,
        TCMI_K_EVIDENCE_COUNTS = 16 /* tcmi_readset_evidence_counts' one launch */,
-       TCMI_K_NKERNELS = 17 };
+       TCMI_K_MATE_JOIN = 17 /* the mate join's table reset and two launches (build, probe) as one bracket */,
+       TCMI_K_NKERNELS = 18 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);
 int  tcmi_profile_get(tcmi_ctx *ctx, int kernel, double *total_ms, int64_t *launches);

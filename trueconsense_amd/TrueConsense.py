@@ -542,6 +542,11 @@ def GetArgs(givenargs):
     additive.append((("--min-baseq",), dict(type=_range_arg(parser, "--min-baseq", 255), default=0, metavar="N",
                                             help="skip pileup tokens (a read on a column) whose base quality is below N in the count matrix\n"
                                                  "(samtools mpileup -Q; qualities as the file stores them); needs the device decoder")))
+    additive.append((("--mate-overlap",), dict(action="store_true",
+                                               help="count the columns that the two mates of a read pair share once in the count matrix: the\n"
+                                                    "mate that starts further right loses them (samtools mpileup's default; by position, qualities\n"
+                                                    "are not summed), joined by read name on the device; needs the device decoder; not with\n"
+                                                    "-i --gpus N")))
     additive.append((("--primers",), dict(type=str, default=None, metavar="File",
                                           help="BED of the amplicon scheme's primers (chrom, start, end, name, pool, strand): a read's tokens\n"
                                                "inside the primer at its head ('+') or tail ('-') stay out of the count matrix\n"
@@ -650,6 +655,8 @@ def GetArgs(givenargs):
             if bad:
                 print(f"{why} Exiting...")
                 sys.exit(1)
+    if a.mate_overlap and a.batch is None and a.gpus and a.gpus > 1:
+        parser.error("--mate-overlap does not go with -i --gpus N: a record's mate may lie in another rank's block range.")
     if a.batch is not None and a.variant_table is not None:
         parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
     if a.batch is None and a.variant_table is None and a.variant_thresholds_given:
@@ -675,6 +682,13 @@ def GetArgs(givenargs):
         if getattr(a, key) is None:                 # (None until here: the checks above ask whether the option was given)
             setattr(a, key, default)
     return a
+
+
+def mate_stats(on, counters):
+    """The --stats keys of --mate-overlap from a read set's counters (ReadSet.mate_overlap; None: none were fetched)."""
+    c = counters or {}
+    return {"mate_overlap": bool(on), "mate_pairs": int(c.get("pairs", 0)), "reads_mate_clipped": int(c.get("clipped_reads", 0)),
+            "columns_mate_clipped": int(c.get("clipped_columns", 0)), "mate_ambiguous": int(c.get("ambiguous", 0))}
 
 
 def _spawn(cmds, envs):
@@ -722,6 +736,8 @@ def _child_argv(a, single, tables=True):
             out += [flag, "0x%x" % v]
     if a.min_baseq:                                 # (the base-quality floor, likewise)
         out += ["--min-baseq", str(a.min_baseq)]
+    if a.mate_overlap:                              # (the mate-overlap rule, likewise: a --batch child's file runner takes it)
+        out += ["--mate-overlap"]
     if a.primers:                                   # (the primer mask, likewise: both flags or neither)
         out += ["--primers", a.primers, "--primer-slack", str(a.primer_slack)]
     if tables and (a.variant_thresholds_given or a.variant_table):     # (the table's thresholds, likewise; --batch children find their tables in the manifest)
@@ -825,7 +841,7 @@ def run_batch(a):
                         decoders=min(4, max(1, cores // 4)), decode_threads=max(1, cores // 2), walkers=min(4, max(1, cores // 4)),
                         gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a),
                         min_baseq=a.min_baseq, primers=prm, variants=dict(variants_of(a), ref=refseq) if tables else None,
-                        intervals=(amplicon_intervals(amps), a.coverage_level) if amps else None)
+                        intervals=(amplicon_intervals(amps), a.coverage_level) if amps else None, mate_overlap=a.mate_overlap or None)
     runner.set_outputs(refID, refseq, vcf_header(date.today().strftime("%Y%m%d"), sys.argv[1:], a.reference, refID), IndexGff.header.raw_text,
                        [gff_row_columns(r) for r in gffrows])
     try:
@@ -845,6 +861,7 @@ def run_batch(a):
         if a.stats:
             with open(a.stats, "w") as fh:
                 json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "primers": len(prm[0]) if prm else 0,
+                           **mate_stats(a.mate_overlap, runner.mate_overlap_totals() if a.mate_overlap else None),
                            "variant_records": int(getattr(runner, "variant_records", 0)),
                            "amplicons": len(amps) if amps else 0, "amplicons_below": n_below, "stage_busy_seconds": runner.seconds,
                            "decoded_on": runner.decoded_on, "status": [int(x) for x in getattr(runner, "last_status", [])]}, fh)
@@ -908,9 +925,11 @@ def main(args=None):
     prm = primers_of(a)                             # (... and the primer table)
     a.primer_rows = len(prm[0]) if prm else 0
     _state.default_context().set_primers(*(prm or ()))
+    _state.default_context().set_mate_overlap(a.mate_overlap)      # (... and the mate-overlap rule)
     try:
         _single_sample(a, flt, t)
     finally:
+        _state.default_context().set_mate_overlap(False)
         _state.default_context().set_min_base_quality(0)
         _state.default_context().set_primers()
 
@@ -978,6 +997,7 @@ def _single_sample(a, flt, t):
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
+                       **mate_stats(a.mate_overlap, build_counts.last_mate_overlap),
                        **vstats, "amplicons": len(amps) if amps else 0, "amplicons_below": n_below, **want.stats(got),
                        "bam_bytes": os.path.getsize(a.input)}, fh)
 

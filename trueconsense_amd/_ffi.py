@@ -18,7 +18,7 @@ TCMI_OK = 0
 E_NODEVICE, E_HIP, E_ARG, E_NOMEM, E_FORMAT, E_IO, E_KEYERROR, E_ZERODIV, E_UNSUPPORTED = range(-1, -10, -1)
 COLS = ("coverage", "A", "T", "C", "G", "X", "I")        # indexing.py:134
 F_LOWCOV, F_PRIMX, F_MINDEL, F_INSCAND, F_COVGT, F_COVZERO, F_AMBIG = 1, 2, 4, 8, 16, 32, 64
-K_TALLY, K_CALL, K_ZERO, K_TALLY_GENERAL, K_PACK_CLASSIFY, K_PACK, K_INFLATE, K_RECORDS, K_CRC, K_INFLATE_COPY, K_VARIANTS, K_INTERVALS, K_AMPLICON_READS, K_STRAND_COUNTS, K_LINK_COUNTS, K_INDEL_EVENTS, K_EVIDENCE_COUNTS = range(17)
+K_TALLY, K_CALL, K_ZERO, K_TALLY_GENERAL, K_PACK_CLASSIFY, K_PACK, K_INFLATE, K_RECORDS, K_CRC, K_INFLATE_COPY, K_VARIANTS, K_INTERVALS, K_AMPLICON_READS, K_STRAND_COUNTS, K_LINK_COUNTS, K_INDEL_EVENTS, K_EVIDENCE_COUNTS, K_MATE_JOIN = range(18)
 
 
 class TcmiError(RuntimeError):
@@ -60,6 +60,8 @@ _SIGS = {
     "tcmi_readset_filtered": (_int, [_vp, _P(_i64)]),
     "tcmi_ctx_set_min_base_quality": (_int, [_vp, _i32]),
     "tcmi_readset_min_base_quality": (_int, [_vp, _P(_i32)]),
+    "tcmi_ctx_set_mate_overlap": (_int, [_vp, _i32]),
+    "tcmi_readset_mate_overlap": (_int, [_vp, _P(_i32), _P(_i64), _P(_i64), _P(_i64), _P(_i64)]),
     "tcmi_ctx_set_primers": (_int, [_vp, _i32, _vp, _vp, _vp, _i32]),
     "tcmi_readset_primers": (_int, [_vp, _P(_i32), _P(_i64)]),
     "tcmi_primers_compile": (_int, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _P(_i32), _vp, _P(_i32), C.c_char_p, _i64]),

@@ -122,7 +122,7 @@ def axis_reference(records, header_names, shift, axis_len):
 
 
 def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, on_readset=None, need_device=None):
+                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, on_readset=None, need_device=None, mate_overlap=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
     first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
@@ -135,12 +135,14 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     (Context.set_intervals): the step also computes the amplicon table's records, which info receives as "amplicon_table".
     on_readset(ctx, read set): called behind the step — info's tables are filled, the layout is still set — while the read set's
     decoded stream is resident; need_device: the flag on whose behalf a file the device decoder declines is refused then (reads
-    decoded on the host leave no stream on the device), as indexing.build_counts takes them."""
+    decoded on the host leave no stream on the device), as indexing.build_counts takes them.  mate_overlap: Context.set_mate_overlap
+    (pairs never cross contigs); info then receives the join's counters as "mate_overlap" (ReadSet.mate_overlap)."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     ctx.set_read_filter(*read_filter_args(read_filter))
     ctx.set_min_base_quality(min_baseq)
     ctx.set_primers(*(primers or ()))
+    ctx.set_mate_overlap(bool(mate_overlap))
     if variants:
         ctx.set_variants(**variants)
     if intervals:
@@ -160,6 +162,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
                 info.update(reads=host.n_records if host is not None else rs.n_reads, reads_filtered=host.n_removed if host is not None else rs.filtered)
                 if primers:                                     # (only under a table: the dict of before otherwise)
                     info["reads_primer_masked"] = rs.primer_masked_reads
+                if mate_overlap:
+                    info["mate_overlap"] = dict(rs.mate_overlap)
             plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
             if variants and info is not None:
                 info["variant_table"] = ctx.step_variants()
@@ -174,6 +178,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
         ctx.set_read_filter()
         ctx.set_min_base_quality()
         ctx.set_primers()
+        ctx.set_mate_overlap()
         if variants:
             ctx.set_variants()
         if intervals:
@@ -184,7 +189,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (StreamCounts, amplicon_intervals, amplicons_of, evidence_stats, primers_of, read_filter_of, variants_of, write_amplicon_reads,
+    from .TrueConsense import (StreamCounts, mate_stats, amplicon_intervals, amplicons_of, evidence_stats, primers_of, read_filter_of, variants_of, write_amplicon_reads,
                                write_amplicon_table, write_indel_table, write_variant_evidence, write_variant_tables)
     flt, seen, got = read_filter_of(a), {}, {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
@@ -207,7 +212,8 @@ def run(a):
                                                                  min_baseq=a.min_baseq, primers=prm, variants=var,
                                                                  intervals=(amplicon_intervals(amps), mincov) if amps else None,
                                                                  on_readset=lambda c, rs: got.update(want.count(c, rs, seen.get("variant_table"))),
-                                                                 need_device=want.need)
+                                                                 need_device=want.need, mate_overlap=a.mate_overlap)
+    seen.update(mate_stats(a.mate_overlap, seen.pop("mate_overlap", None)))
     seen.update(want.stats(got))
     seen.setdefault("reads_primer_masked", 0)
     table, strand, links = seen.pop("variant_table", None), got.get("variant_strand"), got.get("variant_links")

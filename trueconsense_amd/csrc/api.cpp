@@ -353,6 +353,14 @@ int tcmi_ctx_set_min_base_quality(tcmi_ctx *c, int32_t q)
     return TCMI_OK;
 }
 
+int tcmi_ctx_set_mate_overlap(tcmi_ctx *c, int32_t on)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    if (on != 0 && on != 1) return tcmi_fail(c, TCMI_E_ARG, "mate_overlap %d is neither 0 nor 1", (int)on);
+    c->mate_overlap = on;                                       // (read by the next upload: nothing queued reads it)
+    return TCMI_OK;
+}
+
 int tcmi_ctx_set_primers(tcmi_ctx *c, int32_t n, const int64_t *start, const int64_t *end, const int32_t *reverse, int32_t slack)
 {
     if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
@@ -387,6 +395,10 @@ int tcmi_ctx_stat(tcmi_ctx *c, const char *key, int64_t *value)
     else if (!std::strcmp(key, "h2d_piped")) { *value = c->stat_h2d_piped; for (const tcmi_ctx *h : c->helpers) *value += h->stat_h2d_piped; }
     else if (!std::strcmp(key, "one_sync_last_decline_flags")) *value = c->stat_last_decline;
     else if (!std::strcmp(key, "compute_units")) *value = c->n_cu;
+    else if (!std::strcmp(key, "mate_pairs")) *value = c->stat_mate[0];
+    else if (!std::strcmp(key, "mate_clipped_reads")) *value = c->stat_mate[1];
+    else if (!std::strcmp(key, "mate_clipped_columns")) *value = c->stat_mate[2];
+    else if (!std::strcmp(key, "mate_ambiguous")) *value = c->stat_mate[3];
     else return tcmi_fail(c, TCMI_E_ARG, "unknown statistic %s", key);
     return TCMI_OK;
 }

@@ -89,6 +89,10 @@ int refuse_slot_settings(tcmi_pipeline *p)
         if (c->primers)
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context holds a primer table (--primers): the array pipeline runs read sets uploaded "
                              "from flat arrays, which the host packer packs without a primer mask");
+    for (const tcmi_ctx *c : p->slots)                          // (... and no names or mate fields)
+        if (c->mate_overlap)
+            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's mate-overlap rule is on (--mate-overlap): the array pipeline runs read sets uploaded "
+                             "from flat arrays, which carry no names and no mate fields");
     for (const tcmi_ctx *c : p->slots)                          // (... and no variant table: nobody would fetch its records)
         if (tcmi_var_table_on(c))
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries a variant table setting (--variant-table, tcmi_ctx_set_variants): the array "

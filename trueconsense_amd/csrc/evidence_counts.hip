@@ -152,7 +152,7 @@ extern "C" int tcmi_readset_evidence_counts(tcmi_ctx *ctx, const tcmi_readset *r
     const int rc = tcmi_stream_count_parts<Sum>(
         ctx, rs, "evidence counts", TCMI_K_EVIDENCE_COUNTS, c32.data(), c32.size() * 4, sums,
         [n](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, Sum *d_cnt, unsigned grid) {
-            const EvArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n,
+            const EvArgs a = {src, tcmi_mask_args(part), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n,
                               tcmi_evidence_lds_ok(n, src.n, grid, BLOCK) ? 1 : 0};
             hipLaunchKernelGGL(evidence_counts_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
         });

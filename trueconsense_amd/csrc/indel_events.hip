@@ -303,7 +303,7 @@ int indel_events_one(tcmi_ctx *opt, tcmi_ctx *ctx, const tcmi_readset *rs, const
         IeArgs a = {};
         a.src = stream_src(rs);
         a.src.lay = rs->d_lay; a.src.n_lay = rs->n_lay;
-        a.pt = tcmi_primer_args(rs->primers);
+        a.pt = tcmi_mask_args(rs);
         a.cols = reinterpret_cast<const int32_t *>(d);
         a.cov = a.cols + n;
         a.totals = reinterpret_cast<int32_t *>(d + b_in);

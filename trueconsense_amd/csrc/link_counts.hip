@@ -133,7 +133,7 @@ extern "C" int tcmi_readset_link_counts(tcmi_ctx *ctx, const tcmi_readset *rs, i
     const int rc = tcmi_stream_count_parts<int32_t>(
         ctx, rs, "link counts", TCMI_K_LINK_COUNTS, c32.data(), c32.size() * 4, sums,
         [n, k](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, int32_t *d_cnt, unsigned grid) {
-            const LcArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n, k};
+            const LcArgs a = {src, tcmi_mask_args(part), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n, k};
             hipLaunchKernelGGL(link_counts_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
         });
     if (rc) return rc;

@@ -484,6 +484,13 @@ __device__ inline uint32_t mask_word_of(const PrimerTab &pt, const int32_t *s_ta
     if (pt.n_head + pt.n_tail <= PT_LDS) return mask_word(s_tab, pt.n_head, pt.n_tail, p, len);
     return mask_word(pt.seg, pt.n_head, pt.n_tail, p, len);
 }
+// the mate join's clip (mate_join.hip; clip == nullptr: the setting is off) raises the head part of a read's mask word: the read's
+// first clip[record] columns are its mate's — merged AFTER the read was asked whether the primer table masks it (n_masked)
+__device__ inline uint32_t clip_merge(uint32_t mw, const uint32_t *clip, uint64_t record, uint32_t len)
+{
+    if (!clip) return mw;
+    return (mw & ~1023u) | min(max(mw & 1023u, clip[record]), len);
+}
 // one ballot over the lanes that are here and one atomic per wavefront that holds a masked read (as filter_view counts)
 __device__ inline void count_masked(bool masked, PackTotals *tot)
 {
@@ -783,7 +790,12 @@ __device__ __forceinline__ void planes_body(const PackSrc src, const PackOut o, 
         const int n_slot = (int)(words_of(info & 1023u) >> 1);
         s_info[tid] = info; s_word[tid] = word; s_pos[tid] = pos; s_seq[tid] = c_seq[g];
         [[maybe_unused]] uint32_t mw = 0u;
-        if constexpr (BQ) { mw = mask_word_of(pt, s_tab, pos, (int32_t)(info & 1023u)); s_mask[tid] = mw; masked = mw != 0u; }
+        if constexpr (BQ) {
+            mw = mask_word_of(pt, s_tab, pos, (int32_t)(info & 1023u));
+            masked = mw != 0u;
+            mw = clip_merge(mw, pt.clip, c_idx[g], info & 1023u);
+            s_mask[tid] = mw;
+        }
         for (int q = 0; q < n_slot; ++q) s_owner[slot0 + q] = own && q <= npair ? (uint16_t)0xFFFFu : (uint16_t)(tid | (q << 8));
         if (own) pack_read<BQ>(view(src, c_idx[g]), o, tot, info, pos, o.seq + word, BQ ? drop + (word >> 1) : nullptr, Q, mw);
     }
@@ -827,7 +839,7 @@ __global__ __launch_bounds__(PB) void pk_planes(PackSrc src, PackOut o, const ui
                                                 const uint32_t *c_woff, const uint2 *c_seq, uint32_t n_kept, uint32_t n_words,
                                                 PackTotals *tot)
 {
-    planes_body<false>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, nullptr, 0u, PrimerTab{nullptr, 0, 0});
+    planes_body<false>(src, o, c_idx, c_pos, c_info, c_woff, c_seq, n_kept, n_words, tot, nullptr, 0u, PrimerTab{nullptr, 0, 0, nullptr});
 }
 // (8 / 5 waves per SIMD asked of the two BQ kernels: what they ran at before they took the table — the mask word would otherwise cost
 //  them a wave each, 67 and 99 vector registers; no scratch and no vector spill either way, scalar spills to lanes: DESIGN 6)
@@ -891,7 +903,7 @@ struct FusedArgs {
     PackTotals *tot;
     uint32_t *drop;                 // pk_place_bq: the drop plane [word_cap / 2] and the base-quality floor (behind everything else: the
     uint32_t min_bq;                // other kernels' argument offsets stay)
-    PrimerTab pt;                   // pk_place_bq: the primer table (all zero: none), appended likewise
+    PrimerTab pt;                   // pk_place_bq: the primer table (all zero: none) and the mate join's clip (null: off), appended likewise
 };
 
 // the sum of v[0 .. n) over the workgroup (every lane gets it); s4: LDS [PB / 64]
@@ -1143,7 +1155,12 @@ __device__ __forceinline__ void place_body(const FusedArgs a)
             const bool own = (word & INFO_PROJ) != 0;               // (its lane writes its pairs and the zero pair behind them)
             s_info[lk] = word; s_word[lk] = 2u + woff; s_pos[lk] = pos; s_seq[lk] = sq;
             [[maybe_unused]] uint32_t mw = 0u;
-            if constexpr (BQ) { mw = mask_word_of(a.pt, s_tab, pos, (int32_t)(word & 1023u)); s_mask[lk] = mw; masked = mw != 0u; }
+            if constexpr (BQ) {
+                mw = mask_word_of(a.pt, s_tab, pos, (int32_t)(word & 1023u));
+                masked = mw != 0u;
+                mw = clip_merge(mw, a.pt.clip, ex_r + t, word & 1023u);
+                s_mask[lk] = mw;
+            }
             const uint32_t slot0 = lwoff >> 1;
             for (int q = 0; q < (int)(nwords >> 1); ++q) s_owner[slot0 + q] = own && q <= npair ? (uint16_t)0xFFFFu : (uint16_t)(lk | ((uint32_t)q << 8));
             if (own) pack_read<BQ>(view_rec(a.stream + a.rec_off[ex_r + t]), a.o, a.tot, word, pos, a.o.seq + 2u + woff, BQ ? a.drop + ((2u + woff) >> 1) : nullptr, a.min_bq, mw);
@@ -1285,8 +1302,9 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     const uint32_t min_bq = src.mode == 1 ? src.min_bq : 0u;        // (flat arrays carry no QUAL: their entry points refuse a floor)
     rs->min_bq = (int32_t)min_bq;
     if (src.mode == 1) rs->primers = ctx->primers;                  // (... and a primer table likewise)
-    const PrimerTab pt = tcmi_primer_args(rs->primers);
-    const bool drop_on = min_bq || pt.seg;                          // the read set gets a drop plane and the BQ plane kernel
+    PrimerTab pt = tcmi_primer_args(rs->primers);
+    const bool mate = src.mode == 1 && ctx->mate_overlap != 0;      // (flat arrays carry no names: their entry points refuse the rule)
+    const bool drop_on = min_bq || pt.seg || mate;                  // the read set gets a drop plane and the BQ plane kernel
     if (n > 0xFFFFFFF0ll) { *why = PKF_LONG; return TCMI_E_UNSUPPORTED; }
     const int64_t n_blk = (n + PB - 1) / PB;
     uint32_t *info = (uint32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4);
@@ -1297,11 +1315,14 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     int32_t *blk_end = (int32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n_blk, 1) * 4);
     PackTotals *d_tot = (PackTotals *)tcmi_arena_take(ctx, sizeof(PackTotals));
     uint32_t *gen_idx = src.mode == 1 ? (uint32_t *)tcmi_arena_take(ctx, (size_t)std::max<int64_t>(n, 1) * 4) : nullptr;
-    PackTotals *h_tot = (PackTotals *)tcmi_ctx_pinned(ctx, sizeof(PackTotals));     // (pinned: the two read-backs below)
+    PackTotals *h_tot = (PackTotals *)tcmi_ctx_pinned(ctx, 512);                    // (pinned: the two read-backs below; the mate join's counters at + 256)
+    static_assert(sizeof(PackTotals) <= 256, "the mate join's counters lie behind the totals");
     if (!h_tot) return tcmi_fail(ctx, TCMI_E_NOMEM, "pinned scratch for the packer's totals");
     std::memset(h_tot, 0, sizeof *h_tot);
     PackTotals &tot = *h_tot;
     TCMI_HIP(ctx, hipMemsetAsync(d_tot, 0, sizeof(PackTotals), ctx->stream));
+    unsigned long long *h_cnt = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(h_tot) + 256);     // (the mate join's counters)
+    bool counts_owed = false;
     const int32_t n_lay = ctx->layout.n();
     std::vector<int32_t> h_ext((size_t)n_lay);
     if (n_lay) {                            // the context's contig layout (tcmi_ctx_set_layout): its table, the extents zeroed
@@ -1331,13 +1352,37 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     rs->n_filtered = (int64_t)tot.n_filtered;
     rs->n_masked = (int64_t)tot.n_masked;                           // (the long reads', so far)
     rs->ref_ext.assign(h_ext.begin(), h_ext.end());
+    if (mate && n > 0) {
+        // the mate join, in front of the plane kernel: the record count is the host's here; its counters are copied now and read behind
+        // the next wait this function makes anyway (take_counts)
+        tcmi_mate_job mj = {};
+        mj.src = src; mj.stream_len = ~0ull;                    // (the host has checked the record chain: every record ends inside the stream)
+        mj.n = n; mj.rec_cap = (uint32_t)n;
+        mj.table = (unsigned long long *)tcmi_arena_take(ctx, tcmi_mate_table_bytes((size_t)n));
+        mj.clip = (uint32_t *)tcmi_arena_take(ctx, (size_t)n * 4 + 4);
+        if (ctx->dev_arena.used > ctx->dev_arena.cap) return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: mate join scratch under-reserved");
+        if (const int rc = tcmi_mate_join_enqueue(ctx, mj)) return rc;
+        TCMI_HIP(ctx, hipMemcpyAsync(h_cnt, tcmi_mate_counters(mj), 32, hipMemcpyDeviceToHost, ctx->stream));
+        counts_owed = true;
+        rs->mate = 1; rs->d_clip = mj.clip; pt.clip = mj.clip;
+        rs->d_stream = src.stream; rs->d_rec_off = src.rec_off; rs->arena_epoch = ctx->arena_epoch;
+    } else if (mate) rs->mate = 1;
+    auto take_counts = [&]() {              // (behind a wait of the host for the stream)
+        if (!counts_owed) return;
+        counts_owed = false;
+        for (int k = 0; k < 4; ++k) { rs->mate_stat[k] = (int64_t)h_cnt[k]; ctx->stat_mate[k] += rs->mate_stat[k]; }
+    };
     rs->n_piled = nf + (int64_t)tot.n_gen; rs->f_reads = nf; rs->alg_bytes = (int64_t)tot.alg_bytes; rs->max_end = tot.max_end; rs->max_len = (int32_t)tot.max_len;
     rs->packed_on_device = 1;
     if (tot.n_gen) {                        // long reads: tallied from the stream, which stays in the arena until this context's next upload
         rs->d_stream = src.stream; rs->d_rec_off = src.rec_off; rs->d_gen_idx = gen_idx; rs->s_reads = (int64_t)tot.n_gen;
         rs->arena_epoch = ctx->arena_epoch;
     }
-    if (nf == 0) return TCMI_OK;
+    if (nf == 0) {                          // (long reads only: nothing else is queued — the counters get a wait of their own)
+        if (counts_owed) TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        take_counts();
+        return TCMI_OK;
+    }
     if (tot.n_words > 0xF0000000ull) { *why = PKF_WORD_OVF; return TCMI_E_UNSUPPORTED; }
 
     const int n_stages = ctx->chunk_stages > 0 ? std::min(ctx->chunk_stages, TCMI_F_MAXSTAGE) : TCMI_F_MAXSTAGE;
@@ -1382,6 +1427,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
         TCMI_HIP(ctx, hipGetLastError());
         TCMI_HIP(ctx, hipMemcpyAsync(h_tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
         TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        take_counts();
         if (tot.n_events > event_cap && attempt == 0) {          // rare: a read set full of N / indel tokens — once more with room for all
             (void)hipFree(rs->d_blob);
             rs->d_blob = nullptr;
@@ -1407,12 +1453,15 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
 
 // what the host checks after its one wait, stored by the kernel itself into pinned host memory (a copy command between two kernels
 // costs the stream 40 - 100 us of hand-over between the copy engine and the compute queue; these stores cross PCIe on their own)
+// (mate: the mate join's four counters, null when the setting is off; they land behind everything else of the pinned buffer)
 __global__ __launch_bounds__(256) void pk_report(const PackTotals *tot, const unsigned long long *blk_alg, const int32_t *blk_end, const uint32_t *stat,
-                                                 int32_t nb, PackTotals *h_tot, unsigned long long *h_alg, int32_t *h_end, uint32_t *h_stat)
+                                                 int32_t nb, PackTotals *h_tot, unsigned long long *h_alg, int32_t *h_end, uint32_t *h_stat,
+                                                 const unsigned long long *mate, unsigned long long *h_mate)
 {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (i < nb) { h_alg[i] = blk_alg[i]; h_end[i] = blk_end[i]; h_stat[i] = stat[i]; }
     if (i == 0) *h_tot = *tot;
+    if (mate && i < 4) h_mate[i] = mate[i];
 }
 
 // ---- the one-sync path: pk_index + pk_place + pk_pack queued from capacities, checked after the caller's one wait ------------------------------
@@ -1445,9 +1494,15 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     uint32_t *c_woff = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
     uint2 *c_seq = (uint2 *)tcmi_arena_take(ctx, (size_t)cap * 8);
     job->gen_idx = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
+    const bool mate = ctx->mate_overlap != 0;
+    tcmi_mate_job mj = {};
+    if (mate) {                                 // (the join's table, clip[] and counters, beside rrec)
+        mj.table = (unsigned long long *)tcmi_arena_take(ctx, tcmi_mate_table_bytes((size_t)cap));
+        mj.clip = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4 + 4);
+    }
     if (ctx->dev_arena.used > ctx->dev_arena.cap) return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: one-pass packer scratch under-reserved");
     job->d_tot = d_tot;
-    job->h_pin = (char *)tcmi_ctx_pinned(ctx, ReportPin(nb).bytes);
+    job->h_pin = (char *)tcmi_ctx_pinned(ctx, ReportPin(nb).bytes + 256);           // (+ the mate join's counters)
     if (!job->h_pin) return tcmi_fail(ctx, TCMI_E_NOMEM, "pinned scratch for the packer's totals");
     // capacities: what the arrays of the packed read set are sized for (a file beyond them takes the several-kernel path)
     const int n_stages = ctx->chunk_stages > 0 ? std::min(ctx->chunk_stages, TCMI_F_MAXSTAGE) : TCMI_F_MAXSTAGE;
@@ -1466,8 +1521,9 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     PackOut o = {};
     const uint32_t min_bq = (uint32_t)ctx->min_bq;
     rs->primers = ctx->primers;
-    const PrimerTab pt = tcmi_primer_args(rs->primers);
-    const bool drop_on = min_bq || pt.seg;
+    PrimerTab pt = tcmi_primer_args(rs->primers);
+    pt.clip = mj.clip;
+    const bool drop_on = min_bq || pt.seg || mate;
     uint32_t *drop = nullptr;
     size_t drop_bytes = 0;
     if (const int rc = carve_blob(ctx, rs, (size_t)cap, job->word_cap, job->chunk_cap, job->event_cap, &o, drop_on ? &drop : nullptr, &drop_bytes)) return rc;
@@ -1490,6 +1546,17 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     hipLaunchKernelGGL(pk_index, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
     tcmi_prof_end(ctx, TCMI_K_PACK_CLASSIFY);
     TCMI_HIP(ctx, hipGetLastError());
+    if (mate) {
+        // the mate join between pk_index and pk_place_bq: nobody has read the record count back — its kernels take it from what pk_index
+        // left, their grid is sized from the capacity
+        mj.src.stream = job->d_stream; mj.src.rec_off = job->d_rec; mj.src.mode = 1; mj.src.n = cap; mj.src.flt = a.flt;
+        mj.stream_len = job->stream_len; mj.n = -1; mj.rec_cap = (uint32_t)cap;
+        mj.rec_base = rec_base; mj.n_rec = job->d_nrec; mj.n_blocks = (int32_t)nb; mj.n_own = (int32_t)job->n_own;
+        mj.flags = &d_tot->flags; mj.ovf = PKF_REC_OVF;
+        if (const int rc = tcmi_mate_join_enqueue(ctx, mj)) return rc;
+        job->d_mate_cnt = tcmi_mate_counters(mj);
+        rs->mate = 1; rs->d_clip = mj.clip;
+    }
     tcmi_prof_begin(ctx, TCMI_K_PACK);
     zero_drop(ctx, drop, drop_bytes);
     if (prefix) {
@@ -1532,14 +1599,14 @@ int tcmi_pack_fused_report(tcmi_ctx *ctx, tcmi_fused_job *job)
     hipLaunchKernelGGL(pk_report, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, static_cast<const PackTotals *>(job->d_tot),
                        static_cast<const unsigned long long *>(job->d_blk_alg), static_cast<const int32_t *>(job->d_blk_end), job->d_stat, (int32_t)nb,
                        reinterpret_cast<PackTotals *>(h), reinterpret_cast<unsigned long long *>(h + pin.alg), reinterpret_cast<int32_t *>(h + pin.end),
-                       reinterpret_cast<uint32_t *>(h + pin.stat));
+                       reinterpret_cast<uint32_t *>(h + pin.stat), static_cast<const unsigned long long *>(job->d_mate_cnt),
+                       reinterpret_cast<unsigned long long *>(h + pin.bytes));
     TCMI_HIP(ctx, hipGetLastError());
     return TCMI_OK;
 }
 
 int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs, uint32_t *why)
 {
-    (void)ctx;
     const int64_t nb = job->n_blocks;
     const ReportPin pin(nb);
     const PackTotals &tot = *reinterpret_cast<const PackTotals *>(job->h_pin);
@@ -1564,6 +1631,11 @@ int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs,
     rs->s_reads = (int64_t)tot.n_gen;
     rs->n_filtered = (int64_t)tot.n_filtered;
     rs->n_masked = (int64_t)tot.n_masked;
+    if (job->d_mate_cnt)
+        for (int k = 0; k < 4; ++k) {
+            rs->mate_stat[k] = (int64_t)reinterpret_cast<const unsigned long long *>(job->h_pin + pin.bytes)[k];
+            ctx->stat_mate[k] += rs->mate_stat[k];
+        }
     rs->range_first = tot.range_first ? (int64_t)(tot.range_first - 1ull) : -1;
     rs->range_next = tot.range_next ? (int64_t)(tot.range_next - 1ull) : -1;
     rs->f_chunks = nf ? tot.n_chunks : 0; rs->f_words = nf ? (int64_t)tot.n_words + 4 : 0; rs->f_events = tot.n_events;

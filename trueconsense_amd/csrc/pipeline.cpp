@@ -158,9 +158,11 @@ int gpu_decode(FileRun &q, tcmi_ctx *ctx, int64_t i, GpuStep &s)
         if (rc == TCMI_E_NOMEM) rc = TCMI_E_UNSUPPORTED;         // (a file whose decode does not fit the device's memory: the host reader streams it)
     }
     if (rc != TCMI_E_UNSUPPORTED) return rc;
-    // ... but not under a base-quality floor: its packer knows none; nor under a primer table: its packer knows no mask
+    // ... but not under a base-quality floor: its packer knows none; nor under a primer table: its packer knows no mask; nor under the
+    // mate-overlap rule: its packer joins no mates
     if (ctx->min_bq > 0) return refuse_host_packer(ctx, q.paths[i], "--min-baseq " + std::to_string((int)ctx->min_bq), "base-quality floor", it.file != nullptr);
     if (ctx->primers) return refuse_host_packer(ctx, q.paths[i], "--primers", "primer mask", it.file != nullptr);
+    if (ctx->mate_overlap) return refuse_host_packer(ctx, q.paths[i], "--mate-overlap", "mate join", it.file != nullptr);
     rc = s.host.load(q.paths[i], q.r->host_threads, ctx->flt);   // (the context's read filter)
     if (rc) s.host_err = tcmi_last_error(nullptr);
     else rc = tcmi_readset_upload(ctx, &s.host.reads, &s.rs);

@@ -87,6 +87,9 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
     if (ctx->primers)                                           // (... nor a silently unmasked one)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context holds a primer table of %d primers (--primers): the host packer knows no primer mask; only "
                          "files decoded on the device are tallied under it", (int)ctx->primers->n_primers);
+    if (ctx->mate_overlap)                                      // (... nor pairs silently counted twice)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's mate-overlap rule is on (--mate-overlap): flat read arrays carry no names and no mate "
+                         "fields; only whole files decoded on the device are tallied under it");
     int rc = TCMI_OK;
     for (int32_t b = 0; b < n_batch; ++b) {
         rc = check_reads(ctx, batch[b]);
@@ -220,6 +223,17 @@ int tcmi_readset_primers(const tcmi_readset *rs, int32_t *n_primers, int64_t *n_
     if (!rs) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
     if (n_primers) *n_primers = rs->primers ? rs->primers->n_primers : 0;
     if (n_masked_reads) *n_masked_reads = rs->n_masked;
+    return TCMI_OK;
+}
+
+int tcmi_readset_mate_overlap(const tcmi_readset *rs, int32_t *on, int64_t *pairs, int64_t *clipped_reads, int64_t *clipped_columns, int64_t *ambiguous)
+{
+    if (!rs) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    if (on) *on = rs->mate;
+    if (pairs) *pairs = rs->mate_stat[0];
+    if (clipped_reads) *clipped_reads = rs->mate_stat[1];
+    if (clipped_columns) *clipped_columns = rs->mate_stat[2];
+    if (ambiguous) *ambiguous = rs->mate_stat[3];
     return TCMI_OK;
 }
 

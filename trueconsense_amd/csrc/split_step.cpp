@@ -131,6 +131,9 @@ int tcmi_split_step(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first_block, i
 {
     if (!ctx || !f || !d_counts || !reduce || !rs_out) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     if (ctx->layout.n()) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not take a contig layout (tcmi_ctx_set_layout)");
+    if (ctx->mate_overlap)                                      // (a record's mate may lie in another rank's range)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not run under the mate-overlap rule (--mate-overlap): a record's mate may lie in "
+                         "another rank's block range");
     if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld");
     if (world < 1 || rank < 0 || rank >= world) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 <= rank < world");
     *rs_out = nullptr;

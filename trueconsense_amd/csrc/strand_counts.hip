@@ -105,7 +105,7 @@ extern "C" int tcmi_readset_strand_counts(tcmi_ctx *ctx, const tcmi_readset *rs,
     const int rc = tcmi_stream_count_parts<int32_t>(
         ctx, rs, "strand counts", TCMI_K_STRAND_COUNTS, c32.data(), c32.size() * 4, sums,
         [n](tcmi_ctx *cx, const tcmi_readset *part, const PackSrc &src, const char *d_in, int32_t *d_cnt, unsigned grid) {
-            const ScArgs a = {src, tcmi_primer_args(part->primers), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n};
+            const ScArgs a = {src, tcmi_mask_args(part), reinterpret_cast<const int32_t *>(d_in), d_cnt, (int32_t)n};
             hipLaunchKernelGGL(strand_counts_kernel, dim3(grid), dim3(BLOCK), 0, cx->stream, a);
         });
     if (rc) return rc;

@@ -31,6 +31,7 @@ __device__ inline bool open_walk(const PackSrc &src, const tcmi_primer_tab &pt, 
         w.keep0 = seg_find(pt.seg, pt.n_head, w.x, w.x);
         w.keep1 = seg_find(pt.seg + 3 * pt.n_head, pt.n_tail, w.q, w.q + 1);
     }
+    if (pt.clip) w.keep0 = max(w.keep0, w.x + (int32_t)pt.clip[i]);        // (the mate join: the record's first clip columns are its mate's)
     return true;
 }
 

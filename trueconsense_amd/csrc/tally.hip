@@ -216,7 +216,8 @@ __global__ __launch_bounds__(BLOCK) void tally_atomic_kernel(TallyArgs a)
 // Under a primer table (pt; tcmi_ctx_set_primers) the read's head_end and tail_start are looked up once — its CIGAR's reference length
 // first, for the last column — and a token on a column outside [head_end, tail_start) is skipped likewise, column by column: a D / N
 // op that crosses the mask's edge loses only its masked columns, the I mark goes with the op's last column.  Coverage token by token
-// then too; without a floor a query index at or beyond l_seq is not skipped outside the mask.
+// then too; without a floor a query index at or beyond l_seq is not skipped outside the mask.  Under the mate-overlap rule (pt.clip;
+// tcmi_ctx_set_mate_overlap) head_end is at least the read's first column + its clip: the same mask, token by token likewise.
 __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint32_t *gen_idx, uint32_t n_gen, int32_t *counts, int64_t ld, int32_t L,
                                                            tcmi_primer_tab pt)
 {
@@ -231,13 +232,14 @@ __global__ __launch_bounds__(256) void tally_stream_kernel(PackSrc s, const uint
     int32_t x = v.pos + shift_of(s, v.tid), y = 0;
     const int32_t x0 = x;
     const bool table = pt.n_head + pt.n_tail != 0;
-    const bool by_token = Q != 0u || table;                     // coverage token by token
+    const bool by_token = Q != 0u || table || pt.clip != nullptr;      // coverage token by token
     int32_t keep0 = INT32_MIN, keep1 = INT32_MAX;               // tokens on columns outside [keep0, keep1) are masked
     if (table) {
         const int32_t span = (int32_t)ref_span(v);
         keep0 = seg_find(pt.seg, pt.n_head, x0, x0);
         keep1 = seg_find(pt.seg + 3 * pt.n_head, pt.n_tail, x0 + span - 1, x0 + span);
     }
+    if (pt.clip) keep0 = max(keep0, x0 + (int32_t)pt.clip[gen_idx[w]]);        // (the mate join: the read's first clip columns are its mate's)
     auto masked = [&](int32_t col) { return col < keep0 || col >= keep1; };
     for (uint32_t k = 0; k < v.n_cigar; ++k) {
         const uint32_t c = ld_u32(v.cigar + 4 * (size_t)k), op = c & 0xFu;
@@ -284,7 +286,7 @@ static int launch_tally_stream(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t L,
     (void)hipGetLastError();
     tcmi_prof_begin(ctx, TCMI_K_TALLY_GENERAL);
     hipLaunchKernelGGL(tally_stream_kernel, dim3((unsigned)((rs->s_reads + 3) / 4)), dim3(256), 0, ctx->stream, s, rs->d_gen_idx, (uint32_t)rs->s_reads,
-                       d_counts, ld, (int32_t)L, tcmi_primer_args(rs->primers));
+                       d_counts, ld, (int32_t)L, tcmi_mask_args(rs));
     tcmi_prof_end(ctx, TCMI_K_TALLY_GENERAL);
     TCMI_HIP(ctx, hipGetLastError());
     return TCMI_OK;

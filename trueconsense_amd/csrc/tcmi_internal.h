@@ -55,16 +55,22 @@ struct tcmi_primer_dev {
     ~tcmi_primer_dev() { if (seg) (void)hipFree(seg); }
 };
 // ... as the kernels take it: a trailing kernel argument / the tail of FusedArgs (tcmi_pack_src is full).  No table: all zero.
+// clip (tcmi_ctx_set_mate_overlap; null: the setting is off): per record of the decoded stream, the columns at its head that its mate
+// counts (mate_join.hip) — it travels with the table because it masks the same tokens, a head_end of its own.
 struct tcmi_primer_tab {
     const int32_t *seg;
     int32_t n_head, n_tail;
+    const uint32_t *clip;
 };
 static inline tcmi_primer_tab tcmi_primer_args(const std::shared_ptr<const tcmi_primer_dev> &p)
 {
-    tcmi_primer_tab t = {nullptr, 0, 0};
+    tcmi_primer_tab t = {nullptr, 0, 0, nullptr};
     if (p) { t.seg = p->seg; t.n_head = p->n_head; t.n_tail = p->n_tail; }
     return t;
 }
+
+struct tcmi_readset;
+static inline tcmi_primer_tab tcmi_mask_args(const tcmi_readset *rs);   // the table and the clip a read set was built under (below)
 
 struct tcmi_readset {
     uint64_t uid = 0;           // unique per upload (graphs are cached against it, not the pointer)
@@ -100,6 +106,11 @@ struct tcmi_readset {
     // non-empty head or tail mask (tcmi_readset_primers).  The drop plane is there when either is.
     std::shared_ptr<const tcmi_primer_dev> primers;
     int64_t n_masked = 0;
+    // ... and under the mate-overlap rule (tcmi_ctx_set_mate_overlap): d_clip [n_reads] lies in the context's arena beside the stream
+    // (arena_epoch tells) for the kernels that walk the records afterwards; the join's four counters (tcmi_readset_mate_overlap)
+    int32_t mate = 0;
+    const uint32_t *d_clip = nullptr;
+    int64_t mate_stat[4] = {0, 0, 0, 0};    // pairs, clipped reads, clipped columns, ambiguous records
     const uint32_t *d_gen_idx = nullptr;   // records of reads too long for the packed set (s_reads of them): tally_stream_kernel walks them in the stream
     int64_t s_reads = 0;
     // a read set of a block RANGE of a file (tcmi_readset_from_bamfile_blocks): where its first record starts when the range began
@@ -136,6 +147,13 @@ struct tcmi_readset {
     struct Part { tcmi_ctx *cx; tcmi_readset *rs; };
     std::vector<Part> parts;
 };
+
+static inline tcmi_primer_tab tcmi_mask_args(const tcmi_readset *rs)
+{
+    tcmi_primer_tab t = tcmi_primer_args(rs->primers);
+    t.clip = rs->mate ? rs->d_clip : nullptr;
+    return t;
+}
 
 struct tcmi_ride {                  // a finished matrix waiting for its call (see tally_common.h, call_other_tile)
     int32_t *counts; int64_t ld, L; int32_t mincov; int amb; uint8_t *plain, *alt, *flags; bool taken;
@@ -209,11 +227,13 @@ struct tcmi_ctx {
     tcmi_read_filter flt = {0, 0, 0};   // tcmi_ctx_set_read_filter: governs the read sets built from device-decoded record streams
     int32_t min_bq = 0;              // tcmi_ctx_set_min_base_quality: likewise; the flat-array entry points refuse while it is above 0
     std::shared_ptr<const tcmi_primer_dev> primers;   // tcmi_ctx_set_primers: likewise, and refused likewise while set
+    int32_t mate_overlap = 0;        // tcmi_ctx_set_mate_overlap: likewise; block ranges and tcmi_split_step refuse too (a mate may lie outside)
     tcmi_var_table var;              // tcmi_ctx_set_variants
     tcmi_iv_table iv;                // tcmi_ctx_set_intervals
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_one_sync_retried = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
+    int64_t stat_mate[4] = {0, 0, 0, 0};     // the mate join's counters, summed over the read sets this context built (tcmi_ctx_stat "mate_pairs", ...)
     int64_t stat_split_sub = 0;      // tcmi_split_step calls whose range went through sub-ranges
     int64_t stat_decode_batched = 0; // files the device decoder took in batches of blocks (tcmi_ctx_stat "decode_batched")
     // tcmi_readset_indel_events (indel_events.hip): log2 of the device table's first size and the bits of an insertion's hash that are
@@ -395,10 +415,34 @@ struct tcmi_fused_job {
     int32_t *c_pos = nullptr;
     uint32_t chunk_cap = 0, event_cap = 0, word_cap = 0;
     const void *d_blk_alg = nullptr, *d_blk_end = nullptr;
+    const void *d_mate_cnt = nullptr;   // the mate join's four counters (null: the setting is off); the report brings them along
 };
 int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs);
 int tcmi_pack_fused_report(tcmi_ctx *ctx, tcmi_fused_job *job);     // queue it LAST (behind the tally and the call, if any): then wait, then _finish
 int tcmi_pack_fused_finish(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs, uint32_t *why);
+// The mate join (mate_join.hip) between the packers' classification and their plane kernels, on ctx->stream: the table zeroed, the two
+// launches, nothing waited for.  n >= 0: the record count; n < 0 (the one-sync packer): the kernels take it from what pk_index left —
+// rec_base[n_blocks - 1] + the last block's own records — and count nothing while *flags has a bit of `ovf` (the index is incomplete then).
+struct tcmi_mate_job {
+    tcmi_pack_src src;                  // the stream, the record index, the filter, the layout (which records are kept: kept_span)
+    uint64_t stream_len;
+    int64_t n;
+    uint32_t rec_cap;                   // the grid and the table are sized from it
+    const uint32_t *rec_base, *n_rec;
+    int32_t n_blocks, n_own;
+    const uint32_t *flags;
+    uint32_t ovf;
+    unsigned long long *table;          // [slots + 4] {tag << 32 | record + 1}, slots = tcmi_mate_slots(rec_cap); behind them the four
+                                        // counters (tcmi_mate_counters): one memset zeroes both
+    uint32_t *clip;                     // out [rec_cap]
+};
+static inline size_t tcmi_mate_slots(size_t rec_cap) { size_t s = 1024; while (s < 2 * rec_cap) s <<= 1; return s; }
+// arena bytes of the table, clip[] and the counters for rec_cap records
+static inline size_t tcmi_mate_table_bytes(size_t rec_cap) { return tcmi_mate_slots(rec_cap) * 8 + 256; }
+static inline const unsigned long long *tcmi_mate_counters(const tcmi_mate_job &job) { return job.table + tcmi_mate_slots(job.rec_cap); }
+static inline size_t tcmi_mate_bytes(size_t rec_cap) { return tcmi_mate_table_bytes(rec_cap) + ((rec_cap * 4 + 4 + 255) & ~(size_t)255) + 3 * 256; }
+int tcmi_mate_join_enqueue(tcmi_ctx *ctx, const tcmi_mate_job &job);
+
 // the context's device arena (api.cpp): _reserve hands it out anew, `bytes` large (whatever lived in it is gone: arena_epoch tells);
 // _take carves the next piece, 256-byte aligned — the takers check `used > cap` once they have taken all
 int tcmi_arena_reserve(tcmi_ctx *ctx, size_t bytes);

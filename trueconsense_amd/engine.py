@@ -384,6 +384,10 @@ class ReadSet:
         check(lib().tcmi_readset_primers(handle, C.byref(np_), C.byref(nm)))
         self.primers = np_.value                    # primers of the table the set was built under (Context.set_primers; 0: none) ...
         self.primer_masked_reads = nm.value         # ... and its kept reads with a non-empty head or tail mask
+        on, mv = C.c_int32(0), [C.c_int64(0) for _ in range(4)]
+        check(lib().tcmi_readset_mate_overlap(handle, C.byref(on), *[C.byref(x) for x in mv]))
+        # the mate-overlap rule the set was built under (Context.set_mate_overlap) and its join's counters
+        self.mate_overlap = dict(zip(("on", "pairs", "clipped_reads", "clipped_columns", "ambiguous"), [on.value] + [x.value for x in mv]))
 
     def ref_extents(self, n_ref):
         """Uploaded under a contig layout of n_ref references: per reference the kept reads' max end in its own coordinates."""
@@ -415,6 +419,7 @@ class Context:
     read_filter = None              # what set_read_filter / set_min_base_quality last set (a context made by the library starts without either)
     min_base_quality = 0
     primers = 0                     # rows of the table set_primers last set
+    mate_overlap = False            # what set_mate_overlap last set
 
     def __init__(self, device=0, stream=None):
         """stream: a hipStream_t as an int (0 = the default stream) to run on, e.g. another Context's
@@ -495,9 +500,19 @@ class Context:
         check(lib().tcmi_ctx_set_primers(self.handle, len(rows), ptr(s_), ptr(e_), ptr(r_), int(slack)), self.handle)
         self.primers = len(rows)
 
-    def apply(self, read_filter=None, min_baseq=None, primers=None):
-        """A job's read_filter = (min_mapq, require_flags, exclude_flags), min_baseq and primers = (rows, slack) (set_primers; no rows
-        clears the table) onto this context; None leaves what it has."""
+    def set_mate_overlap(self, on=False):
+        """Mate overlap (tcmi_ctx_set_mate_overlap; what samtools mpileup does by default): from now on every read set this context
+        builds from a whole device-decoded file counts the columns that the two mates of a pair share once — the mate that starts
+        further right loses them, joined by name on the device.  While it is on the flat-array entry points, block ranges of a file
+        and the split step refuse with E_UNSUPPORTED.  No argument: off."""
+        check(lib().tcmi_ctx_set_mate_overlap(self.handle, int(bool(on))), self.handle)
+        self.mate_overlap = bool(on)
+
+    def apply(self, read_filter=None, min_baseq=None, primers=None, mate_overlap=None):
+        """A job's read_filter = (min_mapq, require_flags, exclude_flags), min_baseq, primers = (rows, slack) (set_primers; no rows
+        clears the table) and mate_overlap (set_mate_overlap) onto this context; None leaves what it has."""
+        if mate_overlap is not None:
+            self.set_mate_overlap(mate_overlap)
         if read_filter is not None:
             self.set_read_filter(*read_filter_args(read_filter))
         if min_baseq is not None:
@@ -1176,7 +1191,7 @@ class FileRunner:
     (tcmi_bam_load, `decode_threads` threads) and packed from its flat arrays.  `seconds` accumulates each stage's busy time."""
 
     def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None,
-                 min_baseq=0, primers=None, variants=None, intervals=None):
+                 min_baseq=0, primers=None, variants=None, intervals=None, mate_overlap=None):
         """variants: the keyword arguments of Context.set_variants (ref, min_af, min_alt_depth, min_depth), set on every context of the
         runner: run_files(table=...) then writes each sample's variant table.  intervals = ([(start, end)], min_depth)
         (Context.set_intervals), likewise: run_files(stats=True) then returns every sample's interval records."""
@@ -1198,7 +1213,7 @@ class FileRunner:
         # the device path is refused, never tallied without it
         self.variant_records = 0        # records of the tables run_files wrote
         for c in self.contexts:
-            c.apply(read_filter, min_baseq or None, primers)
+            c.apply(read_filter, min_baseq or None, primers, mate_overlap)
             if variants:
                 c.set_variants(**variants)
             if intervals:
@@ -1208,6 +1223,11 @@ class FileRunner:
     @property
     def contexts(self):
         return [_borrowed_context(lib().tcmi_filerunner_ctx(self.handle, k), self._device) for k in range(self.n_ctx)]
+
+    def mate_overlap_totals(self):
+        """The mate join's counters summed over the files this runner's contexts decoded (ReadSet.mate_overlap's keys)."""
+        keys = (("pairs", "mate_pairs"), ("clipped_reads", "mate_clipped_reads"), ("clipped_columns", "mate_clipped_columns"), ("ambiguous", "mate_ambiguous"))
+        return {k: sum(c.stat(s) for c in self.contexts) for k, s in keys}
 
     def _account(self, status, sec, on):
         """What a run of the native runner reported: every sample's code, the stages' busy seconds, where the files were decoded."""

@@ -39,7 +39,7 @@ def Override_index_positions(index, override_data):
 def device_readset(ctx, path, blocks=None, need=None):
     """The device path, or why not: the file at `path` (blocks = (first, count): that range of its BGZF blocks) decoded and packed by
     ctx's device decoder -> ReadSet; None when the decoder declines the file (E_UNSUPPORTED) and the host reader may take it.  Under
-    a base-quality floor (ctx.min_base_quality) or a primer table (ctx.primers) the host reader may not: the refusal is raised with its
+    a base-quality floor (ctx.min_base_quality), a primer table (ctx.primers) or the mate-overlap rule (ctx.mate_overlap) the host reader may not: the refusal is raised with its
     reason; likewise when the caller names a flag that `need`s the device path (--amplicon-reads counts in the decoded stream)."""
     d = DeviceBam(path)
     try:
@@ -53,6 +53,9 @@ def device_readset(ctx, path, blocks=None, need=None):
                                  "which %s left: %s" % (q, path, e)) from e
         if getattr(ctx, "primers", 0):              # (a context of before the table has none)
             raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--primers needs the device path (the host packer knows no primer mask), "
+                                 "which %s left: %s" % (path, e)) from e
+        if getattr(ctx, "mate_overlap", False):
+            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--mate-overlap needs the device path (the host packer joins no mates), "
                                  "which %s left: %s" % (path, e)) from e
         if need:
             raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "%s needs the device path (it counts the records in the stream the device decoded), "
@@ -80,6 +83,7 @@ def build_counts(bamfile, ref, ctx=None, on_readset=None, need_device=None):
             try:
                 build_counts.last_reads, build_counts.last_filtered = int(rs.n_reads), int(rs.filtered)
                 build_counts.last_primer_masked = int(rs.primer_masked_reads)
+                build_counts.last_mate_overlap = dict(rs.mate_overlap)
                 counts = ctx.step(rs, max(ref_length, rs.max_end, 1), 0, True, want_counts=True)[3]
                 if on_readset is not None:
                     on_readset(ctx, rs)
@@ -99,6 +103,7 @@ def build_counts(bamfile, ref, ctx=None, on_readset=None, need_device=None):
 build_counts.last_reads = 0         # alignment records of the file the last call read (the command line's --stats)
 build_counts.last_filtered = 0      # ... of which failed the read filter
 build_counts.last_primer_masked = 0 # piled-up reads with a non-empty primer mask (Context.set_primers)
+build_counts.last_mate_overlap = {} # the mate join's counters of the last device-decoded file (Context.set_mate_overlap; ReadSet.mate_overlap)
 
 
 def BuildIndex(bamfile, ref):
