@@ -233,7 +233,7 @@ def test_amplicons_of_the_reference_and_children(tmp_path, capsys):
 def test_files_that_leave_the_device_path_are_refused(monkeypatch):
     """a file the device decoder declines is refused on behalf of --amplicon-reads, as --primers refuses it: never counted another way"""
     class Ctx:
-        min_base_quality, primers = 0, 0
+        read_rules = engine.ReadRules()
 
         def upload_bamfile(self, d, blocks):
             raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "the device packer declined")

@@ -286,8 +286,8 @@ def test_one_file_over_three_ranks(tmp_path, split_sub):
     path = str(tmp_path / "A.bam")
     bamwriter.write_bam(path, rsp.arrays(big), ref_len=L, block=1024 if split_sub == 2 else 4096)
     tm = {}
-    ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, min_baseq=13, split_sub=split_sub, timings=tm)
-    tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, min_baseq=13, split_sub=1)
+    ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, rules=engine.ReadRules(min_baseq=13), split_sub=split_sub, timings=tm)
+    tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, rules=engine.ReadRules(min_baseq=13), split_sub=1)
     assert np.array_equal(ta[1], times * want)
     assert ta[0] == tb[0] and np.array_equal(ta[1], tb[1]) and ta[2] == tb[2]
     assert (tm["split_sub_taken"] > 0) == (split_sub == 2)
@@ -302,7 +302,7 @@ def test_two_reference_contig_layout(ctx, tmp_path):
     bamwriter.write_bam(path, rsp.arrays(specs), refs=refs, block=4096)
     shift, slot, axis = contigs.layout_for(recs, [n for n, _ in refs], [ln for _, ln in refs])
     t0 = ctx.stat("one_sync_taken")
-    counts = contigs.step_contigs(ctx, path, shift, slot, axis, 10, True, [n for n, _ in refs], want_counts=True, min_baseq=13)[3]
+    counts = contigs.step_contigs(ctx, path, shift, slot, axis, 10, True, [n for n, _ in refs], want_counts=True, rules=engine.ReadRules(min_baseq=13))[3]
     assert ctx.stat("one_sync_taken") == t0
     seen = np.zeros(axis, bool)
     for t, (_, ln) in enumerate(refs):

@@ -211,7 +211,7 @@ def test_block_ranges_over_three_ranks(tmp_path, split_sub):
     big = specs if times == 1 else sorted([dict(r, name="%s_%d" % (r["name"], k)) for k in range(4) for r in specs], key=lambda r: r["pos"])
     path = write(tmp_path, big, block=1024 if split_sub == 2 else 4096)
     tm = {}
-    kw = dict(return_parts=True, primers=(table, 3), min_baseq=13, read_filter=F)
+    kw = dict(return_parts=True, rules=engine.ReadRules(primers=(table, 3), min_baseq=13, read_filter=F))
     ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, split_sub=split_sub, timings=tm, **kw)
     tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, split_sub=1, **kw)
     msg = differ(ta[1], times * want, kept, (seed, "all", "three ranks", split_sub))
@@ -240,7 +240,7 @@ def test_two_reference_contig_layout(ctx, tmp_path):
     shift, slot, axis = contigs.layout_for(recs, names, [ln for _, ln in refs])
     rows = pbed.rows_for_layout([(name, s, e, rev) for name, _, table, _ in parts for s, e, rev in table], names, shift)
     info = {}
-    counts = contigs.step_contigs(ctx, path, shift, slot, axis, 10, True, names, want_counts=True, min_baseq=13, primers=(rows, 0), read_filter=F, info=info)[3]
+    counts = contigs.step_contigs(ctx, path, shift, slot, axis, 10, True, names, want_counts=True, rules=engine.ReadRules(min_baseq=13, primers=(rows, 0), read_filter=F), info=info)[3]
     assert ctx.primers == 0
     seen = np.zeros(axis, bool)
     n_masked = 0

@@ -314,7 +314,7 @@ def test_file_runner_refuses_the_host_reader_fallback(ctx, store):
     path, _ = data(store, "seed11")
     _, orfs = sy.make_reference(L=600, cds=[(50, 500)])
     rows = [{"start": o["start"], "end": o["end"], "strand": "+"} for o in orfs]
-    runner = engine.FileRunner(ctx, rows, 10, gpu_streams=1, mate_overlap=True)
+    runner = engine.FileRunner(ctx, rows, 10, gpu_streams=1, rules=engine.ReadRules(mate_overlap=True))
     try:
         runner.device_decode = False
         said = refused(lambda: runner.run([path], names=["s"], ref_len=mc.FUZZ_L))

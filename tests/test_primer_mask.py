@@ -428,8 +428,8 @@ def test_one_file_over_three_ranks(tmp_path, split_sub):
     path = str(tmp_path / "A.bam")
     bamwriter.write_bam(path, rsp.arrays(big), ref_len=L, block=1024 if split_sub == 2 else 4096)
     tm = {}
-    ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, primers=(SCHEME, 0), split_sub=split_sub, timings=tm)
-    tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, primers=(SCHEME, 0), split_sub=1)
+    ta = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, rules=engine.ReadRules(primers=(SCHEME, 0)), split_sub=split_sub, timings=tm)
+    tb = distributed.split_ranks_in_turn(path, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, rules=engine.ReadRules(primers=(SCHEME, 0)), split_sub=1)
     assert np.array_equal(ta[1], times * want)
     assert ta[0] == tb[0] and np.array_equal(ta[1], tb[1]) and ta[2] == tb[2]
     assert (tm["split_sub_taken"] > 0) == (split_sub == 2)
@@ -460,7 +460,7 @@ def test_two_reference_contig_layout(ctx, tmp_path):
     rows = pbed.rows_for_layout(pbed.read_bed(_contig_bed(str(tmp_path / "p.bed"))), names, shift)
     assert len(rows) == 8
     info = {}
-    counts = contigs.step_contigs(ctx, path, shift, slot, axis, 10, True, names, want_counts=True, primers=(rows, 0), info=info)[3]
+    counts = contigs.step_contigs(ctx, path, shift, slot, axis, 10, True, names, want_counts=True, rules=engine.ReadRules(primers=(rows, 0)), info=info)[3]
     assert ctx.primers == 0
     seen = np.zeros(axis, bool)
     n_masked = 0

@@ -28,10 +28,8 @@ class _StubBam:
 
 
 class _FakeCtx:
-    read_filter = None
-
     def __init__(self, result, floor=0):
-        self.result, self.min_base_quality, self.calls = result, floor, []
+        self.result, self.read_rules, self.calls = result, engine.ReadRules(min_baseq=floor), []
 
     def upload_bamfile(self, dbam, blocks=None):
         self.calls.append((dbam, blocks))
@@ -198,7 +196,7 @@ def test_forced_decline_takes_the_host_leg_or_refuses_under_a_floor(ctx, tmp_pat
         finally:
             ctx.set_min_base_quality(0)
         with pytest.raises(_ffi.TcmiError) as e:
-            contigs.step_contigs(ctx, path, shift, slot, axis, 30, True, ["r"], min_baseq=13)
+            contigs.step_contigs(ctx, path, shift, slot, axis, 30, True, ["r"], rules=engine.ReadRules(min_baseq=13))
         said.append(e.value)
         assert [x.code for x in said] == [_ffi.E_UNSUPPORTED] * 2 and str(said[0]) == str(said[1])
         assert "--min-baseq 13 needs the device path (the host packer knows no base-quality floor), which %s left: " % path in str(said[0])
@@ -260,7 +258,7 @@ def test_file_runner_refuses_a_file_off_the_device_path_under_a_floor_or_a_mask(
     mask = "--primers needs the device path (the host packer knows no primer mask), which this file left: it was not read for the device decoder"
     primers = ([(60, 80, False), (400, 420, True)], 0)
     for settings, said in ((dict(min_baseq=13), floor), (dict(primers=primers), mask), (dict(min_baseq=13, primers=primers), floor)):
-        runner = engine.FileRunner(ctx, rows, 10, gpu_streams=1, **settings)
+        runner = engine.FileRunner(ctx, rows, 10, gpu_streams=1, rules=engine.ReadRules(**settings))
         try:
             runner.device_decode = False
             with pytest.raises(_ffi.TcmiError) as e:
@@ -279,6 +277,55 @@ def test_file_runner_refuses_a_file_off_the_device_path_under_a_floor_or_a_mask(
         assert text[0].startswith(">s mincov=10\n") and len(text[0]) > L
     finally:
         runner.close()
+
+
+@pytest.mark.gpu
+def test_a_rules_block_leaves_the_context_under_none_and_set_rules_none_leaves_it_alone(ctx, tmp_path):
+    """Context.rules(r) with all four rules set, left by an exception: behind the block the context is under none of them — what it
+    reports, and the next upload of the file, which equals a fresh context's exactly.  Context.set_rules(None) keeps a floor that was
+    set before.  The file: a pair whose mates share 15 columns, a duplicate, a read of quality 5, a read on its own."""
+    L = 80
+    seq = _seq(np.random.default_rng(5), 30)
+    reads = [{"pos": 10, "flag": 99, "cigar": "30M", "seq": seq, "qual": 30, "name": "p", "mtid": 0, "mpos": 25, "tlen": 45},
+             {"pos": 12, "flag": 0x400, "cigar": "30M", "seq": seq, "qual": 30, "name": "dup"},
+             {"pos": 15, "flag": 0, "cigar": "30M", "seq": seq, "qual": 5, "name": "low"},
+             {"pos": 25, "flag": 147, "cigar": "30M", "seq": seq, "qual": 30, "name": "p", "mtid": 0, "mpos": 10, "tlen": -45},
+             {"pos": 40, "flag": 16, "cigar": "30M", "seq": seq, "qual": 30, "name": "own"}]
+    path = str(tmp_path / "few.bam")
+    bamwriter.write_bam(path, ss.reads_from_spec({"reads": reads}), "r", L)
+
+    def upload(c):
+        d = engine.DeviceBam(path)
+        try:
+            rs = c.upload_bamfile(d)
+            try:
+                return c.step(rs, L, 0, True)[3], (rs.n_reads, rs.n_piled, rs.filtered, rs.min_base_quality, rs.primers, rs.primer_masked_reads, rs.mate_overlap)
+            finally:
+                rs.free()
+        finally:
+            d.close()
+    with engine.Context(0) as fresh:
+        want = upload(fresh)
+    assert want[1] == (5, 5, 0, 0, 0, 0, dict(on=0, pairs=0, clipped_reads=0, clipped_columns=0, ambiguous=0)) and want[0][:, 0].sum() == 150
+    r = engine.ReadRules(read_filter=(0, 0, 0x400), min_baseq=13, primers=(((10, 14, False),), 0), mate_overlap=True)
+    under = []
+    with pytest.raises(ZeroDivisionError):
+        with ctx.rules(r):
+            assert ctx.read_rules == r
+            under.append(upload(ctx))
+            1 / 0
+    counts, said = under[0]
+    # (every rule took tokens away: the duplicate's 30, the low read's 30, the pair's 15 shared columns, the first mate's 4 in the primer)
+    assert said == (5, 4, 1, 13, 1, 1, dict(on=1, pairs=1, clipped_reads=1, clipped_columns=15, ambiguous=0)) and counts[:, 0].sum() == 150 - 30 - 30 - 15 - 4
+    assert ctx.read_rules == engine.ReadRules()
+    assert (ctx.read_filter, ctx.min_base_quality, ctx.primers, ctx.mate_overlap) == ((0, 0, 0), 0, 0, False)
+    got = upload(ctx)
+    assert np.array_equal(got[0], want[0]) and got[1] == want[1]
+    with engine.Context(0) as c:
+        c.set_min_base_quality(13)
+        c.set_rules(None)
+        assert c.min_base_quality == 13 and c.read_rules == engine.ReadRules(min_baseq=13)
+        assert upload(c)[1][3] == 13
 
 
 @pytest.mark.gpu

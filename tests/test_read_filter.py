@@ -387,7 +387,7 @@ def test_one_file_over_three_ranks(tmp_path, split_sub):
     pa, pb, rb, n_fail = write_pair(tmp_path, big, f, block=1024 if split_sub == 2 else 4096)
     n_pos = c_oracle.extent(rb, L)
     tm = {}
-    ta = distributed.split_ranks_in_turn(pa, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, read_filter=f, split_sub=split_sub, timings=tm)
+    ta = distributed.split_ranks_in_turn(pa, n_pos, cr.gff_rows(orfs), 10, 3, return_parts=True, rules=engine.ReadRules(read_filter=f), split_sub=split_sub, timings=tm)
     tb = distributed.split_ranks_in_turn(pb, n_pos, cr.gff_rows(orfs), 10, 1, return_parts=True, split_sub=1)
     assert ta[0] == tb[0] and np.array_equal(ta[1], tb[1]) and ta[2] == tb[2]
     assert np.array_equal(ta[1], c_oracle.tally(rb, n_pos)) and len(ta[2]) >= 1

@@ -258,7 +258,7 @@ def test_block_ranges_and_sub_ranges_add_up_to_the_file(ctx, tmp_path):
     d = engine.DeviceBam(path4)
     try:
         c.set_option("split_sub", 2)
-        c.apply(f, q, (table, slack))
+        c.set_rules(engine.ReadRules(f, q, (table, slack)))
         ld, n_words = td.split_words(n_pos, 1)
         t = torch.zeros(n_words, dtype=torch.int32, device="cuda")
         hook = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)(lambda user, p, n, stream: 0)

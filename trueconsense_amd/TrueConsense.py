@@ -484,6 +484,12 @@ def primers_of(a, layout=None):
     return rows, int(a.primer_slack)
 
 
+def rules_of(a, layout=None):
+    """The parsed namespace's read rules -> engine.ReadRules (layout: primers_of's)."""
+    from .engine import ReadRules
+    return ReadRules(read_filter_of(a), a.min_baseq, primers_of(a, layout), a.mate_overlap)
+
+
 def GetArgs(givenargs):
     """Same flags, defaults, required-ness and exit codes as TrueConsense.py:25-209; table-driven."""
     parser = argparse.ArgumentParser(
@@ -832,16 +838,16 @@ def run_batch(a):
     IndexGff = Gffindex(a.features)
     gffrows = list(IndexGff.index_dict(seqid="S").values())       # (the runner puts each sample's name there: TrueConsense.py:240)
     refID, refseq = fasta.read_first_record(a.reference)
-    prm = primers_of(a)
+    rules = rules_of(a)
     amps = amplicons_of(a)
     n_below = 0
     t0 = time.perf_counter()
     cores = max(1, min(int(a.threads), os.cpu_count() or 1))
     runner = FileRunner(int(os.environ.get("TCMI_DEVICE", "0")), gffrows, a.coverage_level, a.noambiguity is False,
                         decoders=min(4, max(1, cores // 4)), decode_threads=max(1, cores // 2), walkers=min(4, max(1, cores // 4)),
-                        gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, read_filter=read_filter_of(a),
-                        min_baseq=a.min_baseq, primers=prm, variants=dict(variants_of(a), ref=refseq) if tables else None,
-                        intervals=(amplicon_intervals(amps), a.coverage_level) if amps else None, mate_overlap=a.mate_overlap or None)
+                        gpu_streams=(8 if len(rows) > 16 else 3) if len(rows) > 2 else 1, rules=rules,
+                        variants=dict(variants_of(a), ref=refseq) if tables else None,
+                        intervals=(amplicon_intervals(amps), a.coverage_level) if amps else None)
     runner.set_outputs(refID, refseq, vcf_header(date.today().strftime("%Y%m%d"), sys.argv[1:], a.reference, refID), IndexGff.header.raw_text,
                        [gff_row_columns(r) for r in gffrows])
     try:
@@ -860,7 +866,7 @@ def run_batch(a):
     finally:
         if a.stats:
             with open(a.stats, "w") as fh:
-                json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "primers": len(prm[0]) if prm else 0,
+                json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "primers": len(rules.primers[0]) if rules.primers else 0,
                            **mate_stats(a.mate_overlap, runner.mate_overlap_totals() if a.mate_overlap else None),
                            "variant_records": int(getattr(runner, "variant_records", 0)),
                            "amplicons": len(amps) if amps else 0, "amplicons_below": n_below, "stage_busy_seconds": runner.seconds,
@@ -917,21 +923,12 @@ def main(args=None):
         return run_per_contig(a)
     t = {"start": time.perf_counter()}
 
-    from .engine import read_filter_args
-    flt = read_filter_of(a)
-    _state.default_context().set_read_filter(*read_filter_args(flt))       # (always: the process's one context may have served another call)
-    # (... and the base-quality floor, for this call only: the flat-array entry points of the same context refuse while it is set)
-    _state.default_context().set_min_base_quality(a.min_baseq)
-    prm = primers_of(a)                             # (... and the primer table)
-    a.primer_rows = len(prm[0]) if prm else 0
-    _state.default_context().set_primers(*(prm or ()))
-    _state.default_context().set_mate_overlap(a.mate_overlap)      # (... and the mate-overlap rule)
-    try:
-        _single_sample(a, flt, t)
-    finally:
-        _state.default_context().set_mate_overlap(False)
-        _state.default_context().set_min_base_quality(0)
-        _state.default_context().set_primers()
+    rules = rules_of(a)
+    a.primer_rows = len(rules.primers[0]) if rules.primers else 0
+    # (always: the process's one context may have served another call — and for this call only: the flat-array entry points of the
+    # same context refuse under a floor, a table or the mate rule)
+    with _state.default_context().rules(rules):
+        _single_sample(a, rules.read_filter, t)
 
 
 def _single_sample(a, flt, t):

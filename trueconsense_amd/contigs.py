@@ -22,7 +22,7 @@ from datetime import date
 import numpy as np
 
 from . import _ffi, _state
-from .engine import BamFile, modal_tokens, read_filter_args
+from .engine import BamFile, ReadRules, modal_tokens
 from .Events import _parse_token, candidates_from_flags
 from .io import fasta
 from .indexing import Gffindex, device_readset
@@ -121,77 +121,70 @@ def axis_reference(records, header_names, shift, axis_len):
     return ref
 
 
-def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, read_filter=None,
-                 info=None, min_baseq=0, primers=None, variants=None, intervals=None, on_readset=None, need_device=None, mate_overlap=None):
+def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header_names, threads=0, want_counts=True, rules=ReadRules(),
+                 info=None, variants=None, intervals=None, on_readset=None, need_device=None):
     """One decode + pack + tally + call of the whole file under the layout -> (plain, alt, flags, int32 [axis_len, 7] counts,
     per-reference extents, mapped reads dropped, host BamFile or None); counts None unless `want_counts`.  The device decoder
-    first; a file it declines goes through the host reader (same layout).  read_filter = (min_mapq, require_flags,
-    exclude_flags): extents, `dropped` and the host BamFile see the passing records only; info (a dict) receives "reads" (the
-    file's records) and "reads_filtered".  min_baseq: the base-quality floor of the count matrix (Context.set_min_base_quality);
-    above 0 a file the device decoder declines is refused (the host packer knows no floor).  primers = (rows on the AXIS, slack)
-    (Context.set_primers; io.primers.rows_for_layout shifts a BED's rows): likewise; info then receives "reads_primer_masked" too.
+    first; a file it declines goes through the host reader (same layout).  rules: the ReadRules the context is under for this call
+    (Context.rules).  Its read_filter: extents, `dropped` and the host BamFile see the passing records only; info (a dict) receives
+    "reads" (the file's records) and "reads_filtered".  Its min_baseq: the base-quality floor of the count matrix; above 0 a file the
+    device decoder declines is refused (the host packer knows no floor).  Its primers = (rows on the AXIS, slack)
+    (io.primers.rows_for_layout shifts a BED's rows): likewise; info then receives "reads_primer_masked" too.
     variants = the keyword arguments of Context.set_variants (ref: the reference on the axis, axis_reference): the step also lists
     the variant table's records, which info receives as "variant_table".  intervals = ([(start, end)] on the axis, min_depth)
     (Context.set_intervals): the step also computes the amplicon table's records, which info receives as "amplicon_table".
     on_readset(ctx, read set): called behind the step — info's tables are filled, the layout is still set — while the read set's
     decoded stream is resident; need_device: the flag on whose behalf a file the device decoder declines is refused then (reads
-    decoded on the host leave no stream on the device), as indexing.build_counts takes them.  mate_overlap: Context.set_mate_overlap
-    (pairs never cross contigs); info then receives the join's counters as "mate_overlap" (ReadSet.mate_overlap)."""
+    decoded on the host leave no stream on the device), as indexing.build_counts takes them.  The rules' mate_overlap (pairs never
+    cross contigs): info then receives the join's counters as "mate_overlap" (ReadSet.mate_overlap)."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
-    ctx.set_read_filter(*read_filter_args(read_filter))
-    ctx.set_min_base_quality(min_baseq)
-    ctx.set_primers(*(primers or ()))
-    ctx.set_mate_overlap(bool(mate_overlap))
     if variants:
         ctx.set_variants(**variants)
     if intervals:
         ctx.set_intervals(*intervals)
     host = None
-    try:
-        rs = device_readset(ctx, path, need=need_device)    # (the floor it refuses under is the one just set)
-        if rs is None:
-            host = BamFile(path, threads=threads, read_filter=read_filter)
-            try:
-                rs = ctx.upload(host)
-            except _ffi.TcmiError as e:
-                raise _name_slot_overrun(e, host, header_names) from e
+    with ctx.rules(rules):
         try:
-            ext, dropped = rs.ref_extents(n_ref), rs.dropped()
-            if info is not None:
-                info.update(reads=host.n_records if host is not None else rs.n_reads, reads_filtered=host.n_removed if host is not None else rs.filtered)
-                if primers:                                     # (only under a table: the dict of before otherwise)
-                    info["reads_primer_masked"] = rs.primer_masked_reads
-                if mate_overlap:
-                    info["mate_overlap"] = dict(rs.mate_overlap)
-            plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
-            if variants and info is not None:
-                info["variant_table"] = ctx.step_variants()
-            if intervals and info is not None:
-                info["amplicon_table"] = ctx.step_intervals()
-            if on_readset is not None:                          # (the layout is still set: the read set's shifts are the tables')
-                on_readset(ctx, rs)
+            rs = device_readset(ctx, path, need=need_device)    # (the floor it refuses under is the one just set)
+            if rs is None:
+                host = BamFile(path, threads=threads, read_filter=rules.read_filter)
+                try:
+                    rs = ctx.upload(host)
+                except _ffi.TcmiError as e:
+                    raise _name_slot_overrun(e, host, header_names) from e
+            try:
+                ext, dropped = rs.ref_extents(n_ref), rs.dropped()
+                if info is not None:
+                    info.update(reads=host.n_records if host is not None else rs.n_reads, reads_filtered=host.n_removed if host is not None else rs.filtered)
+                    if rules.primers:                               # (only under a table: the dict of before otherwise)
+                        info["reads_primer_masked"] = rs.primer_masked_reads
+                    if rules.mate_overlap:
+                        info["mate_overlap"] = dict(rs.mate_overlap)
+                plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
+                if variants and info is not None:
+                    info["variant_table"] = ctx.step_variants()
+                if intervals and info is not None:
+                    info["amplicon_table"] = ctx.step_intervals()
+                if on_readset is not None:                          # (the layout is still set: the read set's shifts are the tables')
+                    on_readset(ctx, rs)
+            finally:
+                rs.free()
         finally:
-            rs.free()
-    finally:
-        ctx.set_layout()
-        ctx.set_read_filter()
-        ctx.set_min_base_quality()
-        ctx.set_primers()
-        ctx.set_mate_overlap()
-        if variants:
-            ctx.set_variants()
-        if intervals:
-            ctx.set_intervals()
+            ctx.set_layout()
+            if variants:
+                ctx.set_variants()
+            if intervals:
+                ctx.set_intervals()
     return plain, alt, flags, counts, ext, dropped, host
 
 
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (StreamCounts, mate_stats, amplicon_intervals, amplicons_of, evidence_stats, primers_of, read_filter_of, variants_of, write_amplicon_reads,
+    from .TrueConsense import (StreamCounts, mate_stats, amplicon_intervals, amplicons_of, evidence_stats, rules_of, variants_of, write_amplicon_reads,
                                write_amplicon_table, write_indel_table, write_variant_evidence, write_variant_tables)
-    flt, seen, got = read_filter_of(a), {}, {}
+    seen, got = {}, {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
     hdr_names, hdr_lens = bam_header_refs(a.input)
@@ -199,8 +192,8 @@ def run(a):
     index = {n: t for t, n in enumerate(hdr_names)}
     gffobj = Gffindex(a.features)
     ctx = _state.default_context()
-    prm = primers_of(a, (hdr_names, shift))
-    seen["primers"] = len(prm[0]) if prm else 0
+    rules = rules_of(a, (hdr_names, shift))
+    seen["primers"] = len(rules.primers[0]) if rules.primers else 0
     want_counts = a.variants is not None or a.depth_of_coverage is not None     # (the VCF's DP and the TSV read the counts)
     amps = amplicons_of(a, (hdr_names, shift))      # (each contig's amplicons shifted by its slot; none left: an argument error)
     seen["amplicons"] = len(amps) if amps else 0
@@ -208,11 +201,10 @@ def run(a):
     axis_ref = axis_reference(records, hdr_names, shift, axis_len) if a.variant_table is not None else None
     var = dict(variants_of(a), ref=axis_ref) if axis_ref is not None else None
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
-                                                                 threads=a.threads, want_counts=want_counts, read_filter=flt, info=seen,
-                                                                 min_baseq=a.min_baseq, primers=prm, variants=var,
+                                                                 threads=a.threads, want_counts=want_counts, rules=rules, info=seen, variants=var,
                                                                  intervals=(amplicon_intervals(amps), mincov) if amps else None,
                                                                  on_readset=lambda c, rs: got.update(want.count(c, rs, seen.get("variant_table"))),
-                                                                 need_device=want.need, mate_overlap=a.mate_overlap)
+                                                                 need_device=want.need)
     seen.update(mate_stats(a.mate_overlap, seen.pop("mate_overlap", None)))
     seen.update(want.stats(got))
     seen.setdefault("reads_primer_masked", 0)
@@ -234,7 +226,7 @@ def run(a):
     toks = {}
     if cand:
         if host is None:
-            host = BamFile(a.input, threads=a.threads, read_filter=flt)
+            host = BamFile(a.input, threads=a.threads, read_filter=rules.read_filter)
         toks = {p: t for p, (t, _) in modal_tokens(host, [g for _, g in cand], layout=(shift, slot)).items()}
 
     today = date.today().strftime("%Y%m%d")

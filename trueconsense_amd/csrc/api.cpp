@@ -341,7 +341,7 @@ int tcmi_ctx_set_read_filter(tcmi_ctx *c, int32_t min_mapq, uint32_t require_fla
     tcmi_read_filter f = {0, 0, 0};
     const int rc = tcmi_read_filter_build(c, min_mapq, require_flags, exclude_flags, &f);
     if (rc) return rc;
-    c->flt = f;                                                 // (a kernel argument of the next upload: nothing queued reads it)
+    c->rules.flt = f;                                                 // (a kernel argument of the next upload: nothing queued reads it)
     return TCMI_OK;
 }
 
@@ -349,7 +349,7 @@ int tcmi_ctx_set_min_base_quality(tcmi_ctx *c, int32_t q)
 {
     if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
     if (q < 0 || q > 255) return tcmi_fail(c, TCMI_E_ARG, "min_base_quality %d is outside 0..255", (int)q);
-    c->min_bq = q;                                              // (a kernel argument of the next upload: nothing queued reads it)
+    c->rules.min_bq = q;                                              // (a kernel argument of the next upload: nothing queued reads it)
     return TCMI_OK;
 }
 
@@ -357,7 +357,7 @@ int tcmi_ctx_set_mate_overlap(tcmi_ctx *c, int32_t on)
 {
     if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
     if (on != 0 && on != 1) return tcmi_fail(c, TCMI_E_ARG, "mate_overlap %d is neither 0 nor 1", (int)on);
-    c->mate_overlap = on;                                       // (read by the next upload: nothing queued reads it)
+    c->rules.mate = on;                                       // (read by the next upload: nothing queued reads it)
     return TCMI_OK;
 }
 
@@ -367,7 +367,7 @@ int tcmi_ctx_set_primers(tcmi_ctx *c, int32_t n, const int64_t *start, const int
     std::vector<tcmi_pseg> head, tail;
     char msg[200] = "";
     if (tcmi_primers_build(n, start, end, reverse, slack, head, tail, msg, sizeof msg)) return tcmi_fail(c, TCMI_E_ARG, "%s", msg);
-    if (n == 0) { c->primers.reset(); return TCMI_OK; }         // (read sets built under the old table keep their share of it)
+    if (n == 0) { c->rules.primers.reset(); return TCMI_OK; }         // (read sets built under the old table keep their share of it)
     // a table of its own for every call: nothing queued, and no read set, ever sees one rewritten
     std::vector<int32_t> h(3 * (head.size() + tail.size()) + 1);
     int32_t *hh = h.data(), *ht = h.data() + 3 * head.size();
@@ -378,7 +378,7 @@ int tcmi_ctx_set_primers(tcmi_ctx *c, int32_t n, const int64_t *start, const int
     TCMI_HIP(c, hipMalloc((void **)&dev->seg, h.size() * 4));
     TCMI_HIP(c, hipMemcpy(dev->seg, h.data(), h.size() * 4, hipMemcpyHostToDevice));
     dev->n_head = (int32_t)head.size(); dev->n_tail = (int32_t)tail.size(); dev->n_primers = n;
-    c->primers = std::move(dev);                                // (a kernel argument of the next upload)
+    c->rules.primers = std::move(dev);                                // (a kernel argument of the next upload)
     return TCMI_OK;
 }
 

@@ -78,21 +78,27 @@ void worker_main(tcmi_pipeline *p)
     }
 }
 
+// the first slot context whose answer to tcmi_rules_beyond_host is `rule`, or null.  Asked in the order of that function's
+// precedence: once no slot answers with a rule in front of `rule`, every slot that has `rule` answers with it.
+const tcmi_ctx *first_slot_with(const tcmi_pipeline *p, tcmi_rule_beyond rule)
+{
+    for (const tcmi_ctx *c : p->slots)
+        if (tcmi_rules_beyond_host(c->rules) == rule) return c;
+    return nullptr;
+}
+
 // what a slot context may not carry: the array pipeline runs read sets uploaded from flat arrays, and its steps fill no table
 int refuse_slot_settings(tcmi_pipeline *p)
 {
-    for (const tcmi_ctx *c : p->slots)                          // (read sets uploaded from flat arrays: they know no base-quality floor)
-        if (c->min_bq > 0)
-            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's base-quality floor is %d (--min-baseq): the array pipeline runs read sets "
-                             "uploaded from flat arrays, which carry no QUAL", (int)c->min_bq);
-    for (const tcmi_ctx *c : p->slots)                          // (... and no primer mask)
-        if (c->primers)
-            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context holds a primer table (--primers): the array pipeline runs read sets uploaded "
-                             "from flat arrays, which the host packer packs without a primer mask");
-    for (const tcmi_ctx *c : p->slots)                          // (... and no names or mate fields)
-        if (c->mate_overlap)
-            return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's mate-overlap rule is on (--mate-overlap): the array pipeline runs read sets uploaded "
-                             "from flat arrays, which carry no names and no mate fields");
+    if (const tcmi_ctx *c = first_slot_with(p, TCMI_RULE_FLOOR))    // (read sets uploaded from flat arrays: they know no base-quality floor)
+        return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's base-quality floor is %d (--min-baseq): the array pipeline runs read sets "
+                         "uploaded from flat arrays, which carry no QUAL", (int)c->rules.min_bq);
+    if (first_slot_with(p, TCMI_RULE_PRIMERS))                      // (... and no primer mask)
+        return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context holds a primer table (--primers): the array pipeline runs read sets uploaded "
+                         "from flat arrays, which the host packer packs without a primer mask");
+    if (first_slot_with(p, TCMI_RULE_MATE))                         // (... and no names or mate fields)
+        return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's mate-overlap rule is on (--mate-overlap): the array pipeline runs read sets uploaded "
+                         "from flat arrays, which carry no names and no mate fields");
     for (const tcmi_ctx *c : p->slots)                          // (... and no variant table: nobody would fetch its records)
         if (tcmi_var_table_on(c))
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries a variant table setting (--variant-table, tcmi_ctx_set_variants): the array "

@@ -238,7 +238,7 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
     const size_t b_file = resident ? 256 : tcmi_align256(f->cap), b_desc = tcmi_align256(nb * sizeof(BlockDesc)),
                  b_out = tcmi_align256(f->inflated + 128), b_slot = tcmi_align256(nb * (size_t)MAX_REC_PER_BLOCK * 4),
                  b_small = b_nb4 * 5 + b_nb8 + tcmi_align256(nb * 512) + 256, b_tok = tcmi_align256(tok_words * 4 + 256);
-    D.b_rest = rest_bytes(worst_case ? D.max_rec : D.guess_rec, nb, ctx->mate_overlap != 0);
+    D.b_rest = rest_bytes(worst_case ? D.max_rec : D.guess_rec, nb, ctx->rules.mate != 0);
     if (tcmi_arena_reserve(ctx, b_file + b_desc + b_out + b_slot + b_small + b_tok + D.b_rest + 16 * 256)) return TCMI_E_NOMEM;
     uint8_t *d_file = (uint8_t *)tcmi_arena_take(ctx, b_file);
     D.d_desc = (BlockDesc *)tcmi_arena_take(ctx, b_desc);
@@ -381,7 +381,7 @@ int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, 
     Dout->range_first = v.range_first; Dout->range_next = v.range_next;
     if (total > max_rec) return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: impossible record count", f->path.c_str());
     const size_t n = (size_t)total;
-    const size_t need_rest = rest_bytes(n, nb, ctx->mate_overlap != 0);
+    const size_t need_rest = rest_bytes(n, nb, ctx->rules.mate != 0);
     // records of fewer than 64 bytes on average (single-base reads with one-letter names): the arena cannot grow under live data, but
     // the host has just waited and nothing is in flight — the file is decoded once more into an arena reserved for the worst case
     if (need_rest > b_rest && !worst_case) return decode_on_device(ctx, whole, Dout, first_blk, count, true);
@@ -494,7 +494,7 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
     if (!ctx || !f || !out) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     *out = nullptr;
     // (the mate-overlap rule: a record's mate may start in a block outside the range — never a matrix counted without the rule)
-    if (ctx->mate_overlap && (first_block != 0 || (n_blocks >= 0 && first_block + n_blocks < (int64_t)f->blocks.size())))
+    if (ctx->rules.mate && (first_block != 0 || (n_blocks >= 0 && first_block + n_blocks < (int64_t)f->blocks.size())))
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: blocks [%lld, %lld) of %zu: the mate-overlap rule (--mate-overlap) takes whole files only, a record's mate "
                          "may lie outside a block range", f->path.c_str(), (long long)first_block,
                          (long long)(n_blocks < 0 ? (int64_t)f->blocks.size() : first_block + n_blocks), f->blocks.size());
@@ -543,15 +543,13 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
     if (n_reads_out) *n_reads_out = (int64_t)D.n;
     tcmi_pack_src s = {};
     s.stream = D.d_out; s.rec_off = D.d_rec; s.n = (int64_t)D.n; s.mode = 1; s.pos_shift = 0;
-    s.flt = tcmi_filter_pack(ctx->flt);
-    s.min_bq = (uint32_t)ctx->min_bq;
     tcmi_readset *rs = new tcmi_readset();
     rs->uid = g_next_uid.fetch_add(1);
     rs->n_reads = (int64_t)D.n;
-    rs->flt = ctx->flt;
     rs->device = ctx->device;
+    tcmi_rules_stamp(rs, ctx, true);            // (here: a file without a record never reaches the packer, and is under the rules all the same;
+                                                //  the packer takes the filter and the floor of its kernels from this record)
     uint32_t why = 0;
-    rs->mate = ctx->mate_overlap;               // (a file without a record is under the rule all the same; the packer sets it again)
     rc = D.n ? tcmi_pack_on_device(ctx, &s, rs, &why) : TCMI_OK;
     if (rc == TCMI_OK) {
         rs->packed_on_device = 2;               // decoded AND packed on the device

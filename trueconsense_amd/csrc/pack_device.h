@@ -15,8 +15,7 @@ inline PackSrc stream_src(const tcmi_readset *rs)
 {
     PackSrc s = {};
     s.stream = rs->d_stream; s.rec_off = rs->d_rec_off; s.mode = 1; s.n = rs->n_reads;
-    s.flt = tcmi_filter_pack(rs->flt);          // (the filter the read set was built under)
-    s.min_bq = (uint32_t)rs->min_bq;            // (... and its base-quality floor)
+    tcmi_rules_args(s, rs->rules);              // (the filter and the floor the read set was built under)
     return s;
 }
 

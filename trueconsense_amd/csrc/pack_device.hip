@@ -1299,11 +1299,13 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     PackSrc src = *static_cast<const PackSrc *>(src_);
     *why = 0;
     const int64_t n = src.n;
-    const uint32_t min_bq = src.mode == 1 ? src.min_bq : 0u;        // (flat arrays carry no QUAL: their entry points refuse a floor)
-    rs->min_bq = (int32_t)min_bq;
-    if (src.mode == 1) rs->primers = ctx->primers;                  // (... and a primer table likewise)
-    PrimerTab pt = tcmi_primer_args(rs->primers);
-    const bool mate = src.mode == 1 && ctx->mate_overlap != 0;      // (flat arrays carry no names: their entry points refuse the rule)
+    // the rules: a stream's read set was stamped where it was born (bam_device.hip: a file without a record never comes here); one of
+    // flat arrays is born here, under none.  The kernels' filter and floor come from the read set's record, like everything below.
+    if (src.mode != 1) tcmi_rules_stamp(rs, ctx, false);
+    tcmi_rules_args(src, rs->rules);
+    const uint32_t min_bq = (uint32_t)rs->rules.min_bq;
+    PrimerTab pt = tcmi_primer_args(rs->rules.primers);
+    const bool mate = rs->rules.mate != 0;
     const bool drop_on = min_bq || pt.seg || mate;                  // the read set gets a drop plane and the BQ plane kernel
     if (n > 0xFFFFFFF0ll) { *why = PKF_LONG; return TCMI_E_UNSUPPORTED; }
     const int64_t n_blk = (n + PB - 1) / PB;
@@ -1364,9 +1366,9 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
         if (const int rc = tcmi_mate_join_enqueue(ctx, mj)) return rc;
         TCMI_HIP(ctx, hipMemcpyAsync(h_cnt, tcmi_mate_counters(mj), 32, hipMemcpyDeviceToHost, ctx->stream));
         counts_owed = true;
-        rs->mate = 1; rs->d_clip = mj.clip; pt.clip = mj.clip;
+        rs->d_clip = mj.clip; pt.clip = mj.clip;
         rs->d_stream = src.stream; rs->d_rec_off = src.rec_off; rs->arena_epoch = ctx->arena_epoch;
-    } else if (mate) rs->mate = 1;
+    }
     auto take_counts = [&]() {              // (behind a wait of the host for the stream)
         if (!counts_owed) return;
         counts_owed = false;
@@ -1494,7 +1496,8 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     uint32_t *c_woff = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
     uint2 *c_seq = (uint2 *)tcmi_arena_take(ctx, (size_t)cap * 8);
     job->gen_idx = (uint32_t *)tcmi_arena_take(ctx, (size_t)cap * 4);
-    const bool mate = ctx->mate_overlap != 0;
+    tcmi_rules_stamp(rs, ctx, true);
+    const bool mate = rs->rules.mate != 0;
     tcmi_mate_job mj = {};
     if (mate) {                                 // (the join's table, clip[] and counters, beside rrec)
         mj.table = (unsigned long long *)tcmi_arena_take(ctx, tcmi_mate_table_bytes((size_t)cap));
@@ -1519,11 +1522,9 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     job->chunk_cap = (uint32_t)std::min<int64_t>(cap, 4 * n_wg + job->len_bound / 128 + 64);
     job->event_cap = (uint32_t)std::min<int64_t>(0x7FFFFFF0ll, std::max<int64_t>(1 << 20, cap / 2));
     PackOut o = {};
-    const uint32_t min_bq = (uint32_t)ctx->min_bq;
-    rs->primers = ctx->primers;
-    PrimerTab pt = tcmi_primer_args(rs->primers);
+    PrimerTab pt = tcmi_primer_args(rs->rules.primers);
     pt.clip = mj.clip;
-    const bool drop_on = min_bq || pt.seg || mate;
+    const bool drop_on = rs->rules.min_bq || pt.seg || mate;
     uint32_t *drop = nullptr;
     size_t drop_bytes = 0;
     if (const int rc = carve_blob(ctx, rs, (size_t)cap, job->word_cap, job->chunk_cap, job->event_cap, &o, drop_on ? &drop : nullptr, &drop_bytes)) return rc;
@@ -1535,8 +1536,8 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     a.agg = agg; a.fn = fn; a.rec_base = rec_base; a.rrec = rrec; a.rec_off = job->d_rec; a.rec_cap = (uint32_t)cap;
     a.c_idx = job->c_idx; a.c_pos = job->c_pos; a.c_info = c_info; a.c_woff = c_woff; a.c_seq = c_seq; a.gen_idx = job->gen_idx;
     a.o = o; a.blk_alg = blk_alg; a.blk_end = blk_end; a.tot = d_tot;
-    a.flt = tcmi_filter_pack(ctx->flt); rs->flt = ctx->flt;
-    a.drop = drop; a.min_bq = min_bq; rs->min_bq = (int32_t)min_bq;
+    tcmi_rules_args(a, rs->rules);
+    a.drop = drop;
     a.pt = pt;
     const size_t pre_n = tcmi_align256(((size_t)nb + 1) * 8) / 8;
     if (prefix) { a.pre_rec = pre; a.pre_k = pre + pre_n; a.pre_w = pre + 2 * pre_n; }
@@ -1555,7 +1556,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
         mj.flags = &d_tot->flags; mj.ovf = PKF_REC_OVF;
         if (const int rc = tcmi_mate_join_enqueue(ctx, mj)) return rc;
         job->d_mate_cnt = tcmi_mate_counters(mj);
-        rs->mate = 1; rs->d_clip = mj.clip;
+        rs->d_clip = mj.clip;
     }
     tcmi_prof_begin(ctx, TCMI_K_PACK);
     zero_drop(ctx, drop, drop_bytes);

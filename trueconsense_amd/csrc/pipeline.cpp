@@ -160,10 +160,11 @@ int gpu_decode(FileRun &q, tcmi_ctx *ctx, int64_t i, GpuStep &s)
     if (rc != TCMI_E_UNSUPPORTED) return rc;
     // ... but not under a base-quality floor: its packer knows none; nor under a primer table: its packer knows no mask; nor under the
     // mate-overlap rule: its packer joins no mates
-    if (ctx->min_bq > 0) return refuse_host_packer(ctx, q.paths[i], "--min-baseq " + std::to_string((int)ctx->min_bq), "base-quality floor", it.file != nullptr);
-    if (ctx->primers) return refuse_host_packer(ctx, q.paths[i], "--primers", "primer mask", it.file != nullptr);
-    if (ctx->mate_overlap) return refuse_host_packer(ctx, q.paths[i], "--mate-overlap", "mate join", it.file != nullptr);
-    rc = s.host.load(q.paths[i], q.r->host_threads, ctx->flt);   // (the context's read filter)
+    const tcmi_rule_beyond beyond = tcmi_rules_beyond_host(ctx->rules);
+    if (beyond == TCMI_RULE_FLOOR) return refuse_host_packer(ctx, q.paths[i], "--min-baseq " + std::to_string((int)ctx->rules.min_bq), "base-quality floor", it.file != nullptr);
+    if (beyond == TCMI_RULE_PRIMERS) return refuse_host_packer(ctx, q.paths[i], "--primers", "primer mask", it.file != nullptr);
+    if (beyond == TCMI_RULE_MATE) return refuse_host_packer(ctx, q.paths[i], "--mate-overlap", "mate join", it.file != nullptr);
+    rc = s.host.load(q.paths[i], q.r->host_threads, ctx->rules.flt);   // (the context's read filter)
     if (rc) s.host_err = tcmi_last_error(nullptr);
     else rc = tcmi_readset_upload(ctx, &s.host.reads, &s.rs);
     return rc;
@@ -300,7 +301,7 @@ void walk_item(FileRun &q, int64_t i)
     int rc = TCMI_OK;
     const bool sweep = !it.cand.empty() && !it.pre.valid;    // insert tokens that were not resolved on the device need the reads on the host
     // (the contexts' read filter — the caller sets the same one on all of them: the sweep sees passing records only)
-    if (sweep) rc = host.load(q.paths[i], q.r->host_threads, q.r->ctxs[0]->flt);
+    if (sweep) rc = host.load(q.paths[i], q.r->host_threads, q.r->ctxs[0]->rules.flt);
     const char *nm = q.names && q.names[i] ? q.names[i] : "sample";
     std::string own;                                         // files mode: the FASTA text lives here
     int64_t room = q.stride;

@@ -81,13 +81,14 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
 {
     if (!ctx || !out || !batch || n_batch < 1) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     *out = nullptr;
-    if (ctx->min_bq > 0)                                        // (never a silently unfiltered result)
+    const tcmi_rule_beyond beyond = tcmi_rules_beyond_host(ctx->rules);
+    if (beyond == TCMI_RULE_FLOOR)                              // (never a silently unfiltered result)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's base-quality floor is %d (--min-baseq): flat read arrays carry no QUAL and the host packer "
-                         "knows no floor; only files decoded on the device are tallied under it", (int)ctx->min_bq);
-    if (ctx->primers)                                           // (... nor a silently unmasked one)
+                         "knows no floor; only files decoded on the device are tallied under it", (int)ctx->rules.min_bq);
+    if (beyond == TCMI_RULE_PRIMERS)                            // (... nor a silently unmasked one)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context holds a primer table of %d primers (--primers): the host packer knows no primer mask; only "
-                         "files decoded on the device are tallied under it", (int)ctx->primers->n_primers);
-    if (ctx->mate_overlap)                                      // (... nor pairs silently counted twice)
+                         "files decoded on the device are tallied under it", (int)ctx->rules.primers->n_primers);
+    if (beyond == TCMI_RULE_MATE)                               // (... nor pairs silently counted twice)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's mate-overlap rule is on (--mate-overlap): flat read arrays carry no names and no mate "
                          "fields; only whole files decoded on the device are tallied under it");
     int rc = TCMI_OK;
@@ -214,14 +215,14 @@ int tcmi_readset_dropped(const tcmi_readset *rs, int64_t *n_dropped)
 int tcmi_readset_min_base_quality(const tcmi_readset *rs, int32_t *q)
 {
     if (!rs || !q) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
-    *q = rs->min_bq;
+    *q = rs->rules.min_bq;
     return TCMI_OK;
 }
 
 int tcmi_readset_primers(const tcmi_readset *rs, int32_t *n_primers, int64_t *n_masked_reads)
 {
     if (!rs) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
-    if (n_primers) *n_primers = rs->primers ? rs->primers->n_primers : 0;
+    if (n_primers) *n_primers = rs->rules.primers ? rs->rules.primers->n_primers : 0;
     if (n_masked_reads) *n_masked_reads = rs->n_masked;
     return TCMI_OK;
 }
@@ -229,7 +230,7 @@ int tcmi_readset_primers(const tcmi_readset *rs, int32_t *n_primers, int64_t *n_
 int tcmi_readset_mate_overlap(const tcmi_readset *rs, int32_t *on, int64_t *pairs, int64_t *clipped_reads, int64_t *clipped_columns, int64_t *ambiguous)
 {
     if (!rs) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
-    if (on) *on = rs->mate;
+    if (on) *on = rs->rules.mate;
     if (pairs) *pairs = rs->mate_stat[0];
     if (clipped_reads) *clipped_reads = rs->mate_stat[1];
     if (clipped_columns) *clipped_columns = rs->mate_stat[2];

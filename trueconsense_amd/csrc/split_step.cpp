@@ -30,7 +30,7 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     for (tcmi_ctx *h : ctx->helpers) {                          // (the caller's decoder options)
         h->verify_crc = ctx->verify_crc; h->decode_token_mb = ctx->decode_token_mb; h->one_sync = ctx->one_sync; h->mid_wait = ctx->mid_wait;
         h->prefix_kernels = ctx->prefix_kernels; h->h2d_pieces = ctx->h2d_pieces; h->sym_scratch_div = ctx->sym_scratch_div; h->prof = false;
-        h->flt = ctx->flt; h->min_bq = ctx->min_bq; h->primers = ctx->primers;
+        h->rules = ctx->rules;                                  // (whole: the one caller has refused the mate rule, so that is off in them too)
     }
     TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));            // (the matrix is zero before anybody adds to it)
     std::vector<tcmi_readset *> rs((size_t)K, nullptr);
@@ -106,7 +106,7 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     tcmi_readset *sum = new tcmi_readset();
     sum->device = ctx->device; sum->packed_on_device = 2;
     sum->range_first = rs[0]->range_first; sum->range_next = rs[(size_t)K - 1]->range_next;
-    sum->flt = ctx->flt; sum->min_bq = ctx->min_bq; sum->primers = ctx->primers;
+    tcmi_rules_stamp(sum, ctx, true);
     for (int k = 0; k < K; ++k) {
         const tcmi_readset *r = rs[(size_t)k];
         sum->n_reads += r->n_reads; sum->n_piled += r->n_piled; sum->alg_bytes += r->alg_bytes; sum->dev_bytes += r->dev_bytes;
@@ -131,7 +131,7 @@ int tcmi_split_step(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first_block, i
 {
     if (!ctx || !f || !d_counts || !reduce || !rs_out) return tcmi_fail(ctx, TCMI_E_ARG, "null argument");
     if (ctx->layout.n()) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not take a contig layout (tcmi_ctx_set_layout)");
-    if (ctx->mate_overlap)                                      // (a record's mate may lie in another rank's range)
+    if (ctx->rules.mate)                                        // (a record's mate may lie in another rank's range)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not run under the mate-overlap rule (--mate-overlap): a record's mate may lie in "
                          "another rank's block range");
     if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld");

@@ -69,6 +69,27 @@ static inline tcmi_primer_tab tcmi_primer_args(const std::shared_ptr<const tcmi_
     return t;
 }
 
+// ---- the read rules ------------------------------------------------------------------------------------------------------
+// Which tokens of a BAM reach the count matrix: the read filter (tcmi_ctx_set_read_filter), the base-quality floor
+// (tcmi_ctx_set_min_base_quality; 0: none), the primer table (tcmi_ctx_set_primers; null: none) and the mate-overlap rule
+// (tcmi_ctx_set_mate_overlap; 0: off).  One record on the context (what its next read set is built under) and one on every read set
+// (what it was built under); tcmi_rules_stamp hands it from the one to the other, tcmi_rules_args to the kernels' arguments.
+struct tcmi_read_rules {
+    tcmi_read_filter flt = {0, 0, 0};
+    int32_t min_bq = 0;
+    std::shared_ptr<const tcmi_primer_dev> primers;
+    int32_t mate = 0;
+};
+// the first rule that is beyond the host packer and the flat arrays of struct tcmi_reads (no QUAL, no mask, no names): the entry
+// points that lead there refuse under it, each in its own words, the floor before the table before the mate rule (the filter they know)
+enum tcmi_rule_beyond { TCMI_RULE_NONE = 0, TCMI_RULE_FLOOR, TCMI_RULE_PRIMERS, TCMI_RULE_MATE };
+static inline tcmi_rule_beyond tcmi_rules_beyond_host(const tcmi_read_rules &r)
+{
+    return r.min_bq > 0 ? TCMI_RULE_FLOOR : r.primers ? TCMI_RULE_PRIMERS : r.mate ? TCMI_RULE_MATE : TCMI_RULE_NONE;
+}
+// ... as the kernels take the filter and the floor: `flt` and `min_bq` of tcmi_pack_src and of the one-sync packer's arguments
+template <class Args> static inline void tcmi_rules_args(Args &a, const tcmi_read_rules &r) { a.flt = tcmi_filter_pack(r.flt); a.min_bq = (uint32_t)r.min_bq; }
+
 struct tcmi_readset;
 static inline tcmi_primer_tab tcmi_mask_args(const tcmi_readset *rs);   // the table and the clip a read set was built under (below)
 
@@ -95,20 +116,15 @@ struct tcmi_readset {
     uint64_t lay_gen = 0;           // the context's layout generation at the upload (the device table is rewritten by the next layout)
     std::vector<int64_t> ref_ext;
     int64_t n_dropped = 0;          // mapped reads on references without a slot (tcmi_readset_dropped)
-    // built from a device-decoded record stream: the context's read filter at that time (the insert-candidate kernels apply it to the
-    // resident stream whatever the context is set to later) and the records that failed it (tcmi_readset_filtered)
-    tcmi_read_filter flt = {0, 0, 0};
+    // built from a device-decoded record stream: the rules this set was built under — the kernels that walk the resident stream
+    // afterwards apply them whatever the context is set to later (stream_src, tcmi_mask_args) — and what the build made of them:
+    // the records that failed the filter (tcmi_readset_filtered); under any of the other three the aligned set's third plane, d_fdrop: one
+    // word per {lo, hi} pair of d_fseq (index = word / 2), bit b set when that read's token on that column is skipped; the kept reads
+    // with a non-empty head or tail mask (tcmi_readset_primers); under the mate rule d_clip [n_reads], in the context's arena beside
+    // the stream (arena_epoch tells), and the join's four counters (tcmi_readset_mate_overlap)
+    tcmi_read_rules rules;
     int64_t n_filtered = 0;
-    // ... and its base-quality floor (tcmi_ctx_set_min_base_quality; 0: none).  Above 0 the aligned set carries a third plane,
-    // d_fdrop: one word per {lo, hi} pair of d_fseq (index = word / 2), bit b set when that read's token on that column is skipped
-    int32_t min_bq = 0;
-    // ... and its primer table (tcmi_ctx_set_primers; null: none), which sets bits of the same plane, and the kept reads with a
-    // non-empty head or tail mask (tcmi_readset_primers).  The drop plane is there when either is.
-    std::shared_ptr<const tcmi_primer_dev> primers;
     int64_t n_masked = 0;
-    // ... and under the mate-overlap rule (tcmi_ctx_set_mate_overlap): d_clip [n_reads] lies in the context's arena beside the stream
-    // (arena_epoch tells) for the kernels that walk the records afterwards; the join's four counters (tcmi_readset_mate_overlap)
-    int32_t mate = 0;
     const uint32_t *d_clip = nullptr;
     int64_t mate_stat[4] = {0, 0, 0, 0};    // pairs, clipped reads, clipped columns, ambiguous records
     const uint32_t *d_gen_idx = nullptr;   // records of reads too long for the packed set (s_reads of them): tally_stream_kernel walks them in the stream
@@ -131,7 +147,7 @@ struct tcmi_readset {
     uint32_t *d_fevent = nullptr;// [f_events] position | TCMI_F_EV_*: tokens that are not plain A/C/G/T bases
     tcmi_fast_chunk *d_fchunk = nullptr;   // [f_chunks]
     uint32_t *d_fcovrun = nullptr;         // coverage runs of all chunks (tcmi_fast_chunk::run0 / n_runs)
-    uint32_t *d_fdrop = nullptr;           // [f_words / 2] the drop plane (min_bq > 0 or a primer table; in d_blob behind the events)
+    uint32_t *d_fdrop = nullptr;           // [f_words / 2] the drop plane (a floor, a primer table or the mate rule; in d_blob behind the events)
     // general set
     int64_t g_reads = 0, n_rounds = 0, n_cigar = 0, n_seqw = 0;
     int32_t *d_pos = nullptr;   // [g_reads]
@@ -150,8 +166,8 @@ struct tcmi_readset {
 
 static inline tcmi_primer_tab tcmi_mask_args(const tcmi_readset *rs)
 {
-    tcmi_primer_tab t = tcmi_primer_args(rs->primers);
-    t.clip = rs->mate ? rs->d_clip : nullptr;
+    tcmi_primer_tab t = tcmi_primer_args(rs->rules.primers);
+    t.clip = rs->rules.mate ? rs->d_clip : nullptr;
     return t;
 }
 
@@ -224,10 +240,10 @@ struct tcmi_ctx {
     size_t h_pin_cap = 0;
     char *h_desc = nullptr;          // pinned: the re-based block table of a block range on its way to the device (bam_device.hip: decode_enqueue)
     size_t h_desc_cap = 0;
-    tcmi_read_filter flt = {0, 0, 0};   // tcmi_ctx_set_read_filter: governs the read sets built from device-decoded record streams
-    int32_t min_bq = 0;              // tcmi_ctx_set_min_base_quality: likewise; the flat-array entry points refuse while it is above 0
-    std::shared_ptr<const tcmi_primer_dev> primers;   // tcmi_ctx_set_primers: likewise, and refused likewise while set
-    int32_t mate_overlap = 0;        // tcmi_ctx_set_mate_overlap: likewise; block ranges and tcmi_split_step refuse too (a mate may lie outside)
+    // the read rules (above; their four setters): they govern the read sets built from device-decoded record streams.  The flat-array
+    // entry points refuse under a floor, a table or the mate rule (tcmi_rules_beyond_host); block ranges and tcmi_split_step refuse
+    // under the mate rule too (a mate may lie outside)
+    tcmi_read_rules rules;
     tcmi_var_table var;              // tcmi_ctx_set_variants
     tcmi_iv_table iv;                // tcmi_ctx_set_intervals
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
@@ -306,6 +322,11 @@ struct tcmi_ctx {
     int chunk_stages = 0;           // stages per chunk, 0 = default (up to 8)
     int project_reads = 1;          // reads with indels / skips go to the fast kernel projected onto the reference
 };
+
+// A read set that is about to be built takes its context's rules: the one place they are copied.  from_stream false: flat arrays
+// (tcmi_pack_src::mode 0) carry no MAPQ, no QUAL and no names — no rule applies, and their entry points have refused the three
+// that would have to.
+static inline void tcmi_rules_stamp(tcmi_readset *rs, const tcmi_ctx *ctx, bool from_stream) { rs->rules = from_stream ? ctx->rules : tcmi_read_rules(); }
 
 int tcmi_fail(tcmi_ctx *ctx, int code, const char *fmt, ...);
 void *tcmi_ctx_pinned(tcmi_ctx *ctx, size_t bytes);             // >= bytes of the context's pinned scratch (grow-only; nullptr: no memory)

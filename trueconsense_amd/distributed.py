@@ -143,13 +143,12 @@ def check_range_anchors(ranges, inflated_bytes):
     return None
 
 
-def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to_root=False, read_filter=None, min_baseq=None, primers=None):
+def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to_root=False, rules=None):
     """BASELINE configs[4] from ONE FILE: every rank opens the same BAM, decodes on its GPU only the alignment records that start
     in its contiguous range of BGZF blocks (engine.Context.upload_bamfile(blocks=...): inflate, record index, pack), tallies
     them into a full-length int32 [7][ld] matrix and the matrices are summed — to every rank, or (to_root) to rank 0 only.
     -> int [L,7] (None on the other ranks with to_root).  No rank ever holds the file's reads, decoded or not.
-    read_filter = (min_mapq, require_flags, exclude_flags), min_baseq (Context.set_min_base_quality; 0 sets no floor): set on the
-    rank's context, every rank the same ones; None leaves what the context has."""
+    rules: the ReadRules set on the rank's context (Context.set_rules), every rank the same ones; None leaves what the context has."""
     import torch
     L = int(L)
     ld = (L + 255) // 256 * 256
@@ -157,7 +156,7 @@ def tally_split_bamfile(path, L, rank, world, device=0, group=None, ctx=None, to
     own = ctx is None
     if own:
         ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)         # tally and collective on torch's stream
-    ctx.apply(read_filter, min_baseq, primers)
+    ctx.set_rules(rules)
     d = DeviceBam(path)
     try:
         import torch.distributed as dist
@@ -341,13 +340,13 @@ def _split_step(ctx, d, rank, world, L, ld, t, mincov, include_ambig, fn, user):
     return rc, ReadSet(ctx, h, None), tuple(_grab(vp, np.uint8, L) for vp in (p_, a_, f_)) if rank == 0 else None
 
 
-def _tokens_for(path, cand, pieces, host_sweep, read_filter):
+def _tokens_for(path, cand, pieces, host_sweep, rules):
     """The candidate columns' modal tokens -> {pos: token or None}: the vote on the ranks' pieces; a sweep of the whole file on the
     host (tcmi_bam_load + tcmi_modal_tokens) when the caller says so (a rank could not collect its entries) or the vote meets a pair
-    of mates that only such a sweep resolves (status bit 2)."""
+    of mates that only such a sweep resolves (status bit 2); the sweep under the read filter of `rules` (the caller's ReadRules or None)."""
     toks, st = ({}, 2) if host_sweep else _vote(cand, pieces)
     if st & 2:
-        bam = BamFile(path, read_filter=read_filter)
+        bam = BamFile(path, read_filter=rules.read_filter if rules is not None else None)
         try:
             toks = {p: tk for p, (tk, _) in modal_tokens(bam, cand).items()}
         finally:
@@ -409,8 +408,8 @@ def _root_columns(ctx, counts_root, variants, root, group, multi):
 
 
 def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True, name="S", rank=0, world=1, device=0, group=None,
-                            step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, read_filter=None,
-                            min_baseq=None, primers=None, amplicon_reads=None, variant_strand=None, variant_links=None):
+                            step_fn=None, entries_fn=None, return_parts=False, rccl_user=None, ctx=None, dbam=None, timings=None, rules=None,
+                            amplicon_reads=None, variant_strand=None, variant_links=None):
     """BASELINE configs[4] all the way: ONE BAM file over `world` ranks -> its consensus FASTA text on rank 0 (None on the others).
     What the ranks jointly replace is the reference's single pile-up pass (indexing.py:96-100), its insert candidates' region
     pile-ups (Events.py:47-82) and the walk (Sequences.py:168-322):
@@ -434,11 +433,10 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
     return_parts: rank 0 gets (FASTA text, counts int32 [L,7], {candidate column: modal token}) — what the command line's other
     writers need (Outputs.WriteOutputs, Coverage.BuildCoverage).  ctx / dbam: the caller's (kept open: a bench loop); timings: a dict
     that receives the seconds of "step" (tcmi_split_step, reduce included) and "entries" (steps 2-4 up to the vote).
-    read_filter = (min_mapq, require_flags, exclude_flags): every rank sets the same one on its context (its read set keeps it for
-    step 3), and rank 0's host sweep of step 4 removes the failing records too.  min_baseq: the base-quality floor of the count
-    matrix, on every rank's context (Context.set_min_base_quality; 0 sets no floor, None leaves what the context has); the insert
-    tokens keep their own quality rule.  primers = (rows, slack): the primer table of the count matrix, on every rank's context
-    likewise (Context.set_primers; no rows clears it, None leaves what the context has).  Three counts behind the step, each taken by
+    rules: the ReadRules every rank sets on its context (Context.set_rules; None leaves what the context has).  Its read_filter: the
+    rank's read set keeps it for step 3, and rank 0's host sweep of step 4 removes the failing records too.  Its min_baseq and
+    primers: the base-quality floor and the primer table of the count matrix; the insert tokens keep their own quality rule.  Its
+    mate_overlap: refused by tcmi_split_step (a record's mate may lie in another rank's range).  Three counts behind the step, each taken by
     every rank in its own read set and summed to rank 0 over the same group (_sum_to_root), each one more item of rank 0's return_parts
     tuple, in this order: amplicon_reads = ([(fs, le, rs, fe)], slack): the records per amplicon (Context.amplicon_reads) -> the
     [n + 2, 2] int64 counts; variant_strand = the keyword arguments of Context.variants (ref, min_af, min_alt_depth, min_depth): rank 0
@@ -469,7 +467,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
                     ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)
                 if d is None:
                     d = DeviceBam(path)
-                ctx.apply(read_filter, min_baseq, primers)
+                ctx.set_rules(rules)
             except (TcmiError, OSError) as e:                        # this rank cannot even start: it must still meet the others in the reduce
                 err = (getattr(e, "code", _ffi_E_ARG), str(e))
             t = torch.zeros(n_words, dtype=torch.int32, device="cuda")
@@ -577,7 +575,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
         toks = {}
         if root:
             if cand:
-                toks = _tokens_for(path, cand, pieces, host_sweep, read_filter)
+                toks = _tokens_for(path, cand, pieces, host_sweep, rules)
             if timings is not None:
                 timings["entries"] = time.perf_counter() - t1
             text = _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks)
@@ -600,7 +598,7 @@ def consensus_split_bamfile(path, ref_len, gff_rows, mincov, include_ambig=True,
 
 
 def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=True, name="S", device=0, return_parts=False, timings=None,
-                        split_sub=None, read_filter=None, min_baseq=None, primers=None):
+                        split_sub=None, rules=None):
     """BASELINE configs[4] at ANY world size on the ONE GPU there is: the ranks' steps of a `world`-GPU job played one after the other
     on one context — rank world-1 first, rank 0 (the root) last — each through tcmi_split_step exactly as a rank of the real job runs
     it (its own contiguous range of the file's BGZF blocks + the block behind it, the range table and the failure word behind the
@@ -619,7 +617,7 @@ def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=Tr
     ctx = Context(device, stream=torch.cuda.current_stream().cuda_stream)
     if split_sub is not None:                                        # (tcmi_split_step's sub-ranges per rank: 0 = auto, 1 = never)
         ctx.set_option("split_sub", int(split_sub))
-    ctx.apply(read_filter, min_baseq, primers)                                # (every rank the same filter and base-quality floor)
+    ctx.set_rules(rules)                                             # (every rank the same rules)
     d = DeviceBam(path)
     acc = torch.zeros(n_words, dtype=torch.int32, device="cuda")
     t = torch.zeros(n_words, dtype=torch.int32, device="cuda")
@@ -666,7 +664,7 @@ def split_ranks_in_turn(path, ref_len, gff_rows, mincov, world, include_ambig=Tr
                 finally:
                     rs.free()
                     sets[rank] = None
-            toks = _tokens_for(path, cand, pieces, False, read_filter)
+            toks = _tokens_for(path, cand, pieces, False, rules)
         text = _fasta_from_records(name, mincov, gff_rows, plain, alt, flags, toks)
         if timings is not None:
             timings.update(rank_seconds=secs, blocks_per_rank=[block_range(d.n_blocks, r, world)[1] for r in range(world)],

@@ -9,7 +9,9 @@ Everything that computes goes through the C ABI (include/tcmi.h).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import dataclasses
 
 import numpy as np
 
@@ -17,12 +19,14 @@ from . import _ffi
 from ._ffi import check, lib, ptr
 
 
-def read_filter_args(read_filter):
-    """None or (min_mapq, require_flags, exclude_flags) -> three ints (None: 0, 0, 0, which passes everything)."""
-    if read_filter is None:
-        return 0, 0, 0
-    q, f, F = read_filter
-    return int(q), int(f), int(F)
+@dataclasses.dataclass(frozen=True)
+class ReadRules:
+    """Which tokens of a BAM reach the count matrix (csrc: struct tcmi_read_rules), one value from the command line to a context: read_filter =
+    (min_mapq, require_flags, exclude_flags), min_baseq, primers = (rows, slack), mate_overlap (Context.set_*); the defaults mean none of them."""
+    read_filter: tuple = None
+    min_baseq: int = 0
+    primers: tuple = None
+    mate_overlap: bool = False
 
 
 # struct tcmi_variant: one (position, non-reference allele) of the variant table
@@ -420,6 +424,7 @@ class Context:
     min_base_quality = 0
     primers = 0                     # rows of the table set_primers last set
     mate_overlap = False            # what set_mate_overlap last set
+    read_rules = ReadRules()        # ... and the four as one value: what the context's next read set is built under
 
     def __init__(self, device=0, stream=None):
         """stream: a hipStream_t as an int (0 = the default stream) to run on, e.g. another Context's
@@ -479,6 +484,7 @@ class Context:
         device-decoded file ignores the records that fail it, as it ignores unmapped ones.  No arguments: no filter."""
         check(lib().tcmi_ctx_set_read_filter(self.handle, int(min_mapq), int(require_flags), int(exclude_flags)), self.handle)
         self.read_filter = (int(min_mapq), int(require_flags), int(exclude_flags))
+        self.read_rules = dataclasses.replace(self.read_rules, read_filter=self.read_filter if any(self.read_filter) else None)
 
     def set_min_base_quality(self, q=0):
         """Base-quality floor (tcmi_ctx_set_min_base_quality; samtools mpileup -Q): from now on every read set this context builds
@@ -486,6 +492,7 @@ class Context:
         q > 0 the flat-array entry points (upload, tally, the array Pipeline) refuse with E_UNSUPPORTED.  No argument: no floor."""
         check(lib().tcmi_ctx_set_min_base_quality(self.handle, int(q)), self.handle)
         self.min_base_quality = int(q)
+        self.read_rules = dataclasses.replace(self.read_rules, min_baseq=int(q))
 
     def set_primers(self, rows=None, slack=0):
         """Amplicon primer mask (tcmi_ctx_set_primers; what `ivar trim` does to a BAM): rows = (start, end, reverse) on the count
@@ -499,6 +506,7 @@ class Context:
         r_ = np.ascontiguousarray([int(r[2]) if isinstance(r[2], (bool, int, np.integer)) else int(r[2] == "-") for r in rows], np.int32)
         check(lib().tcmi_ctx_set_primers(self.handle, len(rows), ptr(s_), ptr(e_), ptr(r_), int(slack)), self.handle)
         self.primers = len(rows)
+        self.read_rules = dataclasses.replace(self.read_rules, primers=(tuple(rows), int(slack)) if rows else None)
 
     def set_mate_overlap(self, on=False):
         """Mate overlap (tcmi_ctx_set_mate_overlap; what samtools mpileup does by default): from now on every read set this context
@@ -507,18 +515,24 @@ class Context:
         and the split step refuse with E_UNSUPPORTED.  No argument: off."""
         check(lib().tcmi_ctx_set_mate_overlap(self.handle, int(bool(on))), self.handle)
         self.mate_overlap = bool(on)
+        self.read_rules = dataclasses.replace(self.read_rules, mate_overlap=bool(on))
 
-    def apply(self, read_filter=None, min_baseq=None, primers=None, mate_overlap=None):
-        """A job's read_filter = (min_mapq, require_flags, exclude_flags), min_baseq, primers = (rows, slack) (set_primers; no rows
-        clears the table) and mate_overlap (set_mate_overlap) onto this context; None leaves what it has."""
-        if mate_overlap is not None:
-            self.set_mate_overlap(mate_overlap)
-        if read_filter is not None:
-            self.set_read_filter(*read_filter_args(read_filter))
-        if min_baseq is not None:
-            self.set_min_base_quality(min_baseq)
-        if primers is not None:
-            self.set_primers(*primers)
+    def set_rules(self, rules=None):
+        """A job's ReadRules onto this context, all four, nothing restored (a context that lives for the job); None leaves what it has."""
+        if rules is not None:
+            self.set_mate_overlap(rules.mate_overlap)
+            self.set_read_filter(*(rules.read_filter or ()))
+            self.set_min_base_quality(rules.min_baseq)
+            self.set_primers(*(rules.primers or ()))
+
+    @contextlib.contextmanager
+    def rules(self, rules):
+        """with ctx.rules(r): under r inside the block, under none behind it however it ends (a context that serves other jobs afterwards)."""
+        try:
+            self.set_rules(rules)
+            yield self
+        finally:
+            self.set_rules(ReadRules())
 
     def set_variants(self, ref=None, min_af="0.03", min_alt_depth=1, min_depth=10):
         """Variant table (tcmi_ctx_set_variants): from now on every step of this context (step, bamfile_step) also lists, per position
@@ -1056,7 +1070,7 @@ class BamFile:
         n0, gone = C.c_int64(0), C.c_int64(0)
         check(lib().tcmi_bam_info(h, C.byref(n0), None, None, None, None, None, None))
         if read_filter is not None:
-            check(lib().tcmi_bam_filter(h, *read_filter_args(read_filter), C.byref(gone)))
+            check(lib().tcmi_bam_filter(h, *(int(x) for x in read_filter), C.byref(gone)))
         self.n_records, self.n_removed = n0.value, gone.value
         self.filename = str(path)
         n_ref, name, ln = C.c_int32(0), C.c_char_p(), C.c_int64(0)
@@ -1190,11 +1204,12 @@ class FileRunner:
     A file the device decoder does not take (records straddling BGZF blocks, long reads) is decoded by the host reader
     (tcmi_bam_load, `decode_threads` threads) and packed from its flat arrays.  `seconds` accumulates each stage's busy time."""
 
-    def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, read_filter=None,
-                 min_baseq=0, primers=None, variants=None, intervals=None, mate_overlap=None):
-        """variants: the keyword arguments of Context.set_variants (ref, min_af, min_alt_depth, min_depth), set on every context of the
-        runner: run_files(table=...) then writes each sample's variant table.  intervals = ([(start, end)], min_depth)
-        (Context.set_intervals), likewise: run_files(stats=True) then returns every sample's interval records."""
+    def __init__(self, ctx, gff_rows, mincov, include_ambig=True, decoders=2, decode_threads=8, walkers=2, gpu_streams=2, rules=None,
+                 variants=None, intervals=None):
+        """rules: the ReadRules of the runner's files, set on every context of the runner (Context.set_rules).  variants: the keyword
+        arguments of Context.set_variants (ref, min_af, min_alt_depth, min_depth), set on every context likewise: run_files(table=...)
+        then writes each sample's variant table.  intervals = ([(start, end)], min_depth) (Context.set_intervals), likewise:
+        run_files(stats=True) then returns every sample's interval records."""
         device = ctx.device if isinstance(ctx, Context) else int(ctx)
         self.mincov, self.amb = int(mincov), bool(include_ambig)
         h = C.c_void_p()
@@ -1213,7 +1228,7 @@ class FileRunner:
         # the device path is refused, never tallied without it
         self.variant_records = 0        # records of the tables run_files wrote
         for c in self.contexts:
-            c.apply(read_filter, min_baseq or None, primers, mate_overlap)
+            c.set_rules(rules)
             if variants:
                 c.set_variants(**variants)
             if intervals:

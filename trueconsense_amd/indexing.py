@@ -39,7 +39,7 @@ def Override_index_positions(index, override_data):
 def device_readset(ctx, path, blocks=None, need=None):
     """The device path, or why not: the file at `path` (blocks = (first, count): that range of its BGZF blocks) decoded and packed by
     ctx's device decoder -> ReadSet; None when the decoder declines the file (E_UNSUPPORTED) and the host reader may take it.  Under
-    a base-quality floor (ctx.min_base_quality), a primer table (ctx.primers) or the mate-overlap rule (ctx.mate_overlap) the host reader may not: the refusal is raised with its
+    a base-quality floor, a primer table or the mate-overlap rule (ctx.read_rules, in that order) the host reader may not: the refusal is raised with its
     reason; likewise when the caller names a flag that `need`s the device path (--amplicon-reads counts in the decoded stream)."""
     d = DeviceBam(path)
     try:
@@ -47,19 +47,13 @@ def device_readset(ctx, path, blocks=None, need=None):
     except _ffi.TcmiError as e:
         if e.code != _ffi.E_UNSUPPORTED:
             raise
-        q = ctx.min_base_quality
-        if q:
-            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--min-baseq %d needs the device path (the host packer knows no base-quality floor), "
-                                 "which %s left: %s" % (q, path, e)) from e
-        if getattr(ctx, "primers", 0):              # (a context of before the table has none)
-            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--primers needs the device path (the host packer knows no primer mask), "
-                                 "which %s left: %s" % (path, e)) from e
-        if getattr(ctx, "mate_overlap", False):
-            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "--mate-overlap needs the device path (the host packer joins no mates), "
-                                 "which %s left: %s" % (path, e)) from e
-        if need:
-            raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "%s needs the device path (it counts the records in the stream the device decoded), "
-                                 "which %s left: %s" % (need, path, e)) from e
+        r = ctx.read_rules
+        for flag, why in ((r.min_baseq and "--min-baseq %d" % r.min_baseq, "the host packer knows no base-quality floor"),
+                          (r.primers and "--primers", "the host packer knows no primer mask"),
+                          (r.mate_overlap and "--mate-overlap", "the host packer joins no mates"),
+                          (need, "it counts the records in the stream the device decoded")):
+            if flag:                                # (the first in this order: the floor, the table, the mate rule, the caller's flag)
+                raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "%s needs the device path (%s), which %s left: %s" % (flag, why, path, e)) from e
         return None
     finally:
         d.close()
@@ -90,7 +84,7 @@ def build_counts(bamfile, ref, ctx=None, on_readset=None, need_device=None):
                 return counts
             finally:
                 rs.free()
-        flt = getattr(ctx, "read_filter", None)
+        flt = ctx.read_rules.read_filter
         if isinstance(bamfile, LazyBam) and bamfile.read_filter is None:
             bamfile.read_filter = flt
         bamfile = bamfile.get() if isinstance(bamfile, LazyBam) else BamFile(path, read_filter=flt)

@@ -28,7 +28,7 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import (GetArgs, StreamCounts, amplicon_intervals, amplicons_of, primers_of, read_filter_of, variants_of,
+    from .TrueConsense import (GetArgs, StreamCounts, amplicon_intervals, amplicons_of, rules_of, variants_of,
                                write_amplicon_reads, write_amplicon_table, write_variant_tables)
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
@@ -52,8 +52,7 @@ def main(argv=None):
         refID, refseq = fasta.read_first_record(a.reference)
         want = StreamCounts(a)                                       # (an unusable scheme ends every rank here, before the step)
         parts = td.consensus_split_bamfile(a.input, len(refseq), rows, a.coverage_level, a.noambiguity is False, a.samplename, rank, world,
-                                           device=device, return_parts=True, rccl_user=user, read_filter=read_filter_of(a), min_baseq=a.min_baseq,
-                                           primers=primers_of(a), **want.split_kwargs(refseq))
+                                           device=device, return_parts=True, rccl_user=user, rules=rules_of(a), **want.split_kwargs(refseq))
         if rank == 0:
             _, counts, toks = parts[:3]
             got, recs = want.from_parts(parts)                       # (the ranks' counts, summed: a record starts in one rank's blocks)
