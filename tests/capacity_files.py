@@ -1,6 +1,6 @@
 """Valid BAM files beyond the capacities the one-sync file path (pk_index + pk_place + pk_pack, tcmi_bamfile_step) sizes its device
-arrays for before anybody has seen the file, one per rung of the ladder behind it (pack_device.hip tcmi_pack_fused_enqueue,
-bam_device.hip fast_enqueue):
+arrays for before anybody has seen the file, one per rung of the ladder behind it (csrc/pack_caps.h: pk_one_sync_caps and the
+PKF_* flags; tests/test_pack_caps.py holds the header's own numbers against the restatement below):
 
     rec_cap    min(inflated / 64 + 1024, inflated / 36 + 16, inflated / hint * 5 / 4 + 8192)     PKF_REC_OVF    0x800
     word_cap   inflated / 24 + 8 * rec_cap + 64                                                   PKF_WORD_OVF   64

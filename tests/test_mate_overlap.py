@@ -126,6 +126,24 @@ def test_the_read_set_remembers_and_every_run_gives_the_same(ctx, store):
             check(ctx, rs, y)
 
 
+def test_one_sync_packer_with_every_array_of_its_scratch(ctx, store):
+    """the largest list the one-sync packer takes from the arena (csrc/pack_caps.h pk_one_sync_scratch), all at once: the mate join's
+    table and clip, and pk_prefix's three arrays, which a file of a few blocks gets only when the option asks for them; under a primer
+    table and a read filter (pk_place_bq, pk_mask_long)"""
+    path, _ = data(store, "cases")
+    d = engine.DeviceBam(path)
+    assert 1 < d.n_blocks < 16384                               # (several workgroups; the prefix kernels are the option's doing)
+    d.close()
+    y = yard(store, "cases", "primers_filter")
+    try:
+        ctx.set_option("prefix_kernels", 1)
+        with uploaded(ctx, path, "primers_filter", "one_sync") as rs:
+            assert rs.route == "one_sync"
+            check(ctx, rs, y)
+    finally:
+        ctx.set_option("prefix_kernels", 0)
+
+
 # ---- mates in different BGZF blocks and workgroups -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("how", dvf.PACKERS)
 def test_mates_in_different_blocks(ctx, store, how):

@@ -44,7 +44,7 @@ def test_the_two_caps_stand_in_the_source_where_the_scale_tests_read_them():
     pack = open(os.path.join(rb.CSRC, "pack_device.hip")).read()
     launches = re.findall(r"hipLaunchKernelGGL\(pk_mask_long,\s*dim3\((\w+)\),\s*dim3\((\w+)\)", pack)
     assert launches and set(launches) == {(str(rb.MASK_LONG_GRID), "PB")}, ("pk_mask_long's launch changed: adjust file B of tests/test_stream_scale.py", launches)
-    assert re.search(r"\bPKF_EVENT_OVF\s*=\s*%d\s*," % dvf.PKF_EVENT_OVF, pack), "dvf.PKF_EVENT_OVF changed: tests/test_stream_scale.py admits that decline by its number"
+    assert re.search(r"\bPKF_EVENT_OVF\s*=\s*%d\s*," % dvf.PKF_EVENT_OVF, open(os.path.join(rb.CSRC, "pack_caps.h")).read()),"dvf.PKF_EVENT_OVF changed: tests/test_stream_scale.py admits that decline by its number"
     pb = re.search(r"constexpr\s+int\s+PB\s*=\s*(\d+)\s*;", pack)
     assert pb and int(pb.group(1)) == rb.MASK_LONG_BLOCK, "PB changed: adjust file B of tests/test_stream_scale.py"
 

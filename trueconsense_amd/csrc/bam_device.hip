@@ -169,10 +169,9 @@ struct Decoded {
     uint64_t *d_base = nullptr;
     unsigned long long *d_total = nullptr;
 };
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-// arena bytes of everything that is sized per record: the several-kernel path's arrays (rec_off + 12 words) — the one-pass packer's are fewer
-// (mate: + the mate join's table, clip[] and counters)
-inline size_t rest_bytes(size_t n_rec, size_t nb, bool mate) { return (mate ? tcmi_mate_bytes(n_rec + 1) : 0) + al256(n_rec * 8 + 8) + al256(n_rec * 4 + 4) * 12 + al256((n_rec / 256 + 2) * 8) * 3 + al256(nb * 33 + 64) + al256(nb * 8) * 4 + al256(nb * 4) + 8192 + 32 * 256; }
+// arena bytes of what the packers take behind the decoder's own pieces (pack_caps.h lists both packers' arrays): the several-kernel
+// packer's for n_rec records, the record index included
+inline size_t several_bytes(const tcmi_ctx *ctx, size_t n_rec) { return pk_several_scratch((int64_t)n_rec, 1, ctx->rules.mate != 0).end(0); }
 
 // blocks [first, first + count) of the file (count < 0: to the end): the records that START in them.  A range that does not end
 // with the file takes one block more along — the last record may run into it — whose own records are left out.
@@ -212,10 +211,9 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
     const size_t nb = f->blocks.size(), nb_own = ranged ? (size_t)own : nb;
     D.nb = nb; D.nb_own = nb_own;
     if (nb == 0) return TCMI_OK;
-    // bounds on the records for the arena: a record takes at least 36 bytes of the stream; reserve for records of >= 64 bytes
-    // (block_size + 32 fixed bytes + name + CIGAR + SEQ + QUAL of a 15-base read) — the arena cannot grow under live data
-    D.max_rec = f->inflated / 36 + 16;
-    D.guess_rec = std::min(D.max_rec, f->inflated / 64 + 1024);
+    // bounds on the records for the arena (pack_caps.h): the most the stream can hold, and what is reserved for
+    D.max_rec = (size_t)pk_most_records(f->inflated);
+    D.guess_rec = (size_t)pk_guess_records(f->inflated);
     const bool resident = f->d_bytes != nullptr && f->d_device == ctx->device;       // (the compressed bytes are in HBM already)
     // The tokens of a block in flight take 3 - 10 times its inflated bytes (a token per literal, as many again of scratch for the
     // speculating lanes): a file whose blocks need more than the context's token scratch ("decode_token_mb") is decoded in batches
@@ -238,7 +236,9 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
     const size_t b_file = resident ? 256 : tcmi_align256(f->cap), b_desc = tcmi_align256(nb * sizeof(BlockDesc)),
                  b_out = tcmi_align256(f->inflated + 128), b_slot = tcmi_align256(nb * (size_t)MAX_REC_PER_BLOCK * 4),
                  b_small = b_nb4 * 5 + b_nb8 + tcmi_align256(nb * 512) + 256, b_tok = tcmi_align256(tok_words * 4 + 256);
-    D.b_rest = rest_bytes(worst_case ? D.max_rec : D.guess_rec, nb, ctx->rules.mate != 0);
+    // whichever packer comes: the one-sync packer's capacity is never above the records reserved for (pk_one_sync_caps)
+    const int64_t res_rec = (int64_t)(worst_case ? D.max_rec : D.guess_rec);
+    D.b_rest = std::max(several_bytes(ctx, (size_t)res_rec), pk_one_sync_scratch(res_rec, (int64_t)nb, ctx->rules.mate != 0, pk_prefix_on(ctx->prefix_kernels, (int64_t)nb)).end(0));
     if (tcmi_arena_reserve(ctx, b_file + b_desc + b_out + b_slot + b_small + b_tok + D.b_rest + 16 * 256)) return TCMI_E_NOMEM;
     uint8_t *d_file = (uint8_t *)tcmi_arena_take(ctx, b_file);
     D.d_desc = (BlockDesc *)tcmi_arena_take(ctx, b_desc);
@@ -381,13 +381,13 @@ int decode_on_device(tcmi_ctx *ctx, const tcmi_bamfile *whole, DeviceBam *Dout, 
     Dout->range_first = v.range_first; Dout->range_next = v.range_next;
     if (total > max_rec) return tcmi_fail(ctx, TCMI_E_FORMAT, "%s: impossible record count", f->path.c_str());
     const size_t n = (size_t)total;
-    const size_t need_rest = rest_bytes(n, nb, ctx->rules.mate != 0);
+    const size_t need_rest = several_bytes(ctx, n);
     // records of fewer than 64 bytes on average (single-base reads with one-letter names): the arena cannot grow under live data, but
     // the host has just waited and nothing is in flight — the file is decoded once more into an arena reserved for the worst case
     if (need_rest > b_rest && !worst_case) return decode_on_device(ctx, whole, Dout, first_blk, count, true);
     if (need_rest > b_rest)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: %zu very short records need more device scratch than was reserved: host reader", f->path.c_str(), n);
-    uint64_t *d_rec = (uint64_t *)tcmi_arena_take(ctx, tcmi_align256(n * 8 + 8));
+    uint64_t *d_rec = (uint64_t *)tcmi_arena_take(ctx, pk_several_scratch((int64_t)n, 1, false).bytes[SK_REC_OFF]);
     tcmi_prof_begin(ctx, TCMI_K_RECORDS);
     if (n) hipLaunchKernelGGL(rec_compact, dim3((unsigned)nb_own), dim3(256), 0, ctx->stream, d_desc, d_slot, d_nrec, d_base, d_rec);
     tcmi_prof_end(ctx, TCMI_K_RECORDS);
@@ -461,12 +461,11 @@ int fast_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first_block, int6
     if (rc) return rc;
     J.d_stream = D.d_out; J.stream_len = D.f->inflated; J.d_desc = D.d_desc; J.d_slot = D.d_slot; J.d_nrec = D.d_nrec; J.d_first = D.d_first;
     J.d_over = D.d_over; J.d_stat = D.d_stat; J.n_blocks = (int64_t)D.nb; J.n_own = (int64_t)D.nb_own; J.ranged = D.ranged ? 1 : 0;
-    // records: from the mean size of the file's first records (+ 25 %) where the host saw enough of them, else as the arena was reserved
-    J.rec_cap = (int64_t)D.guess_rec;
-    // (a file whose header fills its first block shows the host no record: the last file of this context stands in — files of a
-    //  batch are alike, and a file beyond the capacity takes the several-kernel path)
-    const uint32_t hint = f->rec_bytes_hint >= 36 ? f->rec_bytes_hint : ctx->rec_bytes_seen;
-    if (hint >= 36 && !safe_caps) J.rec_cap = std::min<int64_t>(J.rec_cap, (int64_t)(D.f->inflated / hint) * 5 / 4 + 8192);
+    // records: from the mean size of the file's first records where the host saw enough of them, else as the arena was reserved
+    // (pack_caps.h: pk_one_sync_caps).  A file whose header fills its first block shows the host no record: the last file of this
+    // context stands in — files of a batch are alike, and a file beyond the capacity takes the several-kernel path
+    J.rec_hint = f->rec_bytes_hint >= 36 ? f->rec_bytes_hint : ctx->rec_bytes_seen;
+    J.safe_caps = safe_caps;
     J.len_bound = (f->ref_len.empty() ? 0 : f->ref_len[0]) + 65536;
     rs->uid = g_next_uid.fetch_add(1);
     rs->device = ctx->device;
@@ -531,7 +530,7 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
         }
         tcmi_readset_free(ctx, rs);
         if (rc != TCMI_E_UNSUPPORTED) return rc;
-        if (attempt == 0 && (why & 0x800u)) { ctx->rec_bytes_seen = 0; ++ctx->stat_one_sync_retried; continue; }     // (PKF_REC_OVF: records shorter than the hint said — once more, sized for the worst case)
+        if (attempt == 0 && (why & PKF_REC_OVF)) { ctx->rec_bytes_seen = 0; ++ctx->stat_one_sync_retried; continue; }     // (records shorter than the hint said — once more, sized for the worst case)
         ++ctx->stat_one_sync_declined; ctx->stat_last_decline = why;
         if (timing) std::fprintf(stderr, "[tcmi bamfile] one-sync path declined (flags 0x%x): the several-kernel path\n", why);
         break;
@@ -567,7 +566,7 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
         return TCMI_OK;
     }
     tcmi_readset_free(ctx, rs);
-    if (rc == TCMI_E_UNSUPPORTED && !(why & (1u << 13)))        // (PKF_SLOT_OVF: the packer's own words name the read and the reference)
+    if (rc == TCMI_E_UNSUPPORTED && !(why & PKF_SLOT_OVF))      // (the packer's own words name the read and the reference)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: the device packer declined (flags 0x%x: long reads, far positions, a second reference or malformed reads): host reader",
                          f->path.c_str(), why);
     return rc;
@@ -662,7 +661,7 @@ int tcmi_bamfile_step(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t ref_len, int
         }
         tcmi_readset_free(ctx, rs);
         if (rc != TCMI_E_UNSUPPORTED) return rc;
-        if (attempt == 0 && (why & 0x800u)) { ctx->rec_bytes_seen = 0; ++ctx->stat_one_sync_retried; continue; }     // (PKF_REC_OVF: once more, sized for the worst case)
+        if (attempt == 0 && (why & PKF_REC_OVF)) { ctx->rec_bytes_seen = 0; ++ctx->stat_one_sync_retried; continue; }     // (once more, sized for the worst case)
         ++ctx->stat_one_sync_declined; ctx->stat_last_decline = why;
         break;
     }

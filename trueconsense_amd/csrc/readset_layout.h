@@ -2,8 +2,11 @@
 // the host packer (host_pack.cpp) and a program around it build without one.  tcmi_internal.h includes it.
 #pragma once
 #include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <vector>
+
+static inline size_t tcmi_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }     // the pieces of device buffers start on 256 bytes
 
 // ---- several contigs on one coordinate axis (tcmi_ctx_set_layout) --------------------------------------------------
 // Reference t's reads pile up at pos + shift[t]; shift[t] < 0: they do not pile up (a reference the caller has no record of);

@@ -13,6 +13,7 @@
 #include "../../include/tcmi.h"
 #include "variants_rule.h"           // the variant table's rule (GPU-free; shared with the host checks)
 #include "readset_layout.h"          // tcmi_layout, the packed read set (TCMI_F_* / TCMI_P_*, tcmi_fast_chunk), the chunk geometry
+#include "pack_caps.h"               // the device packer's decline flags, capacities and arena scratch (GPU-free; shared with the host checks)
 
 // checks n_ref / shift / slot_len (slots in ascending order, disjoint, below TCMI_F_EVPOS) and fills *out; TCMI_OK or TCMI_E_ARG
 int tcmi_layout_build(int32_t n_ref, const int64_t *shift, const int64_t *slot_len, tcmi_layout *out, char *msg, size_t msg_cap);
@@ -426,15 +427,16 @@ struct tcmi_fused_job {
     const int32_t *d_over = nullptr;
     int64_t n_blocks = 0, n_own = 0;
     int ranged = 0;
-    int64_t rec_cap = 0;                // records the arrays are sized for
-    int64_t len_bound = 0;              // positions the reads may reach (chunk capacity)
+    uint32_t rec_hint = 0;              // mean size of the file's first records (< 36: none)   } what the capacities are worked out
+    bool safe_caps = false;             // sized as the arena was reserved, not from the hint     } from: pack_caps.h pk_one_sync_caps
+    int64_t len_bound = 0;              // positions the reads may reach (chunk capacity)         }
     // out (enqueue)
+    PkCaps caps = {};                   // what the arrays are sized for
     char *h_pin = nullptr;              // pinned: PackTotals | per-block partials (filled by the copies queued behind the kernels)
     void *d_tot = nullptr;
     uint64_t *d_rec = nullptr;
     uint32_t *c_idx = nullptr, *gen_idx = nullptr;
     int32_t *c_pos = nullptr;
-    uint32_t chunk_cap = 0, event_cap = 0, word_cap = 0;
     const void *d_blk_alg = nullptr, *d_blk_end = nullptr;
     const void *d_mate_cnt = nullptr;   // the mate join's four counters (null: the setting is off); the report brings them along
 };
@@ -457,15 +459,12 @@ struct tcmi_mate_job {
                                         // counters (tcmi_mate_counters): one memset zeroes both
     uint32_t *clip;                     // out [rec_cap]
 };
-static inline size_t tcmi_mate_slots(size_t rec_cap) { size_t s = 1024; while (s < 2 * rec_cap) s <<= 1; return s; }
-// arena bytes of the table, clip[] and the counters for rec_cap records
-static inline size_t tcmi_mate_table_bytes(size_t rec_cap) { return tcmi_mate_slots(rec_cap) * 8 + 256; }
+// (the table's and clip[]'s arena bytes: pack_caps.h)
 static inline const unsigned long long *tcmi_mate_counters(const tcmi_mate_job &job) { return job.table + tcmi_mate_slots(job.rec_cap); }
-static inline size_t tcmi_mate_bytes(size_t rec_cap) { return tcmi_mate_table_bytes(rec_cap) + ((rec_cap * 4 + 4 + 255) & ~(size_t)255) + 3 * 256; }
 int tcmi_mate_join_enqueue(tcmi_ctx *ctx, const tcmi_mate_job &job);
 
 // the context's device arena (api.cpp): _reserve hands it out anew, `bytes` large (whatever lived in it is gone: arena_epoch tells);
-// _take carves the next piece, 256-byte aligned — the takers check `used > cap` once they have taken all
+// _take carves the next piece, 256-byte aligned — the packers sum a list's pieces against `cap` before they take them (pack_caps.h: PkScratch)
 int tcmi_arena_reserve(tcmi_ctx *ctx, size_t bytes);
 void *tcmi_arena_take(tcmi_ctx *ctx, size_t bytes);
 // kernels (tally.hip / call.hip)
@@ -499,4 +498,3 @@ struct tcmi_iv_job {
 int tcmi_launch_intervals(tcmi_ctx *ctx, const tcmi_iv_job &job);
 
 static inline int64_t tcmi_round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-static inline size_t tcmi_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }     // the pieces of device buffers start on 256 bytes
