@@ -269,6 +269,49 @@ int  tcmi_primers_compile(int32_t n, const int64_t *start, const int64_t *end, c
 int  tcmi_ctx_set_mate_overlap(tcmi_ctx *ctx, int32_t on);
 int  tcmi_readset_mate_overlap(const tcmi_readset *rs, int32_t *on, int64_t *pairs, int64_t *clipped_reads, int64_t *clipped_columns,
                                int64_t *ambiguous);
+/* ---- duplicate templates (additive: what samtools markdup / Picard MarkDuplicates do in a pass of their own) -----------------------
+ * Under this setting the records of a duplicate template add nothing to the count matrix.  The rule is exact and integer only; which
+ * templates exist does not depend on the order of the file, only the stated tie-break does (csrc/dedup_rule.h holds its text).  It
+ * concerns the KEPT records of a device-decoded stream (mapped, through the read filter, consistent, on a reference that piles up,
+ * reference span > 0):
+ *   examined   kept records without FLAG 0x100 / 0x800: secondary and supplementary records are never duplicates and never stand
+ *              for a template (samtools' default)
+ *   end        of a record: (refID, u5, rev).  rev is FLAG 0x10; u5 the unclipped 5' coordinate on the record's own reference, not
+ *              the shifted axis: forward pos - (sum of leading S and H lengths), reverse pos + span - 1 + (sum of trailing S and H
+ *              lengths).  u5 is signed and may be negative (kept in 32 bits, saturating).
+ *   score      of a record: the sum of its QUAL bytes >= 15 (Picard's SUM_OF_BASE_QUALITIES); a byte of 0xFF is a missing quality
+ *              and adds nothing, so a QUAL of all 0xFF scores 0, as l_seq == 0 does; saturates at 2^32 - 1
+ *   templates  a pair is exactly a pair of the mate join above (group of two, eligible, the pair test) — whether or not the mate
+ *              rule is on; every other examined record is a fragment (unpaired, mate unmapped or filtered away, not proper, a
+ *              member of an ambiguous group, ...).  A pair's leader is its record with the lower record index; a fragment leads
+ *              itself.  A pair's score is the sum of both records' scores, saturating likewise.
+ *   key        fragment (F, refID, u5, rev); pair (P, refID, end_a, end_b) with the two ends ordered by (u5, rev) — which end is
+ *              read 1 plays no part.  Fragments and pairs never share a key.
+ *   winner     of the templates of one key the highest score wins, at equal score the template whose leader has the lowest record
+ *              index.  Every other template of the key is a duplicate, and all its records — both mates of a pair — are.
+ *   effect     clip[i] = max(clip[i], span(i)) for a duplicate record: it is clipped from end to end, and everything said of that
+ *              under the mate rule holds (piled up, adds nothing; the piled-up count, the extent and the per-reference extents are
+ *              unchanged).  It combines with the floor, the primer table, the read filter and the mate rule by OR; with the mate
+ *              rule also on a surviving pair still gets its overlap clip.
+ * Deviations from samtools markdup and Picard MarkDuplicates, on purpose: pairs are only the join's pairs, which requires 0x2; a
+ * fragment does not lose to a pair that has an end at its place (both tools let it); there is no optical-distance rule; the mate's end
+ * is taken from the mate's own record, not from an MC tag; nothing is written back, there is no marked BAM; the insert-candidate
+ * sweeps' region pileup (tcmi_readset_modal_tokens and kin) keeps its own pileup and is not touched, exactly as under the mate rule.
+ *   tcmi_ctx_set_dedup   on = 0 / 1 (anything else: TCMI_E_ARG); from now on governs the read sets the floor governs.  A read set
+ *                     REMEMBERS the setting and, while its decoded stream is resident, the verdicts: the stream-walking calls count
+ *                     under the rule.  While on, whatever would tally WITHOUT the rule, or where a template's other records may lie
+ *                     outside what is decoded, refuses with TCMI_E_UNSUPPORTED and a message naming --dedup: the entry points that
+ *                     refuse under the mate rule.  tcmi_readset_amplicon_reads asks only which records are kept and counts
+ *                     duplicates as before.  Off: the launches of before.
+ *   tcmi_readset_dedup   the setting the read set was built under and the counters: examined templates, duplicate templates,
+ *                     duplicate records, keys with at least two templates (any pointer may be NULL)
+ *   tcmi_readset_duplicates   one byte per record of the stream, 1: a duplicate, into out[cap] (cap >= the records, else
+ *                     TCMI_E_ARG), *n the records; on the context that holds the stream, while it is resident: TCMI_E_UNSUPPORTED
+ *                     once another upload happened there, or when the read set was built without the rule */
+int  tcmi_ctx_set_dedup(tcmi_ctx *ctx, int32_t on);
+int  tcmi_readset_dedup(const tcmi_readset *rs, int32_t *on, int64_t *templates, int64_t *dup_templates, int64_t *dup_records,
+                        int64_t *dup_sets);
+int  tcmi_readset_duplicates(tcmi_ctx *ctx, const tcmi_readset *rs, uint8_t *out, int64_t cap, int64_t *n);
 /* ---- variant table (additive: what `ivar variants` reports; the reference has only the consensus and its -vcf) ---------------
  * Every non-reference allele of a position at or above a frequency, with its depth, taken from the count matrix where it lies.
  * All arithmetic is integer.  With the matrix (plane order TCMI_COV..TCMI_I), a reference byte string ref[0..n_ref) on the
@@ -644,7 +687,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_LINK_COUNTS = 14 /* tcmi_readset_link_counts' one launch */,
        TCMI_K_INDEL_EVENTS = 15 /* tcmi_readset_indel_events' launches (count, verify, gather) of one attempt as one bracket */,
        TCMI_K_EVIDENCE_COUNTS = 16 /* tcmi_readset_evidence_counts' one launch */,
-       TCMI_K_MATE_JOIN = 17 /* the mate join's table reset and two launches (build, probe) as one bracket */,
+       TCMI_K_MATE_JOIN = 17 /* the mate join's table reset and two launches (build, probe) as one bracket; under the duplicate rule
+                                "join + dedup": its table reset and three launches (ends, build, mark) behind them, in the same bracket */,
        TCMI_K_NKERNELS = 18 };
 int  tcmi_profile_enable(tcmi_ctx *ctx, int on);
 int  tcmi_profile_reset(tcmi_ctx *ctx);

@@ -487,7 +487,7 @@ def primers_of(a, layout=None):
 def rules_of(a, layout=None):
     """The parsed namespace's read rules -> engine.ReadRules (layout: primers_of's)."""
     from .engine import ReadRules
-    return ReadRules(read_filter_of(a), a.min_baseq, primers_of(a, layout), a.mate_overlap)
+    return ReadRules(read_filter_of(a), a.min_baseq, primers_of(a, layout), a.mate_overlap, getattr(a, "dedup", False))
 
 
 def GetArgs(givenargs):
@@ -553,6 +553,11 @@ def GetArgs(givenargs):
                                                     "mate that starts further right loses them (samtools mpileup's default; by position, qualities\n"
                                                     "are not summed), joined by read name on the device; needs the device decoder; not with\n"
                                                     "-i --gpus N")))
+    additive.append((("--dedup",), dict(action="store_true",
+                                        help="ignore duplicate templates in the count matrix (samtools markdup, Picard MarkDuplicates): of the\n"
+                                             "fragments with one unclipped 5' end and strand, and of the proper pairs with the same two, the one\n"
+                                             "with the highest sum of base qualities >= 15 is kept, found on the device; nothing is written back;\n"
+                                             "needs the device decoder; not with -i --gpus N, not with --amplicon-reads")))
     additive.append((("--primers",), dict(type=str, default=None, metavar="File",
                                           help="BED of the amplicon scheme's primers (chrom, start, end, name, pool, strand): a read's tokens\n"
                                                "inside the primer at its head ('+') or tail ('-') stay out of the count matrix\n"
@@ -663,6 +668,10 @@ def GetArgs(givenargs):
                 sys.exit(1)
     if a.mate_overlap and a.batch is None and a.gpus and a.gpus > 1:
         parser.error("--mate-overlap does not go with -i --gpus N: a record's mate may lie in another rank's block range.")
+    if a.dedup and a.batch is None and a.gpus and a.gpus > 1:
+        parser.error("--dedup does not go with -i --gpus N: a template's other records may lie in another rank's block range.")
+    if a.dedup and a.amplicon_reads is not None:
+        parser.error("--dedup does not go with --amplicon-reads: that count asks only which records are kept and would count the duplicates.")
     if a.batch is not None and a.variant_table is not None:
         parser.error("--variant-table goes with a single sample (-i); with --batch the manifest's 7th column names each sample's table.")
     if a.batch is None and a.variant_table is None and a.variant_thresholds_given:
@@ -695,6 +704,13 @@ def mate_stats(on, counters):
     c = counters or {}
     return {"mate_overlap": bool(on), "mate_pairs": int(c.get("pairs", 0)), "reads_mate_clipped": int(c.get("clipped_reads", 0)),
             "columns_mate_clipped": int(c.get("clipped_columns", 0)), "mate_ambiguous": int(c.get("ambiguous", 0))}
+
+
+def dedup_stats(on, counters):
+    """The --stats keys of --dedup from a read set's counters (ReadSet.dedup; None: none were fetched)."""
+    c = counters or {}
+    return {"dedup": bool(on), "dedup_templates": int(c.get("templates", 0)), "duplicate_templates": int(c.get("duplicate_templates", 0)),
+            "duplicate_records": int(c.get("duplicate_records", 0)), "duplicate_sets": int(c.get("duplicate_sets", 0))}
 
 
 def _spawn(cmds, envs):
@@ -744,6 +760,8 @@ def _child_argv(a, single, tables=True):
         out += ["--min-baseq", str(a.min_baseq)]
     if a.mate_overlap:                              # (the mate-overlap rule, likewise: a --batch child's file runner takes it)
         out += ["--mate-overlap"]
+    if a.dedup:                                     # (the duplicate rule, likewise)
+        out += ["--dedup"]
     if a.primers:                                   # (the primer mask, likewise: both flags or neither)
         out += ["--primers", a.primers, "--primer-slack", str(a.primer_slack)]
     if tables and (a.variant_thresholds_given or a.variant_table):     # (the table's thresholds, likewise; --batch children find their tables in the manifest)
@@ -868,6 +886,7 @@ def run_batch(a):
             with open(a.stats, "w") as fh:
                 json.dump({"seconds": {"batch": time.perf_counter() - t0}, "samples": len(rows), "min_baseq": a.min_baseq, "primers": len(rules.primers[0]) if rules.primers else 0,
                            **mate_stats(a.mate_overlap, runner.mate_overlap_totals() if a.mate_overlap else None),
+                           **dedup_stats(a.dedup, runner.dedup_totals() if a.dedup else None),
                            "variant_records": int(getattr(runner, "variant_records", 0)),
                            "amplicons": len(amps) if amps else 0, "amplicons_below": n_below, "stage_busy_seconds": runner.seconds,
                            "decoded_on": runner.decoded_on, "status": [int(x) for x in getattr(runner, "last_status", [])]}, fh)
@@ -994,7 +1013,7 @@ def _single_sample(a, flt, t):
             secs["bam_decode"] = secs["bam_open"]       # (round 1's name of the same span: the file is opened, decoded with the tally)
             json.dump({"seconds": secs, "positions": len(counts), "reads": build_counts.last_reads, "reads_filtered": build_counts.last_filtered,
                        "min_baseq": a.min_baseq, "primers": a.primer_rows, "reads_primer_masked": build_counts.last_primer_masked,
-                       **mate_stats(a.mate_overlap, build_counts.last_mate_overlap),
+                       **mate_stats(a.mate_overlap, build_counts.last_mate_overlap), **dedup_stats(a.dedup, build_counts.last_dedup),
                        **vstats, "amplicons": len(amps) if amps else 0, "amplicons_below": n_below, **want.stats(got),
                        "bam_bytes": os.path.getsize(a.input)}, fh)
 

@@ -62,6 +62,9 @@ _SIGS = {
     "tcmi_readset_min_base_quality": (_int, [_vp, _P(_i32)]),
     "tcmi_ctx_set_mate_overlap": (_int, [_vp, _i32]),
     "tcmi_readset_mate_overlap": (_int, [_vp, _P(_i32), _P(_i64), _P(_i64), _P(_i64), _P(_i64)]),
+    "tcmi_ctx_set_dedup": (_int, [_vp, _i32]),
+    "tcmi_readset_dedup": (_int, [_vp, _P(_i32), _P(_i64), _P(_i64), _P(_i64), _P(_i64)]),
+    "tcmi_readset_duplicates": (_int, [_vp, _vp, _vp, _i64, _P(_i64)]),
     "tcmi_ctx_set_primers": (_int, [_vp, _i32, _vp, _vp, _vp, _i32]),
     "tcmi_readset_primers": (_int, [_vp, _P(_i32), _P(_i64)]),
     "tcmi_primers_compile": (_int, [_i32, _vp, _vp, _vp, _i32, _i32, _vp, _P(_i32), _vp, _P(_i32), C.c_char_p, _i64]),

@@ -136,7 +136,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
     on_readset(ctx, read set): called behind the step — info's tables are filled, the layout is still set — while the read set's
     decoded stream is resident; need_device: the flag on whose behalf a file the device decoder declines is refused then (reads
     decoded on the host leave no stream on the device), as indexing.build_counts takes them.  The rules' mate_overlap (pairs never
-    cross contigs): info then receives the join's counters as "mate_overlap" (ReadSet.mate_overlap)."""
+    cross contigs): info then receives the join's counters as "mate_overlap" (ReadSet.mate_overlap); its dedup (a key holds its
+    reference): likewise "dedup" (ReadSet.dedup)."""
     n_ref = len(shift)
     ctx.set_layout(shift, slot)
     if variants:
@@ -161,6 +162,8 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
                         info["reads_primer_masked"] = rs.primer_masked_reads
                     if rules.mate_overlap:
                         info["mate_overlap"] = dict(rs.mate_overlap)
+                    if rules.dedup:
+                        info["dedup"] = dict(rs.dedup)
                 plain, alt, flags, counts = ctx.step(rs, max(axis_len, 1), mincov, include_ambig, want_counts=want_counts)
                 if variants and info is not None:
                     info["variant_table"] = ctx.step_variants()
@@ -182,7 +185,7 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (StreamCounts, mate_stats, amplicon_intervals, amplicons_of, evidence_stats, rules_of, variants_of, write_amplicon_reads,
+    from .TrueConsense import (StreamCounts, mate_stats, dedup_stats, amplicon_intervals, amplicons_of, evidence_stats, rules_of, variants_of, write_amplicon_reads,
                                write_amplicon_table, write_indel_table, write_variant_evidence, write_variant_tables)
     seen, got = {}, {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
@@ -206,6 +209,7 @@ def run(a):
                                                                  on_readset=lambda c, rs: got.update(want.count(c, rs, seen.get("variant_table"))),
                                                                  need_device=want.need)
     seen.update(mate_stats(a.mate_overlap, seen.pop("mate_overlap", None)))
+    seen.update(dedup_stats(a.dedup, seen.pop("dedup", None)))
     seen.update(want.stats(got))
     seen.setdefault("reads_primer_masked", 0)
     table, strand, links = seen.pop("variant_table", None), got.get("variant_strand"), got.get("variant_links")

@@ -361,6 +361,14 @@ int tcmi_ctx_set_mate_overlap(tcmi_ctx *c, int32_t on)
     return TCMI_OK;
 }
 
+int tcmi_ctx_set_dedup(tcmi_ctx *c, int32_t on)
+{
+    if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
+    if (on != 0 && on != 1) return tcmi_fail(c, TCMI_E_ARG, "dedup %d is neither 0 nor 1", (int)on);
+    c->rules.dedup = on;                                      // (read by the next upload: nothing queued reads it)
+    return TCMI_OK;
+}
+
 int tcmi_ctx_set_primers(tcmi_ctx *c, int32_t n, const int64_t *start, const int64_t *end, const int32_t *reverse, int32_t slack)
 {
     if (!c) return tcmi_fail(nullptr, TCMI_E_ARG, "ctx is NULL");
@@ -399,6 +407,10 @@ int tcmi_ctx_stat(tcmi_ctx *c, const char *key, int64_t *value)
     else if (!std::strcmp(key, "mate_clipped_reads")) *value = c->stat_mate[1];
     else if (!std::strcmp(key, "mate_clipped_columns")) *value = c->stat_mate[2];
     else if (!std::strcmp(key, "mate_ambiguous")) *value = c->stat_mate[3];
+    else if (!std::strcmp(key, "dedup_templates")) *value = c->stat_dup[0];
+    else if (!std::strcmp(key, "duplicate_templates")) *value = c->stat_dup[1];
+    else if (!std::strcmp(key, "duplicate_records")) *value = c->stat_dup[2];
+    else if (!std::strcmp(key, "duplicate_sets")) *value = c->stat_dup[3];
     else return tcmi_fail(c, TCMI_E_ARG, "unknown statistic %s", key);
     return TCMI_OK;
 }

@@ -99,6 +99,9 @@ int refuse_slot_settings(tcmi_pipeline *p)
     if (first_slot_with(p, TCMI_RULE_MATE))                         // (... and no names or mate fields)
         return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's mate-overlap rule is on (--mate-overlap): the array pipeline runs read sets uploaded "
                          "from flat arrays, which carry no names and no mate fields");
+    if (first_slot_with(p, TCMI_RULE_DEDUP))                        // (... and no QUAL to score a template by)
+        return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context's duplicate rule is on (--dedup): the array pipeline runs read sets uploaded "
+                         "from flat arrays, which carry no names, no mate fields and no QUAL");
     for (const tcmi_ctx *c : p->slots)                          // (... and no variant table: nobody would fetch its records)
         if (tcmi_var_table_on(c))
             return tcmi_fail(p->slots[0], TCMI_E_UNSUPPORTED, "a slot context carries a variant table setting (--variant-table, tcmi_ctx_set_variants): the array "

@@ -171,7 +171,7 @@ struct Decoded {
 };
 // arena bytes of what the packers take behind the decoder's own pieces (pack_caps.h lists both packers' arrays): the several-kernel
 // packer's for n_rec records, the record index included
-inline size_t several_bytes(const tcmi_ctx *ctx, size_t n_rec) { return pk_several_scratch((int64_t)n_rec, 1, ctx->rules.mate != 0).end(0); }
+inline size_t several_bytes(const tcmi_ctx *ctx, size_t n_rec) { return pk_several_scratch((int64_t)n_rec, 1, ctx->rules.mate != 0, ctx->rules.dedup != 0).end(0); }
 
 // blocks [first, first + count) of the file (count < 0: to the end): the records that START in them.  A range that does not end
 // with the file takes one block more along — the last record may run into it — whose own records are left out.
@@ -238,7 +238,7 @@ int decode_enqueue(tcmi_ctx *ctx, const tcmi_bamfile *whole, Decoded &D, int64_t
                  b_small = b_nb4 * 5 + b_nb8 + tcmi_align256(nb * 512) + 256, b_tok = tcmi_align256(tok_words * 4 + 256);
     // whichever packer comes: the one-sync packer's capacity is never above the records reserved for (pk_one_sync_caps)
     const int64_t res_rec = (int64_t)(worst_case ? D.max_rec : D.guess_rec);
-    D.b_rest = std::max(several_bytes(ctx, (size_t)res_rec), pk_one_sync_scratch(res_rec, (int64_t)nb, ctx->rules.mate != 0, pk_prefix_on(ctx->prefix_kernels, (int64_t)nb)).end(0));
+    D.b_rest = std::max(several_bytes(ctx, (size_t)res_rec), pk_one_sync_scratch(res_rec, (int64_t)nb, ctx->rules.mate != 0, pk_prefix_on(ctx->prefix_kernels, (int64_t)nb), ctx->rules.dedup != 0).end(0));
     if (tcmi_arena_reserve(ctx, b_file + b_desc + b_out + b_slot + b_small + b_tok + D.b_rest + 16 * 256)) return TCMI_E_NOMEM;
     uint8_t *d_file = (uint8_t *)tcmi_arena_take(ctx, b_file);
     D.d_desc = (BlockDesc *)tcmi_arena_take(ctx, b_desc);
@@ -496,6 +496,11 @@ static int readset_from_blocks(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t fir
     if (ctx->rules.mate && (first_block != 0 || (n_blocks >= 0 && first_block + n_blocks < (int64_t)f->blocks.size())))
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: blocks [%lld, %lld) of %zu: the mate-overlap rule (--mate-overlap) takes whole files only, a record's mate "
                          "may lie outside a block range", f->path.c_str(), (long long)first_block,
+                         (long long)(n_blocks < 0 ? (int64_t)f->blocks.size() : first_block + n_blocks), f->blocks.size());
+    // (the duplicate rule likewise: the other templates of a record's key may lie outside the range)
+    if (ctx->rules.dedup && (first_block != 0 || (n_blocks >= 0 && first_block + n_blocks < (int64_t)f->blocks.size())))
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: blocks [%lld, %lld) of %zu: the duplicate rule (--dedup) takes whole files only, a template's other "
+                         "records may lie outside a block range", f->path.c_str(), (long long)first_block,
                          (long long)(n_blocks < 0 ? (int64_t)f->blocks.size() : first_block + n_blocks), f->blocks.size());
     TCMI_HIP(ctx, hipSetDevice(ctx->device));
     static const bool timing = std::getenv("TCMI_UPLOAD_TIMING") != nullptr;

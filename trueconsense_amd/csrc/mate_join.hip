@@ -18,6 +18,8 @@
 //                       the pair test; the pair's loser gets its clip.  clip[i] is written for every record below the record count,
 //                       0 for all others.  The four counters: one ballot per wavefront, the sums by shuffles, one atomic per counter
 //                       that is not zero.
+// Under the duplicate rule (dedup.hip) the probe also leaves every pair's two records each other's index + 1 in mate_idx[], and with
+// that rule alone (apply == 0) nothing else: clip[] is zeros, the counters stay 0.
 // Which record is kept and where it lies (kept_span), the unaligned loads (ld_u32): pack_device.h.  The stream is only read.
 #include "stream_count.h"
 #include "mate_rule.h"
@@ -25,17 +27,7 @@
 namespace {
 
 constexpr int BLOCK = SC_BLOCK;
-using MjArgs = tcmi_mate_job;           // the kernels take the job as it is, and the table's mask beside it
-
-// the records of the stream (uniform over the grid)
-__device__ inline int64_t record_count(const MjArgs &a)
-{
-    if (a.n >= 0) return a.n;
-    if (a.n_blocks <= 0 || (*a.flags & a.ovf)) return 0;       // (an index with holes: the host declines the file after its wait)
-    const int32_t b = a.n_blocks - 1;
-    const uint64_t n = (uint64_t)a.rec_base[b] + (b < a.n_own ? a.n_rec[b] : 0u);
-    return (int64_t)(n < a.rec_cap ? n : a.rec_cap);
-}
+using MjArgs = tcmi_mate_job;           // the kernels take the job as it is, and the table's mask beside it (the record count: stream_count.h)
 
 // one record as the join sees it: the rule's fields and the name
 struct Mate {
@@ -121,7 +113,7 @@ __global__ __launch_bounds__(BLOCK) void mate_probe_kernel(MjArgs a, uint32_t sl
     const int lane = threadIdx.x & 63;
     unsigned long long *cnt = a.table + (size_t)slot_mask + 1;     // (the four counters lie behind the table: one memset zeroes both)
     each_record(n, [&](int64_t i) {
-        uint32_t clip = 0, pairs = 0, amb = 0;
+        uint32_t clip = 0, pairs = 0, amb = 0, mate = 0;
         Mate m;
         int64_t p, q;
         if (i < n && open_mate(a, i, m, p, q)) {
@@ -151,13 +143,18 @@ __global__ __launch_bounds__(BLOCK) void mate_probe_kernel(MjArgs a, uint32_t sl
             else if (members == 2u && other >= 0) {
                 Mate c;
                 int64_t pc, qc;
-                if (open_mate(a, other, c, pc, qc) && tcmi_mate_pair(m.f, c.f) && tcmi_mate_loses(m.f, c.f)) {
-                    pairs = 1;                                  // (a pair is counted where it loses)
-                    clip = tcmi_mate_clip(p, q, qc);
+                if (open_mate(a, other, c, pc, qc) && tcmi_mate_pair(m.f, c.f)) {
+                    mate = (uint32_t)other + 1u;                // (from both sides: the duplicate rule's templates, dedup.hip)
+                    if (a.apply && tcmi_mate_loses(m.f, c.f)) {
+                        pairs = 1;                              // (a pair is counted where it loses)
+                        clip = tcmi_mate_clip(p, q, qc);
+                    }
                 }
             }
         }
+        if (!a.apply) amb = 0;                                  // (the join runs for mate_idx alone: its counters stay 0)
         if (i < n) a.clip[i] = clip;
+        if (a.mate_idx && i < n) a.mate_idx[i] = mate;
         // the four counters of the wavefront.  A clip is a record's span: the packers decline a file with a column at or beyond 2^29
         // (PKF_FARPOS), so it fits the int32 that open_walk and tally_stream_kernel add it in; 64 of them do not fit 32 bits: that
         // sum is 64 bits wide.
@@ -181,10 +178,10 @@ __global__ __launch_bounds__(BLOCK) void mate_probe_kernel(MjArgs a, uint32_t sl
 
 } // namespace
 
-int tcmi_mate_join_enqueue(tcmi_ctx *ctx, const tcmi_mate_job &job)
+int tcmi_mate_join_enqueue(tcmi_ctx *ctx, const tcmi_mate_job &job, const tcmi_dedup_job *dedup)
 {
     const size_t slots = tcmi_mate_slots(job.rec_cap);
-    if (slots > (1ull << 32)) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "--mate-overlap: %u records are more than the join's table takes", job.rec_cap);
+    if (slots > (1ull << 32)) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "%s: %u records are more than the join's table takes", job.apply ? "--mate-overlap" : "--dedup", job.rec_cap);
     const uint32_t slot_mask = (uint32_t)(slots - 1);
     const int64_t most = job.n >= 0 ? job.n : (int64_t)job.rec_cap;
     const int64_t blocks = (std::max<int64_t>(most, 1) + BLOCK - 1) / BLOCK;
@@ -194,6 +191,7 @@ int tcmi_mate_join_enqueue(tcmi_ctx *ctx, const tcmi_mate_job &job)
     (void)hipMemsetAsync(job.table, 0, (slots + 4) * 8, ctx->stream);          // (the table and the four counters behind it)
     hipLaunchKernelGGL(mate_build_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, job, slot_mask);
     hipLaunchKernelGGL(mate_probe_kernel, dim3(grid), dim3(BLOCK), 0, ctx->stream, job, slot_mask);
+    if (dedup) tcmi_dedup_launch(ctx, job, *dedup, grid, slot_mask);           // (the duplicate rule: the same bracket, dedup.hip)
     tcmi_prof_end(ctx, TCMI_K_MATE_JOIN);
     TCMI_HIP(ctx, hipGetLastError());
     return TCMI_OK;

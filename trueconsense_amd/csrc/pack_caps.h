@@ -66,13 +66,13 @@ static inline uint32_t pk_beyond_caps(const PkCaps &c, uint64_t n_rec, uint64_t 
 }
 
 // ---- the pinned buffer the packers' totals come back in, as byte offsets -----------------------------------------------------------------
-// PackTotals | blk_alg [n_blocks] | blk_end [n_blocks] | stat [n_blocks] | the mate join's four counters  (pk_report fills it; the
-// several-kernel packer copies its totals and counters to the same places, n_blocks = 0)
+// PackTotals | blk_alg [n_blocks] | blk_end [n_blocks] | stat [n_blocks] | the mate join's four counters, the duplicate rule's four behind
+// them  (pk_report fills it; the several-kernel packer copies its totals and counters to the same places, n_blocks = 0)
 constexpr size_t PK_TOTALS_BYTES = 104;          // sizeof(PackTotals) (pack_device.hip)
 struct ReportPin {
-    size_t alg, end, stat, mate, bytes;
+    size_t alg, end, stat, mate, dup, bytes;
     explicit ReportPin(int64_t nb) : alg(tcmi_align256(PK_TOTALS_BYTES)), end(alg + tcmi_align256((size_t)nb * 8)), stat(end + tcmi_align256((size_t)nb * 4)),
-                                     mate(stat + tcmi_align256((size_t)nb * 4)), bytes(mate + 256) {}
+                                     mate(stat + tcmi_align256((size_t)nb * 4)), dup(mate + 32), bytes(mate + 256) {}
 };
 
 // ---- the packers' arena scratch ----------------------------------------------------------------------------------------------------------
@@ -83,6 +83,10 @@ struct ReportPin {
 static inline size_t tcmi_mate_slots(size_t rec_cap) { size_t s = 1024; while (s < 2 * rec_cap) s <<= 1; return s; }
 // the mate join's table {tag << 32 | record + 1} [slots] and, behind it, its four counters: one memset zeroes both
 static inline size_t tcmi_mate_table_bytes(size_t rec_cap) { return tcmi_mate_slots(rec_cap) * 8 + 256; }
+// the duplicate rule's table (dedup.hip): {tag << 32 | leader + 1} [slots] | best [slots], 8 bytes each | its four counters | the
+// templates per slot [slots], 4 bytes each: one memset zeroes all of it
+static inline size_t tcmi_dup_table_bytes(size_t rec_cap) { return tcmi_align256(tcmi_mate_slots(rec_cap) * 20 + 32); }
+constexpr size_t TCMI_DUP_END_BYTES = 16;       // sizeof(tcmi_dup_end) (dedup_rule.h)
 
 template <int N> struct PkScratch {
     size_t bytes[N] = {};
@@ -101,11 +105,13 @@ template <int N> struct PkScratch {
     template <class T> T *at(int i) const { return static_cast<T *>(p[i]); }
 };
 
-// The several-kernel packer (tcmi_pack_on_device): 24 bytes a record (+ 4 and the record index's 8 from a stream, + the mate join's) and
+// The several-kernel packer (tcmi_pack_on_device): 24 bytes a record (+ 4 and the record index's 8 from a stream, + the mate join's, + the
+// duplicate rule's: the join's, mate_idx[], ends[], slot_of[], dup[] and its own table) and
 // 20 per 256 of them while it classifies; 24 per KEPT read once the host knows how many there are.
 enum { SK_REC_OFF,                                                              // a stream's record index (bam_device.hip: decode_on_device)
        SK_INFO, SK_RD_SEQ, SK_RD_POS, SK_BLK_SUM, SK_BLK_ALG, SK_BLK_END, SK_TOT, SK_GEN_IDX,   // pk_classify, pk_scan
        SK_MATE_TABLE, SK_CLIP,                                                  // the mate join
+       SK_MATE_IDX, SK_DUP_ENDS, SK_DUP_SLOT, SK_DUP, SK_DUP_TABLE,             // the duplicate rule (the join's two as well)
        SK_C_IDX, SK_C_POS, SK_C_INFO, SK_C_WOFF, SK_C_SEQ,                      // pk_scatter: the kept reads, compacted
        SK_N };
 static inline void pk_several_kept(PkScratch<SK_N> &s, int64_t nf)
@@ -113,8 +119,15 @@ static inline void pk_several_kept(PkScratch<SK_N> &s, int64_t nf)
     for (int i : {SK_C_IDX, SK_C_POS, SK_C_INFO, SK_C_WOFF}) s.set(i, 4, (size_t)nf);
     s.set(SK_C_SEQ, 8, (size_t)nf);
 }
-// n records (every one of them kept, until pk_several_kept says how many are); mode: 0 flat arrays, 1 a stream
-static inline PkScratch<SK_N> pk_several_scratch(int64_t n, int mode, bool mate)
+// the duplicate rule's arrays for `cap` records, from list index `first` (SK_MATE_IDX / OS_MATE_IDX) on
+template <int N> static inline void pk_dedup_scratch(PkScratch<N> &s, int first, size_t cap)
+{
+    s.set(first, 4, cap + 1); s.set(first + 1, TCMI_DUP_END_BYTES, cap + 1); s.set(first + 2, 4, cap + 1); s.set(first + 3, 1, cap + 1);
+    s.set(first + 4, 1, tcmi_dup_table_bytes(cap));
+}
+// n records (every one of them kept, until pk_several_kept says how many are); mode: 0 flat arrays, 1 a stream; mate: the join's
+// arrays (the mate rule or the duplicate rule is on); dedup: the duplicate rule's
+static inline PkScratch<SK_N> pk_several_scratch(int64_t n, int mode, bool mate, bool dedup = false)
 {
     PkScratch<SK_N> s;
     const size_t n1 = (size_t)std::max<int64_t>(n, 1), blk1 = (size_t)std::max<int64_t>((n + PK_BLOCK - 1) / PK_BLOCK, 1);
@@ -123,21 +136,22 @@ static inline PkScratch<SK_N> pk_several_scratch(int64_t n, int mode, bool mate)
     s.set(SK_BLK_SUM, 8, blk1); s.set(SK_BLK_ALG, 8, blk1); s.set(SK_BLK_END, 4, blk1);
     s.set(SK_TOT, PK_TOTALS_BYTES, 1);
     if (mode == 1) s.set(SK_GEN_IDX, 4, n1);
-    if (mate && n > 0) { s.set(SK_MATE_TABLE, 1, tcmi_mate_table_bytes((size_t)n)); s.set(SK_CLIP, 4, (size_t)n + 1); }
+    if ((mate || dedup) && n > 0) { s.set(SK_MATE_TABLE, 1, tcmi_mate_table_bytes((size_t)n)); s.set(SK_CLIP, 4, (size_t)n + 1); }
+    if (dedup && n > 0) pk_dedup_scratch(s, SK_MATE_IDX, (size_t)n);
     pk_several_kept(s, n);
     return s;
 }
 
-// The one-sync packer (tcmi_pack_fused_enqueue): 52 bytes a record of the capacity (+ the mate join's) and 32 a BGZF block (+ 24 when
+// The one-sync packer (tcmi_pack_fused_enqueue): 52 bytes a record of the capacity (+ the mate join's, + the duplicate rule's) and 32 a BGZF block (+ 24 when
 // pk_prefix makes the blocks' prefix sums).
 enum { OS_AGG, OS_FN, OS_REC_BASE, OS_RREC, OS_BLK_ALG, OS_BLK_END, OS_TOT, OS_PRE, OS_REC_OFF, OS_C_IDX, OS_C_POS, OS_C_INFO, OS_C_WOFF, OS_C_SEQ,
-       OS_GEN_IDX, OS_MATE_TABLE, OS_CLIP, OS_N };
+       OS_GEN_IDX, OS_MATE_TABLE, OS_CLIP, OS_MATE_IDX, OS_DUP_ENDS, OS_DUP_SLOT, OS_DUP, OS_DUP_TABLE, OS_N };
 // (every workgroup adds up what lies in front of its block: a few thousand words for a 1M-read file, but quadratic in the blocks — at
 //  67 000 blocks, a 4 GiB stream, it was 40 % of these kernels' time: from 16 384 blocks on three small scan launches do it;
 //  option "prefix_kernels": > 0 always, < 0 never)
 static inline bool pk_prefix_on(int option, int64_t nb) { return option > 0 || (option == 0 && nb >= 16384); }
 static inline size_t pk_prefix_words(int64_t nb) { return tcmi_align256(((size_t)nb + 1) * 8) / 8; }     // of each of pk_prefix's three arrays
-static inline PkScratch<OS_N> pk_one_sync_scratch(int64_t rec_cap, int64_t nb, bool mate, bool prefix)
+static inline PkScratch<OS_N> pk_one_sync_scratch(int64_t rec_cap, int64_t nb, bool mate, bool prefix, bool dedup = false)
 {
     PkScratch<OS_N> s;
     const size_t cap = (size_t)rec_cap, b = (size_t)nb;
@@ -150,6 +164,7 @@ static inline PkScratch<OS_N> pk_one_sync_scratch(int64_t rec_cap, int64_t nb, b
     for (int i : {OS_C_IDX, OS_C_POS, OS_C_INFO, OS_C_WOFF}) s.set(i, 4, cap);
     s.set(OS_C_SEQ, 8, cap);
     s.set(OS_GEN_IDX, 4, cap);
-    if (mate) { s.set(OS_MATE_TABLE, 1, tcmi_mate_table_bytes(cap)); s.set(OS_CLIP, 4, cap + 1); }
+    if (mate || dedup) { s.set(OS_MATE_TABLE, 1, tcmi_mate_table_bytes(cap)); s.set(OS_CLIP, 4, cap + 1); }
+    if (dedup) pk_dedup_scratch(s, OS_MATE_IDX, cap);
     return s;
 }

@@ -446,12 +446,15 @@ static int64_t packed_bytes(const PackTotals &tot)
 
 // ---- what both packers do on the host, once each ------------------------------------------------------------------------------------------
 // The plane rules a read set was built under (its record: tcmi_read_rules): the base-quality floor, the primer table, the mate rule —
-// the caller points pt.clip at the join's array once it has one — and whether they give the read set a drop plane and the BQ plane kernel.
-struct PlaneRules { uint32_t min_bq; PrimerTab pt; bool mate, drop_on; };
+// the caller points pt.clip at the join's array once it has one —, the duplicate rule, which raises the same clip[] (join: either of
+// the two is on, the join runs), and whether they give the read set a drop plane and the BQ plane kernel.
+struct PlaneRules { uint32_t min_bq; PrimerTab pt; bool mate, drop_on, dedup, join; };
 static PlaneRules plane_rules(const tcmi_readset *rs)
 {
-    PlaneRules r = {(uint32_t)rs->rules.min_bq, tcmi_primer_args(rs->rules.primers), rs->rules.mate != 0, false};
-    r.drop_on = r.min_bq || r.pt.seg || r.mate;
+    PlaneRules r = {(uint32_t)rs->rules.min_bq, tcmi_primer_args(rs->rules.primers), rs->rules.mate != 0, false, false, false};
+    r.dedup = rs->rules.dedup != 0;
+    r.join = r.mate || r.dedup;
+    r.drop_on = r.min_bq || r.pt.seg || r.join;
     return r;
 }
 
@@ -484,6 +487,19 @@ static void take_mate_counts(tcmi_ctx *ctx, tcmi_readset *rs, const char *h_pin,
 {
     const unsigned long long *h_cnt = reinterpret_cast<const unsigned long long *>(h_pin + pin.mate);
     for (int k = 0; k < 4; ++k) { rs->mate_stat[k] = (int64_t)h_cnt[k]; ctx->stat_mate[k] += rs->mate_stat[k]; }
+    if (!rs->rules.dedup) return;
+    const unsigned long long *h_dup = reinterpret_cast<const unsigned long long *>(h_pin + pin.dup);   // (the duplicate rule's come with them)
+    for (int k = 0; k < 4; ++k) { rs->dup_stat[k] = (int64_t)h_dup[k]; ctx->stat_dup[k] += rs->dup_stat[k]; }
+}
+
+// the duplicate rule's arrays out of a packer's scratch list (first: SK_MATE_IDX / OS_MATE_IDX), mate_idx[] into the join's job
+template <int N> static tcmi_dedup_job dedup_job(const PkScratch<N> &S, int first, tcmi_mate_job &mj)
+{
+    tcmi_dedup_job dj = {};
+    mj.mate_idx = S.template at<uint32_t>(first);
+    dj.ends = S.template at<tcmi_dup_end>(first + 1); dj.slot_of = S.template at<uint32_t>(first + 2); dj.dup = S.template at<uint8_t>(first + 3);
+    dj.table = S.template at<unsigned long long>(first + 4);
+    return dj;
 }
 
 // The read set's fields from the totals.  alg, max_end, max_len: the one-sync packer folds them from its blocks' partials, the
@@ -517,7 +533,7 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     PrimerTab &pt = pr.pt;
     if (n > 0xFFFFFFF0ll) { *why = PKF_LONG; return TCMI_E_UNSUPPORTED; }
     const int64_t n_blk = (n + PB - 1) / PB;
-    PkScratch<SK_N> S = pk_several_scratch(n, src.mode, pr.mate);       // (every array below: pack_caps.h lists them)
+    PkScratch<SK_N> S = pk_several_scratch(n, src.mode, pr.join, pr.dedup);       // (every array below: pack_caps.h lists them)
     if (!take_scratch(ctx, S, SK_INFO, SK_MATE_TABLE)) return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: pack scratch under-reserved");
     uint32_t *info = S.at<uint32_t>(SK_INFO), *gen_idx = S.at<uint32_t>(SK_GEN_IDX);      // (gen_idx: a stream's; else null)
     uint2 *rd_seq = S.at<uint2>(SK_RD_SEQ), *blk_sum = S.at<uint2>(SK_BLK_SUM);
@@ -560,8 +576,8 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
     rs->ref_ext.assign(h_ext.begin(), h_ext.end());
     fill_readset(rs, tot, (int64_t)tot.alg_bytes, tot.max_end, (int32_t)tot.max_len, false);
     rs->packed_on_device = 1;
-    if (pr.mate && n > 0) {
-        // the mate join, in front of the plane kernel: the record count is the host's here; its counters are copied now and read behind
+    if (pr.join && n > 0) {
+        // the mate join (and the duplicate rule behind it), in front of the plane kernel: the record count is the host's here; its counters are copied now and read behind
         // the next wait this function makes anyway (take_counts)
         if (!take_scratch(ctx, S, SK_MATE_TABLE, SK_C_IDX)) return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: mate join scratch under-reserved");
         tcmi_mate_job mj = {};
@@ -569,8 +585,15 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
         mj.n = n; mj.rec_cap = (uint32_t)n;
         mj.table = S.at<unsigned long long>(SK_MATE_TABLE);
         mj.clip = S.at<uint32_t>(SK_CLIP);
-        if (const int rc = tcmi_mate_join_enqueue(ctx, mj)) return rc;
+        mj.apply = pr.mate;
+        tcmi_dedup_job dj = {};
+        if (pr.dedup) dj = dedup_job(S, SK_MATE_IDX, mj);
+        if (const int rc = tcmi_mate_join_enqueue(ctx, mj, pr.dedup ? &dj : nullptr)) return rc;
         TCMI_HIP(ctx, hipMemcpyAsync(reinterpret_cast<char *>(h_tot) + pin.mate, tcmi_mate_counters(mj), 32, hipMemcpyDeviceToHost, ctx->stream));
+        if (pr.dedup) {
+            TCMI_HIP(ctx, hipMemcpyAsync(reinterpret_cast<char *>(h_tot) + pin.dup, tcmi_dup_counters(mj, dj), 32, hipMemcpyDeviceToHost, ctx->stream));
+            rs->d_dup = dj.dup;
+        }
         counts_owed = true;
         rs->d_clip = mj.clip; pt.clip = mj.clip;
         keep_stream(ctx, rs, src.stream, src.rec_off);
@@ -653,12 +676,13 @@ int tcmi_pack_on_device(tcmi_ctx *ctx, const void *src_, tcmi_readset *rs, uint3
 // (mate: the mate join's four counters, null when the setting is off; they land behind everything else of the pinned buffer)
 __global__ __launch_bounds__(256) void pk_report(const PackTotals *tot, const unsigned long long *blk_alg, const int32_t *blk_end, const uint32_t *stat,
                                                  int32_t nb, PackTotals *h_tot, unsigned long long *h_alg, int32_t *h_end, uint32_t *h_stat,
-                                                 const unsigned long long *mate, unsigned long long *h_mate)
+                                                 const unsigned long long *mate, unsigned long long *h_mate, const unsigned long long *dup)
 {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     if (i < nb) { h_alg[i] = blk_alg[i]; h_end[i] = blk_end[i]; h_stat[i] = stat[i]; }
     if (i == 0) *h_tot = *tot;
     if (mate && i < 4) h_mate[i] = mate[i];
+    if (dup && i < 4) h_mate[4 + i] = dup[i];               // (the duplicate rule's four, behind the join's: ReportPin::dup)
 }
 
 // ---- the one-sync path: pk_index + pk_place + pk_pack queued from capacities, checked after the caller's one wait ------------------------------
@@ -672,7 +696,7 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     tcmi_rules_stamp(rs, ctx, true);
     PlaneRules pr = plane_rules(rs);
     const bool prefix = pk_prefix_on(ctx->prefix_kernels, nb);
-    PkScratch<OS_N> S = pk_one_sync_scratch(cap, nb, pr.mate, prefix);      // (every array below: pack_caps.h lists them)
+    PkScratch<OS_N> S = pk_one_sync_scratch(cap, nb, pr.join, prefix, pr.dedup);      // (every array below: pack_caps.h lists them)
     if (!take_scratch(ctx, S, 0, OS_N)) return tcmi_fail(ctx, TCMI_E_NOMEM, "internal: one-pass packer scratch under-reserved");
     PackTotals *d_tot = S.at<PackTotals>(OS_TOT);
     unsigned long long *pre = S.at<unsigned long long>(OS_PRE);
@@ -708,15 +732,19 @@ int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs
     hipLaunchKernelGGL(pk_index, dim3((unsigned)nb), dim3(PB), 0, ctx->stream, a);
     tcmi_prof_end(ctx, TCMI_K_PACK_CLASSIFY);
     TCMI_HIP(ctx, hipGetLastError());
-    if (pr.mate) {
-        // the mate join between pk_index and pk_place_bq: nobody has read the record count back — its kernels take it from what pk_index
+    if (pr.join) {
+        // the mate join (and the duplicate rule behind it) between pk_index and pk_place_bq: nobody has read the record count back — its kernels take it from what pk_index
         // left, their grid is sized from the capacity
         mj.src.stream = job->d_stream; mj.src.rec_off = job->d_rec; mj.src.mode = 1; mj.src.n = cap; mj.src.flt = a.flt;
         mj.stream_len = job->stream_len; mj.n = -1; mj.rec_cap = (uint32_t)cap;
         mj.rec_base = a.rec_base; mj.n_rec = job->d_nrec; mj.n_blocks = (int32_t)nb; mj.n_own = (int32_t)job->n_own;
         mj.flags = &d_tot->flags; mj.ovf = PKF_REC_OVF;
-        if (const int rc = tcmi_mate_join_enqueue(ctx, mj)) return rc;
+        mj.apply = pr.mate;
+        tcmi_dedup_job dj = {};
+        if (pr.dedup) dj = dedup_job(S, OS_MATE_IDX, mj);
+        if (const int rc = tcmi_mate_join_enqueue(ctx, mj, pr.dedup ? &dj : nullptr)) return rc;
         job->d_mate_cnt = tcmi_mate_counters(mj);
+        if (pr.dedup) { job->d_dup_cnt = tcmi_dup_counters(mj, dj); rs->d_dup = dj.dup; }
         rs->d_clip = mj.clip;
     }
     tcmi_prof_begin(ctx, TCMI_K_PACK);
@@ -762,7 +790,7 @@ int tcmi_pack_fused_report(tcmi_ctx *ctx, tcmi_fused_job *job)
                        static_cast<const unsigned long long *>(job->d_blk_alg), static_cast<const int32_t *>(job->d_blk_end), job->d_stat, (int32_t)nb,
                        reinterpret_cast<PackTotals *>(h), reinterpret_cast<unsigned long long *>(h + pin.alg), reinterpret_cast<int32_t *>(h + pin.end),
                        reinterpret_cast<uint32_t *>(h + pin.stat), static_cast<const unsigned long long *>(job->d_mate_cnt),
-                       reinterpret_cast<unsigned long long *>(h + pin.mate));
+                       reinterpret_cast<unsigned long long *>(h + pin.mate), static_cast<const unsigned long long *>(job->d_dup_cnt));
     TCMI_HIP(ctx, hipGetLastError());
     return TCMI_OK;
 }

@@ -159,11 +159,12 @@ int gpu_decode(FileRun &q, tcmi_ctx *ctx, int64_t i, GpuStep &s)
     }
     if (rc != TCMI_E_UNSUPPORTED) return rc;
     // ... but not under a base-quality floor: its packer knows none; nor under a primer table: its packer knows no mask; nor under the
-    // mate-overlap rule: its packer joins no mates
+    // mate-overlap rule: its packer joins no mates; nor under the duplicate rule: its packer finds no duplicate templates
     const tcmi_rule_beyond beyond = tcmi_rules_beyond_host(ctx->rules);
     if (beyond == TCMI_RULE_FLOOR) return refuse_host_packer(ctx, q.paths[i], "--min-baseq " + std::to_string((int)ctx->rules.min_bq), "base-quality floor", it.file != nullptr);
     if (beyond == TCMI_RULE_PRIMERS) return refuse_host_packer(ctx, q.paths[i], "--primers", "primer mask", it.file != nullptr);
     if (beyond == TCMI_RULE_MATE) return refuse_host_packer(ctx, q.paths[i], "--mate-overlap", "mate join", it.file != nullptr);
+    if (beyond == TCMI_RULE_DEDUP) return refuse_host_packer(ctx, q.paths[i], "--dedup", "duplicate templates", it.file != nullptr);
     rc = s.host.load(q.paths[i], q.r->host_threads, ctx->rules.flt);   // (the context's read filter)
     if (rc) s.host_err = tcmi_last_error(nullptr);
     else rc = tcmi_readset_upload(ctx, &s.host.reads, &s.rs);

@@ -91,6 +91,9 @@ static int upload_impl(tcmi_ctx *ctx, const tcmi_reads *const *batch, int32_t n_
     if (beyond == TCMI_RULE_MATE)                               // (... nor pairs silently counted twice)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's mate-overlap rule is on (--mate-overlap): flat read arrays carry no names and no mate "
                          "fields; only whole files decoded on the device are tallied under it");
+    if (beyond == TCMI_RULE_DEDUP)                              // (... nor duplicates silently counted)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "the context's duplicate rule is on (--dedup): flat read arrays carry no names, no mate fields and no "
+                         "QUAL; only whole files decoded on the device are tallied under it");
     int rc = TCMI_OK;
     for (int32_t b = 0; b < n_batch; ++b) {
         rc = check_reads(ctx, batch[b]);
@@ -235,6 +238,17 @@ int tcmi_readset_mate_overlap(const tcmi_readset *rs, int32_t *on, int64_t *pair
     if (clipped_reads) *clipped_reads = rs->mate_stat[1];
     if (clipped_columns) *clipped_columns = rs->mate_stat[2];
     if (ambiguous) *ambiguous = rs->mate_stat[3];
+    return TCMI_OK;
+}
+
+int tcmi_readset_dedup(const tcmi_readset *rs, int32_t *on, int64_t *templates, int64_t *dup_templates, int64_t *dup_records, int64_t *dup_sets)
+{
+    if (!rs) return tcmi_fail(nullptr, TCMI_E_ARG, "null argument");
+    if (on) *on = rs->rules.dedup;
+    if (templates) *templates = rs->dup_stat[0];
+    if (dup_templates) *dup_templates = rs->dup_stat[1];
+    if (dup_records) *dup_records = rs->dup_stat[2];
+    if (dup_sets) *dup_sets = rs->dup_stat[3];
     return TCMI_OK;
 }
 

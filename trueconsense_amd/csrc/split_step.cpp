@@ -30,7 +30,7 @@ static int split_sub_ranges(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first,
     for (tcmi_ctx *h : ctx->helpers) {                          // (the caller's decoder options)
         h->verify_crc = ctx->verify_crc; h->decode_token_mb = ctx->decode_token_mb; h->one_sync = ctx->one_sync; h->mid_wait = ctx->mid_wait;
         h->prefix_kernels = ctx->prefix_kernels; h->h2d_pieces = ctx->h2d_pieces; h->sym_scratch_div = ctx->sym_scratch_div; h->prof = false;
-        h->rules = ctx->rules;                                  // (whole: the one caller has refused the mate rule, so that is off in them too)
+        h->rules = ctx->rules;                                  // (whole: the one caller has refused the mate rule and the duplicate rule, so they are off in them too)
     }
     TCMI_HIP(ctx, hipStreamSynchronize(ctx->stream));            // (the matrix is zero before anybody adds to it)
     std::vector<tcmi_readset *> rs((size_t)K, nullptr);
@@ -133,6 +133,9 @@ int tcmi_split_step(tcmi_ctx *ctx, const tcmi_bamfile *f, int64_t first_block, i
     if (ctx->layout.n()) return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not take a contig layout (tcmi_ctx_set_layout)");
     if (ctx->rules.mate)                                        // (a record's mate may lie in another rank's range)
         return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not run under the mate-overlap rule (--mate-overlap): a record's mate may lie in "
+                         "another rank's block range");
+    if (ctx->rules.dedup)                                       // (... and so may a template's other records)
+        return tcmi_fail(ctx, TCMI_E_UNSUPPORTED, "tcmi_split_step does not run under the duplicate rule (--dedup): a template's other records may lie in "
                          "another rank's block range");
     if (L <= 0 || ld < L) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 < L <= ld");
     if (world < 1 || rank < 0 || rank >= world) return tcmi_fail(ctx, TCMI_E_ARG, "need 0 <= rank < world");

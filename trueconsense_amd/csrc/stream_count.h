@@ -170,4 +170,14 @@ template <class F> __device__ inline void each_record(int64_t n, F f)
     for (int64_t base = (int64_t)blockIdx.x * SC_BLOCK; base < n; base += (int64_t)gridDim.x * SC_BLOCK) f(base + (int64_t)threadIdx.x);
 }
 
+// the records of the stream a mate job (mate_join.hip, dedup.hip) walks (uniform over the grid): the host's count, or what pk_index left
+__device__ inline int64_t record_count(const tcmi_mate_job &a)
+{
+    if (a.n >= 0) return a.n;
+    if (a.n_blocks <= 0 || (*a.flags & a.ovf)) return 0;       // (an index with holes: the host declines the file after its wait)
+    const int32_t b = a.n_blocks - 1;
+    const uint64_t n = (uint64_t)a.rec_base[b] + (b < a.n_own ? a.n_rec[b] : 0u);
+    return (int64_t)(n < a.rec_cap ? n : a.rec_cap);
+}
+
 } // namespace

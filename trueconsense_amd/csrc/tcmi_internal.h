@@ -73,20 +73,22 @@ static inline tcmi_primer_tab tcmi_primer_args(const std::shared_ptr<const tcmi_
 // ---- the read rules ------------------------------------------------------------------------------------------------------
 // Which tokens of a BAM reach the count matrix: the read filter (tcmi_ctx_set_read_filter), the base-quality floor
 // (tcmi_ctx_set_min_base_quality; 0: none), the primer table (tcmi_ctx_set_primers; null: none) and the mate-overlap rule
-// (tcmi_ctx_set_mate_overlap; 0: off).  One record on the context (what its next read set is built under) and one on every read set
+// (tcmi_ctx_set_mate_overlap; 0: off) and the duplicate rule (tcmi_ctx_set_dedup; 0: off).  One record on the context (what its next read set is built under) and one on every read set
 // (what it was built under); tcmi_rules_stamp hands it from the one to the other, tcmi_rules_args to the kernels' arguments.
 struct tcmi_read_rules {
     tcmi_read_filter flt = {0, 0, 0};
     int32_t min_bq = 0;
     std::shared_ptr<const tcmi_primer_dev> primers;
     int32_t mate = 0;
+    int32_t dedup = 0;
 };
 // the first rule that is beyond the host packer and the flat arrays of struct tcmi_reads (no QUAL, no mask, no names): the entry
-// points that lead there refuse under it, each in its own words, the floor before the table before the mate rule (the filter they know)
-enum tcmi_rule_beyond { TCMI_RULE_NONE = 0, TCMI_RULE_FLOOR, TCMI_RULE_PRIMERS, TCMI_RULE_MATE };
+// points that lead there refuse under it, each in its own words, the floor before the table before the mate rule before the duplicate rule
+// (the filter they know)
+enum tcmi_rule_beyond { TCMI_RULE_NONE = 0, TCMI_RULE_FLOOR, TCMI_RULE_PRIMERS, TCMI_RULE_MATE, TCMI_RULE_DEDUP };
 static inline tcmi_rule_beyond tcmi_rules_beyond_host(const tcmi_read_rules &r)
 {
-    return r.min_bq > 0 ? TCMI_RULE_FLOOR : r.primers ? TCMI_RULE_PRIMERS : r.mate ? TCMI_RULE_MATE : TCMI_RULE_NONE;
+    return r.min_bq > 0 ? TCMI_RULE_FLOOR : r.primers ? TCMI_RULE_PRIMERS : r.mate ? TCMI_RULE_MATE : r.dedup ? TCMI_RULE_DEDUP : TCMI_RULE_NONE;
 }
 // ... as the kernels take the filter and the floor: `flt` and `min_bq` of tcmi_pack_src and of the one-sync packer's arguments
 template <class Args> static inline void tcmi_rules_args(Args &a, const tcmi_read_rules &r) { a.flt = tcmi_filter_pack(r.flt); a.min_bq = (uint32_t)r.min_bq; }
@@ -122,12 +124,15 @@ struct tcmi_readset {
     // the records that failed the filter (tcmi_readset_filtered); under any of the other three the aligned set's third plane, d_fdrop: one
     // word per {lo, hi} pair of d_fseq (index = word / 2), bit b set when that read's token on that column is skipped; the kept reads
     // with a non-empty head or tail mask (tcmi_readset_primers); under the mate rule d_clip [n_reads], in the context's arena beside
-    // the stream (arena_epoch tells), and the join's four counters (tcmi_readset_mate_overlap)
+    // the stream (arena_epoch tells), and the join's four counters (tcmi_readset_mate_overlap); under the duplicate rule d_clip likewise
+    // (a duplicate's clip is its span), d_dup [n_reads] beside it (tcmi_readset_duplicates) and dedup.hip's four counters
     tcmi_read_rules rules;
     int64_t n_filtered = 0;
     int64_t n_masked = 0;
     const uint32_t *d_clip = nullptr;
     int64_t mate_stat[4] = {0, 0, 0, 0};    // pairs, clipped reads, clipped columns, ambiguous records
+    const uint8_t *d_dup = nullptr;
+    int64_t dup_stat[4] = {0, 0, 0, 0};     // templates, duplicate templates, duplicate records, duplicate sets
     const uint32_t *d_gen_idx = nullptr;   // records of reads too long for the packed set (s_reads of them): tally_stream_kernel walks them in the stream
     int64_t s_reads = 0;
     // a read set of a block RANGE of a file (tcmi_readset_from_bamfile_blocks): where its first record starts when the range began
@@ -168,7 +173,7 @@ struct tcmi_readset {
 static inline tcmi_primer_tab tcmi_mask_args(const tcmi_readset *rs)
 {
     tcmi_primer_tab t = tcmi_primer_args(rs->rules.primers);
-    t.clip = rs->rules.mate ? rs->d_clip : nullptr;
+    t.clip = rs->rules.mate || rs->rules.dedup ? rs->d_clip : nullptr;
     return t;
 }
 
@@ -250,6 +255,7 @@ struct tcmi_ctx {
     int verify_crc = 1;              // the device decoder checks the BGZF CRC-32 of every block
     int64_t stat_one_sync_taken = 0, stat_one_sync_declined = 0, stat_one_sync_retried = 0, stat_last_decline = 0;     // tcmi_ctx_stat
     int64_t stat_h2d_piped = 0;      // decodes whose compressed bytes crossed PCIe in pieces, ahead of the inflate kernels (bam_device.hip: decode_enqueue)
+    int64_t stat_dup[4] = {0, 0, 0, 0};      // dedup.hip's counters, likewise (tcmi_ctx_stat "dedup_templates", ...)
     int64_t stat_mate[4] = {0, 0, 0, 0};     // the mate join's counters, summed over the read sets this context built (tcmi_ctx_stat "mate_pairs", ...)
     int64_t stat_split_sub = 0;      // tcmi_split_step calls whose range went through sub-ranges
     int64_t stat_decode_batched = 0; // files the device decoder took in batches of blocks (tcmi_ctx_stat "decode_batched")
@@ -439,6 +445,7 @@ struct tcmi_fused_job {
     int32_t *c_pos = nullptr;
     const void *d_blk_alg = nullptr, *d_blk_end = nullptr;
     const void *d_mate_cnt = nullptr;   // the mate join's four counters (null: the setting is off); the report brings them along
+    const void *d_dup_cnt = nullptr;    // dedup.hip's four counters, likewise
 };
 int tcmi_pack_fused_enqueue(tcmi_ctx *ctx, tcmi_fused_job *job, tcmi_readset *rs);
 int tcmi_pack_fused_report(tcmi_ctx *ctx, tcmi_fused_job *job);     // queue it LAST (behind the tally and the call, if any): then wait, then _finish
@@ -458,10 +465,28 @@ struct tcmi_mate_job {
     unsigned long long *table;          // [slots + 4] {tag << 32 | record + 1}, slots = tcmi_mate_slots(rec_cap); behind them the four
                                         // counters (tcmi_mate_counters): one memset zeroes both
     uint32_t *clip;                     // out [rec_cap]
+    // with the duplicate rule (null / 1 without): every record of a pair receives its mate's record index + 1, every other record below
+    // the record count 0; apply == 0 (the duplicate rule without the mate rule): the join runs for mate_idx alone — clip[] is written
+    // as zeros and the counters stay 0
+    uint32_t *mate_idx;                 // out [rec_cap]
+    int32_t apply;
 };
 // (the table's and clip[]'s arena bytes: pack_caps.h)
 static inline const unsigned long long *tcmi_mate_counters(const tcmi_mate_job &job) { return job.table + tcmi_mate_slots(job.rec_cap); }
-int tcmi_mate_join_enqueue(tcmi_ctx *ctx, const tcmi_mate_job &job);
+// The duplicate rule (dedup.hip) behind the join, inside its profiling bracket: ends[] per record, the templates' table, the verdicts.
+// table: {tag << 32 | claimant leader + 1} [slots] | best [slots] (64 bits) | the four counters | the templates per slot [slots]
+// (32 bits), slots = tcmi_mate_slots(rec_cap): one memset zeroes all of it (pack_caps.h: tcmi_dup_table_bytes).
+struct tcmi_dup_end;
+struct tcmi_dedup_job {
+    tcmi_dup_end *ends;                 // [rec_cap]
+    uint32_t *slot_of;                  // [rec_cap] a leader's slot
+    uint8_t *dup;                       // out [rec_cap] 0 / 1
+    unsigned long long *table;
+};
+static inline const unsigned long long *tcmi_dup_counters(const tcmi_mate_job &job, const tcmi_dedup_job &d) { return d.table + 2 * tcmi_mate_slots(job.rec_cap); }
+// (dedup: null without the duplicate rule)
+int tcmi_mate_join_enqueue(tcmi_ctx *ctx, const tcmi_mate_job &job, const tcmi_dedup_job *dedup = nullptr);
+void tcmi_dedup_launch(tcmi_ctx *ctx, const tcmi_mate_job &job, const tcmi_dedup_job &dedup, unsigned grid, uint32_t slot_mask);
 
 // the context's device arena (api.cpp): _reserve hands it out anew, `bytes` large (whatever lived in it is gone: arena_epoch tells);
 // _take carves the next piece, 256-byte aligned — the packers sum a list's pieces against `cap` before they take them (pack_caps.h: PkScratch)

@@ -22,11 +22,13 @@ from ._ffi import check, lib, ptr
 @dataclasses.dataclass(frozen=True)
 class ReadRules:
     """Which tokens of a BAM reach the count matrix (csrc: struct tcmi_read_rules), one value from the command line to a context: read_filter =
-    (min_mapq, require_flags, exclude_flags), min_baseq, primers = (rows, slack), mate_overlap (Context.set_*); the defaults mean none of them."""
+    (min_mapq, require_flags, exclude_flags), min_baseq, primers = (rows, slack), mate_overlap, dedup (Context.set_*); the defaults mean
+    none of them."""
     read_filter: tuple = None
     min_baseq: int = 0
     primers: tuple = None
     mate_overlap: bool = False
+    dedup: bool = False
 
 
 # struct tcmi_variant: one (position, non-reference allele) of the variant table
@@ -364,6 +366,9 @@ def _token_dict(positions, buf, off, cnt):
     return {int(p): (buf.raw[off[k]:off[k + 1]].decode("ascii") if cnt[k] else None, int(cnt[k])) for k, p in enumerate(positions)}
 
 
+DEDUP_COUNTERS = ("templates", "duplicate_templates", "duplicate_records", "duplicate_sets")
+
+
 class ReadSet:
     def __init__(self, ctx, handle, keep):
         self.ctx, self.handle, self._keep = ctx, handle, keep
@@ -392,6 +397,18 @@ class ReadSet:
         check(lib().tcmi_readset_mate_overlap(handle, C.byref(on), *[C.byref(x) for x in mv]))
         # the mate-overlap rule the set was built under (Context.set_mate_overlap) and its join's counters
         self.mate_overlap = dict(zip(("on", "pairs", "clipped_reads", "clipped_columns", "ambiguous"), [on.value] + [x.value for x in mv]))
+        on, dv = C.c_int32(0), [C.c_int64(0) for _ in range(4)]
+        check(lib().tcmi_readset_dedup(handle, C.byref(on), *[C.byref(x) for x in dv]))
+        # the duplicate rule the set was built under (Context.set_dedup) and its counters
+        self.dedup = dict(zip(("on",) + DEDUP_COUNTERS, [on.value] + [x.value for x in dv]))
+
+    def duplicates(self):
+        """Built under the duplicate rule (Context.set_dedup): one bool per record of the file, True: the record belongs to a duplicate
+        template.  While the decoded stream is resident on the context: E_UNSUPPORTED after its next upload."""
+        out = np.zeros(max(int(self.n_reads), 1), np.uint8)
+        n = C.c_int64(0)
+        check(lib().tcmi_readset_duplicates(self.ctx.handle, self.handle, ptr(out), len(out), C.byref(n)), self.ctx.handle)
+        return out[:n.value].astype(bool)
 
     def ref_extents(self, n_ref):
         """Uploaded under a contig layout of n_ref references: per reference the kept reads' max end in its own coordinates."""
@@ -424,7 +441,8 @@ class Context:
     min_base_quality = 0
     primers = 0                     # rows of the table set_primers last set
     mate_overlap = False            # what set_mate_overlap last set
-    read_rules = ReadRules()        # ... and the four as one value: what the context's next read set is built under
+    dedup = False                   # what set_dedup last set
+    read_rules = ReadRules()        # ... and the five as one value: what the context's next read set is built under
 
     def __init__(self, device=0, stream=None):
         """stream: a hipStream_t as an int (0 = the default stream) to run on, e.g. another Context's
@@ -517,10 +535,20 @@ class Context:
         self.mate_overlap = bool(on)
         self.read_rules = dataclasses.replace(self.read_rules, mate_overlap=bool(on))
 
+    def set_dedup(self, on=False):
+        """Duplicate templates (tcmi_ctx_set_dedup; what samtools markdup / Picard MarkDuplicates do in a pass of their own): from now
+        on every read set this context builds from a whole device-decoded file ignores the records of duplicate templates — found on
+        the device by their unclipped 5' ends, the best by base-quality sum kept.  While it is on the flat-array entry points, block
+        ranges of a file and the split step refuse with E_UNSUPPORTED.  No argument: off."""
+        check(lib().tcmi_ctx_set_dedup(self.handle, int(bool(on))), self.handle)
+        self.dedup = bool(on)
+        self.read_rules = dataclasses.replace(self.read_rules, dedup=bool(on))
+
     def set_rules(self, rules=None):
-        """A job's ReadRules onto this context, all four, nothing restored (a context that lives for the job); None leaves what it has."""
+        """A job's ReadRules onto this context, all five, nothing restored (a context that lives for the job); None leaves what it has."""
         if rules is not None:
             self.set_mate_overlap(rules.mate_overlap)
+            self.set_dedup(rules.dedup)
             self.set_read_filter(*(rules.read_filter or ()))
             self.set_min_base_quality(rules.min_baseq)
             self.set_primers(*(rules.primers or ()))
@@ -1242,6 +1270,12 @@ class FileRunner:
     def mate_overlap_totals(self):
         """The mate join's counters summed over the files this runner's contexts decoded (ReadSet.mate_overlap's keys)."""
         keys = (("pairs", "mate_pairs"), ("clipped_reads", "mate_clipped_reads"), ("clipped_columns", "mate_clipped_columns"), ("ambiguous", "mate_ambiguous"))
+        return {k: sum(c.stat(s) for c in self.contexts) for k, s in keys}
+
+    def dedup_totals(self):
+        """The duplicate rule's counters summed over the files this runner's contexts decoded (ReadSet.dedup's keys)."""
+        keys = (("templates", "dedup_templates"), ("duplicate_templates", "duplicate_templates"), ("duplicate_records", "duplicate_records"),
+                ("duplicate_sets", "duplicate_sets"))
         return {k: sum(c.stat(s) for c in self.contexts) for k, s in keys}
 
     def _account(self, status, sec, on):

@@ -39,7 +39,7 @@ def Override_index_positions(index, override_data):
 def device_readset(ctx, path, blocks=None, need=None):
     """The device path, or why not: the file at `path` (blocks = (first, count): that range of its BGZF blocks) decoded and packed by
     ctx's device decoder -> ReadSet; None when the decoder declines the file (E_UNSUPPORTED) and the host reader may take it.  Under
-    a base-quality floor, a primer table or the mate-overlap rule (ctx.read_rules, in that order) the host reader may not: the refusal is raised with its
+    a base-quality floor, a primer table, the mate-overlap rule or the duplicate rule (ctx.read_rules, in that order) the host reader may not: the refusal is raised with its
     reason; likewise when the caller names a flag that `need`s the device path (--amplicon-reads counts in the decoded stream)."""
     d = DeviceBam(path)
     try:
@@ -51,8 +51,9 @@ def device_readset(ctx, path, blocks=None, need=None):
         for flag, why in ((r.min_baseq and "--min-baseq %d" % r.min_baseq, "the host packer knows no base-quality floor"),
                           (r.primers and "--primers", "the host packer knows no primer mask"),
                           (r.mate_overlap and "--mate-overlap", "the host packer joins no mates"),
+                          (r.dedup and "--dedup", "the host packer finds no duplicate templates"),
                           (need, "it counts the records in the stream the device decoded")):
-            if flag:                                # (the first in this order: the floor, the table, the mate rule, the caller's flag)
+            if flag:                                # (the first in this order: the floor, the table, the mate rule, the duplicate rule, the caller's flag)
                 raise _ffi.TcmiError(_ffi.E_UNSUPPORTED, "%s needs the device path (%s), which %s left: %s" % (flag, why, path, e)) from e
         return None
     finally:
@@ -78,6 +79,7 @@ def build_counts(bamfile, ref, ctx=None, on_readset=None, need_device=None):
                 build_counts.last_reads, build_counts.last_filtered = int(rs.n_reads), int(rs.filtered)
                 build_counts.last_primer_masked = int(rs.primer_masked_reads)
                 build_counts.last_mate_overlap = dict(rs.mate_overlap)
+                build_counts.last_dedup = dict(rs.dedup)
                 counts = ctx.step(rs, max(ref_length, rs.max_end, 1), 0, True, want_counts=True)[3]
                 if on_readset is not None:
                     on_readset(ctx, rs)
@@ -97,6 +99,7 @@ def build_counts(bamfile, ref, ctx=None, on_readset=None, need_device=None):
 build_counts.last_reads = 0         # alignment records of the file the last call read (the command line's --stats)
 build_counts.last_filtered = 0      # ... of which failed the read filter
 build_counts.last_primer_masked = 0 # piled-up reads with a non-empty primer mask (Context.set_primers)
+build_counts.last_dedup = {}        # the duplicate rule's counters, likewise (Context.set_dedup; ReadSet.dedup)
 build_counts.last_mate_overlap = {} # the mate join's counters of the last device-decoded file (Context.set_mate_overlap; ReadSet.mate_overlap)
 
 
