@@ -252,7 +252,7 @@ def test_batch_over_gpus_joins_the_parts_in_manifest_order(tmp_path, monkeypatch
             recs = [(100 * int(r[1][1:]) + k, 1, 0, m.start, 0, 0, 0) for r in rows for k, (m, _) in enumerate(amps)]
             cli.write_amplicon_table(child.amplicon_table, [(r[1], ay.as_array(recs[i * len(amps):(i + 1) * len(amps)])) for i, r in enumerate(rows)], amps)
         return status[0]
-    monkeypatch.setattr(cli, "_spawn", fake_spawn)
+    monkeypatch.setattr("trueconsense_amd.launch._spawn", fake_spawn)
     argv = ["--batch", str(man), "--gpus", "2", "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30", "--amplicon-table", table, "--amplicon-scheme", f["s.bed"]]
     cli.main(argv)
     assert seen == [(table + ".part0", ["S0", "S2", "S4"]), (table + ".part1", ["S1", "S3"])]

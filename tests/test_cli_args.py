@@ -59,7 +59,7 @@ def test_gpus_children_get_the_parsed_arguments_not_the_typed_ones(tmp_path, mon
         seen["cmds"], seen["envs"] = cmds, envs
         seen["rows"] = [open(c[4]).read().count("\n") for c in cmds if c[3] == "--batch"]   # (the shards live as long as the children)
         return 0
-    monkeypatch.setattr(cli, "_spawn", fake_spawn)
+    monkeypatch.setattr("trueconsense_amd.launch._spawn", fake_spawn)
     cli.main(["--gpu", "2", "--bat", str(man), "--dev", "5", "-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "12", "-noambig", "-t", "3"])
     assert len(seen["cmds"]) == 2
     for k, cmd in enumerate(seen["cmds"]):
@@ -132,6 +132,6 @@ def test_gff_index_dict_without_pandas_is_what_the_dataframe_gives(tmp_path):
                 assert (isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b)) or (a == b and type(a) is type(b)), (i, c, a, b)
             assert Outputs._gff_line(lean[i]) == Outputs._gff_line(want[i])
         assert g.index_dict(seqid="OTHER")[0]["seqid"] == "OTHER" if want else True      # (a DataFrame that was asked for has the last word)
-    r = subprocess.run([sys.executable, "-c", "import sys, trueconsense_amd.TrueConsense, trueconsense_amd.split_main; print('pandas' in sys.modules)"],
+    r = subprocess.run([sys.executable, "-c", "import sys, trueconsense_amd.TrueConsense, trueconsense_amd.split_main, trueconsense_amd.cli_args, trueconsense_amd.cli_tables, trueconsense_amd.launch; print('pandas' in sys.modules)"],
                        capture_output=True, text=True, cwd=str(tmp_path.parent), env=dict(__import__("os").environ, PYTHONPATH=__import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__)))))
     assert r.stdout.strip() == "False", r.stdout + r.stderr

@@ -1,5 +1,5 @@
 """The counts taken behind the step — --amplicon-reads, --variant-strand, --variant-links — as the command line asks for them:
-TrueConsense.StreamCounts (one request for every runner), write_variant_tables (one writer), GetArgs' refusals, and
+cli_tables.StreamCounts (one request for every runner), cli_tables.write_tables (one writer), cli_args.GetArgs' refusals, and
 distributed._agree / _sum_to_root (the ranks' agreement and the one sum to rank 0) over a real two-process gloo group.  The gpu-marked
 tests run the three flags at once through every runner: each file must be the one the same runner writes under that flag alone."""
 import itertools
@@ -69,7 +69,7 @@ def test_agree_and_sum_to_root_over_gloo():
 FLAGS = {"reads": ["--amplicon-reads", "r.tsv", "--amplicon-reads-slack", "7"], "strand": ["--variant-strand", "--strand-ratio", "1/5"],
          "links": ["--variant-links", "l.tsv", "--link-neighbours", "3"]}
 ZERO = dict(variant_records=0, variant_strand_bias=0, variant_strand_low=0, variant_link_rows=0, variant_links_cis=0, variant_links_trans=0,
-            variant_links_mixed=0, variant_links_none=0, variant_links_low=0)
+            variant_links_mixed=0, variant_links_none=0, variant_links_low=0, variant_evidence_lowq=0, variant_evidence_lowmq=0, variant_evidence_end=0)
 
 
 def _parsed(f, which):
@@ -98,7 +98,7 @@ def test_the_empty_request(tmp_path):
     assert want.stats() == want.stats({}) == dict(amplicon_reads_ambiguous=0, amplicon_reads_unassigned=0)
     assert want.split_kwargs("ACGT") == dict(amplicon_reads=None, variant_strand=None, variant_links=None)
     assert want.from_parts(("text", "counts", {})) == ({}, None)
-    assert cli.write_variant_tables(a, [], want) == ZERO and list(cli.write_variant_tables(a, [], want)) == list(ZERO)
+    assert cli.write_tables(a, [], want) == ZERO and list(cli.write_tables(a, [], want)) == list(ZERO)
 
     class NoCalls:                                          # (nothing is asked of the context)
         pass

@@ -196,7 +196,7 @@ def test_batch_over_gpus_with_a_mixed_manifest(tmp_path, monkeypatch, capsys):
             child = cli.GetArgs(cmd[3:])                                # what the child parses ...
             seen.append((cmd[3:], child, cli.read_manifest(child)))     # ... and its manifest check, which must not exit
         return 0
-    monkeypatch.setattr(cli, "_spawn", fake_spawn)
+    monkeypatch.setattr("trueconsense_amd.launch._spawn", fake_spawn)
     common = ["-ref", f["r.fa"], "-gff", f["f.gff"], "-cov", "30"]
     cli.main(["--batch", str(man), "--gpus", "2"] + common + ["--min-af", "0.05"])
     assert len(seen) == 2

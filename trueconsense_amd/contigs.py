@@ -22,6 +22,8 @@ from datetime import date
 import numpy as np
 
 from . import _ffi, _state
+from .cli_args import amplicon_intervals, amplicons_of, rules_of, variants_of
+from .cli_tables import StreamCounts, dedup_stats, mate_stats, part_of_columns, write_amplicon_reads, write_amplicon_table, write_tables
 from .engine import BamFile, ReadRules, modal_tokens
 from .Events import _parse_token, candidates_from_flags
 from .io import fasta
@@ -185,8 +187,6 @@ def step_contigs(ctx, path, shift, slot, axis_len, mincov, include_ambig, header
 def run(a):
     """The whole --per-contig flow of the command line: every output is computed before the first file is written.
     -> {"contigs": n, "dropped_reads": mapped reads on BAM references the FASTA does not name, "reads", "reads_filtered"}."""
-    from .TrueConsense import (StreamCounts, mate_stats, dedup_stats, amplicon_intervals, amplicons_of, evidence_stats, rules_of, variants_of, write_amplicon_reads,
-                               write_amplicon_table, write_indel_table, write_variant_evidence, write_variant_tables)
     seen, got = {}, {}
     name, mincov, amb = a.samplename, a.coverage_level, a.noambiguity is False
     records = fasta.read_records(a.reference)
@@ -212,7 +212,7 @@ def run(a):
     seen.update(dedup_stats(a.dedup, seen.pop("dedup", None)))
     seen.update(want.stats(got))
     seen.setdefault("reads_primer_masked", 0)
-    table, strand, links = seen.pop("variant_table", None), got.get("variant_strand"), got.get("variant_links")
+    table = seen.pop("variant_table", None)
     arecs = seen.pop("amplicon_table", None)
     seen["amplicons_below"] = 0 if arecs is None else int((arecs["below"] > 0).sum())
 
@@ -271,24 +271,11 @@ def run(a):
     if a.depth_of_coverage is not None:
         with open(a.depth_of_coverage, "w") as out:
             out.write("".join(doc))
-    vparts, iparts, eparts = [], [], []             # one file, the contigs in axis order; rows carry the contig's name and its own positions
-    for rid, seq, s, *_ in sorted(per, key=lambda x: x[2]) if table is not None else ():
-        # (each contig's rows with the strand and link counts of its own columns: no pair across two contigs)
-        mine = [None if x is None else x[(x[key] >= s) & (x[key] < s + len(seq))] for x, key in ((table, "pos"), (strand, "pos"), (links, "a"))]
-        vparts.append((*mine, rid, axis_ref, s))
-        if want.indels:                             # (likewise the contig's own events; a deletion that runs past the contig's end reads N there)
-            events, text, totals = got["indel_events"]
-            found = (events[(events["pos"] >= s) & (events["pos"] < s + len(seq))], text, totals[(totals["pos"] >= s) & (totals["pos"] < s + len(seq))])
-            iparts.append((mine[0], found, rid, axis_ref[:s + len(seq)], s))
-        if want.evidence:                           # (... and the evidence counts of its own columns)
-            ev = got["variant_evidence"]
-            eparts.append((mine[0], ev[(ev["pos"] >= s) & (ev["pos"] < s + len(seq))], rid, axis_ref[:s + len(seq)], s))
-    seen.update(write_variant_tables(a, vparts, want))
-    if want.indels:
-        write_indel_table(want.indels, iparts)
-    seen.update(evidence_stats())
-    if want.evidence:
-        seen.update(write_variant_evidence(want.evidence[0], eparts, want.evidence[1]))
+    # one file per table, the contigs in axis order; rows carry the contig's name and its own positions, from the counts of its own
+    # columns: no pair across two contigs.  The reference ends with the contig: a deletion that runs past its end reads N there.
+    parts = [part_of_columns(table, got, s, s + len(seq), rid, axis_ref[:s + len(seq)], s)
+             for rid, seq, s, *_ in (sorted(per, key=lambda x: x[2]) if table is not None else ())]
+    seen.update(write_tables(a, parts, want))
     if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
         write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
     if want.areads:                                 # one file: REGION is each amplicon's contig

@@ -28,8 +28,8 @@ def main(argv=None):
     from .indexing import Gffindex
     from .io import fasta
     from .Outputs import WriteOutputs
-    from .TrueConsense import (GetArgs, StreamCounts, amplicon_intervals, amplicons_of, rules_of, variants_of,
-                               write_amplicon_reads, write_amplicon_table, write_variant_tables)
+    from .cli_args import GetArgs, amplicon_intervals, amplicons_of, rules_of, variants_of
+    from .cli_tables import StreamCounts, TablePart, write_amplicon_reads, write_amplicon_table, write_tables
     a = GetArgs([x for x in argv])
     backend = os.environ.get("TCMI_SPLIT_BACKEND", "nccl")
     torch.cuda.set_device(device)
@@ -64,7 +64,7 @@ def main(argv=None):
             if a.variant_table is not None:                          # (from the reduced counts, as the single-GPU command line from its own)
                 if recs is None:                                     # (else the records the root listed behind the reduce, for the ranks' counts)
                     recs = _state.default_context().variants(index.counts, refseq, **variants_of(a))
-                write_variant_tables(a, [(recs, got.get("variant_strand"), got.get("variant_links"), refID, refseq, 0)], want)
+                write_tables(a, [TablePart(recs, refID, refseq, 0, got.get("variant_strand"), got.get("variant_links"))], want)
             amps = amplicons_of(a)
             if amps:                                                 # (likewise the amplicon table)
                 arecs = _state.default_context().interval_stats(index.counts, amplicon_intervals(amps), a.coverage_level)
