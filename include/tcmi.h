@@ -664,6 +664,68 @@ int  tcmi_evidence_verdict(int64_t n, int64_t qual, int64_t mapq, int64_t dist, 
 int  tcmi_variants_evidence_text(const tcmi_variant *records, int64_t n, const tcmi_evidence_counts *ev, int64_t n_cols, /* the records' distinct positions, ascending */
                                  int32_t min_qual, int32_t min_mapq, int32_t min_dist, const char *region, int64_t pos_offset,
                                  const uint8_t *ref, int64_t n_ref, char *text, int64_t cap, int64_t *len);
+/* ---- codon counts (additive: what do the variant table's rows mean for the protein?  the reference has nothing like it) -------------
+ * For queried codons — three adjacent columns of the count matrix's axis — the number of kept records by the class of their token at the
+ * first column AND the second AND the third, counted by one HIP kernel over the inflated record stream a device-decoded read set left
+ * resident on its context.  Translating every row of the variant table on its own is wrong whenever two rows fall into one codon
+ * (SARS-CoV-2's N:R203K/G204R, GGG -> AAC): the count matrix forgets which read a token came from, only the records know the triplet a
+ * molecule carries.  All arithmetic is integer; the sums are the same in every run.  RECORDS are counted, not templates.
+ *   codons         c0_0 < c0_1 < ... < c0_{n-1}: the first columns on the count matrix's axis (under a contig layout: shifted by the
+ *                  contig's slot), each in [0, 2^29 - 2), n in 1..16 384.  Codon e is the columns c0_e, c0_e + 1, c0_e + 2.
+ *                  Consecutive c0 may differ by 1 or 2: overlapping reading frames are ordinary in viruses.
+ *   class          tcmi_readset_link_counts' seven, under the read filter, the floor, the primer table, the mate rule, the duplicate
+ *                  rule and the layout the read set REMEMBERS.
+ *   j[t0][t1][t2]  the kept records with those classes at the three columns.  j[0][0][0] is always 0.
+ *   ins_inside     the records counted in j whose token at the first or the second column carries the I mark: inserted bases lie inside
+ *                  the codon, the record is frame-shifted there.  They stay in j.  An I mark on the third column is not inside.
+ *   pos, reserved  c0_e and 0.
+ *   invariant      for every codon, slot k in 0..2 and class x in 1..6: the sum of j with class x at slot k is the count matrix at
+ *                  (plane x, c0 + k) for x in 1..5, and cov minus the planes 1..5 there for x = 6.
+ *   tcmi_readset_codon_counts   residency, sub-ranges, an empty read set (zeros, TCMI_OK), the wait and the scratch as for
+ *                  tcmi_readset_link_counts.  Its launch is timed under TCMI_K_LINK_COUNTS.
+ *   tcmi_cds       one reading frame: a GFF row of type CDS on the axis' columns [start, end), strand +1 or -1, phase 0..2.  On +1 the
+ *                  codons are the consecutive triplets from start + phase upward, on -1 from end - 1 - phase downward; an incomplete
+ *                  last triplet is dropped.  A CDS written as several rows is several frames, each trusted for its own phase; the
+ *                  codon that straddles two rows is not reported.  On the axis a codon is three adjacent columns, the lowest its c0.
+ *   tcmi_codon_aa  HOST: three planes TCMI_A..TCMI_G in coding order -> the amino acid's letter in the standard genetic code, '*' for a
+ *                  stop; anything else: 'X'.
+ *   tcmi_codon_select   HOST: the distinct c0, ascending, of the frames' codons that hold at least one of `records` (ascending by pos)
+ *                  with an allele in planes A..X ('+' rows do not select, as they do not link).  *n_found always says how many there
+ *                  are; more than cap: nothing written and TCMI_E_ARG, except for the sizing call (c0 = NULL, cap = 0).
+ *   tcmi_codons_text   HOST, re-entrant, no GPU: the writer of --codon-table's rows, one per (frame, counted codon inside it, reported
+ *                  triplet).  counts[0..n): ascending by pos; names[f]: frame f's FEATURE; matrix: the count matrix ([TCMI_NCOL][ld],
+ *                  L columns), which the invariant is checked against — a codon's neighbour columns need not have a variant record; a
+ *                  column >= L has depth 0.  Row:
+ *                  REGION FEATURE STRAND CODON POS REF_CODON REF_AA ALT_CODON ALT_AA EFFECT SUBS COUNT SPAN FREQ PARTIAL OTHER INS_INSIDE.
+ *                  CODON: the 1-based number of the codon in its frame, in coding direction; POS = c0 - pos_offset + 1; the codons in
+ *                  coding orientation (on -: the complement of the columns in descending order; a reference base outside A, C, G, T,
+ *                  or beyond n_ref: N).  SPAN = the records with a class >= 1 at all three columns.  A complete triplet has all three
+ *                  classes in 1..4, or all three 5: spelled ---, ALT_AA -, EFFECT DEL.  COUNT: its records; FREQ = COUNT / SPAN with
+ *                  %.6f; OTHER = SPAN minus all complete triplets' counts (mixed deletions, N, bases past SEQ); PARTIAL = the records
+ *                  with class 0 at one or two of the columns.  A complete triplet other than the reference codon is reported iff
+ *                  COUNT >= min_alt_depth, COUNT * den >= num * SPAN and SPAN >= min_depth: the variant table's thresholds and exact
+ *                  integer rule.  SUBS: the differing bases, 1..3; 0 for ---.  EFFECT: SYN, MIS, STOP_GAINED, STOP_LOST, DEL, or
+ *                  UNKNOWN (a reference codon with a base outside A, C, G, T: REF_AA X).  Rows: POS ascending, then the frames in the
+ *                  order given, then COUNT descending, then the triplet's class code ((t0 * 7 + t1) * 7 + t2 on the axis) ascending.
+ *                  TCMI_E_ARG, and NOTHING written (*len = 0), when the invariant fails (the two kernels disagree: no table), a
+ *                  counter is negative, or counts are not ascending.  Sizing call, short buffer and *len as for tcmi_variants_text.
+ *                  The header line (TCMI_CODONS_HEADER) is the caller's.
+ * TCMI_CODONS_LDS: the codons whose first columns and [344] counters a workgroup stages in LDS (11 x 344 counters + 11 columns = 15 180
+ * bytes); more codons are counted with atomics in memory; for tests.
+ * Range errors are TCMI_E_ARG: n outside 1..16 384, a c0 outside [0, 2^29 - 2) or not above the one before; den outside 1..10^6, num
+ * outside 0..den, min_alt_depth < 1, min_depth < 0; a frame with start < 0, end < start, a strand other than +1 / -1 or a phase outside
+ * 0..2. */
+typedef struct tcmi_codon_counts { int32_t j[7][7][7]; int32_t ins_inside, pos, reserved /* 0 */; } tcmi_codon_counts;   /* 346 int32 */
+typedef struct tcmi_cds { int32_t start, end /* axis columns, half open */, strand /* +1 / -1 */, phase /* 0..2 */; } tcmi_cds;
+#define TCMI_CODONS_LDS 11
+#define TCMI_CODONS_HEADER "REGION\tFEATURE\tSTRAND\tCODON\tPOS\tREF_CODON\tREF_AA\tALT_CODON\tALT_AA\tEFFECT\tSUBS\tCOUNT\tSPAN\tFREQ\tPARTIAL\tOTHER\tINS_INSIDE\n"
+int  tcmi_readset_codon_counts(tcmi_ctx *ctx, const tcmi_readset *rs, int64_t n, const int64_t *c0 /* host */,
+                               tcmi_codon_counts *records /* host, n */);
+int  tcmi_codon_aa(int b0, int b1, int b2);
+int  tcmi_codon_select(const tcmi_variant *records, int64_t n, const tcmi_cds *cds, int64_t n_cds, int64_t *c0, int64_t cap, int64_t *n_found);
+int  tcmi_codons_text(const tcmi_codon_counts *counts, int64_t n, const tcmi_cds *cds, int64_t n_cds, const char *const *names,
+                      const int32_t *matrix, int64_t L, int64_t ld, int64_t num, int64_t den, int32_t min_alt_depth, int32_t min_depth,
+                      const char *region, int64_t pos_offset, const uint8_t *ref, int64_t n_ref, char *text, int64_t cap, int64_t *len);
 /* counters of a context: "one_sync_taken" / "one_sync_declined" — files (or block ranges) the one-sync path delivered / handed to the
  * several-kernel path; "one_sync_retried" — files the one-sync path took a second time, its arrays sized for the worst case, because
  * the records outnumbered what the hint of their mean size allowed for; "one_sync_last_decline_flags" — why the last one was handed over (packer flags; 0: it was not a packer flag);
@@ -684,7 +746,8 @@ enum { TCMI_K_TALLY = 0 /* bit-plane tally kernel */, TCMI_K_CALL = 1, TCMI_K_ZE
        TCMI_K_INTERVALS = 11 /* the amplicon table's one launch */,
        TCMI_K_AMPLICON_READS = 12 /* tcmi_readset_amplicon_reads' one launch */,
        TCMI_K_STRAND_COUNTS = 13 /* tcmi_readset_strand_counts' one launch */,
-       TCMI_K_LINK_COUNTS = 14 /* tcmi_readset_link_counts' one launch */,
+       TCMI_K_LINK_COUNTS = 14 /* tcmi_readset_link_counts' one launch; tcmi_readset_codon_counts' one launch is filed in the same bracket
+                                    (a slot of its own would move TCMI_K_NKERNELS, which is part of the ABI) */,
        TCMI_K_INDEL_EVENTS = 15 /* tcmi_readset_indel_events' launches (count, verify, gather) of one attempt as one bracket */,
        TCMI_K_EVIDENCE_COUNTS = 16 /* tcmi_readset_evidence_counts' one launch */,
        TCMI_K_MATE_JOIN = 17 /* the mate join's table reset and two launches (build, probe) as one bracket; under the duplicate rule

@@ -20,7 +20,10 @@ variant table's '+' and '*' positions, with its length, its bases and the record
 --variant-min-depth; counted likewise; needs --variant-table; not with --batch, --index-override or -i --gpus N), the evidence table
 --variant-evidence FILE [--evidence-min-qual Q] [--evidence-min-mapq Q] [--evidence-min-enddist N] (the variant table's rows with the
 mean base quality, mapping quality and distance to the read's end of the reference's and the allele's tokens, and EVIDENCE = PASS or
-LOWQ, LOWMQ, END; counted likewise; needs --variant-table; not with --batch, --index-override or -i --gpus N), and
+LOWQ, LOWMQ, END; counted likewise; needs --variant-table; not with --batch, --index-override or -i --gpus N), the codon table
+--codon-table FILE (for every codon of the GFF's CDS rows that holds a row of the variant table the triplets the records carry there, with
+their amino acids and EFFECT, under the variant table's thresholds: two changes on the same reads are one row; counted likewise; needs
+--variant-table; not with --batch, --index-override or -i --gpus N), and
 
     python -m trueconsense_amd.TrueConsense --batch MANIFEST -ref r.fa -gff r.gff -cov 30 [-noambig] [-t N]
 
@@ -37,10 +40,10 @@ import sys
 import time
 
 from . import _state
-from .cli_args import (GetArgs, _child_argv, amplicon_intervals, amplicon_reads_of, amplicons_of, evidence_of, links_of, primers_of,  # noqa: F401
+from .cli_args import (GetArgs, _child_argv, amplicon_intervals, amplicon_reads_of, amplicons_of, codons_of, evidence_of, links_of, primers_of,  # noqa: F401
                        read_filter_of, read_manifest, rules_of, strand_of, variants_of)
-from .cli_tables import (StreamCounts, TablePart, amplicon_reads_text, dedup_stats, evidence_stats, link_stats, mate_stats,  # noqa: F401
-                         write_amplicon_reads, write_amplicon_table, write_tables)
+from .cli_tables import (CodonPart, StreamCounts, TablePart, amplicon_reads_text, codon_frames, dedup_stats, evidence_stats,  # noqa: F401
+                         link_stats, mate_stats, write_amplicon_reads, write_amplicon_table, write_codon_table, write_tables)
 from .Coverage import BuildCoverage
 from .indexing import Gffindex, Override_index_positions, build_counts, read_override_index
 from .launch import _spawn, run_gpus  # noqa: F401
@@ -161,6 +164,10 @@ def _single_sample(a, flt, t):
     bam = LazyBam(a.input, threads=a.threads, read_filter=flt)      # reads reach the host only if an insert candidate needs its tokens
     t["bam_open"] = time.perf_counter()
     want, got = StreamCounts(a), {}
+    IndexGff = None
+    if want.codons:                                 # (the frames must be known behind the step: the GFF is read in front of it)
+        IndexGff = Gffindex(a.features)
+        want.frames = codon_frames(IndexGff.rows)
     if want:                                        # counted behind the step, on the read set the step returned, while its stream is resident
         if want.lists_records:                      # (the columns must be known then: the step computes the table's records)
             from .io import fasta
@@ -174,7 +181,7 @@ def _single_sample(a, flt, t):
             write_amplicon_reads(a.amplicon_reads, a.samplename, got["amplicon_reads"], want.areads[0])
     else:
         counts = build_counts(bam, a.reference)     # decoded, packed and tallied on the device
-    IndexGff = Gffindex(a.features)
+    IndexGff = IndexGff or Gffindex(a.features)
     t["tally"] = time.perf_counter()
 
     if a.index_override:
@@ -196,6 +203,8 @@ def _single_sample(a, flt, t):
         recs = _state.default_context().variants(indexDict.counts, refseq, **variants_of(a))
         parts = [TablePart(recs, refID, refseq, 0, got.get("variant_strand"), got.get("variant_links"), got.get("indel_events"), got.get("variant_evidence"))]
     vstats = write_tables(a, parts, want)
+    if want.codons:                                 # (its keys only with the flag: the dict of before otherwise)
+        vstats.update(write_codon_table(a, [CodonPart(got["codon_counts"], *want.frames, refID, refseq, 0, indexDict.counts)], want))
 
     amps, n_below = amplicons_of(a), 0
     if amps:                                        # likewise: the matrix behind the read filter, --min-baseq, --primers and --index-override

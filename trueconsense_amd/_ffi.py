@@ -93,6 +93,10 @@ _SIGS = {
     "tcmi_readset_evidence_counts": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "tcmi_evidence_verdict": (_int, [_i64, _i64, _i64, _i64, _i32, _i32, _i32]),
     "tcmi_variants_evidence_text": (_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, C.c_char_p, _i64, _vp, _i64, _vp, _i64, _P(_i64)]),
+    "tcmi_readset_codon_counts": (_int, [_vp, _vp, _i64, _vp, _vp]),
+    "tcmi_codon_aa": (_int, [_int, _int, _int]),
+    "tcmi_codon_select": (_int, [_vp, _i64, _vp, _i64, _vp, _i64, _P(_i64)]),
+    "tcmi_codons_text": (_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, C.c_char_p, _i64, _vp, _i64, _vp, _i64, _P(_i64)]),
     "tcmi_profile_enable": (_int, [_vp, _int]),
     "tcmi_profile_reset": (_int, [_vp]),
     "tcmi_profile_get": (_int, [_vp, _int, _P(C.c_double), _P(_i64)]),

@@ -116,6 +116,11 @@ def links_of(a):
     return a.variant_links, int(a.link_neighbours), dict(min_depth=int(a.link_min_depth), ratio=a.link_ratio)
 
 
+def codons_of(a):
+    """The parsed namespace's --codon-table file, or None without the flag (its thresholds are the variant table's: variants_of)."""
+    return getattr(a, "codon_table", None)
+
+
 def evidence_of(a):
     """The parsed namespace's --variant-evidence settings as (file, keyword arguments of engine.variants_evidence_text), or None without
     the flag."""
@@ -379,6 +384,14 @@ def GetArgs(givenargs):
         (("--evidence-min-enddist",), dict(type=_range_arg(parser, "--evidence-min-enddist", 255), default=None, metavar="N",
                                            help="EVIDENCE names END when the allele sits on average fewer than N bases from its reads'\n"
                                                 "nearer end; 0: off (default 5)")),
+        (("--codon-table",), dict(type=str, default=None, metavar="File",
+                                  help="also write what the variant table's rows mean for the protein: for every codon of the GFF's\n"
+                                       "CDS rows that holds a row of the table, each triplet the records carry there that passes\n"
+                                       "--min-af / --min-alt-depth / --variant-min-depth: REGION FEATURE STRAND CODON POS REF_CODON\n"
+                                       "REF_AA ALT_CODON ALT_AA EFFECT (SYN, MIS, STOP_GAINED, STOP_LOST, DEL, UNKNOWN) SUBS COUNT SPAN\n"
+                                       "FREQ PARTIAL OTHER INS_INSIDE; two changes on the same reads are one row, counted in the\n"
+                                       "records the device decoded; needs --variant-table and the device decoder; not with --batch,\n"
+                                       "--index-override or -i --gpus N")),
         (("--amplicon-table",), dict(type=str, default=None, metavar="File",
                                      help="also write per amplicon of the scheme the depth of its columns, tab-separated: SAMPLE REGION\n"
                                           "AMPLICON POOL START END LEN MEAN MEDIAN MIN MIN_POS BELOW (BELOW: columns under -cov), from\n"
@@ -415,7 +428,8 @@ def GetArgs(givenargs):
     for flag, on, deps in (("--variant-strand", a.variant_strand, ("strand_min_depth", "strand_ratio")),
                            ("--variant-links", a.variant_links is not None, ("link_neighbours", "link_min_depth", "link_ratio")),
                            ("--indel-table", a.indel_table is not None, ()),
-                           ("--variant-evidence", a.variant_evidence is not None, ("evidence_min_qual", "evidence_min_mapq", "evidence_min_enddist"))):
+                           ("--variant-evidence", a.variant_evidence is not None, ("evidence_min_qual", "evidence_min_mapq", "evidence_min_enddist")),
+                           ("--codon-table", a.codon_table is not None, ())):
         names = " / ".join("--" + d.replace("_", "-") for d in deps)
         for bad, why in ((not on and any(getattr(a, d) is not None for d in deps), f"{names} need {flag}."),
                          (on and a.batch is not None, f"{flag} goes with a single sample (-i): --batch is refused, its file runner has no hook behind its steps."),
@@ -424,7 +438,9 @@ def GetArgs(givenargs):
                          (on and flag == "--indel-table" and a.batch is None and a.gpus and a.gpus > 1,
                           f"{flag} does not go with -i --gpus N: the ranks' event lists would have to be merged on rank 0, which is not built."),
                          (on and flag == "--variant-evidence" and a.batch is None and a.gpus and a.gpus > 1,
-                          f"{flag} does not go with -i --gpus N: the ranks' sums would have to be added up on rank 0, which is not built.")):
+                          f"{flag} does not go with -i --gpus N: the ranks' sums would have to be added up on rank 0, which is not built."),
+                         (on and flag == "--codon-table" and a.batch is None and a.gpus and a.gpus > 1,
+                          f"{flag} does not go with -i --gpus N: the ranks' counters would have to be added up on rank 0, which is not built.")):
             if bad:
                 print(f"{why} Exiting...")
                 sys.exit(1)
@@ -498,6 +514,8 @@ def _child_argv(a, single, tables=True):
         if a.variant_links:
             out += ["--variant-links", a.variant_links, "--link-neighbours", str(a.link_neighbours), "--link-min-depth", str(a.link_min_depth),
                     "--link-ratio", str(a.link_ratio)]
+        if getattr(a, "codon_table", None):
+            out += ["--codon-table", a.codon_table]
         if a.amplicon_table:
             out += ["--amplicon-table", a.amplicon_table]
         out += ["-i", a.input, "-o", a.output, "-name", a.samplename]

@@ -1,13 +1,16 @@
 """The command line's tables: what is counted behind the step (StreamCounts) and written from it.  TablePart is one part of the
 tables that hang on the variant table's records — a sample, or a contig of the axis (part_of_columns) — and write_tables their one
-writer, for every runner; beside them the amplicon tables' writers and the --stats keys of the counts."""
+writer, for every runner; beside them the codon table's sibling (CodonPart, codon_part_of_columns, write_codon_table: it hangs on
+the GFF's reading frames and the count matrix as well), the amplicon tables' writers and the --stats keys of the counts."""
 from __future__ import annotations
 
 import os
 from typing import NamedTuple
 
 from . import engine
-from .cli_args import amplicon_reads_of, evidence_of, links_of, strand_of, variants_of
+import numpy as np
+
+from .cli_args import amplicon_reads_of, codons_of, evidence_of, links_of, strand_of, variants_of
 
 
 class StreamCounts:
@@ -19,16 +22,20 @@ class StreamCounts:
     indels = None                                                   # --indel-table's file
     # (nor is --variant-evidence's "variant_evidence": its sums would reduce like the strand counts, but the split's keywords are fixed)
     evidence = None                                                 # --variant-evidence's (file, thresholds)
+    # (nor is --codon-table's "codon_counts", for the same reason)
+    codons = None                                                   # --codon-table's file
+    frames = None                                                   # ... and its reading frames on the axis: codon_frames' (cds, names), set by the runner
 
     def __init__(self, a, layout=None):
         self.areads, self.srule, self.links = amplicon_reads_of(a, layout), strand_of(a), links_of(a)
         self.indels = getattr(a, "indel_table", None)
         self.evidence = evidence_of(a)
-        self.lists_records = bool(self.srule or self.links or self.indels or self.evidence)     # must the step list the variant table's records?
+        self.codons = codons_of(a)
+        self.lists_records = bool(self.srule or self.links or self.indels or self.evidence or self.codons)     # must the step list the variant table's records?
         self.variants = variants_of(a) if self.lists_records else None
         # the flag named when the file leaves the device path (indexing.device_readset's `need`)
         self.need = "--variant-strand" if self.srule else "--variant-links" if self.links else "--indel-table" if self.indels else \
-            "--variant-evidence" if self.evidence else "--amplicon-reads" if self.areads else None
+            "--variant-evidence" if self.evidence else "--amplicon-reads" if self.areads else "--codon-table" if self.codons else None
 
     def __bool__(self):
         return self.need is not None
@@ -49,6 +56,8 @@ class StreamCounts:
             got["indel_events"] = ctx.indel_events_of(rs, records, **self.variants)
         if self.evidence:
             got["variant_evidence"] = ctx.evidence_counts_of(rs, records)
+        if self.codons:
+            got["codon_counts"] = ctx.codon_counts_of(rs, records, (self.frames or codon_frames(()))[0])
         return got
 
     def split_kwargs(self, ref):
@@ -142,6 +151,64 @@ def write_tables(a, parts, want):
         path, rule = want.evidence
         stats.update(evidence_stats(_write(path, engine.VARIANTS_EVIDENCE_HEADER,
                                            lambda p: engine.variants_evidence_text(p.records, p.evidence, p.region, p.ref, p.pos_offset, **rule), parts)))
+    return stats
+
+
+class CodonPart(NamedTuple):
+    """One part of the codon table: a sample, or one contig of the axis.  counts: StreamCounts.count's "codon_counts" at the part's
+    codons; frames, names: its reading frames on the axis (codon_frames); region, ref, pos_offset: as TablePart's; matrix: the count
+    matrix [L, 7] on the counts' axis, which the counts must add up to."""
+    counts: object
+    frames: object
+    names: list
+    region: str
+    ref: object
+    pos_offset: int
+    matrix: object
+
+
+def codon_frames(rows, layout=None):
+    """The GFF's reading frames on the axis -> (engine.CDS_DTYPE array, their names): every row (io.gff's dicts) of type CDS with
+    strand + or - is one frame, its phase column '.' read as 0; a row with another strand, phase or without columns is no frame.
+    layout = (the BAM header's names, their shifts): each contig takes its own rows by seqid, shifted by its slot (a seqid the layout
+    drops or does not know: no frame); without one every CDS row counts, the GFF being the one reference's.  A frame's name is the
+    row's Name, else ID, else gene attribute, else CDS_{start}_{end}."""
+    shift_of = None if layout is None else {n: int(s) for n, s in zip(*layout)}
+    cds, names = [], []
+    for r in rows:
+        strand, phase = r.get("strand"), r.get("phase")
+        if r.get("type") != "CDS" or strand not in ("+", "-") or phase not in (".", "0", "1", "2"):
+            continue
+        sh = 0 if shift_of is None else shift_of.get(r.get("seqid"), -1)
+        start, end = int(r["start"]) - 1 + sh, int(r["end"]) + sh          # (GFF: 1-based, closed)
+        if sh < 0 or start < sh or end < start or end >= 1 << 29:
+            continue
+        cds.append((start, end, 1 if strand == "+" else -1, 0 if phase == "." else int(phase)))
+        names.append(next((str(r[k]) for k in ("Name", "ID", "gene") if isinstance(r.get(k), str) and r[k]), "CDS_%d_%d" % (r["start"], r["end"])))
+    return np.array(cds, engine.CDS_DTYPE), names
+
+
+def codon_part_of_columns(got, frames, names, matrix, lo, hi, region, ref, pos_offset):
+    """The codon table's part of the axis' columns [lo, hi) — a contig's own: the counts of `got` (StreamCounts.count's dict) and the
+    frames that start there."""
+    counts = got.get("codon_counts")
+    counts = np.zeros(0, engine.CODON_DTYPE) if counts is None else counts[(counts["pos"] >= lo) & (counts["pos"] < hi)]
+    keep = [k for k in range(len(frames)) if lo <= int(frames["start"][k]) < hi]
+    return CodonPart(counts, frames[keep], [names[k] for k in keep], region, ref, pos_offset, matrix)
+
+
+def write_codon_table(a, parts, want):
+    """--codon-table: parts = [CodonPart], one per sample or per contig in axis order, want = StreamCounts(a).  Like _write, the whole
+    text is built before the file is opened: a part whose counts do not add up to the matrix (TcmiError) leaves the file unwritten.
+    -> its --stats keys (zeros, and nothing written, without the flag)."""
+    stats = dict(codon_frames=0, codon_codons=0, codon_rows=0, codon_rows_multi=0)
+    if not want.codons:
+        return stats
+    text = _write(want.codons, engine.CODONS_HEADER,
+                  lambda p: engine.codons_text(p.counts, p.frames, p.names, p.matrix, p.region, p.ref, p.pos_offset, **want.variants), parts)
+    rows = [ln.split("\t") for ln in text.splitlines()]
+    stats.update(codon_frames=sum(len(p.frames) for p in parts), codon_codons=sum(len(p.counts) for p in parts), codon_rows=len(rows),
+                 codon_rows_multi=sum(int(r[10]) >= 2 for r in rows))
     return stats
 
 

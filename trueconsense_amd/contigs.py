@@ -23,7 +23,8 @@ import numpy as np
 
 from . import _ffi, _state
 from .cli_args import amplicon_intervals, amplicons_of, rules_of, variants_of
-from .cli_tables import StreamCounts, dedup_stats, mate_stats, part_of_columns, write_amplicon_reads, write_amplicon_table, write_tables
+from .cli_tables import (StreamCounts, codon_frames, codon_part_of_columns, dedup_stats, mate_stats, part_of_columns, write_amplicon_reads,
+                         write_amplicon_table, write_codon_table, write_tables)
 from .engine import BamFile, ReadRules, modal_tokens
 from .Events import _parse_token, candidates_from_flags
 from .io import fasta
@@ -201,6 +202,9 @@ def run(a):
     amps = amplicons_of(a, (hdr_names, shift))      # (each contig's amplicons shifted by its slot; none left: an argument error)
     seen["amplicons"] = len(amps) if amps else 0
     want = StreamCounts(a, (hdr_names, shift))      # (likewise, for --amplicon-reads; one call each over all contigs' columns on the shifted axis)
+    if want.codons:                                 # (each contig's CDS rows shifted by its slot; the table's invariant reads the counts)
+        want.frames = codon_frames(gffobj.rows, (hdr_names, shift))
+        want_counts = True
     axis_ref = axis_reference(records, hdr_names, shift, axis_len) if a.variant_table is not None else None
     var = dict(variants_of(a), ref=axis_ref) if axis_ref is not None else None
     plain, alt, flags, counts, ext, dropped, host = step_contigs(ctx, a.input, shift, slot, axis_len, mincov, amb, hdr_names,
@@ -276,6 +280,9 @@ def run(a):
     parts = [part_of_columns(table, got, s, s + len(seq), rid, axis_ref[:s + len(seq)], s)
              for rid, seq, s, *_ in (sorted(per, key=lambda x: x[2]) if table is not None else ())]
     seen.update(write_tables(a, parts, want))
+    if want.codons:                                 # (its keys only with the flag)
+        seen.update(write_codon_table(a, [codon_part_of_columns(got, *want.frames, counts, s, s + len(seq), rid, axis_ref[:s + len(seq)], s)
+                                          for rid, seq, s, *_ in sorted(per, key=lambda x: x[2])], want))
     if arecs is not None:                           # one table: REGION is the contig, positions are the contig's own
         write_amplicon_table(a.amplicon_table, [(name, arecs)], amps)
     if want.areads:                                 # one file: REGION is each amplicon's contig

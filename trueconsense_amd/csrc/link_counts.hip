@@ -51,14 +51,6 @@ struct LcArgs {
     int32_t n, K;
 };
 
-// the planes a token adds to -> its class
-__device__ inline uint32_t class_of(uint32_t bits)
-{
-    if (bits == 0u) return 0u;
-    const uint32_t m = bits & ((1u << TCMI_A) | (1u << TCMI_T) | (1u << TCMI_C) | (1u << TCMI_G) | (1u << TCMI_X));
-    return m ? (uint32_t)__builtin_ctz(m) : 6u;             // (TCMI_A..TCMI_X are 1..5; a token adds to at most one of them)
-}
-
 __global__ __launch_bounds__(BLOCK) void link_counts_kernel(LcArgs a)
 {
     __shared__ int32_t s_cols[LDS_P];

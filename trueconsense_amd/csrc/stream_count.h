@@ -2,7 +2,8 @@
 // arena.  HOST side: is the stream still there (tally.hip's long reads, ins_entries.hip, the counting calls), grow-only scratch of a
 // context, and the driver of a COUNTING call — one kernel over the records, one lane per record, that turns a small input (a table, a
 // list of columns) into integer counters: tcmi_readset_amplicon_reads (amplicon_reads.hip), tcmi_readset_strand_counts
-// (strand_counts.hip), tcmi_readset_link_counts (link_counts.hip) — with the column check of the latter two; tcmi_readset_indel_events
+// (strand_counts.hip), tcmi_readset_link_counts (link_counts.hip), tcmi_readset_codon_counts (codon_counts.hip) — with the column check
+// of the strand and link counts; tcmi_readset_indel_events
 // (indel_events.hip) keeps a driver of its own (a keyed table, attempts) on the same refusals, scratch and launch shape.  DEVICE side,
 // at the end: the frame such a kernel holds around its counting rule — the workgroup's counters (CountFrame) and the walk over the
 // records (each_record).  Which record such a kernel counts: pack_device.h's kept_span; how its lanes are joined per counter:

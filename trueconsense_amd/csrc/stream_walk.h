@@ -1,6 +1,6 @@
 // stream_walk.h — DEVICE side (.hip files only) of the kernels that ask a kept record for its token at given columns of the count matrix's
 // axis, in ascending order: strand_counts.hip (the planes per strand), link_counts.hip (the token classes of a record at two columns
-// together) and indel_events.hip (the insertion behind and the deletion that starts on a column: after token_at, w.k is the op that
+// together), codon_counts.hip (at the three columns of a codon; class_of is theirs) and indel_events.hip (the insertion behind and the deletion that starts on a column: after token_at, w.k is the op that
 // holds the column).  One copy of the per-record incremental CIGAR walk and of the count matrix's token rule restated for one column, so both
 // kernels count exactly what tally_stream_kernel (tally.hip) counts.  Which record is kept and where it lies (kept_span), the primer
 // table's lookup (seg_find) and the leaves of the rule (base_plane, qual_at): pack_device.h.
@@ -64,6 +64,15 @@ __device__ inline uint32_t token_at(Walk &w, int32_t c, uint32_t Q)
     } else if (op == 2 && !ins) bits |= 1u << TCMI_X;       // "*+.." does not count X
     if (ins) bits |= 1u << TCMI_I;
     return bits;
+}
+
+// the planes a token adds to (token_at) -> its class: 0 nothing, 1..4 plane A, T, C, G, 5 a deleted column that counts X, 6 coverage only
+// (link_counts.hip, codon_counts.hip)
+__device__ inline uint32_t class_of(uint32_t bits)
+{
+    if (bits == 0u) return 0u;
+    const uint32_t m = bits & ((1u << TCMI_A) | (1u << TCMI_T) | (1u << TCMI_C) | (1u << TCMI_G) | (1u << TCMI_X));
+    return m ? (uint32_t)__builtin_ctz(m) : 6u;             // (TCMI_A..TCMI_X are 1..5; a token adds to at most one of them)
 }
 
 __device__ inline int32_t first_at_or_above(const int32_t *cols, int32_t n, int32_t p)

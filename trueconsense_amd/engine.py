@@ -264,6 +264,67 @@ def variants_links_text(records, links, k, region, ref, pos_offset=0, min_depth=
     return buf.raw[:ln.value].decode("latin-1")
 
 
+# struct tcmi_codon_counts: the kept records by token class at the three columns of a codon; struct tcmi_cds: one reading frame (--codon-table)
+CODON_DTYPE = np.dtype([("j", np.int32, (7, 7, 7)), ("ins_inside", np.int32), ("pos", np.int32), ("reserved", np.int32)])
+CDS_DTYPE = np.dtype([("start", np.int32), ("end", np.int32), ("strand", np.int32), ("phase", np.int32)])
+CODONS_HEADER = ("REGION\tFEATURE\tSTRAND\tCODON\tPOS\tREF_CODON\tREF_AA\tALT_CODON\tALT_AA\tEFFECT\tSUBS\tCOUNT\tSPAN\tFREQ\tPARTIAL\tOTHER\t"
+                 "INS_INSIDE\n")
+CODONS_LDS = 11                  # TCMI_CODONS_LDS: codons whose first columns and counters the kernel stages in LDS
+CODONS_MAX = 1 << 14             # the codons of one tcmi_readset_codon_counts call
+
+
+def codon_aa(b0, b1, b2):
+    """tcmi_codon_aa (HOST): three planes A..G (1..4: A, T, C, G) in coding order -> the amino acid's letter in the standard genetic
+    code, "*" for a stop, "X" for anything else."""
+    return chr(lib().tcmi_codon_aa(int(b0), int(b1), int(b2)))
+
+
+def codon_select(records, cds):
+    """tcmi_codon_select (HOST): the distinct first columns, ascending, of the codons of the frames `cds` (CDS_DTYPE) that hold at
+    least one of the variant `records` with an allele in A, T, C, G, * -> int64 array."""
+    records = np.ascontiguousarray(records, VARIANT_DTYPE)
+    cds = np.ascontiguousarray(cds, CDS_DTYPE)
+    args = (ptr(records) if len(records) else None, len(records), ptr(cds) if len(cds) else None, len(cds))
+    n = C.c_int64(0)
+    rc = lib().tcmi_codon_select(*args, None, 0, C.byref(n))                # the sizing call
+    out = np.zeros(n.value, np.int64)
+    if not rc and n.value:
+        rc = lib().tcmi_codon_select(*args, ptr(out), len(out), C.byref(n))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_codon_select: a record outside the axis or the planes, or a frame with start < 0, end < start, "
+                                 "a strand other than +1 / -1 or a phase outside 0..2")
+    return out
+
+
+def codons_text(counts, cds, names, matrix, region, ref, pos_offset=0, min_af="0.03", min_alt_depth=1, min_depth=10):
+    """--codon-table's rows (tcmi_codons_text; HOST): one per (frame, counted codon inside it, reported triplet).  counts:
+    Context.codon_counts, ascending; cds (CDS_DTYPE) and names: the frames and their FEATURE; matrix: the count matrix [L, 7] on the
+    counts' axis.  -> str, without the header line (CODONS_HEADER).  TcmiError(E_ARG) when the counts do not add up to the matrix."""
+    counts = np.ascontiguousarray(counts, CODON_DTYPE)
+    cds = np.ascontiguousarray(cds, CDS_DTYPE)
+    if len(names) != len(cds):
+        raise ValueError("codons_text: %d frames, %d names" % (len(cds), len(names)))
+    planes = np.ascontiguousarray(np.asarray(matrix, np.int32).reshape(-1, 7).T)       # [7][L]
+    L = planes.shape[1]
+    ref = _ref_bytes(ref)
+    num, den = min_af_fraction(min_af)
+    texts = [str(x).encode() for x in names]
+    c_names = (C.c_char_p * max(len(texts), 1))(*texts)
+    args = (ptr(counts) if len(counts) else None, len(counts), ptr(cds) if len(cds) else None, len(cds), C.cast(c_names, C.c_void_p),
+            ptr(planes) if L else None, L, L, num, den, int(min_alt_depth), int(min_depth), str(region).encode(), int(pos_offset),
+            ptr(ref) if len(ref) else None, len(ref))
+    ln = C.c_int64(0)
+    buf = None
+    rc = lib().tcmi_codons_text(*args, None, 0, C.byref(ln))                # the sizing call
+    if not rc:
+        buf = C.create_string_buffer(ln.value + 1)
+        rc = lib().tcmi_codons_text(*args, C.cast(buf, C.c_void_p), ln.value, C.byref(ln))
+    if rc:
+        raise _ffi.TcmiError(rc, "tcmi_codons_text: the codon counts do not add up to the count matrix "
+                                 "(or a frame, the offset or the thresholds are out of range)")
+    return buf.raw[:ln.value].decode("latin-1")
+
+
 # struct tcmi_indel_event / tcmi_indel_totals: one insertion or deletion of the records at a column, the events per column (--indel-table)
 INDEL_EVENT_DTYPE = np.dtype([("pos", np.int32), ("kind", np.int32), ("len", np.int32), ("count", np.int32), ("cov", np.int32),
                               ("reserved", np.int32), ("text_off", np.int64)])
@@ -718,6 +779,26 @@ class Context:
         """link_counts at the distinct positions of variant `records` -> a structured array (LINK_DTYPE), empty without records"""
         cols = np.unique(np.ascontiguousarray(records, VARIANT_DTYPE)["pos"].astype(np.int64))
         return self.link_counts(readset, cols, k) if len(cols) else np.zeros(0, LINK_DTYPE)
+
+    def codon_counts(self, readset, c0):
+        """Joint token classes of the kept records at the three columns of codons (tcmi_readset_codon_counts): c0 the codons' first
+        columns, strictly ascending on the count matrix's axis (they may differ by 1 or 2: overlapping frames), 1..2^14 of them -> a
+        structured array (CODON_DTYPE): j[t0][t1][t2] the records with those classes at c0, c0 + 1, c0 + 2 (0 no token, 1..4 A T C G,
+        5 a deleted column, 6 coverage only), ins_inside those of them with inserted bases behind the first or second column, pos.
+        The read set must have been decoded on the device and its stream must still be resident on this context, else
+        TcmiError(E_UNSUPPORTED)."""
+        c0 = np.ascontiguousarray(c0, np.int64).reshape(-1)
+        out = np.zeros(len(c0), CODON_DTYPE)
+        check(lib().tcmi_readset_codon_counts(self.handle, readset.handle, len(c0), ptr(c0) if len(c0) else None, ptr(out) if len(c0) else None),
+              self.handle)
+        return out
+
+    def codon_counts_of(self, readset, records, cds):
+        """codon_counts at the codons of the frames `cds` (CDS_DTYPE) that hold one of the variant `records` (codon_select), in pieces of
+        2^14 codons -> a structured array (CODON_DTYPE), empty without such a codon"""
+        c0 = codon_select(records, cds)
+        parts = [self.codon_counts(readset, c0[k:k + CODONS_MAX]) for k in range(0, len(c0), CODONS_MAX)]
+        return np.concatenate(parts) if parts else np.zeros(0, CODON_DTYPE)
 
     def _indel_events(self, readset, cols, cov, num, den, min_alt_depth, min_depth):
         """one tcmi_readset_indel_events call of at most 2^20 columns, with room for what a file usually has; a call that says it
