@@ -93,6 +93,35 @@ def two_refs():
     return out
 
 
+SHARED_AT, SHARED_CIGAR, SHARED_INS = 100, "10M2I10M3D10M", "GT"
+SHARED_ELSEWHERE, SHARED_PAIRS = 200, (300, 320)
+
+
+@functools.lru_cache(maxsize=None)
+def shared_indel():
+    """a duplicate set that shares its insertion and its deletion: five forward fragments at SHARED_AT with SHARED_CIGAR and one SEQ,
+    their quality sums distinct, the best the third in the file; one fragment at SHARED_ELSEWHERE with the same inserted bases; two
+    proper pairs of equal ends at SHARED_PAIRS whose second mates carry 5M1I20M (the same base) inside the overlap -> specs in file order"""
+    rng = np.random.default_rng(80)
+    out = []
+    for k, q in enumerate((20, 25, 40, 30, 35)):
+        out.append(_frag(rng, "set_%d" % k, 0, SHARED_AT, SHARED_CIGAR, q, q != 40))
+    seq = out[0]["seq"][:10] + SHARED_INS + out[0]["seq"][12:]
+    for r in out:
+        r["seq"] = seq
+    far = _frag(rng, "elsewhere", 0, SHARED_ELSEWHERE, "10M2I10M", 30, False)
+    far["seq"] = far["seq"][:10] + SHARED_INS + far["seq"][12:]
+    out.append(far)
+    p1, p2 = SHARED_PAIRS
+    pairs = _pair(rng, "eq_a", p1, "40M", p2, "5M1I20M", 30, False) + _pair(rng, "eq_b", p1, "40M", p2, "5M1I20M", 22, True)
+    for r in pairs:
+        if "I" in r["cigar"]:
+            r["seq"] = r["seq"][:5] + "C" + r["seq"][6:]
+    out += pairs
+    order = sorted(range(len(out)), key=lambda i: out[i]["pos"])
+    return [out[i] for i in order]
+
+
 def arrays(specs):
     return mc.arrays(specs)
 

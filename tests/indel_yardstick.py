@@ -49,17 +49,19 @@ def inserted(ops, k, y):
     return out
 
 
-def record_events(r, table=(), q=0, slack=0, shift=0):
+def record_events(r, table=(), q=0, slack=0, shift=0, clip=0):
     """the events of one kept record -> [(column, kind, len, bases)]: a DEL at the first column of every D op, an INS at the last column
     of every reference-consuming op with an insertion behind it — each iff the token on that column is counted at all: the column lies
     in [head_end, tail_start) and the quality at the token's query index (a matched base: its own; a D / N op: the index at which the
-    op starts) is at least q"""
+    op starts) is at least q.  clip: the record's first `clip` columns are its mate's, or all of them a duplicate's (--mate-overlap,
+    --dedup): head_end = max(head_end, p + clip)"""
     ops = ss.parse_cigar(r["cigar"])
     seq = "" if r["seq"] == "*" else r["seq"].upper()
     qual = list(r["qual"]) if seq else []
     span = sum(n for op, n in ops if op in REF_OPS)
     p = r["pos"] + shift
     head_end, tail_start = py.read_mask(p, p + span - 1, table, slack)
+    head_end = max(head_end, p + clip)
 
     def counted(c, qi):
         return head_end <= c < tail_start and (q == 0 or (qual[qi] if qi < len(seq) else 0) >= q)
@@ -82,13 +84,14 @@ def record_events(r, table=(), q=0, slack=0, shift=0):
     return out
 
 
-def events(records, table=(), q=0, slack=0, flt=(0, 0, 0), shift=0):
-    """-> ({(column, kind, len, bases): records}, {column: [ins_total, del_total]}) over the kept records"""
+def events(records, table=(), q=0, slack=0, flt=(0, 0, 0), shift=0, clip=None):
+    """-> ({(column, kind, len, bases): records}, {column: [ins_total, del_total]}) over the kept records; clip: one per record"""
     counts, totals = {}, {}
-    for r in records:
+    assert clip is None or len(clip) == len(records)
+    for i, r in enumerate(records):
         if not kept(r, flt):
             continue
-        for ev in record_events(r, table, q, slack, shift):
+        for ev in record_events(r, table, q, slack, shift, 0 if clip is None else int(clip[i])):
             counts[ev] = counts.get(ev, 0) + 1
             totals.setdefault(ev[0], [0, 0])[ev[1] - 1] += 1
     return counts, totals

@@ -96,9 +96,11 @@ def arrays(specs):
     return rs.arrays(specs)
 
 
-def fuzz_specs(seed, n_pairs=520, n_single=120, ref_len=2000, tid=0, ref=None):
+def fuzz_specs(seed, n_pairs=520, n_single=120, ref_len=2000, tid=0, ref=None, n_edge=6):
     """A paired fuzz: pairs on random CIGARs of fuzz_reads (every op) whose second mate starts inside the first, and among them every
-    class of record the rule leaves alone — planted at fixed rates, so every seed holds them."""
+    class of record the rule leaves alone — planted at fixed rates, so every seed holds them —, n_single records without a mate, and
+    n_edge pairs (six, whatever n_pairs is, unless the caller says otherwise) whose loser carries an insertion on the last column of
+    its clip (_last_clipped_column: made behind all the others, so the first n_pairs pairs and the singles do not depend on n_edge)."""
     rng = np.random.default_rng(seed)
     ref = ref or "".join("ACGT"[int(k)] for k in rng.integers(0, 4, ref_len))
     out = []
@@ -150,6 +152,25 @@ def fuzz_specs(seed, n_pairs=520, n_single=120, ref_len=2000, tid=0, ref=None):
     out.sort(key=lambda r: r["pos"])
     for r in out:
         r["mapq"] = int(rng.choice((0, 19, 20, 60, 60, 60, 60, 60)))
+    out += _last_clipped_column(seed, ref, ref_len, tid, n_edge)
+    out.sort(key=lambda r: r["pos"])
+    return out
+
+
+def _last_clipped_column(seed, ref, ref_len, tid, n):
+    """pairs whose loser carries an insertion right behind the LAST column it shares with the winner — the insertion's token is the
+    clip's last, so it goes with it (mate_overlap_cases.cases' "ins_inside") —, from a generator of their own: the random pairs put an
+    insertion there in one seed of four only, and with these every record of the fuzz above stays what it was"""
+    rng = np.random.default_rng(seed + 9000)
+    out = []
+    for k in range(n):
+        s1, shared = int(rng.integers(30, 80)), int(rng.integers(1, 20))
+        p1 = int(rng.integers(0, max(1, ref_len - 700)))
+        p2 = p1 + s1 - shared                                       # (the winner ends on p1 + s1 - 1: clip = shared, the edge p2 + shared)
+        c2 = [(shared, "M"), (int(rng.integers(1, 5)), "I"), (int(rng.integers(10, 40)), "M")]
+        f1, f2 = (FIRST, LAST) if k % 2 else (163, 83)
+        out += [fz._read(rng, ref, p1, [(s1, "M")], f1, "e%d" % k, tid, mtid=tid, mpos=p2, tlen=0, mapq=60),
+                fz._read(rng, ref, p2, c2, f2, "e%d" % k, tid, mtid=tid, mpos=p1, tlen=0, mapq=60)]
     return out
 
 

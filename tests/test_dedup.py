@@ -15,14 +15,13 @@ from tests import dedup_big as db
 from tests import dedup_cases as dc
 from tests import dedup_yardstick as dy
 from tests import device_file as dvf
-from tests import evidence_yardstick as ey
 from tests import mate_big as mb
 from tests import mate_overlap_cases as mc
 from tests import mate_overlap_yardstick as my
 from tests import primer_yardstick as py
 from tests import repeat_bam as rb
+from tests import rules_marks as rm
 from tests import schemes as sch
-from oracle import tc_oracle as orc
 from trueconsense_amd import _ffi, distributed, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
@@ -229,33 +228,6 @@ def test_long_reads(ctx, store, how):
 
 
 # ---- 7. the tables that walk the records, under the rule ---------------------------------------------------------------------------------------------
-def walked(rd, y, primers=(), q=0, f=dy.NONE):
-    """the existing yardsticks' tallies fed the tokens y keeps -> (fwd, rev int32 [n_pos, 7], {"n", "qual", "mapq", "dist": int64 [n_pos, 7]})"""
-    n_pos = len(y["counts"])
-    fwd, rev = np.zeros((n_pos, 7), np.int32), np.zeros((n_pos, 7), np.int32)
-    ev = {k: np.zeros((n_pos, 7), np.int64) for k in ("qual", "mapq", "dist", "n")}
-    for i in range(int(rd["n_reads"])):
-        if not my.kept(rd, i, f):
-            continue
-        toks, _ = my.tokens(rd, i, y["clip"][i], primers, q)
-        side = rev if int(rd["flag"][i]) & 0x10 else fwd
-        per_col = {}
-        for c, t, _ in toks:
-            per_col.setdefault(c, []).append(t)
-        for c, t in per_col.items():
-            side[c] += np.array(orc.tally_tokens(t), np.int32)
-        keep = {c for c, _, _ in toks}
-        for c, planes, ql, mq, dist in ey.tokens(rd, i):
-            if c in keep:
-                for pl in planes:
-                    ev["qual"][c, pl] += ql
-                    ev["mapq"][c, pl] += mq
-                    ev["dist"][c, pl] += dist
-                    ev["n"][c, pl] += 1
-    assert np.array_equal(fwd + rev, y["counts"]) and np.array_equal(ev["n"], y["counts"])      # (the yardsticks add up to the matrix)
-    return fwd, rev, ev
-
-
 @pytest.mark.parametrize("mate", (False, True))
 @pytest.mark.parametrize("how", dvf.PACKERS)
 def test_strand_and_evidence_counts_under_the_rule(ctx, store, how, mate):
@@ -265,7 +237,7 @@ def test_strand_and_evidence_counts_under_the_rule(ctx, store, how, mate):
     y = yard(store, "cases", mode, mate)
     n_pos = len(y["counts"])
     cols = np.arange(n_pos)
-    fwd, rev, ev = once(store, ("walked", mode, mate), lambda: walked(rd, y, primers, q, f))
+    fwd, rev, ev = once(store, ("walked", mode, mate), lambda: rm.walked(rd, y, primers, q, f))
     with uploaded(ctx, path, mode, how, mate) as rs:
         matrix = ctx.step(rs, n_pos, 0, True)[3]
         sc = ctx.strand_counts(rs, cols)

@@ -17,8 +17,8 @@ from tests import mate_overlap_cases as mc
 from tests import mate_overlap_yardstick as my
 from tests import primer_yardstick as py
 from tests import repeat_bam as rb
+from tests import rules_marks as rm
 from tests import schemes as sch
-from oracle import tc_oracle as orc
 from trueconsense_amd import _ffi, distributed, engine
 from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
@@ -192,34 +192,6 @@ def test_past_one_trip_of_the_grid(ctx, store):
 
 
 # ---- the tables that walk the records, under the rule ------------------------------------------------------------------------------------------------
-def walked(rd, y, primers=(), q=0, f=my.NONE):
-    """the existing yardsticks' tallies fed the clipped tokens of y -> (fwd, rev int32 [n_pos, 7], {"n", "qual", "mapq", "dist": int64
-    [n_pos, 7]}): tc_oracle.tally_tokens per strand, evidence_yardstick.tokens' sums, on the columns the record keeps"""
-    n_pos = len(y["counts"])
-    fwd, rev = np.zeros((n_pos, 7), np.int32), np.zeros((n_pos, 7), np.int32)
-    ev = {k: np.zeros((n_pos, 7), np.int64) for k in ("qual", "mapq", "dist", "n")}
-    for i in range(int(rd["n_reads"])):
-        if not my.kept(rd, i, f):
-            continue
-        toks, _ = my.tokens(rd, i, y["clip"][i], primers, q)
-        side = rev if int(rd["flag"][i]) & 0x10 else fwd
-        per_col = {}
-        for c, t, _ in toks:
-            per_col.setdefault(c, []).append(t)
-        for c, t in per_col.items():
-            side[c] += np.array(orc.tally_tokens(t), np.int32)
-        keep = {c for c, _, _ in toks}
-        for c, planes, ql, mq, dist in ey.tokens(rd, i):
-            if c in keep:
-                for pl in planes:
-                    ev["qual"][c, pl] += ql
-                    ev["mapq"][c, pl] += mq
-                    ev["dist"][c, pl] += dist
-                    ev["n"][c, pl] += 1
-    assert np.array_equal(fwd + rev, y["counts"]) and np.array_equal(ev["n"], y["counts"])      # (the yardsticks add up to the clipped matrix)
-    return fwd, rev, ev
-
-
 @pytest.mark.parametrize("mode", ("floor", "primers_filter"))
 @pytest.mark.parametrize("how", dvf.PACKERS)
 def test_strand_and_evidence_counts_under_the_rule(ctx, store, how, mode):
@@ -228,7 +200,7 @@ def test_strand_and_evidence_counts_under_the_rule(ctx, store, how, mode):
     y = yard(store, "cases", mode)
     n_pos = len(y["counts"])
     cols = np.arange(n_pos)
-    fwd, rev, ev = once(store, ("walked", mode), lambda: walked(rd, y, primers, q, f))
+    fwd, rev, ev = once(store, ("walked", mode), lambda: rm.walked(rd, y, primers, q, f))
     with uploaded(ctx, path, mode, how) as rs:
         matrix = ctx.step(rs, n_pos, 0, True)[3]
         sc = ctx.strand_counts(rs, cols)
@@ -249,7 +221,7 @@ def test_cli_strand_and_evidence_writers_accept(tmp_path, monkeypatch):
     ref, orfs, specs = cli_case()
     rd = mc.arrays(specs)
     y = my.counts(rd, mc.FUZZ_L)
-    fwd, rev, ev = walked(rd, y)
+    fwd, rev, ev = rm.walked(rd, y)
     bamwriter.write_bam("A.bam", rd, refs=mc.FUZZ_REFS, block=4096)
     common = cr.setup_cli(ref, orfs)
     cr.run_cli(monkeypatch, ["-i", "A.bam", "-name", "S"] + common + ["-o", "s.fa", "--mate-overlap", "--variant-table", "s.var", "--variant-strand",
