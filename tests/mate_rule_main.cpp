@@ -1,12 +1,14 @@
 // mate_rule_main.cpp — csrc/mate_rule.h as a program of its own (tests/test_mate_rule.py builds it plain and under AddressSanitizer +
 // UBSan): the rule of --mate-overlap on records given as text, without a GPU.
 //   mate_rule_main IN OUT
+//   mate_rule_main --names      tcmi_mate_same_name on every name length 1 .. 12 x every byte position, prints "names ok <compares>"
 // IN:  one line per kept record: flag tid pos next_tid next_pos p q name-in-hex ("-" for an empty name)
 // OUT: one line per record: eligible hash(hex) members pair loses clip — members: the eligible records of its key (itself included),
 //      pair: its group is a pair, loses: it is the pair's loser, clip: its clip.  Then "ok <records>" on stdout.
 // The grouping here is a std::map over the key; whether two keys are equal, the pair test, the loser and the clip are the header's.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <string>
 #include <tuple>
@@ -22,8 +24,59 @@ struct Rec {
     unsigned long long hash;
 };
 
+// a name as it lies in a record: its bytes, then `junk` where the NUL, the CIGAR and SEQ follow — a dword load at the name's last
+// whole-dword boundary ends inside them
+static std::vector<uint8_t> lying(const std::vector<uint8_t> &name, uint8_t junk)
+{
+    std::vector<uint8_t> v = name;
+    for (int k = 0; k < 4; ++k) v.push_back((uint8_t)(junk + 17 * k));
+    return v;
+}
+static bool same_name(const std::vector<uint8_t> &a, uint8_t junk_a, const std::vector<uint8_t> &b, uint8_t junk_b)
+{
+    const std::vector<uint8_t> la = lying(a, junk_a), lb = lying(b, junk_b);
+    auto word = [](const std::vector<uint8_t> &v) { return [&v](uint32_t k) { uint32_t w; std::memcpy(&w, v.data() + k, 4); return w; }; };   // (little-endian hosts)
+    return tcmi_mate_same_name((uint32_t)a.size(), (uint32_t)b.size(), word(la), word(lb));
+}
+// every length 1 .. 12, every byte position, three ways to differ there; equal names over different bytes behind them; a name and the
+// same name one byte longer or shorter.  -> compares made, -1: a wrong answer (said on stderr)
+static long check_names()
+{
+    long n_cmp = 0;
+    for (size_t n = 1; n <= 12; ++n) {
+        std::vector<uint8_t> a(n);
+        for (size_t k = 0; k < n; ++k) a[k] = (uint8_t)(33 + (7 * k + 3 * n) % 94);
+        for (uint8_t junk_b : {(uint8_t)0x00, (uint8_t)0x5A, (uint8_t)0xFF}) {
+            ++n_cmp;
+            if (!same_name(a, 0x5A, a, junk_b)) { std::fprintf(stderr, "equal names of %zu bytes compare different\n", n); return -1; }
+            for (size_t p = 0; p < n; ++p)
+                for (uint8_t flip : {(uint8_t)0x01, (uint8_t)0x80, (uint8_t)0xFF}) {
+                    std::vector<uint8_t> b = a;
+                    b[p] ^= flip;
+                    n_cmp += 2;
+                    if (same_name(a, 0x5A, b, junk_b) || same_name(b, junk_b, a, 0x5A)) {
+                        std::fprintf(stderr, "names of %zu bytes that differ in byte %zu (^ %02x) compare equal\n", n, p, flip);
+                        return -1;
+                    }
+                }
+            // (the longer name continues with the very byte that lies behind the shorter one)
+            std::vector<uint8_t> longer = a;
+            longer.push_back(junk_b);
+            n_cmp += 2;
+            if (same_name(a, junk_b, longer, 0x5A) || same_name(longer, 0x5A, a, junk_b)) { std::fprintf(stderr, "names of %zu and %zu bytes compare equal\n", n, n + 1); return -1; }
+        }
+    }
+    return n_cmp;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc == 2 && std::string(argv[1]) == "--names") {
+        const long n_cmp = check_names();
+        if (n_cmp < 0) return 1;
+        std::printf("names ok %ld\n", n_cmp);
+        return 0;
+    }
     if (argc != 3) { std::fprintf(stderr, "usage: mate_rule_main IN OUT\n"); return 2; }
     FILE *in = std::fopen(argv[1], "r");
     if (!in) { std::fprintf(stderr, "cannot read %s\n", argv[1]); return 2; }

@@ -68,17 +68,11 @@ __device__ inline uint64_t hash_of(const Mate &m)
     return tcmi_mate_hash_finish(h, m.f);
 }
 
+// (the compare itself: mate_rule.h, which tests/mate_rule_main.cpp runs over every length and every differing byte)
 __device__ inline bool same_name(const Mate &a, const Mate &b)
 {
-    if (a.n_name != b.n_name) return false;
-    uint32_t k = 0;
-    for (; k + 4 <= a.n_name; k += 4)
-        if (ld_u32(a.name + k) != ld_u32(b.name + k)) return false;
-    if (k < a.n_name) {
-        const uint32_t mask = (1u << (8 * (a.n_name - k))) - 1u;
-        if ((ld_u32(a.name + k) ^ ld_u32(b.name + k)) & mask) return false;
-    }
-    return true;
+    const uint8_t *na = a.name, *nb = b.name;
+    return tcmi_mate_same_name(a.n_name, b.n_name, [na](uint32_t k) { return ld_u32(na + k); }, [nb](uint32_t k) { return ld_u32(nb + k); });
 }
 
 __global__ __launch_bounds__(BLOCK) void mate_build_kernel(MjArgs a, uint32_t slot_mask)

@@ -63,6 +63,21 @@ TCMI_MATE_HD inline bool tcmi_mate_same_ints(const tcmi_mate_fields &a, const tc
     return a.tid == b.tid && tcmi_mate_lo(a) == tcmi_mate_lo(b) && tcmi_mate_hi(a) == tcmi_mate_hi(b);
 }
 
+// the names of two keys, as the kernels read them: whole dwords — get_a(k), get_b(k): the little-endian word at byte k of either name;
+// what its bytes behind the name hold plays no part —, then the tail of one to three bytes under a mask
+template <class GetA, class GetB> TCMI_MATE_HD inline bool tcmi_mate_same_name(uint32_t n_a, uint32_t n_b, GetA get_a, GetB get_b)
+{
+    if (n_a != n_b) return false;
+    uint32_t k = 0;
+    for (; k + 4 <= n_a; k += 4)
+        if (get_a(k) != get_b(k)) return false;
+    if (k < n_a) {
+        const uint32_t mask = (1u << (8 * (n_a - k))) - 1u;
+        if ((get_a(k) ^ get_b(k)) & mask) return false;
+    }
+    return true;
+}
+
 // a group of exactly the two eligible records a, b: a pair?
 TCMI_MATE_HD inline bool tcmi_mate_pair(const tcmi_mate_fields &a, const tcmi_mate_fields &b)
 {
