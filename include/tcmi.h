@@ -766,7 +766,11 @@ int tcmi_reads_extent(const tcmi_reads *reads, int64_t ref_len, int64_t *out_L);
 
 /* Reads -> HBM in the tally kernel's layout.  By default the BAM-native arrays are copied to the device as they are
  * and packed there by HIP kernels (CIGAR projection, token classification, coverage runs, 4-bit -> bit planes);
- * inputs the device packer does not take (see option "device_pack") are packed on the host.                        */
+ * inputs the device packer does not take (see option "device_pack") are packed on the host.
+ * A read that would be kept (FLAG 0x4 clear, pos >= 0, on a reference that piles up, a reference span > 0) and whose CIGAR consumes
+ * 2^29 or more query bases (Yq: the lengths of its M, I, S, = and X ops) is no alignment: TCMI_E_FORMAT, with the read's index and
+ * its Yq — on either packer, as the file routes refuse such a record.  Below that Yq may differ from l_qseq: a query index at or
+ * beyond l_qseq reads as N, bases behind Yq are ignored.                                                                         */
 int tcmi_readset_upload(tcmi_ctx *ctx, const tcmi_reads *reads, tcmi_readset **out);
 /* Several BAMs in ONE read set (BASELINE configs[3], many independent BAMs): BAM b's positions are
  * shifted by b * stride (a multiple of 256, >= the extent of every BAM), so one tally launch and one

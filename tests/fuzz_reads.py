@@ -1,6 +1,8 @@
 """Random reads with arbitrary CIGARs (every op of SAM spec §4.2: M I D N S H P = X), odd SEQ
 content (N, IUPAC codes, '=', SEQ '*'), flags and placements — for differential tests between
-the column-major Python emulator, the read-major C oracle and the HIP kernels."""
+the column-major Python emulator, the read-major C oracle and the HIP kernels.  random_cigar's CIGARs are structured ([H][S] core
+[S][H], every op at least one base long, op codes 0-8); the shapes a BAM file may hold and no aligner writes — ops in any order, ops of
+length 0, the reserved op codes, query totals far from len(SEQ) — are tests/odd_cigars.py's."""
 import numpy as np
 
 from tests import synth_small as ss

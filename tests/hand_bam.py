@@ -9,7 +9,7 @@ from trueconsense_amd import synthetic as sy
 from trueconsense_amd.io import bamwriter
 
 NT16 = "=ACMGRSVTWYHKDBN"
-OPS = "MIDNSHP=X"
+OPS = "MIDNSHP=XBabcdef"                           # (9-15: reserved op codes, tests/synth_small.py's letters)
 
 
 def rec(tid, pos, name, flag, cigar, seq, qual, aux=b"", mapq=37, mtid=-1, mpos=-1, tlen=0):

@@ -10,8 +10,8 @@ import re
 import numpy as np
 
 NT16 = "=ACMGRSVTWYHKDBN"
-_CIG_RE = re.compile(r"(\d+)([MIDNSHP=X])")
-_OPS = "MIDNSHP=X"
+_CIG_RE = re.compile(r"(\d+)([MIDNSHP=XBabcdef])")
+_OPS = "MIDNSHP=XBabcdef"                          # op codes 0-8 as SAM writes them; 9 'B' (htslib's letter) and 10-15 'a'-'f': reserved codes
 STOPS = ("TAG", "TAA", "TGA")
 
 

@@ -3,6 +3,7 @@
 #pragma once
 #include <cstdint>
 
+#include "cigar_rule.h"
 #include "indel_rule.h"
 
 namespace tcmi_cigar {

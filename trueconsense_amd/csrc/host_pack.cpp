@@ -81,6 +81,14 @@ void classify_slice(const SelectJob &J, Slice &P, int32_t bi, int t)
         const uint32_t *cg = r->cigar + r->cigar_off[i];
         const int64_t nc = (int64_t)(r->cigar_off[i + 1] - r->cigar_off[i]);
         if (nc > 65535) return fail(P, TCMI_E_UNSUPPORTED, "read %lld has %lld CIGAR ops (> 65535)%.0lld", i, nc, 0);
+        // The CIGAR rule (cigar_rule.h), where the device packer's classify_view raises PKF_BADREAD: a read that would be kept with a
+        // query total of 2^29 or more is no alignment — the walks that follow index SEQ and QUAL by that total.
+        {
+            const tcmi_cigar_sums sums = tcmi_cigar_walk([cg](uint32_t k) { return cg[k]; }, (uint32_t)nc);
+            if (tcmi_cigar_malformed(sums))
+                return fail(P, TCMI_E_FORMAT, "read %lld is malformed: its CIGAR consumes %lld query bases (2^29 or more; the reference span is %lld)",
+                            i, sums.yq, sums.span);
+        }
         const int64_t lq = r->l_qseq[i];
         if (lq < 0) return fail(P, TCMI_E_ARG, "read %lld has negative l_qseq%.0lld%.0lld", i, 0, 0);
         const int64_t nbytes = (int64_t)(r->seq_off[i + 1] - r->seq_off[i]);

@@ -4,6 +4,7 @@
 // strand_counts.hip, link_counts.hip; their host side and their frame: stream_count.h) — and the wave join, which the packer uses too.
 // What only the packers use stays in pack_device.hip.
 #pragma once
+#include "cigar_rule.h"
 #include "tcmi_internal.h"
 
 namespace {
@@ -181,7 +182,8 @@ __device__ inline int64_t ref_span(const ReadView &v)
 
 // Record i of a stream source: true exactly when the device packer keeps it, with its first and last column [p, q] on the one axis.
 // THE kept-record rule outside the packer: mapped, through the read filter the set was built under, consistent, on a reference that
-// piles up, with a reference span.  The packer's own copy is pack_device.hip's classify_view (one walk that also decides `simple`, at
+// piles up, with a reference span and a query total below 2^29 (cigar_rule.h; the packer refuses the file over a record beyond that, so
+// this copy only keeps a kernel that is asked all the same away from it).  The packer's own copy is pack_device.hip's classify_view (one walk that also decides `simple`, at
 // pk_index's register ceiling): a rule changed here is changed there, and the other way round.
 __device__ inline bool kept_span(const PackSrc &s, int64_t i, ReadView &v, int64_t &p, int64_t &q)
 {
@@ -189,8 +191,12 @@ __device__ inline bool kept_span(const PackSrc &s, int64_t i, ReadView &v, int64
     if ((v.flag & 0x4u) || !passes(s.flt, v) || v.bad || v.pos < 0) return false;
     const int32_t shift = shift_of(s, v.tid);
     if (shift < 0) return false;
-    const int64_t span = ref_span(v);
-    if (span <= 0) return false;
+    int64_t span = 0;
+    int32_t yr = TCMI_CIGAR_YR0;    // min(Yq - 2^29, 0)
+    for (uint32_t k = 0; k < v.n_cigar; ++k) {
+        tcmi_cigar_step(span, yr, ld_u32(v.cigar + 4 * (size_t)k));
+    }
+    if (span <= 0 || tcmi_cigar_malformed(span, yr)) return false;
     p = (int64_t)v.pos + shift;
     q = p + span - 1;
     return true;

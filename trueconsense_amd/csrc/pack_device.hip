@@ -157,7 +157,10 @@ __device__ inline void ref_extent_max(int32_t *ext, int32_t t, int32_t e)
 // `shift`: where the read's reference starts on the axis (< 0: not piled up), `slot_end`: where its slot ends, `layout`: a contig
 // layout is set (reads on other references are not an error then).  The read filter: the callers hand a failing record in with FLAG
 // 0x4 set (filter_view) — it is ignored in the three places below, and in pk_classify's `dropped`, exactly as an unmapped record is
-// The kernels that count in the stream afterwards ask pack_device.h's kept_span which records are kept here: the two hold the same rule
+// The kernels that count in the stream afterwards ask pack_device.h's kept_span which records are kept here: the two hold the same rule,
+// the CIGAR rule included (cigar_rule.h: a record that would be kept with a query total Yq >= 2^29 is malformed) — it raises PKF_BADREAD
+// and is NOT kept, neither packed nor a long read: on the one-sync path pk_place, pk_pack and the tally are queued behind pk_index
+// before the host reads the flags, and they must find nothing of such a record to walk (their query index has 32 bits).
 __device__ inline Classified classify_view(const ReadView &v, int32_t mode, int32_t shift, int32_t slot_end, bool layout, const uint8_t *rec,
                                            bool stream_long_ok, PackTotals *tot)
 {
@@ -167,13 +170,14 @@ __device__ inline Classified classify_view(const ReadView &v, int32_t mode, int3
     if (v.broken || (v.bad && !(v.flag & 0x4u) && shift >= 0 && v.pos >= 0)) atomicOr(&tot->flags, (uint32_t)PKF_BADREAD);
     if (!layout && !(v.flag & 0x4u) && v.tid > 0) atomicOr(&tot->flags, (uint32_t)PKF_MULTIREF);   // (the host packer words the error)
     if (!kept) return c;
-    // one walk over the CIGAR: reference span, and is it [H]*[S]* (M|=|X)+ [S]*[H]* ?
+    // one walk over the CIGAR: reference span and query total (cigar_rule.h), and is it [H]*[S]* (M|=|X)+ [S]*[H]* ?
     int64_t span = 0, m = 0, y0 = 0;
+    int32_t yr = TCMI_CIGAR_YR0;    // min(Yq - 2^29, 0)
     int ph = 0;                     // 0 start / leading H, 1 leading S, 2 match run, 3 trailing S, 4 trailing H
     bool simple = true;
     for (uint32_t k = 0; k < v.n_cigar; ++k) {
         const uint32_t cw = ld_u32(v.cigar + 4 * (size_t)k), op = cw & 0xFu, len = cw >> 4;
-        if (consumes_ref(op)) span += len;
+        tcmi_cigar_step(span, yr, cw);
         if (op == 5) { if (ph >= 2) ph = 4; else if (ph == 1) simple = false; }
         else if (op == 4) { if (ph <= 1) { ph = 1; y0 += len; } else if (ph <= 3) ph = 3; else simple = false; }
         else if (is_match(op)) { if (ph <= 2) { ph = 2; m += len; } else simple = false; }
@@ -188,6 +192,7 @@ __device__ inline Classified classify_view(const ReadView &v, int32_t mode, int3
         }
     }
     if (span <= 0) return c;
+    if (tcmi_cigar_malformed(span, yr)) { atomicOr(&tot->flags, (uint32_t)PKF_BADREAD); return c; }
     const int64_t end = (int64_t)v.pos + pos_shift + span;
     const int64_t len = simple ? m : span;
     if (end >= (int64_t)TCMI_F_EVPOS) { atomicOr(&tot->flags, (uint32_t)PKF_FARPOS); return c; }
